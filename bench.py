@@ -9,10 +9,12 @@ i.e. the reference's Trainer.train_step/backward/optimizer.step sequence (nerf/u
 state (mean_count > 0, no host sync inside the step).  Synthetic rays / occupancy / weights:
 no dataset or checkpoint exists offline.  value = all ranks' rays / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (see README / DESIGN.md "Measurement").  Exactly K steps are timed, in one window between
+barriers; `ms_per_step` = that window / K.  --dump-outputs DIR: rank 0 writes what the last timed step returned, and the
+parameters it left, as DIR/<name>.npy (dump_outputs); every input is seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -38,8 +40,8 @@ HEAD_BWD_FLOP = 2 * HEAD_FWD_FLOP                                               
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=200)
-    p.add_argument("--warmup", type=int, default=40)
+    p.add_argument("--steps", type=int, default=None, help="timed steps (default: 200; 20 frames for --workload frame1080)")
+    p.add_argument("--warmup", type=int, default=None, help="untimed steps asked for (default: 40; 3 for --workload frame1080)")
     p.add_argument("--rays", type=int, default=4096)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-frame", action="store_true", help="skip the 800x800 inference-frame timing (extra field eval_frame)")
@@ -67,7 +69,53 @@ def parse():
     p.add_argument("--torch-loss", action="store_true", help="A/B: torch mse_loss + scale() instead of laenerf_amd.losses.mse_loss_scaled")
     p.add_argument("--torch-optimizer", action="store_true",
                    help="A/B: torch.optim.Adam(fused) + torch.amp.GradScaler instead of laenerf_amd.optim.FusedAdam")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most "
+                        "64 MB: see dump_outputs)")
+    args = p.parse_args()
+    frame = args.workload == "frame1080"                  # whole frames: the train defaults would take minutes
+    args.steps = (20 if frame else 200) if args.steps is None else args.steps
+    args.warmup = (3 if frame else 40) if args.warmup is None else args.warmup
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "flower":
+        p.error("--dump-outputs: --workload flower only profiles the flower_step object; use train or frame1080")
+    return args
+
+
+DUMP_MAX_ROWS = 1 << 20          # --dump-outputs: a longer array is written as a fixed sample of this many rows
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, res, net=None):
+    """--dump-outputs: the tensors and numbers of a step's result dict `res` and the parameters of `net` after that step, one
+    DIR/<name>.npy each (float64 tensors and numbers as float64, everything else float32; depth: below).  An array of more than DUMP_MAX_ROWS
+    rows (the hash-grid table, the rays of a 1080p frame) is written as the rows of a seeded sample drawn from its row count
+    alone, so runs of the same command write the same rows.  More than DUMP_MAX_BYTES in all is refused before anything is written."""
+    arrays = {k: v for k, v in res.items() if torch.is_tensor(v) or isinstance(v, (int, float))}
+    if net is not None:
+        arrays.update(net.named_parameters())
+    out = {}
+    for name, v in arrays.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            a = (v.double() if v.dtype == torch.float64 else v.float()).cpu().numpy()
+        else:
+            a = np.array(v, dtype=np.float64)
+        if a.ndim and a.shape[0] > DUMP_MAX_ROWS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_ROWS, replace=False))]
+        out[name] = a
+    if "depth" in out and "nears" in out:
+        # a ray that misses the scene box has nears = fars = FLT_MAX (raymarching.hip) and no depth: the step returns
+        # (z - near) / (far - near) = 0/0 = NaN there, as the reference's formula does.  The dump writes 0 for those rays (nears.npy
+        # marks them), so that every written value is finite and two builds compare value for value; a NaN elsewhere stays.
+        out["depth"] = np.where(out["nears"] == np.finfo(np.float32).max, np.float32(0), out["depth"])
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def host_threads():
@@ -297,7 +345,7 @@ def sharded_frame1080(world, rank, dev, backend_name, steps, warmup, with_n1=Fal
     [n/W, 5] fp32 block per frame (north_star / SURVEY 8e; the reference's dormant `dist.all_gather(preds)`, nerf/utils.py:1555-1570).
     Every rank holds the same (random-init, synthetic-occupancy) model; a step = a frame.  Collective: every rank calls it;
     returns the same dict on every rank.  with_n1: rank 0 also renders the whole frame alone (W = 1, the reference's schedule)
-    while the others wait, for `speedup_vs_n1`."""
+    while the others wait, for `speedup_vs_n1`.  -> (that dict, the last timed frame's result: image / depth / weights_sum)"""
     import hashlib
     import torch.distributed as dist
     from laenerf_amd import synthetic as S
@@ -376,14 +424,16 @@ def sharded_frame1080(world, rank, dev, backend_name, steps, warmup, with_n1=Fal
         out["best_n1_ms_per_frame"] = round(best, 3)             # the fastest one-GPU schedule: what strong scaling is quoted against
         out["speedup_vs_n1"] = round(best / ms, 3)
         out["speedup_vs_n1_reference_schedule"] = round(n1_ms / ms, 3)
-    return out
+    return out, res
 
 
 def frame_workload(args, world, rank, dev, backend_name):
     """`--workload frame1080`: the sharded frame as the bench's own `value` (strong scaling: the frame is fixed)"""
     import torch.distributed as dist
-    f = sharded_frame1080(world, rank, dev, backend_name, args.steps, args.warmup)
+    f, last = sharded_frame1080(world, rank, dev, backend_name, args.steps, args.warmup)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
         print(json.dumps({
             "frame_sha256_per_rank": f["frame_sha256_per_rank"], "ranks_hold_the_same_frame": f["ranks_hold_the_same_frame"],
             "gather_bytes_per_rank": f["gather_bytes_per_rank"],
@@ -1212,8 +1262,6 @@ def main():
         print(json.dumps({"flower_step": flower_step(dev)}), flush=True)
         return
     if args.workload == "frame1080":
-        if args.steps == 200 and args.warmup == 40:            # the train defaults are too long for whole frames
-            args.steps, args.warmup = 20, 3
         return frame_workload(args, world, rank, dev, backend_name)
 
     torch.manual_seed(1234 + rank)
@@ -1243,6 +1291,9 @@ def main():
         o, d = S.lego_like_rays(args.rays, seed=1000 * rank + b, n_views=1)
         batches.append((torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev),
                         torch.rand(args.rays, 3, device=dev)))
+    # the result dict of every batch's latest step stays referenced: inside a captured graph its tensors then keep memory of
+    # their own (a later capture in the same pool would otherwise reuse it) and hold what the replay computed (--dump-outputs)
+    results = [None] * n_batches
     net.train()
 
     def step_body(o, d, gt):
@@ -1260,7 +1311,7 @@ def main():
                 scaler.update()
             else:
                 opt.step()
-        return res["n_samples"]
+        return res
 
     def dp_tail():                                          # --dp: outside the captured graph (a collective + 3 launches)
         if world > 1:
@@ -1277,10 +1328,10 @@ def main():
     def step(i):
         o, d, gt = batches[i % n_batches]
         zero_grad()
-        n = step_body(o, d, gt)
+        res = results[i % n_batches] = step_body(o, d, gt)
         if args.dp:
             dp_tail()
-        return n
+        return res["n_samples"]
 
     # warm-up: the first 16 steps run in the reference's "mean_count <= 0" mode (sized by a D2H read), then the
     # running mean is refreshed every 16 steps exactly like update_extra_state does (renderer.py:644-647)
@@ -1316,7 +1367,8 @@ def main():
             zero_grad()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None):
-                n_graph_samples.append(step_body(*batches[b]))
+                results[b] = step_body(*batches[b])
+                n_graph_samples.append(results[b]["n_samples"])
             graphs.append(g)
         graph = graphs[0]
 
@@ -1361,6 +1413,7 @@ def main():
                                 loss = scaler.scale(torch.nn.functional.mse_loss(res["image"], batches[b][2]))
                         scaler.backward(loss) if fused_loss else loss.backward()
                         opt.step()
+                        results[b] = res
                         n_graph_samples.append(res["n_samples"])
                 g_main.append(g)
             graph = g_main[0]
@@ -1432,6 +1485,7 @@ def main():
                         res = r.shade_train(marched[b], bg_color=1)
                         loss = scaler.scale(torch.nn.functional.mse_loss(res["image"], batches[b][2]))
                 n_graph_samples.append(res["n_samples"])
+            results[b] = res
             g_fwd.append(g); losses.append(loss)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=g_fwd[0].pool()):
@@ -1482,16 +1536,8 @@ def main():
         samples.append(step(n_warm + i))
     sync_all()
     dt = time.perf_counter() - t0
-    # four more windows of the same K steps right after the first (a 7 ms window drifts by a few % on a box); every window is
-    # exactly K steps between barriers, `value` is their median
-    windows = [dt]
-    for wdw in range(1, 5):
-        sync_all()
-        tw = time.perf_counter()
-        for i in range(args.steps):
-            step(n_warm + wdw * args.steps + i)
-        sync_all()
-        windows.append(time.perf_counter() - tw)
+    if args.dump_outputs and rank == 0:                     # before the eager diagnostics below train the model further
+        dump_outputs(args.dump_outputs, results[(n_warm + args.steps - 1) % n_batches], net)
     timing_grid = backend.collect_kernel_timing() if not graph else {}
     backend.enable_kernel_timing(False)
     # diagnostic (outside the timed region): per-operator device time of 20 eager steps (HIP events around each
@@ -1533,14 +1579,12 @@ def main():
     # rank 0 alone for the speed-up.  Collective: every rank takes part, rank 0 reports.
     sharded = None
     if world > 1 and not args.no_frame:
-        sharded = sharded_frame1080(world, rank, dev, backend_name, steps=10, warmup=2, with_n1=True)
+        sharded, _ = sharded_frame1080(world, rank, dev, backend_name, steps=10, warmup=2, with_n1=True)
 
-    if world > 1:                                           # every window: max over ranks (all ranks call the collective)
-        wmax = torch.tensor(windows, device=dev if backend_name == "nccl" else "cpu", dtype=torch.float64)
+    if world > 1:                                           # max over ranks (all ranks call the collective)
+        wmax = torch.tensor([dt], device=dev if backend_name == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(wmax, op=dist.ReduceOp.MAX)
-        windows = [float(x) for x in wmax.tolist()]
-    first_window = windows[0]
-    dt = sorted(windows)[len(windows) // 2]                 # `value` = the MEDIAN of the five K-step windows
+        dt = float(wmax.item())
     if rank == 0:
         ms = dt / args.steps * 1e3
         gf = timing_grid.get("grid_encode_forward", {"ms": float("nan"), "units": 0, "calls": 0})
@@ -1590,11 +1634,9 @@ def main():
                                     "levels run at the L2 request rate, coarse levels at vector-memory issue (DESIGN.md 4)",
                          "timed": "HIP events on the launch stream around the call in 20 eager steps after the timed region"},
             "roofline_more": roofline_more(timing_split, dev, with_frame=not args.no_frame) if timing_split else None,
-            "windows": {"ms_per_step": [round(wd / args.steps * 1e3, 4) for wd in windows],
-                        "min": round(min(windows) / args.steps * 1e3, 4), "median": round(sorted(windows)[len(windows) // 2] / args.steps * 1e3, 4),
-                        "max": round(max(windows) / args.steps * 1e3, 4), "first": round(first_window / args.steps * 1e3, 4),
-                        "note": "5 consecutive windows of exactly K steps, each between barriers + synchronize, max over ranks; "
-                                "`value` / `ms_per_step` are the MEDIAN window"},
+            "windows": {"ms_per_step": [round(ms, 4)], "min": round(ms, 4), "median": round(ms, 4), "max": round(ms, 4), "first": round(ms, 4),
+                        "note": "ONE window: exactly K = --steps timed steps between barriers + synchronize, max over ranks; "
+                                "`value` / `ms_per_step` come from it"},
             "side_stream": side_probe if not args.no_graph else None,        # concurrent_side_stream(): does the side stream run beside the main one?
             "operator_ms_per_step": {k: round(v["ms"] / n_diag, 4) for k, v in sorted(timing_all.items())},
         }

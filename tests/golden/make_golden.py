@@ -467,6 +467,15 @@ def gen_density_grid():
     save("density_grid", **out)
 
 
+def gen_exp_f16():
+    """torch.exp (trunc_exp's forward, activation.py:9) of every fp16 bit pattern, in fp32, on THIS host.  torch's CPU exp runs
+    on MKL's vector math, whose code path (and last ulp: 76 of the 4096 full-sweep sigmas) depends on the CPU's vendor and ISA,
+    and the sigmas of density_grid.npz carry this host's; a test that repeats that exp on an fp16 MLP output looks it up here,
+    so it passes on any host.  Run on the host that ran gen_density_grid (an Intel AVX-512 CPU)."""
+    h = np.arange(1 << 16, dtype=np.uint16).view(np.float16).astype(np.float32)
+    save("exp_f16", exp=torch.exp(torch.from_numpy(h)).numpy())
+
+
 # ---------------------------------------------------------------- F. operator-level vectors under the reference's wrappers
 def gen_ops():
     """small vectors produced THROUGH the reference's Python wrappers (shape/padding/alignment rules of
@@ -584,4 +593,5 @@ if __name__ == "__main__":
     gen_e2e("b2", 2)
     gen_run_upsample()
     gen_density_grid()
+    gen_exp_f16()
     gen_freq()

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -12,9 +13,10 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_prints_one_contract_line():
+def test_bench_prints_one_contract_line(tmp_path):
+    dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "3", "--cpu-rays", "4096",
-                          "--no-frame", "--no-style"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--no-frame", "--no-style", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -57,4 +59,13 @@ def test_bench_prints_one_contract_line():
     for k in ("with_one_edit", "with_two_edits"):                    # the optional edits of INTEGRATION 3b, in the order they pay
         assert "error" not in d[k] and 0 < d[k]["device_ms_per_step"] < d["device_ms_per_step"], (k, d[k])
     assert d["with_two_edits"]["device_ms_per_step"] < d["with_one_edit"]["device_ms_per_step"]
-
+    # --dump-outputs: what the last timed step returned and the parameters it left, float32 / float64, <= 64 MB in all
+    a = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert {"image", "depth", "weights_sum", "loss", "n_samples", "encoder.embeddings", "sigma_net.weights", "color_net.weights"} <= set(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert all(np.isfinite(v).all() for v in a.values())
+    missed = a["nears"] == np.finfo(np.float32).max                   # rays missing the box: the step's depth is 0/0, the dump's 0
+    assert np.all(a["depth"][missed] == 0)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["image"].shape == (4096, 3) and a["weights_sum"].shape == (4096,) and a["n_samples"] > 0
+    assert a["encoder.embeddings"].shape == (1 << 20, 2)

@@ -182,7 +182,7 @@ def test_default_workload_two_ranks_carries_the_sharded_frame_object():
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["world_size"] == 2 and j["backend"] == "gloo"
     assert j["scaling"] == "weak" and j["unit"] == "Mrays/s" and j["value"] > 0
-    assert j["windows"]["median"] == j["ms_per_step"]               # `value` is the median window
+    assert j["windows"]["median"] == j["ms_per_step"]               # `value` is the one timed window
     f = j["frame1080"]
     assert f["n_gpus"] == 2 and f["world_size"] == 2 and f["backend"] == "gloo"
     assert f["ranks_hold_the_same_frame"] is True and len(f["frame_sha256_per_rank"]) == 2

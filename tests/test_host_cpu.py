@@ -169,3 +169,34 @@ def test_bench_imports_touch_no_gpu():
     import torch
     if not torch.cuda.is_available():
         assert "raised" in out.stdout and "no error" not in out.stdout
+
+
+def test_bench_dump_outputs_writes_the_step_as_float_arrays_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: every tensor and number of the step's result dict and every parameter of the model as
+    <name>.npy, float64 kept, everything else float32; depth 0 for rays that miss the box; an array of more than DUMP_MAX_ROWS rows as whole rows of a seeded
+    sample that is the same on every call; more than 64 MB in all refused before anything is written."""
+    import bench
+    net = torch.nn.Module()
+    n_rows = bench.DUMP_MAX_ROWS + 5
+    net.table = torch.nn.Parameter(torch.arange(2 * n_rows, dtype=torch.float32).reshape(n_rows, 2))
+    net.w = torch.nn.Parameter(torch.full((7,), 0.5, dtype=torch.float16))
+    big = torch.finfo(torch.float32).max                                # nears of a ray that misses the scene box
+    res = {"image": torch.rand(10, 3).half(), "loss": torch.tensor(2.5, dtype=torch.float64), "n_samples": 123, "tag": "not an array",
+           "nears": torch.tensor([0.5, big, 0.7]), "depth": torch.tensor([0.25, float("nan"), float("nan")])}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res, net)
+    assert sorted(os.listdir(tmp_path / "a")) == ["depth.npy", "image.npy", "loss.npy", "n_samples.npy", "nears.npy", "table.npy", "w.npy"]
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert a["image"].dtype == np.float32 and np.array_equal(a["image"], res["image"].float().numpy())
+    assert a["loss"].dtype == np.float64 and a["loss"] == 2.5 and a["n_samples"].dtype == np.float64 and a["n_samples"] == 123
+    assert a["w"].dtype == np.float32 and np.all(a["w"] == 0.5)
+    # the missed ray's 0/0 depth is written as 0; a NaN on a ray that hit the box is written as it is
+    assert a["depth"][0] == 0.25 and a["depth"][1] == 0 and np.isnan(a["depth"][2]) and a["nears"][1] == np.finfo(np.float32).max
+    t = a["table"]
+    rows = t[:, 0].astype(np.int64) // 2
+    assert t.shape == (bench.DUMP_MAX_ROWS, 2) and np.array_equal(t[:, 1], t[:, 0] + 1)          # whole rows
+    assert np.all(np.diff(rows) > 0) and rows[-1] < n_rows
+    assert np.array_equal(t, np.load(tmp_path / "b" / "table.npy"))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), {"x": torch.zeros(bench.DUMP_MAX_ROWS, 17)})         # 68 MiB
+    assert not (tmp_path / "c").exists()

@@ -131,8 +131,9 @@ def _oracle_sigma(O, g, xyz):
     pad = 128 - n % 128                                       # ffmlp.py:157-159
     enc_h = O.to_f16_bits(np.concatenate([enc, np.zeros((pad, 32), np.float32)]))
     h, _ = O.ffmlp_forward(enc_h, O.to_f16_bits(g["sigma_w"]), 32, 16, 64, 2)
-    import torch                                              # torch.exp, like trunc_exp (activation.py:9): same last-ulp rounding
-    return torch.exp(torch.from_numpy(O.from_f16_bits(h)[:n, 0].astype(np.float32))).numpy()
+    # trunc_exp (activation.py:9) is torch.exp, whose last ulp on the CPU depends on the CPU's vendor (MKL's vector math): it is
+    # looked up in torch.exp of every fp16 value as computed on the host that recorded these sigmas (make_golden.py::gen_exp_f16)
+    return golden("exp_f16")["exp"][h[:n, 0]]
 
 
 def test_density_grid_full_sweep_matches_reference_update_extra_state(O):
