@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi6"
+#define LAE_ABI_TAG "abi7"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -100,6 +100,35 @@ LAE_API int lae_near_far_from_aabb(const float* rays_o, const float* rays_d, con
 LAE_API int lae_get_rays(const float* poses, uint32_t B, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
                  const int64_t* inds, uint64_t inds_batch_stride, uint32_t N, int perturb, float off_x, float off_y,
                  float* rays_o, float* rays_d, const float* aabb, float min_near, float* nears, float* fars, void* stream);
+
+/* One training batch drawn from a device-resident image stack (the data loader of nerf/provider.py:294-343 + the
+ * pixel gather and background blend of Trainer.train_step, nerf/utils.py:560-580), in one pass.
+ * images [n_img, H, W, C], C in {3, 4}, dtype LAE_IMG_U8 (value / 255 through a 256-entry table), LAE_IMG_F16 or
+ * LAE_IMG_F32; poses [n_img, 4, 4] cam2world; one intrinsics (fx, fy, cx, cy) for all images.
+ * RNG: u(ray, word) = word 0 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ *   (step & 0xffffffff, ray, word, 0), where step = *step_counter (int64, device) read at the start of the call.
+ *   pixel  = (u(ray, 0) * (uint64)(H * W)) >> 32
+ *   image  = (u(r, 1) * (uint64)n_img) >> 32 with r = 0xffffffff in LAE_BATCH_IMAGE mode (one image per batch,
+ *            the reference's batch_size = 1 loader) and r = ray in LAE_BATCH_ALL mode (an image per ray)
+ *   bg_c   = (u(ray, 2 + c) >> 8) * 2^-24, c = 0, 1, 2 (LAE_BG_RANDOM only)
+ *   The reference shuffles the image order once per epoch; here the image is drawn i.i.d. per batch.
+ * Rays, nears and fars are bit-identical to lae_get_rays(poses + 16 * image, ..., inds = &pixel, aabb, min_near)
+ * (one shared device function).  gt = rgb (C == 3) or rgb * a + bg * (1 - a) (C == 4; three roundings, no contraction,
+ * bg = 1 under LAE_BG_WHITE), after sRGB -> linear of rgb when srgb_to_linear != 0.  bg_out [N,3] (LAE_BG_RANDOM
+ * only, may be NULL otherwise) receives the drawn background, inds [N] int64 = image * H * W + pixel.  A second
+ * launch adds 1 to *step_counter after every ray has read it: a replayed graph draws a new batch each time. */
+#define LAE_IMG_U8 0
+#define LAE_IMG_F16 1
+#define LAE_IMG_F32 2
+#define LAE_BATCH_IMAGE 0
+#define LAE_BATCH_ALL 1
+#define LAE_BG_WHITE 0
+#define LAE_BG_RANDOM 1
+LAE_API int lae_sample_train_batch(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                           const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
+                           const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int mode, int bg_mode,
+                           int srgb_to_linear, float* rays_o, float* rays_d, float* nears, float* fars, float* gt,
+                           float* bg_out, int64_t* inds, void* stream);
 
 /* raymarching.cu:201-209  sph_from_ray(rays_o, rays_d, radius, N, coords[N,2]) */
 LAE_API int lae_sph_from_ray(const float* rays_o, const float* rays_d, float radius, uint32_t N,
@@ -135,6 +164,18 @@ LAE_API int lae_march_rays_train(const float* rays_o, const float* rays_d, const
                          float* xyzs, float* dirs, float* deltas,
                          int32_t* rays, int32_t* counter, const float* noises,
                          void* scratch, uint32_t* rows_end_out, void* stream);
+
+/* lae_march_rays_train with the truncation threshold in device memory, so that one captured graph serves every
+ * threshold up to its buffer size: M_cap sample rows are written (xyzs / dirs / deltas hold M_cap rows), and rays are
+ * truncated where lae_march_rays_train with M = min(*m_limit, M_cap) truncates them.  rays, counter and rows_end equal
+ * that call's; rows [rows_end, M_cap) are zero-filled. */
+LAE_API int lae_march_rays_train_limit(const float* rays_o, const float* rays_d, const uint8_t* grid,
+                               float bound, float dt_gamma, uint32_t max_steps,
+                               uint32_t N, uint32_t C, uint32_t H, uint32_t M_cap, const uint32_t* m_limit,
+                               const float* nears, const float* fars,
+                               float* xyzs, float* dirs, float* deltas,
+                               int32_t* rays, int32_t* counter, const float* noises,
+                               void* scratch, uint32_t* rows_end_out, void* stream);
 
 /* raymarching.cu:580-588 */
 LAE_API int lae_composite_rays_train_forward(const float* sigmas, const float* rgbs, const float* deltas,

@@ -200,6 +200,21 @@ class _RayMarching:
                                        ptr(counter), ptr(noises), ptr(ws), ptr(rows_end), stream()), "march_rays_train")
 
     @staticmethod
+    def march_rays_train_limit(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M_cap, m_limit, nears, fars, xyzs, dirs,
+                               deltas, rays, counter, noises, rows_end=None):
+        """march_rays_train with M_cap sample rows and the truncation threshold read from m_limit (device int32[1])"""
+        need_cuda(rays_o, rays_d, grid, m_limit, nears, fars, xyzs, dirs, deltas, rays, counter, noises)
+        need_contig(rays_o, rays_d, grid, nears, fars, xyzs, dirs, deltas, rays, counter, noises)
+        _need_f32(rays_o, rays_d, nears, fars, xyzs, dirs, deltas, noises)
+        assert grid.dtype == torch.uint8 and rays.dtype == torch.int32 and counter.dtype == torch.int32 and m_limit.dtype == torch.int32
+        assert xyzs.shape[0] >= M_cap and dirs.shape[0] >= M_cap and deltas.shape[0] >= M_cap
+        lib = _lib.load()
+        ws = _workspace(rays_o.device, lib.lae_march_rays_train_scratch_bytes(N))
+        check(lib.lae_march_rays_train_limit(ptr(rays_o), ptr(rays_d), ptr(grid), bound, dt_gamma, max_steps, N, C, H, M_cap, ptr(m_limit),
+                                             ptr(nears), ptr(fars), ptr(xyzs), ptr(dirs), ptr(deltas), ptr(rays),
+                                             ptr(counter), ptr(noises), ptr(ws), ptr(rows_end), stream()), "march_rays_train_limit")
+
+    @staticmethod
     def composite_rays_train_forward(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image):
         need_cuda(sigmas, rgbs, deltas, rays, weights_sum, depth, image)
         need_contig(sigmas, rgbs, deltas, rays, weights_sum, depth, image)

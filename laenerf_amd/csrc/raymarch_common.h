@@ -207,6 +207,45 @@ __device__ __forceinline__ float candidate_t(const MarchCfg& cfg, float t_base, 
 
 // ---------------------------------------------------------------- K1
 // raymarching.cu:91-145
+// get_rays (nerf/utils.py:61-153) for one pixel of one cam2world pose P [4,4]: pixel centre = index + 0.5 (:82-83),
+// shared by lae_get_rays and lae_sample_train_batch so that both give the same bits for the same pose and index.
+__device__ __forceinline__ void pinhole_ray(const float* __restrict__ P, float fx, float fy, float cx, float cy, uint32_t W,
+                                            int64_t pix, int perturb, float off_x, float off_y, float o[3], float d[3]) {
+    float i = (float)(uint32_t)(pix % W) + 0.5f, j = (float)(uint32_t)(pix / W) + 0.5f;
+    if (perturb) { i -= off_x; j -= off_y; }                 // :133-136
+    const float xs = (i - cx) / fx, ys = (j - cy) / fy;      // :138-139 (zs = 1)
+    const float nrm = sqrtf(fmaf(ys, ys, xs * xs) + 1.0f);   // :141
+    const float dx = xs / nrm, dy = ys / nrm, dz = 1.0f / nrm;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {                            // :142 directions @ R^T, :144 translation column
+        d[k] = fmaf(dz, P[4 * k + 2], fmaf(dy, P[4 * k + 1], dx * P[4 * k]));
+        o[k] = P[4 * k + 3];
+    }
+}
+
+// the ray/box interval of K1 (raymarching.cu:91-145) for a ray already in registers
+__device__ __forceinline__ void ray_box(const float o[3], const float d[3], const float* __restrict__ aabb, float min_near,
+                                        float* __restrict__ near_out, float* __restrict__ far_out) {
+    const float BIG = 3.402823466e+38f;
+    float tn = 0.f, tf = 0.f;
+    bool miss = false;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        if (miss) break;
+        const float rcp = 1.0f / d[a];
+        float lo = (aabb[a] - o[a]) * rcp, hi = (aabb[a + 3] - o[a]) * rcp;
+        if (lo > hi) { float sw = lo; lo = hi; hi = sw; }
+        if (a == 0) { tn = lo; tf = hi; }
+        else {
+            if (tn > hi || lo > tf) { miss = true; }
+            else { if (lo > tn) tn = lo; if (hi < tf) tf = hi; }
+        }
+    }
+    if (miss) { *near_out = BIG; *far_out = BIG; return; }
+    if (tn < min_near) tn = min_near;
+    *near_out = tn; *far_out = tf;
+}
+
 __global__ void k_near_far(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                            const float* __restrict__ aabb, uint32_t N, float min_near,
                            float* __restrict__ nears, float* __restrict__ fars) {

@@ -48,39 +48,13 @@ __global__ void k_get_rays(const float* __restrict__ poses, uint32_t B, float fx
     if (n >= N) return;
     const float* __restrict__ P = poses + 16 * (size_t)b;
     const int64_t pix = inds ? inds[(size_t)b * inds_stride + n] : (int64_t)n;
-    float i = (float)(uint32_t)(pix % W) + 0.5f, j = (float)(uint32_t)(pix / W) + 0.5f;
-    if (perturb) { i -= off_x; j -= off_y; }                 // :133-136
-    const float xs = (i - cx) / fx, ys = (j - cy) / fy;      // :138-139 (zs = 1)
-    const float nrm = sqrtf(fmaf(ys, ys, xs * xs) + 1.0f);   // :141
-    const float dx = xs / nrm, dy = ys / nrm, dz = 1.0f / nrm;
-    float d[3], o[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {                            // :142 directions @ R^T, :144 translation column
-        d[k] = fmaf(dz, P[4 * k + 2], fmaf(dy, P[4 * k + 1], dx * P[4 * k]));
-        o[k] = P[4 * k + 3];
-    }
+    float o[3], d[3];
+    pinhole_ray(P, fx, fy, cx, cy, W, pix, perturb, off_x, off_y, o, d);
     const size_t r = (size_t)b * N + n;
 #pragma unroll
     for (int k = 0; k < 3; k++) { rays_o[3 * r + k] = o[k]; rays_d[3 * r + k] = d[k]; }
     if (!aabb) return;
-    const float BIG = 3.402823466e+38f;                      // K1, raymarching.cu:91-145
-    float tn = 0.f, tf = 0.f;
-    bool miss = false;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        if (miss) break;
-        const float rcp = 1.0f / d[a];
-        float lo = (aabb[a] - o[a]) * rcp, hi = (aabb[a + 3] - o[a]) * rcp;
-        if (lo > hi) { float sw = lo; lo = hi; hi = sw; }
-        if (a == 0) { tn = lo; tf = hi; }
-        else {
-            if (tn > hi || lo > tf) { miss = true; }
-            else { if (lo > tn) tn = lo; if (hi < tf) tf = hi; }
-        }
-    }
-    if (miss) { nears[r] = BIG; fars[r] = BIG; return; }
-    if (tn < min_near) tn = min_near;
-    nears[r] = tn; fars[r] = tf;
+    ray_box(o, d, aabb, min_near, nears + r, fars + r);
 }
 
 // ---------------------------------------------------------------- K3 / K4 / K5
@@ -147,8 +121,8 @@ struct MarchRecs { uint32_t* nrec; MarchRec* rec; };      // nrec[N], rec[N * MA
 template <bool EMIT>
 __global__ __launch_bounds__(MARCH_BLOCK) void k_march_train_wave(
     const float* __restrict__ rays_o, const float* __restrict__ rays_d, const uint8_t* __restrict__ grid, MarchCfg cfg,
-    uint32_t max_steps, uint32_t N, uint32_t M, const float* __restrict__ nears, const float* __restrict__ fars,
-    const float* __restrict__ noises, uint32_t* __restrict__ counts, const uint32_t* __restrict__ prefix,
+    uint32_t max_steps, uint32_t N, uint32_t M, const uint32_t* __restrict__ m_limit, const float* __restrict__ nears,
+    const float* __restrict__ fars, const float* __restrict__ noises, uint32_t* __restrict__ counts, const uint32_t* __restrict__ prefix,
     float* __restrict__ xyzs, float* __restrict__ dirs, float* __restrict__ deltas, int32_t* __restrict__ rays, MarchRecs recs) {
     const uint32_t n = blockIdx.x * MARCH_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // one ray per wave: scalar
     if (n >= N) return;                                   // whole wave
@@ -170,7 +144,8 @@ __global__ __launch_bounds__(MARCH_BLOCK) void k_march_train_wave(
             rays[3 * (size_t)row + 1] = (int32_t)offset;
             rays[3 * (size_t)row + 2] = (int32_t)limit;
         }
-        if (limit == 0 || offset + limit > M) return;     // :415-416 (overflowing rays write nothing)
+        const uint32_t M_trunc = m_limit ? min(*m_limit, M) : M;   // lae_march_rays_train_limit: threshold from device memory
+        if (limit == 0 || offset + limit > M_trunc) return;     // :415-416 (overflowing rays write nothing)
     }
     const Ray r = load_ray(rays_o, rays_d, n);
     const float far = fars[n];
@@ -290,9 +265,10 @@ __global__ __launch_bounds__(MARCH_BLOCK) void k_march_train_wave(
 // prefix[0..N) = exclusive prefix, prefix[N] / prefix[N+1] = counter values before this call.
 // prefix[N + 2] = rows_end: first sample row not written by this call (end of the last ray that fits into M);
 // the emit pass zero-fills [rows_end, M) so callers need not pre-zero xyzs / dirs / deltas.
-__global__ __launch_bounds__(1024) void k_scan_counts(const uint32_t* __restrict__ counts, uint32_t N, uint32_t M,
-                                                       uint32_t* __restrict__ prefix, int32_t* __restrict__ counter,
-                                                       uint32_t* __restrict__ rows_end_out) {
+__global__ __launch_bounds__(1024) void k_scan_counts(const uint32_t* __restrict__ counts, uint32_t N, uint32_t M_cap,
+                                                       const uint32_t* __restrict__ m_limit, uint32_t* __restrict__ prefix,
+                                                       int32_t* __restrict__ counter, uint32_t* __restrict__ rows_end_out) {
+    const uint32_t M = m_limit ? min(*m_limit, M_cap) : M_cap;
     __shared__ uint32_t lds[17];
     __shared__ uint32_t s_end, s_base;
     if (threadIdx.x == 0) { s_end = 0; s_base = counter ? (uint32_t)counter[0] : 0u; }
@@ -848,10 +824,10 @@ uint64_t lae_march_rays_train_scratch_bytes(uint32_t N) {
     return march_base_bytes(N) + (N <= MARCH_REC_RAYS_MAX ? ((4ull * N + 15) / 16 * 16) + (uint64_t)N * MARCH_REC_MAX * sizeof(MarchRec) : 0ull);
 }
 
-int lae_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
-                         uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
-                         const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
-                         const float* noises, void* scratch, uint32_t* rows_end_out, void* stream) {
+static int march_rays_train_impl(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
+                                 uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const uint32_t* m_limit,
+                                 const float* nears, const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays,
+                                 int32_t* counter, const float* noises, void* scratch, uint32_t* rows_end_out, void* stream) {
     if (N == 0) return LAE_OK;
     if (!rays_o || !rays_d || !grid || !nears || !fars || !xyzs || !dirs || !deltas || !rays || !noises || !scratch)
         return LAE_ENULL;
@@ -867,12 +843,29 @@ int lae_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t
         recs.nrec = reinterpret_cast<uint32_t*>(base);
         recs.rec = reinterpret_cast<MarchRec*>(base + (4ull * N + 15) / 16 * 16);
     }
-    k_march_train_wave<false><<<nblk, MARCH_BLOCK, 0, s>>>(rays_o, rays_d, grid, cfg, max_steps, N, M, nears, fars, noises,
+    k_march_train_wave<false><<<nblk, MARCH_BLOCK, 0, s>>>(rays_o, rays_d, grid, cfg, max_steps, N, M, m_limit, nears, fars, noises,
                                                            counts, nullptr, nullptr, nullptr, nullptr, nullptr, recs);
-    k_scan_counts<<<1, 1024, 0, s>>>(counts, N, M, prefix, counter, rows_end_out);
-    k_march_train_wave<true><<<nblk, MARCH_BLOCK, 0, s>>>(rays_o, rays_d, grid, cfg, max_steps, N, M, nears, fars, noises,
+    k_scan_counts<<<1, 1024, 0, s>>>(counts, N, M, m_limit, prefix, counter, rows_end_out);
+    k_march_train_wave<true><<<nblk, MARCH_BLOCK, 0, s>>>(rays_o, rays_d, grid, cfg, max_steps, N, M, m_limit, nears, fars, noises,
                                                           counts, prefix, xyzs, dirs, deltas, rays, recs);
     return lae::check_launch("march_rays_train");
+}
+
+int lae_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
+                         uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
+                         const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
+                         const float* noises, void* scratch, uint32_t* rows_end_out, void* stream) {
+    return march_rays_train_impl(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nullptr, nears, fars, xyzs, dirs,
+                                 deltas, rays, counter, noises, scratch, rows_end_out, stream);
+}
+
+int lae_march_rays_train_limit(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
+                               uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M_cap, const uint32_t* m_limit,
+                               const float* nears, const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays,
+                               int32_t* counter, const float* noises, void* scratch, uint32_t* rows_end_out, void* stream) {
+    if (N != 0 && !m_limit) return LAE_ENULL;
+    return march_rays_train_impl(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M_cap, m_limit, nears, fars, xyzs,
+                                 dirs, deltas, rays, counter, noises, scratch, rows_end_out, stream);
 }
 
 int lae_composite_rays_train_forward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,

@@ -1,0 +1,218 @@
+"""Posed training images resident on the device, and the per-step ray batch drawn from them.
+
+The reference's loader (NeRFDataset, nerf/provider.py) keeps the images on the GPU (`preload`) and builds every training
+batch in `collate` -> `get_rays` -> `Trainer.train_step` (nerf/utils.py:62-153, 560-580): a pixel draw, a gather of the
+targets, an sRGB -> linear conversion when asked, and a blend of the alpha channel over a per-pixel random background --
+about 15 torch launches and host-side randomness per step.  `ResidentImages.sample` is ONE kernel
+(`lae_sample_train_batch`, csrc/batch.hip) whose step number lives in device memory and is advanced by the call, so a
+captured graph draws a fresh batch on every replay.  Its generator is stated in include/laenerf.h (Philox4x32-10 keyed by
+the seed, counter (step, ray, word, 0)); `philox4x32_10` / `draw_indices` below restate it in numpy.
+
+Deviation: the reference shuffles the image order once per epoch; here the image of a batch (mode 'image', the
+reference's batch_size = 1) or of every ray (mode 'all', as instant-ngp) is drawn i.i.d.
+"""
+import json
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream
+
+__all__ = ["ResidentImages", "nerf_matrix_to_ngp", "philox4x32_10", "draw_indices", "draw_background"]
+
+_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
+_MODES = {"image": 0, "all": 1}
+_BGS = {"white": 0, "random": 1}
+
+
+def nerf_matrix_to_ngp(pose, scale=0.33, offset=(0, 0, 0)):
+    """provider.py:19-27: a NeRF (blender) cam2world matrix in instant-ngp's axis order, scaled and offset"""
+    pose = np.asarray(pose, dtype=np.float32)
+    return np.array([
+        [pose[1, 0], -pose[1, 1], -pose[1, 2], pose[1, 3] * scale + offset[0]],
+        [pose[2, 0], -pose[2, 1], -pose[2, 2], pose[2, 3] * scale + offset[1]],
+        [pose[0, 0], -pose[0, 1], -pose[0, 2], pose[0, 3] * scale + offset[2]],
+        [0, 0, 0, 1],
+    ], dtype=np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the RNG
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 on numpy arrays: ctr [..., 4] uint32, key [..., 2] uint32 (broadcast) -> [..., 4] uint32"""
+    c = [np.asarray(ctr, dtype=np.uint32)[..., i].astype(np.uint64) for i in range(4)]
+    k0 = np.asarray(key, dtype=np.uint32)[..., 0].astype(np.uint64)
+    k1 = np.asarray(key, dtype=np.uint32)[..., 1].astype(np.uint64)
+    m32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        hi0, lo0 = p0 >> np.uint64(32), p0 & m32
+        hi1, lo1 = p1 >> np.uint64(32), p1 & m32
+        c = [hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0]
+        k0 = (k0 + np.uint64(0x9E3779B9)) & m32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & m32
+    return np.stack([x.astype(np.uint32) for x in c], axis=-1)
+
+
+def _u32(seed, step, ray, word):
+    ray = np.asarray(ray, dtype=np.uint64)
+    ctr = np.stack(np.broadcast_arrays(np.uint64(step & 0xFFFFFFFF), ray, np.uint64(word), np.uint64(0)), axis=-1)
+    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint64)
+    return philox4x32_10(ctr.astype(np.uint32), key.astype(np.uint32))[..., 0]
+
+
+def _scale(u, n):
+    return ((u.astype(np.uint64) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+
+
+def draw_indices(seed, step, n_rays, n_img, H, W, mode="image"):
+    """numpy restatement of the kernel's draw -> (image [N] int64, pixel [N] int64)"""
+    rays = np.arange(n_rays, dtype=np.uint64)
+    pix = _scale(_u32(seed, step, rays, 0), H * W)
+    img_ray = np.full(n_rays, 0xFFFFFFFF, dtype=np.uint64) if mode == "image" else rays
+    img = _scale(_u32(seed, step, img_ray, 1), n_img)
+    return img, pix
+
+
+def draw_background(seed, step, n_rays):
+    """numpy restatement of the kernel's RANDOM background -> [N,3] float32"""
+    rays = np.arange(n_rays, dtype=np.uint64)
+    return np.stack([(_u32(seed, step, rays, 2 + c) >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+                     for c in range(3)], axis=-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- images
+class ResidentImages:
+    """images [n, H, W, C] (C = 3 or 4; uint8, fp16 or fp32) + cam2world poses [n, 4, 4] + one (fx, fy, cx, cy), on the GPU.
+
+    bg: 'random' (a per-pixel uniform background, the reference's rule for C = 4) or 'white' (its bg_color = 1, used for
+    C = 3); default by C.  color_space 'linear' converts the colour to linear before the blend (nerf/utils.py:564)."""
+
+    def __init__(self, images, poses, intrinsics, bound=1.0, min_near=0.2, mode="image", bg=None, color_space="srgb", seed=0,
+                 device=None):
+        device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        # (device="cpu" holds the arrays on the host -- loaders and tests without a GPU; sample() needs the GPU)
+        images = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))
+        if images.dim() != 4 or images.shape[-1] not in (3, 4):
+            raise ValueError("ResidentImages: images must be [n, H, W, 3 or 4]")
+        if images.dtype not in _DTYPES:
+            raise ValueError("ResidentImages: image dtype must be uint8, float16 or float32")
+        poses = poses if torch.is_tensor(poses) else torch.from_numpy(np.asarray(poses, dtype=np.float32))
+        if poses.shape != (images.shape[0], 4, 4):
+            raise ValueError("ResidentImages: poses must be [n, 4, 4]")
+        if mode not in _MODES:
+            raise ValueError(f"ResidentImages: mode must be one of {sorted(_MODES)}")
+        self.C = int(images.shape[-1])
+        bg = bg if bg is not None else ("random" if self.C == 4 else "white")
+        if bg not in _BGS:
+            raise ValueError(f"ResidentImages: bg must be one of {sorted(_BGS)}")
+        self.images = images.to(device).contiguous()
+        self.poses = poses.to(device, torch.float32).contiguous()
+        self.n_img, self.H, self.W = (int(x) for x in images.shape[:3])
+        self.intrinsics = tuple(float(v) for v in intrinsics)
+        self.bound, self.min_near = float(bound), float(min_near)
+        self.aabb = torch.tensor([-bound] * 3 + [bound] * 3, dtype=torch.float32, device=device)
+        self.mode, self.bg, self.color_space, self.seed = mode, bg, color_space, int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.step = torch.zeros(1, dtype=torch.int64, device=device)          # the kernel's step counter
+        self._out = {}
+
+    @classmethod
+    def from_arrays(cls, images, poses, intrinsics, **kw):
+        return cls(images, poses, intrinsics, **kw)
+
+    @classmethod
+    def from_transforms(cls, path, scale=0.33, offset=(0, 0, 0), downscale=1, dtype="uint8", split=None, **kw):
+        """a blender-style scene: `path` is a transforms.json (or a directory holding transforms[_split].json).  Poses go
+        through nerf_matrix_to_ngp; focal lengths from fl_x / fl_y or camera_angle_x / _y, cx / cy default to W/2, H/2
+        (provider.py:277-290); images are decoded with PIL and resized with a box filter when `downscale` > 1 (the
+        reference's cv2 INTER_AREA).  dtype 'uint8' keeps the 8-bit values (4x less memory), 'float16' / 'float32' store
+        value / 255."""
+        from PIL import Image
+        if os.path.isdir(path):
+            path = os.path.join(path, f"transforms_{split}.json" if split else "transforms.json")
+        root = os.path.dirname(os.path.abspath(path))
+        with open(path) as f:
+            transform = json.load(f)
+        H = W = None
+        if "h" in transform and "w" in transform:
+            H, W = int(transform["h"]) // downscale, int(transform["w"]) // downscale
+        poses, images = [], []
+        for fr in transform["frames"]:
+            f_path = os.path.join(root, fr["file_path"])
+            if "." not in os.path.basename(f_path):
+                f_path += ".png"
+            if not os.path.exists(f_path):
+                continue
+            poses.append(nerf_matrix_to_ngp(np.array(fr["transform_matrix"], dtype=np.float32), scale=scale, offset=offset))
+            im = Image.open(f_path)
+            im = im.convert("RGBA" if im.mode in ("RGBA", "LA", "PA") or "transparency" in im.info else "RGB")
+            if H is None:
+                H, W = im.height // downscale, im.width // downscale
+            if (im.height, im.width) != (H, W):
+                im = im.resize((W, H), Image.BOX)
+            images.append(np.asarray(im, dtype=np.uint8))
+        if not images:
+            raise RuntimeError(f"ResidentImages.from_transforms: no image of {path} found")
+        images = np.stack(images)
+        if dtype in ("float16", "float32", torch.float16, torch.float32):
+            np_dt = np.float16 if dtype in ("float16", torch.float16) else np.float32
+            images = (images.astype(np.float32) / 255).astype(np_dt)
+        elif dtype not in ("uint8", torch.uint8):
+            raise ValueError("from_transforms: dtype must be 'uint8', 'float16' or 'float32'")
+        if "fl_x" in transform or "fl_y" in transform:
+            fl_x = (transform["fl_x"] if "fl_x" in transform else transform["fl_y"]) / downscale
+            fl_y = (transform["fl_y"] if "fl_y" in transform else transform["fl_x"]) / downscale
+        elif "camera_angle_x" in transform or "camera_angle_y" in transform:
+            fl_x = W / (2 * math.tan(transform["camera_angle_x"] / 2)) if "camera_angle_x" in transform else None
+            fl_y = H / (2 * math.tan(transform["camera_angle_y"] / 2)) if "camera_angle_y" in transform else None
+            fl_x = fl_y if fl_x is None else fl_x
+            fl_y = fl_x if fl_y is None else fl_y
+        else:
+            raise RuntimeError("ResidentImages.from_transforms: no focal length in the transforms file")
+        cx = transform["cx"] / downscale if "cx" in transform else W / 2
+        cy = transform["cy"] / downscale if "cy" in transform else H / 2
+        return cls(images, np.stack(poses), (fl_x, fl_y, cx, cy), **kw)
+
+    def _buffers(self, n):
+        out = self._out.get(n)
+        if out is None:
+            dev = self.images.device
+            out = self._out[n] = {
+                "rays_o": torch.empty(n, 3, dtype=torch.float32, device=dev), "rays_d": torch.empty(n, 3, dtype=torch.float32, device=dev),
+                "nears": torch.empty(n, dtype=torch.float32, device=dev), "fars": torch.empty(n, dtype=torch.float32, device=dev),
+                "gt": torch.empty(n, 3, dtype=torch.float32, device=dev), "inds": torch.empty(n, dtype=torch.int64, device=dev),
+                "bg": torch.empty(n, 3, dtype=torch.float32, device=dev) if self.bg == "random" else None,
+            }
+        return out
+
+    @torch.no_grad()
+    def sample(self, n_rays, step=None, out=None):
+        """one batch of n_rays -> dict rays_o, rays_d [N,3], nears, fars [N], gt [N,3] (blended), bg [N,3] ('random') or the
+        number 1 ('white'), inds [N] (image * H * W + pixel).  step=None: the device counter's value, which the call then
+        advances (capturable); step=k: the counter is set to k first.  The result tensors are reused by the next call with
+        the same n_rays unless `out` (a dict of tensors from an earlier call) is passed."""
+        _lib.need_cuda(self.images)
+        if step is not None:
+            self.step.fill_(int(step))
+        o = out if out is not None else self._buffers(int(n_rays))
+        fx, fy, cx, cy = self.intrinsics
+        check(_lib.load().lae_sample_train_batch(
+            ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self.poses), fx, fy, cx, cy,
+            int(n_rays), ptr(self.aabb), self.min_near, self.seed, ptr(self.step), _MODES[self.mode], _BGS[self.bg],
+            int(self.color_space == "linear"), ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]),
+            ptr(o["bg"]), ptr(o["inds"]), stream()), "sample_train_batch")
+        res = dict(o)
+        if res["bg"] is None:
+            res["bg"] = 1
+        return res
+
+    def view_rays(self, i):
+        """every pixel of image i (scanline order) -> rays_o, rays_d [H*W, 3] and its colour [H*W, C] as fp32 on the device"""
+        from .rays import get_rays
+        r = get_rays(self.poses[i:i + 1], self.intrinsics, self.H, self.W)
+        img = self.images[i].reshape(-1, self.C)
+        img = img.float() / 255 if img.dtype == torch.uint8 else img.float()
+        return r["rays_o"][0], r["rays_d"][0], img

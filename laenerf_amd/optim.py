@@ -31,7 +31,9 @@ _direct_grad = {"depth": 0}
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, model, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, weight_decay=0.0, param_groups=None,
-                 grad_scaler=True, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+                 grad_scaler=True, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, device_lr=False):
+        """device_lr=True: the caller owns the device copy `self.lrs` (one fp32 per parameter group) and writes it on the device,
+        e.g. from a schedule table inside a captured graph (laenerf_amd.trainer); sync_lr() / step() then never overwrite it."""
         groups = param_groups if param_groups is not None else [{"params": [p for p in model.parameters() if p.requires_grad], "lr": lr}]
         # empty groups stay (the reference's get_params has one for the parameter-free direction encoder, network_ff.py:147):
         # group indices must line up with a torch.optim.Adam checkpoint
@@ -79,6 +81,7 @@ class FusedAdam(torch.optim.Optimizer):
                     shadow.nonfinite_flag = self.dev_state.data_ptr() + 8    # the fused head backward reports its weight gradients
         self._scale_view = self.dev_state.view(torch.float32)
         self._scale_view[0] = init_scale if self.use_scaler else 1.0
+        self.device_lr = bool(device_lr)
         self._lr_host = [float(g["lr"]) for g in self.param_groups]
         self.lrs = torch.tensor(self._lr_host, dtype=torch.float32, device=dev)
         if len(self.items) > 8:
@@ -138,7 +141,9 @@ class FusedAdam(torch.optim.Optimizer):
     def sync_lr(self):
         """push `param_groups[i]["lr"]` (what torch's schedulers mutate) to the device copy the kernels read.  step() does
         it by itself when a value changed; a caller that REPLAYS a captured step calls this between replays (the graph
-        reads the device copy, so the new rate takes effect without re-capturing)."""
+        reads the device copy, so the new rate takes effect without re-capturing).  No-op under device_lr=True."""
+        if self.device_lr:
+            return
         cur = [float(g["lr"]) for g in self.param_groups]
         if cur != self._lr_host:
             if torch.cuda.is_current_stream_capturing():

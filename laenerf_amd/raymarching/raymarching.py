@@ -143,7 +143,47 @@ class _march_rays_train(Function):
         return xyzs, dirs, deltas, rays
 
 
-march_rays_train = _march_rays_train.apply
+def march_rays_train(*args, m_limit=None, capacity=None, **kwargs):
+    """raymarching.py:161-235 (arguments as there).  MI355X-native keywords m_limit=<device int32 tensor of 1 element>,
+    capacity=<int>: the sample buffers get `capacity` rows and rays are truncated where a call with the host threshold
+    M = min(m_limit, capacity) truncates them (lae_march_rays_train_limit) -- so one captured graph serves every threshold up to
+    its capacity.  mean_count, align and force_all_rays are then ignored and no host read happens.  Without them: unchanged."""
+    if m_limit is None and capacity is None:
+        return _march_rays_train.apply(*args, **kwargs)
+    if m_limit is None or capacity is None:
+        raise ValueError("march_rays_train: m_limit and capacity go together")
+    import inspect
+    bound_args = inspect.signature(_march_rays_train.forward).bind(None, *args, **kwargs)
+    bound_args.apply_defaults()
+    a = bound_args.arguments
+    return _march_limit(a["rays_o"], a["rays_d"], a["bound"], a["density_bitfield"], a["C"], a["H"], a["nears"], a["fars"],
+                        a["step_counter"], a["perturb"], a["dt_gamma"], a["max_steps"], m_limit, int(capacity))
+
+
+@torch.no_grad()
+def _march_limit(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars, step_counter, perturb, dt_gamma, max_steps, m_limit,
+                 M_cap):
+    rays_o, rays_d = _rays(rays_o).float(), _rays(rays_d).float()
+    density_bitfield = _gpu(density_bitfield).contiguous()
+    if not (torch.is_tensor(m_limit) and m_limit.is_cuda and m_limit.dtype == torch.int32 and m_limit.numel() == 1):
+        raise RuntimeError("march_rays_train: m_limit must be a 1-element int32 tensor on the GPU")
+    if M_cap <= 0:
+        raise ValueError("march_rays_train: capacity must be positive")
+    dev, dt = rays_o.device, rays_o.dtype
+    N = rays_o.shape[0]
+    xyzs = torch.empty(M_cap, 3, dtype=dt, device=dev)
+    dirs = torch.empty(M_cap, 3, dtype=dt, device=dev)
+    deltas = torch.empty(M_cap, 2, dtype=dt, device=dev)
+    rays = torch.empty(N, 3, dtype=torch.int32, device=dev)
+    rows_end = torch.empty(1, dtype=torch.int32, device=dev)
+    if step_counter is None:
+        step_counter = torch.zeros(2, dtype=torch.int32, device=dev)
+    noises = torch.rand(N, dtype=dt, device=dev) if perturb else torch.zeros(N, dtype=dt, device=dev)
+    _backend.march_rays_train_limit(rays_o, rays_d, density_bitfield, bound, dt_gamma, max_steps, N, C, H, M_cap, m_limit,
+                                    nears.float().contiguous(), fars.float().contiguous(), xyzs, dirs, deltas, rays, step_counter,
+                                    noises, rows_end)
+    rays.rows_end = rows_end
+    return xyzs, dirs, deltas, rays
 
 
 class _composite_rays_train(Function):

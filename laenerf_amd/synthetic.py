@@ -134,3 +134,18 @@ def flower_density_grid(H=128, value=20.0):
 def pack_bits_np(grid, thresh):
     bits = (grid.reshape(-1, 8) > thresh).astype(np.uint8)
     return (bits << np.arange(8, dtype=np.uint8)).sum(axis=1).astype(np.uint8)
+
+
+def lookat_poses(n_views, radius=3.2, seed=0):
+    """[n_views, 4, 4] float32 cam2world matrices of cameras on a sphere of `radius` looking at the origin, in get_rays'
+    convention (columns: image x to the right, image y downwards, viewing direction), elevations as lego_like_rays'"""
+    rng = np.random.default_rng(seed)
+    theta = rng.uniform(0.2, np.pi / 2 - 0.1, n_views)
+    phi = rng.uniform(0, 2 * np.pi, n_views)
+    cam = np.stack([np.sin(theta) * np.cos(phi), np.cos(theta), np.sin(theta) * np.sin(phi)], -1) * radius
+    fwd = -cam / np.linalg.norm(cam, axis=-1, keepdims=True)
+    right = np.cross(fwd, np.array([0.0, 1.0, 0.0])); right /= np.linalg.norm(right, axis=-1, keepdims=True)
+    down = np.cross(fwd, right)
+    poses = np.zeros((n_views, 4, 4), np.float32)
+    poses[:, :3, 0], poses[:, :3, 1], poses[:, :3, 2], poses[:, :3, 3], poses[:, 3, 3] = right, down, fwd, cam, 1.0
+    return poses

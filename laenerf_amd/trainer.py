@@ -1,0 +1,214 @@
+"""Training on posed images, the loop of the reference's `Trainer.train_one_epoch` (nerf/utils.py:1442-1503), with every
+16-step group between two occupancy-grid refreshes replayed as ONE captured HIP graph.
+
+Per step: learning rate from a device table -> ray batch (ResidentImages.sample, one kernel) -> occupancy march ->
+field + compositing + fused criterion (render_train's second half) -> backward -> FusedAdam.step.  Every 16 steps,
+between groups and eagerly: update_extra_state (renderer.py:555-649), with its single host read; `mark_untrained_grid`
+once before the first step (nerf/utils.py:752).
+
+What makes a group capturable although the reference changes two host values in it:
+  * the march's truncation threshold M = round_up(mean_count, 128) changes at every refresh.  The group is captured with a
+    buffer capacity M_cap >= M and reads M from device memory (`m_limit`, lae_march_rays_train_limit), so a graph serves
+    every M up to its capacity.  capacity='bucket' rounds M up to 1/8-octave steps (at most 12.5 % padding rows, few
+    distinct graphs); 'exact' uses M_cap = M (a new graph for every new M).
+  * the learning rate `lr * 0.1 ** min(it / iters, 1)` changes every step.  The schedule is uploaded once (fp64 on the
+    host, cast to fp32: the bits FusedAdam.set_lr writes) and each step copies its row into FusedAdam.lrs on the device.
+The first 16 steps run eagerly (mean_count = 0: the march sizes its buffers from a host read, as in the reference).
+The graphs share one memory pool: they never run concurrently.
+"""
+import math
+
+import numpy as np
+import torch
+
+from .raymarching import raymarching
+
+__all__ = ["Trainer", "lr_schedule", "bucket_capacity", "psnr"]
+
+GROUP = 16                      # update_extra_interval of the reference (main_nerf.py), = the step_counter ring length
+
+
+def lr_schedule(lr, iters, n_rows, n_groups=1):
+    """[n_rows, n_groups] float32: row it = float32(lr * 0.1 ** min(it / iters, 1)) (main_nerf.py:239-245's LambdaLR)"""
+    lrs = np.broadcast_to(np.asarray(lr, dtype=np.float64).reshape(-1), (n_groups,))
+    it = np.arange(n_rows, dtype=np.float64)
+    return np.stack([np.array([float(l) * 0.1 ** min(float(i) / iters, 1.0) for i in it], dtype=np.float64) for l in lrs],
+                    axis=1).astype(np.float32)
+
+
+def round_up_always(m, align=128):
+    """the reference's `m += align - m % align` (raymarching.py:125-127)"""
+    return m + (align - m % align)
+
+
+def bucket_capacity(M, align=128):
+    """M rounded up to the next of 8 steps per octave (and to `align`): at most 12.5 % of the rows are padding"""
+    if M <= 8 * align:
+        return -(-M // align) * align
+    step = max(align, 1 << (int(M).bit_length() - 1 - 3))
+    return -(-M // step) * step
+
+
+def psnr(pred, gt):
+    """PSNRMeter (nerf/utils.py:222): -10 log10(mean squared error)"""
+    mse = float(((pred.float() - gt.float()) ** 2).mean())
+    return -10.0 * math.log10(max(mse, 1e-20))
+
+
+class Trainer:
+    """Trainer(renderer, optimizer, data, iters, lr): `optimizer` is a FusedAdam over the renderer's network (its device
+    learning rates are taken over: device_lr is switched on), `data` a ResidentImages, `iters` the decay horizon of the
+    learning rate, `lr` its start value (one number for every parameter group, or one per group).
+    graph=False runs the same steps eagerly; capacity 'bucket' / 'exact' (see the module docstring).
+    Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
+    eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
+
+    def __init__(self, renderer, optimizer, data, iters, lr, num_rays=4096, seed=0, graph=True, capacity="bucket",
+                 max_steps=1024, dt_gamma=0.0):
+        if capacity not in ("bucket", "exact"):
+            raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
+        self.r, self.opt, self.data = renderer, optimizer, data
+        self.iters, self.num_rays, self.graph, self.capacity = int(iters), int(num_rays), bool(graph), capacity
+        self.max_steps, self.dt_gamma = int(max_steps), float(dt_gamma)
+        dev = renderer.density_grid.device
+        data.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        data.aabb = renderer.aabb_train.to(dev, torch.float32).contiguous()      # the batch's near / far = the march's
+        data.min_near = float(renderer.min_near)
+        optimizer.device_lr = True
+        n_groups = len(optimizer.param_groups)
+        self.lr_table = torch.from_numpy(lr_schedule(lr, self.iters, self.iters + 1, n_groups)).to(dev)
+        self.m_limit = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.loss_slots = torch.zeros(GROUP, dtype=torch.float32, device=dev)
+        self.global_step = 0
+        self.started = False
+        self.graphs = {}
+        self._pool = None
+        self._rows_seen = 0
+        self.captures = self.cache_misses = self.warm_groups = 0
+        self._loss_hist = []
+
+    # ------------------------------------------------------------------ one step
+    def _m(self):
+        return round_up_always(self.r.mean_count, 128)
+
+    def _m_cap(self):
+        M = self._m()
+        return M if self.capacity == "exact" else bucket_capacity(M)
+
+    def _step(self, k, m_cap):
+        """one training step (eager or under capture); k = its slot in the group.  m_cap None: host-sized march."""
+        r, opt = self.r, self.opt
+        with torch.no_grad():
+            row = torch.clamp(self.data.step, max=self.iters)
+            opt.lrs.copy_(self.lr_table.index_select(0, row).view(-1))
+        b = self.data.sample(self.num_rays)
+        counter = r.step_counter[r.local_step % GROUP]
+        counter.zero_()
+        r.local_step += 1
+        with torch.autocast("cuda", dtype=torch.float16):
+            if m_cap is None:
+                xyzs, dirs, deltas, rays = raymarching.march_rays_train(
+                    b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
+                    r.mean_count, True, 128, False, self.dt_gamma, self.max_steps)
+            else:
+                xyzs, dirs, deltas, rays = raymarching.march_rays_train(
+                    b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
+                    perturb=True, dt_gamma=self.dt_gamma, max_steps=self.max_steps, m_limit=self.m_limit, capacity=m_cap)
+            if not torch.cuda.is_current_stream_capturing():
+                self._rows_seen = max(self._rows_seen, xyzs.shape[0])
+            res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt)
+        loss = res["loss"]
+        opt.backward(loss)
+        opt.step()
+        with torch.no_grad():
+            self.loss_slots[k].copy_(loss.unscaled.view(()))
+
+    def _refresh(self):
+        with torch.autocast("cuda", dtype=torch.float16):
+            self.r.update_extra_state()
+
+    # ------------------------------------------------------------------ groups
+    def _run_group(self, m_cap):
+        g = self.graphs.get(m_cap)
+        if g is None:
+            self.cache_misses += 1
+            if m_cap > self._rows_seen:
+                # the encoder / MLP workspaces may have to grow to m_cap rows, which is refused inside a capture: this group
+                # runs eagerly (the same kernels, hence the same bits) and the next one with this capacity is captured
+                self.warm_groups += 1
+                for k in range(GROUP):
+                    self._step(k, m_cap)
+                self._rows_seen = max(self._rows_seen, m_cap)
+                return
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=self._pool):
+                for k in range(GROUP):
+                    self._step(k, m_cap)
+            if self._pool is None:
+                self._pool = g.pool()
+            self.graphs[m_cap] = g
+            self.captures += 1
+        g.replay()
+        self.r.local_step = GROUP
+
+    def train(self, n_steps):
+        """n_steps steps of the reference's loop (refresh every 16 global steps, before the step)"""
+        r = self.r
+        if not self.started:
+            r.mark_untrained_grid(self.data.poses, self.data.intrinsics)
+            self.data.step.fill_(self.global_step)
+            self.started = True
+        r.model.train()
+        done = 0
+        while done < n_steps:
+            if self.global_step % GROUP == 0:
+                self._refresh()
+            pos = self.global_step % GROUP
+            if r.mean_count > 0:
+                self.m_limit.fill_(self._m())
+            if self.graph and r.mean_count > 0 and pos == 0 and n_steps - done >= GROUP:
+                self._run_group(self._m_cap())
+                n = GROUP
+            else:
+                self._step(pos, self._m_cap() if r.mean_count > 0 else None)
+                n = 1
+            self._loss_hist.append(self.loss_slots[pos:pos + n].clone())
+            done += n
+            self.global_step += n
+        return self
+
+    # ------------------------------------------------------------------ results
+    def losses(self):
+        """per-step losses (the unscaled MSE of every step so far) as a float32 numpy array"""
+        if not self._loss_hist:
+            return np.zeros(0, np.float32)
+        return torch.cat(self._loss_hist).cpu().numpy()
+
+    @property
+    def steps_skipped(self):
+        """optimizer steps the GradScaler skipped (non-finite gradients)"""
+        return self.opt.steps_skipped
+
+    @torch.no_grad()
+    def evaluate(self, views, data=None, bg_color=1.0):
+        """mean PSNR over `views` (image indices of `data`, default the training set) rendered with render_eval over a plain
+        background `bg_color` (the ground truth is blended over the same background)"""
+        data = self.data if data is None else data
+        r = self.r
+        was_training = r.model.training
+        r.model.eval()
+        vals = []
+        try:
+            for i in views:
+                o, d, img = data.view_rays(int(i))
+                if img.shape[-1] == 4:
+                    a = img[:, 3:]
+                    gt = img[:, :3] * a + bg_color * (1 - a)
+                else:
+                    gt = img
+                with torch.autocast("cuda", dtype=torch.float16):
+                    pred = r.render_eval(o, d, bg_color=bg_color, image_hw=(data.H, data.W))["image"]
+                vals.append(psnr(pred.reshape(-1, 3), gt))
+        finally:
+            r.model.train(was_training)
+        return float(np.mean(vals))
