@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi7"
+#define LAE_ABI_TAG "abi8"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -129,6 +129,45 @@ LAE_API int lae_sample_train_batch(const void* images, int dtype, uint32_t n_img
                            const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int mode, int bg_mode,
                            int srgb_to_linear, float* rays_o, float* rays_d, float* nears, float* fars, float* gt,
                            float* bg_out, int64_t* inds, void* stream);
+
+/* The error-map sampler (the reference's --error_map, nerf/utils.py:112-124, and LAENeRF's --use_error_maps): the batch of
+ * lae_sample_train_batch (LAE_BATCH_IMAGE mode) with the pixels drawn by a per-image map of 128 x 128 cell weights.
+ * error_map [n_img, 16384] fp32 (row-major cells c = cx * 128 + cy); cells_out [N] int32; N <= 16384 (else LAE_EINVAL).
+ * u(r, word) and step as above; the same step protocol (read at the start, advanced by a trailing one-thread launch).
+ *   image  = (u(0xffffffff, 1) * (uint64)n_img) >> 32 (the uniform sampler's image at the same step)
+ *   cells: torch.multinomial(map[image], N, replacement=False)'s algorithm, key = w / E with E ~ Exp(1), top N:
+ *     v = word 0 of Philox4x32-10 with counter (step, c, 0, 1) (counter word 3 = 1: apart from the per-ray draws)
+ *     u = ((v >> 8) + 0.5) * 2^-24 in (0, 1), i.e. j * 2^-25 with the odd integer j = 2 * (v >> 8) + 1
+ *     E = -ln(u), computed from j, every step one fp32 rounding (no contraction), never libm:
+ *       p = bit length of j; if 2 j^2 < 2^(2p): p -= 1                 (j / 2^p in [sqrt(1/2), sqrt(2)))
+ *       f = float(j - 2^p) * 2^-p (exact), e = float(p - 25), z = f * f
+ *       P = 7.0376836292e-2; P = P * f + c for c in (-1.1514610310e-1, 1.1676998740e-1, -1.2420140846e-1, 1.4249322787e-1,
+ *           -1.6668057665e-1, 2.0000714765e-1, -2.4999993993e-1, 3.3333331174e-1)   (Cephes logf)
+ *       y = f * (z * P); y = y + e * -2.12194440e-4; y = y + -0.5 * z; r = f + y; r = r + e * 0.693359375; E = -r
+ *       (relative error of E <= 2^-20 against float64 for every one of the 2^24 inputs)
+ *     key = w / E, correctly rounded; a weight that is negative, NaN or infinite counts as 0 (key +0)
+ *     selection: the N largest keys compared as uint32 bit patterns (every key >= +0); ties at the threshold go to the
+ *     lower cell index; cells_out lists the chosen cells in increasing cell order.  Deviations from torch: torch returns
+ *     the cells in descending key order (within a batch the order changes only the rounding of the mean), and raises
+ *     when fewer than N cells have a positive weight, where here zero-weight cells fill the rest, lowest index first.
+ *   pixel of ray n in cell c: rx = (u(n, 0) >> 8) * 2^-24, ry = (u(n, 5) >> 8) * 2^-24, sx = fp32(H / 128),
+ *     sy = fp32(W / 128), row = min(trunc(fp32(fp32(cx * sx) + fp32(rx * sx))), H - 1) with cx = c / 128,
+ *     col = min(trunc(fp32(fp32(cy * sy) + fp32(ry * sy))), W - 1) with cy = c % 128, pixel = row * W + col
+ *     (the reference's `(inds_x * sx + rand * sx).long().clamp(max=H - 1)`).
+ *   background words 2..4, rays, nears, fars, gt, bg_out and inds = image * H * W + pixel as lae_sample_train_batch
+ *   (one shared per-ray device function). */
+LAE_API int lae_sample_train_batch_weighted(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                                    const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
+                                    const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int bg_mode,
+                                    int srgb_to_linear, const float* error_map, int32_t* cells_out, float* rays_o, float* rays_d,
+                                    float* nears, float* fars, float* gt, float* bg_out, int64_t* inds, void* stream);
+
+/* The error map's EMA after a step (nerf/utils.py:609-631), one thread per ray: image = inds[n] / (H * W),
+ * d = pred[n] - gt[n], err = ((d0 * d0 + d1 * d1) + d2 * d2) / 3, map[image][cells[n]] = 0.1 * old + 0.9 * err (fp32, each
+ * product and the sum rounded).  The cells of one batch are distinct (lae_sample_train_batch_weighted), so there is no race;
+ * a ray whose image is >= n_img or cell >= 16384 is skipped.  pred, gt [N,3] fp32. */
+LAE_API int lae_error_map_update(float* error_map, uint32_t n_img, uint32_t H, uint32_t W, const int64_t* inds, const int32_t* cells,
+                                 const float* pred, const float* gt, uint32_t N, void* stream);
 
 /* raymarching.cu:201-209  sph_from_ray(rays_o, rays_d, radius, N, coords[N,2]) */
 LAE_API int lae_sph_from_ray(const float* rays_o, const float* rays_d, float radius, uint32_t N,

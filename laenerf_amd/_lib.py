@@ -30,6 +30,9 @@ SIGNATURES = {
     "lae_march_rays_train_limit": [vp, vp, vp, f32, f32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_sample_train_batch": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, vp, f32, u64, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                vp, vp, vp],
+    "lae_sample_train_batch_weighted": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, vp, f32, u64, vp, i32, i32, vp, vp,
+                                        vp, vp, vp, vp, vp, vp, vp, vp],
+    "lae_error_map_update": [vp, u32, u32, u32, vp, vp, vp, vp, u32, vp],
     "lae_composite_rays_train_forward": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, vp],
     "lae_composite_rays_train_backward": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, vp, vp],
     "lae_composite_rays_train_forward_blend": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp],
@@ -120,7 +123,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi7"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi8"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

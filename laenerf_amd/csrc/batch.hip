@@ -55,19 +55,14 @@ __device__ __forceinline__ float texel(const void* __restrict__ images, size_t e
     return reinterpret_cast<const float*>(images)[e];
 }
 
+// the per-ray body shared by both samplers: ray and near / far of pixel `pix` of image `img`, the texel gather, the
+// background draw (words 2..4 of ray n) and the blend
 template <int DT>
-__global__ __launch_bounds__(256) void k_sample_train_batch(
-    const void* __restrict__ images, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
-    const float* __restrict__ poses, float fx, float fy, float cx, float cy, uint32_t N, const float* __restrict__ aabb,
-    float min_near, uint32_t k0, uint32_t k1, const int64_t* __restrict__ step_counter, int mode, int bg_mode, int linear,
-    float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears, float* __restrict__ fars,
-    float* __restrict__ gt, float* __restrict__ bg_out, int64_t* __restrict__ inds) {
-    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    const BatchRng rng{(uint32_t)(uint64_t)step_counter[0], k0, k1};
-    const uint64_t HW = (uint64_t)H * W;
-    const uint32_t pix = scale_u32(rng.u(n, 0), HW);                                 // < H * W
-    const uint32_t img = scale_u32(rng.u(mode == LAE_BATCH_IMAGE ? 0xFFFFFFFFu : n, 1), n_img);   // < n_img
+__device__ __forceinline__ void batch_ray(
+    const void* __restrict__ images, uint64_t HW, uint32_t W, uint32_t C, const float* __restrict__ poses, float fx, float fy,
+    float cx, float cy, const float* __restrict__ aabb, float min_near, const BatchRng& rng, uint32_t n, uint32_t img, uint32_t pix,
+    int bg_mode, int linear, float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears,
+    float* __restrict__ fars, float* __restrict__ gt, float* __restrict__ bg_out, int64_t* __restrict__ inds) {
     inds[n] = (int64_t)img * (int64_t)HW + pix;
 
     float o[3], d[3];
@@ -101,6 +96,180 @@ __global__ __launch_bounds__(256) void k_sample_train_batch(
     for (int c = 0; c < 3; c++) gt[3 * (size_t)n + c] = rgb[c];
 }
 
+template <int DT>
+__global__ __launch_bounds__(256) void k_sample_train_batch(
+    const void* __restrict__ images, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+    const float* __restrict__ poses, float fx, float fy, float cx, float cy, uint32_t N, const float* __restrict__ aabb,
+    float min_near, uint32_t k0, uint32_t k1, const int64_t* __restrict__ step_counter, int mode, int bg_mode, int linear,
+    float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears, float* __restrict__ fars,
+    float* __restrict__ gt, float* __restrict__ bg_out, int64_t* __restrict__ inds) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const BatchRng rng{(uint32_t)(uint64_t)step_counter[0], k0, k1};
+    const uint64_t HW = (uint64_t)H * W;
+    const uint32_t pix = scale_u32(rng.u(n, 0), HW);                                 // < H * W
+    const uint32_t img = scale_u32(rng.u(mode == LAE_BATCH_IMAGE ? 0xFFFFFFFFu : n, 1), n_img);   // < n_img
+    batch_ray<DT>(images, HW, W, C, poses, fx, fy, cx, cy, aabb, min_near, rng, n, img, pix, bg_mode, linear, rays_o, rays_d,
+                  nears, fars, gt, bg_out, inds);
+}
+
+// ---------------------------------------------------------------- the weighted draw (lae_sample_train_batch_weighted)
+constexpr uint32_t EM_SIDE = 128, EM_CELLS = EM_SIDE * EM_SIDE;      // the reference's 128 x 128 error map
+constexpr uint32_t SEL_THREADS = 1024, SEL_PER = EM_CELLS / SEL_THREADS;   // 16 consecutive cells per thread
+
+// -ln(u) for u = j * 2^-25, j odd in [1, 2^25) (u = ((v >> 8) + 0.5) * 2^-24): the rule of include/laenerf.h.  The reduction
+// u = m * 2^e, m = 1 + f in [sqrt(1/2), sqrt(2)) is done on the integer j, so f = (j - 2^p) * 2^-p is exact in fp32 (|j - 2^p| <
+// 2^24) even where u itself is not; then log1p(f) = f - f^2/2 + f^3 P(f) (a degree-8 minimax P, Cephes logf) and e * ln 2
+// in two parts, every operation one fp32 rounding in the stated order.
+__device__ __forceinline__ float neg_log_u(uint32_t j) {
+    int p = 32 - __clz(j);                                             // j in [2^(p-1), 2^p)
+    if (2ull * j * j < (1ull << (2 * p))) p -= 1;                      // j / 2^p < sqrt(1/2): one octave down
+    const float f = __fmul_rn((float)((int32_t)j - (int32_t)(1u << p)), __int_as_float((127 - p) << 23));
+    const float e = (float)(p - 25);
+    const float z = __fmul_rn(f, f);
+    float P = 7.0376836292e-2f;
+    P = __fadd_rn(__fmul_rn(P, f), -1.1514610310e-1f);
+    P = __fadd_rn(__fmul_rn(P, f), 1.1676998740e-1f);
+    P = __fadd_rn(__fmul_rn(P, f), -1.2420140846e-1f);
+    P = __fadd_rn(__fmul_rn(P, f), 1.4249322787e-1f);
+    P = __fadd_rn(__fmul_rn(P, f), -1.6668057665e-1f);
+    P = __fadd_rn(__fmul_rn(P, f), 2.0000714765e-1f);
+    P = __fadd_rn(__fmul_rn(P, f), -2.4999993993e-1f);
+    P = __fadd_rn(__fmul_rn(P, f), 3.3333331174e-1f);
+    float y = __fmul_rn(f, __fmul_rn(z, P));
+    y = __fadd_rn(y, __fmul_rn(e, -2.12194440e-4f));
+    y = __fadd_rn(y, __fmul_rn(-0.5f, z));
+    float r = __fadd_rn(f, y);
+    r = __fadd_rn(r, __fmul_rn(e, 0.693359375f));
+    return -r;
+}
+
+// the bit pattern of key = w / E (>= +0: a weight that is negative, NaN or infinite counts as 0)
+__device__ __forceinline__ uint32_t cell_key(float w, uint32_t step, uint32_t c, uint32_t k0, uint32_t k1) {
+    if (!(w > 0.0f) || !(w < INFINITY)) return 0u;
+    const uint32_t v = philox4x32_10_w0(step, c, 0u, 1u, k0, k1);
+    return __float_as_uint(__fdiv_rn(w, neg_log_u(((v >> 8) << 1) | 1u)));
+}
+
+// exclusive prefix sum over the 1024 threads of the block (wave64 shuffles, then the 16 wave totals through LDS)
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* __restrict__ s_wave, uint32_t& total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o, 64);
+        if (lane >= (uint32_t)o) x += y;
+    }
+    if (lane == 63) s_wave[wave] = x;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < SEL_THREADS / 64; w++) {
+        const uint32_t t = s_wave[w];
+        before += w < wave ? t : 0u;
+        all += t;
+    }
+    __syncthreads();                                                   // s_wave is reused by the next scan
+    total = all;
+    return before + x - v;
+}
+
+// the N largest keys of one image's map (4 passes of an 8-bit radix select for the N-th largest key T, then the keys > T
+// and the lowest-index keys == T), written in increasing cell order
+__global__ __launch_bounds__(SEL_THREADS) void k_select_cells(
+    const float* __restrict__ error_map, uint32_t n_img, uint32_t N, uint32_t k0, uint32_t k1,
+    const int64_t* __restrict__ step_counter, int32_t* __restrict__ cells_out) {
+    __shared__ uint32_t s_hist[256], s_wave[SEL_THREADS / 64], s_digit, s_rank;
+    const BatchRng rng{(uint32_t)(uint64_t)step_counter[0], k0, k1};
+    const uint32_t img = scale_u32(rng.u(0xFFFFFFFFu, 1), n_img);    // the uniform sampler's image rule
+    const float* __restrict__ row = error_map + (size_t)img * EM_CELLS;
+    const uint32_t t = threadIdx.x, c0 = t * SEL_PER;
+    uint32_t key[SEL_PER];
+#pragma unroll
+    for (uint32_t i = 0; i < SEL_PER; i++) key[i] = cell_key(row[c0 + i], rng.step, c0 + i, k0, k1);
+
+    uint32_t prefix = 0, rank = N;                                     // rank: the wanted key's 1-based rank among the matching keys
+#pragma unroll
+    for (int pass = 0; pass < 4; pass++) {
+        const int shift = 24 - 8 * pass;
+        const uint32_t hi_mask = pass == 0 ? 0u : 0xFFFFFFFFu << (shift + 8);
+        if (t < 256) s_hist[t] = 0;
+        __syncthreads();
+#pragma unroll
+        for (uint32_t i = 0; i < SEL_PER; i++)
+            if ((key[i] & hi_mask) == prefix) atomicAdd(&s_hist[(key[i] >> shift) & 255u], 1u);
+        __syncthreads();
+        // the digit d with (count of digits > d) < rank <= (count of digits >= d): thread t < 256 holds bin 255 - t, so its
+        // exclusive prefix sum is the count above that bin
+        const uint32_t h = t < 256 ? s_hist[255 - t] : 0u;
+        uint32_t total;
+        const uint32_t above = block_exclusive_scan(h, s_wave, total);
+        if (t < 256 && above < rank && rank <= above + h) { s_digit = 255 - t; s_rank = rank - above; }
+        __syncthreads();
+        prefix |= s_digit << shift;
+        rank = s_rank;
+        __syncthreads();
+    }
+    const uint32_t T = prefix;                                        // the N-th largest key; `rank` of the keys == T are taken
+    uint32_t gt = 0, eq = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < SEL_PER; i++) { gt += key[i] > T; eq += key[i] == T; }
+    uint32_t total;
+    const uint32_t eq_before = block_exclusive_scan(eq, s_wave, total);
+    const uint32_t take_eq = eq_before >= rank ? 0u : min(eq, rank - eq_before);
+    const uint32_t pos0 = block_exclusive_scan(gt + take_eq, s_wave, total);
+    uint32_t pos = pos0, ties = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < SEL_PER; i++) {
+        bool take = key[i] > T;
+        if (key[i] == T) { take = ties < take_eq; ties++; }
+        if (take && pos < N) cells_out[pos++] = (int32_t)(c0 + i);
+    }
+}
+
+// one thread per ray: the pixel drawn inside its cell, then the uniform sampler's per-ray body
+template <int DT>
+__global__ __launch_bounds__(256) void k_sample_train_batch_weighted(
+    const void* __restrict__ images, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+    const float* __restrict__ poses, float fx, float fy, float cx, float cy, uint32_t N, const float* __restrict__ aabb,
+    float min_near, uint32_t k0, uint32_t k1, const int64_t* __restrict__ step_counter, int bg_mode, int linear,
+    float sx, float sy, const int32_t* __restrict__ cells, float* __restrict__ rays_o, float* __restrict__ rays_d,
+    float* __restrict__ nears, float* __restrict__ fars, float* __restrict__ gt, float* __restrict__ bg_out,
+    int64_t* __restrict__ inds) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const BatchRng rng{(uint32_t)(uint64_t)step_counter[0], k0, k1};
+    const uint64_t HW = (uint64_t)H * W;
+    const uint32_t img = scale_u32(rng.u(0xFFFFFFFFu, 1), n_img);
+    const uint32_t c = (uint32_t)cells[n];
+    const float rx = (float)(rng.u(n, 0) >> 8) * 0x1p-24f, ry = (float)(rng.u(n, 5) >> 8) * 0x1p-24f;
+    const float fr = __fadd_rn(__fmul_rn((float)(c / EM_SIDE), sx), __fmul_rn(rx, sx));
+    const float fc = __fadd_rn(__fmul_rn((float)(c % EM_SIDE), sy), __fmul_rn(ry, sy));
+    const uint32_t r = min((uint32_t)fr, H - 1), col = min((uint32_t)fc, W - 1);    // trunc of a value >= 0
+    batch_ray<DT>(images, HW, W, C, poses, fx, fy, cx, cy, aabb, min_near, rng, n, img, r * W + col, bg_mode, linear, rays_o,
+                  rays_d, nears, fars, gt, bg_out, inds);
+}
+
+// one thread per ray: map[image][cell] = 0.1 * map + 0.9 * mean over RGB of (pred - gt)^2
+__global__ __launch_bounds__(256) void k_error_map_update(
+    float* __restrict__ error_map, uint32_t n_img, uint64_t HW, const int64_t* __restrict__ inds, const int32_t* __restrict__ cells,
+    const float* __restrict__ pred, const float* __restrict__ gt, uint32_t N) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float d = __fsub_rn(pred[3 * (size_t)n + k], gt[3 * (size_t)n + k]);
+        s = k == 0 ? __fmul_rn(d, d) : __fadd_rn(s, __fmul_rn(d, d));
+    }
+    const float err = __fdiv_rn(s, 3.0f);
+    const uint64_t img = (uint64_t)inds[n] / HW;
+    const uint32_t c = (uint32_t)cells[n];
+    if (img >= n_img || c >= EM_CELLS) return;                        // not a batch of this stack: nothing to update
+    float* m = error_map + (size_t)img * EM_CELLS + c;
+    *m = __fadd_rn(__fmul_rn(0.1f, *m), __fmul_rn(0.9f, err));
+}
+
 __global__ void k_advance_step(int64_t* __restrict__ step_counter) { step_counter[0] += 1; }
 
 }  // namespace
@@ -130,6 +299,44 @@ int lae_sample_train_batch(const void* images, int dtype, uint32_t n_img, uint32
 #undef LAE_BATCH_ARGS
     k_advance_step<<<1, 1, 0, s>>>(step_counter);
     return lae::check_launch("sample_train_batch");
+}
+
+int lae_sample_train_batch_weighted(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                                    const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
+                                    const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int bg_mode,
+                                    int srgb_to_linear, const float* error_map, int32_t* cells_out, float* rays_o, float* rays_d,
+                                    float* nears, float* fars, float* gt, float* bg_out, int64_t* inds, void* stream) {
+    if (N == 0) return LAE_OK;
+    if (!images || !poses || !aabb || !step_counter || !error_map || !cells_out || !rays_o || !rays_d || !nears || !fars || !gt ||
+        !inds) return LAE_ENULL;
+    if (bg_mode == LAE_BG_RANDOM && !bg_out) return LAE_ENULL;
+    if (N > EM_CELLS) return LAE_EINVAL;
+    if (n_img == 0 || H == 0 || W == 0 || (C != 3 && C != 4) || (uint64_t)H * W > 0xFFFFFFFFull) return LAE_EINVAL;
+    if (dtype != LAE_IMG_U8 && dtype != LAE_IMG_F16 && dtype != LAE_IMG_F32) return LAE_EINVAL;
+    if (bg_mode != LAE_BG_WHITE && bg_mode != LAE_BG_RANDOM) return LAE_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const float sx = (float)((double)H / EM_SIDE), sy = (float)((double)W / EM_SIDE);
+    k_select_cells<<<1, SEL_THREADS, 0, s>>>(error_map, n_img, N, k0, k1, step_counter, cells_out);
+    const dim3 grid(lae::cdiv(N, 256)), block(256);
+#define LAE_BATCH_ARGS images, n_img, H, W, C, poses, fx, fy, cx, cy, N, aabb, min_near, k0, k1, step_counter, bg_mode, \
+                       srgb_to_linear, sx, sy, cells_out, rays_o, rays_d, nears, fars, gt, bg_out, inds
+    if (dtype == LAE_IMG_U8) k_sample_train_batch_weighted<LAE_IMG_U8><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+    else if (dtype == LAE_IMG_F16) k_sample_train_batch_weighted<LAE_IMG_F16><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+    else k_sample_train_batch_weighted<LAE_IMG_F32><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+#undef LAE_BATCH_ARGS
+    k_advance_step<<<1, 1, 0, s>>>(step_counter);
+    return lae::check_launch("sample_train_batch_weighted");
+}
+
+int lae_error_map_update(float* error_map, uint32_t n_img, uint32_t H, uint32_t W, const int64_t* inds, const int32_t* cells,
+                         const float* pred, const float* gt, uint32_t N, void* stream) {
+    if (N == 0) return LAE_OK;
+    if (!error_map || !inds || !cells || !pred || !gt) return LAE_ENULL;
+    if (n_img == 0 || H == 0 || W == 0 || N > EM_CELLS) return LAE_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    k_error_map_update<<<lae::cdiv(N, 256), 256, 0, s>>>(error_map, n_img, (uint64_t)H * W, inds, cells, pred, gt, N);
+    return lae::check_launch("error_map_update");
 }
 
 }  // extern "C"

@@ -10,6 +10,11 @@ the seed, counter (step, ray, word, 0)); `philox4x32_10` / `draw_indices` below 
 
 Deviation: the reference shuffles the image order once per epoch; here the image of a batch (mode 'image', the
 reference's batch_size = 1) or of every ray (mode 'all', as instant-ngp) is drawn i.i.d.
+
+With an error map (`error_map=True` / `enable_error_map`: the reference's --error_map and LAENeRF's --use_error_maps) the
+pixels of a batch are drawn by 128 x 128 cell weights per image (`lae_sample_train_batch_weighted`: torch.multinomial's
+without-replacement algorithm, then a uniform pixel inside each cell), and `update_error_map` writes the per-ray error back
+(`lae_error_map_update`).  `draw_cells`, `cell_pixels` and `ema_update` restate both rules in numpy.
 """
 import json
 import math
@@ -21,11 +26,14 @@ import torch
 from . import _lib
 from ._lib import check, ptr, stream
 
-__all__ = ["ResidentImages", "nerf_matrix_to_ngp", "philox4x32_10", "draw_indices", "draw_background"]
+__all__ = ["ResidentImages", "nerf_matrix_to_ngp", "philox4x32_10", "draw_indices", "draw_background", "neg_log_u", "cell_keys",
+           "draw_cells", "cell_pixels", "cell_span", "ema_update", "ERROR_MAP_CELLS"]
 
 _DTYPES = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
 _MODES = {"image": 0, "all": 1}
 _BGS = {"white": 0, "random": 1}
+ERROR_MAP_SIDE = 128
+ERROR_MAP_CELLS = ERROR_MAP_SIDE * ERROR_MAP_SIDE     # the reference's 128 x 128 error map per image
 
 
 def nerf_matrix_to_ngp(pose, scale=0.33, offset=(0, 0, 0)):
@@ -57,9 +65,10 @@ def philox4x32_10(ctr, key):
     return np.stack([x.astype(np.uint32) for x in c], axis=-1)
 
 
-def _u32(seed, step, ray, word):
+def _u32(seed, step, ray, word, w3=0):
     ray = np.asarray(ray, dtype=np.uint64)
-    ctr = np.stack(np.broadcast_arrays(np.uint64(step & 0xFFFFFFFF), ray, np.uint64(word), np.uint64(0)), axis=-1)
+    step = np.asarray(step, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    ctr = np.stack(np.broadcast_arrays(step, ray, np.uint64(word), np.uint64(w3)), axis=-1)
     key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint64)
     return philox4x32_10(ctr.astype(np.uint32), key.astype(np.uint32))[..., 0]
 
@@ -84,6 +93,95 @@ def draw_background(seed, step, n_rays):
                      for c in range(3)], axis=-1)
 
 
+# ---------------------------------------------------------------------------------------------------------------- error map
+_LOG_P = [7.0376836292e-2, -1.1514610310e-1, 1.1676998740e-1, -1.2420140846e-1, 1.4249322787e-1, -1.6668057665e-1,
+          2.0000714765e-1, -2.4999993993e-1, 3.3333331174e-1]
+
+
+def neg_log_u(j):
+    """-ln(j * 2^-25) for odd j in [1, 2^25) (uint32 array) -> float32: the kernel's logarithm (include/laenerf.h), every
+    step one fp32 rounding in the kernel's order"""
+    j = np.asarray(j, dtype=np.int64)
+    p = np.zeros(j.shape, np.int64)
+    for b in range(26):                                                   # bit length
+        p = np.where(j >> b != 0, b + 1, p)
+    p = np.where(2 * j * j < (np.int64(1) << (2 * p)), p - 1, p)
+    f32 = np.float32
+    f = (j - (np.int64(1) << p)).astype(f32) * np.ldexp(f32(1), -p).astype(f32)
+    e = (p - 25).astype(f32)
+    z = f * f
+    P = np.full(j.shape, f32(_LOG_P[0]), f32)
+    for c in _LOG_P[1:]:
+        P = P * f + f32(c)
+    y = f * (z * P)
+    y = y + e * f32(-2.12194440e-4)
+    y = y + f32(-0.5) * z
+    r = f + y
+    r = r + e * f32(0.693359375)
+    return -r
+
+
+def cell_keys(seed, step, weights):
+    """the kernel's keys w / E of one map row [16384] -> uint32 bit patterns (a weight that is negative, NaN or infinite: 0).
+    `step` may be an array [S, 1] (-> keys [S, n cells]); a shorter row restates the rule on its first cells."""
+    w = np.asarray(weights, dtype=np.float32).reshape(-1)
+    c = np.arange(w.size, dtype=np.uint64)
+    v = _u32(seed, step, c, 0, 1)
+    E = neg_log_u(((v >> np.uint32(8)).astype(np.int64) << 1) | 1)
+    ok = (w > 0) & np.isfinite(w)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        key = np.where(ok, np.where(ok, w, np.float32(0)) / E, np.float32(0)).astype(np.float32)
+    return key.view(np.uint32)
+
+
+def draw_cells(seed, step, weights, n):
+    """numpy restatement of the weighted draw's cells: the n largest keys (as uint32; ties to the lower cell), in increasing
+    cell order -> int64 [n] (or [S, n] for steps [S, 1])"""
+    key = cell_keys(seed, step, weights).astype(np.int64)
+    idx = np.broadcast_to(np.arange(key.shape[-1]), key.shape)
+    order = np.lexsort((idx, -key), axis=-1)                              # key descending, then cell ascending
+    return np.sort(order[..., :n], axis=-1).astype(np.int64)
+
+
+def _cell_rows_cols(cells, rx, ry, H, W):
+    f32 = np.float32
+    sx, sy = f32(H / ERROR_MAP_SIDE), f32(W / ERROR_MAP_SIDE)
+    cells = np.asarray(cells, dtype=np.int64)
+    cx, cy = (cells // ERROR_MAP_SIDE).astype(f32), (cells % ERROR_MAP_SIDE).astype(f32)
+    row = np.minimum((cx * sx + f32(rx) * sx).astype(np.int64), H - 1)    # astype(int64) truncates
+    col = np.minimum((cy * sy + f32(ry) * sy).astype(np.int64), W - 1)
+    return row, col
+
+
+def cell_pixels(seed, step, cells, H, W):
+    """numpy restatement of the pixel drawn in cell cells[n] by ray n -> flat pixel index row * W + col, int64 [N]"""
+    rays = np.arange(len(cells), dtype=np.uint64)
+    two24 = np.float32(2.0 ** -24)
+    rx = (_u32(seed, step, rays, 0) >> np.uint32(8)).astype(np.float32) * two24
+    ry = (_u32(seed, step, rays, 5) >> np.uint32(8)).astype(np.float32) * two24
+    row, col = _cell_rows_cols(cells, rx, ry, H, W)
+    return row * W + col
+
+
+def cell_span(cells, H, W):
+    """the pixels the rule can give in each cell: (row_lo, row_hi, col_lo, col_hi), inclusive (the rule is monotone in rx, ry)"""
+    lo = _cell_rows_cols(cells, np.float32(0), np.float32(0), H, W)
+    hi = _cell_rows_cols(cells, np.float32(1 - 2.0 ** -24), np.float32(1 - 2.0 ** -24), H, W)
+    return lo[0], hi[0], lo[1], hi[1]
+
+
+def ema_update(error_map, inds, cells, pred, gt, H, W):
+    """numpy restatement of lae_error_map_update on a copy of error_map [n_img, 16384] -> the updated map"""
+    out = np.array(error_map, dtype=np.float32, copy=True)
+    f32 = np.float32
+    d = np.asarray(pred, f32) - np.asarray(gt, f32)
+    err = ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]) / f32(3)
+    img = np.asarray(inds, np.int64) // (H * W)
+    c = np.asarray(cells, np.int64)
+    out[img, c] = f32(0.1) * out[img, c] + f32(0.9) * err
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- images
 class ResidentImages:
     """images [n, H, W, C] (C = 3 or 4; uint8, fp16 or fp32) + cam2world poses [n, 4, 4] + one (fx, fy, cx, cy), on the GPU.
@@ -92,7 +190,7 @@ class ResidentImages:
     C = 3); default by C.  color_space 'linear' converts the colour to linear before the blend (nerf/utils.py:564)."""
 
     def __init__(self, images, poses, intrinsics, bound=1.0, min_near=0.2, mode="image", bg=None, color_space="srgb", seed=0,
-                 device=None):
+                 device=None, error_map=False):
         device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         # (device="cpu" holds the arrays on the host -- loaders and tests without a GPU; sample() needs the GPU)
         images = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))
@@ -118,6 +216,19 @@ class ResidentImages:
         self.mode, self.bg, self.color_space, self.seed = mode, bg, color_space, int(seed) & 0xFFFFFFFFFFFFFFFF
         self.step = torch.zeros(1, dtype=torch.int64, device=device)          # the kernel's step counter
         self._out = {}
+        self.error_map = None
+        if error_map:
+            self.enable_error_map()
+
+    def enable_error_map(self, init=1.0):
+        """create .error_map: [n_img, 16384] fp32 cell weights, every one `init` (the reference's torch.ones).  From then on
+        sample() draws its pixels by these weights (mode 'image' only) and returns the cells it drew; the caller may write
+        rows (LAENeRF's --use_error_maps seeds them from edit-grid weights)."""
+        if self.mode != "image":
+            raise ValueError("ResidentImages: an error map needs mode 'image' (one image per batch, as the reference)")
+        self.error_map = torch.full((self.n_img, ERROR_MAP_CELLS), float(init), dtype=torch.float32, device=self.images.device)
+        self._out = {}
+        return self.error_map
 
     @classmethod
     def from_arrays(cls, images, poses, intrinsics, **kw):
@@ -186,6 +297,8 @@ class ResidentImages:
                 "gt": torch.empty(n, 3, dtype=torch.float32, device=dev), "inds": torch.empty(n, dtype=torch.int64, device=dev),
                 "bg": torch.empty(n, 3, dtype=torch.float32, device=dev) if self.bg == "random" else None,
             }
+            if self.error_map is not None:
+                out["cells"] = torch.empty(n, dtype=torch.int32, device=dev)
         return out
 
     @torch.no_grad()
@@ -194,6 +307,8 @@ class ResidentImages:
         number 1 ('white'), inds [N] (image * H * W + pixel).  step=None: the device counter's value, which the call then
         advances (capturable); step=k: the counter is set to k first.  The result tensors are reused by the next call with
         the same n_rays unless `out` (a dict of tensors from an earlier call) is passed."""
+        if self.error_map is not None:
+            return self._sample_weighted(n_rays, step, out)
         _lib.need_cuda(self.images)
         if step is not None:
             self.step.fill_(int(step))
@@ -208,6 +323,52 @@ class ResidentImages:
         if res["bg"] is None:
             res["bg"] = 1
         return res
+
+    def _check_error_map(self, n_rays):
+        if self.mode != "image":
+            raise ValueError("ResidentImages: an error map needs mode 'image' (one image per batch, as the reference)")
+        if not 0 < int(n_rays) <= ERROR_MAP_CELLS:
+            raise ValueError(f"ResidentImages: with an error map n_rays must be in 1..{ERROR_MAP_CELLS} (cells drawn without replacement)")
+        m = self.error_map
+        if not torch.is_tensor(m) or m.shape != (self.n_img, ERROR_MAP_CELLS) or m.dtype != torch.float32 or not m.is_contiguous():
+            raise ValueError(f"ResidentImages: error_map must be a contiguous float32 [{self.n_img}, {ERROR_MAP_CELLS}] tensor")
+        if m.device != self.images.device:
+            raise ValueError("ResidentImages: error_map must live on the images' device")
+
+    def _sample_weighted(self, n_rays, step, out):
+        """sample() with an error map: lae_sample_train_batch_weighted; the result also holds cells [N] int32"""
+        self._check_error_map(n_rays)
+        _lib.need_cuda(self.images)
+        if step is not None:
+            self.step.fill_(int(step))
+        o = out if out is not None else self._buffers(int(n_rays))
+        fx, fy, cx, cy = self.intrinsics
+        check(_lib.load().lae_sample_train_batch_weighted(
+            ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self.poses), fx, fy, cx, cy,
+            int(n_rays), ptr(self.aabb), self.min_near, self.seed, ptr(self.step), _BGS[self.bg], int(self.color_space == "linear"),
+            ptr(self.error_map), ptr(o["cells"]), ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]),
+            ptr(o["bg"]), ptr(o["inds"]), stream()), "sample_train_batch_weighted")
+        res = dict(o)
+        if res["bg"] is None:
+            res["bg"] = 1
+        return res
+
+    @torch.no_grad()
+    def update_error_map(self, pred, batch):
+        """the reference's EMA after a step (nerf/utils.py:609-631): map[image][cell] = 0.1 * map + 0.9 * mean over RGB of
+        (pred - gt)^2 for every ray of `batch` (a result of sample() with the map); pred [N,3] is the step's image"""
+        if self.error_map is None:
+            raise ValueError("ResidentImages.update_error_map: no error map (error_map=True or enable_error_map())")
+        cells, inds, gt = batch["cells"], batch["inds"], batch["gt"]
+        n = int(cells.shape[0])
+        pred = pred.detach().reshape(-1, 3)
+        if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.shape[0] != n:
+            pred = pred.float().contiguous()
+        if pred.shape[0] != n:
+            raise ValueError("ResidentImages.update_error_map: pred must be [N, 3] for the batch's N rays")
+        _lib.need_cuda(self.error_map, pred, gt)
+        check(_lib.load().lae_error_map_update(ptr(self.error_map), self.n_img, self.H, self.W, ptr(inds), ptr(cells), ptr(pred),
+                                               ptr(gt), n, stream()), "error_map_update")
 
     def view_rays(self, i):
         """every pixel of image i (scanline order) -> rays_o, rays_d [H*W, 3] and its colour [H*W, C] as fp32 on the device"""

@@ -15,6 +15,12 @@ What makes a group capturable although the reference changes two host values in 
     host, cast to fp32: the bits FusedAdam.set_lr writes) and each step copies its row into FusedAdam.lrs on the device.
 The first 16 steps run eagerly (mean_count = 0: the march sizes its buffers from a host read, as in the reference).
 The graphs share one memory pool: they never run concurrently.
+
+error_map='ema' is the reference's --error_map: the batch is drawn by the data's per-image error map
+(ResidentImages.sample with a map) and the step's per-ray error is written back into it (ResidentImages.update_error_map)
+after the compositing, as train_step does (nerf/utils.py:609-631).  'fixed' is LAENeRF's --use_error_maps: the same draw
+from a map the caller seeded, never updated.  Both kernels read and write only device memory, so they run inside the
+captured group like the rest of the step.
 """
 import math
 
@@ -60,16 +66,23 @@ class Trainer:
     learning rates are taken over: device_lr is switched on), `data` a ResidentImages, `iters` the decay horizon of the
     learning rate, `lr` its start value (one number for every parameter group, or one per group).
     graph=False runs the same steps eagerly; capacity 'bucket' / 'exact' (see the module docstring).
+    error_map: None (uniform pixels), 'ema' (drawn by the data's error map, updated after every step) or 'fixed' (drawn by
+    it, never updated); a map of ones is created on the data when it has none.
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
     def __init__(self, renderer, optimizer, data, iters, lr, num_rays=4096, seed=0, graph=True, capacity="bucket",
-                 max_steps=1024, dt_gamma=0.0):
+                 max_steps=1024, dt_gamma=0.0, error_map=None):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
+        if error_map not in (None, "ema", "fixed"):
+            raise ValueError("Trainer: error_map must be None, 'ema' or 'fixed'")
+        if error_map is not None and data.error_map is None:
+            data.enable_error_map()
         self.r, self.opt, self.data = renderer, optimizer, data
         self.iters, self.num_rays, self.graph, self.capacity = int(iters), int(num_rays), bool(graph), capacity
         self.max_steps, self.dt_gamma = int(max_steps), float(dt_gamma)
+        self.error_map = error_map
         dev = renderer.density_grid.device
         data.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         data.aabb = renderer.aabb_train.to(dev, torch.float32).contiguous()      # the batch's near / far = the march's
@@ -117,6 +130,8 @@ class Trainer:
             if not torch.cuda.is_current_stream_capturing():
                 self._rows_seen = max(self._rows_seen, xyzs.shape[0])
             res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt)
+        if self.error_map == "ema":
+            self.data.update_error_map(res["image"], b)
         loss = res["loss"]
         opt.backward(loss)
         opt.step()
