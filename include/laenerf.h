@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi8"
+#define LAE_ABI_TAG "abi9"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -579,6 +579,53 @@ LAE_API uint64_t lae_palette_backward_scratch_bytes(uint32_t M);
 LAE_API int lae_palette_backward(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask,
                          uint32_t M, const void* g_pred, const float* g_w, const void* g_o, void* g_w_logits, void* g_o_raw,
                          float* g_palette, void* scratch, void* stream);
+
+/* ---- recolored views of a trained palette network (nerf/utils.py:1230-1386 test_gui_styleenc / val_gui_styleenc,
+ * nerf/gui.py:659-714 eval_style_predictor: torch ops and a host nonzero() in the reference) ----
+ * A view is prepared once per pose (edit-grid render, compaction, the two MLPs) and recolored by one compose launch per edit:
+ * what the network predicts at a pixel depends on the pose only, the palette edits only on the recomposition.
+ *
+ * lae_recolor_compact: depth, weights_sum [N] of an edit-grid render (scale_depth off), rays_o, rays_d [N,3] fp32.
+ *   d = depth with NaN -> 0; pixel i is an edit pixel when d != 0 (d.flatten().nonzero(), utils.py:1268-1273).
+ *   indices [N cap] int32: the edit pixels in ascending order; slot_map [N] int32: i's slot in that list, or -1;
+ *   x_term [round_up(N,16) cap, 3] = rays_o + d * rays_d (a multiply, then an add: two roundings, torch's two elementwise
+ *   kernels bit for bit); dirs [round_up(N,16) cap, 3] = rays_d; alpha [N cap] = weights_sum (the reference's pred_t);
+ *   *count (device int32) = K.  Rows K .. round_up(K, 16) - 1 of x_term and dirs are zero (the MLPs take multiples of 16 rows).
+ *   Stable compaction: per-block counts, a one-block scan, a scatter.  scratch: lae_recolor_compact_scratch_bytes(N).
+ *
+ * lae_recolor_compose: one thread per pixel.  w_logits [K_pad, >= P] fp16 (row stride w_stride) and o_raw [K_pad, >= 3] fp16
+ *   (row stride o_stride): the weight / offset nets' outputs for the compacted rows (LAENeRF._logits); active_mask bit j =
+ *   base j active, n_active = popcount; palette [n_active, 3], p_weights, p_bias [n_active], alpha [K], bg [3]: fp32 DEVICE
+ *   arrays (no host scalar changes with an edit: a captured launch replays new values); base [N,3] the render's image.
+ *   Per edit pixel (slot s): t = alpha[s], u = 1 - t; w = softmax over the active logits (e_j = exp(l_j - max): fp32
+ *   difference, exp in double rounded once to fp32; sum in column order; w_j = e_j / sum); o = the first 3 columns of o_raw
+ *   (raw as get_offsets returns them, style_encoder.py:98-109, or tanh(o) with LAE_RECOLOR_TANH: then identity edits give
+ *   LAENeRF.forward); w @ pal summed in column order.  Every operation one fp32 rounding, no contraction.
+ *   LAE_RECOLOR_PREVIEW (utils.py:1290-1302, 1310-1311): w'_j = max(p_bias_j + p_weights_j * w_j, 0), w' /= sum(w'),
+ *     out = clamp(o + w' @ pal, 0, 1) + u * bg;  with LAE_RECOLOR_NO_OFFSETS (:1303-1308): clamp(w @ pal, 0, 1) + u * bg
+ *     (p_weights / p_bias unused, as in the reference).  Other pixels: base.
+ *   LAE_RECOLOR_WEIGHTS (:1275-1281): w_k (k-th ACTIVE base) in all three channels + u * bg.  Other pixels: base.
+ *   LAE_RECOLOR_OFFSETS (:1282-1286): o * 0.5 + 0.5 + u * bg.  Other pixels: base.
+ *   LAE_RECOLOR_EVAL (gui.py:708-714): clamp(w @ pal + o, 0, 1) * t + bg * u (no edit weights; NO_OFFSETS ignored).
+ *     Other pixels: bg.
+ *   Deviations from the reference: it computes the palette product and the sums in fp16 under autocast, here they are fp32;
+ *   where sum(w') = 0 (an edit that clamps every weight away) it divides 0 / 0 and shows NaN, here the weights count as zero.
+ *   out [N,3] fp32; out_u8 [N,3] (may be NULL) = torch's (out * 255).byte(): the fp32 product, truncated to int64, low byte
+ *   (NaN -> 0).  k >= n_active in LAE_RECOLOR_WEIGHTS, P outside 1..16 or no active base: LAE_EINVAL. */
+#define LAE_RECOLOR_PREVIEW 0
+#define LAE_RECOLOR_WEIGHTS 1
+#define LAE_RECOLOR_OFFSETS 2
+#define LAE_RECOLOR_EVAL 3
+#define LAE_RECOLOR_NO_OFFSETS 1
+#define LAE_RECOLOR_TANH 2
+LAE_API uint64_t lae_recolor_compact_scratch_bytes(uint32_t N);
+LAE_API int lae_recolor_compact(const float* depth, const float* weights_sum, const float* rays_o, const float* rays_d, uint32_t N,
+                                int32_t* indices, int32_t* slot_map, float* x_term, float* dirs, float* alpha, int32_t* count,
+                                void* scratch, void* stream);
+LAE_API int lae_recolor_compose(const int32_t* slot_map, uint32_t N, const void* w_logits, uint32_t w_stride, const void* o_raw,
+                                uint32_t o_stride, uint32_t P, uint32_t active_mask, const float* palette, const float* p_weights,
+                                const float* p_bias, const float* alpha, const float* base, const float* bg, int mode, uint32_t k,
+                                int flags, float* out, uint8_t* out_u8, void* stream);
 
 /* The point-wise losses of train_LAENeRF_step (nerf/utils.py:990-996; style_encoder.py:183-205) fused behind the
  * recomposition: loss = MSE(pred, target) + w_uniform * max_j sum_i w_hat[i,j] + w_non_uniform * sum_i (1 - max_j w_hat[i,j])

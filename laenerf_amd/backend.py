@@ -796,6 +796,39 @@ class _Style:
                                           int(reg_w is not None) | (2 if accumulate else 0), float(reg_w[0]) if reg_w else 0.0, float(reg_w[1]) if reg_w else 0.0,
                                           stream()), "style_loss_backward")
 
+    @staticmethod
+    def recolor_compact(depth, weights_sum, rays_o, rays_d, N, indices, slot_map, x_term, dirs, alpha, count):
+        """edit pixels of an edit-grid render (d != 0 after NaN -> 0) and their palette-network inputs (include/laenerf.h)"""
+        ts = (depth, weights_sum, rays_o, rays_d, indices, slot_map, x_term, dirs, alpha, count)
+        need_cuda(*ts); need_contig(*ts)
+        _need_f32(depth, weights_sum, rays_o, rays_d, x_term, dirs, alpha)
+        if any(t.dtype != torch.int32 for t in (indices, slot_map, count)):
+            raise RuntimeError("recolor_compact: indices / slot_map / count int32")
+        Np = (N + 15) // 16 * 16
+        if depth.numel() < N or weights_sum.numel() < N or rays_o.numel() < 3 * N or rays_d.numel() < 3 * N or indices.numel() < N \
+                or slot_map.numel() < N or alpha.numel() < N or x_term.numel() < 3 * Np or dirs.numel() < 3 * Np:
+            raise RuntimeError("recolor_compact: a buffer is smaller than the view (x_term / dirs: round_up(N, 16) rows)")
+        lib = _lib.load()
+        ws = _workspace(depth.device, lib.lae_recolor_compact_scratch_bytes(N))
+        check(lib.lae_recolor_compact(ptr(depth), ptr(weights_sum), ptr(rays_o), ptr(rays_d), N, ptr(indices), ptr(slot_map), ptr(x_term),
+                                      ptr(dirs), ptr(alpha), ptr(count), ptr(ws), stream()), "recolor_compact")
+
+    @staticmethod
+    def recolor_compose(slot_map, N, w_logits, o_raw, P, active_mask, palette, p_weights, p_bias, alpha, base, bg, mode, k, flags, out,
+                        out_u8=None):
+        """one launch per palette edit: softmax, edit and recomposition of every pixel (include/laenerf.h lae_recolor_compose)"""
+        ts = (slot_map, w_logits, o_raw, palette, p_weights, p_bias, alpha, base, bg, out, out_u8)
+        need_cuda(*ts); need_contig(*ts)
+        if w_logits.dtype != _F16 or o_raw.dtype != _F16 or slot_map.dtype != torch.int32 or (out_u8 is not None and out_u8.dtype != torch.uint8):
+            raise RuntimeError("recolor_compose: logits / offsets float16, slot_map int32, out_u8 uint8")
+        _need_f32(*(t for t in (palette, p_weights, p_bias, alpha, base, bg, out) if t is not None))
+        if slot_map.numel() < N or out.numel() < 3 * N or (base is not None and base.numel() < 3 * N) or \
+                (out_u8 is not None and out_u8.numel() < 3 * N) or bg.numel() < 3:
+            raise RuntimeError("recolor_compose: a buffer is smaller than the view")
+        check(_lib.load().lae_recolor_compose(ptr(slot_map), N, ptr(w_logits), w_logits.shape[1], ptr(o_raw), o_raw.shape[1], P, active_mask,
+                                              ptr(palette), ptr(p_weights), ptr(p_bias), ptr(alpha), ptr(base), ptr(bg), int(mode), int(k),
+                                              int(flags), ptr(out), ptr(out_u8), stream()), "recolor_compose")
+
 
 style_backend = _Style
 
