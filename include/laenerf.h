@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi9"
+#define LAE_ABI_TAG "abi10"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -647,6 +647,44 @@ LAE_API int lae_style_loss_backward(const void* w_logits, const void* o_raw, con
                             uint32_t M, const float* target, const float* fin, const float* upstream, float w_uniform,
                             float w_non_uniform, float c_offset, void* g_w_logits, void* g_o_raw, float* g_palette, void* scratch,
                             int flags, float w_valid, float w_distinct, void* stream);
+
+/* The fused criterion with a DEVICE row count (the palette network's training on views of any size K, laenerf_amd.editing.
+ * StyleTrainer): the same two launches each way, on buffers of `cap` rows (the host size every array is allocated for; a
+ * multiple of 16 for the MLPs) of which the first M = min(*m_dev, cap) are live.  *m_dev >= 1 (M = 0 gives a NaN mean).
+ *   - rows >= M are excluded from every sum: the MSE mean divides by 3 M, the per-column sums whose maximum is the uniform term,
+ *     the non-uniform sum and the offset sum see only rows < M;
+ *   - rows >= M get exactly zero g_w_logits / g_o_raw rows and add nothing to the palette gradient;
+ *   - the partials of workgroups past cdiv(M, 256) are zeros, and the final reductions read only the first cdiv(M, 256) of
+ *     them, in the order of the exact-size call: fin[] and g_palette are the bits of lae_style_loss_forward / _backward called
+ *     with M rows on the same first M rows.
+ * lae_palette_forward is called with the capacity (its rows are independent); scratch as above with M = cap. */
+LAE_API int lae_style_loss_forward_dev(const void* pred, const float* target, const float* w_hat, const void* o_hat, uint32_t cap,
+                               const uint32_t* m_dev, uint32_t n_active, float w_uniform, float w_non_uniform, float c_offset,
+                               const float* scale, float* fin, void* scratch, const float* reg_palette, uint32_t reg_P, float w_valid,
+                               float w_distinct, void* stream);
+LAE_API int lae_style_loss_backward_dev(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask,
+                                uint32_t cap, const uint32_t* m_dev, const float* target, const float* fin, const float* upstream,
+                                float w_uniform, float w_non_uniform, float c_offset, void* g_w_logits, void* g_o_raw, float* g_palette,
+                                void* scratch, int flags, float w_valid, float w_distinct, void* stream);
+
+/* One training view of the palette network from a device-resident edit set (EditDataset.collate, editing/edit_dataset.py:289-300,
+ * laenerf_amd.editing.EditSet.sample).  The set: V views packed as x_term, dirs, targets [sum K, 3] fp32, view v's rows at
+ * offsets[v] (int64) .. offsets[v] + counts[v] (int32, >= 1), depth_factor [V] fp32 (the view's (d.max() - d.min()) / num_steps).
+ *   step = *step_counter (int64, device), read at the start; v = schedule[step mod n_sched] (int32, 0 <= v < V; values out of range
+ *   are clamped, the caller validates); K = min(counts[v], cap); *m_dev = K (uint32).
+ *   jitter of row r < K: w = word 0 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ *     (step & 0xffffffff, r, 0, 2) (counter word 3 = 2: apart from lae_sample_train_batch's (.., 0) and the error map's (.., 1));
+ *     u = (w >> 8) * 2^-24 (exact, in [0, 1 - 2^-24]);  t = fp32(fp32(u - 0.5) * depth_factor[v]);
+ *     x[r][c] = fp32(x_term[o + r][c] + fp32(t * dirs[o + r][c]))   (o = offsets[v]; multiply then add, no contraction: the
+ *     roundings of torch's `x_term + d_[..., None] * dirs`);  d[r] = dirs[o + r], target[r] = targets[o + r] (copies).
+ *   rows K..cap-1: copies of row K - 1 after its jitter (the same hash-table lines; the losses skip them through m_dev).
+ *   Deviation: the reference draws the jitter with torch.rand on the device (another generator): the law is the same, U[0, 1)
+ *   in 2^-24 steps, the bits are not.
+ * x, d, target [cap, 3] fp32, 16-byte aligned; cap a multiple of 4 (else LAE_EINVAL).  A second one-thread launch adds 1 to
+ * *step_counter after the draw: a replayed graph draws the next step's view. */
+LAE_API int lae_sample_edit_view(const float* x_term, const float* dirs, const float* targets, const int64_t* offsets, const int32_t* counts,
+                         const float* depth_factor, uint32_t V, const int32_t* schedule, uint32_t n_sched, uint32_t cap, uint64_t seed,
+                         int64_t* step_counter, float* x, float* d, float* target, uint32_t* m_dev, void* stream);
 
 /* ---- LAENeRF input assembly (editing/style_encoder.py:135-146: encoder rows, SH(3) of the directions, cast, pad, cat -- torch ops
  * and separate launches in the reference) ----

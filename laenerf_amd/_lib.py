@@ -91,6 +91,9 @@ SIGNATURES = {
     "lae_style_loss_scratch_bytes": [u32],
     "lae_style_loss_forward": [vp, vp, vp, vp, u32, u32, f32, f32, f32, vp, vp, vp, vp, u32, f32, f32, vp],
     "lae_style_loss_backward": [vp, vp, vp, u32, u32, u32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, i32, f32, f32, vp],
+    "lae_style_loss_forward_dev": [vp, vp, vp, vp, u32, vp, u32, f32, f32, f32, vp, vp, vp, vp, u32, f32, f32, vp],
+    "lae_style_loss_backward_dev": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, i32, f32, f32, vp],
+    "lae_sample_edit_view": [vp, vp, vp, vp, vp, vp, u32, vp, u32, u32, u64, vp, vp, vp, vp, vp, vp],
     "lae_grow_region": [vp, vp, u32, u32, f32, vp, u32, vp, u32, u32, vp],
     "lae_style_assemble_forward": [vp, vp, u32, u32, u32, vp, vp, u32, vp],
     "lae_style_assemble_backward": [vp, vp, u32, u32, vp, vp],
@@ -127,7 +130,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi9"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi10"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

@@ -772,29 +772,51 @@ class _Style:
         check(_lib.load().lae_style_assemble_backward(ptr(g_feat), ptr(g_off), M, off_cols, ptr(grad_lm), stream()), "style_assemble_backward")
 
     @staticmethod
-    def style_loss_forward(pred, target, w_hat, o_hat, M, n_active, lw, scale, fin, reg_palette=None, reg_w=(0.0, 0.0)):
-        """reg_palette [P,3] fp32 + reg_w = (palette_loss_valid, palette_loss_distinct): `palet_loss` joins the criterion (include/laenerf.h)"""
-        ts = (pred, target, w_hat, o_hat, scale, fin, reg_palette)
+    def style_loss_forward(pred, target, w_hat, o_hat, M, n_active, lw, scale, fin, reg_palette=None, reg_w=(0.0, 0.0), m_dev=None):
+        """reg_palette [P,3] fp32 + reg_w = (palette_loss_valid, palette_loss_distinct): `palet_loss` joins the criterion (include/laenerf.h).
+        m_dev (a 1-element int32 / uint32 device tensor): M is the buffers' capacity and *m_dev the live rows (lae_style_loss_forward_dev)"""
+        ts = (pred, target, w_hat, o_hat, scale, fin, reg_palette, m_dev)
         need_cuda(*ts); need_contig(*ts)
         assert fin.numel() >= 12
         lib = _lib.load()
         ws = _workspace(pred.device, lib.lae_style_loss_scratch_bytes(M))
-        check(lib.lae_style_loss_forward(ptr(pred), ptr(target), ptr(w_hat), ptr(o_hat), M, n_active, float(lw[0]), float(lw[1]), float(lw[2]),
-                                         ptr(scale), ptr(fin), ptr(ws), ptr(reg_palette), 0 if reg_palette is None else reg_palette.shape[0],
-                                         float(reg_w[0]), float(reg_w[1]), stream()), "style_loss_forward")
+        reg = (ptr(reg_palette), 0 if reg_palette is None else reg_palette.shape[0], float(reg_w[0]), float(reg_w[1]))
+        if m_dev is None:
+            check(lib.lae_style_loss_forward(ptr(pred), ptr(target), ptr(w_hat), ptr(o_hat), M, n_active, float(lw[0]), float(lw[1]), float(lw[2]),
+                                             ptr(scale), ptr(fin), ptr(ws), *reg, stream()), "style_loss_forward")
+        else:
+            check(lib.lae_style_loss_forward_dev(ptr(pred), ptr(target), ptr(w_hat), ptr(o_hat), M, ptr(m_dev), n_active, float(lw[0]),
+                                                 float(lw[1]), float(lw[2]), ptr(scale), ptr(fin), ptr(ws), *reg, stream()), "style_loss_forward_dev")
 
     @staticmethod
     def style_loss_backward(w_logits, o_raw, palette, P, active_mask, M, target, fin, upstream, lw, g_w_logits, g_o_raw, g_palette,
-                            reg_w=None, accumulate=False):
-        """accumulate: g_palette += (LAE_STYLE_ACCUMULATE_PALETTE) -- the caller's persistent fp32 gradient buffer"""
-        ts = (w_logits, o_raw, palette, target, fin, upstream, g_w_logits, g_o_raw, g_palette)
+                            reg_w=None, accumulate=False, m_dev=None):
+        """accumulate: g_palette += (LAE_STYLE_ACCUMULATE_PALETTE) -- the caller's persistent fp32 gradient buffer; m_dev: as
+        style_loss_forward (lae_style_loss_backward_dev)"""
+        ts = (w_logits, o_raw, palette, target, fin, upstream, g_w_logits, g_o_raw, g_palette, m_dev)
         need_cuda(*ts); need_contig(*ts)
         lib = _lib.load()
         ws = _workspace(w_logits.device, max(lib.lae_palette_backward_scratch_bytes(M), lib.lae_style_loss_scratch_bytes(M)))
-        check(lib.lae_style_loss_backward(ptr(w_logits), ptr(o_raw), ptr(palette), P, active_mask, M, ptr(target), ptr(fin), ptr(upstream),
-                                          float(lw[0]), float(lw[1]), float(lw[2]), ptr(g_w_logits), ptr(g_o_raw), ptr(g_palette), ptr(ws),
-                                          int(reg_w is not None) | (2 if accumulate else 0), float(reg_w[0]) if reg_w else 0.0, float(reg_w[1]) if reg_w else 0.0,
-                                          stream()), "style_loss_backward")
+        tail = (float(lw[0]), float(lw[1]), float(lw[2]), ptr(g_w_logits), ptr(g_o_raw), ptr(g_palette), ptr(ws),
+                int(reg_w is not None) | (2 if accumulate else 0), float(reg_w[0]) if reg_w else 0.0, float(reg_w[1]) if reg_w else 0.0, stream())
+        if m_dev is None:
+            check(lib.lae_style_loss_backward(ptr(w_logits), ptr(o_raw), ptr(palette), P, active_mask, M, ptr(target), ptr(fin), ptr(upstream),
+                                              *tail), "style_loss_backward")
+        else:
+            check(lib.lae_style_loss_backward_dev(ptr(w_logits), ptr(o_raw), ptr(palette), P, active_mask, M, ptr(m_dev), ptr(target), ptr(fin),
+                                                  ptr(upstream), *tail), "style_loss_backward_dev")
+
+    @staticmethod
+    def sample_edit_view(x_term, dirs, targets, offsets, counts, depth_factor, schedule, cap, seed, step, x, d, target, m_dev):
+        """one step's view of a packed edit set into [cap,3] buffers + the live row count (lae_sample_edit_view); advances `step`"""
+        ts = (x_term, dirs, targets, offsets, counts, depth_factor, schedule, step, x, d, target, m_dev)
+        need_cuda(*ts); need_contig(*ts)
+        if any(t.dtype != torch.float32 for t in (x_term, dirs, targets, depth_factor, x, d, target)) or offsets.dtype != torch.int64 or \
+                counts.dtype != torch.int32 or schedule.dtype != torch.int32 or step.dtype != torch.int64 or m_dev.dtype not in (torch.int32, torch.uint32):
+            raise RuntimeError("sample_edit_view: fp32 points / targets / depth factors, int64 offsets and step, int32 counts, schedule and row count")
+        check(_lib.load().lae_sample_edit_view(ptr(x_term), ptr(dirs), ptr(targets), ptr(offsets), ptr(counts), ptr(depth_factor),
+                                               counts.numel(), ptr(schedule), schedule.numel(), int(cap), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                               ptr(step), ptr(x), ptr(d), ptr(target), ptr(m_dev), stream()), "sample_edit_view")
 
     @staticmethod
     def recolor_compact(depth, weights_sum, rays_o, rays_d, N, indices, slot_map, x_term, dirs, alpha, count):

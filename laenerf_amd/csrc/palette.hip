@@ -42,6 +42,8 @@ __device__ __forceinline__ Palette load_palette(const float* __restrict__ palett
 
 struct Row16 { half_t v[16]; };
 
+__device__ __forceinline__ uint32_t blocks_for(uint32_t rows) { return rows / PAL_BLOCK + (rows % PAL_BLOCK ? 1u : 0u); }   // cdiv on the device
+
 __device__ __forceinline__ Row16 load_row16(const half_t* __restrict__ p) {
     Row16 r;
     const uint4 a = *reinterpret_cast<const uint4*>(p), b = *reinterpret_cast<const uint4*>(p + 8);
@@ -119,9 +121,12 @@ __global__ __launch_bounds__(PAL_BLOCK) void k_palette_bwd(const half_t* __restr
                                                            const float* __restrict__ palette, uint32_t P, uint32_t mask, uint32_t M,
                                                            const half_t* __restrict__ g_pred, const float* __restrict__ g_w,
                                                            const half_t* __restrict__ g_o, half_t* __restrict__ g_wl,
-                                                           half_t* __restrict__ g_ol, float* __restrict__ slab, LossSrc ls) {
+                                                           half_t* __restrict__ g_ol, float* __restrict__ slab, LossSrc ls,
+                                                           const uint32_t* __restrict__ m_dev) {
     __shared__ float red[PAL_BLOCK / 64][PAL_MAX * 3];
     const uint32_t i = blockIdx.x * PAL_BLOCK + threadIdx.x;
+    const uint32_t cap = M;
+    if (m_dev) M = min(*m_dev, cap);                     // device row count: rows M..cap-1 get zero gradients and no palette share
     const Palette pal = load_palette(palette, P, mask);
     float gp_pal[PAL_MAX][3];
 #pragma unroll
@@ -185,6 +190,12 @@ __global__ __launch_bounds__(PAL_BLOCK) void k_palette_bwd(const half_t* __restr
         *reinterpret_cast<uint4*>(g_wl + (size_t)i * 16 + 8) = *reinterpret_cast<const uint4*>(&out_w.v[8]);
         *reinterpret_cast<uint4*>(g_ol + (size_t)i * 16) = *reinterpret_cast<const uint4*>(&out_o.v[0]);
         *reinterpret_cast<uint4*>(g_ol + (size_t)i * 16 + 8) = *reinterpret_cast<const uint4*>(&out_o.v[8]);
+    } else if (i < cap) {
+        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+        *reinterpret_cast<uint4*>(g_wl + (size_t)i * 16) = z;
+        *reinterpret_cast<uint4*>(g_wl + (size_t)i * 16 + 8) = z;
+        *reinterpret_cast<uint4*>(g_ol + (size_t)i * 16) = z;
+        *reinterpret_cast<uint4*>(g_ol + (size_t)i * 16 + 8) = z;
     }
     // palette gradient: wave reduce of the active bases (uniform mask) -> LDS (compact rows) -> one partial row per workgroup
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -265,8 +276,10 @@ __device__ __forceinline__ float pal_reg_grad(const PalReg& r, const PalStats& s
 // + gmul[0] * gmul[1] * d(reg) / d(palette) on every entry (gmul = upstream, fin: the scaled upstream gradient of the criterion)
 __global__ __launch_bounds__(64) void k_palette_grad_reduce(const float* __restrict__ slab, uint32_t n_blocks, uint32_t P, uint32_t mask,
                                                             float* __restrict__ g_palette, PalReg reg, const float* __restrict__ upstream,
-                                                            const float* __restrict__ fin, int accumulate) {
+                                                            const float* __restrict__ fin, int accumulate,
+                                                            const uint32_t* __restrict__ m_dev) {
     __shared__ float spal[PAL_MAX * 3];                  // the regulariser's loops read the palette ~P^2 times: from LDS, not from memory
+    if (m_dev) n_blocks = min(n_blocks, blocks_for(*m_dev));      // the exact-size call's partials, in its order
     if (reg.palette && threadIdx.x < reg.P * 3u) spal[threadIdx.x] = reg.palette[threadIdx.x];
     __syncthreads();
     if (reg.palette) reg.palette = spal;
@@ -297,9 +310,11 @@ __global__ __launch_bounds__(64) void k_palette_grad_reduce(const float* __restr
 // forward of the fused criterion: per-workgroup partial sums (fixed order inside the wave / workgroup)
 __global__ __launch_bounds__(PAL_BLOCK) void k_style_loss_partial(const half_t* __restrict__ pred, const float* __restrict__ target,
                                                                   const float* __restrict__ w_hat, const half_t* __restrict__ o_hat,
-                                                                  uint32_t M, uint32_t na, float* __restrict__ slab) {
+                                                                  uint32_t M, uint32_t na, float* __restrict__ slab,
+                                                                  const uint32_t* __restrict__ m_dev) {
     __shared__ float red[PAL_BLOCK / 64][SL_COLS];
     const uint32_t i = blockIdx.x * PAL_BLOCK + threadIdx.x;
+    if (m_dev) M = min(*m_dev, M);                       // rows >= the device row count add nothing (whole blocks write zeros)
     float v[SL_COLS];
 #pragma unroll
     for (int k = 0; k < SL_COLS; k++) v[k] = 0.0f;
@@ -335,8 +350,13 @@ __global__ __launch_bounds__(PAL_BLOCK) void k_style_loss_partial(const half_t* 
 
 // one workgroup: fixed-order totals of the partials, the loss terms, the arg-max column of the uniform term
 __global__ __launch_bounds__(1024) void k_style_loss_final(const float* __restrict__ slab, uint32_t n_blocks, uint32_t M, uint32_t na,
-                                                           StyleLossW lw, const float* __restrict__ scale, float* __restrict__ fin, PalReg reg) {
+                                                           StyleLossW lw, const float* __restrict__ scale, float* __restrict__ fin, PalReg reg,
+                                                           const uint32_t* __restrict__ m_dev) {
     __shared__ float tot[SL_COLS];
+    if (m_dev) {                                         // the exact-size call's totals: its partials, in its order, its mean
+        M = min(*m_dev, M);
+        n_blocks = min(n_blocks, blocks_for(M));
+    }
     __shared__ float spal[PAL_MAX * 3];
     if (reg.palette && threadIdx.x < reg.P * 3u) spal[threadIdx.x] = reg.palette[threadIdx.x];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -468,6 +488,40 @@ __global__ __launch_bounds__(SA_BLOCK) void k_style_assemble_bwd(const uint32_t*
     for (int l = 0; l < 16; l++) grad_lm[(size_t)l * M + b] = tile[threadIdx.x * 17 + l];
 }
 
+
+// the fused criterion's two launches each way; m_dev == NULL: M rows, else M is the buffers' capacity and *m_dev (<= M) the live rows
+int style_loss_forward_impl(const void* pred, const float* target, const float* w_hat, const void* o_hat, uint32_t M, const uint32_t* m_dev,
+                            uint32_t n_active, float w_uniform, float w_non_uniform, float c_offset, const float* scale, float* fin,
+                            void* scratch, const float* reg_palette, uint32_t reg_P, float w_valid, float w_distinct, void* stream) {
+    if (!pred || !target || !w_hat || !o_hat || !fin || !scratch) return LAE_ENULL;
+    if (M == 0 || n_active == 0 || n_active > PAL_MAX || (reg_palette && (reg_P == 0 || reg_P > PAL_MAX))) return LAE_EINVAL;
+    hipStream_t s = STREAM(stream);
+    const uint32_t nb = lae::cdiv(M, PAL_BLOCK);
+    k_style_loss_partial<<<nb, PAL_BLOCK, 0, s>>>((const half_t*)pred, target, w_hat, (const half_t*)o_hat, M, n_active, (float*)scratch, m_dev);
+    k_style_loss_final<<<1, 1024, 0, s>>>((const float*)scratch, nb, M, n_active, StyleLossW{w_uniform, w_non_uniform, c_offset},
+                                                  scale, fin, PalReg{reg_palette, reg_P, w_valid, w_distinct}, m_dev);
+    return lae::check_launch("style_loss_forward");
+}
+
+int style_loss_backward_impl(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask, uint32_t M,
+                             const uint32_t* m_dev, const float* target, const float* fin, const float* upstream, float w_uniform,
+                             float w_non_uniform, float c_offset, void* g_w_logits, void* g_o_raw, float* g_palette, void* scratch, int flags,
+                             float w_valid, float w_distinct, void* stream) {
+    if (!w_logits || !o_raw || !palette || !target || !fin || !upstream || !g_w_logits || !g_o_raw || !g_palette || !scratch) return LAE_ENULL;
+    if (M == 0) return LAE_EINVAL;
+    const int rc = check_palette(P, active_mask);
+    if (rc) return rc;
+    hipStream_t s = STREAM(stream);
+    const uint32_t nb = lae::cdiv(M, PAL_BLOCK);
+    const LossSrc ls{target, fin, upstream, StyleLossW{w_uniform, w_non_uniform, c_offset}};
+    k_palette_bwd<true><<<nb, PAL_BLOCK, 0, s>>>((const half_t*)w_logits, (const half_t*)o_raw, palette, P, active_mask, M, nullptr, nullptr,
+                                                 nullptr, (half_t*)g_w_logits, (half_t*)g_o_raw, (float*)scratch, ls, m_dev);
+    k_palette_grad_reduce<<<PAL_MAX * 3, 64, 0, s>>>((const float*)scratch, nb, P, active_mask, g_palette,
+                                                     PalReg{(flags & LAE_STYLE_WITH_REG) ? palette : nullptr, P, w_valid, w_distinct}, upstream, fin,
+                                                     (flags & LAE_STYLE_ACCUMULATE_PALETTE) ? 1 : 0, m_dev);
+    return lae::check_launch("style_loss_backward");
+}
+
 }  // namespace
 
 extern "C" {
@@ -525,8 +579,8 @@ int lae_palette_backward(const void* w_logits, const void* o_raw, const float* p
     const uint32_t nb = lae::cdiv(M, PAL_BLOCK);
     k_palette_bwd<false><<<nb, PAL_BLOCK, 0, s>>>((const half_t*)w_logits, (const half_t*)o_raw, palette, P, active_mask, M,
                                                   (const half_t*)g_pred, g_w, (const half_t*)g_o, (half_t*)g_w_logits, (half_t*)g_o_raw,
-                                                  (float*)scratch, LossSrc{});
-    k_palette_grad_reduce<<<PAL_MAX * 3, 64, 0, s>>>((const float*)scratch, nb, P, active_mask, g_palette, PalReg{nullptr, 0, 0.f, 0.f}, nullptr, nullptr, 0);
+                                                  (float*)scratch, LossSrc{}, nullptr);
+    k_palette_grad_reduce<<<PAL_MAX * 3, 64, 0, s>>>((const float*)scratch, nb, P, active_mask, g_palette, PalReg{nullptr, 0, 0.f, 0.f}, nullptr, nullptr, 0, nullptr);
     return lae::check_launch("palette_backward");
 }
 
@@ -535,33 +589,34 @@ uint64_t lae_style_loss_scratch_bytes(uint32_t M) { return (uint64_t)lae::cdiv(M
 int lae_style_loss_forward(const void* pred, const float* target, const float* w_hat, const void* o_hat, uint32_t M, uint32_t n_active,
                            float w_uniform, float w_non_uniform, float c_offset, const float* scale, float* fin, void* scratch,
                            const float* reg_palette, uint32_t reg_P, float w_valid, float w_distinct, void* stream) {
-    if (!pred || !target || !w_hat || !o_hat || !fin || !scratch) return LAE_ENULL;
-    if (M == 0 || n_active == 0 || n_active > PAL_MAX || (reg_palette && (reg_P == 0 || reg_P > PAL_MAX))) return LAE_EINVAL;
-    hipStream_t s = STREAM(stream);
-    const uint32_t nb = lae::cdiv(M, PAL_BLOCK);
-    k_style_loss_partial<<<nb, PAL_BLOCK, 0, s>>>((const half_t*)pred, target, w_hat, (const half_t*)o_hat, M, n_active, (float*)scratch);
-    k_style_loss_final<<<1, 1024, 0, s>>>((const float*)scratch, nb, M, n_active, StyleLossW{w_uniform, w_non_uniform, c_offset},
-                                                  scale, fin, PalReg{reg_palette, reg_P, w_valid, w_distinct});
-    return lae::check_launch("style_loss_forward");
+    return style_loss_forward_impl(pred, target, w_hat, o_hat, M, nullptr, n_active, w_uniform, w_non_uniform, c_offset, scale, fin, scratch,
+                                   reg_palette, reg_P, w_valid, w_distinct, stream);
+}
+
+int lae_style_loss_forward_dev(const void* pred, const float* target, const float* w_hat, const void* o_hat, uint32_t cap,
+                               const uint32_t* m_dev, uint32_t n_active, float w_uniform, float w_non_uniform, float c_offset,
+                               const float* scale, float* fin, void* scratch, const float* reg_palette, uint32_t reg_P, float w_valid,
+                               float w_distinct, void* stream) {
+    if (!m_dev) return LAE_ENULL;
+    return style_loss_forward_impl(pred, target, w_hat, o_hat, cap, m_dev, n_active, w_uniform, w_non_uniform, c_offset, scale, fin, scratch,
+                                   reg_palette, reg_P, w_valid, w_distinct, stream);
 }
 
 int lae_style_loss_backward(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask, uint32_t M,
                             const float* target, const float* fin, const float* upstream, float w_uniform, float w_non_uniform,
                             float c_offset, void* g_w_logits, void* g_o_raw, float* g_palette, void* scratch, int flags, float w_valid,
                             float w_distinct, void* stream) {
-    if (!w_logits || !o_raw || !palette || !target || !fin || !upstream || !g_w_logits || !g_o_raw || !g_palette || !scratch) return LAE_ENULL;
-    if (M == 0) return LAE_EINVAL;
-    const int rc = check_palette(P, active_mask);
-    if (rc) return rc;
-    hipStream_t s = STREAM(stream);
-    const uint32_t nb = lae::cdiv(M, PAL_BLOCK);
-    const LossSrc ls{target, fin, upstream, StyleLossW{w_uniform, w_non_uniform, c_offset}};
-    k_palette_bwd<true><<<nb, PAL_BLOCK, 0, s>>>((const half_t*)w_logits, (const half_t*)o_raw, palette, P, active_mask, M, nullptr, nullptr,
-                                                 nullptr, (half_t*)g_w_logits, (half_t*)g_o_raw, (float*)scratch, ls);
-    k_palette_grad_reduce<<<PAL_MAX * 3, 64, 0, s>>>((const float*)scratch, nb, P, active_mask, g_palette,
-                                                     PalReg{(flags & LAE_STYLE_WITH_REG) ? palette : nullptr, P, w_valid, w_distinct}, upstream, fin,
-                                                     (flags & LAE_STYLE_ACCUMULATE_PALETTE) ? 1 : 0);
-    return lae::check_launch("style_loss_backward");
+    return style_loss_backward_impl(w_logits, o_raw, palette, P, active_mask, M, nullptr, target, fin, upstream, w_uniform, w_non_uniform,
+                                    c_offset, g_w_logits, g_o_raw, g_palette, scratch, flags, w_valid, w_distinct, stream);
+}
+
+int lae_style_loss_backward_dev(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask, uint32_t cap,
+                                const uint32_t* m_dev, const float* target, const float* fin, const float* upstream, float w_uniform,
+                                float w_non_uniform, float c_offset, void* g_w_logits, void* g_o_raw, float* g_palette, void* scratch,
+                                int flags, float w_valid, float w_distinct, void* stream) {
+    if (!m_dev) return LAE_ENULL;
+    return style_loss_backward_impl(w_logits, o_raw, palette, P, active_mask, cap, m_dev, target, fin, upstream, w_uniform, w_non_uniform,
+                                    c_offset, g_w_logits, g_o_raw, g_palette, scratch, flags, w_valid, w_distinct, stream);
 }
 
 }  // extern "C"

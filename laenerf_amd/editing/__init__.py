@@ -2,3 +2,4 @@ from .style_encoder import LAENeRF, palette_recompose  # noqa: F401
 from .editgrid import EditGrid  # noqa: F401
 from .edit_dataset import extract_view, extract_views, select_edit_pixels  # noqa: F401
 from .recolor import RecolorView, compose_numpy, recolor_views, render_recolored  # noqa: F401
+from .style_trainer import EditSet, StyleTrainer, jitter_numpy  # noqa: F401

@@ -63,7 +63,7 @@ class _palette_point_loss(Function):
 
     @staticmethod
     @custom_fwd(device_type="cuda")
-    def forward(ctx, w_logits, o_raw, palette, active_mask, target, lw, scale, reg_w=None):
+    def forward(ctx, w_logits, o_raw, palette, active_mask, target, lw, scale, reg_w=None, m_dev=None):
         M = w_logits.shape[0]
         w_logits, o_raw = w_logits.half().contiguous(), o_raw.half().contiguous()
         palette_in = palette
@@ -78,9 +78,10 @@ class _palette_point_loss(Function):
         fin = torch.empty(12, dtype=torch.float32, device=dev)
         # reg_w = (palette_loss_valid, palette_loss_distinct): the palette-only term `palet_loss` rides in the same two launches
         _backend.style_loss_forward(pred, target, w_hat, o_hat, M, n_active, lw, scale, fin,
-                                    reg_palette=palette if reg_w is not None else None, reg_w=reg_w or (0.0, 0.0))
+                                    reg_palette=palette if reg_w is not None else None, reg_w=reg_w or (0.0, 0.0), m_dev=m_dev)
         ctx.save_for_backward(w_logits, o_raw, palette, target, fin)
         ctx.meta = (P, active_mask, M, lw, reg_w)
+        ctx.m_dev = m_dev                                # device row count: rows >= *m_dev of the M-row buffers are excluded
         # a palette parameter whose fp32 .grad is a FusedAdam's persistent buffer takes its gradient by an add inside the
         # reduction launch (round 5) instead of through autograd's AccumulateGrad (one more launch on the step's critical path)
         ctx.palette_param = palette_in if getattr(palette_in, "_lae_persistent_grad", False) and palette_in is palette else None
@@ -92,7 +93,7 @@ class _palette_point_loss(Function):
     @custom_bwd(device_type="cuda")
     def backward(ctx, g_loss, *_):
         if g_loss is None:
-            return (None,) * 8
+            return (None,) * 9
         w_logits, o_raw, palette, target, fin = ctx.saved_tensors
         P, active_mask, M, lw, reg_w = ctx.meta
         g_wl, g_ol = torch.empty_like(w_logits), torch.empty_like(o_raw)
@@ -106,8 +107,8 @@ class _palette_point_loss(Function):
             and not getattr(owner, "_post_accumulate_grad_hooks", None)
         g_pal = owner.grad if direct else torch.empty_like(palette)
         _backend.style_loss_backward(w_logits, o_raw, palette, P, active_mask, M, target, fin, g_loss.float().reshape(1).contiguous(), lw,
-                                     g_wl, g_ol, g_pal, reg_w=reg_w, accumulate=direct)
-        return g_wl, g_ol, (None if direct else g_pal), None, None, None, None, None
+                                     g_wl, g_ol, g_pal, reg_w=reg_w, accumulate=direct, m_dev=ctx.m_dev)
+        return g_wl, g_ol, (None if direct else g_pal), None, None, None, None, None, None
 
 
 def palette_recompose(w_logits, o_raw, palette, active_mask):
@@ -288,23 +289,28 @@ class LAENeRF(nn.Module):
         """style_encoder.py:111-133"""
         return self.forward_train(x, d)[0]
 
-    def forward_train_loss(self, x, d, target, params, scaler=None, with_palet_loss=False, plan=None):
+    def forward_train_loss(self, x, d, target, params, scaler=None, with_palet_loss=False, plan=None, m_dev=None):
         """MI355X-native: forward_train + the point-wise losses of train_LAENeRF_step (nerf/utils.py:990-996) in one node:
         loss = MSE(pred, target) + weights_loss(w_hat) + offset_loss(o_hat) [+ palet_loss(params) with with_palet_loss=True: the
         palette-only term and its gradient then ride in the criterion's own launches instead of ~40 tiny torch kernels per step],
         multiplied by `scaler`'s loss scale (a FusedAdam, a 1-element fp32 cuda tensor, or None).
-        -> (loss, pred [M,3], w_hat, o_hat); loss.terms = [scaled loss, loss, mse, uniform, non-uniform, offset, jmax, scale, palet, ...]"""
+        -> (loss, pred [M,3], w_hat, o_hat); loss.terms = [scaled loss, loss, mse, uniform, non-uniform, offset, jmax, scale, palet, ...]
+        m_dev: a 1-element int32 device tensor holding the live row count K <= M (lae_sample_edit_view writes it): x, d, target are
+        buffers of M rows (a multiple of 16) of which the first K count -- the losses, their mean and the gradients see only those,
+        with the bits of the call on the K rows alone (include/laenerf.h lae_style_loss_*_dev)."""
         if self.dir_encoding is not None:
             assert d is not None
         w_logits, o_raw, M = self._logits(x, d, plan)
         if w_logits.shape[0] != M:
-            raise RuntimeError("forward_train_loss: the number of points must be a multiple of 16")
+            raise RuntimeError("forward_train_loss: the number of points must be a multiple of 16"
+                               + ("" if m_dev is None else " (the buffers' capacity, with m_dev)"))
         scale = None
         if scaler is not None:
             scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
         lw = (float(params.weight_loss_uniform), float(params.weight_loss_non_uniform), float(params.offset_loss))
         reg_w = (float(params.palette_loss_valid), float(params.palette_loss_distinct)) if with_palet_loss else None
-        loss, pred, w_hat, o_hat, fin = _palette_point_loss.apply(w_logits, o_raw, self.color_palette, self._active_mask, target, lw, scale, reg_w)
+        loss, pred, w_hat, o_hat, fin = _palette_point_loss.apply(w_logits, o_raw, self.color_palette, self._active_mask, target, lw, scale, reg_w,
+                                                             m_dev)
         loss.terms = fin
         return loss, pred, w_hat, o_hat
 
@@ -319,10 +325,12 @@ class LAENeRF(nn.Module):
         return self._logits(x, d)[1][:x.shape[0], :3]
 
     @torch.no_grad()
-    def distill_color_palettes(self, x_terms, n=10, thresh=0.025):
+    def distill_color_palettes(self, x_terms, n=10, thresh=0.025, idx=None):
         """style_encoder.py:160-173: bases whose mean weight over n sampled views is below `thresh` are switched off.
-        x_terms: list of [P_i,3] point sets (the reference indexes its EditDataset)."""
-        idx = torch.randint(0, len(x_terms), (n,))
+        x_terms: list of [P_i,3] point sets (the reference indexes its EditDataset); idx: the n view indices (default: drawn with
+        torch.randint, as the reference does)."""
+        idx = torch.randint(0, len(x_terms), (n,)) if idx is None else torch.as_tensor(idx).reshape(-1)
+        n = int(idx.numel())
         weights = torch.zeros(self.num_color_bases, dtype=torch.float32, device=self.color_palette.device)
         for i in idx.tolist():
             weights[self.active_palets] += self.get_weights(x_terms[i].to(weights.device)).float().mean(0)
