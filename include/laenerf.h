@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi10"
+#define LAE_ABI_TAG "abi11"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -626,6 +626,47 @@ LAE_API int lae_recolor_compose(const int32_t* slot_map, uint32_t N, const void*
                                 uint32_t o_stride, uint32_t P, uint32_t active_mask, const float* palette, const float* p_weights,
                                 const float* p_bias, const float* alpha, const float* base, const float* bg, int mode, uint32_t k,
                                 int flags, float* out, uint8_t* out_u8, void* stream);
+
+/* ---- LAENeRF's dataset rewrite before the edit is distilled into the NeRF (nerf/gui.py:357-541 distill_dataset: a per-view host
+ * loop of forward_train, ~20 torch ops, a host round trip of each image and a torchvision Resize in the reference) ----
+ *
+ * lae_distill_compose: one thread per row over ALL views.  Rows are the extracted edit pixels, packed per view: img_idx [R] (the
+ *   training image), pix [R] (pixel in scanline order), w [R] (the edit weight, weights_editgrid[indices]), pred [R,3] fp32 (the
+ *   distill render's premultiplied colour at the pixel, no background), dist [R] (the smooth-transition distance weight d, 0 for rows
+ *   not in indices_interp; NULL: no smooth transition).  w_logits [R_pad, >= P] / o_raw [R_pad, >= 3] fp16 with row strides as in
+ *   lae_recolor_compose (LAENeRF._logits).  palette_mod / palette_og [n_active, 3], p_weights / p_bias [n_active]: fp32 DEVICE arrays
+ *   (a captured launch replays a new edit); palette_og is read only with dist.
+ *   Per row, in the order of gui.py:433-469 (every operation one fp32 rounding, no contraction):
+ *     w_og = softmax of the active logits (lae_recolor_compose's rule), o = tanh(o_raw) (double, rounded once);
+ *     w' = max(p_bias + p_weights * w_og, 0), w' /= sum(w');
+ *     c = clamp(w' @ palette_mod + o, 0, 1)  (= LAE_RECOLOR_PREVIEW | LAE_RECOLOR_TANH's colour, the same device code);
+ *     with dist: c = clamp((d w_og + (1 - d) w') @ (d palette_og + (1 - d) palette_mod) + o, 0, 1), the weight and palette
+ *       interpolations each a multiply, a multiply and an add, the product summed in column order;
+ *     s = (1 - w) * pred + w * c, or w * c with LAE_DISTILL_NO_BG;
+ *     rows with w > blend_thresh write clamp(s, 0, 1) into channels 0..2 of images[img_idx, pix] (fp16: round to nearest from the
+ *     fp32 value).  Every other pixel, and the alpha channel of a 4-channel image, is never touched (gui.py:464-467).
+ *   images [n_img, HW, C] (C = 3 or 4), dtype 1 = fp16, 2 = fp32 (ResidentImages' codes; uint8: LAE_EINVAL), written in place.  Rows
+ *   whose img_idx / pix lie outside the images are skipped.
+ *   Deviations from the reference: it runs the palette product and the sums in fp16 under .half(), here they are fp32; where
+ *   sum(w') = 0 (an edit that clamps every weight away) it divides 0 / 0 and writes NaN, here the weights count as zero; its
+ *   ~mask * style + mask * gt lets a NaN of the render at a pixel at or below the threshold into that pixel, here such a pixel is
+ *   never written.
+ *
+ * lae_error_map_seed: LAENeRF's --use_error_maps seed (gui.py:419-425).  dense [n_img, H*W] fp32 scratch: zeroed, then every row's w
+ *   is scattered to its pixel (the dense edit-weight image of each view).  For each of the V images view_img [V] (int32, the
+ *   non-occluded views), the image is resized to 128 x 128 bilinearly without antialiasing, as torch.nn.functional.interpolate(...,
+ *   mode="bilinear", align_corners=False) (torchvision 0.15's Resize on a tensor): per axis scale = in / 128 (fp32),
+ *   src = max(scale * (dst + 0.5) - 0.5, 0), i0 = min(floor(src), in - 1), i1 = i0 + (i0 < in - 1), l = clamp(src - i0, 0, 1);
+ *   x = (1 - ly) * ((1 - lx) x[y0][x0] + lx x[y0][x1]) + ly * ((1 - lx) x[y1][x0] + lx x[y1][x1]) (one rounding per operation);
+ *   error_map[img, cell] = clamp(x + 0.15, 0, 1).  Rows of other images (the occluded views) are not touched. */
+#define LAE_DISTILL_NO_BG 1
+LAE_API int lae_distill_compose(uint32_t R, const int32_t* img_idx, const int32_t* pix, const float* w, const float* pred,
+                                const float* dist, const void* w_logits, uint32_t w_stride, const void* o_raw, uint32_t o_stride,
+                                uint32_t P, uint32_t active_mask, const float* palette_mod, const float* palette_og,
+                                const float* p_weights, const float* p_bias, float blend_thresh, int flags, void* images, int dtype,
+                                uint32_t n_img, uint32_t HW, uint32_t C, void* stream);
+LAE_API int lae_error_map_seed(uint32_t R, const int32_t* img_idx, const int32_t* pix, const float* w, const int32_t* view_img,
+                               uint32_t V, uint32_t n_img, uint32_t H, uint32_t W, float* dense, float* error_map, void* stream);
 
 /* The point-wise losses of train_LAENeRF_step (nerf/utils.py:990-996; style_encoder.py:183-205) fused behind the
  * recomposition: loss = MSE(pred, target) + w_uniform * max_j sum_i w_hat[i,j] + w_non_uniform * sum_i (1 - max_j w_hat[i,j])

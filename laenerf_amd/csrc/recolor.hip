@@ -6,6 +6,7 @@
 // lae_recolor_compose: one thread per pixel, one pass: softmax of the cached logits, the palette edit and the recomposition of
 //   the reference's display / evaluation paths (include/laenerf.h states the rules).
 #include "lae_common.h"
+#include "palette_edit.h"
 
 namespace {
 
@@ -133,16 +134,7 @@ __global__ void __launch_bounds__(RC_THREADS) k_recolor_compose(ComposeArgs a) {
         } else {
             // softmax over the active columns: e = exp(l - max) (fp32 difference, exp in double, one rounding), w = e / sum
             float l[16];
-            float m = -INFINITY;
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                l[j] = (a.active_mask >> j) & 1u ? (float)wl[j] : 0.0f;
-                if ((a.active_mask >> j) & 1u) m = fmaxf(m, l[j]);
-            }
-            float sum = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 16; j++)
-                if ((a.active_mask >> j) & 1u) { l[j] = (float)exp((double)__fsub_rn(l[j], m)); sum = __fadd_rn(sum, l[j]); }
+            const float sum = lae::palette_softmax_exp(wl, a.active_mask, l);
             if (MODE == LAE_RECOLOR_WEIGHTS) {
                 int act = 0;
                 float wk = 0.0f;
@@ -153,28 +145,10 @@ __global__ void __launch_bounds__(RC_THREADS) k_recolor_compose(ComposeArgs a) {
                 r1 = __fadd_rn(wk, __fmul_rn(u, bg1));
                 r2 = __fadd_rn(wk, __fmul_rn(u, bg2));
             } else {
-                const bool edit = MODE == LAE_RECOLOR_PREVIEW && OFFSETS;
-                float wsum = 0.0f;
-                int act = 0;
-#pragma unroll
-                for (int j = 0; j < 16; j++)
-                    if ((a.active_mask >> j) & 1u) {
-                        float w = __fdiv_rn(l[j], sum);
-                        if (edit) { w = fmaxf(__fadd_rn(a.p_bias[act], __fmul_rn(a.p_weights[act], w)), 0.0f); wsum = __fadd_rn(wsum, w); }
-                        l[j] = w;
-                        act++;
-                    }
-                float acc[3] = {0.0f, 0.0f, 0.0f};
-                act = 0;
-#pragma unroll
-                for (int j = 0; j < 16; j++)
-                    if ((a.active_mask >> j) & 1u) {
-                        // w' /= sum(w'); sum(w') == 0 (every edited weight clamped away): the weights count as zero (the reference: 0/0)
-                        const float w = edit ? (wsum > 0.0f ? __fdiv_rn(l[j], wsum) : 0.0f) : l[j];
-#pragma unroll
-                        for (int c = 0; c < 3; c++) acc[c] = __fadd_rn(acc[c], __fmul_rn(w, a.palette[3 * act + c]));
-                        act++;
-                    }
+                lae::palette_normalise(l, a.active_mask, sum);
+                if (MODE == LAE_RECOLOR_PREVIEW && OFFSETS) lae::palette_edit(l, a.active_mask, a.p_weights, a.p_bias);
+                float acc[3];
+                lae::palette_product(l, a.active_mask, a.palette, acc);
                 const float bgc[3] = {bg0, bg1, bg2};
                 float r[3];
 #pragma unroll

@@ -18,9 +18,11 @@ The graphs share one memory pool: they never run concurrently.
 
 error_map='ema' is the reference's --error_map: the batch is drawn by the data's per-image error map
 (ResidentImages.sample with a map) and the step's per-ray error is written back into it (ResidentImages.update_error_map)
-after the compositing, as train_step does (nerf/utils.py:609-631).  'fixed' is LAENeRF's --use_error_maps: the same draw
-from a map the caller seeded, never updated.  Both kernels read and write only device memory, so they run inside the
-captured group like the rest of the step.
+after the compositing, as train_step does (nerf/utils.py:609-631).  'fixed' is the same draw from a map the caller seeded,
+never updated; the reference has no such mode.  LAENeRF's --use_error_maps seeds the map from the edit weights
+(nerf/gui.py:419-425) and hands it to the trainer, whose train_step then updates it: that is 'ema' on a seeded map
+(laenerf_amd.editing.distill).  Both kernels read and write only device memory, so they run inside the captured group like
+the rest of the step.
 """
 import math
 
