@@ -9,12 +9,16 @@ i.e. the reference's Trainer.train_step/backward/optimizer.step sequence (nerf/u
 state (mean_count > 0, no host sync inside the step).  Synthetic rays / occupancy / weights:
 no dataset or checkpoint exists offline.  value = all ranks' rays / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md "Measurement").  Exactly K steps are timed, in one window between
 barriers; `ms_per_step` = that window / K.  --dump-outputs DIR: rank 0 writes what the last timed step returned, and the
 parameters it left, as DIR/<name>.npy (dump_outputs); every input is seeded, so two builds can be compared output for output.
+A plain run stops there: set-up, warm-up, the K timed steps, the dump, the line.  --full adds everything else the line has
+carried, each measured after the timed window: the roofline objects and operator_ms_per_step (eager diagnostic steps), the
+drop-in step, the inference frames, the palette-network and other workloads' steps, the CPU baselines and, for N > 1, the
+ray-sharded 1080p frame.  --no-cpu-baseline / --no-frame / --no-style / --no-dropin trim a --full run.
 """
 import argparse
 import json
@@ -43,10 +47,13 @@ def parse():
     p.add_argument("--steps", type=int, default=None, help="timed steps (default: 200; 20 frames for --workload frame1080)")
     p.add_argument("--warmup", type=int, default=None, help="untimed steps asked for (default: 40; 3 for --workload frame1080)")
     p.add_argument("--rays", type=int, default=4096)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-frame", action="store_true", help="skip the 800x800 inference-frame timing (extra field eval_frame)")
-    p.add_argument("--no-style", action="store_true", help="skip the LAENeRF palette-network step timing (extra field style_step)")
-    p.add_argument("--no-dropin", action="store_true", help="skip the zero-edit drop-in train step (extra field drop_in_step)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure the line's other objects (rooflines, per-operator times, frames, other "
+                        "workloads' steps, CPU baselines, the sharded frame for N > 1); off: only what value / ms_per_step need")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines (extra field cpu_baseline)")
+    p.add_argument("--no-frame", action="store_true", help="--full: skip the inference-frame timings (extra fields eval_frame, frame1080)")
+    p.add_argument("--no-style", action="store_true", help="--full: skip the LAENeRF palette-network step timing and the other workloads' steps (style_step ... sparse_step)")
+    p.add_argument("--no-dropin", action="store_true", help="--full: skip the zero-edit drop-in train step (extra field drop_in_step)")
     p.add_argument("--cpu-rays", type=int, default=0, help="rays in the CPU-baseline sample (0 = auto, ~15 s)")
     p.add_argument("--no-optimizer", action="store_true", help="diagnostic only: skip Adam/GradScaler (not the reported metric)")
     p.add_argument("--workload", choices=["train", "frame1080", "flower"], default="train",
@@ -1187,6 +1194,38 @@ def cpu_baseline_cfg1(n_threads, budget_s=8.0):
                       f"backward incl. weight gradients, oracle operators for the hash grid / SH in {n_threads} chunks + torch CPU ops on {n_threads} threads, {dt:.1f} s"}
 
 
+def grid_forward_roofline(timing_grid):
+    """--full: the `roofline` object -- the hash-grid encode forward's HIP-event time (`timing_grid`: the eager diagnostic steps, or
+    the timed steps themselves under --no-graph) against HBM on its algorithmic bytes per sample"""
+    gf = timing_grid.get("grid_encode_forward", {"ms": float("nan"), "units": 0, "calls": 0})
+    per_launch_bytes = gf["units"] / max(gf["calls"], 1) * GRID_FWD_BYTES_FP16
+    achieved = per_launch_bytes / (gf["ms"] / max(gf["calls"], 1) * 1e-3) / 1e9 if gf["calls"] else float("nan")
+    traffic, traffic_source = None, None
+    tp = os.path.join(ROOT, "profiles", "grid_fwd_traffic.json")
+    if os.path.exists(tp):
+        try:
+            tj = json.load(open(tp))
+            traffic = tj.get("hbm_bytes_per_launch")
+            # NOT a counter of this run: PMC passes need rocprofv3 around the process; the committed result of the most recent
+            # counter run of this same command is read back (its file says which run)
+            traffic_source = "read back from profiles/grid_fwd_traffic.json (%s), not counted in this run" % tj.get("source", tj.get("note", "committed PMC run"))
+        except Exception:
+            traffic = None
+    return {"kernel": "k_grid_fwd_lean (hash-grid encode forward, fp16 table)", "bound": "hbm",
+            "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+            "bytes_per_sample": GRID_FWD_BYTES_FP16,
+            "samples_per_launch": int(gf["units"] / max(gf["calls"], 1)),
+            "avg_launch_us": round(gf["ms"] / max(gf["calls"], 1) * 1e3, 2),
+            "launch_us_min_median_max": [round(gf.get(k, float("nan")) * 1e3, 2) for k in ("min_ms", "median_ms", "max_ms")],
+            "algorithmic_bytes_per_launch": int(per_launch_bytes),
+            "frac_of_peak_on_measured_bytes": (round(traffic / (gf["ms"] / max(gf["calls"], 1) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                                               if traffic and gf["calls"] else None),
+            "limiter": "on-chip: the 2 MiB level tables stay in the XCDs' L2s (measured traffic < algorithmic bytes); fine "
+                       "levels run at the L2 request rate, coarse levels at vector-memory issue (DESIGN.md 4)",
+            "timed": "HIP events on the launch stream around the call in 20 eager steps after the timed region"}
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` (N > 1) outside any rendezvous environment: start the N ranks ourselves, as a FRESH child --
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same args>`
@@ -1540,45 +1579,46 @@ def main():
         dump_outputs(args.dump_outputs, results[(n_warm + args.steps - 1) % n_batches], net)
     timing_grid = backend.collect_kernel_timing() if not graph else {}
     backend.enable_kernel_timing(False)
-    # diagnostic (outside the timed region): per-operator device time of 20 eager steps (HIP events around each
-    # operator on the launch stream); with graph replay this is also where the roofline kernel is timed, because
-    # events cannot be read back from inside a replayed graph
-    if graph:
-        for i in range(3):                                  # untimed: the first eager steps after the replays (allocations, caches)
-            o, d, gt = batches[i % n_batches]
-            zero_grad()
-            step_body(o, d, gt)
-        torch.cuda.synchronize()
-    # (the collector is off while the timing is on -- backend.enable_kernel_timing says why; `launch_us_min_median_max` shows the spread)
+    # --full only: the diagnostics below are not part of `value` (a plain run goes straight to its line)
+    timing_all = timing_split = {}
     n_diag = 20
-    with backend.kernel_timing(only=None) as kt:
-        for i in range(n_diag):
-            o, d, gt = batches[i % n_batches]
-            zero_grad()
-            step_body(o, d, gt)
-    timing_all = kt.result
-    # the same 20 steps with the hash-grid backward in its two halves (counting pass + scans = what the side stream runs ahead;
-    # fill + accumulate = what stays on the main stream), HIP events around each: the `roofline_more` objects below
-    if fused_loss and not args.no_optimizer and not args.dp:
+    if args.full:
+        # diagnostic (outside the timed region): per-operator device time of 20 eager steps (HIP events around each
+        # operator on the launch stream); with graph replay this is also where the roofline kernel is timed, because
+        # events cannot be read back from inside a replayed graph
+        if graph:
+            for i in range(3):                                  # untimed: the first eager steps after the replays (allocations, caches)
+                o, d, gt = batches[i % n_batches]
+                zero_grad()
+                step_body(o, d, gt)
+            torch.cuda.synchronize()
+        # (the collector is off while the timing is on -- backend.enable_kernel_timing says why; `launch_us_min_median_max` shows the spread)
         with backend.kernel_timing(only=None) as kt:
             for i in range(n_diag):
                 o, d, gt = batches[i % n_batches]
                 zero_grad()
-                with torch.autocast("cuda", dtype=torch.float16):
-                    marched = r.march_train(o, d, perturb=True, max_steps=1024, plan_backward=True)
-                    res = r.shade_train(marched, bg_color=1, gt=gt, scaler=scaler)
-                scaler.backward(res["loss"])
-                opt.step()
-        timing_split = kt.result
-    else:
-        timing_split = {}
-    if graph:
-        timing_grid = {"grid_encode_forward": timing_all.get("grid_encode_forward", {"ms": float("nan"), "units": 0, "calls": 0})}
+                step_body(o, d, gt)
+        timing_all = kt.result
+        # the same 20 steps with the hash-grid backward in its two halves (counting pass + scans = what the side stream runs ahead;
+        # fill + accumulate = what stays on the main stream), HIP events around each: the `roofline_more` objects below
+        if fused_loss and not args.no_optimizer and not args.dp:
+            with backend.kernel_timing(only=None) as kt:
+                for i in range(n_diag):
+                    o, d, gt = batches[i % n_batches]
+                    zero_grad()
+                    with torch.autocast("cuda", dtype=torch.float16):
+                        marched = r.march_train(o, d, perturb=True, max_steps=1024, plan_backward=True)
+                        res = r.shade_train(marched, bg_color=1, gt=gt, scaler=scaler)
+                    scaler.backward(res["loss"])
+                    opt.step()
+            timing_split = kt.result
+        if graph:
+            timing_grid = {"grid_encode_forward": timing_all.get("grid_encode_forward", {"ms": float("nan"), "units": 0, "calls": 0})}
     # N > 1: the north star's split, beside the replica `value` -- the configs[3] frame ray-sharded over the ranks with ONE
     # all-gather per frame on the job's backend (RCCL under the driver), timed like `--workload frame1080`, and the same frame on
     # rank 0 alone for the speed-up.  Collective: every rank takes part, rank 0 reports.
     sharded = None
-    if world > 1 and not args.no_frame:
+    if world > 1 and args.full and not args.no_frame:
         sharded, _ = sharded_frame1080(world, rank, dev, backend_name, steps=10, warmup=2, with_n1=True)
 
     if world > 1:                                           # max over ranks (all ranks call the collective)
@@ -1587,20 +1627,6 @@ def main():
         dt = float(wmax.item())
     if rank == 0:
         ms = dt / args.steps * 1e3
-        gf = timing_grid.get("grid_encode_forward", {"ms": float("nan"), "units": 0, "calls": 0})
-        per_launch_bytes = gf["units"] / max(gf["calls"], 1) * GRID_FWD_BYTES_FP16
-        achieved = per_launch_bytes / (gf["ms"] / max(gf["calls"], 1) * 1e-3) / 1e9 if gf["calls"] else float("nan")
-        traffic, traffic_source = None, None
-        tp = os.path.join(ROOT, "profiles", "grid_fwd_traffic.json")
-        if os.path.exists(tp):
-            try:
-                tj = json.load(open(tp))
-                traffic = tj.get("hbm_bytes_per_launch")
-                # NOT a counter of this run: PMC passes need rocprofv3 around the process; the committed result of the most recent
-                # counter run of this same command is read back (its file says which run)
-                traffic_source = "read back from profiles/grid_fwd_traffic.json (%s), not counted in this run" % tj.get("source", tj.get("note", "committed PMC run"))
-            except Exception:
-                traffic = None
         out = {
             "metric": "Mrays/s, lego 800x800 train-step (4096 rays/step)",
             "value": round(world * args.rays * args.steps / dt / 1e6, 4),
@@ -1620,52 +1646,42 @@ def main():
                        "march_pipelined_on_side_stream": bool(pipelined), "steps_per_graph_replay": (G if pipelined else 1),
                        "parallelism": (f"{world} data-parallel ranks, one flat gradient all-reduce per dtype per step" if args.dp else
                                        f"{world} independent ray-batch replicas (no data-path collective)")},
-            "roofline": {"kernel": "k_grid_fwd_lean (hash-grid encode forward, fp16 table)", "bound": "hbm",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                         "bytes_per_sample": GRID_FWD_BYTES_FP16,
-                         "samples_per_launch": int(gf["units"] / max(gf["calls"], 1)),
-                         "avg_launch_us": round(gf["ms"] / max(gf["calls"], 1) * 1e3, 2),
-                         "launch_us_min_median_max": [round(gf.get(k, float("nan")) * 1e3, 2) for k in ("min_ms", "median_ms", "max_ms")],
-                         "algorithmic_bytes_per_launch": int(per_launch_bytes),
-                         "frac_of_peak_on_measured_bytes": (round(traffic / (gf["ms"] / max(gf["calls"], 1) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                                                            if traffic and gf["calls"] else None),
-                         "limiter": "on-chip: the 2 MiB level tables stay in the XCDs' L2s (measured traffic < algorithmic bytes); fine "
-                                    "levels run at the L2 request rate, coarse levels at vector-memory issue (DESIGN.md 4)",
-                         "timed": "HIP events on the launch stream around the call in 20 eager steps after the timed region"},
-            "roofline_more": roofline_more(timing_split, dev, with_frame=not args.no_frame) if timing_split else None,
-            "windows": {"ms_per_step": [round(ms, 4)], "min": round(ms, 4), "median": round(ms, 4), "max": round(ms, 4), "first": round(ms, 4),
-                        "note": "ONE window: exactly K = --steps timed steps between barriers + synchronize, max over ranks; "
-                                "`value` / `ms_per_step` come from it"},
-            "side_stream": side_probe if not args.no_graph else None,        # concurrent_side_stream(): does the side stream run beside the main one?
-            "operator_ms_per_step": {k: round(v["ms"] / n_diag, 4) for k, v in sorted(timing_all.items())},
         }
-        if sharded is not None:
-            sharded["note"] = ("configs[3]-shaped (mip360/bonsai) 1080p inference frame, rays sharded over the ranks of THIS job "
-                               "(laenerf_amd/dist.py: 8x8-pixel-tile order, 128-ray units round-robin, one all_gather_into_tensor per frame), 10 frames between "
-                               "barriers, max over ranks; n1_ms_per_frame: the whole frame on rank 0 alone on the reference schedule, "
-                               "best_n1_ms_per_frame: on the fastest of {reference rule, 2N, 4N, 8N rows per iteration}; speedup_vs_n1 divides THAT by ms_per_frame")
-            out["frame1080"] = sharded                         # the north star's 8-GPU split (not `value`)
-        def extra(fn, *a, **k):                              # the objects beside `value`: a failure inside one of them must not take the line down (it shows as {"error": ...})
-            try:
-                return fn(*a, **k)
-            except Exception as ex:
-                return {"error": repr(ex)}
-        if world == 1 and not args.no_dropin:
-            out["drop_in_step"] = extra(drop_in_step, dev, ms)   # the reference's own operator sequence on the installed backends (not `value`)
-        if world == 1 and not args.no_frame:
-            out["eval_frame"] = extra(eval_frame, dev)              # the "ms/frame" half of BASELINE.json's metric (not `value`)
-            out["eval_frame_surface"] = extra(eval_frame, dev, density_scale=30.0)   # the same frame on a trained-shaped density
-            out["frame1080"] = extra(frame1080, dev)               # configs[3] on one GPU (not `value`)
-        if world == 1 and not args.no_style:
-            out["style_step"] = extra(style_step, dev)              # configs[4] inner loop (not `value`)
-            out["edit_extract"] = extra(edit_extract, dev)          # configs[4] extraction around it (not `value`)
-            out["grid_update"] = extra(grid_update, dev)
-            out["flower_step"] = extra(flower_step, dev)            # configs[2]-shaped train step (not `value`)
-            out["sparse_step"] = extra(sparse_step, dev)       # the sparse occupancy preset of SURVEY 8d (not `value`)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_rays, host_threads())
-            out["cpu_baseline"]["cfg1_run_path"] = cpu_baseline_cfg1(host_threads())
+        if args.full:
+            out["roofline"] = grid_forward_roofline(timing_grid)
+            out["roofline_more"] = roofline_more(timing_split, dev, with_frame=not args.no_frame) if timing_split else None
+        out["windows"] = {"ms_per_step": [round(ms, 4)], "min": round(ms, 4), "median": round(ms, 4), "max": round(ms, 4), "first": round(ms, 4),
+                          "note": "ONE window: exactly K = --steps timed steps between barriers + synchronize, max over ranks; "
+                                  "`value` / `ms_per_step` come from it"}
+        out["side_stream"] = side_probe if not args.no_graph else None        # concurrent_side_stream(): does the side stream run beside the main one?
+        if args.full:
+            out["operator_ms_per_step"] = {k: round(v["ms"] / n_diag, 4) for k, v in sorted(timing_all.items())}
+            if sharded is not None:
+                sharded["note"] = ("configs[3]-shaped (mip360/bonsai) 1080p inference frame, rays sharded over the ranks of THIS job "
+                                   "(laenerf_amd/dist.py: 8x8-pixel-tile order, 128-ray units round-robin, one all_gather_into_tensor per frame), 10 frames between "
+                                   "barriers, max over ranks; n1_ms_per_frame: the whole frame on rank 0 alone on the reference schedule, "
+                                   "best_n1_ms_per_frame: on the fastest of {reference rule, 2N, 4N, 8N rows per iteration}; speedup_vs_n1 divides THAT by ms_per_frame")
+                out["frame1080"] = sharded                         # the north star's 8-GPU split (not `value`)
+            def extra(fn, *a, **k):                              # the objects beside `value`: a failure inside one of them must not take the line down (it shows as {"error": ...})
+                try:
+                    return fn(*a, **k)
+                except Exception as ex:
+                    return {"error": repr(ex)}
+            if world == 1 and not args.no_dropin:
+                out["drop_in_step"] = extra(drop_in_step, dev, ms)   # the reference's own operator sequence on the installed backends (not `value`)
+            if world == 1 and not args.no_frame:
+                out["eval_frame"] = extra(eval_frame, dev)              # the "ms/frame" half of BASELINE.json's metric (not `value`)
+                out["eval_frame_surface"] = extra(eval_frame, dev, density_scale=30.0)   # the same frame on a trained-shaped density
+                out["frame1080"] = extra(frame1080, dev)               # configs[3] on one GPU (not `value`)
+            if world == 1 and not args.no_style:
+                out["style_step"] = extra(style_step, dev)              # configs[4] inner loop (not `value`)
+                out["edit_extract"] = extra(edit_extract, dev)          # configs[4] extraction around it (not `value`)
+                out["grid_update"] = extra(grid_update, dev)
+                out["flower_step"] = extra(flower_step, dev)            # configs[2]-shaped train step (not `value`)
+                out["sparse_step"] = extra(sparse_step, dev)       # the sparse occupancy preset of SURVEY 8d (not `value`)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.cpu_rays, host_threads())
+                out["cpu_baseline"]["cfg1_run_path"] = cpu_baseline_cfg1(host_threads())
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

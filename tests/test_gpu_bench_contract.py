@@ -1,9 +1,11 @@
-"""-m gpu: bench.py keeps the driver's contract -- one JSON line on stdout with the agreed keys, the roofline and cpu_baseline
-objects, exactly K timed steps -- on a shortened run (small CPU-baseline sample, no frame / style extras)."""
+"""-m gpu: bench.py keeps the driver's contract -- one JSON line on stdout with the agreed keys and exactly K timed steps; a
+plain run carries nothing else, --full adds the roofline and cpu_baseline objects (shortened: small CPU-baseline sample, no
+frame / style extras)."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -15,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_prints_one_contract_line(tmp_path):
     dump = tmp_path / "outputs"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "3", "--cpu-rays", "4096",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "3", "--full", "--cpu-rays", "4096",
                           "--no-frame", "--no-style", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -69,3 +71,34 @@ def test_bench_prints_one_contract_line(tmp_path):
     assert sum(v.nbytes for v in a.values()) <= 64 << 20
     assert a["image"].shape == (4096, 3) and a["weights_sum"].shape == (4096,) and a["n_samples"] > 0
     assert a["encoder.embeddings"].shape == (1 << 20, 2)
+
+
+# what a plain line may carry: the headline and what describes how it was measured; everything else needs --full
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "world_size", "backend", "steps", "warmup", "warmup_requested", "ms_per_step",
+              "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "windows", "side_stream"}
+
+
+def test_plain_bench_is_the_headline_alone(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: set-up, warm-up, the K timed steps, the dump and the line -- no eager
+    diagnostic steps, extra workloads or CPU baselines -- and at most 30 s of the process's wall time outside its steps."""
+    dump = tmp_path / "outputs"
+    steps, warmup = 24, 3
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert set(j) == PLAIN_KEYS, set(j) ^ PLAIN_KEYS
+    assert j["metric"] == "Mrays/s, lego 800x800 train-step (4096 rays/step)" and j["unit"] == "Mrays/s" and j["higher_is_better"] is True
+    assert j["dtype"] == "f16 (table, MLP) / f32 (march, composite)"
+    assert j["n_gpus"] == 1 and j["steps"] == steps and j["warmup_requested"] == warmup and j["warmup"] >= 17
+    assert abs(j["value"] - 4096 / (j["ms_per_step"] * 1e-3) / 1e6) < 1e-2 * j["value"]
+    assert j["windows"]["median"] == j["ms_per_step"] and j["config"]["hip_graph_replay"] is True
+    outside = wall - (steps + warmup) * j["ms_per_step"] * 1e-3
+    assert outside < 30.0, f"{outside:.1f} s outside the steps"
+    a = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}       # --dump-outputs works without --full
+    assert {"image", "depth", "weights_sum", "loss", "n_samples", "encoder.embeddings", "sigma_net.weights", "color_net.weights"} <= set(a)
+    assert all(np.isfinite(v).all() for v in a.values()) and a["image"].shape == (4096, 3)

@@ -165,16 +165,16 @@ def test_frame1080_two_ranks_in_fresh_processes_hold_the_same_frame():
 
 
 def test_default_workload_two_ranks_carries_the_sharded_frame_object():
-    """`python bench.py --gpus 2` WITHOUT --workload and WITHOUT torchrun: bench.py starts the two ranks itself
-    (a fresh torch.distributed.run child before any GPU call of the parent), relays rank 0's line and exit code.  Beside the
-    replica `value` the line must carry the north star's split -- the configs[3] frame ray-sharded over the job's ranks with one
+    """`python bench.py --gpus 2 --full` WITHOUT --workload and WITHOUT torchrun: bench.py starts the two ranks
+    itself (a fresh torch.distributed.run child before any GPU call of the parent), relays rank 0's line and exit code.  Beside the
+    replica `value` the --full line must carry the north star's split -- the configs[3] frame ray-sharded over the job's ranks with one
     all-gather per frame, timed, with the speed-up against the BEST one-GPU time of the same frame on rank 0 alone, the backend
     and the world size as the process group reports them (the reference's dormant gather: nerf/utils.py:1555-1570).  Same gloo /
     one-device rehearsal as above (the driver's torchrun form is the previous test)."""
     env = dict(os.environ, LAE_BENCH_DIST_BACKEND="gloo", LAE_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
