@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi11"
+#define LAE_ABI_TAG "abi12"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -785,6 +785,30 @@ LAE_API int lae_density_grid_update(const float* sigmas, const int32_t* indices,
  *   min_near to one.  poses [B,4,4] fp32 camera-to-world, intrinsics (fx, fy, cx, cy), grid [C, H^3] fp32 in place. */
 LAE_API int lae_mark_untrained_grid(const float* poses, uint32_t B, float fx, float fy, float cx, float cy, uint32_t C, uint32_t H,
                             float bound, float min_near, int filter_close_point, float* grid, void* stream);
+
+/* ---- marching cubes (extract_geometry's mcubes.marching_cubes, nerf/utils.py:207-219; PyMCubes on the host there).
+ * u [nx, ny, nz] fp32, C order, indexed (i, j, k) as mcubes does; 2 <= nx, ny, nz <= 512 (else LAE_EINVAL, so every count fits in
+ * int32).  NULL pointers (LAE_ENULL) and bad sizes are rejected before any launch.
+ *   Inside rule: a lattice point is inside iff u > threshold (strictly; NaN is outside).
+ *   Vertices: one per crossed lattice edge (its two ends on different sides), owned by its lower end point, ordered by (that point's
+ *     linear index (i * ny + j) * nz + k, then axis x < y < z).  Position in index space: the lower point + t along the edge's axis,
+ *     t = (threshold - a) / (b - a) in fp32 without contraction (a at the lower end); a non-finite t becomes 0.5, then t is clamped
+ *     to [0, 1].
+ *   Triangles: int32 [T, 3] vertex ids (welded: one vertex per lattice edge), ordered by (cube linear index = its lower corner's,
+ *     then the case table's order).
+ *   Face rule (tools/gen_mc_table.py -> csrc/mc_table.inc): on an ambiguous cube face (its inside corners on one diagonal) the
+ *     inside corners are separated; the choice depends on that face's 4 corners only, so neighbouring cubes agree and the mesh is
+ *     watertight.  Each polygon's right-hand normal points from inside to outside (towards lower values); polygons are fanned
+ *     from their lowest cube-local edge id whose fan draws no diagonal between two edges of one face (a neighbouring cube could
+ *     draw the same one), so every mesh edge of a surface closed inside the lattice lies in exactly two triangles.
+ * count: counts[0] = V, counts[1] = T (device int32[2]); scratch: lae_marching_cubes_scratch_bytes(nx, ny, nz) bytes (0 for bad
+ *   sizes), kept between count and emit.  emit (same u, threshold and scratch, after count on the same stream; only when V > 0):
+ *   verts [V, 3] fp32, tris [T, 3] int32.  Deterministic: no atomics, the same bits on every run. */
+LAE_API uint64_t lae_marching_cubes_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+LAE_API int lae_marching_cubes_count(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void* scratch,
+                             int32_t* counts, void* stream);
+LAE_API int lae_marching_cubes_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void* scratch, float* verts,
+                            int32_t* tris, void* stream);
 
 /* ---- fused Adam + GradScaler (torch.optim.Adam / torch.cuda.amp.GradScaler in the reference: main_nerf.py:223,
  * nerf/utils.py:1474-1482).  `state` is a 64-byte device block:

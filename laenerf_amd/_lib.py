@@ -90,6 +90,9 @@ SIGNATURES = {
     "lae_recolor_compose": [vp, u32, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, i32, u32, i32, vp, vp, vp],
     "lae_distill_compose": [u32, vp, vp, vp, vp, vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, f32, i32, vp, i32, u32, u32, u32, vp],
     "lae_error_map_seed": [u32, vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp],
+    "lae_marching_cubes_scratch_bytes": [u32, u32, u32],
+    "lae_marching_cubes_count": [vp, u32, u32, u32, f32, vp, vp, vp],
+    "lae_marching_cubes_emit": [vp, u32, u32, u32, f32, vp, vp, vp, vp],
     "lae_style_loss_scratch_bytes": [u32],
     "lae_style_loss_forward": [vp, vp, vp, vp, u32, u32, f32, f32, f32, vp, vp, vp, vp, u32, f32, f32, vp],
     "lae_style_loss_backward": [vp, vp, vp, u32, u32, u32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, i32, f32, f32, vp],
@@ -122,6 +125,7 @@ _RESTYPES = {
     "lae_palette_backward_scratch_bytes": u64,
     "lae_style_loss_scratch_bytes": u64,
     "lae_recolor_compact_scratch_bytes": u64,
+    "lae_marching_cubes_scratch_bytes": u64,
     "lae_render_frame_workspace_bytes": u64,
     "lae_workspace_bytes": u64,
     "lae_grid_backward_workspace_bytes": u64,
@@ -132,7 +136,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi11"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi12"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

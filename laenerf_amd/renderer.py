@@ -108,6 +108,27 @@ class NeRFRenderer(nn.Module):
     def density(self, x):
         return self.model.density(x)
 
+    # ------------------------------------------------------------------ mesh (nerf/utils.py:722-741 save_mesh)
+    @torch.no_grad()
+    def extract_mesh(self, resolution=256, threshold=10, chunk=128):
+        """the reference's extract_geometry over aabb_infer: sigma of model.density under fp16 autocast (not multiplied by
+        density_scale) on a resolution^3 lattice, marching cubes on the device -> vertices [V,3] float64, triangles [T,3] int32"""
+        from . import mesh
+        sigma = getattr(self.model, "density_sigma", None) or (lambda x: self.model.density(x)["sigma"])
+
+        def query(pts):
+            with torch.autocast("cuda", dtype=torch.float16):
+                return sigma(pts)
+
+        return mesh.extract_geometry(self.aabb_infer[:3], self.aabb_infer[3:], resolution, threshold, query, S=chunk)
+
+    def save_mesh(self, path, resolution=256, threshold=10):
+        """extract_mesh written as a binary PLY (the reference exports through trimesh)"""
+        from . import mesh
+        v, t = self.extract_mesh(resolution, threshold)
+        mesh.write_ply(path, v, t)
+        return v, t
+
     # ------------------------------------------------------------------ occupancy-grid maintenance
     @torch.no_grad()
     def mark_untrained_grid(self, poses, intrinsic):

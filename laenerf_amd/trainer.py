@@ -206,6 +206,10 @@ class Trainer:
         """optimizer steps the GradScaler skipped (non-finite gradients)"""
         return self.opt.steps_skipped
 
+    def save_mesh(self, path, resolution=256, threshold=10):
+        """nerf/utils.py:722-741: the renderer's mesh as a binary PLY"""
+        return self.r.save_mesh(path, resolution=resolution, threshold=threshold)
+
     @torch.no_grad()
     def evaluate(self, views, data=None, bg_color=1.0):
         """mean PSNR over `views` (image indices of `data`, default the training set) rendered with render_eval over a plain
