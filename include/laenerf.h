@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi12"
+#define LAE_ABI_TAG "abi13"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -707,6 +707,55 @@ LAE_API int lae_style_loss_backward_dev(const void* w_logits, const void* o_raw,
                                 uint32_t cap, const uint32_t* m_dev, const float* target, const float* fin, const float* upstream,
                                 float w_uniform, float w_non_uniform, float c_offset, void* g_w_logits, void* g_o_raw, float* g_palette,
                                 void* scratch, int flags, float w_valid, float w_distinct, void* stream);
+
+/* lae_style_loss_backward_dev plus a per-row g_pred [cap,3] fp32 (device; the image terms' dL/dpred, already multiplied by the loss
+ * scale): added to the criterion's dL/dpred of every live row BEFORE the clamp mask, so the step keeps one palette-backward launch.
+ * g_pred == NULL: exactly lae_style_loss_backward_dev. */
+LAE_API int lae_style_loss_backward_image_dev(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask,
+                                      uint32_t cap, const uint32_t* m_dev, const float* target, const float* fin, const float* upstream,
+                                      float w_uniform, float w_non_uniform, float c_offset, const float* g_pred, void* g_w_logits,
+                                      void* g_o_raw, float* g_palette, void* scratch, int flags, float w_valid, float w_distinct, void* stream);
+
+/* The image-space terms of LAENeRF's stylization step (nerf/utils.py:997-1033; editing/style_encoder.py:207-235,
+ * editing/style_network.py:129-191) on the step's view, everything read from device memory (capturable; one graph serves every view):
+ *   v = schedule[(*step_counter - 1) mod n_sched] (the sampler advanced the counter after its draw), K = min(*m_dev, cap).
+ * The edit set's image arrays: box [V,4] int32 (x_min, x_max, y_min, y_max; crop = rows x_min..x_max-1, columns y_min..y_max-1,
+ * h = x_max - x_min >= 1, w = y_max - y_min >= 1), img_off [V] int64 (first crop pixel of view v in the per-pixel arrays; crop pixel
+ * (i, j) is img_off + i * w + j), pix2row [.] int32 (the view's row whose pixel that is, -1: none), cut_gt [., 3], tv_h [.] (valid for
+ * i < h - 1), tv_v [.] (valid for j < w - 1), smooth [.] (cut_smooth_trans; NULL when unused), vmax [V,2] (max tv_h, max tv_v of the
+ * view; 0 for an empty one).  Crop value x(i, j) = pred[pix2row] (fp16 -> fp32) if 0 <= pix2row < K, else 0.
+ * forward (flags):
+ *   LAE_STYLE_IMG_RESIZE: vgg_in [3,S,S] fp32 = (bilinear(x) - mean_c) / std_c, PyTorch's arithmetic for align_corners=False:
+ *     src = max((dst + 0.5) * (in / out) - 0.5, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1,
+ *     val = l0y (l0x x00 + l1x x01) + l1y (l0x x10 + l1x x11); ImageNet mean / std.
+ *   terms[3] fp32 = {tv, smooth, disc} (0 where the flag is off):
+ *     tv  (LAE_STYLE_IMG_TV) = sum |x(i,j) - x(i+1,j)|^2 wh + sum |x(i,j) - x(i,j+1)|^2 wv, with wh = wv = 1, or with
+ *         LAE_STYLE_IMG_TV_DEPTH wh = 1 - tv_h(i,j) [* (1 - smooth(i+1,j)) with LAE_STYLE_IMG_TV_SMOOTH], wv likewise;
+ *     smooth (LAE_STYLE_IMG_SMOOTH) = sum |x - cut_gt|^2 smooth;
+ *     disc (LAE_STYLE_IMG_DISC) = -sum |dx_h|^2 tv_h / vmax_h - sum |dx_v|^2 tv_v / vmax_v (a view whose maximum is 0 gives NaN,
+ *         like the reference).
+ *   The sums: n_blocks workgroups (fixed by the caller) stride over the crop, then one workgroup sums the partials in a fixed
+ *   order.  scratch: lae_style_image_scratch_bytes(n_blocks).
+ * backward: g_pred [cap,3] fp32 = dL/dx at each row's crop pixel (row2pix [sum K] int32: the row's crop pixel or -1, rows of view
+ *   v at row_off[v]): the adjoint of resize + normalize of g_vgg [3,S,S] (LAE_STYLE_IMG_RESIZE), plus g_terms[0..2] (device) times
+ *   the stencil gradients of tv / smooth / disc.  Rows >= K and rows outside the crop get exactly 0.  One thread per row gathers;
+ *   no atomics (the bits do not depend on scheduling). */
+#define LAE_STYLE_IMG_TV 1
+#define LAE_STYLE_IMG_TV_DEPTH 2
+#define LAE_STYLE_IMG_TV_SMOOTH 4
+#define LAE_STYLE_IMG_SMOOTH 8
+#define LAE_STYLE_IMG_DISC 16
+#define LAE_STYLE_IMG_RESIZE 32
+LAE_API uint64_t lae_style_image_scratch_bytes(uint32_t n_blocks);
+LAE_API int lae_style_image_forward(const void* pred, uint32_t cap, const uint32_t* m_dev, const int32_t* schedule, uint32_t n_sched,
+                            const int64_t* step_counter, uint32_t V, const int32_t* box, const int64_t* img_off, const int32_t* pix2row,
+                            const float* cut_gt, const float* tv_h, const float* tv_v, const float* smooth, const float* vmax, uint32_t S,
+                            float* vgg_in, int flags, uint32_t n_blocks, float* scratch, float* terms, void* stream);
+LAE_API int lae_style_image_backward(const void* pred, uint32_t cap, const uint32_t* m_dev, const int32_t* schedule, uint32_t n_sched,
+                             const int64_t* step_counter, uint32_t V, const int32_t* box, const int64_t* img_off, const int32_t* pix2row,
+                             const float* cut_gt, const float* tv_h, const float* tv_v, const float* smooth, const float* vmax,
+                             const int64_t* row_off, const int32_t* row2pix, uint32_t S, const float* g_vgg, const float* g_terms, int flags,
+                             float* g_pred, void* stream);
 
 /* One training view of the palette network from a device-resident edit set (EditDataset.collate, editing/edit_dataset.py:289-300,
  * laenerf_amd.editing.EditSet.sample).  The set: V views packed as x_term, dirs, targets [sum K, 3] fp32, view v's rows at

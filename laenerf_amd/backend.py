@@ -807,6 +807,51 @@ class _Style:
                                                   ptr(upstream), *tail), "style_loss_backward_dev")
 
     @staticmethod
+    def style_loss_backward_image(w_logits, o_raw, palette, P, active_mask, M, target, fin, upstream, lw, g_pred, g_w_logits, g_o_raw,
+                                  g_palette, m_dev, reg_w=None, accumulate=False):
+        """style_loss_backward with a device row count and the image terms' fp32 dL/dpred [M,3] added before the clamp mask
+        (lae_style_loss_backward_image_dev; g_pred None: lae_style_loss_backward_dev)"""
+        ts = (w_logits, o_raw, palette, target, fin, upstream, g_pred, g_w_logits, g_o_raw, g_palette, m_dev)
+        need_cuda(*ts); need_contig(*ts)
+        if g_pred is not None and (g_pred.dtype != torch.float32 or g_pred.numel() < 3 * M):
+            raise RuntimeError("style_loss_backward_image: g_pred must be float32 [M,3]")
+        lib = _lib.load()
+        ws = _workspace(w_logits.device, max(lib.lae_palette_backward_scratch_bytes(M), lib.lae_style_loss_scratch_bytes(M)))
+        check(lib.lae_style_loss_backward_image_dev(ptr(w_logits), ptr(o_raw), ptr(palette), P, active_mask, M, ptr(m_dev), ptr(target),
+                                                    ptr(fin), ptr(upstream), float(lw[0]), float(lw[1]), float(lw[2]), ptr(g_pred),
+                                                    ptr(g_w_logits), ptr(g_o_raw), ptr(g_palette), ptr(ws),
+                                                    int(reg_w is not None) | (2 if accumulate else 0), float(reg_w[0]) if reg_w else 0.0,
+                                                    float(reg_w[1]) if reg_w else 0.0, stream()), "style_loss_backward_image_dev")
+
+    @staticmethod
+    def _image_args(es, pred, cap, m_dev):
+        if pred.dtype != _F16 or pred.numel() < 3 * cap or m_dev.dtype not in (torch.int32, torch.uint32):
+            raise RuntimeError("style_image: pred float16 [cap,3], m_dev int32")
+        im = es.image
+        return (ptr(pred), int(cap), ptr(m_dev), ptr(es.schedule), es.schedule.numel(), ptr(es.step), es.V, ptr(im["box"]), ptr(im["img_off"]),
+                ptr(im["pix2row"]), ptr(im["cut_gt"]), ptr(im["tv_h"]), ptr(im["tv_v"]), ptr(im.get("smooth")), ptr(im["vmax"]))
+
+    @staticmethod
+    def style_image_forward(es, pred, cap, m_dev, S, vgg_in, flags, n_blocks, terms):
+        """the image terms of the edit set `es`'s current step (lae_style_image_forward): vgg_in [3,S,S] fp32 (LAE_STYLE_IMG_RESIZE),
+        terms [3] fp32 = tv, smooth, disc"""
+        need_cuda(pred, m_dev, vgg_in, terms); need_contig(pred, vgg_in, terms)
+        lib = _lib.load()
+        ws = _workspace(pred.device, lib.lae_style_image_scratch_bytes(n_blocks))
+        check(lib.lae_style_image_forward(*_Style._image_args(es, pred, cap, m_dev), int(S), ptr(vgg_in), int(flags), int(n_blocks), ptr(ws),
+                                          ptr(terms), stream()), "style_image_forward")
+
+    @staticmethod
+    def style_image_backward(es, pred, cap, m_dev, S, g_vgg, g_terms, flags, g_pred):
+        """dL/dpred [cap,3] fp32 of the image terms (lae_style_image_backward)"""
+        need_cuda(pred, m_dev, g_vgg, g_terms, g_pred); need_contig(pred, g_vgg, g_terms, g_pred)
+        if g_pred.dtype != torch.float32 or g_pred.numel() < 3 * cap:
+            raise RuntimeError("style_image_backward: g_pred float32 [cap,3]")
+        im = es.image
+        check(_lib.load().lae_style_image_backward(*_Style._image_args(es, pred, cap, m_dev), ptr(es.offsets), ptr(im["row2pix"]), int(S),
+                                                   ptr(g_vgg), ptr(g_terms), int(flags), ptr(g_pred), stream()), "style_image_backward")
+
+    @staticmethod
     def sample_edit_view(x_term, dirs, targets, offsets, counts, depth_factor, schedule, cap, seed, step, x, d, target, m_dev):
         """one step's view of a packed edit set into [cap,3] buffers + the live row count (lae_sample_edit_view); advances `step`"""
         ts = (x_term, dirs, targets, offsets, counts, depth_factor, schedule, step, x, d, target, m_dev)

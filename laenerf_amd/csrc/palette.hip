@@ -108,7 +108,8 @@ __global__ __launch_bounds__(PAL_BLOCK) void k_palette_fwd(const half_t* __restr
 //   loss = MSE(pred, target) + w_uniform * max_j sum_i w_ij + w_non_uniform * sum_i (1 - max_j w_ij) + c_offset * sum o^2
 // (style_encoder.py:183-205).  `fin` is the result block of k_style_loss_final (totals, arg-max column, loss scale).
 struct StyleLossW { float w_uniform, w_non_uniform, c_offset; };
-struct LossSrc { const float* target; const float* fin; const float* upstream; StyleLossW lw; };
+struct LossSrc { const float* target; const float* fin; const float* upstream; StyleLossW lw;
+                 const float* g_pred; };         // g_pred: fp32 [M,3] dL/dpred of the image terms (scaled), added before the clamp mask, or NULL
 constexpr int SL_COLS = 3 + PAL_MAX;             // partial sums per workgroup: squared error, o^2, 1 - max w, column sums
 constexpr int FIN_LOSS_SCALED = 0, FIN_LOSS = 1, FIN_MSE = 2, FIN_UNIFORM = 3, FIN_NON_UNIFORM = 4, FIN_OFFSET = 5, FIN_JMAX = 6,
               FIN_SCALE = 7, FIN_REG = 8;      // fin: 12 floats
@@ -158,6 +159,7 @@ __global__ __launch_bounds__(PAL_BLOCK) void k_palette_bwd(const half_t* __restr
             if constexpr (LOSS) {
                 const float pc = fminf(fmaxf(p, 0.0f), 1.0f);
                 gpc[c] = pass ? gmul * 2.0f * (pc - ls.target[(size_t)i * 3 + c]) / (3.0f * (float)M) : 0.0f;
+                if (ls.g_pred && pass) gpc[c] += ls.g_pred[(size_t)i * 3 + c];
                 got[c] = gpc[c] + gmul * 2.0f * ls.lw.c_offset * (float)o[c];
             } else {
                 gpc[c] = (g_pred && pass) ? (float)g_pred[(size_t)i * 3 + c] : 0.0f;
@@ -506,14 +508,14 @@ int style_loss_forward_impl(const void* pred, const float* target, const float* 
 int style_loss_backward_impl(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask, uint32_t M,
                              const uint32_t* m_dev, const float* target, const float* fin, const float* upstream, float w_uniform,
                              float w_non_uniform, float c_offset, void* g_w_logits, void* g_o_raw, float* g_palette, void* scratch, int flags,
-                             float w_valid, float w_distinct, void* stream) {
+                             float w_valid, float w_distinct, void* stream, const float* g_pred = nullptr) {
     if (!w_logits || !o_raw || !palette || !target || !fin || !upstream || !g_w_logits || !g_o_raw || !g_palette || !scratch) return LAE_ENULL;
     if (M == 0) return LAE_EINVAL;
     const int rc = check_palette(P, active_mask);
     if (rc) return rc;
     hipStream_t s = STREAM(stream);
     const uint32_t nb = lae::cdiv(M, PAL_BLOCK);
-    const LossSrc ls{target, fin, upstream, StyleLossW{w_uniform, w_non_uniform, c_offset}};
+    const LossSrc ls{target, fin, upstream, StyleLossW{w_uniform, w_non_uniform, c_offset}, g_pred};
     k_palette_bwd<true><<<nb, PAL_BLOCK, 0, s>>>((const half_t*)w_logits, (const half_t*)o_raw, palette, P, active_mask, M, nullptr, nullptr,
                                                  nullptr, (half_t*)g_w_logits, (half_t*)g_o_raw, (float*)scratch, ls, m_dev);
     k_palette_grad_reduce<<<PAL_MAX * 3, 64, 0, s>>>((const float*)scratch, nb, P, active_mask, g_palette,
@@ -617,6 +619,15 @@ int lae_style_loss_backward_dev(const void* w_logits, const void* o_raw, const f
     if (!m_dev) return LAE_ENULL;
     return style_loss_backward_impl(w_logits, o_raw, palette, P, active_mask, cap, m_dev, target, fin, upstream, w_uniform, w_non_uniform,
                                     c_offset, g_w_logits, g_o_raw, g_palette, scratch, flags, w_valid, w_distinct, stream);
+}
+
+int lae_style_loss_backward_image_dev(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask,
+                                      uint32_t cap, const uint32_t* m_dev, const float* target, const float* fin, const float* upstream,
+                                      float w_uniform, float w_non_uniform, float c_offset, const float* g_pred, void* g_w_logits,
+                                      void* g_o_raw, float* g_palette, void* scratch, int flags, float w_valid, float w_distinct, void* stream) {
+    if (!m_dev) return LAE_ENULL;
+    return style_loss_backward_impl(w_logits, o_raw, palette, P, active_mask, cap, m_dev, target, fin, upstream, w_uniform, w_non_uniform,
+                                    c_offset, g_w_logits, g_o_raw, g_palette, scratch, flags, w_valid, w_distinct, stream, g_pred);
 }
 
 }  // extern "C"

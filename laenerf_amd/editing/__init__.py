@@ -2,5 +2,6 @@ from .style_encoder import LAENeRF, palette_recompose  # noqa: F401
 from .editgrid import EditGrid  # noqa: F401
 from .edit_dataset import extract_view, extract_views, select_edit_pixels  # noqa: F401
 from .recolor import RecolorView, compose_numpy, recolor_views, render_recolored  # noqa: F401
-from .style_trainer import EditSet, StyleTrainer, jitter_numpy  # noqa: F401
+from .style_trainer import EditSet, StyleTrainer, image_terms_on, jitter_numpy  # noqa: F401
 from .distill import DistillSet, compose_distill_numpy, distill_images, distill_nerf, distill_steps, error_map_seed_numpy  # noqa: F401
+from .style_network import StyleNetwork, load_style_image, load_vgg19_features  # noqa: F401

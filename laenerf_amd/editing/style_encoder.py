@@ -10,7 +10,8 @@ shapes instead (tests/test_gpu_style.py).  Here they are `FFMLP`s (the repositor
 for the 32- and 48-wide inputs), and softmax / tanh / palette product / clamp and their backward are one kernel each
 (csrc/palette.hip).  tcnn pads the 41-wide offset input to 48 the same way.
 
-Not here (out of scope): the VGG style network (`StyleNetwork`, torchvision), image-space TV / depth losses.
+The VGG style network of the stylization (`style_transfer_net`, `style_loss`) is editing/style_network.py; the image-space terms
+of the stylization step are editing/style_image.py.
 """
 import torch
 import torch.nn as nn
@@ -63,7 +64,7 @@ class _palette_point_loss(Function):
 
     @staticmethod
     @custom_fwd(device_type="cuda")
-    def forward(ctx, w_logits, o_raw, palette, active_mask, target, lw, scale, reg_w=None, m_dev=None):
+    def forward(ctx, w_logits, o_raw, palette, active_mask, target, lw, scale, reg_w=None, m_dev=None, with_pred32=False):
         M = w_logits.shape[0]
         w_logits, o_raw = w_logits.half().contiguous(), o_raw.half().contiguous()
         palette_in = palette
@@ -87,14 +88,24 @@ class _palette_point_loss(Function):
         ctx.palette_param = palette_in if getattr(palette_in, "_lae_persistent_grad", False) and palette_in is palette else None
         ctx.mark_non_differentiable(pred, w_hat, o_hat, fin)
         ctx.set_materialize_grads(False)                 # no zero-filled gradients for the auxiliary outputs
+        ctx.with_pred32 = bool(with_pred32)
+        if with_pred32:
+            # the one differentiable view of pred (fp32, exact): the image terms of the stylization step read it, and their dL/dpred
+            # comes back here in fp32 and joins the criterion's in the palette backward (lae_style_loss_backward_image_dev)
+            if m_dev is None:
+                raise RuntimeError("_palette_point_loss: pred32 needs the device row count m_dev")
+            return fin[0], pred, w_hat, o_hat, fin, pred.float()
         return fin[0], pred, w_hat, o_hat, fin
 
     @staticmethod
     @custom_bwd(device_type="cuda")
-    def backward(ctx, g_loss, *_):
-        if g_loss is None:
-            return (None,) * 9
+    def backward(ctx, g_loss, *rest):
+        g_pred = rest[-1] if ctx.with_pred32 else None
+        if g_loss is None and g_pred is None:
+            return (None,) * 10
         w_logits, o_raw, palette, target, fin = ctx.saved_tensors
+        if g_loss is None:
+            g_loss = torch.zeros(1, dtype=torch.float32, device=fin.device)
         P, active_mask, M, lw, reg_w = ctx.meta
         g_wl, g_ol = torch.empty_like(w_logits), torch.empty_like(o_raw)
         owner = ctx.palette_param
@@ -106,9 +117,13 @@ class _palette_point_loss(Function):
             and owner.grad.is_contiguous() and owner.grad.shape == palette.shape and not owner._backward_hooks \
             and not getattr(owner, "_post_accumulate_grad_hooks", None)
         g_pal = owner.grad if direct else torch.empty_like(palette)
-        _backend.style_loss_backward(w_logits, o_raw, palette, P, active_mask, M, target, fin, g_loss.float().reshape(1).contiguous(), lw,
-                                     g_wl, g_ol, g_pal, reg_w=reg_w, accumulate=direct, m_dev=ctx.m_dev)
-        return g_wl, g_ol, (None if direct else g_pal), None, None, None, None, None, None
+        if g_pred is not None:
+            _backend.style_loss_backward_image(w_logits, o_raw, palette, P, active_mask, M, target, fin, g_loss.float().reshape(1).contiguous(), lw,
+                                               g_pred.float().contiguous(), g_wl, g_ol, g_pal, ctx.m_dev, reg_w=reg_w, accumulate=direct)
+        else:
+            _backend.style_loss_backward(w_logits, o_raw, palette, P, active_mask, M, target, fin, g_loss.float().reshape(1).contiguous(), lw,
+                                         g_wl, g_ol, g_pal, reg_w=reg_w, accumulate=direct, m_dev=ctx.m_dev)
+        return g_wl, g_ol, (None if direct else g_pal), None, None, None, None, None, None, None
 
 
 def palette_recompose(w_logits, o_raw, palette, active_mask):
@@ -176,11 +191,13 @@ class _style_features(Function):
 
 
 class LAENeRF(nn.Module):
-    """style_encoder.py:20-90.  `params` needs `.bound` and `.num_palette_bases` (and `style_weight`, which must be 0:
-    the VGG style network is out of scope)."""
+    """style_encoder.py:20-90.  `params` needs `.bound` and `.num_palette_bases`.  With style_weight > 0 and a style image and
+    VGG weights (the arguments `style_img` [3,H,W] / `vgg` (a load_vgg19_features module, a path or a state dict), or `params.style_image` /
+    `params.vgg_weights` paths) it builds `style_transfer_net` (editing/style_network.py StyleNetwork with params.style_layers, default
+    (10, 12, 14), and crop size `size`); otherwise style_transfer_net is None."""
 
     def __init__(self, params, encoding="hashgrid", dir_encoding=None, num_layers=3, hidden_dim=64, color_palette=None, size=256,
-                 style_img=None):
+                 style_img=None, vgg=None, style_generator=None):
         super().__init__()
         self.opt = params
         self.bound = params.bound
@@ -190,8 +207,6 @@ class LAENeRF(nn.Module):
         self.num_color_bases = params.num_palette_bases
         if not 0 < self.num_color_bases <= 16:
             raise ValueError("LAENeRF: 1..16 palette bases (the MLP output tile is 16 wide)")
-        if getattr(params, "style_weight", 0) > 0:
-            raise NotImplementedError("LAENeRF: the VGG style network is outside the MI355X hot path (SURVEY.md 2.1)")
         self.register_buffer("active_palets", torch.ones(self.num_color_bases, dtype=torch.bool))
         self._active_mask = (1 << self.num_color_bases) - 1                    # host copy of active_palets (no sync per step)
         pal = color_palette if color_palette is not None else torch.rand(self.num_color_bases, 3, dtype=torch.float32)
@@ -205,6 +220,24 @@ class LAENeRF(nn.Module):
         self.offset_in_dim = (self.in_dim + self.in_dim_dir + 15) // 16 * 16     # 41 -> 48, zero columns (tcnn pads alike)
         self.offset_net = FFMLP(self.offset_in_dim, 3, hidden_dim, num_layers - 1)
         self.weight_net = FFMLP(self.in_dim, self.num_color_bases, hidden_dim, num_layers - 1)
+        self.style_transfer_net = None
+        if float(getattr(params, "style_weight", 0) or 0) > 0:
+            from . import style_network as sn
+            style_img = style_img if style_img is not None else getattr(params, "style_image", None)
+            vgg = vgg if vgg is not None else getattr(params, "vgg_weights", None)
+            if style_img is not None and vgg is not None:
+                if isinstance(style_img, str):
+                    style_img = sn.load_style_image(style_img)
+                layers = tuple(getattr(params, "style_layers", None) or (10, 12, 14))
+                if not isinstance(vgg, nn.Module):
+                    vgg = sn.load_vgg19_features(vgg, max(layers))
+                self.style_transfer_net = sn.StyleNetwork(style_img, vgg, style_layers=layers, size=size, generator=style_generator)
+
+    def style_loss(self, img):
+        """style_encoder.py: the VGG Gram loss of the [3,h,w] image `img` (StyleNetwork.forward)"""
+        if self.style_transfer_net is None:
+            raise RuntimeError("LAENeRF.style_loss: no style network (style_weight > 0 with a style image and VGG weights builds one)")
+        return self.style_transfer_net(img)
 
     # ---- the two heads as the fused MLP writes them: [M,16] fp16 with padded columns
     def plan_backward(self, x):
@@ -289,7 +322,7 @@ class LAENeRF(nn.Module):
         """style_encoder.py:111-133"""
         return self.forward_train(x, d)[0]
 
-    def forward_train_loss(self, x, d, target, params, scaler=None, with_palet_loss=False, plan=None, m_dev=None):
+    def forward_train_loss(self, x, d, target, params, scaler=None, with_palet_loss=False, plan=None, m_dev=None, with_pred32=False):
         """MI355X-native: forward_train + the point-wise losses of train_LAENeRF_step (nerf/utils.py:990-996) in one node:
         loss = MSE(pred, target) + weights_loss(w_hat) + offset_loss(o_hat) [+ palet_loss(params) with with_palet_loss=True: the
         palette-only term and its gradient then ride in the criterion's own launches instead of ~40 tiny torch kernels per step],
@@ -297,7 +330,9 @@ class LAENeRF(nn.Module):
         -> (loss, pred [M,3], w_hat, o_hat); loss.terms = [scaled loss, loss, mse, uniform, non-uniform, offset, jmax, scale, palet, ...]
         m_dev: a 1-element int32 device tensor holding the live row count K <= M (lae_sample_edit_view writes it): x, d, target are
         buffers of M rows (a multiple of 16) of which the first K count -- the losses, their mean and the gradients see only those,
-        with the bits of the call on the K rows alone (include/laenerf.h lae_style_loss_*_dev)."""
+        with the bits of the call on the K rows alone (include/laenerf.h lae_style_loss_*_dev).
+        with_pred32=True (needs m_dev): a fifth result, pred as a differentiable fp32 [M,3] tensor for the image terms of the stylization
+        step (their gradient joins the criterion's in the same palette-backward launch)."""
         if self.dir_encoding is not None:
             assert d is not None
         w_logits, o_raw, M = self._logits(x, d, plan)
@@ -309,10 +344,10 @@ class LAENeRF(nn.Module):
             scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
         lw = (float(params.weight_loss_uniform), float(params.weight_loss_non_uniform), float(params.offset_loss))
         reg_w = (float(params.palette_loss_valid), float(params.palette_loss_distinct)) if with_palet_loss else None
-        loss, pred, w_hat, o_hat, fin = _palette_point_loss.apply(w_logits, o_raw, self.color_palette, self._active_mask, target, lw, scale, reg_w,
-                                                             m_dev)
+        out = _palette_point_loss.apply(w_logits, o_raw, self.color_palette, self._active_mask, target, lw, scale, reg_w, m_dev, bool(with_pred32))
+        loss, pred, w_hat, o_hat, fin = out[:5]
         loss.terms = fin
-        return loss, pred, w_hat, o_hat
+        return (loss, pred, w_hat, o_hat, out[5]) if with_pred32 else (loss, pred, w_hat, o_hat)
 
     def get_weights(self, x):
         """style_encoder.py:93-96"""
