@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi13"
+#define LAE_ABI_TAG "abi14"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -901,6 +901,40 @@ LAE_API int lae_adam_apply_multi(uint32_t n_tensors, float* const* params, float
  * caller computes one_minus_decay = 1 - min(decay, (1 + num_updates) / (10 + num_updates)) like torch_ema does. */
 LAE_API int lae_ema_update_multi(uint32_t n_tensors, float* const* shadows, const float* const* params, const uint64_t* sizes,
                          float one_minus_decay, void* stream);
+/* the same update once per epoch inside a captured training step (the reference updates after every epoch of one image per
+ * batch): nothing happens unless *step (the int64 device step counter, i.e. the 1-based index of the step just taken) is a
+ * positive multiple of epoch_len.  Then, with n = count[0] + 1: decay_t = min(decay, (1 + n) / (10 + n)) in fp64 (decay itself
+ * when use_num_updates == 0), one_minus_decay = (float)(1 - decay_t), lae_ema_update_multi's arithmetic, and count[0] = n.
+ * count: int32 [2] device words, the update count and a block ticket that must be 0 before the call (it is left at 0). */
+LAE_API int lae_ema_update_gated(uint32_t n_tensors, float* const* shadows, const float* const* params, const uint64_t* sizes,
+                         const int64_t* step, int64_t epoch_len, int32_t* count, double decay, int use_num_updates, void* stream);
+
+/* ------------------------------------------------------------------ */
+/* evaluation (evaluate.hip): evaluate_one_epoch / test (nerf/utils.py:1526-1624, :777-827) with PSNRMeter / LPIPSMeter    */
+/* (:240-247, main_nerf.py:203, 242) and LAENeRF's eval_masked (nerf/gui.py:853-947)                                        */
+/* ------------------------------------------------------------------ */
+#define LAE_EVAL_VIEW_SCRATCH_DOUBLES 2048
+/* one rendered view against its ground truth in one pass.  pred fp32 [n_pixels,3] and depth fp32 [n_pixels] (16-byte aligned;
+ * depth may be NULL unless depth_u8 is asked for); gt [n_pixels, gt_channels] as stored (gt_dtype 0 uint8 = value / 255, 1 fp16,
+ * 2 fp32; channels 3 or 4) or NULL when only the uint8 images are wanted.  For C = 4 the ground truth is blended over bg as
+ * rgb * a + bg * (1 - a) with torch's separate fp32 roundings.  Every output is optional:
+ *   sse_out         one double: sum over n_pixels * 3 of (pred - gt)^2 (differences and sum in fp64; fixed-order two-stage
+ *                   reduction through scratch, LAE_EVAL_VIEW_SCRATCH_DOUBLES doubles: two calls give the same bits)
+ *   masked_sse_out  one double (needs sse_out and mask, uint8 [n_pixels]): the same sum against the UNblended gt[:3] over the
+ *                   pixels whose mask byte is 0 (eval_masked's m = 1 - clip(mask[..., -1], 0, 1))
+ *   gt_out          fp32 [n_pixels,3], the blended ground truth
+ *   rgb_u8 / depth_u8  clip(x, 0, 1) * 255 truncated, [n_pixels,3] / [n_pixels]
+ *   lpips_in        fp32 [2,3,n_pixels] planes: index 0 the blended gt, 1 pred, each ((2x - 1) - shift_c) / scale_c with lpips'
+ *                   ScalingLayer (shift -.030 -.088 -.188, scale .458 .448 .450) */
+LAE_API int lae_eval_view(const float* pred, const float* depth, const void* gt, int gt_dtype, uint32_t gt_channels, uint32_t n_pixels,
+                          float bg, const uint8_t* mask, double* scratch, double* sse_out, double* masked_sse_out, float* gt_out,
+                          uint8_t* rgb_u8, uint8_t* depth_u8, float* lpips_in, void* stream);
+/* LPIPS v0.1's distance head (normalize_tensor, NetLinLayer, spatial_average, sum over layers) for n_pairs pairs in one launch:
+ * feats[l] fp32 [2 * n_pairs, channels[l], hw[l]] (pair p = rows 2p and 2p + 1), weights[l] fp32 [channels[l]] (host arrays of
+ * n_layers <= 5 device pointers); out[p] = sum_l mean_px sum_c w_c (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2 as double,
+ * accumulated in fp64 with a fixed-order reduction.  scratch: n_pairs * sum_l ceil(hw[l] / 256) doubles. */
+LAE_API int lae_lpips_head(uint32_t n_layers, const float* const* feats, const float* const* weights, const uint32_t* channels,
+                           const uint32_t* hw, uint32_t n_pairs, double* scratch, double* out, void* stream);
 
 /* MI355X-native: 0 (default) = fused backward (activations recomputed in registers, forward_buffer /
  * backward_buffer untouched: both are scratch the reference's Python never reads), every wave accumulating all dW tiles

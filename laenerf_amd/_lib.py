@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("LAE_HIP_LIB") or os.path.join(_HERE, "lib", "liblaenerf_hip.so")   # LAE_HIP_LIB: A/B against another build
 
 u32, u64, f32, i32, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p
+i64, f64 = ctypes.c_int64, ctypes.c_double
 
 # name -> argtypes (everything returns int unless listed in _RESTYPES); mirrors include/laenerf.h
 SIGNATURES = {
@@ -113,6 +114,9 @@ SIGNATURES = {
     "lae_adam_apply_multi": [u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp],
     "lae_adam_begin": [vp, f32, f32, i32, f32, f32, i32, vp],
     "lae_ema_update_multi": [u32, vp, vp, vp, f32, vp],
+    "lae_ema_update_gated": [u32, vp, vp, vp, vp, i64, vp, f64, i32, vp],
+    "lae_eval_view": [vp, vp, vp, i32, u32, u32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "lae_lpips_head": [u32, vp, vp, vp, vp, u32, vp, vp, vp],
     "lae_adam_apply": [vp, vp, vp, vp, i32, vp, u64, vp, vp, f32, f32, f32, f32, vp],
     "lae_ffmlp_set_mode": [i32],
     "lae_allocate_splitk": [u64],
@@ -141,7 +145,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi13"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi14"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

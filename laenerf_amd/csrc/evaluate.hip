@@ -1,0 +1,307 @@
+// evaluate.hip -- scoring a rendered view (the reference's evaluate_one_epoch / test, nerf/utils.py:1526-1624, :777-827, with
+// PSNRMeter and LPIPSMeter(net='alex'), main_nerf.py:203, 242; LAENeRF's eval_masked, nerf/gui.py:853-947).
+//
+//   k_eval_view     ONE pass over a view: reads the render (fp32 rgb [HW,3] + depth [HW]) and the ground truth in its storage
+//                   dtype (uint8 / fp16 / fp32, C = 3 or 4) once, four pixels per thread with vector loads; per pixel the blended
+//                   ground truth, the squared error and the masked squared error (fp64), the uint8 rgb / depth and the LPIPS input.
+//                   Per-block fp64 partials, summed in a fixed order by k_eval_finish (one block): two runs give the same bits.
+//   k_lpips_head    LPIPS v0.1's distance head (normalize_tensor, NetLinLayer, spatial_average, the sum over layers) for all
+//                   five layers and a batch of pairs in one launch: one lane per pixel of one layer, a loop over the channels
+//                   (NCHW: every load coalesced across the wave), fp64 sums; per-block partials / (h w), k_lpips_finish sums a
+//                   pair's partials in a fixed order.
+#include "lae_common.h"
+#include <algorithm>
+
+#define STREAM(s) reinterpret_cast<hipStream_t>(s)
+
+namespace {
+
+constexpr int EV_THREADS = 256;
+constexpr uint32_t EV_MAX_BLOCKS = LAE_EVAL_VIEW_SCRATCH_DOUBLES / 2;
+
+// `img.float() / 255` on the device: torch divides by a CPU scalar as a multiplication by its fp32 reciprocal
+// (div_true_kernel_cuda), which is what Trainer.evaluate's ground truth went through
+__device__ __forceinline__ float to_f(uint8_t v) { return __fmul_rn((float)v, 1.0f / 255.0f); }
+__device__ __forceinline__ float to_f(_Float16 v) { return (float)v; }
+__device__ __forceinline__ float to_f(float v) { return v; }
+
+__device__ __forceinline__ uint8_t to_u8(float x) { return (uint8_t)(int)__fmul_rn(lae::clampf(x, 0.0f, 1.0f), 255.0f); }
+
+struct EvalOut {
+    double* scratch;             // [2 * EV_MAX_BLOCKS]: per-block sse | masked sse
+    float* gt_out;               // [HW,3] or NULL
+    uint8_t* rgb_u8;             // [HW,3] or NULL
+    uint8_t* depth_u8;           // [HW] or NULL
+    float* lpips_in;             // [2,3,H,W] or NULL
+};
+
+// the four pixels 4q .. 4q+3 of a thread's quad are loaded in one piece: B bytes of ground truth in W-byte vector loads
+template <typename T, int C> struct Quad {
+    static constexpr int B = 4 * C * (int)sizeof(T);
+    static constexpr int W = B % 16 == 0 ? 16 : (B % 8 == 0 ? 8 : 4);
+};
+
+template <typename T, int C, bool VEC>
+__device__ __forceinline__ void load_gt(const T* __restrict__ gt, uint32_t p0, int n, T (&v)[4 * C]) {
+    if constexpr (VEC) {
+        constexpr int B = Quad<T, C>::B, W = Quad<T, C>::W;
+        const uint8_t* src = reinterpret_cast<const uint8_t*>(gt + (size_t)p0 * C);
+        uint32_t raw[B / 4];
+#pragma unroll
+        for (int k = 0; k < B / W; k++) {
+            if constexpr (W == 16) {
+                const uint4 x = reinterpret_cast<const uint4*>(src)[k];
+                raw[4 * k] = x.x; raw[4 * k + 1] = x.y; raw[4 * k + 2] = x.z; raw[4 * k + 3] = x.w;
+            } else if constexpr (W == 8) {
+                const uint2 x = reinterpret_cast<const uint2*>(src)[k];
+                raw[2 * k] = x.x; raw[2 * k + 1] = x.y;
+            } else {
+                raw[k] = reinterpret_cast<const uint32_t*>(src)[k];
+            }
+        }
+        __builtin_memcpy(v, raw, B);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4 * C; k++) v[k] = k < n * C ? gt[(size_t)p0 * C + k] : T(0);
+    }
+}
+
+template <typename T, int C, bool VEC>
+__global__ __launch_bounds__(EV_THREADS) void k_eval_view(const float* __restrict__ pred, const float* __restrict__ depth,
+                                                          const T* __restrict__ gt, uint32_t HW, float bg,
+                                                          const uint8_t* __restrict__ mask, EvalOut o) {
+    __shared__ double s_red[2][EV_THREADS];
+    const float shift[3] = {-0.030f, -0.088f, -0.188f};          // lpips ScalingLayer (lpips/pretrained_networks.py)
+    const float scale[3] = {0.458f, 0.448f, 0.450f};
+    double sse = 0.0, msse = 0.0;
+    const uint32_t quads = (HW + 3) / 4;
+    for (uint32_t q = blockIdx.x * EV_THREADS + threadIdx.x; q < quads; q += gridDim.x * EV_THREADS) {
+        const uint32_t p0 = 4 * q;
+        const int n = (int)min(4u, HW - p0);
+        float pr[12], de[4];
+        T g[4 * C];
+        if (n == 4) {                                            // 48 + 16 bytes of render in four 16-byte loads
+            const float4* pp = reinterpret_cast<const float4*>(pred + (size_t)p0 * 3);
+#pragma unroll
+            for (int k = 0; k < 3; k++) { const float4 x = pp[k]; pr[4 * k] = x.x; pr[4 * k + 1] = x.y; pr[4 * k + 2] = x.z; pr[4 * k + 3] = x.w; }
+            if (depth) { const float4 x = *reinterpret_cast<const float4*>(depth + p0); de[0] = x.x; de[1] = x.y; de[2] = x.z; de[3] = x.w; }
+            else { de[0] = de[1] = de[2] = de[3] = 0.0f; }
+            if (gt) load_gt<T, C, VEC>(gt, p0, 4, g);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; k++) pr[k] = k < 3 * n ? pred[(size_t)p0 * 3 + k] : 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; k++) de[k] = (depth && k < n) ? depth[p0 + k] : 0.0f;
+            if (gt) load_gt<T, C, false>(gt, p0, n, g);
+        }
+        uint32_t mw = 0;                                         // the mask bytes of the quad
+        if (mask) {
+            if (n == 4 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0) mw = *reinterpret_cast<const uint32_t*>(mask + p0);
+            else for (int k = 0; k < n; k++) mw |= (uint32_t)mask[p0 + k] << (8 * k);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (k >= n) break;
+            const uint32_t p = p0 + k;
+            float x[3];
+            if (gt) {
+                float raw[3];
+#pragma unroll
+                for (int c = 0; c < 3; c++) raw[c] = to_f(g[k * C + c]);
+                if constexpr (C == 4) {                          // img[:, :3] * a + bg * (1 - a), each op rounded as torch's
+                    const float a = to_f(g[k * C + 3]);
+                    const float b = __fmul_rn(bg, __fsub_rn(1.0f, a));
+#pragma unroll
+                    for (int c = 0; c < 3; c++) x[c] = __fadd_rn(__fmul_rn(raw[c], a), b);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 3; c++) x[c] = raw[c];
+                }
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const double d = (double)pr[3 * k + c] - (double)x[c];
+                    sse = fma(d, d, sse);
+                }
+                if (mask && ((mw >> (8 * k)) & 255u) == 0u) {    // eval_masked: m = 1 - clip(mask, 0, 1), no blend
+#pragma unroll
+                    for (int c = 0; c < 3; c++) {
+                        const double d = (double)pr[3 * k + c] - (double)raw[c];
+                        msse = fma(d, d, msse);
+                    }
+                }
+                if (o.gt_out) {
+#pragma unroll
+                    for (int c = 0; c < 3; c++) o.gt_out[(size_t)p * 3 + c] = x[c];
+                }
+            }
+            if (o.rgb_u8) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) o.rgb_u8[(size_t)p * 3 + c] = to_u8(pr[3 * k + c]);
+            }
+            if (o.depth_u8) o.depth_u8[p] = to_u8(de[k]);
+            if (o.lpips_in && gt) {                              // lpips(truths, preds, normalize=True): [0] = gt, [1] = pred
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const float u = __fsub_rn(__fmul_rn(2.0f, x[c]), 1.0f);
+                    const float v = __fsub_rn(__fmul_rn(2.0f, pr[3 * k + c]), 1.0f);
+                    o.lpips_in[(size_t)c * HW + p] = __fdiv_rn(__fsub_rn(u, shift[c]), scale[c]);
+                    o.lpips_in[(size_t)(3 + c) * HW + p] = __fdiv_rn(__fsub_rn(v, shift[c]), scale[c]);
+                }
+            }
+        }
+    }
+    s_red[0][threadIdx.x] = sse;
+    s_red[1][threadIdx.x] = msse;
+    __syncthreads();
+    for (int s = EV_THREADS / 2; s > 0; s >>= 1) {               // fixed-order tree
+        if ((int)threadIdx.x < s) {
+            s_red[0][threadIdx.x] += s_red[0][threadIdx.x + s];
+            s_red[1][threadIdx.x] += s_red[1][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        o.scratch[blockIdx.x] = s_red[0][0];
+        o.scratch[EV_MAX_BLOCKS + blockIdx.x] = s_red[1][0];
+    }
+}
+
+// one block per row of n partials (rows `stride` apart), summed in a fixed order: thread t takes t, t + 256, ..., then a tree.
+// The sum of row r goes to out1 when r == 1 and out1 is given (the view's masked sum), else to out0[r].
+__global__ __launch_bounds__(EV_THREADS) void k_sum_partials(const double* __restrict__ part, uint32_t n, uint32_t stride,
+                                                             double* out0, double* out1) {
+    __shared__ double s_red[EV_THREADS];
+    const double* p = part + (size_t)blockIdx.x * stride;
+    double s = 0.0;
+    for (uint32_t i = threadIdx.x; i < n; i += EV_THREADS) s += p[i];
+    s_red[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = EV_THREADS / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) s_red[threadIdx.x] += s_red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (out1 && blockIdx.x == 1) *out1 = s_red[0];
+        else out0[blockIdx.x] = s_red[0];
+    }
+}
+
+constexpr int LP_MAX_LAYERS = 5;
+struct LpipsArgs {
+    const float* f[LP_MAX_LAYERS];          // [2 * n_pairs, C, h, w]: pair p = rows 2p (x0) and 2p + 1 (x1)
+    const float* w[LP_MAX_LAYERS];          // [C]
+    uint32_t C[LP_MAX_LAYERS], hw[LP_MAX_LAYERS];
+    uint32_t blk0[LP_MAX_LAYERS + 1];       // first block of each layer; blk0[n_layers] = blocks per pair
+    uint32_t n_layers;
+};
+
+__global__ __launch_bounds__(EV_THREADS) void k_lpips_head(LpipsArgs a, uint32_t blocks_per_pair, double* __restrict__ partials) {
+    __shared__ double s_red[EV_THREADS];
+    const uint32_t pair = blockIdx.y, b = blockIdx.x;
+    uint32_t l = 0;
+    while (l + 1 < a.n_layers && b >= a.blk0[l + 1]) l++;
+    const uint32_t hw = a.hw[l], C = a.C[l];
+    const uint32_t px = (b - a.blk0[l]) * EV_THREADS + threadIdx.x;
+    double d = 0.0;
+    if (px < hw) {
+        const float* __restrict__ f0 = a.f[l] + (size_t)(2 * pair) * C * hw + px;
+        const float* __restrict__ f1 = f0 + (size_t)C * hw;
+        const float* __restrict__ w = a.w[l];
+        // one pass: |f0|^2, |f1|^2 and the weighted sums of f0 f0, f0 f1, f1 f1; then
+        // sum_c w_c (f0 / n0 - f1 / n1)^2 = w00 / n0^2 - 2 w01 / (n0 n1) + w11 / n1^2 with n = sqrt(|f|^2) + 1e-10 (fp64 throughout)
+        double s00 = 0.0, s11 = 0.0, w00 = 0.0, w01 = 0.0, w11 = 0.0;
+        uint32_t c = 0;
+        for (; c + 4 <= C; c += 4) {
+            float x[4], y[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) { x[k] = f0[(size_t)(c + k) * hw]; y[k] = f1[(size_t)(c + k) * hw]; }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const double xd = x[k], yd = y[k], wc = w[c + k];
+                s00 = fma(xd, xd, s00); s11 = fma(yd, yd, s11);
+                w00 = fma(wc * xd, xd, w00); w01 = fma(wc * xd, yd, w01); w11 = fma(wc * yd, yd, w11);
+            }
+        }
+        for (; c < C; c++) {
+            const double xd = f0[(size_t)c * hw], yd = f1[(size_t)c * hw], wc = w[c];
+            s00 = fma(xd, xd, s00); s11 = fma(yd, yd, s11);
+            w00 = fma(wc * xd, xd, w00); w01 = fma(wc * xd, yd, w01); w11 = fma(wc * yd, yd, w11);
+        }
+        const double n0 = sqrt(s00) + 1e-10, n1 = sqrt(s11) + 1e-10;
+        const double t0 = w00 / (n0 * n0), t1 = w01 / (n0 * n1), t2 = w11 / (n1 * n1);
+        d = (t0 - 2.0 * t1) + t2;                                // identical features: t0 = t1 = t2, exactly 0
+    }
+    s_red[threadIdx.x] = d;
+    __syncthreads();
+    for (int h = EV_THREADS / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) s_red[threadIdx.x] += s_red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[(size_t)pair * blocks_per_pair + b] = s_red[0] / (double)hw;
+}
+
+template <typename T, int C>
+void launch_eval(bool vec, uint32_t blocks, const float* pred, const float* depth, const void* gt, uint32_t HW, float bg,
+                 const uint8_t* mask, const EvalOut& o, hipStream_t s) {
+    if (vec) k_eval_view<T, C, true><<<blocks, EV_THREADS, 0, s>>>(pred, depth, (const T*)gt, HW, bg, mask, o);
+    else k_eval_view<T, C, false><<<blocks, EV_THREADS, 0, s>>>(pred, depth, (const T*)gt, HW, bg, mask, o);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lae_eval_view(const float* pred, const float* depth, const void* gt, int gt_dtype, uint32_t gt_channels, uint32_t n_pixels, float bg,
+                  const uint8_t* mask, double* scratch, double* sse_out, double* masked_sse_out, float* gt_out, uint8_t* rgb_u8,
+                  uint8_t* depth_u8, float* lpips_in, void* stream) {
+    if (n_pixels == 0) return LAE_OK;
+    if (!pred || !scratch) return LAE_ENULL;
+    if (gt_dtype < 0 || gt_dtype > 2 || (gt_channels != 3 && gt_channels != 4)) return LAE_EINVAL;
+    if (!gt && (sse_out || masked_sse_out || gt_out || lpips_in || mask)) return LAE_ENULL;     // these need the ground truth
+    if (masked_sse_out && (!mask || !sse_out)) return LAE_ENULL;
+    if (depth_u8 && !depth) return LAE_ENULL;
+    if ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(depth)) & 15) return LAE_EINVAL;   // float4 loads
+    const size_t esize = gt_dtype == 0 ? 1 : (gt_dtype == 1 ? 2 : 4);
+    const size_t quad_bytes = 4 * gt_channels * esize;
+    const size_t w = quad_bytes % 16 == 0 ? 16 : (quad_bytes % 8 == 0 ? 8 : 4);
+    const bool vec = gt && (reinterpret_cast<uintptr_t>(gt) % w) == 0;
+    const uint32_t quads = (n_pixels + 3) / 4;
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(lae::cdiv(quads, EV_THREADS), EV_MAX_BLOCKS));
+    hipStream_t s = STREAM(stream);
+    EvalOut o{scratch, gt_out, rgb_u8, depth_u8, lpips_in};
+    const bool c4 = gt_channels == 4;
+    if (gt_dtype == 0) { if (c4) launch_eval<uint8_t, 4>(vec, blocks, pred, depth, gt, n_pixels, bg, mask, o, s); else launch_eval<uint8_t, 3>(vec, blocks, pred, depth, gt, n_pixels, bg, mask, o, s); }
+    else if (gt_dtype == 1) { if (c4) launch_eval<_Float16, 4>(vec, blocks, pred, depth, gt, n_pixels, bg, mask, o, s); else launch_eval<_Float16, 3>(vec, blocks, pred, depth, gt, n_pixels, bg, mask, o, s); }
+    else { if (c4) launch_eval<float, 4>(vec, blocks, pred, depth, gt, n_pixels, bg, mask, o, s); else launch_eval<float, 3>(vec, blocks, pred, depth, gt, n_pixels, bg, mask, o, s); }
+    int rc = lae::check_launch("eval_view");
+    if (rc != LAE_OK || !sse_out) return rc;
+    // row 0 of the partials -> sse_out, row 1 -> masked_sse_out
+    k_sum_partials<<<masked_sse_out ? 2 : 1, EV_THREADS, 0, s>>>(scratch, blocks, EV_MAX_BLOCKS, sse_out, masked_sse_out);
+    return lae::check_launch("eval_view_sum");
+}
+
+int lae_lpips_head(uint32_t n_layers, const float* const* feats, const float* const* weights, const uint32_t* channels, const uint32_t* hw,
+                   uint32_t n_pairs, double* scratch, double* out, void* stream) {
+    if (n_pairs == 0) return LAE_OK;
+    if (!feats || !weights || !channels || !hw || !scratch || !out) return LAE_ENULL;
+    if (n_layers == 0 || n_layers > (uint32_t)LP_MAX_LAYERS || n_pairs > 65535u) return LAE_EINVAL;
+    LpipsArgs a{};
+    uint32_t nb = 0;
+    for (uint32_t l = 0; l < n_layers; l++) {
+        if (!feats[l] || !weights[l]) return LAE_ENULL;
+        if (channels[l] == 0 || hw[l] == 0) return LAE_EINVAL;
+        a.f[l] = feats[l]; a.w[l] = weights[l]; a.C[l] = channels[l]; a.hw[l] = hw[l];
+        a.blk0[l] = nb;
+        nb += lae::cdiv(hw[l], EV_THREADS);
+    }
+    a.blk0[n_layers] = nb;
+    a.n_layers = n_layers;
+    hipStream_t s = STREAM(stream);
+    k_lpips_head<<<dim3(nb, n_pairs), EV_THREADS, 0, s>>>(a, nb, scratch);
+    int rc = lae::check_launch("lpips_head");
+    if (rc != LAE_OK) return rc;
+    k_sum_partials<<<n_pairs, EV_THREADS, 0, s>>>(scratch, nb, nb, out, nullptr);     // one block per pair
+    return lae::check_launch("lpips_head_sum");
+}
+
+}  // extern "C"

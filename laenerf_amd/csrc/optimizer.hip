@@ -274,7 +274,7 @@ __global__ __launch_bounds__(256) void k_apply_multi(ApplySegs sg, OptState* __r
 // torch_ema.ExponentialMovingAverage.update() (the trainer's `ema`, nerf/utils.py:407-408, 1502-1503):
 // shadow -= (1 - decay) * (shadow - param), every parameter tensor in one launch
 struct EmaSegs { float* shadow[MAX_SEGS]; const float* param[MAX_SEGS]; size_t n[MAX_SEGS]; int count; };
-__global__ __launch_bounds__(256) void k_ema_multi(EmaSegs sg, float one_minus_decay) {
+__device__ __forceinline__ void ema_segs(const EmaSegs& sg, float one_minus_decay) {
     const size_t stride = (size_t)gridDim.x * 256 * 4;
     for (int s = 0; s < sg.count; s++) {
         float* __restrict__ sh = sg.shadow[s];
@@ -288,6 +288,36 @@ __global__ __launch_bounds__(256) void k_ema_multi(EmaSegs sg, float one_minus_d
             *reinterpret_cast<float4*>(sh + i) = a;
         }
         if (blockIdx.x == 0 && threadIdx.x < n - n4) { const size_t j = n4 + threadIdx.x; sh[j] -= (sh[j] - p[j]) * one_minus_decay; }
+    }
+}
+__global__ __launch_bounds__(256) void k_ema_multi(EmaSegs sg, float one_minus_decay) { ema_segs(sg, one_minus_decay); }
+
+// the same update once per epoch inside a captured training step: every block reads the step counter and the update count,
+// the last block to finish (a ticket in count[1]) advances the count -- after every block has read it
+__global__ __launch_bounds__(256) void k_ema_gated(EmaSegs sg, const int64_t* __restrict__ step, int64_t epoch_len, int32_t* count,
+                                                   double decay, int use_num_updates) {
+    __shared__ float s_omd;
+    __shared__ int s_go;
+    if (threadIdx.x == 0) {
+        const int64_t s = __hip_atomic_load(step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int go = s > 0 && s % epoch_len == 0;
+        if (go) {
+            double d = decay;
+            if (use_num_updates) {                   // torch_ema: num_updates += 1, then min(decay, (1 + n) / (10 + n)) in double
+                const double n = (double)__hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1.0;
+                const double t = (1.0 + n) / (10.0 + n);
+                d = t < decay ? t : decay;
+            }
+            s_omd = (float)(1.0 - d);                // what EMA.update() hands over through ctypes: the fp64 value rounded to fp32
+        }
+        s_go = go;
+    }
+    __syncthreads();
+    if (!s_go) return;
+    ema_segs(sg, s_omd);
+    if (threadIdx.x == 0 && atomicAdd(count + 1, 1) == (int)gridDim.x - 1) {
+        atomicAdd(count, 1);
+        atomicExch(count + 1, 0);
     }
 }
 
@@ -344,6 +374,24 @@ int lae_ema_update_multi(uint32_t n_tensors, float* const* shadows, const float*
     sg.count = (int)n_tensors;
     k_ema_multi<<<stream_blocks(biggest, 4), 256, 0, STREAM(stream)>>>(sg, one_minus_decay);
     return lae::check_launch("ema_update_multi");
+}
+
+int lae_ema_update_gated(uint32_t n_tensors, float* const* shadows, const float* const* params, const uint64_t* sizes, const int64_t* step,
+                         int64_t epoch_len, int32_t* count, double decay, int use_num_updates, void* stream) {
+    if (n_tensors == 0) return LAE_OK;
+    if (!shadows || !params || !sizes || !step || !count) return LAE_ENULL;
+    if (n_tensors > (uint32_t)MAX_SEGS || epoch_len < 1) return LAE_EINVAL;
+    EmaSegs sg{};
+    size_t biggest = 0;
+    for (uint32_t i = 0; i < n_tensors; i++) {
+        if (sizes[i] && (!shadows[i] || !params[i])) return LAE_ENULL;
+        if ((reinterpret_cast<uintptr_t>(shadows[i]) | reinterpret_cast<uintptr_t>(params[i])) & 15) return LAE_EINVAL;
+        sg.shadow[i] = shadows[i]; sg.param[i] = params[i]; sg.n[i] = sizes[i];
+        biggest = std::max(biggest, (size_t)sizes[i]);
+    }
+    sg.count = (int)n_tensors;
+    k_ema_gated<<<stream_blocks(biggest, 4), 256, 0, STREAM(stream)>>>(sg, step, epoch_len, count, decay, use_num_updates);
+    return lae::check_launch("ema_update_gated");
 }
 
 int lae_adam_apply_multi(uint32_t n_tensors, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs, void* const* grads,

@@ -1,0 +1,284 @@
+"""Scoring a trained NeRF on held-out views: PSNR, LPIPS (alex, v0.1), LAENeRF's masked MSE, uint8 test images.
+
+The reference ends training with `trainer.evaluate(test_loader)` and `trainer.test(test_loader)` (main_nerf.py:201-219,
+258-264): every view is rendered with the EMA weights, scored by PSNRMeter and LPIPSMeter(net='alex') (nerf/utils.py:240-247,
+main_nerf.py:203, 242) and written as uint8 PNGs; LAENeRF's GUI adds `eval_masked` (nerf/gui.py:853-947), the MSE outside an
+edit mask.  Here each rendered view goes through ONE kernel (`lae_eval_view`, csrc/evaluate.hip) that reads the render and
+the ground truth in its storage dtype once and writes what is asked: the squared error into a per-view device slot (fp64, fixed
+order: the whole split needs one host read), the masked squared error, uint8 rgb / depth and the LPIPS input.  LPIPS's AlexNet
+trunk is torch modules on MIOpen (plumbing, like the VGG of editing/style_network.py); its distance head over all five layers
+and a batch of view pairs is ONE launch (`lae_lpips_head`).
+
+    lp = load_lpips_alex("alexnet-owt-7be5be79.pth", "alex.pth")     # torchvision trunk + the lpips package's v0.1 heads
+    res = trainer.evaluate_one_epoch(test_data, lpips=lp, masks=load_masks("scene", "test"))
+
+Nothing is downloaded: the weights come from files (or dicts) the user already has.  `LPIPS.random(seed)` builds seeded
+weights for tests and benchmarks.  Parity with the lpips package itself is pinned only by a restatement (tests/lpips_util.py):
+neither the package nor its pretrained weights were available to test against.
+"""
+import ctypes
+import json
+import math
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from ._lib import check, ptr, stream
+
+__all__ = ["LPIPS", "alexnet_trunk", "load_lpips_alex", "load_masks", "eval_view", "eval_view_numpy", "psnr_from_sse",
+           "ALEX_CHANNELS", "ALEX_TAPS", "LPIPS_SHIFT", "LPIPS_SCALE", "EVAL_SCRATCH_DOUBLES"]
+
+ALEX_CHANNELS = (64, 192, 384, 256, 256)
+ALEX_TAPS = (1, 4, 7, 9, 11)                  # relu1..relu5 of torchvision's alexnet().features (lpips' pretrained alexnet slices)
+ALEX_CONVS = {0: (64, 3, 11), 3: (192, 64, 5), 6: (384, 192, 3), 8: (256, 384, 3), 10: (256, 256, 3)}
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)        # lpips ScalingLayer
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+EVAL_SCRATCH_DOUBLES = 2048                   # include/laenerf.h LAE_EVAL_VIEW_SCRATCH_DOUBLES
+_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
+
+
+def alexnet_trunk():
+    """torchvision's alexnet().features[0:12] (ReLU not in place), randomly initialised"""
+    return nn.Sequential(
+        nn.Conv2d(3, 64, kernel_size=11, stride=4, padding=2), nn.ReLU(), nn.MaxPool2d(kernel_size=3, stride=2),
+        nn.Conv2d(64, 192, kernel_size=5, padding=2), nn.ReLU(), nn.MaxPool2d(kernel_size=3, stride=2),
+        nn.Conv2d(192, 384, kernel_size=3, padding=1), nn.ReLU(),
+        nn.Conv2d(384, 256, kernel_size=3, padding=1), nn.ReLU(),
+        nn.Conv2d(256, 256, kernel_size=3, padding=1), nn.ReLU())
+
+
+class LPIPS(nn.Module):
+    """LPIPS(net='alex', version='0.1') with frozen weights: `trunk` = alexnet_trunk(), `lins` = five [C_k] head vectors.
+    `self(x)` takes the scaled input lae_eval_view writes ([2B,3,H,W] or [B,2,3,H,W]: pair p = x0 (the ground truth), then
+    x1) and returns the B distances as float64 on the device."""
+
+    def __init__(self, trunk, lins):
+        super().__init__()
+        if len(trunk) != 12:
+            raise ValueError("LPIPS: the trunk must be alexnet().features[0:12]")
+        if len(lins) != 5 or any(tuple(w.shape) != (c,) for w, c in zip(lins, ALEX_CHANNELS)):
+            raise ValueError(f"LPIPS: the heads must be five vectors of {ALEX_CHANNELS} weights")
+        self.trunk = trunk
+        for k, w in enumerate(lins):
+            self.register_buffer(f"lin{k}", w.detach().float().contiguous().clone())
+        for p in self.trunk.parameters():
+            p.requires_grad_(False)
+        self.eval()
+        self._scratch = {}
+
+    @property
+    def lins(self):
+        return [getattr(self, f"lin{k}") for k in range(5)]
+
+    @classmethod
+    def random(cls, seed=0, device=None):
+        """seeded stand-in weights (uniform within torch's default conv bounds, heads uniform in [0, 1)): tests and benchmarks"""
+        g = torch.Generator().manual_seed(int(seed))
+        trunk = alexnet_trunk()
+        with torch.no_grad():
+            for i, (_, c_in, k) in ALEX_CONVS.items():
+                bound = 1.0 / math.sqrt(c_in * k * k)
+                trunk[i].weight.copy_(torch.rand(trunk[i].weight.shape, generator=g) * 2 * bound - bound)
+                trunk[i].bias.copy_(torch.rand(trunk[i].bias.shape, generator=g) * 2 * bound - bound)
+        m = cls(trunk, [torch.rand(c, generator=g) for c in ALEX_CHANNELS])
+        return m.to(device) if device is not None else m
+
+    @torch.no_grad()
+    def features(self, x):
+        """the five relu taps of the trunk for x [N,3,H,W] (fp32, autocast off) -> list of contiguous [N,C_k,h_k,w_k]"""
+        out = []
+        with torch.autocast("cuda", enabled=False):
+            h = x.float()
+            for i, layer in enumerate(self.trunk):
+                h = layer(h)
+                if i in ALEX_TAPS:
+                    out.append(h.contiguous())
+        return out
+
+    @torch.no_grad()
+    def head(self, feats, out=None):
+        """lpips' distance head on the taps of 2B images (pairs = consecutive rows) -> [B] float64: one launch over the five
+        layers (lae_lpips_head) + one fixed-order sum"""
+        if len(feats) != 5:
+            raise ValueError("LPIPS.head: five feature maps expected")
+        n2 = int(feats[0].shape[0])
+        if n2 % 2:
+            raise ValueError("LPIPS.head: feature maps of 2B images expected")
+        B = n2 // 2
+        for f, c in zip(feats, ALEX_CHANNELS):
+            if f.dim() != 4 or f.shape[0] != n2 or f.shape[1] != c or f.dtype != torch.float32 or not f.is_contiguous():
+                raise ValueError("LPIPS.head: contiguous fp32 [2B, C, h, w] feature maps expected")
+        _lib.need_cuda(*feats, *self.lins)
+        hw = [int(f.shape[2] * f.shape[3]) for f in feats]
+        n_part = B * sum(-(-h // 256) for h in hw)
+        dev = feats[0].device
+        scratch = self._scratch.get((dev, n_part))
+        if scratch is None:
+            scratch = self._scratch[(dev, n_part)] = torch.empty(n_part, dtype=torch.float64, device=dev)
+        if out is None:
+            out = torch.empty(B, dtype=torch.float64, device=dev)
+        if out.dtype != torch.float64 or out.numel() != B or not out.is_contiguous():
+            raise ValueError("LPIPS.head: out must be a contiguous float64 tensor of B values")
+        arr = lambda ts: (ctypes.c_void_p * 5)(*[t.data_ptr() for t in ts])
+        check(_lib.load().lae_lpips_head(5, arr(feats), arr(self.lins), (ctypes.c_uint32 * 5)(*ALEX_CHANNELS),
+                                         (ctypes.c_uint32 * 5)(*hw), B, ptr(scratch), ptr(out), stream()), "lpips_head")
+        return out
+
+    def forward(self, x, out=None):
+        return self.head(self.features(x.reshape(-1, *x.shape[-3:])), out=out)
+
+
+def _state_dict(src):
+    sd = src if isinstance(src, dict) else torch.load(src, map_location="cpu", weights_only=True)
+    if "state_dict" in sd and isinstance(sd["state_dict"], dict):
+        sd = sd["state_dict"]
+    return sd
+
+
+def load_lpips_alex(alexnet_weights, lin_weights, device=None):
+    """LPIPS from weights the user already has: `alexnet_weights` a torchvision `alexnet` state dict (path or dict;
+    `features.{0,3,6,8,10}.weight / .bias`, other keys ignored), `lin_weights` the lpips package's weights/v0.1/alex.pth
+    (`lin{k}.model.1.weight`, [1, C_k, 1, 1]).  Missing keys, keys of layers without weights and wrong shapes raise ValueError."""
+    sd = _state_dict(alexnet_weights)
+    trunk = alexnet_trunk()
+    for k in sd:
+        parts = k.split(".")
+        if len(parts) == 3 and parts[0] == "features" and parts[1].isdigit() and int(parts[1]) < 12:
+            if int(parts[1]) not in ALEX_CONVS or parts[2] not in ("weight", "bias"):
+                raise ValueError(f"load_lpips_alex: unexpected key {k!r} (layer {parts[1]} is {type(trunk[int(parts[1])]).__name__})")
+    for i in ALEX_CONVS:
+        for name in ("weight", "bias"):
+            key = f"features.{i}.{name}"
+            if key not in sd:
+                raise ValueError(f"load_lpips_alex: missing {key!r}")
+            t = torch.as_tensor(sd[key])
+            p = getattr(trunk[i], name)
+            if tuple(t.shape) != tuple(p.shape):
+                raise ValueError(f"load_lpips_alex: {key} has shape {tuple(t.shape)}, AlexNet needs {tuple(p.shape)}")
+            with torch.no_grad():
+                p.copy_(t.float())
+    ld = _state_dict(lin_weights)
+    lins = []
+    for k, c in enumerate(ALEX_CHANNELS):
+        key = f"lin{k}.model.1.weight"
+        if key not in ld:
+            raise ValueError(f"load_lpips_alex: missing {key!r}")
+        t = torch.as_tensor(ld[key])
+        if tuple(t.shape) != (1, c, 1, 1):
+            raise ValueError(f"load_lpips_alex: {key} has shape {tuple(t.shape)}, the v0.1 alex head needs {(1, c, 1, 1)}")
+        lins.append(t.float().reshape(c))
+    m = LPIPS(trunk, lins)
+    return m.to(device) if device is not None else m
+
+
+def _mask_plane(im):
+    """the reference's `mask[..., -1]` of a cv2.IMREAD_UNCHANGED read (BGR / BGRA order: alpha, else red) as one uint8 plane;
+    a one-channel mask is taken as it is"""
+    if im.mode in ("RGBA", "LA", "PA") or (im.mode == "P" and "transparency" in im.info):
+        return im.convert("RGBA").getchannel("A")
+    if im.mode in ("RGB", "P", "CMYK", "YCbCr"):
+        return im.convert("RGB").getchannel("R")
+    return im.convert("L")
+
+
+def load_masks(transforms_path, split=None, H=None, W=None, device=None):
+    """the `<image>_mask.png` beside each frame of a blender-style scene (provider.py:216-223) -> a list with one uint8 [H, W]
+    tensor per frame (None where the frame has no mask), in the frame order of ResidentImages.from_transforms (frames whose
+    image is missing are skipped there and here).  A mask of another size is resized to H x W (default: its image's size) with
+    PIL's bilinear filter (the reference: cv2.resize, also bilinear; the two can differ at the mask's edge)."""
+    from PIL import Image
+    path = transforms_path
+    if os.path.isdir(path):
+        path = os.path.join(path, f"transforms_{split}.json" if split else "transforms.json")
+    root = os.path.dirname(os.path.abspath(path))
+    with open(path) as f:
+        frames = json.load(f)["frames"]
+    out = []
+    for fr in frames:
+        f_path = os.path.join(root, fr["file_path"])
+        if "." not in os.path.basename(f_path):
+            f_path += ".png"
+        if not os.path.exists(f_path):
+            continue
+        m_path = os.path.splitext(f_path)[0] + "_mask.png"
+        if not os.path.exists(m_path):
+            out.append(None)
+            continue
+        if H is None or W is None:
+            with Image.open(f_path) as im:
+                h, w = im.height, im.width
+        else:
+            h, w = int(H), int(W)
+        with Image.open(m_path) as im:
+            m = _mask_plane(im)
+            if (m.height, m.width) != (h, w):
+                m = m.resize((w, h), Image.BILINEAR)
+            t = torch.from_numpy(np.asarray(m, dtype=np.uint8).copy())
+        out.append(t.to(device) if device is not None else t)
+    return out
+
+
+def psnr_from_sse(sse, n_values):
+    """PSNRMeter (nerf/utils.py:240-247): -10 log10(sse / n_values), elementwise"""
+    return -10.0 * np.log10(np.maximum(np.asarray(sse, dtype=np.float64) / float(n_values), 1e-20))
+
+
+def eval_view(pred, gt, depth=None, bg=1.0, sse=None, mask=None, masked_sse=None, gt_out=None, rgb_u8=None, depth_u8=None,
+              lpips_in=None, scratch=None):
+    """one rendered view against its ground truth in one pass (lae_eval_view).  pred fp32 with HW*3 values, gt the view's
+    stored image (uint8 / fp16 / fp32, HW*C values, C = 3 or 4; read as stored, no fp32 copy) or None, depth fp32 [HW].
+    Outputs, each optional and written in place:
+      sse        float64 slot: the sum over HW*3 of (pred - gt)^2, gt blended over `bg` when C = 4
+      masked_sse float64 slot (with `mask`, uint8 [HW]): the same sum against the UNblended gt[:3], over the pixels whose mask
+                 byte is 0 -- eval_masked's m = 1 - clip(mask[..., -1], 0, 1), its mean times 3HW
+      gt_out     fp32 [HW,3], the blended ground truth
+      rgb_u8 / depth_u8  clip(x, 0, 1) * 255 truncated (the reference's unclipped astype(np.uint8) is undefined outside [0,1])
+      lpips_in   fp32 [2,3,H,W]: index 0 the blended gt, 1 pred, each ((2x - 1) - shift) / scale (lpips' ScalingLayer)"""
+    lib = _lib.load()
+    HW = pred.numel() // 3
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.numel() != 3 * HW:
+        raise ValueError("eval_view: pred must be a contiguous fp32 tensor of HW x 3 values")
+    C = 3
+    if gt is not None:
+        C = int(gt.shape[-1])
+        if gt.dtype not in _DTYPES or C not in (3, 4) or gt.numel() != HW * C or not gt.is_contiguous():
+            raise ValueError("eval_view: gt must be a contiguous uint8 / fp16 / fp32 image of HW x 3 or 4 values")
+    for name, t, dt, n in (("depth", depth, torch.float32, HW), ("mask", mask, torch.uint8, HW), ("gt_out", gt_out, torch.float32, 3 * HW),
+                           ("rgb_u8", rgb_u8, torch.uint8, 3 * HW), ("depth_u8", depth_u8, torch.uint8, HW),
+                           ("lpips_in", lpips_in, torch.float32, 6 * HW), ("sse", sse, torch.float64, 1),
+                           ("masked_sse", masked_sse, torch.float64, 1)):
+        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"eval_view: {name} must be a contiguous {dt} tensor of {n} values")
+    if scratch is None:
+        scratch = torch.empty(EVAL_SCRATCH_DOUBLES, dtype=torch.float64, device=pred.device)
+    _lib.need_cuda(pred, gt, depth, mask, gt_out, rgb_u8, depth_u8, lpips_in, sse, masked_sse, scratch)
+    check(lib.lae_eval_view(ptr(pred), ptr(depth), ptr(gt), _DTYPES[gt.dtype] if gt is not None else 0, C, HW, float(bg),
+                            ptr(mask), ptr(scratch), ptr(sse), ptr(masked_sse), ptr(gt_out), ptr(rgb_u8), ptr(depth_u8), ptr(lpips_in),
+                            stream()), "eval_view")
+
+
+def eval_view_numpy(pred, gt, depth=None, bg=1.0, mask=None):
+    """numpy restatement of lae_eval_view -> dict gt (blended, fp32 [HW,3]), sse, masked_sse (fp64 sums; None without a
+    mask), rgb_u8 [HW,3], depth_u8 [HW] (None without depth), lpips_in [2,3,HW] fp32"""
+    f32 = np.float32
+    pred = np.asarray(pred, dtype=f32).reshape(-1, 3)
+    HW = pred.shape[0]
+    g = np.asarray(gt)
+    g = g.reshape(HW, g.shape[-1])
+    x = g.astype(f32) * (f32(1.0) / f32(255.0)) if g.dtype == np.uint8 else g.astype(f32)
+    raw = x[:, :3]
+    blend = raw * x[:, 3:] + f32(bg) * (f32(1.0) - x[:, 3:]) if g.shape[1] == 4 else raw.copy()
+    p64 = pred.astype(np.float64)
+    out = {"gt": blend, "sse": float(((p64 - blend.astype(np.float64)) ** 2).sum()), "masked_sse": None, "depth_u8": None}
+    if mask is not None:
+        m = (np.asarray(mask, dtype=np.uint8).reshape(HW) == 0)[:, None]
+        out["masked_sse"] = float((((p64 - raw.astype(np.float64)) ** 2) * m).sum())
+    out["rgb_u8"] = (np.clip(pred, f32(0), f32(1)) * f32(255)).astype(np.uint8)
+    if depth is not None:
+        out["depth_u8"] = (np.clip(np.asarray(depth, dtype=f32).reshape(HW), f32(0), f32(1)) * f32(255)).astype(np.uint8)
+    shift, scale = np.array(LPIPS_SHIFT, f32)[:, None], np.array(LPIPS_SCALE, f32)[:, None]
+    out["lpips_in"] = np.stack([((f32(2) * v.T - f32(1)) - shift) / scale for v in (blend, pred)]).astype(f32)
+    return out

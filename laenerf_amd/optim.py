@@ -18,6 +18,7 @@ device; `state_dict()` / `load_state_dict()` are torch.optim.Adam's (`state[i] =
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -315,6 +316,7 @@ class EMA:
         self.num_updates = 0 if use_num_updates else None
         self.shadow_params = [p.detach().clone() for p in self.params]
         self.collected_params = None
+        self._dev_count = None                                # update_gated's count on the device (device_count())
         n = len(self.params)
         self._n = n
         self._shadows = (ctypes.c_void_p * n)(*[t.data_ptr() for t in self.shadow_params])
@@ -331,6 +333,32 @@ class EMA:
             self._params = (ctypes.c_void_p * self._n)(*[p.data_ptr() for p in self.params])
         _lib.check(_lib.load().lae_ema_update_multi(self._n, self._shadows, self._params, self._sizes, float(1.0 - decay), _lib.stream()),
                    "ema_update")
+
+    def device_count(self):
+        """the count update_gated() keeps on the device: int32 [number of updates, block ticket], created from num_updates on the
+        first call (which must come before any stream capture)"""
+        if self._dev_count is None:
+            self._dev_count = torch.tensor([self.num_updates or 0, 0], dtype=torch.int32, device=self.params[0].device)
+        return self._dev_count
+
+    @torch.no_grad()
+    def update_gated(self, step, epoch_len):
+        """update() after the step whose 1-based index, the int64 device counter `step`, is a multiple of epoch_len, and nothing
+        after any other step: one launch that decides on the device (lae_ema_update_gated), so it can sit in a captured graph.
+        decay_t is update()'s, computed in fp64 from the device count (ema_one_minus_decay restates it); num_updates follows
+        the device count in state_dict()."""
+        if self._dev_count is None and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("EMA.update_gated: call device_count() before the capture")
+        if not torch.is_tensor(step) or step.dtype != torch.int64 or step.numel() != 1 or not step.is_cuda:
+            raise ValueError("EMA.update_gated: step must be an int64 device counter of one value")
+        if int(epoch_len) < 1:
+            raise ValueError("EMA.update_gated: epoch_len must be at least 1")
+        cnt = self.device_count()
+        if [p.data_ptr() for p in self.params] != list(self._params):
+            self._params = (ctypes.c_void_p * self._n)(*[p.data_ptr() for p in self.params])
+        _lib.check(_lib.load().lae_ema_update_gated(self._n, self._shadows, self._params, self._sizes, step.data_ptr(), int(epoch_len),
+                                                    cnt.data_ptr(), float(self.decay), int(self.num_updates is not None), _lib.stream()),
+                   "ema_update_gated")
 
     @torch.no_grad()
     def store(self):
@@ -350,6 +378,8 @@ class EMA:
         self.collected_params = None
 
     def state_dict(self):
+        if self._dev_count is not None and self.num_updates is not None:
+            self.num_updates = int(self._dev_count[0].item())
         return {"decay": self.decay, "num_updates": self.num_updates, "shadow_params": [t.clone() for t in self.shadow_params],
                 "collected_params": None if self.collected_params is None else [t.clone() for t in self.collected_params]}
 
@@ -359,3 +389,17 @@ class EMA:
             t.copy_(src.to(t.device))
         cp = sd.get("collected_params")
         self.collected_params = None if cp is None else [c.to(p.device).clone() for c, p in zip(cp, self.params)]
+        if self._dev_count is not None:
+            self._dev_count[0] = int(self.num_updates or 0)
+
+
+def ema_update_steps(start, n_steps, epoch_len):
+    """the 1-based global step indices among start + 1 .. start + n_steps after which EMA.update_gated updates"""
+    return [s for s in range(start + 1, start + n_steps + 1) if s % epoch_len == 0]
+
+
+def ema_one_minus_decay(decay, num_updates, use_num_updates=True):
+    """the fp32 factor of the num_updates-th update (counted from 1): update() computes it on the host, update_gated() on
+    the device, both as float32(1 - min(decay, (1 + n) / (10 + n))) with the min and the subtraction in fp64"""
+    d = min(decay, (1 + num_updates) / (10 + num_updates)) if use_num_updates else decay
+    return np.float32(1.0 - d)

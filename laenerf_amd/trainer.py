@@ -24,11 +24,14 @@ never updated; the reference has no such mode.  LAENeRF's --use_error_maps seeds
 (laenerf_amd.editing.distill).  Both kernels read and write only device memory, so they run inside the captured group like
 the rest of the step.
 """
+import contextlib
 import math
+import os
 
 import numpy as np
 import torch
 
+from .optim import EMA
 from .raymarching import raymarching
 
 __all__ = ["Trainer", "lr_schedule", "bucket_capacity", "psnr"]
@@ -63,6 +66,24 @@ def psnr(pred, gt):
     return -10.0 * math.log10(max(mse, 1e-20))
 
 
+class _TrainerEMA(EMA):
+    """the Trainer's EMA of the renderer's parameters (the reference's ema_decay, main_nerf.py:244).  copy_to() and restore()
+    re-derive the optimizer's fp16 shadow tables: a graph replay reads them without the version check of an eager forward."""
+
+    def __init__(self, renderer, optimizer, decay):
+        super().__init__(renderer.parameters(), decay)
+        self._opt = optimizer
+        self.device_count()
+
+    def copy_to(self):
+        super().copy_to()
+        self._opt.sync_shadows()
+
+    def restore(self):
+        super().restore()
+        self._opt.sync_shadows()
+
+
 class Trainer:
     """Trainer(renderer, optimizer, data, iters, lr): `optimizer` is a FusedAdam over the renderer's network (its device
     learning rates are taken over: device_lr is switched on), `data` a ResidentImages, `iters` the decay horizon of the
@@ -70,11 +91,15 @@ class Trainer:
     graph=False runs the same steps eagerly; capacity 'bucket' / 'exact' (see the module docstring).
     error_map: None (uniform pixels), 'ema' (drawn by the data's error map, updated after every step) or 'fixed' (drawn by
     it, never updated); a map of ones is created on the data when it has none.
+    ema_decay: None (no EMA, nothing added to a step) or the decay of an EMA of the renderer's parameters (`self.ema`), updated
+    after every step whose 1-based global index is a multiple of epoch_len (default data.n_img: the reference's epoch of one
+    image per batch, nerf/utils.py:1502-1503) by one gated launch inside the captured group; evaluate_one_epoch / test render
+    with it swapped in.
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
     def __init__(self, renderer, optimizer, data, iters, lr, num_rays=4096, seed=0, graph=True, capacity="bucket",
-                 max_steps=1024, dt_gamma=0.0, error_map=None):
+                 max_steps=1024, dt_gamma=0.0, error_map=None, ema_decay=None, epoch_len=None):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
         if error_map not in (None, "ema", "fixed"):
@@ -101,6 +126,10 @@ class Trainer:
         self._rows_seen = 0
         self.captures = self.cache_misses = self.warm_groups = 0
         self._loss_hist = []
+        self.epoch_len = int(epoch_len) if epoch_len is not None else data.n_img
+        if self.epoch_len < 1:
+            raise ValueError("Trainer: epoch_len must be at least 1")
+        self.ema = None if ema_decay is None else _TrainerEMA(renderer, optimizer, float(ema_decay))
 
     # ------------------------------------------------------------------ one step
     def _m(self):
@@ -137,6 +166,8 @@ class Trainer:
         loss = res["loss"]
         opt.backward(loss)
         opt.step()
+        if self.ema is not None:
+            self.ema.update_gated(self.data.step, self.epoch_len)      # sample() has advanced the counter to this step's index
         with torch.no_grad():
             self.loss_slots[k].copy_(loss.unscaled.view(()))
 
@@ -233,3 +264,102 @@ class Trainer:
         finally:
             r.model.train(was_training)
         return float(np.mean(vals))
+
+    @contextlib.contextmanager
+    def _eval_weights(self):
+        """the model in eval mode with the EMA weights swapped in (nerf/utils.py:1539-1541), both undone afterwards"""
+        r = self.r
+        was_training = r.model.training
+        if self.ema is not None:
+            self.ema.store()
+            self.ema.copy_to()
+        r.model.eval()
+        try:
+            yield
+        finally:
+            r.model.train(was_training)
+            if self.ema is not None:
+                self.ema.restore()
+
+    def _render_view(self, data, i, scale_depth):
+        """eval_step / test_step's render of view i (bg_color 1, perturb False) -> image [HW,3], depth [HW] fp32"""
+        from .rays import get_rays
+        if data.color_space == "linear":
+            raise NotImplementedError("Trainer: color_space='linear' data is not supported here (every shipped config uses srgb)")
+        ray = get_rays(data.poses[i:i + 1], data.intrinsics, data.H, data.W)
+        with torch.autocast("cuda", dtype=torch.float16):
+            res = self.r.render_eval(ray["rays_o"][0], ray["rays_d"][0], bg_color=1.0, perturb=False, scale_depth=scale_depth,
+                                     image_hw=(data.H, data.W))
+        return res["image"].float().contiguous(), res["depth"].float().contiguous()
+
+    @staticmethod
+    def _write_pngs(out_dir, name, i, rgb_u8, depth_u8):
+        from PIL import Image
+        os.makedirs(out_dir, exist_ok=True)
+        Image.fromarray(rgb_u8.cpu().numpy()).save(os.path.join(out_dir, f"{name}_{i:04d}_rgb.png"))
+        Image.fromarray(depth_u8.cpu().numpy()).save(os.path.join(out_dir, f"{name}_{i:04d}_depth.png"))
+
+    @torch.no_grad()
+    def evaluate_one_epoch(self, data, lpips=None, masks=None, out_dir=None, name="ngp"):
+        """the reference's evaluate_one_epoch (nerf/utils.py:1526-1624, eval_step :674-698) over every view of `data` (a
+        ResidentImages): rendered with the EMA weights over white, scale_depth=False; per view one lae_eval_view pass (PSNRMeter's
+        squared error into a device slot; with `lpips` (metrics.LPIPS) its input, then the trunk and the head; with `masks` (a list
+        of uint8 [H, W] or None per view, metrics.load_masks) eval_masked's MSE); one host read for the whole split.  out_dir:
+        `{name}_{i:04d}_rgb.png` / `_depth.png` (uint8, clipped).  -> dict psnr [n], lpips [n] or None, masked_mse [n] (NaN where
+        a view has no mask) or None, mean_psnr, mean_lpips, mean_masked_mse (over the views with a mask)"""
+        from . import metrics as M
+        n, H, W = data.n_img, data.H, data.W
+        if masks is not None and len(masks) != n:
+            raise ValueError("evaluate_one_epoch: one mask (or None) per view expected")
+        dev = data.images.device
+        sums = torch.zeros(n, 2, dtype=torch.float64, device=dev)
+        scratch = torch.empty(M.EVAL_SCRATCH_DOUBLES, dtype=torch.float64, device=dev)
+        lp = torch.zeros(n, dtype=torch.float64, device=dev) if lpips is not None else None
+        lp_in = torch.empty(2, 3, H, W, dtype=torch.float32, device=dev) if lpips is not None else None
+        rgb_u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if out_dir else None
+        depth_u8 = torch.empty(H, W, dtype=torch.uint8, device=dev) if out_dir else None
+        has_mask = np.zeros(n, bool)
+        with self._eval_weights():
+            for i in range(n):
+                m = None if masks is None else masks[i]
+                if m is not None:
+                    m = m.to(dev, torch.uint8).contiguous()
+                    if m.numel() != H * W:
+                        raise ValueError(f"evaluate_one_epoch: mask {i} must have H x W = {H} x {W} values")
+                    has_mask[i] = True
+                pred, depth = self._render_view(data, i, scale_depth=False)
+                M.eval_view(pred, data.images[i], depth=depth, bg=1.0, sse=sums[i, 0:1], mask=m,
+                            masked_sse=sums[i, 1:2] if m is not None else None, rgb_u8=rgb_u8, depth_u8=depth_u8, lpips_in=lp_in,
+                            scratch=scratch)
+                if lpips is not None:
+                    lpips(lp_in, out=lp[i:i + 1])
+                if out_dir:
+                    self._write_pngs(out_dir, name, i, rgb_u8, depth_u8)
+        s = sums.cpu().numpy()
+        res = {"psnr": M.psnr_from_sse(s[:, 0], 3 * H * W), "lpips": None if lp is None else lp.cpu().numpy(), "masked_mse": None}
+        if masks is not None:
+            res["masked_mse"] = np.where(has_mask, s[:, 1] / (3 * H * W), np.nan)
+        res["mean_psnr"] = float(np.mean(res["psnr"]))
+        res["mean_lpips"] = None if lp is None else float(np.mean(res["lpips"]))
+        res["mean_masked_mse"] = float(np.mean(res["masked_mse"][has_mask])) if has_mask.any() else None
+        return res
+
+    @torch.no_grad()
+    def test(self, data, out_dir=None, name="ngp"):
+        """the reference's test (nerf/utils.py:777-827, test_step :701-719): every view of `data` rendered with the EMA weights
+        over white, scale_depth=True -> rgb [n, H, W, 3] and depth [n, H, W] uint8 on the device (clip to [0,1], * 255, truncate);
+        out_dir: the same as `{name}_{i:04d}_rgb.png` / `_depth.png`"""
+        from . import metrics as M
+        n, H, W = data.n_img, data.H, data.W
+        dev = data.images.device
+        rgb = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
+        depth = torch.empty(n, H, W, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(M.EVAL_SCRATCH_DOUBLES, dtype=torch.float64, device=dev)
+        with self._eval_weights():
+            for i in range(n):
+                pred, d = self._render_view(data, i, scale_depth=True)
+                M.eval_view(pred, None, depth=d, rgb_u8=rgb[i], depth_u8=depth[i], scratch=scratch)
+        if out_dir:
+            for i in range(n):
+                self._write_pngs(out_dir, name, i, rgb[i], depth[i])
+        return rgb, depth

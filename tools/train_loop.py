@@ -5,7 +5,7 @@ RGBA views from cameras on a sphere: colour = image over a black background / we
 weights_sum; 8-bit like a real dataset.  A fresh student trains on them with the reference's loop (random background,
 refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated on held-out views over white.
 
-    python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed]
+    python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed] [--ema]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
 ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR."""
@@ -54,7 +54,7 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
 
 
 def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=True, capacity="bucket", seed=0, student_seed=0,
-                 error_map=None):
+                 error_map=None, ema_decay=None):
     from laenerf_amd.data import ResidentImages
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.optim import FusedAdam
@@ -65,7 +65,8 @@ def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=Tr
     r = NeRFRenderer(net, bound=1, density_thresh=10).to(dev)
     opt = FusedAdam(net, param_groups=net.get_params(lr), betas=(0.9, 0.99), eps=1e-15, device_lr=True)
     data = ResidentImages.from_arrays(images, poses, intr, bg="random", device=dev)
-    return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map)
+    return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map,
+                   ema_decay=ema_decay)
 
 
 def main():
@@ -77,6 +78,7 @@ def main():
     ap.add_argument("--views", type=int, default=28)
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--error-map", default="none", choices=["none", "ema", "fixed"])
+    ap.add_argument("--ema", action="store_true", help="Trainer(ema_decay=0.95): the gated EMA update in every step")
     args = ap.parse_args()
     error_map = None if args.error_map == "none" else args.error_map
     dev = torch.device("cuda:0")
@@ -85,7 +87,7 @@ def main():
     images, poses, intr = teacher_views(dev, args.views, args.res, args.res)
     held = 4
     tr = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
-                      capacity=args.capacity, error_map=error_map)
+                      capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     tr.train(64)
@@ -116,7 +118,8 @@ def main():
         "ms_per_step_all_in": round(all_in, 4), "ms_per_step_after_64": round(steady, 4), "steps": args.steps, "rays": args.rays,
         "ratio_to_headline": round(all_in / HEADLINE_MS, 3), "ratio_after_64_to_headline": round(steady / HEADLINE_MS, 3),
         "headline_ms": HEADLINE_MS, "graph": not args.no_graph, "capacity": args.capacity,
-        **({"error_map": args.error_map} if error_map is not None else {}), "captures": tr.captures,
+        **({"error_map": args.error_map} if error_map is not None else {}), **({"ema_decay": 0.95} if args.ema else {}),
+        "captures": tr.captures,
         "cache_misses": tr.cache_misses, "warm_groups": tr.warm_groups, "capacities": sorted(tr.graphs),
         "mean_count": tr.r.mean_count, "steps_skipped": tr.steps_skipped, "heldout_psnr_white": round(p, 3),
         "final_loss": float(tr.losses()[-16:].mean()),
