@@ -78,7 +78,7 @@ extern "C" {
  * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi14"
+#define LAE_ABI_TAG "abi15"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -410,7 +410,8 @@ LAE_API int lae_grid_encode_backward_ex(const void* grad, const float* inputs, c
                                 void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
                                 uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype,
                                 int align_corners, uint32_t interp, int dtype, int blc, float in_shift, float in_scale,
-                                const int32_t* offsets_host, int32_t* nonfinite_flag, uint32_t* touched_lines, void* stream);
+                                const int32_t* offsets_host, int32_t* nonfinite_flag, uint32_t* touched_lines, uint32_t* grad_dirty,
+                                void* stream);
 /* nonfinite_flag (may be NULL): device word that is OR-ed with 1 when this call STORES a non-finite value into
  * grad_embeddings (an overflowed sum, a non-finite contribution, or a non-finite value already there that it adds to).  A
  * caller whose gradient buffer is written by these calls only can hand the optimizer's found_inf word (state word 2 of
@@ -420,7 +421,12 @@ LAE_API int lae_grid_encode_backward_ex(const void* grad, const float* inputs, c
  * 8 * (32 w + k) ... + 7, i.e. one 64-byte line of the fp32 table); the counting half of the call sets the bits of the lines
  * that hold a corner of a cell some sample lies in (a superset of the lines that receive a non-zero gradient).
  * lae_adam_apply_multi skips lines whose bit was never set (their gradient and both Adam moments are exactly zero).  With
- * the two-call form the bitmap goes to lae_grid_encode_backward_plan (the counting half), not to _planned. */
+ * the two-call form the bitmap goes to lae_grid_encode_backward_plan (the counting half), not to _planned.
+ * grad_dirty (may be NULL = "may hold anything"): one device word per gradient accumulator, 0 = grad_embeddings holds nothing but
+ * zeros.  The call hands the word's value to its accumulate pass and sets the word to 1 (the generic atomic kernel just sets it);
+ * on 0 the binned fp16 pass does not read the old value of the entries it stores (16 KB per 4096-entry partition) and stores
+ * RN(sum), which is what RN(0 + sum) gives: same bits.  lae_adam_apply_multi(grad_dirty) sets the word back to 0 for the
+ * gradients it has zeroed.  Whoever else writes grad_embeddings sets the word to 1; whoever zeroes it may set it to 0. */
 
 /* MI355X-native: the binned backward (D = 3, C = 2) in two halves.  Its first half -- the bookkeeping of a counting
  * sort: items per (level, 1024 samples, table partition), their scans -- depends on the sample positions only,
@@ -443,7 +449,8 @@ LAE_API int lae_grid_encode_backward_plan(const float* inputs, const int32_t* of
 LAE_API int lae_grid_encode_backward_planned(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings,
                                      uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
                                      int align_corners, uint32_t interp, int dtype, float in_shift, float in_scale,
-                                     const int32_t* offsets_host, const void* plan, int32_t* nonfinite_flag, void* stream);
+                                     const int32_t* offsets_host, const void* plan, int32_t* nonfinite_flag, uint32_t* grad_dirty,
+                                     void* stream);
 
 /* Bytes of LIBRARY workspace the binned backward (D = 3, C = 2) takes for B samples and L levels when it runs both halves
  * itself: the plan + the item queue, sized for the worst case of 8 items per (sample, level) at 10 bytes each for fp16
@@ -556,6 +563,24 @@ LAE_API int lae_nerf_head_backward(const float* grad_sigmas, const float* grad_r
 /* loss_out != NULL (round 3): the launch that reduces the weight-gradient slabs carries one workgroup more, which finishes a
  * loss value deferred by lae_composite_rays_train_step(defer_loss): loss_out[0] = sum(loss_partials[0 .. loss_n_part)) /
  * loss_n_elem * (*loss_scale, or 1 when NULL), loss_out[1] = the same unscaled -- the bits lae_loss_finish would write. */
+
+/* Backward of the whole field (hash grid D = 3, C = 2, fp16 table -> lae_nerf_head_forward with enc_level_major) in one call:
+ * lae_nerf_head_backward(enc_level_major = 1) followed by lae_grid_encode_backward_ex (plan == NULL) or _planned on grad_enc
+ * [L, M, 2].  The arguments are those of the two calls; weights_nonfinite_flag / table_nonfinite_flag are their nonfinite_flag
+ * words (may be the same word), touched_lines is ignored with a plan (it went to lae_grid_encode_backward_plan).  Where the
+ * binned pipeline runs (L <= 32, M <= 2^24, backward mode 0) the launch that reduces the weight-gradient slabs (and finishes the
+ * deferred loss) is not made: its workgroups ride as tail tasks in the grid backward's accumulate pass, behind the partition
+ * tasks.  Every result has the bits the two calls give.  LAE_FIELD_NO_RIDE_ALONG=1 in the environment (read at every call) makes
+ * the two calls as they are: an A/B switch.  Invalid arguments of either half are refused before the first launch. */
+LAE_API int lae_nerf_field_backward(const float* grad_sigmas, const float* grad_rgbs, const void* enc, const float* dirs, const void* h,
+                            const float* rgbs, const void* sigma_weights, const void* color_weights, uint32_t M, float density_scale,
+                            void* grad_h, void* grad_enc, void* grad_sigma_weights, void* grad_color_weights,
+                            int accumulate_weight_grads, int32_t* weights_nonfinite_flag, const float* loss_partials,
+                            uint32_t loss_n_part, uint32_t loss_n_elem, const float* loss_scale, float* loss_out,
+                            const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t L, float S, uint32_t H,
+                            uint32_t gridtype, int align_corners, uint32_t interp, float in_shift, float in_scale,
+                            const int32_t* offsets_host, const void* plan, int32_t* table_nonfinite_flag, uint32_t* touched_lines,
+                            uint32_t* grad_dirty, void* stream);
 
 /* ---- freqencoder (freqencoder/src/freqencoder.h:6-10; bindings.cpp:5-8) ----
  * outputs [B, C], C = D + 2*D*deg: the input, then per frequency f < deg the D sines and D cosines of x * 2^f.
@@ -889,12 +914,14 @@ LAE_API int lae_mse_loss_forward(const float* pred, const float* target, uint32_
 /* multi-tensor forms of check / apply: host arrays of n_tensors (<= 8) device pointers / sizes; one launch each.
  * touched_lines (may be NULL, entries may be NULL): per tensor the bitmap lae_grid_encode_backward_ex maintains (one bit per 16
  * parameters); with weight_decay == 0 a line whose bit is clear is neither read nor written -- Adam's update of parameters whose
- * gradient, exp_avg and exp_avg_sq are all zero is exactly zero. */
+ * gradient, exp_avg and exp_avg_sq are all zero is exactly zero.
+ * grad_dirty (may be NULL, entries may be NULL): per tensor the "dirty" word of its gradient accumulator
+ * (lae_grid_encode_backward_ex); apply leaves every gradient zero and sets the words to 0. */
 LAE_API int lae_adam_check_multi(uint32_t n_tensors, const void* const* grads, const int* grad_is_half, const uint64_t* sizes, void* state,
                          void* stream);
 LAE_API int lae_adam_apply_multi(uint32_t n_tensors, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs, void* const* grads,
                          const int* grad_is_half, void* const* shadows_half, const uint64_t* sizes, const float* const* lrs, const void* const* touched_lines,
-                         const void* state, float beta1, float beta2, float eps, float weight_decay, void* stream);
+                         void* const* grad_dirty, const void* state, float beta1, float beta2, float eps, float weight_decay, void* stream);
 
 /* torch_ema.ExponentialMovingAverage.update() of the reference's trainer (nerf/utils.py:407-408 construct, :1502-1503 update once per
  * epoch; decay 0.95, main_nerf.py:244): shadow -= one_minus_decay * (shadow - param) for up to 8 fp32 tensors in one launch.  The

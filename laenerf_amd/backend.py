@@ -458,11 +458,12 @@ class _GridEncoder:
     @staticmethod
     def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs,
                              gridtype, align_corners, interp, blc=False, in_map=(0.0, 1.0), offsets_host=None, plan=None,
-                             nonfinite_flag=None, touched_lines=None):
+                             nonfinite_flag=None, touched_lines=None, grad_dirty=None):
         """plan (MI355X extension): result of grid_backward_plan for the same inputs -- skips the count pass and scans.
         nonfinite_flag: address (int) of a device int32 that is OR-ed with 1 when the call stores a non-finite table gradient;
         touched_lines: address (int) of the "ever touched" bitmap, one bit per 8 table entries (include/laenerf.h: binned
-        pipeline only)"""
+        pipeline only); grad_dirty: address (int) of grad_embeddings' "dirty" word (0 = all zeros: no old values are read), which
+        the call sets to 1 -- None: grad_embeddings may hold anything"""
         ts = (grad, inputs, embeddings, offsets, grad_embeddings, dy_dx, grad_inputs, plan)
         need_cuda(*ts); need_contig(*ts)
         if grad.dtype != grad_embeddings.dtype:
@@ -475,14 +476,15 @@ class _GridEncoder:
                 raise RuntimeError("grid_encode_backward: the plan was made without the touched-lines bitmap (pass it to grid_backward_plan)")
             check(lib.lae_grid_encode_backward_planned(ptr(grad), ptr(inputs), ptr(offsets), ptr(grad_embeddings), B, D, C, L, float(S), H,
                                                        gridtype, int(bool(align_corners)), interp, _dtype_code(grad), float(in_map[0]),
-                                                       float(in_map[1]), _host_i32(offsets_host, L + 1), ptr(plan), nonfinite_flag, stream()),
+                                                       float(in_map[1]), _host_i32(offsets_host, L + 1), ptr(plan), nonfinite_flag, grad_dirty, stream()),
                   "grid_encode_backward")
             return
         args = (ptr(grad), ptr(inputs), ptr(embeddings), ptr(offsets), ptr(grad_embeddings), B, D, C, L, float(S), H,
                 ptr(dy_dx), ptr(grad_inputs), gridtype, int(bool(align_corners)), interp, _dtype_code(grad))
-        if blc or tuple(in_map) != (0.0, 1.0) or offsets_host is not None or nonfinite_flag is not None or touched_lines is not None:
+        if (blc or tuple(in_map) != (0.0, 1.0) or offsets_host is not None or nonfinite_flag is not None or touched_lines is not None
+                or grad_dirty is not None):
             check(lib.lae_grid_encode_backward_ex(*args, int(bool(blc)), float(in_map[0]), float(in_map[1]), _host_i32(offsets_host, L + 1),
-                                                  nonfinite_flag, touched_lines, stream()), "grid_encode_backward")
+                                                  nonfinite_flag, touched_lines, grad_dirty, stream()), "grid_encode_backward")
         else:
             check(lib.lae_grid_encode_backward(*args, stream()), "grid_encode_backward")
 
@@ -605,27 +607,61 @@ class _FFMLP:
               grad_sigma_weights, grad_color_weights)
         need_cuda(*ts); need_contig(*ts)
         _FFMLP._half(enc, h, sigma_weights, color_weights, grad_h, grad_enc, grad_sigma_weights, grad_color_weights)
-        # the deferred loss value of the criterion node whose gradient THIS call consumes rides in the reduction launch -- only on
-        # the stream its partials were written on (another stream gives no ordering against them)
+        _FFMLP._with_pending_loss(grad_sigmas, lambda lp, ln, le, lsc, lo: check(_lib.load().lae_nerf_head_backward(
+            ptr(grad_sigmas), ptr(grad_rgbs), ptr(enc), ptr(dirs), ptr(h), ptr(rgbs), ptr(sigma_weights), ptr(color_weights), M,
+            float(density_scale), ptr(grad_h), ptr(grad_enc), ptr(grad_sigma_weights), ptr(grad_color_weights), int(bool(accumulate)),
+            int(bool(level_major)), nonfinite_flag, ptr(lp), ln, le, ptr(lsc), ptr(lo), stream()), "nerf_head_backward"))
+
+    @staticmethod
+    def _with_pending_loss(grad_sigmas, call):
+        """call(loss_partials, n_part, n_elem, loss_scale, loss_out) with the deferred loss value of the criterion node whose
+        gradient the head backward consumes (it rides in the reduction of the weight-gradient slabs) -- only on the stream its
+        partials were written on (another stream gives no ordering against them)"""
         key = _loss_key(grad_sigmas)
         pend = _pending_loss.get(key)
         if pend is not None and pend[5] != stream():
             pend = None
         if pend is not None:
             del _pending_loss[key]
-        lp, ln, le, lsc, lo = pend[:5] if pend is not None else (None, 0, 0, None, None)
         try:
-            check(_lib.load().lae_nerf_head_backward(ptr(grad_sigmas), ptr(grad_rgbs), ptr(enc), ptr(dirs), ptr(h), ptr(rgbs),
-                                                     ptr(sigma_weights), ptr(color_weights), M, float(density_scale),
-                                                     ptr(grad_h), ptr(grad_enc), ptr(grad_sigma_weights),
-                                                     ptr(grad_color_weights), int(bool(accumulate)), int(bool(level_major)),
-                                                     nonfinite_flag, ptr(lp), ln, le, ptr(lsc), ptr(lo), stream()), "nerf_head_backward")
+            call(*(pend[:5] if pend is not None else (None, 0, 0, None, None)))
         except RuntimeError:
             if pend is not None:
                 _pending_loss[key] = pend             # the launch failed: the value is still unfinished, flush_pending_loss() can finish it
             raise
         if pend is not None:
             deferred_loss_stats["carried"] += 1
+
+    @staticmethod
+    def nerf_field_backward(grad_sigmas, grad_rgbs, enc, dirs, h, rgbs, sigma_weights, color_weights, M, density_scale, grad_h, grad_enc,
+                            grad_sigma_weights, grad_color_weights, inputs, offsets, grad_embeddings, L, S, H, gridtype, align_corners,
+                            interp, accumulate=False, weights_nonfinite_flag=None, in_map=(0.0, 1.0), offsets_host=None, plan=None,
+                            table_nonfinite_flag=None, touched_lines=None, grad_dirty=None):
+        """nerf_head_backward(level_major=True) + grid_encode_backward(D = 3, C = 2, fp16, level-major grad_enc) in one call: the
+        reduction of the weight-gradient slabs rides in the grid backward's accumulate pass (include/laenerf.h)"""
+        ts = (grad_sigmas, grad_rgbs, enc, dirs, h, rgbs, sigma_weights, color_weights, grad_h, grad_enc, grad_sigma_weights,
+              grad_color_weights, inputs, offsets, grad_embeddings, plan)
+        need_cuda(*ts); need_contig(*ts)
+        _FFMLP._half(enc, h, sigma_weights, color_weights, grad_h, grad_enc, grad_sigma_weights, grad_color_weights, grad_embeddings)
+        if plan is not None and touched_lines is not None and not getattr(plan, "marks_touched", False):
+            raise RuntimeError("nerf_field_backward: the plan was made without the touched-lines bitmap (pass it to grid_backward_plan)")
+        if _timing["on"]:
+            # the per-call timers (enable_kernel_timing: a diagnostic) know the two halves by name: they run as the two calls the
+            # timers bracket, with the reduction launched on its own -- same bits
+            _FFMLP.nerf_head_backward(grad_sigmas, grad_rgbs, enc, dirs, h, rgbs, sigma_weights, color_weights, M, density_scale, grad_h,
+                                      grad_enc, grad_sigma_weights, grad_color_weights, accumulate=accumulate, level_major=True,
+                                      nonfinite_flag=weights_nonfinite_flag)
+            _GridEncoder.grid_encode_backward(grad_enc[:L], inputs, grad_embeddings, offsets, grad_embeddings, M, 3, 2, L, S, H, None, None,
+                                              gridtype, align_corners, interp, blc=False, in_map=in_map, offsets_host=offsets_host,
+                                              plan=plan, nonfinite_flag=table_nonfinite_flag, touched_lines=touched_lines,
+                                              grad_dirty=grad_dirty)
+            return
+        _FFMLP._with_pending_loss(grad_sigmas, lambda lp, ln, le, lsc, lo: check(_lib.load().lae_nerf_field_backward(
+            ptr(grad_sigmas), ptr(grad_rgbs), ptr(enc), ptr(dirs), ptr(h), ptr(rgbs), ptr(sigma_weights), ptr(color_weights), M,
+            float(density_scale), ptr(grad_h), ptr(grad_enc), ptr(grad_sigma_weights), ptr(grad_color_weights), int(bool(accumulate)),
+            weights_nonfinite_flag, ptr(lp), ln, le, ptr(lsc), ptr(lo), ptr(inputs), ptr(offsets), ptr(grad_embeddings), L, float(S), H,
+            gridtype, int(bool(align_corners)), interp, float(in_map[0]), float(in_map[1]), _host_i32(offsets_host, L + 1), ptr(plan),
+            table_nonfinite_flag, touched_lines, grad_dirty, stream()), "nerf_field_backward"))
 
     @staticmethod
     def ffmlp_set_mode(mode):

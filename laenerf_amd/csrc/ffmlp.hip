@@ -19,6 +19,7 @@
 #include <type_traits>
 #include <stdlib.h>
 #include "lae_common.h"
+#include "dw_reduce.h"
 
 namespace {
 
@@ -358,87 +359,21 @@ __global__ __launch_bounds__(MLP_BLOCK) void k_mlp_dw(
     }
 }
 
-// sum the per-slice slabs in a fixed order (deterministic) and round once to fp16.
-// 1024 threads = 64 weights x 16 slice groups, 8 slab loads in flight per lane (the kernel is pure load latency: 512
-// slabs of 45 KB); the 16 partial sums are combined in a fixed tree.
-// accumulate != 0: gw += sum (the optimizer's persistent gradient buffer) instead of gw = sum.
-constexpr int DWR_GROUPS = 16;
-__device__ __forceinline__ void dw_reduce_body(const float* __restrict__ slabs, uint32_t n_slices, uint32_t nW, half_t* __restrict__ gw,
-                                               int accumulate, uint32_t block, int32_t* __restrict__ nf_flag = nullptr) {
-    __shared__ float part[DWR_GROUPS][64];
-    const uint32_t e = threadIdx.x & 63, sg = threadIdx.x >> 6;
-    const uint32_t i = block * 64 + e;
-    float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (i < nW) {
-        uint32_t k = sg;
-        for (; k + 7 * DWR_GROUPS < n_slices; k += 8 * DWR_GROUPS) {
-#pragma unroll
-            for (int u = 0; u < 8; u++) s[u] += slabs[(size_t)(k + u * DWR_GROUPS) * nW + i];
-        }
-        for (; k < n_slices; k += DWR_GROUPS) s[0] += slabs[(size_t)k * nW + i];
-    }
-    part[sg][e] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-    __syncthreads();
-    if (sg == 0 && i < nW) {
-        float t[DWR_GROUPS];
-#pragma unroll
-        for (int u = 0; u < DWR_GROUPS; u++) t[u] = part[u][e];
-#pragma unroll
-        for (int w = DWR_GROUPS / 2; w > 0; w >>= 1)
-#pragma unroll
-            for (int u = 0; u < w; u++) t[u] = t[u] + t[u + w];
-        const half_t r = accumulate ? (half_t)((float)gw[i] + t[0]) : (half_t)t[0];
-        gw[i] = r;
-        // the caller's flag (the optimizer's found_inf word): a non-finite weight gradient is reported where it is stored
-        if (nf_flag && (__builtin_bit_cast(uint16_t, r) & 0x7c00u) == 0x7c00u) atomicOr(nf_flag, 1);
-    }
-}
+// the slab reduction and the deferred loss value: device bodies in dw_reduce.h (shared with the hash-grid accumulate pass, which
+// takes them along as tail tasks in the fused field backward)
+using lae_dw::DWR_GROUPS;
+using lae_dw::LossFinish;
 __global__ __launch_bounds__(64 * DWR_GROUPS) void k_dw_reduce(const float* __restrict__ slabs, uint32_t n_slices, uint32_t nW,
                                                                half_t* __restrict__ gw, int accumulate = 0, int32_t* __restrict__ nf_flag = nullptr) {
-    dw_reduce_body(slabs, n_slices, nW, gw, accumulate, blockIdx.x, nf_flag);
+    __shared__ float part[lae_dw::DWR_LDS_FLOATS];
+    lae_dw::dw_reduce_body(slabs, n_slices, nW, gw, accumulate, blockIdx.x, nf_flag, part);
 }
 // the same reduction for two networks in one launch (blocks [0, nb_a) reduce A, the rest B): one graph node less per step
 // One block more than the reduction needs takes the deferred loss value along (lae_composite_rays_train_step with
-// defer_loss): the fixed-order sum of the criterion's per-workgroup partials -> loss_out[0] = mean * scale, [1] = mean,
-// the arithmetic of k_loss_finish (raymarching.hip), without a launch of its own on the step's critical path.
-struct LossFinish { const float* partials; uint32_t n_part, n_elem; const float* scale; float* out; };
-__global__ __launch_bounds__(64 * DWR_GROUPS) void k_dw_reduce2(const float* __restrict__ slabs_a, uint32_t n_a, uint32_t nW_a,
-                                                                half_t* __restrict__ gw_a, const float* __restrict__ slabs_b,
-                                                                uint32_t n_b, uint32_t nW_b, half_t* __restrict__ gw_b,
-                                                                uint32_t nb_a, uint32_t nb_b, int accumulate, int32_t* __restrict__ nf_flag,
-                                                                LossFinish lf) {
-    if (blockIdx.x < nb_a) dw_reduce_body(slabs_a, n_a, nW_a, gw_a, accumulate, blockIdx.x, nf_flag);
-    else if (blockIdx.x < nb_a + nb_b) dw_reduce_body(slabs_b, n_b, nW_b, gw_b, accumulate, blockIdx.x - nb_a, nf_flag);
-    else {
-        static_assert(64 * DWR_GROUPS == 1024, "the loss sum is written for 16 waves, like k_loss_finish");
-        __shared__ float part[16];
-        float acc = 0.0f;
-        for (uint32_t i = threadIdx.x; i < lf.n_part; i += 1024) acc += lf.partials[i];
-        {   // the wave sum of raymarching.hip (wave_sum = last lane of the DPP inclusive scan), statement for statement: the
-            // deferred value has the same bits as the one k_loss_finish writes
-            auto dpp = [](float v, auto ctrl, auto mask) {
-                return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value, decltype(mask)::value, 0xf, false));
-            };
-            using std::integral_constant;
-            acc += dpp(acc, integral_constant<int, 0x111>{}, integral_constant<int, 0xf>{});
-            acc += dpp(acc, integral_constant<int, 0x112>{}, integral_constant<int, 0xf>{});
-            acc += dpp(acc, integral_constant<int, 0x114>{}, integral_constant<int, 0xf>{});
-            acc += dpp(acc, integral_constant<int, 0x118>{}, integral_constant<int, 0xf>{});
-            acc += dpp(acc, integral_constant<int, 0x142>{}, integral_constant<int, 0xa>{});
-            acc += dpp(acc, integral_constant<int, 0x143>{}, integral_constant<int, 0xc>{});
-            acc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, acc), 63));
-        }
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float t = 0.0f;
-#pragma unroll
-            for (int w = 0; w < 16; w++) t += part[w];
-            const float loss = t / (float)lf.n_elem;
-            lf.out[0] = loss * (lf.scale ? lf.scale[0] : 1.0f);
-            lf.out[1] = loss;
-        }
-    }
+// defer_loss), without a launch of its own on the step's critical path.
+__global__ __launch_bounds__(64 * DWR_GROUPS) void k_dw_reduce2(lae_dw::DwTailJob job) {
+    __shared__ float part[lae_dw::DWR_LDS_FLOATS];
+    lae_dw::dw_tail_task(job, blockIdx.x, part);
 }
 
 // ---------------------------------------------------------------- fused NeRF head (network_ff.py:51-81 in one kernel)
@@ -1988,6 +1923,22 @@ int lae_nerf_head_backward(const float* grad_sigmas, const float* grad_rgbs, con
                            void* grad_color_weights, int accumulate_weight_grads, int enc_level_major, int32_t* nonfinite_flag,
                            const float* loss_partials, uint32_t loss_n_part, uint32_t loss_n_elem, const float* loss_scale,
                            float* loss_out, void* stream) {
+    return lae::nerf_head_backward(grad_sigmas, grad_rgbs, enc, dirs, h, rgbs, sigma_weights, color_weights, M, density_scale, grad_h,
+                                   grad_enc, grad_sigma_weights, grad_color_weights, accumulate_weight_grads, enc_level_major,
+                                   nonfinite_flag, loss_partials, loss_n_part, loss_n_elem, loss_scale, loss_out, stream, nullptr);
+}
+
+}  // extern "C"
+
+// tail != nullptr (lae_nerf_field_backward, M > 0): the reduction of the two networks' slabs and the deferred loss value are not
+// launched but handed back as a job; the caller's next launch on the stream (the grid backward's accumulate pass) runs it
+int lae::nerf_head_backward(const float* grad_sigmas, const float* grad_rgbs, const void* enc, const float* dirs, const void* h,
+                            const float* rgbs, const void* sigma_weights, const void* color_weights, uint32_t M,
+                            float density_scale, void* grad_h, void* grad_enc, void* grad_sigma_weights,
+                            void* grad_color_weights, int accumulate_weight_grads, int enc_level_major, int32_t* nonfinite_flag,
+                            const float* loss_partials, uint32_t loss_n_part, uint32_t loss_n_elem, const float* loss_scale,
+                            float* loss_out, void* stream, lae_dw::DwTailJob* tail) {
+    if (tail) tail->n_tasks = 0;
     if (!grad_sigma_weights || !grad_color_weights) return LAE_ENULL;
     if (loss_out && (!loss_partials || loss_n_elem == 0)) return LAE_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2021,11 +1972,14 @@ int lae_nerf_head_backward(const float* grad_sigmas, const float* grad_rgbs, con
     if (rc != LAE_OK) return rc;
     const uint32_t nb_c = lae::cdiv(nW_c, 64u), nb_s = lae::cdiv(nW_s, 64u);
     const LossFinish lf{loss_partials, loss_n_part, loss_n_elem, loss_scale, loss_out};
-    k_dw_reduce2<<<nb_c + nb_s + (loss_out ? 1u : 0u), 64 * DWR_GROUPS, 0, s>>>(ws, n_c, nW_c, (half_t*)grad_color_weights, ws_s, n_s, nW_s,
-                                                                               (half_t*)grad_sigma_weights, nb_c, nb_s,
-                                                                               accumulate_weight_grads, nonfinite_flag, lf);
+    const lae_dw::DwTailJob job{ws, n_c, nW_c, (half_t*)grad_color_weights, ws_s, n_s, nW_s, (half_t*)grad_sigma_weights, nb_c, nb_s,
+                                accumulate_weight_grads, nonfinite_flag, lf, nb_c + nb_s + (loss_out ? 1u : 0u)};
+    if (tail) *tail = job;
+    else k_dw_reduce2<<<job.n_tasks, 64 * DWR_GROUPS, 0, s>>>(job);
     return lae::check_launch("nerf_head_backward");
 }
+
+extern "C" {
 
 int lae_ffmlp_set_mode(int mode) {
     // 0: default (fused backward, wave-private dW with MFMA transposes); 1: buffer-faithful three-kernel backward (the reference's

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "lae_common.h"
+#include "dw_reduce.h"
 #include <vector>
 #include <mutex>
 #include <utility>
@@ -403,7 +404,10 @@ template <typename T, int D, int C>
 __global__ __launch_bounds__(GRID_BLOCK) void k_grid_bwd(
     const T* __restrict__ grad, const float* __restrict__ inputs, const int32_t* __restrict__ offsets,
     T* __restrict__ grad_grid, uint32_t B, uint32_t L, LevelScales sc, uint32_t gridtype, bool align_corners,
-    uint32_t interp, uint32_t nb, bool xcd_mode, uint64_t gs_b, uint64_t gs_l, bool only_unbinned) {
+    uint32_t interp, uint32_t nb, bool xcd_mode, uint64_t gs_b, uint64_t gs_l, bool only_unbinned,
+    uint32_t* __restrict__ grad_dirty = nullptr) {
+    // the accumulator's "dirty" word (see k_bwd_walk<FILL>): these atomics add on top of whatever is there and leave it non-zero
+    if (grad_dirty && blockIdx.x == 0 && threadIdx.x == 0) *grad_dirty = 1u;
     uint32_t level, chunk;
     block_to_level_chunk(nb, xcd_mode, level, chunk);
     if (level >= L) return;
@@ -517,6 +521,17 @@ struct BwdPlan {
     uint32_t* tickets;    // [TICKET_WORDS]
 };
 
+// behind the ticket words (plan_layout leaves room), written by the fill pass for the accumulate pass: its tail job, and the
+// snapshot of the accumulator's "dirty" word (0 = the table gradient is all zero, no old values are needed).  Not among the
+// tickets: every workgroup's atomics keep the line of tickets[0] busy, and a load from it waits behind them.
+__host__ __device__ __forceinline__ lae_dw::DwTailJob* plan_tail_job(const BwdPlan& plan) {
+    static_assert((TICKET_WORDS * 4) % alignof(lae_dw::DwTailJob) == 0, "the tail job sits right behind the tickets");
+    return reinterpret_cast<lae_dw::DwTailJob*>(plan.tickets + TICKET_WORDS);
+}
+__host__ __device__ __forceinline__ uint32_t* plan_dirty_snapshot(const BwdPlan& plan) {
+    return plan.tickets + TICKET_WORDS + sizeof(lae_dw::DwTailJob) / 4;
+}
+
 __device__ __forceinline__ uint32_t pack_half2(float a, float b) {
     const half2_t h = {(half_t)a, (half_t)b};
     return __builtin_bit_cast(uint32_t, h);
@@ -529,14 +544,27 @@ __global__ __launch_bounds__(FILL_THREADS) void k_bwd_walk(
     const T* __restrict__ gradT, const float* __restrict__ inputs, const int32_t* __restrict__ offsets, uint32_t B,
     uint32_t L, LevelScales sc, uint32_t gridtype_, bool align_corners_, uint32_t interp_, uint32_t U, BwdPlan plan,
     typename BVal<T>::type* __restrict__ qvals, uint16_t* __restrict__ qkeys, uint32_t* __restrict__ touched_,
-    uint32_t* __restrict__ level_full) {
+    uint32_t* __restrict__ level_full, uint32_t* __restrict__ grad_dirty = nullptr, lae_dw::DwTailJob tail = lae_dw::DwTailJob{}) {
     const uint32_t gridtype = PLAIN ? 0u : gridtype_, interp = PLAIN ? 0u : interp_;
     const bool align_corners = PLAIN ? false : align_corners_;
     using V = typename BVal<T>::type;
     if constexpr (FILL) GRID_STAMP(blockIdx.x, 0);
     const uint32_t NBLK = U / SEGS;                           // U is a multiple of SEGS
     const uint32_t level = blockIdx.x / NBLK, chunk = blockIdx.x % NBLK;
-    if (FILL && blockIdx.x == 0) for (uint32_t k = threadIdx.x; k < TICKET_WORDS; k += FILL_THREADS) plan.tickets[k] = 0;   // work queue / arrival counters of the accumulate pass
+    if (FILL && blockIdx.x == 0) {
+        for (uint32_t k = threadIdx.x; k < TICKET_WORDS; k += FILL_THREADS) plan.tickets[k] = 0;   // work queue / arrival counters of the accumulate pass
+        // the caller's "dirty" word of the gradient accumulator (0: nothing but zeros in it, the optimizer's apply kernel has just
+        // consumed it): the accumulate pass of THIS backward gets its value, and from here on the accumulator counts as written.
+        // No block of this launch reads either word and the accumulate pass is a later launch on the stream: no counter, no fence.
+        // Without a word the accumulator may hold anything.
+        if (threadIdx.x == 0) {
+            *plan_dirty_snapshot(plan) = grad_dirty ? *grad_dirty : 1u;
+            if (grad_dirty) *grad_dirty = 1u;
+            // the accumulate pass's tail job (n_tasks == 0: none) travels through the plan as well: as an argument of that launch
+            // its 26 words would stay in scalar registers for the whole pass, which has none to spare
+            *plan_tail_job(plan) = tail;
+        }
+    }
     const LevelInfo<3> li = level_info<3>(sc, offsets, level, gridtype, align_corners);
     const uint32_t P = (li.hashmap_size + PART - 1) >> PART_SHIFT;
     if (P > BK_MAX) return;                                // handled by the generic atomic kernel
@@ -1031,6 +1059,7 @@ __global__ __launch_bounds__(ACC_THREADS, 8) void k_bwd_acc(
     // the first task of every workgroup is its own index (gridDim.x same-address atomics at launch would queue up behind one
     // another); later tasks are drawn from the ticket counter, which therefore counts from gridDim.x
     bool first_task = true;
+    uint32_t tail_task;                                         // first ticket behind the partition tasks
     [[maybe_unused]] uint32_t stamp_task = 0;
     GRID_STAMP(4096 + blockIdx.x, 0);
     for (;;) {
@@ -1039,7 +1068,7 @@ __global__ __launch_bounds__(ACC_THREADS, 8) void k_bwd_acc(
         __syncthreads();
         const uint32_t t = __builtin_amdgcn_readfirstlane(s_ticket);       // scalar: everything derived from it is wave-uniform
         GRID_STAMP(4096 + blockIdx.x, 1 + stamp_task * 6);                   // ticket in hand
-        if (t >= total_buckets) break;
+        if (t >= total_buckets) { tail_task = t - total_buckets; break; }
         GRID_NOTE(4096 + blockIdx.x, 2 + stamp_task * 6, t);
         const uint32_t item = t;                                // coarse levels first: their sub-ranges + merge are the longest chains
         uint32_t level = 0;
@@ -1048,18 +1077,23 @@ __global__ __launch_bounds__(ACC_THREADS, 8) void k_bwd_acc(
         const uint32_t bk = item - __builtin_amdgcn_readfirstlane(s_first[level]);
         const uint32_t SUB = __builtin_amdgcn_readfirstlane(s_sub[level]), p = bk / SUB, sub = bk % SUB;
         const uint32_t table_off = (uint32_t)offsets[level], hashmap_size = (uint32_t)offsets[level + 1] - table_off;
-        const uint32_t n = __builtin_amdgcn_readfirstlane(plan.totals[level * BK_MAX + p]), q0 = __builtin_amdgcn_readfirstlane(plan.offs[level * BK_MAX + p]);
+        // (the dirty snapshot travels with the two plan words: three loads in flight, one wait)
+        const uint32_t n_raw = plan.totals[level * BK_MAX + p], q0_raw = plan.offs[level * BK_MAX + p], dirty_raw = *plan_dirty_snapshot(plan);
+        const uint32_t n = __builtin_amdgcn_readfirstlane(n_raw), q0 = __builtin_amdgcn_readfirstlane(q0_raw);
+        const bool grad_dirty = __builtin_amdgcn_readfirstlane(dirty_raw) != 0u;
         const uint32_t lo = (uint32_t)(((uint64_t)n * sub) / SUB), hi = (uint32_t)(((uint64_t)n * (sub + 1)) / SUB);
         if (n == 0) { __syncthreads(); continue; }              // uniform per (level, partition): no sub-range has work
         // the old values of the lane's table entries: requested now, consumed after the items (their latency hides behind
-        // the partition's whole accumulate phase)
+        // the partition's whole accumulate phase).  A clean accumulator (training: the optimizer zeroes it in every step) holds
+        // zeros: nothing is read (16 KB per task), and RN(0 + sum) below is what the read would have given.
         const uint32_t part_lo = p << PART_SHIFT;
         const uint32_t n_ent = min(PART, hashmap_size - part_lo);
         T* __restrict__ dst = grad_grid + ((size_t)table_off + part_lo) * 2;
         uint32_t oldv[HALF ? PART / ACC_THREADS : 1];
+        const uint32_t n_old = grad_dirty ? n_ent : 0u;
         if constexpr (HALF) {
 #pragma unroll
-            for (int it = 0; it < (int)(PART / ACC_THREADS); it++) { const uint32_t e = tid + it * ACC_THREADS; oldv[it] = e < n_ent ? reinterpret_cast<const uint32_t*>(dst)[e] : 0u; }
+            for (int it = 0; it < (int)(PART / ACC_THREADS); it++) { const uint32_t e = tid + it * ACC_THREADS; oldv[it] = e < n_old ? reinterpret_cast<const uint32_t*>(dst)[e] : 0u; }
         }
         for (uint32_t i = tid; i < ACCW; i += ACC_THREADS) acc64[i] = 0ull;
         if (tid < PART / 32) poison[tid] = 0u;
@@ -1200,7 +1234,8 @@ __global__ __launch_bounds__(ACC_THREADS, 8) void k_bwd_acc(
                 const uint32_t e = tid + it * ACC_THREADS;
                 if (e >= n_ent) break;
                 const long long i0 = (long long)acc64[e], i1 = (long long)acc64[PART + e];
-                const bool bad = (poison[e >> 5] >> (e & 31)) & 1u;
+                // e >> 5 = (tid >> 5) + 32 * it, e & 31 = tid & 31: one address register for the four words, not four
+                const bool bad = (poison[(tid >> 5) + it * (ACC_THREADS / 32)] >> (tid & 31)) & 1u;
                 if (i0 == 0 && i1 == 0 && !bad) continue;
                 const uint32_t o = oldv[it];               // only writer of this table slice: old + exact sum, rounded ONCE
                 uint32_t r0, r1;
@@ -1228,6 +1263,20 @@ __global__ __launch_bounds__(ACC_THREADS, 8) void k_bwd_acc(
         GRID_STAMP(4096 + blockIdx.x, 6 + stamp_task * 6);                   // flushed
         stamp_task++;
         __syncthreads();
+    }
+    // tail tasks (fused field backward): the tickets behind the partition tasks reduce the MLP weight-gradient slabs and finish the
+    // deferred loss, one block of k_dw_reduce2 each, where workgroups are running out of partitions.  Tickets only grow, so a
+    // workgroup that has drawn one of them draws no partition task any more: a loop of its own, in which nothing of the loop
+    // above is live (inside it the tail's addresses cost scalar registers the pass does not have).  The LDS scratch aliases
+    // acc64; the job was left in the plan by the fill pass (n_tasks == 0: none).
+    static_assert(sizeof(acc64) >= lae_dw::DWR_LDS_FLOATS * sizeof(float) && ACC_THREADS == (int)lae_dw::DWR_THREADS, "tail tasks run in this workgroup");
+    const lae_dw::DwTailJob& tail = *plan_tail_job(plan);
+    const uint32_t n_tail = __builtin_amdgcn_readfirstlane(tail.n_tasks);
+    while (tail_task < n_tail) {
+        lae_dw::dw_tail_task(tail, tail_task, reinterpret_cast<float*>(acc64));     // one barrier inside: every wave has read s_ticket
+        if (tid == 0) s_ticket = atomicAdd(&plan.tickets[0], 1u) + gridDim.x;
+        __syncthreads();
+        tail_task = __builtin_amdgcn_readfirstlane(s_ticket) - total_buckets;
     }
 }
 
@@ -1536,6 +1585,8 @@ struct BwdArgs {
     int32_t* nf_flag = nullptr;                                 // set to 1 when a non-finite table gradient is stored (binned path)
     uint32_t* touched = nullptr;                                // bit per 8 table entries (one 64-byte line of fp32 pairs): set by the count pass
     uint32_t* touched_full = nullptr;                           // MAX_LEVELS words behind the bitmap: level l is fully marked
+    uint32_t* dirty = nullptr;                                  // the accumulator's "dirty" word (include/laenerf.h), or NULL
+    const lae_dw::DwTailJob* tail = nullptr;                    // binned fp16 path only: tasks the accumulate pass takes along
 };
 template <typename T, int D, int C>
 static void launch_bwd(const BwdArgs& a) {
@@ -1543,7 +1594,7 @@ static void launch_bwd(const BwdArgs& a) {
     const bool xcd = (a.L % 8) == 0;
     k_grid_bwd<T, D, C><<<nb * a.L, GRID_BLOCK, 0, a.stream>>>(a.grad ? (const T*)a.grad : nullptr, a.inputs, a.offsets,
                                                                 (T*)a.gemb, a.B, a.L, a.sc, a.gridtype, a.align,
-                                                                a.interp, nb, xcd, a.gs_b, a.gs_l, false);
+                                                                a.interp, nb, xcd, a.gs_b, a.gs_l, false, a.dirty);
 }
 template <typename T, int D>
 static int dispatch_bwd_c(const BwdArgs& a, uint32_t C) {
@@ -1624,7 +1675,7 @@ static inline PlanLayout plan_layout(uint32_t B, uint32_t L) {
     const size_t U = bwd_units(B);
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     PlanLayout w;
-    w.totals_off = up((size_t)TICKET_WORDS * 4);
+    w.totals_off = up((size_t)TICKET_WORDS * 4 + sizeof(lae_dw::DwTailJob) + 4);
     w.offs_off = w.totals_off + up((size_t)L * BK_MAX * 4);
     w.cnt_off = w.offs_off + up((size_t)L * BK_MAX * 4);
     w.part_off = w.cnt_off + up((size_t)L * U * BK_MAX * 2);
@@ -1711,6 +1762,7 @@ static int launch_bwd_fast(const void* gT, const float* inputs, const int32_t* o
     const T* g = (const T*)gT;
     T* ge = (T*)gemb;
     if (!caller_plan) bwd_plan<T>(inputs, offsets, B, L, a, plan);
+    const lae_dw::DwTailJob tail_job = a.tail ? *a.tail : lae_dw::DwTailJob{};
 #ifdef LAE_GRID_BWD_PHASE_PROBE
     // probe builds only (tools/fill_beside_mlp_probe.py): LAE_GRID_BWD_PHASE=1 launches the fill pass alone, =2 the accumulate
     // pass alone (on whatever the queue holds); results are meaningless, durations are what is measured
@@ -1719,9 +1771,9 @@ static int launch_bwd_fast(const void* gT, const float* inputs, const int32_t* o
     if (phase_probe != 2)
 #endif
     if (a.gridtype == 0 && !a.align && a.interp == 0)
-        k_bwd_walk<T, true, true><<<U / SEGS * L, FILL_THREADS, 0, a.stream>>>(g, inputs, offsets, B, L, a.sc, a.gridtype, a.align, a.interp, U, plan, qvals, qkeys, nullptr, nullptr);
+        k_bwd_walk<T, true, true><<<U / SEGS * L, FILL_THREADS, 0, a.stream>>>(g, inputs, offsets, B, L, a.sc, a.gridtype, a.align, a.interp, U, plan, qvals, qkeys, nullptr, nullptr, a.dirty, tail_job);
     else
-        k_bwd_walk<T, true, false><<<U / SEGS * L, FILL_THREADS, 0, a.stream>>>(g, inputs, offsets, B, L, a.sc, a.gridtype, a.align, a.interp, U, plan, qvals, qkeys, nullptr, nullptr);
+        k_bwd_walk<T, true, false><<<U / SEGS * L, FILL_THREADS, 0, a.stream>>>(g, inputs, offsets, B, L, a.sc, a.gridtype, a.align, a.interp, U, plan, qvals, qkeys, nullptr, nullptr, a.dirty, tail_job);
 #ifdef LAE_GRID_BWD_PHASE_PROBE
     if (phase_probe == 1) return lae::check_launch("grid backward (fill-only probe)");
 #endif
@@ -1763,10 +1815,12 @@ static int grid_backward(const void* grad, const float* inputs, const void* embe
                          const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners, uint32_t interp,
                          int dtype, bool blc, void* stream, float in_shift = 0.0f, float in_scale = 1.0f,
                          const int32_t* offsets_host = nullptr, const void* plan = nullptr, int32_t* nf_flag = nullptr,
-                         uint32_t* touched = nullptr) {
+                         uint32_t* touched = nullptr, uint32_t* dirty = nullptr, const lae_dw::DwTailJob* tail = nullptr) {
     (void)embeddings;
     if (B == 0) return LAE_OK;
     if (!grad || !inputs || !offsets || !grad_embeddings) return LAE_ENULL;
+    // tail tasks ride in the accumulate pass of the binned fp16 pipeline and nowhere else (lae_nerf_field_backward decides with the same conditions)
+    if (tail && !(D == 3 && C == 2 && L <= 32 && B <= BWD_MAX_SAMPLES && !g_force_atomic_bwd && dtype == LAE_F16)) return LAE_EINVAL;
     if (plan && !(D == 3 && C == 2 && L <= 32 && B <= BWD_MAX_SAMPLES && !blc && !g_force_atomic_bwd)) return LAE_EINVAL;
     if (gridtype > 1 || interp > 1) return LAE_EINVAL;
     if (touched && dtype != LAE_F16) return LAE_EINVAL;
@@ -1782,6 +1836,8 @@ static int grid_backward(const void* grad, const float* inputs, const void* embe
     a.nf_flag = nf_flag;
     a.touched = touched;
     if (touched) a.touched_full = touched + touched_words(offsets_host, L);
+    a.dirty = dirty;
+    a.tail = tail;
     a.grad = grad; a.inputs = inputs; a.offsets = offsets; a.gemb = grad_embeddings; a.B = B; a.L = L;
     int rc = fill_scales(a.sc, L, S, H);
     if (rc) return rc;
@@ -1884,10 +1940,11 @@ int lae_grid_encode_backward_ex(const void* grad, const float* inputs, const voi
                                 void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
                                 uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype,
                                 int align_corners, uint32_t interp, int dtype, int blc, float in_shift, float in_scale,
-                                const int32_t* offsets_host, int32_t* nonfinite_flag, uint32_t* touched_lines, void* stream) {
+                                const int32_t* offsets_host, int32_t* nonfinite_flag, uint32_t* touched_lines, uint32_t* grad_dirty,
+                                void* stream) {
     return grid_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs,
                          gridtype, align_corners, interp, dtype, blc != 0, stream, in_shift, in_scale, offsets_host, nullptr,
-                         nonfinite_flag, touched_lines);
+                         nonfinite_flag, touched_lines, grad_dirty);
 }
 
 uint64_t lae_grid_backward_workspace_bytes(uint32_t B, uint32_t L, int dtype) {
@@ -1928,10 +1985,55 @@ int lae_grid_encode_backward_plan(const float* inputs, const int32_t* offsets, u
 int lae_grid_encode_backward_planned(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B,
                                      uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
                                      uint32_t interp, int dtype, float in_shift, float in_scale, const int32_t* offsets_host,
-                                     const void* plan, int32_t* nonfinite_flag, void* stream) {
+                                     const void* plan, int32_t* nonfinite_flag, uint32_t* grad_dirty, void* stream) {
     if (!plan) return LAE_ENULL;
     return grid_backward(grad, inputs, nullptr, offsets, grad_embeddings, B, D, C, L, S, H, nullptr, nullptr, gridtype, align_corners,
-                         interp, dtype, false, stream, in_shift, in_scale, offsets_host, plan, nonfinite_flag, nullptr);
+                         interp, dtype, false, stream, in_shift, in_scale, offsets_host, plan, nonfinite_flag, nullptr, grad_dirty);
+}
+
+// Fused field backward: colour-net backward, sigma-net backward, fill pass, accumulate pass -- lae_nerf_head_backward (level-major
+// encoder features) followed by lae_grid_encode_backward_ex / _planned (D = 3, C = 2, fp16, level-major gradients) in one call, so
+// that the reduction of the MLP weight-gradient slabs and the deferred loss value need no launch of their own: they ride as tail
+// tasks in the accumulate pass (k_bwd_acc), behind its partition tasks.  Same bits as the two calls.  Where the binned pipeline
+// does not run (more than 32 levels or 2^24 samples, lae_grid_set_backward_mode(1)) and under LAE_FIELD_NO_RIDE_ALONG=1 (A/B
+// switch, read at every call) the two calls are made as they are.
+int lae_nerf_field_backward(const float* grad_sigmas, const float* grad_rgbs, const void* enc, const float* dirs, const void* h,
+                            const float* rgbs, const void* sigma_weights, const void* color_weights, uint32_t M, float density_scale,
+                            void* grad_h, void* grad_enc, void* grad_sigma_weights, void* grad_color_weights,
+                            int accumulate_weight_grads, int32_t* weights_nonfinite_flag, const float* loss_partials,
+                            uint32_t loss_n_part, uint32_t loss_n_elem, const float* loss_scale, float* loss_out,
+                            const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t L, float S, uint32_t H,
+                            uint32_t gridtype, int align_corners, uint32_t interp, float in_shift, float in_scale,
+                            const int32_t* offsets_host, const void* plan, int32_t* table_nonfinite_flag, uint32_t* touched_lines,
+                            uint32_t* grad_dirty, void* stream) {
+    // everything either half would refuse is refused here, before the first launch
+    if (!grad_sigma_weights || !grad_color_weights) return LAE_ENULL;
+    if (loss_out && (!loss_partials || loss_n_elem == 0)) return LAE_EINVAL;
+    if (M > 0) {
+        if (!grad_sigmas || !grad_rgbs || !enc || !dirs || !h || !rgbs || !sigma_weights || !color_weights || !grad_h || !grad_enc ||
+            !inputs || !offsets || !grad_embeddings) return LAE_ENULL;
+        if (M % 16 != 0 || gridtype > 1 || interp > 1) return LAE_EINVAL;
+        LevelScales sc;
+        if (const int rc = fill_scales(sc, L, S, H)) return rc;
+        const bool binned = L <= 32 && M <= BWD_MAX_SAMPLES && !g_force_atomic_bwd;
+        if (plan && !binned) return LAE_EINVAL;
+        if (table_nonfinite_flag || touched_lines) {
+            if (!binned || !offsets_host) return LAE_EINVAL;
+            for (uint32_t l = 0; l < L; l++)
+                if (!level_is_binned((uint32_t)(offsets_host[l + 1] - offsets_host[l]))) return LAE_EINVAL;
+        }
+    }
+    const char* off = getenv("LAE_FIELD_NO_RIDE_ALONG");
+    const bool ride = M > 0 && L <= 32 && M <= BWD_MAX_SAMPLES && !g_force_atomic_bwd && !(off && off[0] == '1');
+    lae_dw::DwTailJob tail{};
+    int rc = lae::nerf_head_backward(grad_sigmas, grad_rgbs, enc, dirs, h, rgbs, sigma_weights, color_weights, M, density_scale, grad_h,
+                                     grad_enc, grad_sigma_weights, grad_color_weights, accumulate_weight_grads, 1, weights_nonfinite_flag,
+                                     loss_partials, loss_n_part, loss_n_elem, loss_scale, loss_out, stream, ride ? &tail : nullptr);
+    if (rc != LAE_OK) return rc;
+    // with a plan the bitmap was maintained by lae_grid_encode_backward_plan
+    return grid_backward(grad_enc, inputs, nullptr, offsets, grad_embeddings, M, 3, 2, L, S, H, nullptr, nullptr, gridtype, align_corners,
+                         interp, LAE_F16, false, stream, in_shift, in_scale, offsets_host, plan, table_nonfinite_flag,
+                         plan ? nullptr : touched_lines, grad_dirty, ride ? &tail : nullptr);
 }
 
 int lae_grid_forward_schedule(const int32_t* offsets_host, uint32_t L, float S, uint32_t H, uint32_t n_chunks, uint32_t* nseg_out,

@@ -59,6 +59,19 @@ int nerf_head_composite_frame(const void* enc, const float* dirs, const void* si
                               hipStream_t stream);
 uint32_t frame_head_max_blocks();
 
+}  // namespace lae
+namespace lae_dw { struct DwTailJob; }                       // dw_reduce.h
+namespace lae {
+// lae_nerf_head_backward (ffmlp.hip) for the fused field backward (lae_nerf_field_backward, gridencoder.hip): with `tail` the
+// reduction of the weight-gradient slabs and the deferred loss value are returned as a job (n_tasks == 0: nothing left to do)
+// for the grid backward's accumulate pass instead of being launched
+int nerf_head_backward(const float* grad_sigmas, const float* grad_rgbs, const void* enc, const float* dirs, const void* h,
+                       const float* rgbs, const void* sigma_weights, const void* color_weights, uint32_t M, float density_scale,
+                       void* grad_h, void* grad_enc, void* grad_sigma_weights, void* grad_color_weights,
+                       int accumulate_weight_grads, int enc_level_major, int32_t* nonfinite_flag, const float* loss_partials,
+                       uint32_t loss_n_part, uint32_t loss_n_elem, const float* loss_scale, float* loss_out, void* stream,
+                       lae_dw::DwTailJob* tail);
+
 // every launch is followed by this: the reference never checked its launches
 // (SURVEY 8b "Errors"); we do, and surface the error through the return code.
 static inline int check_launch(const char* what) {

@@ -174,6 +174,7 @@ struct ApplySegs {
     float* p[MAX_SEGS]; float* m[MAX_SEGS]; float* v[MAX_SEGS]; void* grad[MAX_SEGS]; half_t* shadow[MAX_SEGS];
     const float* lr[MAX_SEGS]; size_t n[MAX_SEGS]; int is_half[MAX_SEGS]; int count;
     const uint32_t* touched[MAX_SEGS];       // bit per 16 parameters (8 table entries x 2): 0 = gradient and both moments are zero
+    uint32_t* dirty[MAX_SEGS];               // the gradient accumulator's "dirty" word (lae_grid_encode_backward_ex), or NULL
 };
 
 template <typename G>
@@ -264,6 +265,13 @@ __global__ __launch_bounds__(256) void k_apply_multi(ApplySegs sg, OptState* __r
     const float inv_scale = st->inv_scale, bc2_sqrt = st->bc2_sqrt;
     // the LAST workgroup's first thread (the first workgroups carry the table's head, the longest work): words 9-13 only
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) prepare_next_step(st, h.beta1, h.beta2);
+    // this launch leaves every gradient it walks zero (step or skip alike): the accumulators are clean again.  Nobody in this
+    // launch reads the words; the next backward is a later launch on the stream.  One thread of a workgroup in the middle of the
+    // grid (neither the table's head nor the one that prepares the next step), pointers at fixed offsets: one round of loads.
+    if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) {
+#pragma unroll
+        for (int s = 0; s < MAX_SEGS; s++) if (s < sg.count && sg.dirty[s]) *sg.dirty[s] = 0u;
+    }
     for (int s = 0; s < sg.count; s++) {
         const float lr_over_bc1 = (float)((double)sg.lr[s][0] * (double)st->inv_bc1);
         if (sg.is_half[s]) seg_apply(sg.p[s], sg.m[s], sg.v[s], (half_t*)sg.grad[s], sg.shadow[s], sg.n[s], skip, inv_scale, bc2_sqrt, lr_over_bc1, h, sg.touched[s]);
@@ -396,7 +404,7 @@ int lae_ema_update_gated(uint32_t n_tensors, float* const* shadows, const float*
 
 int lae_adam_apply_multi(uint32_t n_tensors, float* const* params, float* const* exp_avgs, float* const* exp_avg_sqs, void* const* grads,
                          const int* grad_is_half, void* const* shadows_half, const uint64_t* sizes, const float* const* lrs,
-                         const void* const* touched_lines, const void* state, float beta1, float beta2, float eps, float weight_decay,
+                         const void* const* touched_lines, void* const* grad_dirty, const void* state, float beta1, float beta2, float eps, float weight_decay,
                          void* stream) {
     if (n_tensors == 0) return LAE_OK;
     if (!params || !exp_avgs || !exp_avg_sqs || !grads || !grad_is_half || !shadows_half || !sizes || !lrs || !state) return LAE_ENULL;
@@ -412,6 +420,7 @@ int lae_adam_apply_multi(uint32_t n_tensors, float* const* params, float* const*
         sg.p[i] = params[i]; sg.m[i] = exp_avgs[i]; sg.v[i] = exp_avg_sqs[i]; sg.grad[i] = grads[i];
         sg.shadow[i] = (half_t*)shadows_half[i]; sg.lr[i] = lrs[i]; sg.n[i] = sizes[i]; sg.is_half[i] = grad_is_half[i];
         sg.touched[i] = (touched_lines && weight_decay == 0.0f) ? (const uint32_t*)touched_lines[i] : nullptr;
+        sg.dirty[i] = grad_dirty ? (uint32_t*)grad_dirty[i] : nullptr;
         biggest = std::max(biggest, (size_t)sizes[i]);
     }
     sg.count = (int)n_tensors;

@@ -186,7 +186,8 @@ class _style_features(Function):
             enc.shadow.mark_all_touched()
         _grid.grid_encode_backward(grad_feats, x, table, enc.offsets, grad_table, M, 3, 2, L, S, H, None, None, enc.gridtype_id,
                                    enc.align_corners, enc.interp_id, blc=False, in_map=ctx.in_map, offsets_host=enc.offsets_host,
-                                   plan=ctx.plan, nonfinite_flag=flag, touched_lines=touched)
+                                   plan=ctx.plan, nonfinite_flag=flag, touched_lines=touched,
+                                   grad_dirty=enc.shadow.dirty_for_backward() if enc.shadow is not None else None)
         return None, None, (None if enc.shadow is not None else grad_table), None, None, None, None, None
 
 

@@ -64,8 +64,6 @@ class _nerf_field(Function):
             wflag = _weights_flag(ctx.shadows)
         else:
             gws, gwc = torch.empty_like(ws), torch.empty_like(wc)
-        _mlp.nerf_head_backward(grad_sigmas, grad_rgbs, feats, dirs, h, rgbs, ws, wc, M, ctx.density_scale, grad_h, grad_feats,
-                                gws, gwc, accumulate=ctx.shadows is not None, level_major=True, nonfinite_flag=wflag)
         grad_table = enc.shadow.grad_half if enc.shadow is not None else torch.zeros_like(table)
         flag = enc.shadow.flag_for_backward(M) if enc.shadow is not None else None    # the optimizer's found_inf word, or None
         touched = enc.shadow.touched_for_backward(M) if flag is not None else None     # its "ever touched" bitmap, or None
@@ -73,9 +71,14 @@ class _nerf_field(Function):
             touched = None                                 # a plan made without the bitmap: nothing was marked
         if enc.shadow is not None and touched is None:
             enc.shadow.mark_all_touched()
-        _grid.grid_encode_backward(grad_feats, x, table, enc.offsets, grad_table, M, 3, 2, L, S, H, None, None, enc.gridtype_id,
-                                   enc.align_corners, enc.interp_id, blc=False, in_map=ctx.in_map, offsets_host=enc.offsets_host, plan=ctx.plan,
-                                   nonfinite_flag=flag, touched_lines=touched)
+        dirty = enc.shadow.dirty_for_backward() if enc.shadow is not None else None    # "the accumulator holds zeros" word, or None
+        # both networks' backward, then the table's: one call, so that the reduction of the weight-gradient slabs (and the deferred
+        # loss value) rides in the table backward's accumulate pass instead of a launch of its own
+        _mlp.nerf_field_backward(grad_sigmas, grad_rgbs, feats, dirs, h, rgbs, ws, wc, M, ctx.density_scale, grad_h, grad_feats, gws, gwc,
+                                 x, enc.offsets, grad_table, L, S, H, enc.gridtype_id, enc.align_corners, enc.interp_id,
+                                 accumulate=ctx.shadows is not None, weights_nonfinite_flag=wflag, in_map=ctx.in_map,
+                                 offsets_host=enc.offsets_host, plan=ctx.plan, table_nonfinite_flag=flag, touched_lines=touched,
+                                 grad_dirty=dirty)
         return (None, None, None if enc.shadow is not None else grad_table,
                 None if ctx.shadows is not None else gws.to(ctx.wdtypes[0]),
                 None if ctx.shadows is not None else gwc.to(ctx.wdtypes[1]), None, None, None, None, None, None)

@@ -68,7 +68,8 @@ class _grid_encode(Function):
             ctx.shadow.mark_all_touched()
         _backend.grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx,
                                       grad_inputs, gridtype, ctx.align_corners, interpolation, blc=True, in_map=ctx.in_map,
-                                      offsets_host=ctx.offsets_host, nonfinite_flag=flag, touched_lines=touched)
+                                      offsets_host=ctx.offsets_host, nonfinite_flag=flag, touched_lines=touched,
+                                      grad_dirty=ctx.shadow.dirty_for_backward() if ctx.shadow is not None else None)
         if dy_dx is not None:
             grad_inputs = grad_inputs.to(inputs.dtype)
             if ctx.in_map[1] != 1.0:
@@ -94,11 +95,30 @@ class TableShadow:
         # the table out of its scan (optim.FusedAdam.step).  `unreported` = grad_half was written by something that does
         # not report (a folded .grad, a gradient all-reduce): the next step scans it again.
         self.nonfinite_flag = None
-        self.unreported = False
+        # "dirty" word of the accumulator (one int32 on the device, given by FusedAdam): 0 = grad_half holds nothing but zeros, so
+        # the binned backward reads no old values (16 KB per partition task).  The backward sets it, the optimizer's apply kernel
+        # and zero_grad() clear it -- all on the device, so a captured step carries it along.  Any other writer of grad_half says
+        # so with `unreported = True` (the convention above), which sets the word as well.
+        self.grad_dirty = None
+        self._unreported = False
         # "ever touched" bitmap (one bit per 8 entries = one 64-byte line of the fp32 table), set by the binned backward where it
         # stores a gradient; the optimizer skips lines whose bit is clear (gradient and both Adam moments exactly zero).  A
         # writer that does not report turns every bit on (mark_all_touched): from then on nothing is skipped.
         self.touched_lines = None
+
+    @property
+    def unreported(self):
+        return self._unreported
+
+    @unreported.setter
+    def unreported(self, value):
+        self._unreported = bool(value)
+        if value and self.grad_dirty is not None:
+            self.grad_dirty.fill_(1)
+
+    def dirty_for_backward(self):
+        """address of the accumulator's dirty word for grid_encode_backward(grad_dirty=...), or None"""
+        return None if self.grad_dirty is None else self.grad_dirty.data_ptr()
 
     def mark_all_touched(self):
         if self.touched_lines is not None:

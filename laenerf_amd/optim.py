@@ -80,6 +80,12 @@ class FusedAdam(torch.optim.Optimizer):
                         shadow.touched_lines = torch.zeros(n_words, dtype=torch.int32, device=p.device)
                 elif shadow is not None and isinstance(owner, FFMLP):
                     shadow.nonfinite_flag = self.dev_state.data_ptr() + 8    # the fused head backward reports its weight gradients
+        # every table's accumulator gets its "dirty" word (TableShadow.grad_dirty; LAE_GRID_NO_DIRTY_WORD=1 is the A/B switch): it
+        # starts at 1 -- an adopted shadow may hold gradients already -- and the first apply / zero_grad clears it
+        if not os.environ.get("LAE_GRID_NO_DIRTY_WORD"):
+            for p, _, _, shadow, _ in self.items:
+                if shadow is not None and isinstance(tables.get(id(p)), GridEncoder) and shadow.grad_dirty is None:
+                    shadow.grad_dirty = torch.ones(1, dtype=torch.int32, device=p.device)
         self._scale_view = self.dev_state.view(torch.float32)
         self._scale_view[0] = init_scale if self.use_scaler else 1.0
         self.device_lr = bool(device_lr)
@@ -184,6 +190,8 @@ class FusedAdam(torch.optim.Optimizer):
         for p, _, _, shadow, _ in self.items:
             if shadow is not None:
                 shadow.grad_half.zero_()
+                if getattr(shadow, "grad_dirty", None) is not None:
+                    shadow.grad_dirty.zero_()
                 p.grad = None
             elif p.grad is not None:
                 p.grad.zero_()
@@ -207,13 +215,14 @@ class FusedAdam(torch.optim.Optimizer):
 
     def _tables(self):
         grads = [self._grad(p, sh) for p, _, _, sh, _ in self.items]
-        key = tuple(g.data_ptr() for g, _ in grads)
+        dirty = [None if sh is None or getattr(sh, "grad_dirty", None) is None else sh.grad_dirty.data_ptr() for _, _, _, sh, _ in self.items]
+        key = tuple(g.data_ptr() for g, _ in grads) + tuple(dirty)
         if self._args is None or self._args["key"] != key:
             n = len(self.items)
             arr = lambda vals: (ctypes.c_void_p * n)(*vals)
             self._args = {
                 "key": key, "n": n,
-                "grads": arr(key), "is_half": (ctypes.c_int * n)(*[h for _, h in grads]),
+                "grads": arr(key[:n]), "dirty": arr(dirty), "is_half": (ctypes.c_int * n)(*[h for _, h in grads]),
                 "sizes": (ctypes.c_uint64 * n)(*[p.numel() for p, *_ in self.items]),
                 "params": arr([p.data_ptr() for p, *_ in self.items]),
                 "m": arr([m.data_ptr() for _, m, *_ in self.items]), "v": arr([v.data_ptr() for _, _, v, *_ in self.items]),
@@ -243,7 +252,7 @@ class FusedAdam(torch.optim.Optimizer):
         _lib.check(lib.lae_adam_begin(st, self.betas[0], self.betas[1], self.growth_interval, self.growth_factor,
                                       self.backoff_factor, int(self.use_scaler), s), "adam_begin")
         _lib.check(lib.lae_adam_apply_multi(a["n"], a["params"], a["m"], a["v"], a["grads"], a["is_half"], a["shadows"],
-                                            a["sizes"], a["lrs"], a["touched"], st, self.betas[0], self.betas[1], self.eps,
+                                            a["sizes"], a["lrs"], a["touched"], a["dirty"], st, self.betas[0], self.betas[1], self.eps,
                                             self.weight_decay, s), "adam_apply")
         for *_, shadow, _ in self.items:                     # the accumulators are zero again
             if shadow is not None and hasattr(shadow, "unreported"):
