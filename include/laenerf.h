@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi15"
+#define LAE_ABI_TAG "abi16"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -269,6 +269,43 @@ LAE_API int lae_composite_rays_train_backward_blend_ex(const float* grad_weights
                                                float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
                                                const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
                                                float* grad_rgbs, void* stream);
+
+/* lae_composite_rays_train_backward_blend_ex that also takes the gradient of the RAW depth output D = sum_k w_k t_k (`depth` of the
+ * forward, not depth_out; t_k = running sum of deltas[.,1]), which the reference's backward drops (raymarching.py:273-275):
+ *   grad_sigmas_k += delta0_k * grad_depth * (T_post_k * t_k - (D - D_k)),  D_k = the running sum including sample k,
+ * inside the same bracket as the colour terms; grad_rgbs is unchanged.  grad_depth [N] (zeros allowed: such a ray takes the path
+ * of lae_composite_rays_train_backward_blend_ex and gives its bits), depth [N] the forward's raw depth.  grad_scale multiplies
+ * grad_depth as well. */
+LAE_API int lae_composite_rays_train_backward_blend_depth(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
+                                                  const float* rgbs, const float* deltas, const int32_t* rays,
+                                                  const float* weights_sum, const float* image, uint32_t M, uint32_t N,
+                                                  float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
+                                                  const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
+                                                  float* grad_rgbs, const float* grad_depth, const float* depth, void* stream);
+
+/* lae_composite_rays_train_step with a second criterion on the ray's raw depth D, the reference's depth supervision
+ * (nerf/utils.py:585-589, 634-635: loss += 1e-3 * mean(((depth - (gt_depth - nears)) * (gt_depth > 0))^2)), in the same launch:
+ *   z = depth_src[depth_inds ? depth_inds[ray] : ray]   depth_src fp32 or fp16 (depth_dtype LAE_IMG_F32 / LAE_IMG_F16), depth_inds
+ *                                                       int64 or NULL (the `inds` of lae_sample_train_batch into a [n_img, H, W] plane)
+ *   res = (z > 0 && nears[ray] < fars[ray]) * (D - (z - nears[ray]))   zero in the plane = no supervision; neither is a ray that
+ *                                                       misses the bounding box (lae_near_far_from_aabb gives it near == far ==
+ *                                                       FLT_MAX, the reference's rule would make the loss infinite there)
+ *   grad_depth[ray] = g_D = ((res * (2 * lambda / N)) * *scale), carried through the backward as
+ *   lae_composite_rays_train_backward_blend_depth does; depth_value_only != 0 computes the value and forces g_D = 0 (the
+ *   reference's effective behaviour: its backward ignores the gradient of depth).  A ray with g_D == 0 gets the sample gradients
+ *   of lae_composite_rays_train_step bit for bit; a ray without samples adds its residual to the value and has no gradient.
+ * partials[b] = sum over the workgroup's rays of (squared colour error + 3 * lambda * res^2), so every finisher of
+ * lae_composite_rays_train_step (n_elem = 3 N) yields loss_out = MSE + lambda * mean(res^2) unchanged; depth_partials
+ * [cdiv(N, 4)] receive sum(res^2): lae_loss_finish(depth_partials, cdiv(N, 4), N, NULL, out) gives mean(res^2) alone.
+ * lambda: finite, >= 0 (LAE_EINVAL otherwise). */
+LAE_API int lae_composite_rays_train_step_depth(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                        uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
+                                        float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
+                                        const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
+                                        float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
+                                        float* partials, int defer_loss, const void* depth_src, int depth_dtype,
+                                        const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
+                                        float* depth_partials, void* stream);
 
 /* raymarching.cu:929-936 */
 LAE_API int lae_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive,

@@ -114,6 +114,9 @@ def retarget_pending_loss(old_grad_sigmas, new_grad_sigmas):
         _pending_loss[_loss_key(new_grad_sigmas)] = e
 
 
+_DEPTH_DTYPES = {torch.float16: 1, torch.float32: 2}        # include/laenerf.h LAE_IMG_F16 / LAE_IMG_F32
+
+
 class _RayMarching:
     @staticmethod
     def near_far_from_aabb(rays_o, rays_d, aabb, N, min_near, nears, fars):
@@ -237,10 +240,13 @@ class _RayMarching:
     @staticmethod
     def composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears, fars, bg_rays, bg, rows_end, target, scale,
                                   weights_sum, depth, image, depth_out, image_out, grad_image, grad_sigmas, grad_rgbs, loss_out,
-                                  partials, defer_loss=False):
+                                  partials, defer_loss=False, depth_sup=None):
         """MI355X extension: compositing forward (+ blend) + MSE criterion + compositing backward in one launch.
         defer_loss: the loss VALUE (loss_out, NaN until then) is summed later -- by the fused head's backward, which takes it
-        along in its reduction launch, or by flush_pending_loss() (laenerf_amd.optim.FusedAdam.backward / step call it)."""
+        along in its reduction launch, or by flush_pending_loss() (laenerf_amd.optim.FusedAdam.backward / step call it).
+        depth_sup: None, or (depth_src, depth_inds, weight, value_only, grad_depth, depth_partials): the depth criterion of
+        lae_composite_rays_train_step_depth in the same launch (depth_src fp16 / fp32, depth_inds int64 or None); the loss value
+        then holds MSE + weight * depth MSE whoever finishes it."""
         ts = (sigmas, rgbs, deltas, rays, nears, fars, bg_rays, rows_end, target, scale, weights_sum, depth, image, depth_out,
               image_out, grad_image, grad_sigmas, grad_rgbs, loss_out, partials)
         need_cuda(*ts); need_contig(*ts)
@@ -248,11 +254,30 @@ class _RayMarching:
                   grad_image, grad_sigmas, grad_rgbs, loss_out, partials)
         if partials.numel() < (N + 3) // 4:
             raise RuntimeError("composite_rays_train_step: partials needs cdiv(N, 4) floats")
-        check(_lib.load().lae_composite_rays_train_step(
-            ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1], bg[2],
-            ptr(rows_end), ptr(target), ptr(scale), ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out),
-            ptr(grad_image), ptr(grad_sigmas), ptr(grad_rgbs), ptr(loss_out), ptr(partials), int(bool(defer_loss)), stream()),
-            "composite_rays_train_step")
+        if depth_sup is None:
+            check(_lib.load().lae_composite_rays_train_step(
+                ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1], bg[2],
+                ptr(rows_end), ptr(target), ptr(scale), ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out),
+                ptr(grad_image), ptr(grad_sigmas), ptr(grad_rgbs), ptr(loss_out), ptr(partials), int(bool(defer_loss)), stream()),
+                "composite_rays_train_step")
+        else:
+            depth_src, depth_inds, weight, value_only, grad_depth, depth_partials = depth_sup
+            ds = (depth_src, depth_inds, grad_depth, depth_partials)
+            need_cuda(*ds); need_contig(*ds); _need_f32(grad_depth, depth_partials)
+            if depth_src.dtype not in _DEPTH_DTYPES:
+                raise RuntimeError("composite_rays_train_step: the depth plane must be float16 or float32")
+            if depth_inds is not None and (depth_inds.dtype != torch.int64 or depth_inds.numel() < N):
+                raise RuntimeError("composite_rays_train_step: depth_inds must be int64 with an entry per ray")
+            if depth_inds is None and depth_src.numel() < N:
+                raise RuntimeError("composite_rays_train_step: without depth_inds the depth needs a value per ray")
+            if grad_depth.numel() < N or depth_partials.numel() < (N + 3) // 4:
+                raise RuntimeError("composite_rays_train_step: grad_depth needs N, depth_partials cdiv(N, 4) floats")
+            check(_lib.load().lae_composite_rays_train_step_depth(
+                ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1], bg[2],
+                ptr(rows_end), ptr(target), ptr(scale), ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out),
+                ptr(grad_image), ptr(grad_sigmas), ptr(grad_rgbs), ptr(loss_out), ptr(partials), int(bool(defer_loss)),
+                ptr(depth_src), _DEPTH_DTYPES[depth_src.dtype], ptr(depth_inds), float(weight), int(bool(value_only)), ptr(grad_depth),
+                ptr(depth_partials), stream()), "composite_rays_train_step_depth")
         if defer_loss and N > 0:                      # N == 0: the library returned at once, there is nothing to finish
             capturing = torch.cuda.is_current_stream_capturing()
             key = _loss_key(grad_sigmas)
@@ -282,6 +307,31 @@ class _RayMarching:
             ptr(grad_weights_sum), ptr(grad_image), ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(weights_sum),
             ptr(image), M, N, T_thresh, ptr(bg_rays), bg[0], bg[1], bg[2], ptr(rows_end), ptr(grad_scale), ptr(grad_sigmas),
             ptr(grad_rgbs), stream()), "composite_rays_train_backward_blend")
+
+    @staticmethod
+    def composite_rays_train_backward_blend_depth(grad_weights_sum, grad_image, grad_depth, sigmas, rgbs, deltas, rays, weights_sum,
+                                                  depth, image, M, N, T_thresh, bg_rays, bg, rows_end, grad_sigmas, grad_rgbs,
+                                                  grad_scale=None):
+        """composite_rays_train_backward_blend that also carries grad_depth [N], the gradient of the forward's RAW depth [N]"""
+        ts = (grad_weights_sum, grad_image, grad_depth, sigmas, rgbs, deltas, rays, weights_sum, depth, image, bg_rays, rows_end,
+              grad_sigmas, grad_rgbs, grad_scale)
+        need_cuda(*ts); need_contig(*ts)
+        _need_f32(grad_weights_sum, grad_image, grad_depth, sigmas, rgbs, deltas, weights_sum, depth, image, bg_rays, grad_sigmas,
+                  grad_rgbs, grad_scale)
+        if grad_depth is None or depth is None or grad_depth.numel() < N or depth.numel() < N:
+            raise RuntimeError("composite_rays_train_backward_blend_depth: grad_depth and depth need a value per ray")
+        check(_lib.load().lae_composite_rays_train_backward_blend_depth(
+            ptr(grad_weights_sum), ptr(grad_image), ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(weights_sum),
+            ptr(image), M, N, T_thresh, ptr(bg_rays), bg[0], bg[1], bg[2], ptr(rows_end), ptr(grad_scale), ptr(grad_sigmas),
+            ptr(grad_rgbs), ptr(grad_depth), ptr(depth), stream()), "composite_rays_train_backward_blend_depth")
+
+    @staticmethod
+    def loss_finish(partials, n_part, n_elem, scale, loss_out):
+        """loss_out[0] = sum(partials[:n_part]) / n_elem * (*scale or 1), loss_out[1] = the same unscaled (fixed order)"""
+        need_cuda(partials, scale, loss_out); need_contig(partials, scale, loss_out); _need_f32(partials, scale, loss_out)
+        if partials.numel() < n_part or loss_out.numel() < 2:
+            raise RuntimeError("loss_finish: partials needs n_part floats, loss_out two")
+        check(_lib.load().lae_loss_finish(ptr(partials), n_part, n_elem, ptr(scale), ptr(loss_out), stream()), "loss_finish")
 
     @staticmethod
     def composite_rays_train_backward(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,

@@ -12,6 +12,8 @@
 #include <string.h>
 #include <algorithm>
 #include <climits>
+#include <type_traits>
+#include <hip/hip_fp16.h>
 #include "lae_common.h"
 #include "raymarch_common.h"
 
@@ -406,12 +408,27 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_fwd(
 // layout lae_march_rays_train produces.
 struct Dense { const float* bg_rays; float bg[3]; const uint32_t* rows_end; const float* grad_scale; };   // grad_scale: device scalar or NULL
 
-template <bool DENSE>
+// DEPTH: additionally the gradient of the raw depth D = sum_k w_k t_k (t_k = running sum of deltas[.,1], as the forward), which
+// the reference's backward drops (raymarching.py:273-275): with D_k the running sum including sample k,
+//   dD / dsigma_k = delta0_k * (T_post_k * t_k - (D - D_k))
+// -- the colour rule with t in place of the colour -- enters the bracket of grad_sigmas times grad_depth[ray]; grad_rgbs does
+// not change.  Two more scans per pass (t, w * t).  A ray whose grad_depth is zero takes the path without them (one ray is one
+// wave: the branch is uniform), so its gradients are the bits of the flavour without DEPTH.  The DEPTH = false instantiations are
+// the kernels they were: every addition is behind `if constexpr`.
+struct DepthGrad { const float* grad_depth; const float* depth; };
+
+// per-ray state of the DEPTH flavours: g_D, the ray's D, the running t and D_k, the squared residual; `on` = g_D != 0 (uniform over
+// the wave: one ray is one wave).  Empty without DEPTH.
+template <bool DEPTH> struct DepthState { float gD = 0.0f, df = 0.0f, t = 0.0f, dsum = 0.0f, dq = 0.0f; bool on = false; };
+template <> struct DepthState<false> {};
+struct NoArg {};                                          // the trailing kernel argument of the flavours without DEPTH
+
+template <bool DENSE, bool DEPTH = false>
 __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
     const float* __restrict__ grad_ws, const float* __restrict__ grad_image, const float* __restrict__ sigmas,
     const float* __restrict__ rgbs, const float* __restrict__ deltas, const int32_t* __restrict__ rays,
     const float* __restrict__ weights_sum, const float* __restrict__ image, uint32_t M, uint32_t N, float T_thresh,
-    float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, Dense dn) {
+    float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, Dense dn, std::conditional_t<DEPTH, DepthGrad, NoArg> dg) {
     const uint32_t n = blockIdx.x * COMP_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // one ray per wave: scalar
     if (n >= N) return;
     const int lane = threadIdx.x & 63;
@@ -425,10 +442,13 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
     if (num_steps == 0 || offset + num_steps > M) return;                   // :624
     float gws = grad_ws ? grad_ws[index] : 0.0f;
     float g0 = grad_image[3 * (size_t)index], g1 = grad_image[3 * (size_t)index + 1], g2 = grad_image[3 * (size_t)index + 2];
+    [[maybe_unused]] DepthState<DEPTH> ds;
+    if constexpr (DEPTH) { ds.gD = dg.grad_depth[index]; ds.df = dg.depth[index]; }
     if constexpr (DENSE) {
         if (dn.grad_scale) {                               // fused criterion: upstream d(loss) arrives as a device scalar
             const float gs = dn.grad_scale[0];
             g0 *= gs; g1 *= gs; g2 *= gs; gws *= gs;
+            if constexpr (DEPTH) ds.gD *= gs;
         }
         const float* bg = dn.bg_rays ? dn.bg_rays + 3 * (size_t)index : dn.bg;
         gws = gws - ((g0 * bg[0] + g1 * bg[1]) + g2 * bg[2]);
@@ -436,6 +456,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
     const float rf = image[3 * (size_t)index], gf = image[3 * (size_t)index + 1], bf = image[3 * (size_t)index + 2];
     const float tail = gws * (1 - weights_sum[index]);
     float T = 1.0f, r = 0, g = 0, b = 0;
+    if constexpr (DEPTH) ds.on = ds.gD != 0.0f;
     bool stopped = false;
     for (uint32_t base = 0; base < num_steps; base += 64) {
         const uint32_t k = base + lane;
@@ -462,16 +483,32 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
         const float rk = r + wave_scan_add(w * c0, lane);                   // running sums INCLUDING this sample
         const float gk = g + wave_scan_add(w * c1, lane);
         const float bk = b + wave_scan_add(w * c2, lane);
+        [[maybe_unused]] float tk = 0.0f, dk = 0.0f;
+        if constexpr (DEPTH) {
+            if (ds.on) {
+                tk = ds.t + wave_scan_add(in_ray ? deltas[2 * i + 1] : 0.0f, lane);  // t_k, as k_composite_train_fwd
+                dk = ds.dsum + wave_scan_add(w * tk, lane);                          // D_k, including this sample
+            }
+        }
         if (valid) {
             grad_rgbs[3 * i] = g0 * w; grad_rgbs[3 * i + 1] = g1 * w; grad_rgbs[3 * i + 2] = g2 * w;      // :657-659
-            grad_sigmas[i] = d0 * (g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gk)) +
-                                   g2 * (T_post * c2 - (bf - bk)) + tail);                                // :662-667
+            if constexpr (DEPTH) {
+                const float br = g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gk)) + g2 * (T_post * c2 - (bf - bk)) + tail;
+                if (ds.on) grad_sigmas[i] = d0 * (br + ds.gD * (T_post * tk - (ds.df - dk)));
+                else grad_sigmas[i] = d0 * br;
+            } else {
+                grad_sigmas[i] = d0 * (g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gk)) +
+                                       g2 * (T_post * c2 - (bf - bk)) + tail);                            // :662-667
+            }
         } else if (DENSE && in_ray) {
             grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f; grad_sigmas[i] = 0.f;
         }
         if (done) { if (DENSE) { stopped = true; continue; } break; }
         T *= wave_last(incl);
         r = wave_last(rk); g = wave_last(gk); b = wave_last(bk);
+        if constexpr (DEPTH) {
+            if (ds.on) { ds.t = wave_last(tk); ds.dsum = wave_last(dk); }
+        }
     }
 }
 
@@ -484,12 +521,24 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
 // order (deterministic).
 struct StepLoss { const float* target; const float* scale; float* grad_image; float* partials; float* poison_loss; };
 
+// DEPTH: a second criterion on the raw depth D of the ray, the reference's depth supervision (nerf/utils.py:585-589, 634-635):
+//   z = depth_src[inds ? inds[index] : index] (fp32 or fp16),  m = z > 0 && nears[index] < fars[index],  res = m * (D - (z - nears[index])),
+//   loss += lambda * mean(res^2),  g_D = ((res * (2 * lambda / N)) * scale) -> grad_depth[index]
+// and the backward carries g_D as k_composite_train_bwd<true, true> does (the reference's backward drops it; value_only restores that:
+// the value is computed, g_D is forced to zero).  A ray with g_D == 0 runs the statements of the flavour without DEPTH.
+// partials[] receive sum(sq + 3 * lambda * res^2): the finishers, which divide by 3 N, yield MSE + lambda * mean(res^2) as they are;
+// depth_partials[] receive sum(res^2) (lae_loss_finish with n_elem = N gives the depth term alone).
+struct DepthLoss { const void* src; int dtype; const int64_t* inds; float lambda; int value_only; float* grad_depth; float* partials; };
+
+template <bool DEPTH>
 __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
     const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum,
     float* __restrict__ depth, float* __restrict__ image, Blend bl, StepLoss sl, const uint32_t* __restrict__ rows_end_p,
-    float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs) {
+    float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, std::conditional_t<DEPTH, DepthLoss, NoArg> dl) {
     __shared__ float s_sq[COMP_WAVES];
+    [[maybe_unused]] __shared__ float s_dq[COMP_WAVES];
+    [[maybe_unused]] DepthState<DEPTH> ds;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t n = blockIdx.x * COMP_WAVES + wv;                      // one ray per wave: scalar
     const int lane = threadIdx.x & 63;
@@ -555,6 +604,20 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
                     e2 = o2 - sl.target[3 * (size_t)index + 2];
         sq = fmaf(e2, e2, fmaf(e1, e1, e0 * e0));
         float g0 = (e0 * gk) * s, g1 = (e1 * gk) * s, g2 = (e2 * gk) * s;
+        if constexpr (DEPTH) {
+            const size_t zi = dl.inds ? (size_t)dl.inds[index] : (size_t)index;
+            const float z = dl.dtype == LAE_IMG_F16 ? __half2float(((const __half*)dl.src)[zi]) : ((const float*)dl.src)[zi];
+            // a ray that misses the bounding box carries the sentinel interval near == far == FLT_MAX: it has no near to measure from
+            // and is left unsupervised like a pixel with z == 0 (its residual would be ~FLT_MAX and the loss value infinite)
+            const float nr = bl.nears[index];
+            const float res = (z > 0.0f && nr < bl.fars[index] ? 1.0f : 0.0f) * (d - (z - nr));
+            ds.dq = res * res;
+            sq = sq + (3.0f * dl.lambda) * ds.dq;
+            ds.gD = dl.value_only ? 0.0f : (res * (2.0f * dl.lambda / (float)N)) * s;
+            ds.df = d;
+            ds.on = ds.gD != 0.0f;
+            if (lane == 0) dl.grad_depth[index] = ds.gD;
+        }
         if (lane == 0) {
             weights_sum[index] = ws; depth[index] = d;
             image[3 * (size_t)index] = r; image[3 * (size_t)index + 1] = g; image[3 * (size_t)index + 2] = b;
@@ -598,26 +661,49 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
                 const float rk = rr + wave_scan_add(w * c0, lane);
                 const float gkk = gg + wave_scan_add(w * c1, lane);
                 const float bk = bb + wave_scan_add(w * c2, lane);
+                [[maybe_unused]] float tk = 0.0f, dk = 0.0f;
+                if constexpr (DEPTH) {
+                    if (ds.on) {
+                        tk = ds.t + wave_scan_add(cur.d1, lane);                     // cur.d1 is zero past the ray's end
+                        dk = ds.dsum + wave_scan_add(w * tk, lane);
+                    }
+                }
                 if (valid) {
                     grad_rgbs[3 * i] = g0 * w; grad_rgbs[3 * i + 1] = g1 * w; grad_rgbs[3 * i + 2] = g2 * w;
-                    grad_sigmas[i] = d0 * (g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gkk)) +
-                                           g2 * (T_post * c2 - (bf - bk)) + tail);
+                    if constexpr (DEPTH) {
+                        const float br = g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gkk)) + g2 * (T_post * c2 - (bf - bk)) + tail;
+                        if (ds.on) grad_sigmas[i] = d0 * (br + ds.gD * (T_post * tk - (ds.df - dk)));
+                        else grad_sigmas[i] = d0 * br;
+                    } else {
+                        grad_sigmas[i] = d0 * (g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gkk)) +
+                                               g2 * (T_post * c2 - (bf - bk)) + tail);
+                    }
                 } else if (in_ray) {
                     grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f; grad_sigmas[i] = 0.f;
                 }
                 if (done) { stopped = true; continue; }
                 T *= wave_last(incl);
                 rr = wave_last(rk); gg = wave_last(gkk); bb = wave_last(bk);
+                if constexpr (DEPTH) {
+                    if (ds.on) { ds.t = wave_last(tk); ds.dsum = wave_last(dk); }
+                }
             }
         }
     }
     if (lane == 0) s_sq[wv] = sq;
+    if constexpr (DEPTH) { if (lane == 0) s_dq[wv] = ds.dq; }
     __syncthreads();
     if (threadIdx.x == 0) {
         float t = 0.0f;
 #pragma unroll
         for (int w = 0; w < COMP_WAVES; w++) t += s_sq[w];
         sl.partials[blockIdx.x] = t;
+        if constexpr (DEPTH) {
+            float u = 0.0f;
+#pragma unroll
+            for (int w = 0; w < COMP_WAVES; w++) u += s_dq[w];
+            dl.partials[blockIdx.x] = u;
+        }
         // deferred loss value (lae_composite_rays_train_step with poison_loss): whoever reads it before the finishing
         // launch (lae_loss_finish, or the extra block of lae_nerf_head_backward) sees NaN, not a stale number
         if (blockIdx.x == 0 && sl.poison_loss) { sl.poison_loss[0] = __builtin_nanf(""); sl.poison_loss[1] = __builtin_nanf(""); }
@@ -906,13 +992,38 @@ int lae_composite_rays_train_step(const float* sigmas, const float* rgbs, const 
     const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
     const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
     const uint32_t nb = lae::cdiv(N, COMP_WAVES);
-    k_composite_train_step<<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image, bl,
-                                                                 sl, rows_end, grad_sigmas, grad_rgbs);
+    k_composite_train_step<false><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth,
+                                                                        image, bl, sl, rows_end, grad_sigmas, grad_rgbs, NoArg{});
     // defer_loss: the one-block sum of the partials (5.5 us + a kernel boundary on the step's critical path for a number that
     // feeds nothing on the device) is left to lae_loss_finish or to a later launch that takes it along
     // (lae_nerf_head_backward); loss_out holds NaN until then
     if (!defer_loss) k_loss_finish<<<1, 1024, 0, STREAM(stream)>>>(partials, nb, 3u * N, scale, loss_out);
     return lae::check_launch("composite_rays_train_step");
+}
+
+int lae_composite_rays_train_step_depth(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                        uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
+                                        float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
+                                        const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
+                                        float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
+                                        float* partials, int defer_loss, const void* depth_src, int depth_dtype,
+                                        const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
+                                        float* depth_partials, void* stream) {
+    if (depth_dtype != LAE_IMG_F16 && depth_dtype != LAE_IMG_F32) return LAE_EINVAL;
+    if (!(lambda >= 0.0f) || !(lambda <= 3.0e38f)) return LAE_EINVAL;      // NaN, negative and infinite weights
+    if (N == 0) return LAE_OK;
+    if (!rays || !weights_sum || !depth || !image || !nears || !fars || !depth_out || !image_out || !rows_end || !target || !grad_image ||
+        !loss_out || !partials || !depth_src || !grad_depth || !depth_partials)
+        return LAE_ENULL;                                   // depth_inds may be NULL (depth_src holds one value per ray)
+    if (M > 0 && (!sigmas || !rgbs || !deltas || !grad_sigmas || !grad_rgbs)) return LAE_ENULL;
+    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
+    const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
+    const DepthLoss dl{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials};
+    const uint32_t nb = lae::cdiv(N, COMP_WAVES);
+    k_composite_train_step<true><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth,
+                                                                       image, bl, sl, rows_end, grad_sigmas, grad_rgbs, dl);
+    if (!defer_loss) k_loss_finish<<<1, 1024, 0, STREAM(stream)>>>(partials, nb, 3u * N, scale, loss_out);
+    return lae::check_launch("composite_rays_train_step_depth");
 }
 
 int lae_loss_finish(const float* partials, uint32_t n_part, uint32_t n_elem, const float* scale, float* loss_out, void* stream) {
@@ -933,8 +1044,25 @@ int lae_composite_rays_train_backward_blend_ex(const float* grad_weights_sum, co
         return LAE_ENULL;                                   // grad_weights_sum may be NULL (= zero)
     const Dense dn{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale};
     k_composite_train_bwd<true><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
-        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn);
+        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn, NoArg{});
     return lae::check_launch("composite_rays_train_backward_blend");
+}
+
+int lae_composite_rays_train_backward_blend_depth(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
+                                                  const float* rgbs, const float* deltas, const int32_t* rays,
+                                                  const float* weights_sum, const float* image, uint32_t M, uint32_t N,
+                                                  float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
+                                                  const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
+                                                  float* grad_rgbs, const float* grad_depth, const float* depth, void* stream) {
+    if (N == 0 || M == 0) return LAE_OK;
+    if (!grad_image || !sigmas || !rgbs || !deltas || !rays || !weights_sum || !image || !grad_sigmas || !grad_rgbs || !rows_end ||
+        !grad_depth || !depth)
+        return LAE_ENULL;                                   // grad_weights_sum may be NULL (= zero)
+    const Dense dn{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale};
+    k_composite_train_bwd<true, true><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
+        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn,
+        DepthGrad{grad_depth, depth});
+    return lae::check_launch("composite_rays_train_backward_blend_depth");
 }
 
 int lae_composite_rays_train_backward_blend(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
@@ -958,7 +1086,7 @@ int lae_composite_rays_train_backward(const float* grad_weights_sum, const float
         return LAE_ENULL;
     k_composite_train_bwd<false><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
         grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas,
-        grad_rgbs, Dense{});
+        grad_rgbs, Dense{}, NoArg{});
     return lae::check_launch("composite_rays_train_backward");
 }
 

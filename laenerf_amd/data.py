@@ -187,10 +187,13 @@ class ResidentImages:
     """images [n, H, W, C] (C = 3 or 4; uint8, fp16 or fp32) + cam2world poses [n, 4, 4] + one (fx, fy, cx, cy), on the GPU.
 
     bg: 'random' (a per-pixel uniform background, the reference's rule for C = 4) or 'white' (its bg_color = 1, used for
-    C = 3); default by C.  color_space 'linear' converts the colour to linear before the blend (nerf/utils.py:564)."""
+    C = 3); default by C.  color_space 'linear' converts the colour to linear before the blend (nerf/utils.py:564).
+    depths (optional, or set_depths): a per-pixel depth plane [n, H, W], fp16 or fp32, resident on the device: the distance
+    along the pixel's ray from its origin, zero = no supervision (the reference's `d_` planes, nerf/gui.py:406, 508-511).
+    sample() does not read it: the Trainer's compositing kernel gathers it by the batch's `inds`."""
 
     def __init__(self, images, poses, intrinsics, bound=1.0, min_near=0.2, mode="image", bg=None, color_space="srgb", seed=0,
-                 device=None, error_map=False):
+                 device=None, error_map=False, depths=None):
         device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         # (device="cpu" holds the arrays on the host -- loaders and tests without a GPU; sample() needs the GPU)
         images = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))
@@ -219,6 +222,25 @@ class ResidentImages:
         self.error_map = None
         if error_map:
             self.enable_error_map()
+        self.depths = None
+        if depths is not None:
+            self.set_depths(depths)
+
+    def set_depths(self, plane):
+        """set .depths: the depth plane [n_img, H, W] (fp16 / fp32 tensor or array; other float arrays are stored as fp32), copied
+        to the images' device; None removes it"""
+        if plane is None:
+            self.depths = None
+            return None
+        plane = plane if torch.is_tensor(plane) else torch.from_numpy(np.ascontiguousarray(plane))
+        if tuple(plane.shape) != (self.n_img, self.H, self.W):
+            raise ValueError(f"ResidentImages: depths must be [{self.n_img}, {self.H}, {self.W}]")
+        if not plane.dtype.is_floating_point:
+            raise ValueError("ResidentImages: depths must be a floating-point plane")
+        if plane.dtype not in (torch.float16, torch.float32):
+            plane = plane.to(torch.float32)
+        self.depths = plane.to(self.images.device).contiguous()
+        return self.depths
 
     def enable_error_map(self, init=1.0):
         """create .error_map: [n_img, 16384] fp32 cell weights, every one `init` (the reference's torch.ones).  From then on

@@ -38,15 +38,19 @@ class DistillSet:
     """The extracted edit rows of every non-occluded view, packed once: img_idx, pix [R] int32 (target image, pixel), w [R] (the edit
     weight, weights_editgrid[indices]), pred [R,3] (the distill render's colour there), x_term, dirs [R,3] (the palette network's
     inputs), dist [R] (the smooth-transition weight, 0 off indices_interp; None without a grow grid), and per view offsets [V] int64,
-    counts [V] int32, view_img [V] int32 (pose_idx).  occluded: the image indices without rows; n_img: images of the training set."""
+    counts [V] int32, view_img [V] int32 (pose_idx).  occluded: the image indices without rows; n_img: images of the training set.
+    depth [R] (optional): the distill render's depth at the rows (the views' `depths`), for distill_images(depth_sup=True)."""
 
-    def __init__(self, img_idx, pix, w, pred, x_term, dirs, dist, counts, view_img, occluded, n_img, device=None):
+    def __init__(self, img_idx, pix, w, pred, x_term, dirs, dist, counts, view_img, occluded, n_img, device=None, depth=None):
         device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         t = lambda a, dt: a.detach().to(device, dt).contiguous()
         self.img_idx, self.pix = t(img_idx, torch.int32), t(pix, torch.int32)
         self.w, self.pred = t(w, torch.float32), t(pred, torch.float32).reshape(-1, 3)
         self.x_term, self.dirs = t(x_term, torch.float32).reshape(-1, 3), t(dirs, torch.float32).reshape(-1, 3)
         self.dist = None if dist is None else t(dist, torch.float32)
+        self.depth = None if depth is None else t(depth, torch.float32).reshape(-1)
+        if self.depth is not None and self.depth.numel() != self.w.numel():
+            raise ValueError("DistillSet: depth needs a value per row")
         self.counts_host = np.asarray(counts, np.int64).reshape(-1)
         self.offsets_host = np.concatenate([[0], np.cumsum(self.counts_host)[:-1]]).astype(np.int64)
         self.view_img_host = np.asarray(view_img, np.int64).reshape(-1)
@@ -64,7 +68,8 @@ class DistillSet:
     def from_views(cls, views, occluded, n_img, device=None):
         """the per-view dicts of extract_views (CPU or device tensors; `pose_idx` is the target image) and its occluded list.
         Rows: the view's `indices` (pixels), `w8s` (= weights_editgrid[indices]), pred_imgs[indices], x_term, dirs; with a grow grid,
-        dist_weights scattered to the rows at indices_interp."""
+        dist_weights scattered to the rows at indices_interp; `depths` (K values, the render's depth at the rows) when every view
+        has them."""
         views = list(views)
         occ = {int(i) for i in occluded}
         n_img = int(n_img)
@@ -80,7 +85,8 @@ class DistillSet:
         if any(smooth) and not all(smooth):
             raise ValueError("DistillSet.from_views: indices_interp / dist_weights in some views only")
         cpu = lambda a: a.detach().cpu()
-        img, pix, w, pred, xt, dr, dist, counts = [], [], [], [], [], [], [], []
+        img, pix, w, pred, xt, dr, dist, counts, dep = [], [], [], [], [], [], [], [], []
+        has_depth = bool(views) and all(v.get("depths") is not None for v in views)
         for v in views:
             idx = cpu(v["indices"]).long().reshape(-1)
             K = int(idx.numel())
@@ -93,6 +99,10 @@ class DistillSet:
             pred.append(cpu(v["pred_imgs"]).float().reshape(-1, 3)[idx])
             xt.append(cpu(v["x_term"]).float().reshape(-1, 3))
             dr.append(cpu(v["dirs"]).float().reshape(-1, 3))
+            if has_depth:
+                if int(v["depths"].numel()) != K:
+                    raise ValueError("DistillSet.from_views: a view's depths must have one value per row of indices")
+                dep.append(cpu(v["depths"]).float().reshape(-1))
             if all(smooth) and views:
                 d = torch.zeros(K, dtype=torch.float32)
                 d[cpu(v["indices_interp"]).long().reshape(-1)] = cpu(v["dist_weights"]).float().reshape(-1)
@@ -101,7 +111,8 @@ class DistillSet:
             z3 = torch.zeros(0, 3)
             return cls(torch.zeros(0), torch.zeros(0), torch.zeros(0), z3, z3, z3, None, [], [], sorted(occ), n_img, device=device)
         return cls(torch.cat(img), torch.cat(pix), torch.cat(w), torch.cat(pred), torch.cat(xt), torch.cat(dr),
-                   torch.cat(dist) if all(smooth) else None, counts, [int(v["pose_idx"]) for v in views], sorted(occ), n_img, device=device)
+                   torch.cat(dist) if all(smooth) else None, counts, [int(v["pose_idx"]) for v in views], sorted(occ), n_img, device=device,
+                   depth=torch.cat(dep) if has_depth else None)
 
 
 @torch.no_grad()
@@ -156,14 +167,16 @@ def _copy_images(images, dtype):
 
 @torch.no_grad()
 def distill_images(data, style_enc, dset, palette=None, p_weights=None, p_bias=None, blend_thresh=0.5, no_bg=False,
-                   smooth_transition=False, error_maps=False, dtype=torch.float16):
+                   smooth_transition=False, error_maps=False, dtype=torch.float16, depth_sup=False):
     """distill_dataset (gui.py:357-541) on the device -> a NEW ResidentImages (same poses, intrinsics, bound, mode, bg, colour space)
     whose images are the recoloured targets; `data` is left untouched.
     The images are copied in `dtype` (uint8 as value / 255 in fp32, then dtype), the palette network runs once over the packed rows,
     one lae_distill_compose launch rewrites every view.  palette [n_active, 3], p_weights / p_bias [n_active]: the edit (default:
     the network's active palette, ones, zeros).  smooth_transition: interpolate towards the original palette by the rows' distance
     weights (needs a DistillSet extracted with a grow grid), applied only when the edit is not the identity (gui.py:447).
-    error_maps: a map of ones, the non-occluded views' rows seeded from the edit weights (lae_error_map_seed, gui.py:419-425)."""
+    error_maps: a map of ones, the non-occluded views' rows seeded from the edit weights (lae_error_map_seed, gui.py:419-425).
+    depth_sup: the result carries a depth plane [n_img, H, W] fp32 (`.depths`): the rows' depths scattered to their pixels,
+    `d_[indices] = depth`, zero elsewhere and on occluded views (gui.py:406, 508-511) -- once per distillation, torch indexing."""
     if dtype not in _DTYPE_CODES:
         raise ValueError("distill_images: dtype must be torch.float16 or torch.float32 (quantised targets would deviate from the "
                          "reference, which trains on float images)")
@@ -171,6 +184,8 @@ def distill_images(data, style_enc, dset, palette=None, p_weights=None, p_bias=N
         raise ValueError(f"distill_images: the set was packed for {dset.n_img} images, the data has {data.n_img}")
     if dset.device != data.images.device or dset.device != style_enc.color_palette.device:
         raise ValueError("distill_images: the data, the set and the network must live on the same device")
+    if depth_sup and dset.depth is None:
+        raise ValueError("distill_images: depth_sup needs views that carry `depths` (extract_views returns them)")
     if smooth_transition and dset.dist is None:
         raise ValueError("distill_images: smooth_transition needs views extracted with a grow grid (indices_interp / dist_weights)")
     images = _copy_images(data.images, dtype)
@@ -186,6 +201,10 @@ def distill_images(data, style_enc, dset, palette=None, p_weights=None, p_bias=N
     if error_maps:
         out.enable_error_map()
         seed_launch(dset, out.error_map, data.H, data.W)
+    if depth_sup:
+        plane = torch.zeros(data.n_img, data.H * data.W, dtype=torch.float32, device=images.device)
+        plane[dset.img_idx.long(), dset.pix.long()] = dset.depth
+        out.set_depths(plane.view(data.n_img, data.H, data.W))
     return out
 
 
@@ -220,14 +239,19 @@ def seed_launch(dset, error_map, H, W):
 
 
 def distill_nerf(renderer, optimizer, data, style_enc, views, occluded, steps=3000, lr=1e-2, error_maps=False, trainer_kw=None,
-                 **compose_kw):
+                 depth_sup=False, depth_weight=1e-3, depth_grad=True, **compose_kw):
     """the whole stage: distill_images, then a new Trainer(renderer, optimizer, distilled, iters=steps, lr=lr, error_map='ema' with
     error maps) run for distill_steps(steps) steps -> (distilled ResidentImages, Trainer).  views / occluded: extract_views' result;
-    compose_kw: distill_images' edit arguments; trainer_kw: further Trainer arguments (num_rays, seed, ...)."""
+    compose_kw: distill_images' edit arguments; trainer_kw: further Trainer arguments (num_rays, seed, ...).
+    depth_sup: train with the reference's depth term (its `depth_sup = style_weight > 0`, gui.py:202) on the views' extracted
+    depths, weight depth_weight (1e-3 and the mask depth > 0: nerf/utils.py:587-589, 635).  depth_grad=True lets the term hold the
+    geometry in place; depth_grad=False is the reference's effective behaviour, where the term only changes the logged loss."""
     from ..trainer import Trainer
     dset = DistillSet.from_views(views, occluded, data.n_img, device=data.images.device)
-    distilled = distill_images(data, style_enc, dset, error_maps=error_maps, **compose_kw)
-    tr = Trainer(renderer, optimizer, distilled, iters=steps, lr=lr, error_map="ema" if error_maps else None, **(trainer_kw or {}))
+    distilled = distill_images(data, style_enc, dset, error_maps=error_maps, depth_sup=depth_sup, **compose_kw)
+    depth_kw = {"depth_weight": depth_weight, "depth_grad": depth_grad} if depth_sup else {}
+    tr = Trainer(renderer, optimizer, distilled, iters=steps, lr=lr, error_map="ema" if error_maps else None, **depth_kw,
+                 **(trainer_kw or {}))
     tr.train(distill_steps(steps))
     return distilled, tr
 

@@ -14,7 +14,8 @@ from ..backend import raymarching_backend as _backend
 
 __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", "packbits", "march_rays_train",
            "composite_rays_train", "march_rays", "march_rays_distill", "composite_rays", "composite_rays_distill",
-           "compact_rays_alive", "render_frame", "composite_rays_train_blend", "composite_rays_train_blend_mse", "density_grid_positions", "density_grid_partial_positions", "density_grid_update", "mark_untrained_grid"]
+           "compact_rays_alive", "render_frame", "composite_rays_train_blend", "composite_rays_train_blend_mse", "composite_rays_train_blend_depth", "finish_depth_loss",
+           "composite_depth_numpy", "density_grid_positions", "density_grid_partial_positions", "density_grid_update", "mark_untrained_grid"]
 
 
 def _gpu(t):
@@ -282,6 +283,60 @@ def composite_rays_train_blend(sigmas, rgbs, deltas, rays, nears, fars, bg_color
     return _composite_rays_train_blend.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh)
 
 
+class _composite_rays_train_blend_depth(Function):
+    """_composite_rays_train_blend that also returns the RAW depth D = sum_k w_k t_k, differentiable: its backward is
+    lae_composite_rays_train_backward_blend_depth, which carries the gradient the reference's backward drops (raymarching.py:273-275)"""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh):
+        sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
+        M, N = sigmas.shape[0], rays.shape[0]
+        dev, dt = sigmas.device, sigmas.dtype
+        weights_sum, depth, image = (torch.empty(N, dtype=dt, device=dev), torch.empty(N, dtype=dt, device=dev),
+                                     torch.empty(N, 3, dtype=dt, device=dev))
+        depth_out, image_out = torch.empty(N, dtype=dt, device=dev), torch.empty(N, 3, dtype=dt, device=dev)
+        _backend.composite_rays_train_forward_blend(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(),
+                                                    fars.contiguous(), bg_rays, bg, weights_sum, depth, image, depth_out, image_out)
+        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, depth, image, bg_rays, rows_end)
+        ctx.dims = [M, N, T_thresh, bg]
+        ctx.mark_non_differentiable(depth_out)
+        ctx.set_materialize_grads(False)
+        return weights_sum, depth, depth_out, image_out
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, grad_weights_sum, grad_depth, grad_depth_out, grad_image):
+        sigmas, rgbs, deltas, rays, weights_sum, depth, image, bg_rays, rows_end = ctx.saved_tensors
+        M, N, T_thresh, bg = ctx.dims
+        if grad_image is None and grad_weights_sum is None and grad_depth is None:
+            return (None,) * 10
+        if grad_image is None:
+            grad_image = torch.zeros_like(image)
+        gws = None if grad_weights_sum is None else grad_weights_sum.float().contiguous()
+        grad_sigmas, grad_rgbs = torch.empty_like(sigmas), torch.empty_like(rgbs)
+        if grad_depth is None:
+            _backend.composite_rays_train_backward_blend(gws, grad_image.float().contiguous(), sigmas, rgbs, deltas, rays, weights_sum,
+                                                         image, M, N, T_thresh, bg_rays, bg, rows_end, grad_sigmas, grad_rgbs)
+        else:
+            _backend.composite_rays_train_backward_blend_depth(gws, grad_image.float().contiguous(), grad_depth.float().contiguous(),
+                                                               sigmas, rgbs, deltas, rays, weights_sum, depth, image, M, N, T_thresh,
+                                                               bg_rays, bg, rows_end, grad_sigmas, grad_rgbs)
+        return (grad_sigmas, grad_rgbs) + (None,) * 8
+
+
+def composite_rays_train_blend_depth(sigmas, rgbs, deltas, rays, nears, fars, bg_color=1, T_thresh=1e-4):
+    """-> weights_sum [N], depth_raw [N], depth_out [N] (normalised to [0,1], no gradient), image blended over bg_color [N,3].
+    depth_raw = sum_k w_k t_k (t from the ray's first sample, the `depth` of composite_rays_train) carries a gradient to the
+    densities: the building block of depth losses (DS-NeRF-style sparse depth, the distillation's depth term).  The
+    reference-named composite_rays_train keeps ignoring the gradient of depth."""
+    rows_end = getattr(rays, "rows_end", None)
+    if rows_end is None:
+        raise RuntimeError("composite_rays_train_blend_depth: `rays` must be the tensor returned by laenerf_amd march_rays_train")
+    bg_rays, bg = _bg_args(bg_color, sigmas.device)
+    return _composite_rays_train_blend_depth.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh)
+
+
 # root gradients known to be all ones (laenerf_amd.optim.FusedAdam.backward registers the tensor it passes to
 # loss.backward): for them the fused node below hands its stored sample gradients on unchanged.  address -> weak reference:
 # an address whose tensor has died may belong to anything by now
@@ -345,13 +400,110 @@ class _composite_rays_train_blend_mse(Function):
         return grad_sigmas, grad_rgbs, None, None, None, None, None, None, None, None, None, None, None
 
 
+class _DepthPlane:
+    """holds the depth plane on its way through Function.apply: custom_fwd(cast_inputs=float32) would copy a fp16 plane of the whole
+    image set to fp32 in every step under autocast; the kernel reads fp16 itself"""
+    __slots__ = ("t",)
+
+    def __init__(self, t):
+        self.t = t
+
+
+class _composite_rays_train_blend_mse_depth(Function):
+    """_composite_rays_train_blend_mse with the depth criterion in the same kernel (`lae_composite_rays_train_step_depth`):
+    loss = MSE + depth_weight * mean(((D - (z - nears)) * (z > 0))^2), z gathered from the depth plane by the kernel."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, defer_loss, depth_src,
+                depth_inds, depth_weight, value_only):
+        sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
+        M, N = sigmas.shape[0], rays.shape[0]
+        dev, dt = sigmas.device, sigmas.dtype
+        weights_sum, depth, image = (torch.empty(N, dtype=dt, device=dev), torch.empty(N, dtype=dt, device=dev),
+                                     torch.empty(N, 3, dtype=dt, device=dev))
+        depth_out, image_out = torch.empty(N, dtype=dt, device=dev), torch.empty(N, 3, dtype=dt, device=dev)
+        target = target.float().contiguous()
+        if target.shape != image_out.shape:
+            raise RuntimeError("composite_rays_train_blend_mse: target must be [N,3]")
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        grad_image = torch.empty_like(image_out)
+        grad_sigmas, grad_rgbs = torch.empty_like(sigmas), torch.empty_like(rgbs)
+        partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
+        grad_depth = torch.empty(N, dtype=torch.float32, device=dev)
+        depth_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
+        _backend.composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(), fars.contiguous(), bg_rays,
+                                           bg, rows_end, target, scale, weights_sum, depth, image, depth_out, image_out, grad_image,
+                                           grad_sigmas, grad_rgbs, out, partials, defer_loss=defer_loss,
+                                           depth_sup=(depth_src.t, depth_inds, depth_weight, value_only, grad_depth, depth_partials))
+        ctx.save_for_backward(grad_sigmas, grad_rgbs)
+        ctx.mark_non_differentiable(weights_sum, depth_out, image_out, out, depth_partials, grad_depth)
+        ctx.set_materialize_grads(False)
+        return out[0], weights_sum, depth_out, image_out, out, depth_partials, grad_depth
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, grad_loss, *_):
+        if grad_loss is None:
+            return (None,) * 17
+        grad_sigmas, grad_rgbs = ctx.saved_tensors
+        if not _is_unit_root_grad(grad_loss):
+            gl = grad_loss.float()
+            scaled = grad_sigmas * gl
+            from ..backend import retarget_pending_loss
+            retarget_pending_loss(grad_sigmas, scaled)
+            grad_sigmas, grad_rgbs = scaled, grad_rgbs * gl
+        return (grad_sigmas, grad_rgbs) + (None,) * 15
+
+
+def finish_depth_loss(loss, out=None):
+    """the depth term alone, mean(((D - (z - nears)) * (z > 0))^2) without its weight, of a `loss` made by
+    composite_rays_train_blend_mse(depth=...): one lae_loss_finish launch over the step's depth partial sums, off the gradient
+    path.  out: a float32 tensor of 2 elements to write to (both receive the value); -> out[1] as a 0-dim tensor"""
+    parts = getattr(loss, "depth_partials", None)
+    if parts is None:
+        raise RuntimeError("finish_depth_loss: the loss was made without a depth criterion")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=parts.device)
+    _backend.loss_finish(parts, parts.numel(), loss.depth_rays, None, out)
+    return out[1]
+
+
 def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, target, bg_color=1, T_thresh=1e-4, scaler=None,
-                                   defer_loss=None):
+                                   defer_loss=None, depth=None, depth_inds=None, depth_weight=0.0, depth_grad=True):
     """-> (loss, weights_sum, depth, image): loss = MSE(image, target) times the loss scale of `scaler` (a FusedAdam, a
     1-element fp32 cuda tensor, or None); `loss.unscaled` holds the plain MSE.  Only `loss` carries a gradient.
     defer_loss (default: True when `scaler` is a FusedAdam): the VALUE of loss / loss.unscaled is NaN until the backward pass
     has run (the fused head's backward sums it in its reduction launch; FusedAdam.backward() / step() finish it otherwise) --
-    the gradients do not depend on it, and the trainer reads it after the step (nerf/utils.py `loss.item()` for logging)."""
+    the gradients do not depend on it, and the trainer reads it after the step (nerf/utils.py `loss.item()` for logging).
+    depth (default None: today's call, bit for bit): depth supervision in the same kernel.  A float16 / float32 tensor of
+    ray-origin distances, zero = no supervision: one value per ray, or with depth_inds [N] int64 (ResidentImages.sample's `inds`)
+    any plane they index.  loss becomes MSE + depth_weight * mean(((D - (depth - nears)) * (depth > 0))^2), the reference's depth
+    term (nerf/utils.py:585-589, 634-635, weight 1e-3 there); D is the raw composited depth.  A ray that misses the bounding box
+    (nears == fars, the sentinel of near_far_from_aabb) is unsupervised whatever the plane holds: it has no near.  depth_grad=True carries the
+    term's gradient to the densities -- the reference's backward drops it (raymarching.py:273-275), depth_grad=False restates
+    that: the value only, the sample gradients of the call without depth bit for bit.  `loss.grad_depth` [N] holds d loss / d D,
+    finish_depth_loss(loss) the unweighted depth term."""
+    rows_end = getattr(rays, "rows_end", None)
+    if rows_end is None:
+        raise RuntimeError("composite_rays_train_blend_mse: `rays` must be the tensor returned by laenerf_amd march_rays_train")
+    bg_rays, bg = _bg_args(bg_color, sigmas.device)
+    scale = None
+    if scaler is not None:
+        scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
+    if defer_loss is None:
+        defer_loss = scaler is not None and not torch.is_tensor(scaler) and hasattr(scaler, "finish_loss")
+    if depth is not None:
+        if not torch.is_tensor(depth) or depth.dtype not in (torch.float16, torch.float32):
+            raise RuntimeError("composite_rays_train_blend_mse: depth must be a float16 or float32 tensor")
+        if not (float(depth_weight) >= 0.0) or float(depth_weight) == float("inf"):
+            raise ValueError("composite_rays_train_blend_mse: depth_weight must be finite and >= 0")
+        loss, weights_sum, depth_o, image, both, depth_partials, grad_depth = _composite_rays_train_blend_mse_depth.apply(
+            sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, bool(defer_loss),
+            _DepthPlane(depth.contiguous()), None if depth_inds is None else depth_inds.contiguous(), float(depth_weight), not depth_grad)
+        loss.unscaled = both[1]
+        loss.depth_partials, loss.grad_depth, loss.depth_rays = depth_partials, grad_depth, rays.shape[0]
+        return loss, weights_sum, depth_o, image
     rows_end = getattr(rays, "rows_end", None)
     if rows_end is None:
         raise RuntimeError("composite_rays_train_blend_mse: `rays` must be the tensor returned by laenerf_amd march_rays_train")
@@ -544,3 +696,88 @@ def mark_untrained_grid(density_grid, poses, intrinsics, bound, min_near=0.2, fi
     _backend.mark_untrained_grid(poses, poses.shape[0], fx, fy, cx, cy, density_grid.shape[0], H, bound, min_near,
                                  filter_close_point, density_grid)
     return density_grid
+
+
+# ---------------------------------------------------------------- numpy restatement of the depth-supervised compositing
+def composite_depth_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=None, bg=None, grad_weights_sum=None, grad_image=None,
+                          grad_depth=None, target=None, z=None, nears=None, depth_weight=0.0, scale=1.0, depth_grad=True, n_rays=None,
+                          fars=None):
+    """The training compositing with the depth gradient, restated sample by sample in `dtype` (default float64): the forward
+    (k_composite_train_fwd: early stop after the first sample with T_post < T_thresh, that sample included; rays with
+    num_steps == 0 or offset + num_steps > M dropped), optionally the criterion of lae_composite_rays_train_step_depth
+    (target [N,3], z [N] already gathered, nears [N], optionally fars [N]: rays with nears >= fars, the sentinel interval of a ray
+    that misses the bounding box, are unsupervised; grad_image / grad_depth are then the criterion's) and the backward
+    (lae_composite_rays_train_backward_blend_depth; bg: None = no blend term, [3] or [N,3]).  Everything is indexed as the
+    kernels do: per-ray values by rays[n, 0]; n_rays: the length of the per-ray arrays when `rays` holds only some rows of a table.
+    -> dict weights_sum, depth (raw D), image [N,3], stop [N] (index of the last sample used, -1 for a ray without samples),
+    margin (the smallest |T_post / T_thresh - 1| over the samples used: how far the early stop is from flipping), and with
+    gradients grad_sigmas [M], grad_rgbs [M,3] (zero on rows no ray uses); with a criterion also image_out, res, grad_image,
+    grad_depth, mse, depth_mse, loss (= mse + depth_weight * depth_mse)."""
+    import numpy as np
+    dt = np.dtype(np.float64 if dtype is None else dtype).type
+    sig, col, dl = np.asarray(sigmas).astype(dt), np.asarray(rgbs).astype(dt).reshape(-1, 3), np.asarray(deltas).astype(dt).reshape(-1, 2)
+    rays = np.asarray(rays).astype(np.int64).reshape(-1, 3)
+    M, N = sig.shape[0], rays.shape[0] if n_rays is None else int(n_rays)
+    one, thr = dt(1), dt(T_thresh)
+    ws, D, img = np.zeros(N, dt), np.zeros(N, dt), np.zeros((N, 3), dt)
+    stop = np.full(N, -1, np.int64)
+    margin = np.inf
+    per_ray = {}
+    for n in range(rays.shape[0]):
+        index, offset, steps = (int(v) for v in rays[n])
+        if steps == 0 or offset + steps > M:
+            continue
+        T, t = one, dt(0)
+        w_l, t_l, tp_l = [], [], []
+        for k in range(steps):
+            i = offset + k
+            alpha = one - dt(np.exp(-sig[i] * dl[i, 0]))
+            w = alpha * T
+            t = t + dl[i, 1]
+            T = T * (one - alpha)
+            w_l.append(w); t_l.append(t); tp_l.append(T)
+            ws[index] = ws[index] + w
+            D[index] = D[index] + w * t
+            img[index] = img[index] + w * col[i]
+            margin = min(margin, abs(float(T) / float(thr) - 1.0))
+            stop[index] = k
+            if T < thr:
+                break
+        per_ray[n] = (np.array(w_l, dt), np.array(t_l, dt), np.array(tp_l, dt))
+    res = {"weights_sum": ws, "depth": D, "image": img, "stop": stop, "margin": margin}
+    bgv = None if bg is None else np.broadcast_to(np.asarray(bg).astype(dt).reshape(-1, 3), (N, 3))
+    if target is not None:
+        lam, sc = dt(depth_weight), dt(scale)
+        out = img + (one - ws)[:, None] * (bgv if bgv is not None else dt(0))
+        err = out - np.asarray(target).astype(dt).reshape(N, 3)
+        zz = np.asarray(z).astype(dt).reshape(N)
+        nr = np.asarray(nears).astype(dt).reshape(N)
+        sup = zz > 0 if fars is None else (zz > 0) & (nr < np.asarray(fars).astype(dt).reshape(N))
+        with np.errstate(over="ignore"):
+            r = np.where(sup, D - (zz - nr), dt(0))
+        grad_image = (err * (dt(2) / dt(3 * N))) * sc
+        grad_depth = (r * (dt(2) * lam / dt(N))) * sc if depth_grad else np.zeros(N, dt)
+        mse, dmse = (err * err).sum() / dt(3 * N), (r * r).sum() / dt(N)
+        res.update(image_out=out, res=r, grad_image=grad_image, grad_depth=grad_depth, mse=mse, depth_mse=dmse, loss=mse + lam * dmse)
+    if grad_image is None and grad_depth is None and grad_weights_sum is None:
+        return res
+    zero = np.zeros(N, dt)
+    g_img = np.zeros((N, 3), dt) if grad_image is None else np.asarray(grad_image).astype(dt).reshape(N, 3)
+    g_ws = zero if grad_weights_sum is None else np.asarray(grad_weights_sum).astype(dt).reshape(N)
+    g_D = zero if grad_depth is None else np.asarray(grad_depth).astype(dt).reshape(N)
+    gs, gc = np.zeros(M, dt), np.zeros((M, 3), dt)
+    for n, (w_l, t_l, tp_l) in per_ray.items():
+        index, offset, _ = (int(v) for v in rays[n])
+        g = g_img[index]
+        gws = g_ws[index] - (g * bgv[index]).sum() if bgv is not None else g_ws[index]
+        tail = gws * (one - ws[index])
+        c_run, d_run = np.zeros(3, dt), dt(0)
+        for k in range(len(w_l)):
+            i = offset + k
+            c_run = c_run + w_l[k] * col[i]
+            d_run = d_run + w_l[k] * t_l[k]
+            gc[i] = g * w_l[k]
+            br = (g * (tp_l[k] * col[i] - (img[index] - c_run))).sum() + tail
+            gs[i] = dl[i, 0] * (br + g_D[index] * (tp_l[k] * t_l[k] - (D[index] - d_run)))
+    res.update(grad_sigmas=gs, grad_rgbs=gc)
+    return res

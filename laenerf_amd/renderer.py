@@ -296,10 +296,15 @@ class NeRFRenderer(nn.Module):
             return xyzs, dirs, deltas, rays, nears, fars, self.model.plan_backward(xyzs)
         return xyzs, dirs, deltas, rays, nears, fars
 
-    def shade_train(self, marched, bg_color=1, T_thresh=1e-4, gt=None, scaler=None):
+    def shade_train(self, marched, bg_color=1, T_thresh=1e-4, gt=None, scaler=None, depth=None, depth_inds=None, depth_weight=0.0,
+                    depth_grad=True):
         """second half: network on the samples, compositing, background blend, depth normalisation (renderer.py:313-334).
         gt [N,3] (optional, MI355X-native): also evaluate the trainer's criterion MSE(image, gt) (scaled by `scaler`'s
-        loss scale) inside the compositing op -> result["loss"]; call loss.backward() on it."""
+        loss scale) inside the compositing op -> result["loss"]; call loss.backward() on it.
+        depth / depth_inds / depth_weight / depth_grad (with gt and fused_post_ops only): the depth criterion of
+        raymarching.composite_rays_train_blend_mse in the same kernel; depth=None leaves the call as it was."""
+        if depth is not None and not (self.fused_post_ops and gt is not None):
+            raise RuntimeError("shade_train: depth supervision needs gt and fused_post_ops (it lives in the fused criterion kernel)")
         xyzs, dirs, deltas, rays, nears, fars = marched[:6]
         plan = marched[6] if len(marched) > 6 else None
         sigmas, rgbs = self.model(xyzs, dirs, plan=plan) if plan is not None else self.model(xyzs, dirs)
@@ -307,8 +312,13 @@ class NeRFRenderer(nn.Module):
             sigmas = self.density_scale * sigmas
         loss = None
         if self.fused_post_ops and gt is not None:
-            loss, weights_sum, depth, image = raymarching.composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars,
-                                                                                        gt, bg_color, T_thresh, scaler)
+            if depth is None:
+                loss, weights_sum, depth, image = raymarching.composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars,
+                                                                                            gt, bg_color, T_thresh, scaler)
+            else:
+                loss, weights_sum, depth, image = raymarching.composite_rays_train_blend_mse(
+                    sigmas, rgbs, deltas, rays, nears, fars, gt, bg_color, T_thresh, scaler, depth=depth, depth_inds=depth_inds,
+                    depth_weight=depth_weight, depth_grad=depth_grad)
         elif self.fused_post_ops:    # composite + bg blend + depth normalisation in one kernel, gradients without zero fills
             weights_sum, depth, image = raymarching.composite_rays_train_blend(sigmas, rgbs, deltas, rays, nears, fars,
                                                                                bg_color, T_thresh)

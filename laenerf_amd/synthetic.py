@@ -149,3 +149,23 @@ def lookat_poses(n_views, radius=3.2, seed=0):
     poses = np.zeros((n_views, 4, 4), np.float32)
     poses[:, :3, 0], poses[:, :3, 1], poses[:, :3, 2], poses[:, :3, 3], poses[:, 3, 3] = right, down, fwd, cam, 1.0
     return poses
+
+
+def sphere_depth_planes(poses, intrinsics, H, W, radius=0.6):
+    """[n, H, W] float32: the distance along each pixel's ray (get_rays' convention: pixel centre = index + 0.5, unit directions)
+    from the camera to a sphere of `radius` around the origin; 0 where the ray misses it -- an analytic depth plane for
+    ResidentImages(depths=...)"""
+    poses = np.asarray(poses, np.float64)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    j, i = np.meshgrid(np.arange(H) + 0.5, np.arange(W) + 0.5, indexing="ij")
+    d_cam = np.stack([(i - cx) / fx, (j - cy) / fy, np.ones_like(i)], -1)
+    d_cam /= np.linalg.norm(d_cam, axis=-1, keepdims=True)
+    out = np.zeros((poses.shape[0], H, W), np.float32)
+    for n, P in enumerate(poses):
+        d = d_cam @ P[:3, :3].T
+        o = P[:3, 3]
+        b = d @ o
+        disc = b * b - (o @ o - radius * radius)
+        t = -b - np.sqrt(np.maximum(disc, 0.0))
+        out[n] = np.where((disc > 0) & (t > 0), t, 0.0).astype(np.float32)
+    return out

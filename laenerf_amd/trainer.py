@@ -23,6 +23,13 @@ never updated; the reference has no such mode.  LAENeRF's --use_error_maps seeds
 (nerf/gui.py:419-425) and hands it to the trainer, whose train_step then updates it: that is 'ema' on a seeded map
 (laenerf_amd.editing.distill).  Both kernels read and write only device memory, so they run inside the captured group like
 the rest of the step.
+
+depth_weight (with a depth plane on the data, ResidentImages.depths) adds the reference's depth supervision
+`depth_weight * mean(((depth - (gt_depth - nears)) * (gt_depth > 0))^2)` (nerf/utils.py:585-589, 634-635; 1e-3 during the
+distillation) to the step's loss inside the fused compositing kernel, which gathers the plane by the batch's pixel indices: the same
+captured 16-step groups, every pointer constant, nothing new on the host inside a group.  depth_grad=True carries the term's gradient
+to the densities; the reference's compositing backward drops it (raymarching/raymarching.py:273-275), so there the term changes the
+logged loss and nothing else -- depth_grad=False restates that, with parameters bit-equal to a run without depth.
 """
 import contextlib
 import math
@@ -95,11 +102,15 @@ class Trainer:
     after every step whose 1-based global index is a multiple of epoch_len (default data.n_img: the reference's epoch of one
     image per batch, nerf/utils.py:1502-1503) by one gated launch inside the captured group; evaluate_one_epoch / test render
     with it swapped in.
+    depth_weight: None (no depth term; the step is the one without this argument, bit for bit) or the weight of the depth term, which
+    needs data.depths; depth_grad: whether its gradient reaches the densities (False: the reference's value-only behaviour).
+    With it losses() holds the total, MSE + depth_weight * depth term, and depth_losses() the per-step depth term without its
+    weight: one lae_loss_finish node per step, off the gradient path.
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
     def __init__(self, renderer, optimizer, data, iters, lr, num_rays=4096, seed=0, graph=True, capacity="bucket",
-                 max_steps=1024, dt_gamma=0.0, error_map=None, ema_decay=None, epoch_len=None):
+                 max_steps=1024, dt_gamma=0.0, error_map=None, ema_decay=None, epoch_len=None, depth_weight=None, depth_grad=True):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
         if error_map not in (None, "ema", "fixed"):
@@ -110,6 +121,15 @@ class Trainer:
         self.iters, self.num_rays, self.graph, self.capacity = int(iters), int(num_rays), bool(graph), capacity
         self.max_steps, self.dt_gamma = int(max_steps), float(dt_gamma)
         self.error_map = error_map
+        if depth_weight is not None:
+            if getattr(data, "depths", None) is None:
+                raise ValueError("Trainer: depth_weight needs a depth plane on the data (ResidentImages(depths=...) / set_depths)")
+            if not (float(depth_weight) >= 0.0) or float(depth_weight) == float("inf"):
+                raise ValueError("Trainer: depth_weight must be finite and >= 0")
+            if not renderer.fused_post_ops:
+                raise ValueError("Trainer: depth supervision needs the renderer's fused_post_ops")
+        self.depth_weight = None if depth_weight is None else float(depth_weight)
+        self.depth_grad = bool(depth_grad)
         dev = renderer.density_grid.device
         data.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         data.aabb = renderer.aabb_train.to(dev, torch.float32).contiguous()      # the batch's near / far = the march's
@@ -119,6 +139,8 @@ class Trainer:
         self.lr_table = torch.from_numpy(lr_schedule(lr, self.iters, self.iters + 1, n_groups)).to(dev)
         self.m_limit = torch.zeros(1, dtype=torch.int32, device=dev)
         self.loss_slots = torch.zeros(GROUP, dtype=torch.float32, device=dev)
+        self.depth_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.depth_weight is not None else None
+        self._depth_hist = []
         self.global_step = 0
         self.started = False
         self.graphs = {}
@@ -160,10 +182,17 @@ class Trainer:
                     perturb=True, dt_gamma=self.dt_gamma, max_steps=self.max_steps, m_limit=self.m_limit, capacity=m_cap)
             if not torch.cuda.is_current_stream_capturing():
                 self._rows_seen = max(self._rows_seen, xyzs.shape[0])
-            res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt)
+            if self.depth_weight is None:
+                res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt)
+            else:
+                res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt,
+                                    depth=self.data.depths, depth_inds=b["inds"], depth_weight=self.depth_weight,
+                                    depth_grad=self.depth_grad)
         if self.error_map == "ema":
             self.data.update_error_map(res["image"], b)
         loss = res["loss"]
+        if self.depth_weight is not None:
+            raymarching.finish_depth_loss(loss, out=self.depth_slots[k])
         opt.backward(loss)
         opt.step()
         if self.ema is not None:
@@ -221,16 +250,26 @@ class Trainer:
                 self._step(pos, self._m_cap() if r.mean_count > 0 else None)
                 n = 1
             self._loss_hist.append(self.loss_slots[pos:pos + n].clone())
+            if self.depth_slots is not None:
+                self._depth_hist.append(self.depth_slots[pos:pos + n, 1].clone())
             done += n
             self.global_step += n
         return self
 
     # ------------------------------------------------------------------ results
     def losses(self):
-        """per-step losses (the unscaled MSE of every step so far) as a float32 numpy array"""
+        """per-step losses (the unscaled loss of every step so far: the MSE, plus depth_weight * the depth term with depth
+        supervision) as a float32 numpy array"""
         if not self._loss_hist:
             return np.zeros(0, np.float32)
         return torch.cat(self._loss_hist).cpu().numpy()
+
+    def depth_losses(self):
+        """per-step depth term mean(((depth - (gt_depth - nears)) * (gt_depth > 0))^2), without its weight, as a float32 numpy
+        array (empty without depth supervision).  Each step finishes it with one lae_loss_finish node off the gradient path."""
+        if not self._depth_hist:
+            return np.zeros(0, np.float32)
+        return torch.cat(self._depth_hist).cpu().numpy()
 
     @property
     def steps_skipped(self):

@@ -5,10 +5,13 @@ RGBA views from cameras on a sphere: colour = image over a black background / we
 weights_sum; 8-bit like a real dataset.  A fresh student trains on them with the reference's loop (random background,
 refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated on held-out views over white.
 
-    python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed] [--ema]
+    python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed] [--ema] [--depth]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
-ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR."""
+ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR.
+--depth: a second, identically seeded student trains with depth supervision (Trainer(depth_weight=...)) on the teacher's own depth
+(its rendered ray-origin distance where the view is opaque, zero elsewhere); the line then carries ms/step with and without the
+term ("depth": {...}) and the replay time of five windows for each."""
 import argparse
 import json
 import os
@@ -23,12 +26,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 HEADLINE_MS = 0.353           # README.md: bench.py's train step (fixed resident batches, no grid refresh)
 
 
-def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
-    """-> images [n, H, W, 4] uint8 (straight colour + alpha), poses [n, 4, 4] float32, intrinsics (fx, fy, cx, cy)"""
+def _teacher(dev, bound, opacity):
     from laenerf_amd import synthetic as S
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.renderer import NeRFRenderer
-    from laenerf_amd.rays import get_rays
     g = torch.random.fork_rng(devices=[dev])
     with g:
         torch.manual_seed(11)
@@ -37,6 +38,31 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
         net.sigma_net.weights.data.mul_(opacity)
     r = NeRFRenderer(net, bound=bound, density_thresh=10).to(dev).eval()
     r.density_bitfield = torch.from_numpy(S.pack_bits_np(S.sphere_density_grid(cascade=r.cascade, bound=float(bound)), 10.0)).to(dev)
+    return r
+
+
+def teacher_depths(dev, poses, intr, H, W, bound=1, opacity=1.5, min_alpha=0.5):
+    """-> [n, H, W] float32: the teacher's composited depth (distance from the ray origin) of teacher_views' views where the view is
+    opaque enough (weights_sum > min_alpha), zero (= no supervision) elsewhere"""
+    from laenerf_amd.rays import get_rays
+    r = _teacher(dev, bound, opacity)
+    out = []
+    with torch.no_grad():
+        for i in range(len(poses)):
+            ray = get_rays(torch.from_numpy(poses[i:i + 1]).to(dev), intr, H, W)
+            with torch.autocast("cuda", dtype=torch.float16):
+                res = r.render_eval(ray["rays_o"][0], ray["rays_d"][0], bg_color=0, max_steps=1024, perturb=False, scale_depth=False)
+            ws = res["weights_sum"].float()
+            d = torch.where(ws > min_alpha, res["depth"].float() / ws.clamp(min=1e-6), torch.zeros_like(ws))
+            out.append(d.reshape(H, W).cpu().numpy())
+    return np.stack(out).astype(np.float32)
+
+
+def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
+    """-> images [n, H, W, 4] uint8 (straight colour + alpha), poses [n, 4, 4] float32, intrinsics (fx, fy, cx, cy)"""
+    from laenerf_amd import synthetic as S
+    from laenerf_amd.rays import get_rays
+    r = _teacher(dev, bound, opacity)
     poses = S.lookat_poses(n_views, radius=radius, seed=seed)
     focal = 0.5 * W / np.tan(0.5 * 0.69)                                  # camera_angle_x of the blender scenes
     intr = (focal, focal, W / 2, H / 2)
@@ -54,7 +80,7 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
 
 
 def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=True, capacity="bucket", seed=0, student_seed=0,
-                 error_map=None, ema_decay=None):
+                 error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True):
     from laenerf_amd.data import ResidentImages
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.optim import FusedAdam
@@ -64,9 +90,38 @@ def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=Tr
     net = NeRFNetwork(bound=1).to(dev)
     r = NeRFRenderer(net, bound=1, density_thresh=10).to(dev)
     opt = FusedAdam(net, param_groups=net.get_params(lr), betas=(0.9, 0.99), eps=1e-15, device_lr=True)
-    data = ResidentImages.from_arrays(images, poses, intr, bg="random", device=dev)
+    data = ResidentImages.from_arrays(images, poses, intr, bg="random", device=dev, depths=depths)
+    depth_kw = {} if depth_weight is None else {"depth_weight": depth_weight, "depth_grad": depth_grad}
     return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map,
-                   ema_decay=ema_decay)
+                   ema_decay=ema_decay, **depth_kw)
+
+
+def _replay_windows(tr, n=5):
+    """after a run: n windows of (refresh ms, ms per step of a 16-step replay at the current capacity)"""
+    refresh_ms, group_ms = [], []
+    if tr.graph and tr.r.mean_count > 0:
+        for _ in range(n):
+            torch.cuda.synchronize(); a = time.perf_counter()
+            tr._refresh()
+            torch.cuda.synchronize(); b = time.perf_counter()
+            tr.m_limit.fill_(tr._m())
+            tr._run_group(tr._m_cap())
+            torch.cuda.synchronize(); c = time.perf_counter()
+            tr.global_step += 16
+            refresh_ms.append((b - a) * 1e3); group_ms.append((c - b) * 1e3 / 16)
+    return refresh_ms, group_ms
+
+
+def _timed_run(tr, steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tr.train(64)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    tr.train(steps - 64)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    return (t2 - t0) * 1e3 / steps, (t2 - t1) * 1e3 / (steps - 64)
 
 
 def main():
@@ -79,6 +134,9 @@ def main():
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--error-map", default="none", choices=["none", "ema", "fixed"])
     ap.add_argument("--ema", action="store_true", help="Trainer(ema_decay=0.95): the gated EMA update in every step")
+    ap.add_argument("--depth", action="store_true", help="also train a second student with depth supervision on the teacher's depth")
+    ap.add_argument("--depth-weight", type=float, default=1e-3)
+    ap.add_argument("--depth-value-only", action="store_true", help="depth_grad=False: the reference's value-only depth term")
     args = ap.parse_args()
     error_map = None if args.error_map == "none" else args.error_map
     dev = torch.device("cuda:0")
@@ -88,32 +146,27 @@ def main():
     held = 4
     tr = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
                       capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    tr.train(64)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    tr.train(args.steps - 64)
-    torch.cuda.synchronize()
-    t2 = time.perf_counter()
+    all_in, steady = _timed_run(tr, args.steps)
     from laenerf_amd.data import ResidentImages
     test = ResidentImages.from_arrays(images[:held], poses[:held], intr, device=dev)
     p = tr.evaluate(range(held), data=test, bg_color=1.0)
     # where the time goes (after the measurement; each part synchronised on its own): the refresh with its host read, a
     # 16-step replay at the current capacity, and the padding rows of that capacity
-    refresh_ms, group_ms = [], []
-    if tr.graph and tr.r.mean_count > 0:
-        for _ in range(5):
-            torch.cuda.synchronize(); a = time.perf_counter()
-            tr._refresh()
-            torch.cuda.synchronize(); b = time.perf_counter()
-            tr.m_limit.fill_(tr._m())
-            tr._run_group(tr._m_cap())
-            torch.cuda.synchronize(); c = time.perf_counter()
-            tr.global_step += 16
-            refresh_ms.append((b - a) * 1e3); group_ms.append((c - b) * 1e3 / 16)
-    all_in = (t2 - t0) * 1e3 / args.steps
-    steady = (t2 - t1) * 1e3 / (args.steps - 64)
+    refresh_ms, group_ms = _replay_windows(tr)
+    depth = None
+    if args.depth:
+        planes = teacher_depths(dev, poses[held:], intr, args.res, args.res)
+        td = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
+                          capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, depths=planes,
+                          depth_weight=args.depth_weight, depth_grad=not args.depth_value_only)
+        d_all_in, d_steady = _timed_run(td, args.steps)
+        d_psnr = td.evaluate(range(held), data=test, bg_color=1.0)
+        _, d_group_ms = _replay_windows(td)
+        depth = {"ms_per_step_all_in": round(d_all_in, 4), "ms_per_step_after_64": round(d_steady, 4), "depth_weight": args.depth_weight,
+                 "depth_grad": not args.depth_value_only, "supervised_pixels_frac": round(float((planes > 0).mean()), 4),
+                 "replay_ms_per_step_windows": [round(v, 4) for v in d_group_ms], "mean_count": td.r.mean_count,
+                 "first_depth_loss": float(td.depth_losses()[:16].mean()), "final_depth_loss": float(td.depth_losses()[-16:].mean()),
+                 "final_loss": float(td.losses()[-16:].mean()), "heldout_psnr_white": round(d_psnr, 3), "steps_skipped": td.steps_skipped}
     print(json.dumps({
         "ms_per_step_all_in": round(all_in, 4), "ms_per_step_after_64": round(steady, 4), "steps": args.steps, "rays": args.rays,
         "ratio_to_headline": round(all_in / HEADLINE_MS, 3), "ratio_after_64_to_headline": round(steady / HEADLINE_MS, 3),
@@ -125,7 +178,9 @@ def main():
         "final_loss": float(tr.losses()[-16:].mean()),
         "breakdown": {"refresh_ms": round(float(np.median(refresh_ms)), 4) if refresh_ms else None,
                       "replay_ms_per_step": round(float(np.median(group_ms)), 4) if group_ms else None,
+                      "replay_ms_per_step_windows": [round(v, 4) for v in group_ms],
                       "padding_rows_frac": round(1 - tr._m() / tr._m_cap(), 4) if tr.r.mean_count > 0 else None},
+        **({"depth": depth} if depth is not None else {}),
         "scene": f"{args.views - held} training + {held} held-out {args.res}x{args.res} RGBA uint8 views of a teacher network"}), flush=True)
 
 
