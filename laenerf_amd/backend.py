@@ -117,6 +117,18 @@ def retarget_pending_loss(old_grad_sigmas, new_grad_sigmas):
 _DEPTH_DTYPES = {torch.float16: 1, torch.float32: 2}        # include/laenerf.h LAE_IMG_F16 / LAE_IMG_F32
 
 
+def _backward_blend_args(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, bg_rays, bg,
+                         rows_end, grad_sigmas, grad_rgbs, grad_scale, *depth_pair):
+    """checks the tensors of a DENSE backward (depth_pair: grad_depth and depth of the DEPTH flavour) -> the arguments both
+    library entries share"""
+    fs = (grad_weights_sum, grad_image, sigmas, rgbs, deltas, weights_sum, image, bg_rays, grad_sigmas, grad_rgbs, grad_scale) + depth_pair
+    need_cuda(*fs, rays, rows_end); need_contig(*fs, rays, rows_end)
+    _need_f32(*fs)
+    return (ptr(grad_weights_sum), ptr(grad_image), ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(weights_sum),
+            ptr(image), M, N, T_thresh, ptr(bg_rays), bg[0], bg[1], bg[2], ptr(rows_end), ptr(grad_scale), ptr(grad_sigmas),
+            ptr(grad_rgbs))
+
+
 class _RayMarching:
     @staticmethod
     def near_far_from_aabb(rays_o, rays_d, aabb, N, min_near, nears, fars):
@@ -254,12 +266,11 @@ class _RayMarching:
                   grad_image, grad_sigmas, grad_rgbs, loss_out, partials)
         if partials.numel() < (N + 3) // 4:
             raise RuntimeError("composite_rays_train_step: partials needs cdiv(N, 4) floats")
-        if depth_sup is None:
-            check(_lib.load().lae_composite_rays_train_step(
-                ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1], bg[2],
+        args = (ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1], bg[2],
                 ptr(rows_end), ptr(target), ptr(scale), ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out),
-                ptr(grad_image), ptr(grad_sigmas), ptr(grad_rgbs), ptr(loss_out), ptr(partials), int(bool(defer_loss)), stream()),
-                "composite_rays_train_step")
+                ptr(grad_image), ptr(grad_sigmas), ptr(grad_rgbs), ptr(loss_out), ptr(partials), int(bool(defer_loss)))
+        if depth_sup is None:
+            check(_lib.load().lae_composite_rays_train_step(*args, stream()), "composite_rays_train_step")
         else:
             depth_src, depth_inds, weight, value_only, grad_depth, depth_partials = depth_sup
             ds = (depth_src, depth_inds, grad_depth, depth_partials)
@@ -273,11 +284,8 @@ class _RayMarching:
             if grad_depth.numel() < N or depth_partials.numel() < (N + 3) // 4:
                 raise RuntimeError("composite_rays_train_step: grad_depth needs N, depth_partials cdiv(N, 4) floats")
             check(_lib.load().lae_composite_rays_train_step_depth(
-                ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1], bg[2],
-                ptr(rows_end), ptr(target), ptr(scale), ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out),
-                ptr(grad_image), ptr(grad_sigmas), ptr(grad_rgbs), ptr(loss_out), ptr(partials), int(bool(defer_loss)),
-                ptr(depth_src), _DEPTH_DTYPES[depth_src.dtype], ptr(depth_inds), float(weight), int(bool(value_only)), ptr(grad_depth),
-                ptr(depth_partials), stream()), "composite_rays_train_step_depth")
+                *args, ptr(depth_src), _DEPTH_DTYPES[depth_src.dtype], ptr(depth_inds), float(weight), int(bool(value_only)),
+                ptr(grad_depth), ptr(depth_partials), stream()), "composite_rays_train_step_depth")
         if defer_loss and N > 0:                      # N == 0: the library returned at once, there is nothing to finish
             capturing = torch.cuda.is_current_stream_capturing()
             key = _loss_key(grad_sigmas)
@@ -299,31 +307,21 @@ class _RayMarching:
     def composite_rays_train_backward_blend(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M,
                                             N, T_thresh, bg_rays, bg, rows_end, grad_sigmas, grad_rgbs, grad_scale=None):
         """grad_scale (MI355X extension): device scalar multiplied into the incoming gradients; grad_weights_sum may be None"""
-        ts = (grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, bg_rays, rows_end, grad_sigmas,
-              grad_rgbs, grad_scale)
-        need_cuda(*ts); need_contig(*ts)
-        _need_f32(grad_weights_sum, grad_image, sigmas, rgbs, deltas, weights_sum, image, bg_rays, grad_sigmas, grad_rgbs, grad_scale)
-        check(_lib.load().lae_composite_rays_train_backward_blend_ex(
-            ptr(grad_weights_sum), ptr(grad_image), ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(weights_sum),
-            ptr(image), M, N, T_thresh, ptr(bg_rays), bg[0], bg[1], bg[2], ptr(rows_end), ptr(grad_scale), ptr(grad_sigmas),
-            ptr(grad_rgbs), stream()), "composite_rays_train_backward_blend")
+        args = _backward_blend_args(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, bg_rays,
+                                    bg, rows_end, grad_sigmas, grad_rgbs, grad_scale)
+        check(_lib.load().lae_composite_rays_train_backward_blend_ex(*args, stream()), "composite_rays_train_backward_blend")
 
     @staticmethod
     def composite_rays_train_backward_blend_depth(grad_weights_sum, grad_image, grad_depth, sigmas, rgbs, deltas, rays, weights_sum,
                                                   depth, image, M, N, T_thresh, bg_rays, bg, rows_end, grad_sigmas, grad_rgbs,
                                                   grad_scale=None):
         """composite_rays_train_backward_blend that also carries grad_depth [N], the gradient of the forward's RAW depth [N]"""
-        ts = (grad_weights_sum, grad_image, grad_depth, sigmas, rgbs, deltas, rays, weights_sum, depth, image, bg_rays, rows_end,
-              grad_sigmas, grad_rgbs, grad_scale)
-        need_cuda(*ts); need_contig(*ts)
-        _need_f32(grad_weights_sum, grad_image, grad_depth, sigmas, rgbs, deltas, weights_sum, depth, image, bg_rays, grad_sigmas,
-                  grad_rgbs, grad_scale)
+        args = _backward_blend_args(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, bg_rays,
+                                    bg, rows_end, grad_sigmas, grad_rgbs, grad_scale, grad_depth, depth)
         if grad_depth is None or depth is None or grad_depth.numel() < N or depth.numel() < N:
             raise RuntimeError("composite_rays_train_backward_blend_depth: grad_depth and depth need a value per ray")
-        check(_lib.load().lae_composite_rays_train_backward_blend_depth(
-            ptr(grad_weights_sum), ptr(grad_image), ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(weights_sum),
-            ptr(image), M, N, T_thresh, ptr(bg_rays), bg[0], bg[1], bg[2], ptr(rows_end), ptr(grad_scale), ptr(grad_sigmas),
-            ptr(grad_rgbs), ptr(grad_depth), ptr(depth), stream()), "composite_rays_train_backward_blend_depth")
+        check(_lib.load().lae_composite_rays_train_backward_blend_depth(*args, ptr(grad_depth), ptr(depth), stream()),
+              "composite_rays_train_backward_blend_depth")
 
     @staticmethod
     def loss_finish(partials, n_part, n_elem, scale, loss_out):

@@ -349,59 +349,6 @@ constexpr int COMP_BLOCK = 64 * COMP_WAVES;
 // `image` keeps the un-blended colour the backward needs.
 struct Blend { const float* nears; const float* fars; const float* bg_rays; float bg[3]; float* image_out; float* depth_out; };
 
-template <bool BLEND>
-__global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_fwd(
-    const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
-    const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum,
-    float* __restrict__ depth, float* __restrict__ image, Blend bl) {
-    const uint32_t n = blockIdx.x * COMP_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // one ray per wave: scalar
-    if (n >= N) return;
-    const int lane = threadIdx.x & 63;
-    const uint32_t index = (uint32_t)rays[3 * (size_t)n], offset = (uint32_t)rays[3 * (size_t)n + 1];
-    const uint32_t num_steps = (uint32_t)rays[3 * (size_t)n + 2];
-    float r = 0, g = 0, b = 0, ws = 0, d = 0;
-    if (!(num_steps == 0 || offset + num_steps > M)) {                      // :521
-        float T = 1.0f, t = 0.0f;
-        for (uint32_t base = 0; base < num_steps; base += 64) {
-            const uint32_t k = base + lane;
-            bool valid = k < num_steps;
-            float alpha = 0.f, d1 = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
-            if (valid) {
-                const size_t i = (size_t)offset + k;
-                alpha = 1.0f - __expf(-sigmas[i] * deltas[2 * i]);
-                d1 = deltas[2 * i + 1];
-                c0 = rgbs[3 * i]; c1 = rgbs[3 * i + 1]; c2 = rgbs[3 * i + 2];
-            }
-            const float incl = wave_scan_mul(1.0f - alpha, lane);           // prod_{j<=k} within the pass
-            const float excl = wave_prev(incl, 1.0f);
-            const float T_post = T * incl;
-            const unsigned long long stop = __ballot(valid && T_post < T_thresh);   // :557 (sample included)
-            bool done = false;
-            if (stop) { const int last = __builtin_ctzll(stop); valid = valid && lane <= last; done = true; }
-            const float w = valid ? alpha * (T * excl) : 0.0f;
-            const float tk = t + wave_scan_add(d1, lane);
-            r += wave_sum(w * c0); g += wave_sum(w * c1); b += wave_sum(w * c2);
-            d += wave_sum(w * tk); ws += wave_sum(w);
-            if (done) break;
-            T *= wave_last(incl);
-            t = wave_last(tk);
-        }
-    }
-    if (lane == 0) {
-        weights_sum[index] = ws; depth[index] = d;
-        image[3 * (size_t)index] = r; image[3 * (size_t)index + 1] = g; image[3 * (size_t)index + 2] = b;
-        if constexpr (BLEND) {
-            const float* bg = bl.bg_rays ? bl.bg_rays + 3 * (size_t)index : bl.bg;
-            const float rest = 1.0f - ws;
-            bl.image_out[3 * (size_t)index] = r + rest * bg[0];
-            bl.image_out[3 * (size_t)index + 1] = g + rest * bg[1];
-            bl.image_out[3 * (size_t)index + 2] = b + rest * bg[2];
-            const float nr = bl.nears[index];
-            bl.depth_out[index] = fmaxf(d - nr, 0.0f) / (bl.fars[index] - nr);
-        }
-    }
-}
-
 // DENSE: (a) the gradient of the BLEND epilogue is folded in: grad_ws_eff = grad_ws - sum_c grad_image_c * bg_c;
 // (b) EVERY row of grad_sigmas / grad_rgbs in [0, M) is written (zeros for samples after the early stop and for the
 // rows [rows_end, M) no ray owns), so the caller allocates them uninitialised.  Needs the contiguous ray-id-order
@@ -423,6 +370,154 @@ template <bool DEPTH> struct DepthState { float gD = 0.0f, df = 0.0f, t = 0.0f, 
 template <> struct DepthState<false> {};
 struct NoArg {};                                          // the trailing kernel argument of the flavours without DEPTH
 
+// ---- the pieces every training compositing kernel is made of.  The kernels keep their loops and decide when a pass is loaded (the
+// step kernel requests the next pass before it scans the current one); the per-pass arithmetic exists once, here.
+
+// row n of `rays`; `has` is false for a ray that is dropped: no samples, or samples that do not fit into M (:521 / :624)
+struct RayHead { uint32_t index, offset, num_steps; bool has; };
+__device__ __forceinline__ RayHead load_ray_head(const int32_t* __restrict__ rays, uint32_t n, uint32_t M) {
+    RayHead h;
+    h.index = (uint32_t)rays[3 * (size_t)n]; h.offset = (uint32_t)rays[3 * (size_t)n + 1]; h.num_steps = (uint32_t)rays[3 * (size_t)n + 2];
+    h.has = !(h.num_steps == 0 || h.offset + h.num_steps > M);
+    return h;
+}
+__device__ __forceinline__ const float* ray_bg(const float* bg_rays, const float* bg, uint32_t index) {
+    return bg_rays ? bg_rays + 3 * (size_t)index : bg;
+}
+
+// operands of sample k of a ray (one lane of a pass of 64): all zero past the ray's end; d1 is read only where t_k is wanted
+struct Sample { float sg, d0, d1, c0, c1, c2; };
+__device__ __forceinline__ Sample load_sample(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                              const float* __restrict__ deltas, const RayHead& h, uint32_t k, bool with_t) {
+    Sample s{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (k < h.num_steps) {
+        const size_t i = (size_t)h.offset + k;
+        s.sg = sigmas[i]; s.d0 = deltas[2 * i];
+        if (with_t) s.d1 = deltas[2 * i + 1];
+        s.c0 = rgbs[3 * i]; s.c1 = rgbs[3 * i + 1]; s.c2 = rgbs[3 * i + 2];
+    }
+    return s;
+}
+
+// alpha, the transmittance scan and the early stop of one pass, common to forward and backward.  T: transmittance before the pass.
+// `valid` comes in as "inside the ray" and leaves as "inside the ray and not after the stop"; w is zero elsewhere.
+struct PassW { float w, T_post, incl; bool done; };
+__device__ __forceinline__ PassW pass_weights(const Sample& s, bool& valid, float T, float T_thresh, int lane) {
+    const float alpha = valid ? 1.0f - __expf(-s.sg * s.d0) : 0.0f;
+    PassW p;
+    p.incl = wave_scan_mul(1.0f - alpha, lane);                             // prod_{j<=k} within the pass
+    const float excl = wave_prev(p.incl, 1.0f);
+    p.T_post = T * p.incl;
+    const unsigned long long stop = __ballot(valid && p.T_post < T_thresh); // :557 (sample included)
+    p.done = false;
+    if (stop) { const int last = __builtin_ctzll(stop); valid = valid && lane <= last; p.done = true; }
+    p.w = valid ? alpha * (T * excl) : 0.0f;
+    return p;
+}
+
+// one forward pass: adds the pass to the ray's sums, carries T and t; -> the ray stopped in this pass
+struct FwdAcc { float r, g, b, d, ws; };
+__device__ __forceinline__ bool composite_fwd_pass(const Sample& s, bool valid, float T_thresh, int lane, float& T, float& t, FwdAcc& a) {
+    const PassW p = pass_weights(s, valid, T, T_thresh, lane);
+    const float tk = t + wave_scan_add(s.d1, lane);
+    a.r += wave_sum(p.w * s.c0); a.g += wave_sum(p.w * s.c1); a.b += wave_sum(p.w * s.c2);
+    a.d += wave_sum(p.w * tk); a.ws += wave_sum(p.w);
+    if (p.done) return true;
+    T *= wave_last(p.incl);
+    t = wave_last(tk);
+    return false;
+}
+
+// lane 0 of a forward wave: the ray's sums, the blended colour o, the BLEND outputs
+__device__ __forceinline__ void store_ray(float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image,
+                                          uint32_t index, const FwdAcc& a) {
+    weights_sum[index] = a.ws; depth[index] = a.d;
+    image[3 * (size_t)index] = a.r; image[3 * (size_t)index + 1] = a.g; image[3 * (size_t)index + 2] = a.b;
+}
+__device__ __forceinline__ void blend_colour(const float* bg, const FwdAcc& a, float o[3]) {
+    const float rest = 1.0f - a.ws;
+    o[0] = a.r + rest * bg[0]; o[1] = a.g + rest * bg[1]; o[2] = a.b + rest * bg[2];
+}
+__device__ __forceinline__ void store_blend(const Blend& bl, uint32_t index, const float o[3], float d) {
+    bl.image_out[3 * (size_t)index] = o[0]; bl.image_out[3 * (size_t)index + 1] = o[1]; bl.image_out[3 * (size_t)index + 2] = o[2];
+    const float nr = bl.nears[index];
+    bl.depth_out[index] = fmaxf(d - nr, 0.0f) / (bl.fars[index] - nr);
+}
+
+// what the backward of a ray holds fixed over its passes (the colour gradient, the ray's colour, the weights_sum term of the
+// bracket) and what it carries from pass to pass
+struct BwdRay { float g0, g1, g2, rf, gf, bf, tail; };
+struct BwdRun { float T = 1.0f, r = 0.0f, g = 0.0f, b = 0.0f; };
+__device__ __forceinline__ void zero_grad_row(float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, size_t i) {
+    grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f; grad_sigmas[i] = 0.f;
+}
+
+// one backward pass: writes the gradient rows of the pass (row i in this lane), carries T and the running sums; -> the ray stopped
+// in this pass.  With DEPTH and ds.on, s.d1 must be loaded.
+template <bool DENSE, bool DEPTH>
+__device__ __forceinline__ bool composite_bwd_pass(const Sample& s, bool valid, size_t i, const BwdRay& c, float T_thresh, int lane,
+                                                   BwdRun& st, DepthState<DEPTH>& ds, float* __restrict__ grad_sigmas,
+                                                   float* __restrict__ grad_rgbs) {
+    const bool in_ray = valid;
+    const PassW p = pass_weights(s, valid, st.T, T_thresh, lane);
+    const float rk = st.r + wave_scan_add(p.w * s.c0, lane);                // running sums INCLUDING this sample
+    const float gk = st.g + wave_scan_add(p.w * s.c1, lane);
+    const float bk = st.b + wave_scan_add(p.w * s.c2, lane);
+    [[maybe_unused]] float tk = 0.0f, dk = 0.0f;
+    if constexpr (DEPTH) {
+        if (ds.on) {
+            tk = ds.t + wave_scan_add(s.d1, lane);                          // t_k, as the forward
+            dk = ds.dsum + wave_scan_add(p.w * tk, lane);                   // D_k, including this sample
+        }
+    }
+    if (valid) {
+        grad_rgbs[3 * i] = c.g0 * p.w; grad_rgbs[3 * i + 1] = c.g1 * p.w; grad_rgbs[3 * i + 2] = c.g2 * p.w;      // :657-659
+        float br = c.g0 * (p.T_post * s.c0 - (c.rf - rk)) + c.g1 * (p.T_post * s.c1 - (c.gf - gk)) +
+                   c.g2 * (p.T_post * s.c2 - (c.bf - bk)) + c.tail;                                               // :662-667
+        if constexpr (DEPTH) {
+            if (ds.on) br = br + ds.gD * (p.T_post * tk - (ds.df - dk));
+        }
+        grad_sigmas[i] = s.d0 * br;
+    } else if (DENSE && in_ray) {
+        zero_grad_row(grad_sigmas, grad_rgbs, i);
+    }
+    if (p.done) return true;
+    st.T *= wave_last(p.incl);
+    st.r = wave_last(rk); st.g = wave_last(gk); st.b = wave_last(bk);
+    if constexpr (DEPTH) {
+        if (ds.on) { ds.t = wave_last(tk); ds.dsum = wave_last(dk); }
+    }
+    return false;
+}
+
+template <bool BLEND>
+__global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_fwd(
+    const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
+    const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum,
+    float* __restrict__ depth, float* __restrict__ image, Blend bl) {
+    const uint32_t n = blockIdx.x * COMP_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // one ray per wave: scalar
+    if (n >= N) return;
+    const int lane = threadIdx.x & 63;
+    const RayHead h = load_ray_head(rays, n, M);
+    FwdAcc a{0.f, 0.f, 0.f, 0.f, 0.f};
+    if (h.has) {
+        float T = 1.0f, t = 0.0f;
+        for (uint32_t base = 0; base < h.num_steps; base += 64) {
+            const uint32_t k = base + lane;
+            const Sample s = load_sample(sigmas, rgbs, deltas, h, k, true);
+            if (composite_fwd_pass(s, k < h.num_steps, T_thresh, lane, T, t, a)) break;
+        }
+    }
+    if (lane == 0) {
+        store_ray(weights_sum, depth, image, h.index, a);
+        if constexpr (BLEND) {
+            float o[3];
+            blend_colour(ray_bg(bl.bg_rays, bl.bg, h.index), a, o);
+            store_blend(bl, h.index, o, a.d);
+        }
+    }
+}
+
 template <bool DENSE, bool DEPTH = false>
 __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
     const float* __restrict__ grad_ws, const float* __restrict__ grad_image, const float* __restrict__ sigmas,
@@ -437,9 +532,9 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
         zero_tail_rows(rows_end, M, n, N, lane, grad_sigmas, 1);
         zero_tail_rows(rows_end, M, n, N, lane, grad_rgbs, 3);
     }
-    const uint32_t index = (uint32_t)rays[3 * (size_t)n], offset = (uint32_t)rays[3 * (size_t)n + 1];
-    const uint32_t num_steps = (uint32_t)rays[3 * (size_t)n + 2];
-    if (num_steps == 0 || offset + num_steps > M) return;                   // :624
+    const RayHead h = load_ray_head(rays, n, M);
+    if (!h.has) return;
+    const uint32_t index = h.index;
     float gws = grad_ws ? grad_ws[index] : 0.0f;
     float g0 = grad_image[3 * (size_t)index], g1 = grad_image[3 * (size_t)index + 1], g2 = grad_image[3 * (size_t)index + 2];
     [[maybe_unused]] DepthState<DEPTH> ds;
@@ -450,64 +545,26 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
             g0 *= gs; g1 *= gs; g2 *= gs; gws *= gs;
             if constexpr (DEPTH) ds.gD *= gs;
         }
-        const float* bg = dn.bg_rays ? dn.bg_rays + 3 * (size_t)index : dn.bg;
+        const float* bg = ray_bg(dn.bg_rays, dn.bg, index);
         gws = gws - ((g0 * bg[0] + g1 * bg[1]) + g2 * bg[2]);
     }
-    const float rf = image[3 * (size_t)index], gf = image[3 * (size_t)index + 1], bf = image[3 * (size_t)index + 2];
-    const float tail = gws * (1 - weights_sum[index]);
-    float T = 1.0f, r = 0, g = 0, b = 0;
-    if constexpr (DEPTH) ds.on = ds.gD != 0.0f;
+    const BwdRay c{g0, g1, g2, image[3 * (size_t)index], image[3 * (size_t)index + 1], image[3 * (size_t)index + 2],
+                   gws * (1 - weights_sum[index])};
+    bool with_t = false;
+    if constexpr (DEPTH) with_t = ds.on = ds.gD != 0.0f;
+    BwdRun st;
     bool stopped = false;
-    for (uint32_t base = 0; base < num_steps; base += 64) {
+    for (uint32_t base = 0; base < h.num_steps; base += 64) {
         const uint32_t k = base + lane;
-        bool valid = k < num_steps;
-        const size_t i = (size_t)offset + k;
+        const size_t i = (size_t)h.offset + k;
         if (DENSE && stopped) {                                             // samples after the early stop: zero gradient
-            if (valid) { grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f; grad_sigmas[i] = 0.f; }
+            if (k < h.num_steps) zero_grad_row(grad_sigmas, grad_rgbs, i);
             continue;
         }
-        const bool in_ray = valid;
-        float alpha = 0.f, d0 = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
-        if (valid) {
-            d0 = deltas[2 * i];
-            alpha = 1.0f - __expf(-sigmas[i] * d0);
-            c0 = rgbs[3 * i]; c1 = rgbs[3 * i + 1]; c2 = rgbs[3 * i + 2];
-        }
-        const float incl = wave_scan_mul(1.0f - alpha, lane);
-        const float excl = wave_prev(incl, 1.0f);
-        const float T_post = T * incl;
-        const unsigned long long stop = __ballot(valid && T_post < T_thresh);
-        bool done = false;
-        if (stop) { const int last = __builtin_ctzll(stop); valid = valid && lane <= last; done = true; }
-        const float w = valid ? alpha * (T * excl) : 0.0f;
-        const float rk = r + wave_scan_add(w * c0, lane);                   // running sums INCLUDING this sample
-        const float gk = g + wave_scan_add(w * c1, lane);
-        const float bk = b + wave_scan_add(w * c2, lane);
-        [[maybe_unused]] float tk = 0.0f, dk = 0.0f;
-        if constexpr (DEPTH) {
-            if (ds.on) {
-                tk = ds.t + wave_scan_add(in_ray ? deltas[2 * i + 1] : 0.0f, lane);  // t_k, as k_composite_train_fwd
-                dk = ds.dsum + wave_scan_add(w * tk, lane);                          // D_k, including this sample
-            }
-        }
-        if (valid) {
-            grad_rgbs[3 * i] = g0 * w; grad_rgbs[3 * i + 1] = g1 * w; grad_rgbs[3 * i + 2] = g2 * w;      // :657-659
-            if constexpr (DEPTH) {
-                const float br = g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gk)) + g2 * (T_post * c2 - (bf - bk)) + tail;
-                if (ds.on) grad_sigmas[i] = d0 * (br + ds.gD * (T_post * tk - (ds.df - dk)));
-                else grad_sigmas[i] = d0 * br;
-            } else {
-                grad_sigmas[i] = d0 * (g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gk)) +
-                                       g2 * (T_post * c2 - (bf - bk)) + tail);                            // :662-667
-            }
-        } else if (DENSE && in_ray) {
-            grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f; grad_sigmas[i] = 0.f;
-        }
-        if (done) { if (DENSE) { stopped = true; continue; } break; }
-        T *= wave_last(incl);
-        r = wave_last(rk); g = wave_last(gk); b = wave_last(bk);
-        if constexpr (DEPTH) {
-            if (ds.on) { ds.t = wave_last(tk); ds.dsum = wave_last(dk); }
+        const Sample s = load_sample(sigmas, rgbs, deltas, h, k, with_t);
+        if (composite_bwd_pass<DENSE, DEPTH>(s, k < h.num_steps, i, c, T_thresh, lane, st, ds, grad_sigmas, grad_rgbs)) {
+            if (!DENSE) break;
+            stopped = true;
         }
     }
 }
@@ -516,9 +573,9 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
 // composite_rays_train forward with the BLEND epilogue, the trainer's MSE criterion (d loss / d pixel needs this ray's
 // pixel only) and composite_rays_train backward (DENSE), one wavefront per ray: the three launches of the step's middle
 // (11.8 + 5.6 + 11 us and two kernel boundaries) become one.  Arithmetic is that of k_composite_train_fwd<true>,
-// k_mse_fwd and k_composite_train_bwd<true> (grad_scale = 1), statement for statement.  The loss VALUE needs all rays:
-// every workgroup leaves the sum of its rays' squared errors in partials[blockIdx.x], k_loss_finish adds them in a fixed
-// order (deterministic).
+// k_mse_fwd and k_composite_train_bwd<true> (grad_scale = 1): the passes are the same two functions.  The loss VALUE needs
+// all rays: every workgroup leaves the sum of its rays' squared errors in partials[blockIdx.x], k_loss_finish adds them in a
+// fixed order (deterministic).
 struct StepLoss { const float* target; const float* scale; float* grad_image; float* partials; float* poison_loss; };
 
 // DEPTH: a second criterion on the raw depth D of the ray, the reference's depth supervision (nerf/utils.py:585-589, 634-635):
@@ -547,146 +604,66 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
         const uint32_t rows_end = rows_end_p[0];
         zero_tail_rows(rows_end, M, n, N, lane, grad_sigmas, 1);
         zero_tail_rows(rows_end, M, n, N, lane, grad_rgbs, 3);
-        const uint32_t index = (uint32_t)rays[3 * (size_t)n], offset = (uint32_t)rays[3 * (size_t)n + 1];
-        const uint32_t num_steps = (uint32_t)rays[3 * (size_t)n + 2];
-        const bool has = !(num_steps == 0 || offset + num_steps > M);
-        // ---- forward (k_composite_train_fwd<true>)
-        float r = 0, g = 0, b = 0, ws = 0, d = 0;
-        // operands of one pass of 64 samples; the next pass is requested before the current one is scanned: the kernel's
-        // time is that of its longest rays (several passes, forward and backward), one memory latency per pass otherwise
-        struct Pass { float sg, d0, d1, c0, c1, c2; };
-        auto fetch = [&](uint32_t base) {
-            Pass p{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            const uint32_t k = base + lane;
-            if (k < num_steps) {
-                const size_t i = (size_t)offset + k;
-                p.sg = sigmas[i]; p.d0 = deltas[2 * i]; p.d1 = deltas[2 * i + 1];
-                p.c0 = rgbs[3 * i]; p.c1 = rgbs[3 * i + 1]; p.c2 = rgbs[3 * i + 2];
-            }
-            return p;
-        };
-        if (has) {
+        const RayHead h = load_ray_head(rays, n, M);
+        const uint32_t index = h.index;
+        // ---- forward.  The next pass of 64 samples is requested before the current one is scanned: the kernel's time is that of
+        // its longest rays (several passes, forward and backward), one memory latency per pass otherwise
+        FwdAcc a{0.f, 0.f, 0.f, 0.f, 0.f};
+        if (h.has) {
             float T = 1.0f, t = 0.0f;
-            Pass nxt = fetch(0);
-            for (uint32_t base = 0; base < num_steps; base += 64) {
-                const uint32_t k = base + lane;
-                bool valid = k < num_steps;
-                const Pass cur = nxt;
-                if (base + 64 < num_steps) nxt = fetch(base + 64);
-                float alpha = 0.f, d1 = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
-                if (valid) {
-                    alpha = 1.0f - __expf(-cur.sg * cur.d0);
-                    d1 = cur.d1;
-                    c0 = cur.c0; c1 = cur.c1; c2 = cur.c2;
-                }
-                const float incl = wave_scan_mul(1.0f - alpha, lane);
-                const float excl = wave_prev(incl, 1.0f);
-                const float T_post = T * incl;
-                const unsigned long long stop = __ballot(valid && T_post < T_thresh);
-                bool done = false;
-                if (stop) { const int last = __builtin_ctzll(stop); valid = valid && lane <= last; done = true; }
-                const float w = valid ? alpha * (T * excl) : 0.0f;
-                const float tk = t + wave_scan_add(d1, lane);
-                r += wave_sum(w * c0); g += wave_sum(w * c1); b += wave_sum(w * c2);
-                d += wave_sum(w * tk); ws += wave_sum(w);
-                if (done) break;
-                T *= wave_last(incl);
-                t = wave_last(tk);
+            Sample nxt = load_sample(sigmas, rgbs, deltas, h, lane, true);
+            for (uint32_t base = 0; base < h.num_steps; base += 64) {
+                const Sample cur = nxt;
+                if (base + 64 < h.num_steps) nxt = load_sample(sigmas, rgbs, deltas, h, base + 64 + lane, true);
+                if (composite_fwd_pass(cur, base + lane < h.num_steps, T_thresh, lane, T, t, a)) break;
             }
         }
-        const float* bg = bl.bg_rays ? bl.bg_rays + 3 * (size_t)index : bl.bg;
-        const float rest = 1.0f - ws;
-        const float o0 = r + rest * bg[0], o1 = g + rest * bg[1], o2 = b + rest * bg[2];
+        const float* bg = ray_bg(bl.bg_rays, bl.bg, index);
+        float o[3];
+        blend_colour(bg, a, o);
         // ---- criterion (k_mse_fwd): grad = ((pred - target) * 2 / n_elements) * scale
         const float s = sl.scale ? sl.scale[0] : 1.0f;
         const float gk = 2.0f / (float)(3u * N);
-        const float e0 = o0 - sl.target[3 * (size_t)index], e1 = o1 - sl.target[3 * (size_t)index + 1],
-                    e2 = o2 - sl.target[3 * (size_t)index + 2];
+        const float e0 = o[0] - sl.target[3 * (size_t)index], e1 = o[1] - sl.target[3 * (size_t)index + 1],
+                    e2 = o[2] - sl.target[3 * (size_t)index + 2];
         sq = fmaf(e2, e2, fmaf(e1, e1, e0 * e0));
-        float g0 = (e0 * gk) * s, g1 = (e1 * gk) * s, g2 = (e2 * gk) * s;
+        const float g0 = (e0 * gk) * s, g1 = (e1 * gk) * s, g2 = (e2 * gk) * s;
         if constexpr (DEPTH) {
             const size_t zi = dl.inds ? (size_t)dl.inds[index] : (size_t)index;
             const float z = dl.dtype == LAE_IMG_F16 ? __half2float(((const __half*)dl.src)[zi]) : ((const float*)dl.src)[zi];
             // a ray that misses the bounding box carries the sentinel interval near == far == FLT_MAX: it has no near to measure from
             // and is left unsupervised like a pixel with z == 0 (its residual would be ~FLT_MAX and the loss value infinite)
             const float nr = bl.nears[index];
-            const float res = (z > 0.0f && nr < bl.fars[index] ? 1.0f : 0.0f) * (d - (z - nr));
+            const float res = (z > 0.0f && nr < bl.fars[index] ? 1.0f : 0.0f) * (a.d - (z - nr));
             ds.dq = res * res;
             sq = sq + (3.0f * dl.lambda) * ds.dq;
             ds.gD = dl.value_only ? 0.0f : (res * (2.0f * dl.lambda / (float)N)) * s;
-            ds.df = d;
+            ds.df = a.d;
             ds.on = ds.gD != 0.0f;
             if (lane == 0) dl.grad_depth[index] = ds.gD;
         }
         if (lane == 0) {
-            weights_sum[index] = ws; depth[index] = d;
-            image[3 * (size_t)index] = r; image[3 * (size_t)index + 1] = g; image[3 * (size_t)index + 2] = b;
-            bl.image_out[3 * (size_t)index] = o0; bl.image_out[3 * (size_t)index + 1] = o1; bl.image_out[3 * (size_t)index + 2] = o2;
-            const float nr = bl.nears[index];
-            bl.depth_out[index] = fmaxf(d - nr, 0.0f) / (bl.fars[index] - nr);
+            store_ray(weights_sum, depth, image, index, a);
+            store_blend(bl, index, o, a.d);
             sl.grad_image[3 * (size_t)index] = g0; sl.grad_image[3 * (size_t)index + 1] = g1; sl.grad_image[3 * (size_t)index + 2] = g2;
         }
-        // ---- backward (k_composite_train_bwd<true>, grad_weights_sum = 0, grad_scale = 1)
-        if (has) {
+        // ---- backward (DENSE, grad_weights_sum = 0, grad_scale = 1)
+        if (h.has) {
             const float gws = 0.0f - ((g0 * bg[0] + g1 * bg[1]) + g2 * bg[2]);
-            const float rf = r, gf = g, bf = b;
-            const float tail = gws * (1 - ws);
-            float T = 1.0f, rr = 0, gg = 0, bb = 0;
+            const BwdRay c{g0, g1, g2, a.r, a.g, a.b, gws * (1 - a.ws)};
+            BwdRun st;
             bool stopped = false;
-            Pass nxt = fetch(0);
-            for (uint32_t base = 0; base < num_steps; base += 64) {
+            Sample nxt = load_sample(sigmas, rgbs, deltas, h, lane, true);
+            for (uint32_t base = 0; base < h.num_steps; base += 64) {
                 const uint32_t k = base + lane;
-                bool valid = k < num_steps;
-                const size_t i = (size_t)offset + k;
-                const Pass cur = nxt;
-                if (!stopped && base + 64 < num_steps) nxt = fetch(base + 64);
+                const size_t i = (size_t)h.offset + k;
+                const Sample cur = nxt;
+                if (!stopped && base + 64 < h.num_steps) nxt = load_sample(sigmas, rgbs, deltas, h, base + 64 + lane, true);
                 if (stopped) {                                                      // samples after the early stop: zero gradient
-                    if (valid) { grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f; grad_sigmas[i] = 0.f; }
+                    if (k < h.num_steps) zero_grad_row(grad_sigmas, grad_rgbs, i);
                     continue;
                 }
-                const bool in_ray = valid;
-                float alpha = 0.f, d0 = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
-                if (valid) {
-                    d0 = cur.d0;
-                    alpha = 1.0f - __expf(-cur.sg * d0);
-                    c0 = cur.c0; c1 = cur.c1; c2 = cur.c2;
-                }
-                const float incl = wave_scan_mul(1.0f - alpha, lane);
-                const float excl = wave_prev(incl, 1.0f);
-                const float T_post = T * incl;
-                const unsigned long long stop = __ballot(valid && T_post < T_thresh);
-                bool done = false;
-                if (stop) { const int last = __builtin_ctzll(stop); valid = valid && lane <= last; done = true; }
-                const float w = valid ? alpha * (T * excl) : 0.0f;
-                const float rk = rr + wave_scan_add(w * c0, lane);
-                const float gkk = gg + wave_scan_add(w * c1, lane);
-                const float bk = bb + wave_scan_add(w * c2, lane);
-                [[maybe_unused]] float tk = 0.0f, dk = 0.0f;
-                if constexpr (DEPTH) {
-                    if (ds.on) {
-                        tk = ds.t + wave_scan_add(cur.d1, lane);                     // cur.d1 is zero past the ray's end
-                        dk = ds.dsum + wave_scan_add(w * tk, lane);
-                    }
-                }
-                if (valid) {
-                    grad_rgbs[3 * i] = g0 * w; grad_rgbs[3 * i + 1] = g1 * w; grad_rgbs[3 * i + 2] = g2 * w;
-                    if constexpr (DEPTH) {
-                        const float br = g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gkk)) + g2 * (T_post * c2 - (bf - bk)) + tail;
-                        if (ds.on) grad_sigmas[i] = d0 * (br + ds.gD * (T_post * tk - (ds.df - dk)));
-                        else grad_sigmas[i] = d0 * br;
-                    } else {
-                        grad_sigmas[i] = d0 * (g0 * (T_post * c0 - (rf - rk)) + g1 * (T_post * c1 - (gf - gkk)) +
-                                               g2 * (T_post * c2 - (bf - bk)) + tail);
-                    }
-                } else if (in_ray) {
-                    grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f; grad_sigmas[i] = 0.f;
-                }
-                if (done) { stopped = true; continue; }
-                T *= wave_last(incl);
-                rr = wave_last(rk); gg = wave_last(gkk); bb = wave_last(bk);
-                if constexpr (DEPTH) {
-                    if (ds.on) { ds.t = wave_last(tk); ds.dsum = wave_last(dk); }
-                }
+                if (composite_bwd_pass<true, DEPTH>(cur, k < h.num_steps, i, c, T_thresh, lane, st, ds, grad_sigmas, grad_rgbs)) stopped = true;
             }
         }
     }
@@ -846,6 +823,50 @@ __global__ __launch_bounds__(COMPACT_BLOCK) void k_compact_scatter(const int32_t
     if (v >= 0) out[block_prefix[blockIdx.x] + local_prefix[i]] = v;
 }
 
+// ---------------------------------------------------------------- host side of K7 / K8: one body per pair of C entries
+// lae_composite_rays_train_step[_depth]: the depth-only arguments are checked first, before the N == 0 return
+template <bool DEPTH>
+int composite_train_step_impl(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                     float T_thresh, const Blend& bl, const uint32_t* rows_end, const StepLoss& sl, float* weights_sum,
+                                     float* depth, float* image, float* grad_sigmas, float* grad_rgbs, float* loss_out, int defer_loss,
+                                     const std::conditional_t<DEPTH, DepthLoss, NoArg>& dl, const char* what, void* stream) {
+    if constexpr (DEPTH) {
+        if (dl.dtype != LAE_IMG_F16 && dl.dtype != LAE_IMG_F32) return LAE_EINVAL;
+        if (!(dl.lambda >= 0.0f) || !(dl.lambda <= 3.0e38f)) return LAE_EINVAL;      // NaN, negative and infinite weights
+    }
+    if (N == 0) return LAE_OK;
+    if (!rays || !weights_sum || !depth || !image || !bl.nears || !bl.fars || !bl.depth_out || !bl.image_out || !rows_end || !sl.target ||
+        !sl.grad_image || !loss_out || !sl.partials)
+        return LAE_ENULL;
+    if constexpr (DEPTH) {
+        if (!dl.src || !dl.grad_depth || !dl.partials) return LAE_ENULL;    // dl.inds may be NULL (src holds one value per ray)
+    }
+    if (M > 0 && (!sigmas || !rgbs || !deltas || !grad_sigmas || !grad_rgbs)) return LAE_ENULL;
+    const uint32_t nb = lae::cdiv(N, COMP_WAVES);
+    k_composite_train_step<DEPTH><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth,
+                                                                        image, bl, sl, rows_end, grad_sigmas, grad_rgbs, dl);
+    // defer_loss: the one-block sum of the partials (5.5 us + a kernel boundary on the step's critical path for a number that
+    // feeds nothing on the device) is left to lae_loss_finish or to a later launch that takes it along
+    // (lae_nerf_head_backward); loss_out holds NaN until then
+    if (!defer_loss) k_loss_finish<<<1, 1024, 0, STREAM(stream)>>>(sl.partials, nb, 3u * N, sl.scale, loss_out);
+    return lae::check_launch(what);
+}
+
+template <bool DEPTH>
+int composite_train_backward_blend_impl(const float* grad_weights_sum, const float* grad_image, const float* sigmas, const float* rgbs,
+                                               const float* deltas, const int32_t* rays, const float* weights_sum, const float* image,
+                                               uint32_t M, uint32_t N, float T_thresh, const Dense& dn, float* grad_sigmas, float* grad_rgbs,
+                                               const std::conditional_t<DEPTH, DepthGrad, NoArg>& dg, const char* what, void* stream) {
+    if (N == 0 || M == 0) return LAE_OK;
+    if (!grad_image || !sigmas || !rgbs || !deltas || !rays || !weights_sum || !image || !grad_sigmas || !grad_rgbs || !dn.rows_end)
+        return LAE_ENULL;                                   // grad_weights_sum may be NULL (= zero)
+    if constexpr (DEPTH) {
+        if (!dg.grad_depth || !dg.depth) return LAE_ENULL;
+    }
+    k_composite_train_bwd<true, DEPTH><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
+        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn, dg);
+    return lae::check_launch(what);
+}
 
 }  // namespace
 
@@ -984,21 +1005,9 @@ int lae_composite_rays_train_step(const float* sigmas, const float* rgbs, const 
                                   float* weights_sum, float* depth, float* image, float* depth_out, float* image_out,
                                   float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out, float* partials,
                                   int defer_loss, void* stream) {
-    if (N == 0) return LAE_OK;
-    if (!rays || !weights_sum || !depth || !image || !nears || !fars || !depth_out || !image_out || !rows_end || !target || !grad_image ||
-        !loss_out || !partials)
-        return LAE_ENULL;
-    if (M > 0 && (!sigmas || !rgbs || !deltas || !grad_sigmas || !grad_rgbs)) return LAE_ENULL;
-    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
-    const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
-    const uint32_t nb = lae::cdiv(N, COMP_WAVES);
-    k_composite_train_step<false><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth,
-                                                                        image, bl, sl, rows_end, grad_sigmas, grad_rgbs, NoArg{});
-    // defer_loss: the one-block sum of the partials (5.5 us + a kernel boundary on the step's critical path for a number that
-    // feeds nothing on the device) is left to lae_loss_finish or to a later launch that takes it along
-    // (lae_nerf_head_backward); loss_out holds NaN until then
-    if (!defer_loss) k_loss_finish<<<1, 1024, 0, STREAM(stream)>>>(partials, nb, 3u * N, scale, loss_out);
-    return lae::check_launch("composite_rays_train_step");
+    return composite_train_step_impl<false>(sigmas, rgbs, deltas, rays, M, N, T_thresh, Blend{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out},
+                                            rows_end, StepLoss{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr}, weights_sum, depth,
+                                            image, grad_sigmas, grad_rgbs, loss_out, defer_loss, NoArg{}, "composite_rays_train_step", stream);
 }
 
 int lae_composite_rays_train_step_depth(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
@@ -1009,21 +1018,11 @@ int lae_composite_rays_train_step_depth(const float* sigmas, const float* rgbs, 
                                         float* partials, int defer_loss, const void* depth_src, int depth_dtype,
                                         const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
                                         float* depth_partials, void* stream) {
-    if (depth_dtype != LAE_IMG_F16 && depth_dtype != LAE_IMG_F32) return LAE_EINVAL;
-    if (!(lambda >= 0.0f) || !(lambda <= 3.0e38f)) return LAE_EINVAL;      // NaN, negative and infinite weights
-    if (N == 0) return LAE_OK;
-    if (!rays || !weights_sum || !depth || !image || !nears || !fars || !depth_out || !image_out || !rows_end || !target || !grad_image ||
-        !loss_out || !partials || !depth_src || !grad_depth || !depth_partials)
-        return LAE_ENULL;                                   // depth_inds may be NULL (depth_src holds one value per ray)
-    if (M > 0 && (!sigmas || !rgbs || !deltas || !grad_sigmas || !grad_rgbs)) return LAE_ENULL;
-    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
-    const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
-    const DepthLoss dl{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials};
-    const uint32_t nb = lae::cdiv(N, COMP_WAVES);
-    k_composite_train_step<true><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth,
-                                                                       image, bl, sl, rows_end, grad_sigmas, grad_rgbs, dl);
-    if (!defer_loss) k_loss_finish<<<1, 1024, 0, STREAM(stream)>>>(partials, nb, 3u * N, scale, loss_out);
-    return lae::check_launch("composite_rays_train_step_depth");
+    return composite_train_step_impl<true>(sigmas, rgbs, deltas, rays, M, N, T_thresh, Blend{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out},
+                                           rows_end, StepLoss{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr}, weights_sum, depth,
+                                           image, grad_sigmas, grad_rgbs, loss_out, defer_loss,
+                                           DepthLoss{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials},
+                                           "composite_rays_train_step_depth", stream);
 }
 
 int lae_loss_finish(const float* partials, uint32_t n_part, uint32_t n_elem, const float* scale, float* loss_out, void* stream) {
@@ -1039,13 +1038,9 @@ int lae_composite_rays_train_backward_blend_ex(const float* grad_weights_sum, co
                                                float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
                                                const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
                                                float* grad_rgbs, void* stream) {
-    if (N == 0 || M == 0) return LAE_OK;
-    if (!grad_image || !sigmas || !rgbs || !deltas || !rays || !weights_sum || !image || !grad_sigmas || !grad_rgbs || !rows_end)
-        return LAE_ENULL;                                   // grad_weights_sum may be NULL (= zero)
-    const Dense dn{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale};
-    k_composite_train_bwd<true><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
-        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn, NoArg{});
-    return lae::check_launch("composite_rays_train_backward_blend");
+    return composite_train_backward_blend_impl<false>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh,
+                                                      Dense{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale}, grad_sigmas, grad_rgbs, NoArg{},
+                                                      "composite_rays_train_backward_blend", stream);
 }
 
 int lae_composite_rays_train_backward_blend_depth(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
@@ -1054,15 +1049,9 @@ int lae_composite_rays_train_backward_blend_depth(const float* grad_weights_sum,
                                                   float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
                                                   const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
                                                   float* grad_rgbs, const float* grad_depth, const float* depth, void* stream) {
-    if (N == 0 || M == 0) return LAE_OK;
-    if (!grad_image || !sigmas || !rgbs || !deltas || !rays || !weights_sum || !image || !grad_sigmas || !grad_rgbs || !rows_end ||
-        !grad_depth || !depth)
-        return LAE_ENULL;                                   // grad_weights_sum may be NULL (= zero)
-    const Dense dn{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale};
-    k_composite_train_bwd<true, true><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
-        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn,
-        DepthGrad{grad_depth, depth});
-    return lae::check_launch("composite_rays_train_backward_blend_depth");
+    return composite_train_backward_blend_impl<true>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh,
+                                                     Dense{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale}, grad_sigmas, grad_rgbs,
+                                                     DepthGrad{grad_depth, depth}, "composite_rays_train_backward_blend_depth", stream);
 }
 
 int lae_composite_rays_train_backward_blend(const float* grad_weights_sum, const float* grad_image, const float* sigmas,

@@ -14,8 +14,9 @@ from ..backend import raymarching_backend as _backend
 
 __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", "packbits", "march_rays_train",
            "composite_rays_train", "march_rays", "march_rays_distill", "composite_rays", "composite_rays_distill",
-           "compact_rays_alive", "render_frame", "composite_rays_train_blend", "composite_rays_train_blend_mse", "composite_rays_train_blend_depth", "finish_depth_loss",
-           "composite_depth_numpy", "density_grid_positions", "density_grid_partial_positions", "density_grid_update", "mark_untrained_grid"]
+           "compact_rays_alive", "render_frame", "composite_rays_train_blend", "composite_rays_train_blend_mse",
+           "composite_rays_train_blend_depth", "finish_depth_loss", "composite_depth_numpy", "density_grid_positions",
+           "density_grid_partial_positions", "density_grid_update", "mark_untrained_grid"]
 
 
 def _gpu(t):
@@ -219,44 +220,52 @@ class _composite_rays_train(Function):
 composite_rays_train = _composite_rays_train.apply
 
 
+def _train_outputs(N, dt, dev):
+    """weights_sum [N], raw depth [N], un-blended image [N,3], depth_out [N], image_out [N,3] of the BLEND forward"""
+    return (torch.empty(N, dtype=dt, device=dev), torch.empty(N, dtype=dt, device=dev), torch.empty(N, 3, dtype=dt, device=dev),
+            torch.empty(N, dtype=dt, device=dev), torch.empty(N, 3, dtype=dt, device=dev))
+
+
 class _composite_rays_train_blend(Function):
     """MI355X-native: composite_rays_train + the post-ops of run_cuda (nerf/renderer.py:321, 325) in the same kernels:
     image + (1 - weights_sum) * bg_color and clamp(depth - nears, min=0) / (fars - nears).  The backward writes every
-    gradient row itself (no zero fills).  `rays` must come from this package's march_rays_train (ray-id order)."""
+    gradient row itself (no zero fills).  `rays` must come from this package's march_rays_train (ray-id order).
+    Also returns the RAW depth D = sum_k w_k t_k, differentiable: where it receives a gradient the backward is
+    lae_composite_rays_train_backward_blend_depth, which carries what the reference's backward drops (raymarching.py:273-275)."""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh):
         sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
         M, N = sigmas.shape[0], rays.shape[0]
-        dev, dt = sigmas.device, sigmas.dtype
-        weights_sum, depth, image = (torch.empty(N, dtype=dt, device=dev), torch.empty(N, dtype=dt, device=dev),
-                                     torch.empty(N, 3, dtype=dt, device=dev))
-        depth_out, image_out = torch.empty(N, dtype=dt, device=dev), torch.empty(N, 3, dtype=dt, device=dev)
+        weights_sum, depth, image, depth_out, image_out = _train_outputs(N, sigmas.dtype, sigmas.device)
         _backend.composite_rays_train_forward_blend(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(),
                                                     fars.contiguous(), bg_rays, bg, weights_sum, depth, image, depth_out, image_out)
-        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image, bg_rays, rows_end)
+        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, depth, image, bg_rays, rows_end)
         ctx.dims = [M, N, T_thresh, bg]
         ctx.mark_non_differentiable(depth_out)
-        ctx.set_materialize_grads(False)                 # an unused weights_sum arrives as None, not as a zero fill
-        return weights_sum, depth_out, image_out
+        ctx.set_materialize_grads(False)                 # an unused output's gradient arrives as None, not as a zero fill
+        return weights_sum, depth, depth_out, image_out
 
     @staticmethod
     @custom_bwd(device_type="cuda")
-    def backward(ctx, grad_weights_sum, grad_depth, grad_image):
-        sigmas, rgbs, deltas, rays, weights_sum, image, bg_rays, rows_end = ctx.saved_tensors
+    def backward(ctx, grad_weights_sum, grad_depth, grad_depth_out, grad_image):
+        sigmas, rgbs, deltas, rays, weights_sum, depth, image, bg_rays, rows_end = ctx.saved_tensors
         M, N, T_thresh, bg = ctx.dims
-        if grad_image is None and grad_weights_sum is None:
-            return None, None, None, None, None, None, None, None, None, None
-        if grad_weights_sum is None:
-            grad_weights_sum = torch.zeros_like(weights_sum)
+        if grad_image is None and grad_weights_sum is None and grad_depth is None:
+            return (None,) * 10
         if grad_image is None:
             grad_image = torch.zeros_like(image)
+        gws = None if grad_weights_sum is None else grad_weights_sum.float().contiguous()     # None: the kernel takes zero
         grad_sigmas, grad_rgbs = torch.empty_like(sigmas), torch.empty_like(rgbs)
-        _backend.composite_rays_train_backward_blend(grad_weights_sum.contiguous(), grad_image.contiguous(), sigmas, rgbs,
-                                                     deltas, rays, weights_sum, image, M, N, T_thresh, bg_rays, bg, rows_end,
-                                                     grad_sigmas, grad_rgbs)
-        return grad_sigmas, grad_rgbs, None, None, None, None, None, None, None, None
+        if grad_depth is None:
+            _backend.composite_rays_train_backward_blend(gws, grad_image.float().contiguous(), sigmas, rgbs, deltas, rays, weights_sum,
+                                                         image, M, N, T_thresh, bg_rays, bg, rows_end, grad_sigmas, grad_rgbs)
+        else:
+            _backend.composite_rays_train_backward_blend_depth(gws, grad_image.float().contiguous(), grad_depth.float().contiguous(),
+                                                               sigmas, rgbs, deltas, rays, weights_sum, depth, image, M, N, T_thresh,
+                                                               bg_rays, bg, rows_end, grad_sigmas, grad_rgbs)
+        return (grad_sigmas, grad_rgbs) + (None,) * 8
 
 
 def _bg_args(bg_color, device):
@@ -273,56 +282,21 @@ def _bg_args(bg_color, device):
     return bg_rays, bg
 
 
+def _blend_args(who, rays, bg_color, device):
+    """-> rows_end, bg_rays, bg of a composite_rays_train_blend* call (`who`: the function the user called)"""
+    rows_end = getattr(rays, "rows_end", None)
+    if rows_end is None:
+        raise RuntimeError(f"{who}: `rays` must be the tensor returned by laenerf_amd march_rays_train")
+    return (rows_end,) + _bg_args(bg_color, device)
+
+
 def composite_rays_train_blend(sigmas, rgbs, deltas, rays, nears, fars, bg_color=1, T_thresh=1e-4):
     """-> weights_sum [N], depth normalised to [0,1] [N], image blended over bg_color [N,3]
     bg_color: number, 3 numbers / tensor of 3, or a per-ray [N,3] tensor (renderer.py:313-321)"""
-    rows_end = getattr(rays, "rows_end", None)
-    if rows_end is None:
-        raise RuntimeError("composite_rays_train_blend: `rays` must be the tensor returned by laenerf_amd march_rays_train")
-    bg_rays, bg = _bg_args(bg_color, sigmas.device)
-    return _composite_rays_train_blend.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh)
-
-
-class _composite_rays_train_blend_depth(Function):
-    """_composite_rays_train_blend that also returns the RAW depth D = sum_k w_k t_k, differentiable: its backward is
-    lae_composite_rays_train_backward_blend_depth, which carries the gradient the reference's backward drops (raymarching.py:273-275)"""
-
-    @staticmethod
-    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh):
-        sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
-        M, N = sigmas.shape[0], rays.shape[0]
-        dev, dt = sigmas.device, sigmas.dtype
-        weights_sum, depth, image = (torch.empty(N, dtype=dt, device=dev), torch.empty(N, dtype=dt, device=dev),
-                                     torch.empty(N, 3, dtype=dt, device=dev))
-        depth_out, image_out = torch.empty(N, dtype=dt, device=dev), torch.empty(N, 3, dtype=dt, device=dev)
-        _backend.composite_rays_train_forward_blend(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(),
-                                                    fars.contiguous(), bg_rays, bg, weights_sum, depth, image, depth_out, image_out)
-        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, depth, image, bg_rays, rows_end)
-        ctx.dims = [M, N, T_thresh, bg]
-        ctx.mark_non_differentiable(depth_out)
-        ctx.set_materialize_grads(False)
-        return weights_sum, depth, depth_out, image_out
-
-    @staticmethod
-    @custom_bwd(device_type="cuda")
-    def backward(ctx, grad_weights_sum, grad_depth, grad_depth_out, grad_image):
-        sigmas, rgbs, deltas, rays, weights_sum, depth, image, bg_rays, rows_end = ctx.saved_tensors
-        M, N, T_thresh, bg = ctx.dims
-        if grad_image is None and grad_weights_sum is None and grad_depth is None:
-            return (None,) * 10
-        if grad_image is None:
-            grad_image = torch.zeros_like(image)
-        gws = None if grad_weights_sum is None else grad_weights_sum.float().contiguous()
-        grad_sigmas, grad_rgbs = torch.empty_like(sigmas), torch.empty_like(rgbs)
-        if grad_depth is None:
-            _backend.composite_rays_train_backward_blend(gws, grad_image.float().contiguous(), sigmas, rgbs, deltas, rays, weights_sum,
-                                                         image, M, N, T_thresh, bg_rays, bg, rows_end, grad_sigmas, grad_rgbs)
-        else:
-            _backend.composite_rays_train_backward_blend_depth(gws, grad_image.float().contiguous(), grad_depth.float().contiguous(),
-                                                               sigmas, rgbs, deltas, rays, weights_sum, depth, image, M, N, T_thresh,
-                                                               bg_rays, bg, rows_end, grad_sigmas, grad_rgbs)
-        return (grad_sigmas, grad_rgbs) + (None,) * 8
+    rows_end, bg_rays, bg = _blend_args("composite_rays_train_blend", rays, bg_color, sigmas.device)
+    weights_sum, _, depth_out, image = _composite_rays_train_blend.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end,
+                                                                         T_thresh)
+    return weights_sum, depth_out, image
 
 
 def composite_rays_train_blend_depth(sigmas, rgbs, deltas, rays, nears, fars, bg_color=1, T_thresh=1e-4):
@@ -330,11 +304,8 @@ def composite_rays_train_blend_depth(sigmas, rgbs, deltas, rays, nears, fars, bg
     depth_raw = sum_k w_k t_k (t from the ray's first sample, the `depth` of composite_rays_train) carries a gradient to the
     densities: the building block of depth losses (DS-NeRF-style sparse depth, the distillation's depth term).  The
     reference-named composite_rays_train keeps ignoring the gradient of depth."""
-    rows_end = getattr(rays, "rows_end", None)
-    if rows_end is None:
-        raise RuntimeError("composite_rays_train_blend_depth: `rays` must be the tensor returned by laenerf_amd march_rays_train")
-    bg_rays, bg = _bg_args(bg_color, sigmas.device)
-    return _composite_rays_train_blend_depth.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh)
+    rows_end, bg_rays, bg = _blend_args("composite_rays_train_blend_depth", rays, bg_color, sigmas.device)
+    return _composite_rays_train_blend.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh)
 
 
 # root gradients known to be all ones (laenerf_amd.optim.FusedAdam.backward registers the tensor it passes to
@@ -353,53 +324,6 @@ def _is_unit_root_grad(t):
     return r is not None and r() is not None and r().shape == t.shape
 
 
-class _composite_rays_train_blend_mse(Function):
-    """composite_rays_train_blend + the trainer's criterion and loss scaling (`MSELoss(pred_rgb, gt).mean()` then
-    `scaler.scale(loss)`, nerf/utils.py train_step) as ONE autograd node and ONE kernel: d loss / d pixel of a ray depends on
-    that ray's pixel only, so the compositing forward, the criterion and the compositing backward of a ray run back to back
-    in the wavefront that owns it (`lae_composite_rays_train_step`; three launches and two kernel boundaries in the middle of
-    the step before).  The sample gradients are therefore computed in forward() for an upstream gradient of 1 and stored;
-    backward() returns them -- multiplied by the upstream gradient unless that is known to be ones."""
-
-    @staticmethod
-    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, defer_loss=False):
-        sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
-        M, N = sigmas.shape[0], rays.shape[0]
-        dev, dt = sigmas.device, sigmas.dtype
-        weights_sum, depth, image = (torch.empty(N, dtype=dt, device=dev), torch.empty(N, dtype=dt, device=dev),
-                                     torch.empty(N, 3, dtype=dt, device=dev))
-        depth_out, image_out = torch.empty(N, dtype=dt, device=dev), torch.empty(N, 3, dtype=dt, device=dev)
-        target = target.float().contiguous()
-        if target.shape != image_out.shape:
-            raise RuntimeError("composite_rays_train_blend_mse: target must be [N,3]")
-        out = torch.empty(2, dtype=torch.float32, device=dev)
-        grad_image = torch.empty_like(image_out)
-        grad_sigmas, grad_rgbs = torch.empty_like(sigmas), torch.empty_like(rgbs)
-        partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
-        _backend.composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(), fars.contiguous(), bg_rays,
-                                           bg, rows_end, target, scale, weights_sum, depth, image, depth_out, image_out, grad_image,
-                                           grad_sigmas, grad_rgbs, out, partials, defer_loss=defer_loss)
-        ctx.save_for_backward(grad_sigmas, grad_rgbs)
-        ctx.mark_non_differentiable(weights_sum, depth_out, image_out, out)
-        ctx.set_materialize_grads(False)                 # no zero-filled gradients for the four auxiliary outputs (4 fill launches)
-        return out[0], weights_sum, depth_out, image_out, out
-
-    @staticmethod
-    @custom_bwd(device_type="cuda")
-    def backward(ctx, grad_loss, *_):
-        if grad_loss is None:
-            return (None,) * 13
-        grad_sigmas, grad_rgbs = ctx.saved_tensors
-        if not _is_unit_root_grad(grad_loss):              # a general upstream gradient: d(loss) scales every sample gradient
-            gl = grad_loss.float()
-            scaled = grad_sigmas * gl
-            from ..backend import retarget_pending_loss
-            retarget_pending_loss(grad_sigmas, scaled)     # a deferred loss value follows the tensor the head backward will receive
-            grad_sigmas, grad_rgbs = scaled, grad_rgbs * gl
-        return grad_sigmas, grad_rgbs, None, None, None, None, None, None, None, None, None, None, None
-
-
 class _DepthPlane:
     """holds the depth plane on its way through Function.apply: custom_fwd(cast_inputs=float32) would copy a fp16 plane of the whole
     image set to fp32 in every step under autocast; the kernel reads fp16 itself"""
@@ -409,20 +333,25 @@ class _DepthPlane:
         self.t = t
 
 
-class _composite_rays_train_blend_mse_depth(Function):
-    """_composite_rays_train_blend_mse with the depth criterion in the same kernel (`lae_composite_rays_train_step_depth`):
-    loss = MSE + depth_weight * mean(((D - (z - nears)) * (z > 0))^2), z gathered from the depth plane by the kernel."""
+class _composite_rays_train_blend_mse(Function):
+    """composite_rays_train_blend + the trainer's criterion and loss scaling (`MSELoss(pred_rgb, gt).mean()` then
+    `scaler.scale(loss)`, nerf/utils.py train_step) as ONE autograd node and ONE kernel: d loss / d pixel of a ray depends on
+    that ray's pixel only, so the compositing forward, the criterion and the compositing backward of a ray run back to back
+    in the wavefront that owns it (`lae_composite_rays_train_step`; three launches and two kernel boundaries in the middle of
+    the step before).  The sample gradients are therefore computed in forward() for an upstream gradient of 1 and stored;
+    backward() returns them -- multiplied by the upstream gradient unless that is known to be ones.
+    depth_sup = (_DepthPlane, depth_inds, depth_weight, value_only) adds the depth criterion in the same kernel
+    (`lae_composite_rays_train_step_depth`): loss = MSE + depth_weight * mean(((D - (z - nears)) * (z > 0))^2), z gathered from the
+    depth plane by the kernel; the last two outputs (the depth partial sums, d loss / d D) are None without it."""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, defer_loss, depth_src,
-                depth_inds, depth_weight, value_only):
+    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, defer_loss=False,
+                depth_sup=None):
         sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
         M, N = sigmas.shape[0], rays.shape[0]
-        dev, dt = sigmas.device, sigmas.dtype
-        weights_sum, depth, image = (torch.empty(N, dtype=dt, device=dev), torch.empty(N, dtype=dt, device=dev),
-                                     torch.empty(N, 3, dtype=dt, device=dev))
-        depth_out, image_out = torch.empty(N, dtype=dt, device=dev), torch.empty(N, 3, dtype=dt, device=dev)
+        dev = sigmas.device
+        weights_sum, depth, image, depth_out, image_out = _train_outputs(N, sigmas.dtype, dev)
         target = target.float().contiguous()
         if target.shape != image_out.shape:
             raise RuntimeError("composite_rays_train_blend_mse: target must be [N,3]")
@@ -430,30 +359,34 @@ class _composite_rays_train_blend_mse_depth(Function):
         grad_image = torch.empty_like(image_out)
         grad_sigmas, grad_rgbs = torch.empty_like(sigmas), torch.empty_like(rgbs)
         partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
-        grad_depth = torch.empty(N, dtype=torch.float32, device=dev)
-        depth_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
+        grad_depth = depth_partials = None
+        if depth_sup is not None:
+            plane, depth_inds, depth_weight, value_only = depth_sup
+            grad_depth = torch.empty(N, dtype=torch.float32, device=dev)
+            depth_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
+            depth_sup = (plane.t, depth_inds, depth_weight, value_only, grad_depth, depth_partials)
         _backend.composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(), fars.contiguous(), bg_rays,
                                            bg, rows_end, target, scale, weights_sum, depth, image, depth_out, image_out, grad_image,
-                                           grad_sigmas, grad_rgbs, out, partials, defer_loss=defer_loss,
-                                           depth_sup=(depth_src.t, depth_inds, depth_weight, value_only, grad_depth, depth_partials))
+                                           grad_sigmas, grad_rgbs, out, partials, defer_loss=defer_loss, depth_sup=depth_sup)
         ctx.save_for_backward(grad_sigmas, grad_rgbs)
-        ctx.mark_non_differentiable(weights_sum, depth_out, image_out, out, depth_partials, grad_depth)
-        ctx.set_materialize_grads(False)
+        aux = (weights_sum, depth_out, image_out, out) + (() if depth_sup is None else (depth_partials, grad_depth))
+        ctx.mark_non_differentiable(*aux)
+        ctx.set_materialize_grads(False)                 # no zero-filled gradients for the auxiliary outputs (a fill launch each)
         return out[0], weights_sum, depth_out, image_out, out, depth_partials, grad_depth
 
     @staticmethod
     @custom_bwd(device_type="cuda")
     def backward(ctx, grad_loss, *_):
         if grad_loss is None:
-            return (None,) * 17
+            return (None,) * 14
         grad_sigmas, grad_rgbs = ctx.saved_tensors
-        if not _is_unit_root_grad(grad_loss):
+        if not _is_unit_root_grad(grad_loss):              # a general upstream gradient: d(loss) scales every sample gradient
             gl = grad_loss.float()
             scaled = grad_sigmas * gl
             from ..backend import retarget_pending_loss
-            retarget_pending_loss(grad_sigmas, scaled)
+            retarget_pending_loss(grad_sigmas, scaled)     # a deferred loss value follows the tensor the head backward will receive
             grad_sigmas, grad_rgbs = scaled, grad_rgbs * gl
-        return (grad_sigmas, grad_rgbs) + (None,) * 15
+        return (grad_sigmas, grad_rgbs) + (None,) * 12
 
 
 def finish_depth_loss(loss, out=None):
@@ -484,39 +417,26 @@ def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, targ
     term's gradient to the densities -- the reference's backward drops it (raymarching.py:273-275), depth_grad=False restates
     that: the value only, the sample gradients of the call without depth bit for bit.  `loss.grad_depth` [N] holds d loss / d D,
     finish_depth_loss(loss) the unweighted depth term."""
-    rows_end = getattr(rays, "rows_end", None)
-    if rows_end is None:
-        raise RuntimeError("composite_rays_train_blend_mse: `rays` must be the tensor returned by laenerf_amd march_rays_train")
-    bg_rays, bg = _bg_args(bg_color, sigmas.device)
+    rows_end, bg_rays, bg = _blend_args("composite_rays_train_blend_mse", rays, bg_color, sigmas.device)
     scale = None
     if scaler is not None:
         scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
     if defer_loss is None:
         defer_loss = scaler is not None and not torch.is_tensor(scaler) and hasattr(scaler, "finish_loss")
+    depth_sup = None
     if depth is not None:
         if not torch.is_tensor(depth) or depth.dtype not in (torch.float16, torch.float32):
             raise RuntimeError("composite_rays_train_blend_mse: depth must be a float16 or float32 tensor")
         if not (float(depth_weight) >= 0.0) or float(depth_weight) == float("inf"):
             raise ValueError("composite_rays_train_blend_mse: depth_weight must be finite and >= 0")
-        loss, weights_sum, depth_o, image, both, depth_partials, grad_depth = _composite_rays_train_blend_mse_depth.apply(
-            sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, bool(defer_loss),
-            _DepthPlane(depth.contiguous()), None if depth_inds is None else depth_inds.contiguous(), float(depth_weight), not depth_grad)
-        loss.unscaled = both[1]
-        loss.depth_partials, loss.grad_depth, loss.depth_rays = depth_partials, grad_depth, rays.shape[0]
-        return loss, weights_sum, depth_o, image
-    rows_end = getattr(rays, "rows_end", None)
-    if rows_end is None:
-        raise RuntimeError("composite_rays_train_blend_mse: `rays` must be the tensor returned by laenerf_amd march_rays_train")
-    bg_rays, bg = _bg_args(bg_color, sigmas.device)
-    scale = None
-    if scaler is not None:
-        scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
-    if defer_loss is None:
-        defer_loss = scaler is not None and not torch.is_tensor(scaler) and hasattr(scaler, "finish_loss")
-    loss, weights_sum, depth, image, both = _composite_rays_train_blend_mse.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg,
-                                                                                  rows_end, T_thresh, target, scale, bool(defer_loss))
+        depth_sup = (_DepthPlane(depth.contiguous()), None if depth_inds is None else depth_inds.contiguous(), float(depth_weight),
+                     not depth_grad)
+    loss, weights_sum, depth_o, image, both, depth_partials, grad_depth = _composite_rays_train_blend_mse.apply(
+        sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, bool(defer_loss), depth_sup)
     loss.unscaled = both[1]
-    return loss, weights_sum, depth, image
+    if depth_sup is not None:
+        loss.depth_partials, loss.grad_depth, loss.depth_rays = depth_partials, grad_depth, rays.shape[0]
+    return loss, weights_sum, depth_o, image
 
 
 def _infer_buffers(n_alive, n_step, align, dt, dev):

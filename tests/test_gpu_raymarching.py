@@ -301,3 +301,30 @@ def test_composite_train_step_equals_the_three_kernels(rm, bg_mode):
         assert loss1[1].item() == pytest.approx(loss0[1].item(), rel=2e-6) and loss1[0].item() == pytest.approx(1024.0 * loss1[1].item(), rel=1e-6)
         ref = torch.nn.functional.mse_loss(io1, target).item()
         assert loss1[1].item() == pytest.approx(ref, rel=1e-5)
+
+
+@pytest.mark.parametrize("op", ["composite_rays_train_blend", "composite_rays_train_blend_depth"])
+def test_blend_backward_without_weights_sum_gradient(rm, op):
+    """a backward that receives a gradient for `image` only (weights_sum -- and the raw depth -- unused) hands NULL to the
+    kernel instead of a zero fill: the same bits as lae_composite_rays_train_backward_blend with an explicit all-zero
+    grad_weights_sum on NaN-poisoned gradient buffers.  The hand-built table of depth_sup_util: passes of 64 samples, stops
+    in the first and second pass and at lane 63, an empty and a dropped ray, unowned rows."""
+    from depth_sup_util import T_THRESH, build_case, build_grads
+    from laenerf_amd.backend import raymarching_backend as B
+    c = build_case()
+    t = {k: T(c[k]) for k in ("sigmas", "rgbs", "deltas", "rays", "nears", "fars", "bg_rays")}
+    t["rays"].rows_end = torch.tensor([c["rows_end"]], dtype=torch.int32, device=DEV)
+    M, n = c["M"], c["N"]
+    gimg = T(build_grads(n)[1])
+    sig, rgb = t["sigmas"].clone().requires_grad_(), t["rgbs"].clone().requires_grad_()
+    out = getattr(rm, op)(sig, rgb, t["deltas"], t["rays"], t["nears"], t["fars"], bg_color=t["bg_rays"], T_thresh=T_THRESH)
+    out[-1].backward(gimg)
+    new = lambda *shape: torch.full(shape, float("nan"), device=DEV)
+    ws, dp, im, do, io = new(n), new(n), new(n, 3), new(n), new(n, 3)
+    B.composite_rays_train_forward_blend(t["sigmas"], t["rgbs"], t["deltas"], t["rays"], M, n, T_THRESH, t["nears"], t["fars"],
+                                         t["bg_rays"], (0.0, 0.0, 0.0), ws, dp, im, do, io)
+    gs, gc = new(M), new(M, 3)
+    B.composite_rays_train_backward_blend(torch.zeros(n, device=DEV), gimg, t["sigmas"], t["rgbs"], t["deltas"], t["rays"], ws, im, M, n,
+                                          T_THRESH, t["bg_rays"], (0.0, 0.0, 0.0), t["rays"].rows_end, gs, gc)
+    assert torch.isfinite(gs).all() and torch.isfinite(gc).all() and gs.any() and gc.any()
+    assert torch.equal(sig.grad, gs) and torch.equal(rgb.grad, gc)
