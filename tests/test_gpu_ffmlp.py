@@ -1,5 +1,7 @@
 """-m gpu: MFMA MLP vs the oracle (fp16 storage, fp32 accumulate).  Tolerances: outputs differ from the oracle only
-by the MFMA's internal summation order before the fp16 rounding of each stored activation (<= 1 fp16 ulp per layer)."""
+by the MFMA's internal summation order before the fp16 rounding of each stored activation (<= 1 fp16 ulp per layer).
+These max-norm tolerances do not see an error of single rows (a row dropped from dW, a wrong row in a tail tile): those are caught by
+the exact-arithmetic cases of tests/test_gpu_mlp_exact.py, which compare bit for bit."""
 import numpy as np
 import pytest
 import torch
