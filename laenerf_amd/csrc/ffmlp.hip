@@ -1404,8 +1404,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_nerf_head_fwd5(
 // :1037-1142) for the rays whose rows the wave just shaded.  Rows are ray-major in 64-row groups of whole rays
 // (lae_common.h FrameCtrl), lane L of a wave does the per-row work of row L of its group, so the sigma / rgb of a ray's
 // n_step rows sit in n_step consecutive lanes: they go through the wave's LDS scratch to the lane of the ray's first row,
-// which runs the reference's serial loop (same operations in the same order: the image is the same bits as the two-kernel
-// form's) on the ray's 32-byte accumulator record.  sigmas / rgbs never reach memory (16 B written + 16 B read per row) and
+// which runs the reference's serial loop (lae::composite_infer_sample, the body k_composite_infer runs: the image is the same
+// bits as the two-kernel form's) on the ray's 32-byte accumulator record.  sigmas / rgbs never reach memory (16 B written + 16 B read per row) and
 // the compositing launch with its 40-56 B per ray of scattered accumulator traffic is gone: 9 / 29 us per iteration of the
 // 800x800 / 1080p frame (profiles/r4_*).
 // Work is dealt in CONTIGUOUS runs of groups, one run per wave (unit u = blockIdx.x * WAVES + wave), and a wave appends the
@@ -1444,7 +1444,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_frame_head(
     half_t* img = lds;
     Head4Scratch* sc = reinterpret_cast<Head4Scratch*>(lds + I::END) + w;
     FrameHeadScratch* fs = reinterpret_cast<FrameHeadScratch*>(reinterpret_cast<Head4Scratch*>(lds + I::END) + WAVES) + w;
-    {   // weights -> swizzled LDS image (k_nerf_head_fwd5)
+    {   // weights -> swizzled LDS image.  The head below is k_nerf_head_fwd5<true>'s, written out a second time ON PURPOSE: shared
+        // pieces cost that kernel 1.5-3.5 % ("shared bodies"); a change to the head is made in both
         constexpr int N1 = (4 * 1 * 64 + NTH - 1) / NTH, N2 = (4 * 2 * 64 + NTH - 1) / NTH, NO = (1 * 2 * 64 + NTH - 1) / NTH;
         uint4 b0[N1], b1[N2], b2[NO], c0[N1], c1[N2], c2[N2], c3[NO];
         stage_swizzled_issue<4, 1, NTH>(Ws, b0);
@@ -1563,26 +1564,19 @@ __global__ __launch_bounds__(64 * WAVES) void k_frame_head(
         // ---- composite_rays of the group's rays (raymarching.cu:948-1035; k_frame_composite of round 1-3, same statements)
         bool keep = false;
         if (valid) {
-            float ws = a0.x, d = a0.y, r = a0.z, gc = a0.w, b = a1.x, t = a1.y, wse = a1.z, de = a1.w;
+            lae::RayAcc a{a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
             uint32_t step = 0;
             while (step < n_step) {
                 const float e0 = fs->dl[lane + step][0];
                 if (e0 == 0) break;
-                const f4 v = *reinterpret_cast<const f4*>(&sc->q[lane + step][0]);
-                const float alpha = 1.0f - __expf(-v[0] * e0);
-                const float T = 1 - ws;
-                const float wgt = alpha * T;
-                ws += wgt;
-                if (EDIT) { if (fs->eo[lane + step]) { wse += wgt; de = fmaf(wgt, t, de); } }
-                t += fs->dl[lane + step][1];
-                d = fmaf(wgt, t, d);
-                r = fmaf(wgt, v[1], r); gc = fmaf(wgt, v[2], gc); b = fmaf(wgt, v[3], b);
-                if (T < fa.T_thresh) break;
+                const f4 v = *reinterpret_cast<const f4*>(&sc->q[lane + step][0]);         // sigma, rgb
+                if (lae::composite_infer_sample<EDIT>(a, v[0], e0, fs->dl[lane + step][1], v[1], v[2], v[3],
+                                                      EDIT && fs->eo[lane + step], fa.T_thresh)) break;
                 step++;
             }
             keep = step == n_step;
-            reinterpret_cast<float4*>(ap)[0] = make_float4(ws, d, r, gc);
-            reinterpret_cast<float4*>(ap)[1] = make_float4(b, keep ? t : a1.y, wse, de);      // rays_t moves only for rays that go on
+            reinterpret_cast<float4*>(ap)[0] = make_float4(a.ws, a.depth, a.r, a.g);
+            reinterpret_cast<float4*>(ap)[1] = make_float4(a.b, keep ? a.t : a1.y, a.wse, a.de);   // rays_t moves only for rays that go on
         }
         const unsigned long long km = __ballot(keep);
         if (keep) seg[kept + (uint32_t)__builtin_popcountll(km & ((1ull << lane) - 1ull))] = (int32_t)idx;

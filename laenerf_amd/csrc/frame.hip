@@ -655,6 +655,67 @@ __host__ __device__ constexpr uint32_t emit_img_rows(uint32_t n_step) { return (
 static_assert(emit_img_rows(3) % 16u == 0u && emit_img_rows(8) >= 64u * 8u + 4u * 10u, "image sizing");
 // xyz + delta rows (20 B each), 64 x (direction, samples held), edit flags
 __host__ __device__ constexpr uint32_t emit_img_floats(uint32_t rows) { return 5u * rows + 256u + rows / 4u; }
+// ---- what k_frame_emit's two paths and k_frame_emit8 share; each path keeps its own addressing (the wave's LDS image, the
+// 32-ray two-pass image, stores straight from the lanes)
+// first thread of the launch: publish the loop state, fill the host's mirror, zero the pad rows of the last 16-row MLP tile
+__device__ __forceinline__ void emit_publish(const FrameCtrl& c, FrameCtrl* __restrict__ cur, FrameMirror* __restrict__ mirror, uint64_t frame_id,
+                                             float* __restrict__ xyzs, float* __restrict__ dirs, float* __restrict__ deltas) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    *cur = c;
+    mirror->total_rows = c.total_rows; mirror->iters = c.iter; mirror->n_alive = c.n_alive; mirror->done = c.done;   // done last
+    __threadfence_system();
+    mirror->tag = frame_id;
+    for (uint32_t row = c.n_rows; row < ((c.n_rows + 15u) & ~15u); row++) {
+        xyzs[3 * (size_t)row] = 0.f; xyzs[3 * (size_t)row + 1] = 0.f; xyzs[3 * (size_t)row + 2] = 0.f;
+        dirs[3 * (size_t)row] = 0.f; dirs[3 * (size_t)row + 1] = 0.f; dirs[3 * (size_t)row + 2] = 0.f;
+        deltas[2 * (size_t)row] = 0.f; deltas[2 * (size_t)row + 1] = 0.f;
+    }
+}
+// a ray's look-ahead record: the ray, the samples held (of the n_step this iteration takes), where the previous sample ended,
+// the recorded times as two 16-byte loads (+ one 8-byte load of the edit flags), not a dependent load per sample
+struct EmitRec { Ray r; uint32_t have; float last_t; float st[FRAME_LA]; unsigned long long ste; };
+static_assert(FRAME_LA == 8, "EmitRec is filled from two float4 and one 64-bit word");
+template <bool EDIT>
+__device__ __forceinline__ EmitRec emit_load_record(const LookRec& in, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                    const MarchCfg& cfg, const float* __restrict__ noises, bool first_iter,
+                                                    uint32_t index, uint32_t n, uint32_t n_step) {
+    EmitRec q;
+    q.r = load_ray(rays_o, rays_d, index);
+    q.have = min(in.cnt[index], n_step);
+    q.last_t = in.tc[index];
+    if (first_iter) q.last_t = perturbed_start(cfg, q.last_t, noises, n);
+    const float4 ra = reinterpret_cast<const float4*>(in.t + (size_t)index * FRAME_LA)[0];
+    const float4 rb = reinterpret_cast<const float4*>(in.t + (size_t)index * FRAME_LA)[1];
+    q.st[0] = ra.x; q.st[1] = ra.y; q.st[2] = ra.z; q.st[3] = ra.w; q.st[4] = rb.x; q.st[5] = rb.y; q.st[6] = rb.z; q.st[7] = rb.w;
+    q.ste = 0ull;
+    if (EDIT) q.ste = *reinterpret_cast<const unsigned long long*>(in.e + (size_t)index * FRAME_LA);
+    return q;
+}
+// sample row j of a record (raymarching.cu:761-790 with the recorded time); a sample the record does not hold is a zero row
+// (the reference's buffers are torch.zeros).  Advances q.last_t.
+struct EmitRow { float x, y, z, dt, dl; uint8_t e; bool real; };
+template <bool EDIT>
+__device__ __forceinline__ EmitRow emit_row(const MarchCfg& cfg, EmitRec& q, uint32_t j) {
+    EmitRow o;
+    o.real = j < q.have;
+    const float t = q.st[j], dt = step_of(cfg, t), tn = t + dt;
+    o.x = o.real ? clampf(fmaf(t, q.r.dx, q.r.ox), -cfg.bound, cfg.bound) : 0.f;
+    o.y = o.real ? clampf(fmaf(t, q.r.dy, q.r.oy), -cfg.bound, cfg.bound) : 0.f;
+    o.z = o.real ? clampf(fmaf(t, q.r.dz, q.r.oz), -cfg.bound, cfg.bound) : 0.f;
+    o.dt = o.real ? dt : 0.f; o.dl = o.real ? tn - q.last_t : 0.f;
+    if (o.real) q.last_t = tn;
+    o.e = EDIT && o.real ? (uint8_t)(q.ste >> (8u * j)) : (uint8_t)0;
+    return o;
+}
+// go at the kernel's end: the workgroup holding the LAST ray of the list was dispatched last of those with work: when it is
+// done the kernel is (all but) done and the lookahead may start.  Nothing alive / loop over: workgroup 0 says so.
+// (The workgroup's vote, __syncthreads_or, stays in the kernels: inside a helper it reads the workgroup size from memory.)
+__device__ __forceinline__ bool emit_holds_last_ray(const FrameSlot& f, const FrameCtrl& c) {
+    return (f.has && f.n + 1u == f.n_alive) || ((c.done || f.n_alive == 0u) && blockIdx.x == 0);
+}
+__device__ __forceinline__ void emit_go(unsigned long long* __restrict__ go, unsigned long long go_value, int last) {
+    if (last && threadIdx.x == 0) { __threadfence(); __hip_atomic_store(go, go_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+}
 template <bool EDIT>
 __global__ __launch_bounds__(FRAME_BLOCK) void k_frame_emit(
     const FrameCtrl* __restrict__ prev, FrameCtrl* __restrict__ cur, FrameSegs sg, uint32_t N, uint32_t row_budget, uint32_t max_steps,
@@ -669,17 +730,7 @@ __global__ __launch_bounds__(FRAME_BLOCK) void k_frame_emit(
     const FrameSlot f = frame_locate(sg, N, wv, lane);
     const FrameCtrl c = frame_next_ctrl(*prev, f.n_alive, row_budget, max_steps, max_n_step);
     const uint32_t rpg = lae::frame_rays_per_group(max(c.n_step, 1u));
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        *cur = c;
-        mirror->total_rows = c.total_rows; mirror->iters = c.iter; mirror->n_alive = c.n_alive; mirror->done = c.done;   // done last
-        __threadfence_system();
-        mirror->tag = frame_id;
-        for (uint32_t row = c.n_rows; row < ((c.n_rows + 15u) & ~15u); row++) {     // pad rows of the last 16-row MLP tile
-            xyzs[3 * (size_t)row] = 0.f; xyzs[3 * (size_t)row + 1] = 0.f; xyzs[3 * (size_t)row + 2] = 0.f;
-            dirs[3 * (size_t)row] = 0.f; dirs[3 * (size_t)row + 1] = 0.f; dirs[3 * (size_t)row + 2] = 0.f;
-            deltas[2 * (size_t)row] = 0.f; deltas[2 * (size_t)row + 1] = 0.f;
-        }
-    }
+    emit_publish(c, cur, mirror, frame_id, xyzs, dirs, deltas);
     // n_step >= 3: a lane's rows are n_step x 32 bytes apart from its neighbour's, every store instruction of the loop below
     // scatters 64 x 12 (or 8) bytes over 64 x 32 x n_step bytes (the emit kernel of the late iterations, 8 rows per ray, took 28 us
     // for the rows the early ones write in 11).  The wave's rays are consecutive in the compact order, so their rows (and the
@@ -701,31 +752,18 @@ __global__ __launch_bounds__(FRAME_BLOCK) void k_frame_emit(
             const uint32_t row1 = sl == rpg - 1u ? gl * 64u + 64u : gl * 64u + (sl + 1u) * n_step;   // the last slot of a group takes its padding rows along
             const uint32_t nrows = row1 - row0;                // <= 64 n_step + 4 (groups + 1) <= img_rows
             if (f.has) {
-                const uint32_t index = f.index;
-                alive[f.n] = (int32_t)index;
-                const Ray r = load_ray(rays_o, rays_d, index);
-                const uint32_t have = min(in.cnt[index], n_step);
-                float last_t = in.tc[index];
-                if (sg.nu == 0) last_t = perturbed_start(cfg, last_t, noises, f.n);
-                const float4 ra = reinterpret_cast<const float4*>(in.t + (size_t)index * FRAME_LA)[0];
-                const float4 rb = reinterpret_cast<const float4*>(in.t + (size_t)index * FRAME_LA)[1];
-                const float st[FRAME_LA] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w};
-                unsigned long long ste = 0ull;
-                if (EDIT) ste = *reinterpret_cast<const unsigned long long*>(in.e + (size_t)index * FRAME_LA);
+                alive[f.n] = (int32_t)f.index;
+                EmitRec q = emit_load_record<EDIT>(in, rays_o, rays_d, cfg, noises, sg.nu == 0, f.index, f.n, n_step);
                 const uint32_t grp = f.n / rpg, slot = f.n - grp * rpg;
                 uint32_t lr = grp * 64u + slot * n_step - row0;
-                idr[4 * lane] = r.dx; idr[4 * lane + 1] = r.dy; idr[4 * lane + 2] = r.dz; idr[4 * lane + 3] = __uint_as_float(have);
+                idr[4 * lane] = q.r.dx; idr[4 * lane + 1] = q.r.dy; idr[4 * lane + 2] = q.r.dz; idr[4 * lane + 3] = __uint_as_float(q.have);
 #pragma unroll
                 for (uint32_t j = 0; j < FRAME_LA; j++, lr++) {
                     if (j >= n_step) break;                    // uniform
-                    const bool real = j < have;                // the reference's buffers are torch.zeros
-                    const float t = st[j], dt = step_of(cfg, t), tn = t + dt;
-                    ix[3 * lr] = real ? clampf(fmaf(t, r.dx, r.ox), -cfg.bound, cfg.bound) : 0.f;
-                    ix[3 * lr + 1] = real ? clampf(fmaf(t, r.dy, r.oy), -cfg.bound, cfg.bound) : 0.f;
-                    ix[3 * lr + 2] = real ? clampf(fmaf(t, r.dz, r.oz), -cfg.bound, cfg.bound) : 0.f;
-                    il[2 * lr] = real ? dt : 0.f; il[2 * lr + 1] = real ? tn - last_t : 0.f;
-                    if (real) last_t = tn;
-                    if (EDIT) ie[lr] = real ? (uint8_t)(ste >> (8u * j)) : (uint8_t)0;
+                    const EmitRow o = emit_row<EDIT>(cfg, q, j);
+                    ix[3 * lr] = o.x; ix[3 * lr + 1] = o.y; ix[3 * lr + 2] = o.z;
+                    il[2 * lr] = o.dt; il[2 * lr + 1] = o.dl;
+                    if (EDIT) ie[lr] = o.e;
                 }
                 if (slot == rpg - 1u)                          // the group's padding rows (n_step = 3, 5, 6, 7: at most 4)
                     for (uint32_t pr = rpg * n_step; pr < 64u; pr++) {
@@ -752,37 +790,18 @@ __global__ __launch_bounds__(FRAME_BLOCK) void k_frame_emit(
     } else
     if (!c.done && f.has) {
     const uint32_t n = f.n, n_step = c.n_step;
-    const uint32_t index = f.index;
-    alive[n] = (int32_t)index;
-    const Ray r = load_ray(rays_o, rays_d, index);
-    const uint32_t have = min(in.cnt[index], n_step);
-    float last_t = in.tc[index];
-    if (sg.nu == 0) last_t = perturbed_start(cfg, last_t, noises, n);
-    // the record as two 16-byte loads (+ one 8-byte load of the edit flags), not a dependent load per sample
-    const float4 ra = reinterpret_cast<const float4*>(in.t + (size_t)index * FRAME_LA)[0];
-    const float4 rb = reinterpret_cast<const float4*>(in.t + (size_t)index * FRAME_LA)[1];
-    const float st[FRAME_LA] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w};
-    unsigned long long ste = 0ull;
-    if (EDIT) ste = *reinterpret_cast<const unsigned long long*>(in.e + (size_t)index * FRAME_LA);
+    alive[n] = (int32_t)f.index;
+    EmitRec q = emit_load_record<EDIT>(in, rays_o, rays_d, cfg, noises, sg.nu == 0, f.index, n, n_step);
     const uint32_t grp = n / rpg, slot = n - grp * rpg;
     size_t row = (size_t)grp * 64u + (size_t)slot * n_step;
 #pragma unroll
     for (uint32_t j = 0; j < FRAME_LA; j++, row++) {
         if (j >= n_step) break;                            // uniform
-        if (j < have) {                                    // :761-790 with the recorded time
-            const float t = st[j], dt = step_of(cfg, t), tn = t + dt;
-            xyzs[3 * row] = clampf(fmaf(t, r.dx, r.ox), -cfg.bound, cfg.bound);
-            xyzs[3 * row + 1] = clampf(fmaf(t, r.dy, r.oy), -cfg.bound, cfg.bound);
-            xyzs[3 * row + 2] = clampf(fmaf(t, r.dz, r.oz), -cfg.bound, cfg.bound);
-            dirs[3 * row] = r.dx; dirs[3 * row + 1] = r.dy; dirs[3 * row + 2] = r.dz;
-            deltas[2 * row] = dt; deltas[2 * row + 1] = tn - last_t; last_t = tn;
-            if (EDIT) edit_occ[row] = (uint8_t)(ste >> (8u * j));
-        } else {                                           // the reference's buffers are torch.zeros
-            xyzs[3 * row] = 0.f; xyzs[3 * row + 1] = 0.f; xyzs[3 * row + 2] = 0.f;
-            dirs[3 * row] = 0.f; dirs[3 * row + 1] = 0.f; dirs[3 * row + 2] = 0.f;
-            deltas[2 * row] = 0.f; deltas[2 * row + 1] = 0.f;
-            if (EDIT) edit_occ[row] = 0;
-        }
+        const EmitRow o = emit_row<EDIT>(cfg, q, j);
+        xyzs[3 * row] = o.x; xyzs[3 * row + 1] = o.y; xyzs[3 * row + 2] = o.z;
+        dirs[3 * row] = o.real ? q.r.dx : 0.f; dirs[3 * row + 1] = o.real ? q.r.dy : 0.f; dirs[3 * row + 2] = o.real ? q.r.dz : 0.f;
+        deltas[2 * row] = o.dt; deltas[2 * row + 1] = o.dl;
+        if (EDIT) edit_occ[row] = o.e;
     }
     if (slot == rpg - 1u) {                                // the group's padding rows (n_step = 3, 5, 6, 7: at most 4)
         for (size_t pr = (size_t)grp * 64u + (size_t)rpg * n_step; pr < (size_t)grp * 64u + 64u; pr++) {
@@ -793,19 +812,15 @@ __global__ __launch_bounds__(FRAME_BLOCK) void k_frame_emit(
         }
     }
     }
-    if (go && !go_early) {
-        // the workgroup holding the LAST ray of the list was dispatched last of those with work: when it is done the kernel
-        // is (all but) done and the lookahead may start.  Nothing alive / loop over: workgroup 0 says so.
-        const int last = __syncthreads_or((f.has && f.n + 1u == f.n_alive) || ((c.done || f.n_alive == 0u) && blockIdx.x == 0));
-        if (last && threadIdx.x == 0) { __threadfence(); __hip_atomic_store(go, go_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
-    }
+    if (go && !go_early) emit_go(go, go_value, __syncthreads_or(emit_holds_last_ray(f, c)));
 }
 
 // k_frame_emit for iterations whose n_step is CERTAINLY 8 (the host's bound of n_alive already gives budget / bound >= 8, and 8
 // is the cap): rows of ray n are 8 n .. 8 n + 7, no padding.  The general kernel's LDS image for 64 rays x 8 samples is 13 KB per wave --
 // three workgroups per CU, 768 resident of the 1024 such a launch has: it ran in two rounds (22-24 us against 12-15 for n_step
 // 3-7).  Here a wave's rays go through a 32-ray image in two passes (6 KB per wave).  A separate kernel on purpose: the same two
-// passes inside k_frame_emit changed its register allocation and slowed EVERY path.
+// passes inside k_frame_emit changed its register allocation and slowed EVERY path.  What it shares with
+// k_frame_emit are the pieces above (emit_publish, emit_load_record, emit_row, emit_go); the two-pass image is its own.
 constexpr uint32_t EMIT8_ROWS = 256;                       // 32 rays x 8 samples
 constexpr uint32_t EMIT8_FLOATS = 5u * EMIT8_ROWS + 128u + EMIT8_ROWS / 4u;   // xyz + delta rows, 32 x (direction, samples held), edit flags
 template <bool EDIT>
@@ -821,17 +836,7 @@ __global__ __launch_bounds__(FRAME_BLOCK) void k_frame_emit8(
     if (go && go_early && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(go, go_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     const FrameSlot f = frame_locate(sg, N, wv, lane);
     const FrameCtrl c = frame_next_ctrl(*prev, f.n_alive, row_budget, max_steps, max_n_step);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        *cur = c;
-        mirror->total_rows = c.total_rows; mirror->iters = c.iter; mirror->n_alive = c.n_alive; mirror->done = c.done;   // done last
-        __threadfence_system();
-        mirror->tag = frame_id;
-        for (uint32_t row = c.n_rows; row < ((c.n_rows + 15u) & ~15u); row++) {     // pad rows of the last 16-row MLP tile
-            xyzs[3 * (size_t)row] = 0.f; xyzs[3 * (size_t)row + 1] = 0.f; xyzs[3 * (size_t)row + 2] = 0.f;
-            dirs[3 * (size_t)row] = 0.f; dirs[3 * (size_t)row + 1] = 0.f; dirs[3 * (size_t)row + 2] = 0.f;
-            deltas[2 * (size_t)row] = 0.f; deltas[2 * (size_t)row + 1] = 0.f;
-        }
-    }
+    emit_publish(c, cur, mirror, frame_id, xyzs, dirs, deltas);
     const unsigned long long hm = __ballot(f.has);
     if (!c.done && c.n_step == 8u && hm) {                     // (n_step == 8 by construction of the launch; valid lanes are a prefix of the wave)
         const uint32_t cnt = (uint32_t)__builtin_popcountll(hm);
@@ -839,23 +844,11 @@ __global__ __launch_bounds__(FRAME_BLOCK) void k_frame_emit8(
         float* ix = img; float* il = img + 3 * EMIT8_ROWS; float* idr = img + 5 * EMIT8_ROWS;
         uint8_t* ie = reinterpret_cast<uint8_t*>(img + 5 * EMIT8_ROWS + 128);
         const uint32_t n_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.n);
-        Ray r{};
-        uint32_t have = 0;
-        float last_t = 0.f;
-        float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
-        unsigned long long ste = 0ull;
+        EmitRec q{};
         if (f.has) {
-            const uint32_t index = f.index;
-            alive[f.n] = (int32_t)index;
-            r = load_ray(rays_o, rays_d, index);
-            have = min(in.cnt[index], 8u);
-            last_t = in.tc[index];
-            if (sg.nu == 0) last_t = perturbed_start(cfg, last_t, noises, f.n);
-            ra = reinterpret_cast<const float4*>(in.t + (size_t)index * FRAME_LA)[0];
-            rb = reinterpret_cast<const float4*>(in.t + (size_t)index * FRAME_LA)[1];
-            if (EDIT) ste = *reinterpret_cast<const unsigned long long*>(in.e + (size_t)index * FRAME_LA);
+            alive[f.n] = (int32_t)f.index;
+            q = emit_load_record<EDIT>(in, rays_o, rays_d, cfg, noises, sg.nu == 0, f.index, f.n, 8u);
         }
-        const float st[8] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w};
 #pragma unroll 1
         for (uint32_t h = 0; h < 2u; h++) {
             const uint32_t lane_lo = h * 32u;
@@ -863,19 +856,14 @@ __global__ __launch_bounds__(FRAME_BLOCK) void k_frame_emit8(
             const uint32_t cnt_h = min(cnt - lane_lo, 32u), row0 = (n_first + lane_lo) * 8u, nrows = cnt_h * 8u;
             if (f.has && (uint32_t)lane >= lane_lo && (uint32_t)lane < lane_lo + 32u) {
                 const uint32_t li = (uint32_t)lane - lane_lo;
-                idr[4 * li] = r.dx; idr[4 * li + 1] = r.dy; idr[4 * li + 2] = r.dz; idr[4 * li + 3] = __uint_as_float(have);
-                float lt = last_t;
+                idr[4 * li] = q.r.dx; idr[4 * li + 1] = q.r.dy; idr[4 * li + 2] = q.r.dz; idr[4 * li + 3] = __uint_as_float(q.have);
 #pragma unroll
-                for (uint32_t j = 0; j < 8u; j++) {
+                for (uint32_t j = 0; j < 8u; j++) {            // (a lane is in one of the two passes: q.last_t moves once)
                     const uint32_t lr = li * 8u + j;
-                    const bool real = j < have;                // the reference's buffers are torch.zeros
-                    const float t = st[j], dt = step_of(cfg, t), tn = t + dt;
-                    ix[3 * lr] = real ? clampf(fmaf(t, r.dx, r.ox), -cfg.bound, cfg.bound) : 0.f;
-                    ix[3 * lr + 1] = real ? clampf(fmaf(t, r.dy, r.oy), -cfg.bound, cfg.bound) : 0.f;
-                    ix[3 * lr + 2] = real ? clampf(fmaf(t, r.dz, r.oz), -cfg.bound, cfg.bound) : 0.f;
-                    il[2 * lr] = real ? dt : 0.f; il[2 * lr + 1] = real ? tn - lt : 0.f;
-                    if (real) lt = tn;
-                    if (EDIT) ie[lr] = real ? (uint8_t)(ste >> (8u * j)) : (uint8_t)0;
+                    const EmitRow o = emit_row<EDIT>(cfg, q, j);
+                    ix[3 * lr] = o.x; ix[3 * lr + 1] = o.y; ix[3 * lr + 2] = o.z;
+                    il[2 * lr] = o.dt; il[2 * lr + 1] = o.dl;
+                    if (EDIT) ie[lr] = o.e;
                 }
             }
             __builtin_amdgcn_wave_barrier();                    // wave-private image: one wave's LDS accesses execute in order
@@ -892,10 +880,7 @@ __global__ __launch_bounds__(FRAME_BLOCK) void k_frame_emit8(
             __builtin_amdgcn_wave_barrier();                    // the second pass overwrites the image
         }
     }
-    if (go && !go_early) {
-        const int last = __syncthreads_or((f.has && f.n + 1u == f.n_alive) || ((c.done || f.n_alive == 0u) && blockIdx.x == 0));
-        if (last && threadIdx.x == 0) { __threadfence(); __hip_atomic_store(go, go_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
-    }
+    if (go && !go_early) emit_go(go, go_value, __syncthreads_or(emit_holds_last_ray(f, c)));
 }
 
 // renderer.py:381-383: the accumulators go out to the caller's arrays with the background blend and the depth normalisation
@@ -1087,12 +1072,12 @@ hipStream_t frame_pick_side(hipStream_t s) {
         }
     hipStream_t best = nullptr;
     float best_us = 0.f;
+    for (int c = 0; c < FrameHost::MAX_CAND; c++) g_frame.last_probe_us[c] = -1.f;   // the record is of THIS probe: a candidate behind the one taken is "not probed", not the time an earlier caller stream measured
     for (int c = 0; c < FrameHost::MAX_CAND; c++) {
         if (c >= g_frame.n_cand) {
             if (hipStreamCreateWithPriority(&g_frame.cand[c], hipStreamNonBlocking, g_frame.later_prio) != hipSuccess) break;
             g_frame.n_cand = c + 1;
         }
-        g_frame.last_probe_us[c] = -1.f;
         if (!frame_probe_concurrent(s, g_frame.cand[c], spins)) continue;
         (void)frame_probe_handshake_us(s, g_frame.cand[c]);                  // first run: the queue wakes up, code objects load
         const float us = frame_probe_handshake_us(s, g_frame.cand[c]);

@@ -39,6 +39,24 @@ __host__ __device__ __forceinline__ uint32_t frame_rays_per_group(uint32_t n_ste
 // loads / stores per ray and iteration instead of six to eight scattered 4-byte ones
 struct __attribute__((aligned(16))) RayAcc { float ws, depth, r, g, b, t, wse, de; };
 static_assert(sizeof(RayAcc) == 32, "RayAcc layout");
+// One sample of composite_rays / composite_rays_distill (the body of the reference's serial loop) on a ray's running state:
+// -> true when the ray stops here (T below the threshold ends the ray AFTER the sample is taken).  The caller fetches the
+// sample and has looked at delta0 first: a zero delta ends the samples a ray holds, nothing is fetched for it.  Shared by
+// k_composite_infer (raymarching.hip: samples from the global arrays) and k_frame_head (ffmlp.hip: samples from the wave's
+// LDS scratch); compiled with -ffp-contract=off, the statement order is the reference's.
+template <bool EDIT>
+__device__ __forceinline__ bool composite_infer_sample(RayAcc& a, float sigma, float delta0, float delta1, float cr, float cg,
+                                                       float cb, bool edit, float T_thresh) {
+    const float alpha = 1.0f - __expf(-sigma * delta0);
+    const float T = 1 - a.ws;
+    const float w = alpha * T;
+    a.ws += w;
+    if (EDIT) { if (edit) { a.wse += w; a.de = fmaf(w, a.t, a.de); } }
+    a.t += delta1;
+    a.depth = fmaf(w, a.t, a.depth);
+    a.r = fmaf(w, cr, a.r); a.g = fmaf(w, cg, a.g); a.b = fmaf(w, cb, a.b);
+    return T < T_thresh;
+}
 struct FrameHeadArgs {
     const FrameCtrl* cur;            // this iteration's state
     const int32_t* alive;            // compact list of ray indices

@@ -745,7 +745,8 @@ __global__ void k_march_infer(uint32_t n_alive, uint32_t n_step, const int32_t* 
 }
 
 // ---------------------------------------------------------------- K11 / K12 (inference composite)
-// raymarching.cu:948-1035 and :1037-1142
+// raymarching.cu:948-1035 and :1037-1142.  Its own: the fetch from the global arrays and the write-back; the loop body is
+// lae::composite_infer_sample.
 template <bool EDIT>
 __global__ void k_composite_infer(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t* __restrict__ rays_alive,
                                   float* __restrict__ rays_t, const float* __restrict__ sigmas,
@@ -760,30 +761,21 @@ __global__ void k_composite_infer(uint32_t n_alive, uint32_t n_step, float T_thr
     const float* c = rgbs + 3 * (size_t)n * n_step;
     const float* dl = deltas + 2 * (size_t)n * n_step;
     const uint8_t* eo = EDIT ? edit_occ + (size_t)n * n_step : nullptr;
-    float t = rays_t[index];
-    float ws = weights_sum[index], d = depth[index];
-    float wse = 0, de = 0;
-    if (EDIT) { wse = weights_edit_sum[index]; de = depth_edit[index]; }
-    float r = image[3 * (size_t)index], g = image[3 * (size_t)index + 1], b = image[3 * (size_t)index + 2];
+    lae::RayAcc a{weights_sum[index], depth[index], image[3 * (size_t)index], image[3 * (size_t)index + 1], image[3 * (size_t)index + 2],
+                  rays_t[index], 0.f, 0.f};
+    if (EDIT) { a.wse = weights_edit_sum[index]; a.de = depth_edit[index]; }
     uint32_t step = 0;
     while (step < n_step) {
         const float d0 = dl[2 * step];
         if (d0 == 0) break;
-        const float alpha = 1.0f - __expf(-s[step] * d0);
-        const float T = 1 - ws;
-        const float w = alpha * T;
-        ws += w;
-        if (EDIT) { if (eo[step]) { wse += w; de = fmaf(w, t, de); } }
-        t += dl[2 * step + 1];
-        d = fmaf(w, t, d);
-        r = fmaf(w, c[3 * step], r); g = fmaf(w, c[3 * step + 1], g); b = fmaf(w, c[3 * step + 2], b);
-        if (T < T_thresh) break;
+        if (lae::composite_infer_sample<EDIT>(a, s[step], d0, dl[2 * step + 1], c[3 * step], c[3 * step + 1], c[3 * step + 2],
+                                              EDIT && eo[step], T_thresh)) break;           // (lae_common.h, shared with k_frame_head)
         step++;
     }
-    if (step < n_step) rays_alive[n] = -1; else rays_t[index] = t;
-    weights_sum[index] = ws; depth[index] = d;
-    if (EDIT) { weights_edit_sum[index] = wse; depth_edit[index] = de; }
-    image[3 * (size_t)index] = r; image[3 * (size_t)index + 1] = g; image[3 * (size_t)index + 2] = b;
+    if (step < n_step) rays_alive[n] = -1; else rays_t[index] = a.t;
+    weights_sum[index] = a.ws; depth[index] = a.depth;
+    if (EDIT) { weights_edit_sum[index] = a.wse; depth_edit[index] = a.de; }
+    image[3 * (size_t)index] = a.r; image[3 * (size_t)index + 1] = a.g; image[3 * (size_t)index + 2] = a.b;
 }
 
 // ---------------------------------------------------------------- alive-list compaction

@@ -420,6 +420,60 @@ def test_lookahead_variants_render_the_same_bits(bound, n):
     assert len(set(hashes.values())) == 1, hashes
 
 
+_AB_DISTILL_SCRIPT = r"""
+import hashlib, sys, numpy as np, torch
+sys.path.insert(0, {root!r}); sys.path.insert(0, {root!r} + "/tests")
+import test_gpu_frame as F
+from laenerf_amd import synthetic as S
+net, r = F.make(bound=1, seed=2)
+o, d = F.rays({n}, seed=7)
+edit = F.T(S.pack_bits_np(S.sphere_density_grid(radius=0.35, boxes=False), 10.0)) & r.density_bitfield
+KEYS = ("image", "depth", "depth_edit", "weights_edit", "weights", "x_term")
+with torch.autocast("cuda", dtype=torch.float16):
+    b = r.render_distill(o, d, edit, frame_loop=True)
+    a = r.render_distill(o, d, edit, frame_loop=False) if {oploop} else None
+torch.cuda.synchronize()
+h = hashlib.sha256()
+for k in KEYS:
+    h.update(b[k].float().contiguous().cpu().numpy().tobytes())
+print("HASH", h.hexdigest())
+print("EDITED", int((b["weights_edit"] > 0).sum()))
+if a is not None:
+    print("OPLOOP", " ".join(k for k in KEYS if np.array_equal(F.N(a[k]), F.N(b[k]))))
+"""
+AB_DISTILL_RAYS = 1000
+
+
+def test_emit_variants_render_the_same_distill_bits():
+    """The distill render (edit grid: k_frame_emit<true> / k_frame_emit8<true> / k_frame_head<true>) of test_frame_loop_distill's
+    scene in fresh child processes (the switches are read once per process): the default, where the late iterations -- the
+    host's bound of n_alive at or below an eighth of the row budget -- go through k_frame_emit8<true>, and LAE_FRAME_EMIT8=0,
+    where k_frame_emit<true> writes the same rows.  Same bits; and the default run equals the operator loop
+    (k_composite_infer<true>, eight samples per ray in the late iterations) array for array.
+    1000 rays.  The host takes k_frame_emit8 once its lagging bound of n_alive is at most an eighth of the row budget (n_lb >= 8),
+    i.e. at most 125 rays here; of the counts traced (1000 / 2000 / 4000) this is the smallest, and no smaller one was tried, so
+    it is an upper bound of the smallest count that reaches the kernel, not that count.  Emit launches of the default run (one kernel
+    trace of the child script per count on an MI355X; the counts move by a launch or two from run to run with the host's lag):
+    1000 rays, 97 iterations: k_frame_emit<true> 63, k_frame_emit8<true> 34, k_frame_emit<false> 0, k_frame_emit8<false> 0;
+    2000 rays: 64 / 29 / 0 / 0; 4000 rays: 66 / 28 / 0 / 0."""
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    hashes, keys = {}, None
+    for name, env, oploop in (("default", {}, 1), ("general emit kernel at 8 samples per ray", {"LAE_FRAME_EMIT8": "0"}, 0)):
+        out = subprocess.run([sys.executable, "-c", _AB_DISTILL_SCRIPT.format(root=ROOT, n=AB_DISTILL_RAYS, oploop=oploop)],
+                             capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
+        lines = {l.split(" ", 1)[0]: l.split(" ", 1)[1] for l in out.stdout.splitlines() if l.startswith(("HASH ", "EDITED ", "OPLOOP "))}
+        assert out.returncode == 0 and "HASH" in lines, (name, out.stdout[-1000:], out.stderr[-2000:])
+        assert int(lines["EDITED"]) > 0, name
+        hashes[name] = lines["HASH"]
+        if oploop:
+            keys = lines["OPLOOP"].split()
+    assert len(set(hashes.values())) == 1, hashes
+    assert keys == ["image", "depth", "depth_edit", "weights_edit", "weights", "x_term"], keys
+
+
 def _degrade_child(env):
     import json
     import os

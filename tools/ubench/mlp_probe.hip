@@ -11,7 +11,7 @@ extern "C" int lae_loss_finish(const float*, uint32_t, uint32_t, const float*, f
 int main(int argc, char** argv) {
     const uint32_t M = argc > 1 ? (uint32_t)atoi(argv[1]) : 257792u;
     const int bpc = argc > 2 ? atoi(argv[2]) : 1;
-    const int variant = argc > 3 ? atoi(argv[3]) : 4;          // 4: k_nerf_head_fwd4; 54 / 58: k_nerf_head_fwd5 with 4 / 8 waves per workgroup
+    const int variant = argc > 3 ? atoi(argv[3]) : 54;         // 54 / 58: k_nerf_head_fwd5 with 4 / 8 waves per workgroup; 100 / 101: backward probe
     std::vector<uint16_t> h_enc((size_t)M * 32), h_ws(64 * 112), h_wc(64 * 176);
     std::vector<float> h_dirs((size_t)M * 3);
     uint32_t x = 1;
@@ -37,9 +37,8 @@ int main(int argc, char** argv) {
     for (int rep = 0; rep < 3; rep++) {
         hipEventRecord(e0);
         for (int k = 0; k < 10; k++) {
-            if (variant == 54) k_nerf_head_fwd5<true, 4><<<blocks, 256, lds5>>>(enc, dirs, ws, wc, n_tiles, 1.0f, hout, sig, rgb, 1, nullptr, M);
-            else if (variant == 58) k_nerf_head_fwd5<true, 8><<<blocks, 512, lds5>>>(enc, dirs, ws, wc, n_tiles, 1.0f, hout, sig, rgb, 1, nullptr, M);
-            else k_nerf_head_fwd4<true><<<blocks, 256, 4 * sizeof(Head4Scratch)>>>(enc, dirs, ws, wc, n_tiles, 1.0f, hout, sig, rgb, 1, nullptr, M);
+            if (variant == 58) k_nerf_head_fwd5<true, 8><<<blocks, 512, lds5>>>(enc, dirs, ws, wc, n_tiles, 1.0f, hout, sig, rgb, 1, nullptr, M);
+            else k_nerf_head_fwd5<true, 4><<<blocks, 256, lds5>>>(enc, dirs, ws, wc, n_tiles, 1.0f, hout, sig, rgb, 1, nullptr, M);
         }
         hipEventRecord(e1); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1);
