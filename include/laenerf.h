@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi16"
+#define LAE_ABI_TAG "abi17"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -306,6 +306,53 @@ LAE_API int lae_composite_rays_train_step_depth(const float* sigmas, const float
                                         float* partials, int defer_loss, const void* depth_src, int depth_dtype,
                                         const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
                                         float* depth_partials, void* stream);
+
+/* The distortion regularizer of mip-NeRF 360 on the ray's weights, in the O(n) form of the reference's loss.py:29-76
+ * (eff_distloss(w, m, interval) with m = t_k and interval = deltas[k,0]; its CUDA-ray path never calls it), inside the compositing
+ * kernels.  Over the samples the forward uses (k = 0 .. the early-stop sample, included), w_k = alpha_k T_k, t_k = the running sum
+ * of deltas[.,1] including sample k, lengths in the march's own units (NOT divided by far - near):
+ *   l_ray = (1/3) sum_k delta0_k w_k^2 + 2 sum_k w_k (t_k W_<k - WT_<k)        W_<k = sum_{j<k} w_j,  WT_<k = sum_{j<k} w_j t_j
+ *         = (1/3) sum_k delta0_k w_k^2 + sum_{i,j} w_i w_j |t_i - t_j|
+ *
+ * lae_composite_rays_train_forward_blend plus the output dist [N] = l_ray (0 for a ray without samples); every other output has
+ * the bits of lae_composite_rays_train_forward_blend. */
+LAE_API int lae_composite_rays_train_forward_blend_dist(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                                uint32_t M, uint32_t N, float T_thresh, const float* nears, const float* fars,
+                                                const float* bg_rays, float bg_r, float bg_g, float bg_b, float* weights_sum,
+                                                float* depth, float* image, float* depth_out, float* image_out, float* dist,
+                                                void* stream);
+/* lae_composite_rays_train_backward_blend_depth that also takes grad_dist [N], the gradient of l_ray, and dist [N], the forward's
+ * l_ray.  With W = weights_sum, D = depth and W_k, WT_k the running sums including sample k:
+ *   q_k = d l_ray / d w_k = (2/3) delta0_k w_k + 2 (t_k (W_<k - (W - W_k)) + ((D - WT_k) - WT_<k))
+ *   grad_sigmas_k += delta0_k * grad_dist * (T_post_k * q_k - (Q - Q_k)),   Q_k = sum_{j<=k} q_j w_j,   Q = 2 * dist
+ * (l_ray is homogeneous of degree 2 in w) inside the same bracket as the colour terms; grad_rgbs is unchanged.  grad_depth may be
+ * NULL: no depth gradient.  depth [N], the forward's raw depth, is always read (it is the D of q_k).  A ray whose grad_dist is zero
+ * has the bits of lae_composite_rays_train_backward_blend_depth (of _ex without grad_depth).  grad_scale multiplies grad_dist too. */
+LAE_API int lae_composite_rays_train_backward_blend_dist(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
+                                                 const float* rgbs, const float* deltas, const int32_t* rays,
+                                                 const float* weights_sum, const float* image, uint32_t M, uint32_t N,
+                                                 float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
+                                                 const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
+                                                 float* grad_rgbs, const float* grad_depth, const float* depth, const float* grad_dist,
+                                                 const float* dist, void* stream);
+/* lae_composite_rays_train_step_depth with the distortion term in the same launch:
+ *   loss = MSE [+ lambda * mean(res^2)] + dist_lambda * L_dist,   L_dist = (1/N) sum over ALL N rays of l_ray
+ *   dist[ray] = l_ray (0 without samples),  grad_dist[ray] = g = (dist_lambda / N) * *scale, carried through the backward as
+ *   lae_composite_rays_train_backward_blend_dist does; dist_value_only != 0 computes the value and forces g = 0.  With g == 0
+ *   (dist_lambda == 0 or dist_value_only) the sample gradients are those of lae_composite_rays_train_step[_depth] bit for bit.
+ * depth_src == NULL switches the depth term off: the other depth arguments are then not looked at.
+ * partials[b] additionally receive 3 * dist_lambda * sum(l_ray), so every finisher (n_elem = 3 N) yields the total loss unchanged;
+ * dist_partials [cdiv(N, 4)] receive sum(l_ray): lae_loss_finish(dist_partials, cdiv(N, 4), N, NULL, out) gives L_dist alone.
+ * dist_lambda: finite, >= 0 (LAE_EINVAL otherwise). */
+LAE_API int lae_composite_rays_train_step_dist(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                       uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
+                                       float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
+                                       const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
+                                       float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
+                                       float* partials, int defer_loss, const void* depth_src, int depth_dtype,
+                                       const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
+                                       float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
+                                       float* dist_partials, void* stream);
 
 /* raymarching.cu:929-936 */
 LAE_API int lae_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive,

@@ -40,6 +40,9 @@ SIGNATURES = {
     "lae_composite_rays_train_step": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
     "lae_composite_rays_train_step_depth": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, vp],
     "lae_composite_rays_train_backward_blend_depth": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
+    "lae_composite_rays_train_forward_blend_dist": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
+    "lae_composite_rays_train_step_dist": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, f32, i32, vp, vp, vp, vp],
+    "lae_composite_rays_train_backward_blend_dist": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_loss_finish": [vp, u32, u32, vp, vp, vp],
     "lae_composite_rays_train_backward_blend": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp],
     "lae_composite_rays_train_backward_blend_ex": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp],
@@ -149,7 +152,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi16"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi17"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

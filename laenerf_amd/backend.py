@@ -250,15 +250,32 @@ class _RayMarching:
             "composite_rays_train_forward_blend")
 
     @staticmethod
+    def composite_rays_train_forward_blend_dist(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears, fars, bg_rays, bg, weights_sum,
+                                                depth, image, depth_out, image_out, dist):
+        """composite_rays_train_forward_blend that also writes dist [N], the distortion l_ray of every ray (include/laenerf.h)"""
+        ts = (sigmas, rgbs, deltas, rays, nears, fars, bg_rays, weights_sum, depth, image, depth_out, image_out, dist)
+        need_cuda(*ts); need_contig(*ts)
+        _need_f32(sigmas, rgbs, deltas, nears, fars, bg_rays, weights_sum, depth, image, depth_out, image_out, dist)
+        if dist.numel() < N:
+            raise RuntimeError("composite_rays_train_forward_blend_dist: dist needs a value per ray")
+        check(_lib.load().lae_composite_rays_train_forward_blend_dist(
+            ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1],
+            bg[2], ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out), ptr(dist), stream()),
+            "composite_rays_train_forward_blend_dist")
+
+    @staticmethod
     def composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears, fars, bg_rays, bg, rows_end, target, scale,
                                   weights_sum, depth, image, depth_out, image_out, grad_image, grad_sigmas, grad_rgbs, loss_out,
-                                  partials, defer_loss=False, depth_sup=None):
+                                  partials, defer_loss=False, depth_sup=None, dist_sup=None):
         """MI355X extension: compositing forward (+ blend) + MSE criterion + compositing backward in one launch.
         defer_loss: the loss VALUE (loss_out, NaN until then) is summed later -- by the fused head's backward, which takes it
         along in its reduction launch, or by flush_pending_loss() (laenerf_amd.optim.FusedAdam.backward / step call it).
         depth_sup: None, or (depth_src, depth_inds, weight, value_only, grad_depth, depth_partials): the depth criterion of
         lae_composite_rays_train_step_depth in the same launch (depth_src fp16 / fp32, depth_inds int64 or None); the loss value
-        then holds MSE + weight * depth MSE whoever finishes it."""
+        then holds MSE + weight * depth MSE whoever finishes it.
+        dist_sup: None, or (weight, value_only, dist, grad_dist, dist_partials): the distortion term of
+        lae_composite_rays_train_step_dist in the same launch, with or without depth_sup; the loss value then also holds
+        weight * mean(l_ray)."""
         ts = (sigmas, rgbs, deltas, rays, nears, fars, bg_rays, rows_end, target, scale, weights_sum, depth, image, depth_out,
               image_out, grad_image, grad_sigmas, grad_rgbs, loss_out, partials)
         need_cuda(*ts); need_contig(*ts)
@@ -269,9 +286,8 @@ class _RayMarching:
         args = (ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1], bg[2],
                 ptr(rows_end), ptr(target), ptr(scale), ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out),
                 ptr(grad_image), ptr(grad_sigmas), ptr(grad_rgbs), ptr(loss_out), ptr(partials), int(bool(defer_loss)))
-        if depth_sup is None:
-            check(_lib.load().lae_composite_rays_train_step(*args, stream()), "composite_rays_train_step")
-        else:
+        dargs = (None, 0, None, 0.0, 0, None, None)       # lae_composite_rays_train_step_dist without a depth term
+        if depth_sup is not None:
             depth_src, depth_inds, weight, value_only, grad_depth, depth_partials = depth_sup
             ds = (depth_src, depth_inds, grad_depth, depth_partials)
             need_cuda(*ds); need_contig(*ds); _need_f32(grad_depth, depth_partials)
@@ -283,9 +299,21 @@ class _RayMarching:
                 raise RuntimeError("composite_rays_train_step: without depth_inds the depth needs a value per ray")
             if grad_depth.numel() < N or depth_partials.numel() < (N + 3) // 4:
                 raise RuntimeError("composite_rays_train_step: grad_depth needs N, depth_partials cdiv(N, 4) floats")
-            check(_lib.load().lae_composite_rays_train_step_depth(
-                *args, ptr(depth_src), _DEPTH_DTYPES[depth_src.dtype], ptr(depth_inds), float(weight), int(bool(value_only)),
-                ptr(grad_depth), ptr(depth_partials), stream()), "composite_rays_train_step_depth")
+            dargs = (ptr(depth_src), _DEPTH_DTYPES[depth_src.dtype], ptr(depth_inds), float(weight), int(bool(value_only)),
+                     ptr(grad_depth), ptr(depth_partials))
+        if dist_sup is not None:
+            dist_weight, dist_value_only, dist, grad_dist, dist_partials = dist_sup
+            xs = (dist, grad_dist, dist_partials)
+            need_cuda(*xs); need_contig(*xs); _need_f32(*xs)
+            if any(x is None for x in xs) or dist.numel() < N or grad_dist.numel() < N or dist_partials.numel() < (N + 3) // 4:
+                raise RuntimeError("composite_rays_train_step: dist and grad_dist need N, dist_partials cdiv(N, 4) floats")
+            check(_lib.load().lae_composite_rays_train_step_dist(
+                *args, *dargs, float(dist_weight), int(bool(dist_value_only)), ptr(dist), ptr(grad_dist), ptr(dist_partials), stream()),
+                "composite_rays_train_step_dist")
+        elif depth_sup is not None:
+            check(_lib.load().lae_composite_rays_train_step_depth(*args, *dargs, stream()), "composite_rays_train_step_depth")
+        else:
+            check(_lib.load().lae_composite_rays_train_step(*args, stream()), "composite_rays_train_step")
         if defer_loss and N > 0:                      # N == 0: the library returned at once, there is nothing to finish
             capturing = torch.cuda.is_current_stream_capturing()
             key = _loss_key(grad_sigmas)
@@ -322,6 +350,19 @@ class _RayMarching:
             raise RuntimeError("composite_rays_train_backward_blend_depth: grad_depth and depth need a value per ray")
         check(_lib.load().lae_composite_rays_train_backward_blend_depth(*args, ptr(grad_depth), ptr(depth), stream()),
               "composite_rays_train_backward_blend_depth")
+
+    @staticmethod
+    def composite_rays_train_backward_blend_dist(grad_weights_sum, grad_image, grad_depth, grad_dist, sigmas, rgbs, deltas, rays,
+                                                 weights_sum, depth, dist, image, M, N, T_thresh, bg_rays, bg, rows_end, grad_sigmas,
+                                                 grad_rgbs, grad_scale=None):
+        """composite_rays_train_backward_blend_depth that also carries grad_dist [N], the gradient of the forward's dist [N];
+        grad_depth may be None (no depth gradient), depth [N] is always needed"""
+        args = _backward_blend_args(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, bg_rays,
+                                    bg, rows_end, grad_sigmas, grad_rgbs, grad_scale, grad_depth, depth, grad_dist, dist)
+        if any(x is None or x.numel() < N for x in (depth, grad_dist, dist)) or (grad_depth is not None and grad_depth.numel() < N):
+            raise RuntimeError("composite_rays_train_backward_blend_dist: depth, grad_dist, dist (and grad_depth) need a value per ray")
+        check(_lib.load().lae_composite_rays_train_backward_blend_dist(*args, ptr(grad_depth), ptr(depth), ptr(grad_dist), ptr(dist),
+                                                                       stream()), "composite_rays_train_backward_blend_dist")
 
     @staticmethod
     def loss_finish(partials, n_part, n_elem, scale, loss_out):

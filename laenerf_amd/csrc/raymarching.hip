@@ -364,11 +364,30 @@ struct Dense { const float* bg_rays; float bg[3]; const uint32_t* rows_end; cons
 // the kernels they were: every addition is behind `if constexpr`.
 struct DepthGrad { const float* grad_depth; const float* depth; };
 
-// per-ray state of the DEPTH flavours: g_D, the ray's D, the running t and D_k, the squared residual; `on` = g_D != 0 (uniform over
-// the wave: one ray is one wave).  Empty without DEPTH.
-template <bool DEPTH> struct DepthState { float gD = 0.0f, df = 0.0f, t = 0.0f, dsum = 0.0f, dq = 0.0f; bool on = false; };
+// per-ray state of the DEPTH flavours: g_D, the ray's D, the squared residual; `on` = g_D != 0 (uniform over the wave: one ray is
+// one wave).  Empty without DEPTH.  The running t and D_k live in BwdRun: the DIST flavours carry the same two.
+template <bool DEPTH> struct DepthState { float gD = 0.0f, df = 0.0f, dq = 0.0f; bool on = false; };
 template <> struct DepthState<false> {};
-struct NoArg {};                                          // the trailing kernel argument of the flavours without DEPTH
+struct NoArg {};                                          // a trailing kernel argument of the flavours without DEPTH / DIST
+
+// DIST: the mip-NeRF-360 distortion of the ray's weights in its O(n) form (the reference's loss.py:29-76, eff_distloss(w, t, delta0),
+// which its CUDA-ray path never calls), over the samples the forward uses, lengths in the march's own units (not divided by
+// far - near: m = t_k, interval = deltas[k,0], what that function would be handed here):
+//   l_ray = (1/3) sum_k delta0_k w_k^2 + 2 sum_k w_k (t_k W_<k - WT_<k),   W_<k = sum_{j<k} w_j,  WT_<k = sum_{j<k} w_j t_j
+// Forward: the two sums of the pass (w, w * t) become scans, whose lane below gives the exclusive prefixes, and one more sum.
+// Backward, with W = weights_sum, D = the raw depth and W_k, WT_k the prefixes including sample k:
+//   q_k = dl / dw_k = (2/3) delta0_k w_k + 2 (t_k (W_<k - (W - W_k)) + ((D - WT_k) - WT_<k))
+//   grad_sigmas_k += delta0_k * g * (T_post_k * q_k - (Q - Q_k)),   Q_k = sum_{j<=k} q_j w_j,   g = d loss / d l_ray
+// -- the colour rule with q in place of the colour; grad_rgbs does not change.  l is homogeneous of degree 2 in w, so Q = 2 l: the
+// backward needs W, D and l of the forward and nothing else.  Scans per pass: t and w * t (shared with DEPTH), w, q * w.  A ray whose
+// g is zero takes the path without them (uniform over its wave) and has the bits of the flavour without DIST; the DIST = false
+// instantiations are the kernels they were.
+struct DistGrad { const float* grad_dist; const float* dist; const float* depth; };
+// per-ray state of the DIST backward: g, Q = 2 l, W, D, the running W_k and Q_k; `on` = g != 0.  Empty without DIST.
+template <bool DIST> struct DistState { float g = 0.0f, qf = 0.0f, wf = 0.0f, df = 0.0f, w = 0.0f, q = 0.0f; bool on = false; };
+template <> struct DistState<false> {};
+template <bool DIST> struct DistAcc { float l = 0.0f; };  // the forward's l_ray
+template <> struct DistAcc<false> {};
 
 // ---- the pieces every training compositing kernel is made of.  The kernels keep their loops and decide when a pass is loaded (the
 // step kernel requests the next pass before it scans the current one); the per-pass arithmetic exists once, here.
@@ -417,11 +436,20 @@ __device__ __forceinline__ PassW pass_weights(const Sample& s, bool& valid, floa
 
 // one forward pass: adds the pass to the ray's sums, carries T and t; -> the ray stopped in this pass
 struct FwdAcc { float r, g, b, d, ws; };
-__device__ __forceinline__ bool composite_fwd_pass(const Sample& s, bool valid, float T_thresh, int lane, float& T, float& t, FwdAcc& a) {
+template <bool DIST>
+__device__ __forceinline__ bool composite_fwd_pass(const Sample& s, bool valid, float T_thresh, int lane, float& T, float& t, FwdAcc& a,
+                                                   DistAcc<DIST>& xa) {
     const PassW p = pass_weights(s, valid, T, T_thresh, lane);
     const float tk = t + wave_scan_add(s.d1, lane);
     a.r += wave_sum(p.w * s.c0); a.g += wave_sum(p.w * s.c1); a.b += wave_sum(p.w * s.c2);
-    a.d += wave_sum(p.w * tk); a.ws += wave_sum(p.w);
+    if constexpr (DIST) {                                                   // the two sums below as scans: same bits in lane 63
+        const float dk = wave_scan_add(p.w * tk, lane), wk = wave_scan_add(p.w, lane);
+        const float d_lt = a.d + wave_prev(dk, 0.0f), w_lt = a.ws + wave_prev(wk, 0.0f);     // WT_<k, W_<k
+        xa.l += wave_sum(p.w * ((1.0f / 3.0f) * s.d0 * p.w + 2.0f * (tk * w_lt - d_lt)));
+        a.d += wave_last(dk); a.ws += wave_last(wk);
+    } else {
+        a.d += wave_sum(p.w * tk); a.ws += wave_sum(p.w);
+    }
     if (p.done) return true;
     T *= wave_last(p.incl);
     t = wave_last(tk);
@@ -447,27 +475,38 @@ __device__ __forceinline__ void store_blend(const Blend& bl, uint32_t index, con
 // what the backward of a ray holds fixed over its passes (the colour gradient, the ray's colour, the weights_sum term of the
 // bracket) and what it carries from pass to pass
 struct BwdRay { float g0, g1, g2, rf, gf, bf, tail; };
-struct BwdRun { float T = 1.0f, r = 0.0f, g = 0.0f, b = 0.0f; };
+struct BwdRun { float T = 1.0f, r = 0.0f, g = 0.0f, b = 0.0f, t = 0.0f, d = 0.0f; };    // t, d (= D_k): DEPTH / DIST rays only
 __device__ __forceinline__ void zero_grad_row(float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, size_t i) {
     grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f; grad_sigmas[i] = 0.f;
 }
 
 // one backward pass: writes the gradient rows of the pass (row i in this lane), carries T and the running sums; -> the ray stopped
-// in this pass.  With DEPTH and ds.on, s.d1 must be loaded.
-template <bool DENSE, bool DEPTH>
+// in this pass.  With DEPTH and ds.on, or DIST and xs.on, s.d1 must be loaded.
+template <bool DENSE, bool DEPTH, bool DIST>
 __device__ __forceinline__ bool composite_bwd_pass(const Sample& s, bool valid, size_t i, const BwdRay& c, float T_thresh, int lane,
-                                                   BwdRun& st, DepthState<DEPTH>& ds, float* __restrict__ grad_sigmas,
-                                                   float* __restrict__ grad_rgbs) {
+                                                   BwdRun& st, DepthState<DEPTH>& ds, DistState<DIST>& xs,
+                                                   float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs) {
     const bool in_ray = valid;
     const PassW p = pass_weights(s, valid, st.T, T_thresh, lane);
     const float rk = st.r + wave_scan_add(p.w * s.c0, lane);                // running sums INCLUDING this sample
     const float gk = st.g + wave_scan_add(p.w * s.c1, lane);
     const float bk = st.b + wave_scan_add(p.w * s.c2, lane);
-    [[maybe_unused]] float tk = 0.0f, dk = 0.0f;
-    if constexpr (DEPTH) {
-        if (ds.on) {
-            tk = ds.t + wave_scan_add(s.d1, lane);                          // t_k, as the forward
-            dk = ds.dsum + wave_scan_add(p.w * tk, lane);                   // D_k, including this sample
+    [[maybe_unused]] float tk = 0.0f, dk = 0.0f, wk = 0.0f, qk = 0.0f, Qk = 0.0f;
+    [[maybe_unused]] bool with_t = false;
+    if constexpr (DEPTH) with_t = ds.on;
+    if constexpr (DIST) with_t = with_t || xs.on;
+    if constexpr (DEPTH || DIST) {
+        if (with_t) {
+            tk = st.t + wave_scan_add(s.d1, lane);                          // t_k, as the forward
+            dk = st.d + wave_scan_add(p.w * tk, lane);                      // D_k, including this sample
+        }
+    }
+    if constexpr (DIST) {
+        if (xs.on) {
+            wk = xs.w + wave_scan_add(p.w, lane);                           // W_k, including this sample
+            const float w_lt = wave_prev(wk, xs.w), d_lt = wave_prev(dk, st.d);
+            qk = (2.0f / 3.0f) * s.d0 * p.w + 2.0f * (tk * (w_lt - (xs.wf - wk)) + ((xs.df - dk) - d_lt));
+            Qk = xs.q + wave_scan_add(qk * p.w, lane);
         }
     }
     if (valid) {
@@ -477,6 +516,9 @@ __device__ __forceinline__ bool composite_bwd_pass(const Sample& s, bool valid, 
         if constexpr (DEPTH) {
             if (ds.on) br = br + ds.gD * (p.T_post * tk - (ds.df - dk));
         }
+        if constexpr (DIST) {
+            if (xs.on) br = br + xs.g * (p.T_post * qk - (xs.qf - Qk));
+        }
         grad_sigmas[i] = s.d0 * br;
     } else if (DENSE && in_ray) {
         zero_grad_row(grad_sigmas, grad_rgbs, i);
@@ -484,32 +526,37 @@ __device__ __forceinline__ bool composite_bwd_pass(const Sample& s, bool valid, 
     if (p.done) return true;
     st.T *= wave_last(p.incl);
     st.r = wave_last(rk); st.g = wave_last(gk); st.b = wave_last(bk);
-    if constexpr (DEPTH) {
-        if (ds.on) { ds.t = wave_last(tk); ds.dsum = wave_last(dk); }
+    if constexpr (DEPTH || DIST) {
+        if (with_t) { st.t = wave_last(tk); st.d = wave_last(dk); }
+    }
+    if constexpr (DIST) {
+        if (xs.on) { xs.w = wave_last(wk); xs.q = wave_last(Qk); }
     }
     return false;
 }
 
-template <bool BLEND>
+template <bool BLEND, bool DIST = false>
 __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_fwd(
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
     const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum,
-    float* __restrict__ depth, float* __restrict__ image, Blend bl) {
+    float* __restrict__ depth, float* __restrict__ image, Blend bl, std::conditional_t<DIST, float*, NoArg> dist) {
     const uint32_t n = blockIdx.x * COMP_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // one ray per wave: scalar
     if (n >= N) return;
     const int lane = threadIdx.x & 63;
     const RayHead h = load_ray_head(rays, n, M);
     FwdAcc a{0.f, 0.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] DistAcc<DIST> xa;
     if (h.has) {
         float T = 1.0f, t = 0.0f;
         for (uint32_t base = 0; base < h.num_steps; base += 64) {
             const uint32_t k = base + lane;
             const Sample s = load_sample(sigmas, rgbs, deltas, h, k, true);
-            if (composite_fwd_pass(s, k < h.num_steps, T_thresh, lane, T, t, a)) break;
+            if (composite_fwd_pass<DIST>(s, k < h.num_steps, T_thresh, lane, T, t, a, xa)) break;
         }
     }
     if (lane == 0) {
         store_ray(weights_sum, depth, image, h.index, a);
+        if constexpr (DIST) dist[h.index] = xa.l;
         if constexpr (BLEND) {
             float o[3];
             blend_colour(ray_bg(bl.bg_rays, bl.bg, h.index), a, o);
@@ -518,12 +565,13 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_fwd(
     }
 }
 
-template <bool DENSE, bool DEPTH = false>
+template <bool DENSE, bool DEPTH = false, bool DIST = false>
 __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
     const float* __restrict__ grad_ws, const float* __restrict__ grad_image, const float* __restrict__ sigmas,
     const float* __restrict__ rgbs, const float* __restrict__ deltas, const int32_t* __restrict__ rays,
     const float* __restrict__ weights_sum, const float* __restrict__ image, uint32_t M, uint32_t N, float T_thresh,
-    float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, Dense dn, std::conditional_t<DEPTH, DepthGrad, NoArg> dg) {
+    float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, Dense dn, std::conditional_t<DEPTH, DepthGrad, NoArg> dg,
+    std::conditional_t<DIST, DistGrad, NoArg> xg) {
     const uint32_t n = blockIdx.x * COMP_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // one ray per wave: scalar
     if (n >= N) return;
     const int lane = threadIdx.x & 63;
@@ -539,11 +587,14 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
     float g0 = grad_image[3 * (size_t)index], g1 = grad_image[3 * (size_t)index + 1], g2 = grad_image[3 * (size_t)index + 2];
     [[maybe_unused]] DepthState<DEPTH> ds;
     if constexpr (DEPTH) { ds.gD = dg.grad_depth[index]; ds.df = dg.depth[index]; }
+    [[maybe_unused]] DistState<DIST> xs;
+    if constexpr (DIST) { xs.g = xg.grad_dist[index]; xs.qf = 2.0f * xg.dist[index]; xs.wf = weights_sum[index]; xs.df = xg.depth[index]; }
     if constexpr (DENSE) {
         if (dn.grad_scale) {                               // fused criterion: upstream d(loss) arrives as a device scalar
             const float gs = dn.grad_scale[0];
             g0 *= gs; g1 *= gs; g2 *= gs; gws *= gs;
             if constexpr (DEPTH) ds.gD *= gs;
+            if constexpr (DIST) xs.g *= gs;
         }
         const float* bg = ray_bg(dn.bg_rays, dn.bg, index);
         gws = gws - ((g0 * bg[0] + g1 * bg[1]) + g2 * bg[2]);
@@ -552,6 +603,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
                    gws * (1 - weights_sum[index])};
     bool with_t = false;
     if constexpr (DEPTH) with_t = ds.on = ds.gD != 0.0f;
+    if constexpr (DIST) { xs.on = xs.g != 0.0f; with_t = with_t || xs.on; }
     BwdRun st;
     bool stopped = false;
     for (uint32_t base = 0; base < h.num_steps; base += 64) {
@@ -562,7 +614,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
             continue;
         }
         const Sample s = load_sample(sigmas, rgbs, deltas, h, k, with_t);
-        if (composite_bwd_pass<DENSE, DEPTH>(s, k < h.num_steps, i, c, T_thresh, lane, st, ds, grad_sigmas, grad_rgbs)) {
+        if (composite_bwd_pass<DENSE, DEPTH, DIST>(s, k < h.num_steps, i, c, T_thresh, lane, st, ds, xs, grad_sigmas, grad_rgbs)) {
             if (!DENSE) break;
             stopped = true;
         }
@@ -587,15 +639,26 @@ struct StepLoss { const float* target; const float* scale; float* grad_image; fl
 // depth_partials[] receive sum(res^2) (lae_loss_finish with n_elem = N gives the depth term alone).
 struct DepthLoss { const void* src; int dtype; const int64_t* inds; float lambda; int value_only; float* grad_depth; float* partials; };
 
-template <bool DEPTH>
+// DIST: a further criterion, the distortion l_ray of the ray's weights (see DistGrad): loss += lambda * mean over ALL N rays of l_ray (a
+// ray without samples has l = 0), g = ((lambda / N) * scale) -> grad_dist[index] for every ray, carried through the backward as
+// k_composite_train_bwd<true, ., true> does; value_only forces g = 0.  With g == 0 (lambda == 0 or value_only: every ray of the launch)
+// the backward runs the statements of the flavour without DIST.  partials[] additionally receive 3 * lambda * sum(l_ray), partials of
+// the term alone go to DistLoss::partials (lae_loss_finish with n_elem = N gives L_dist).
+struct DistLoss { float lambda; int value_only; float* dist; float* grad_dist; float* partials; };
+
+template <bool DEPTH, bool DIST>
 __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
     const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum,
     float* __restrict__ depth, float* __restrict__ image, Blend bl, StepLoss sl, const uint32_t* __restrict__ rows_end_p,
-    float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, std::conditional_t<DEPTH, DepthLoss, NoArg> dl) {
+    float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, std::conditional_t<DEPTH, DepthLoss, NoArg> dl,
+    std::conditional_t<DIST, DistLoss, NoArg> xl) {
     __shared__ float s_sq[COMP_WAVES];
     [[maybe_unused]] __shared__ float s_dq[COMP_WAVES];
+    [[maybe_unused]] __shared__ float s_xq[COMP_WAVES];
     [[maybe_unused]] DepthState<DEPTH> ds;
+    [[maybe_unused]] DistState<DIST> xs;
+    [[maybe_unused]] DistAcc<DIST> xa;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t n = blockIdx.x * COMP_WAVES + wv;                      // one ray per wave: scalar
     const int lane = threadIdx.x & 63;
@@ -615,7 +678,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
             for (uint32_t base = 0; base < h.num_steps; base += 64) {
                 const Sample cur = nxt;
                 if (base + 64 < h.num_steps) nxt = load_sample(sigmas, rgbs, deltas, h, base + 64 + lane, true);
-                if (composite_fwd_pass(cur, base + lane < h.num_steps, T_thresh, lane, T, t, a)) break;
+                if (composite_fwd_pass<DIST>(cur, base + lane < h.num_steps, T_thresh, lane, T, t, a, xa)) break;
             }
         }
         const float* bg = ray_bg(bl.bg_rays, bl.bg, index);
@@ -642,6 +705,13 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
             ds.on = ds.gD != 0.0f;
             if (lane == 0) dl.grad_depth[index] = ds.gD;
         }
+        if constexpr (DIST) {
+            sq = sq + (3.0f * xl.lambda) * xa.l;
+            xs.g = xl.value_only ? 0.0f : (xl.lambda / (float)N) * s;
+            xs.qf = 2.0f * xa.l; xs.wf = a.ws; xs.df = a.d;
+            xs.on = xs.g != 0.0f;
+            if (lane == 0) { xl.dist[index] = xa.l; xl.grad_dist[index] = xs.g; }
+        }
         if (lane == 0) {
             store_ray(weights_sum, depth, image, index, a);
             store_blend(bl, index, o, a.d);
@@ -663,12 +733,13 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
                     if (k < h.num_steps) zero_grad_row(grad_sigmas, grad_rgbs, i);
                     continue;
                 }
-                if (composite_bwd_pass<true, DEPTH>(cur, k < h.num_steps, i, c, T_thresh, lane, st, ds, grad_sigmas, grad_rgbs)) stopped = true;
+                if (composite_bwd_pass<true, DEPTH, DIST>(cur, k < h.num_steps, i, c, T_thresh, lane, st, ds, xs, grad_sigmas, grad_rgbs)) stopped = true;
             }
         }
     }
     if (lane == 0) s_sq[wv] = sq;
     if constexpr (DEPTH) { if (lane == 0) s_dq[wv] = ds.dq; }
+    if constexpr (DIST) { if (lane == 0) s_xq[wv] = xa.l; }
     __syncthreads();
     if (threadIdx.x == 0) {
         float t = 0.0f;
@@ -680,6 +751,12 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
 #pragma unroll
             for (int w = 0; w < COMP_WAVES; w++) u += s_dq[w];
             dl.partials[blockIdx.x] = u;
+        }
+        if constexpr (DIST) {
+            float u = 0.0f;
+#pragma unroll
+            for (int w = 0; w < COMP_WAVES; w++) u += s_xq[w];
+            xl.partials[blockIdx.x] = u;
         }
         // deferred loss value (lae_composite_rays_train_step with poison_loss): whoever reads it before the finishing
         // launch (lae_loss_finish, or the extra block of lae_nerf_head_backward) sees NaN, not a stale number
@@ -816,15 +893,19 @@ __global__ __launch_bounds__(COMPACT_BLOCK) void k_compact_scatter(const int32_t
 }
 
 // ---------------------------------------------------------------- host side of K7 / K8: one body per pair of C entries
-// lae_composite_rays_train_step[_depth]: the depth-only arguments are checked first, before the N == 0 return
-template <bool DEPTH>
+// lae_composite_rays_train_step[_depth | _dist]: the depth- and dist-only arguments are checked first, before the N == 0 return
+template <bool DEPTH, bool DIST = false>
 int composite_train_step_impl(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
                                      float T_thresh, const Blend& bl, const uint32_t* rows_end, const StepLoss& sl, float* weights_sum,
                                      float* depth, float* image, float* grad_sigmas, float* grad_rgbs, float* loss_out, int defer_loss,
-                                     const std::conditional_t<DEPTH, DepthLoss, NoArg>& dl, const char* what, void* stream) {
+                                     const std::conditional_t<DEPTH, DepthLoss, NoArg>& dl, const char* what, void* stream,
+                                     const std::conditional_t<DIST, DistLoss, NoArg>& xl = {}) {
     if constexpr (DEPTH) {
         if (dl.dtype != LAE_IMG_F16 && dl.dtype != LAE_IMG_F32) return LAE_EINVAL;
         if (!(dl.lambda >= 0.0f) || !(dl.lambda <= 3.0e38f)) return LAE_EINVAL;      // NaN, negative and infinite weights
+    }
+    if constexpr (DIST) {
+        if (!(xl.lambda >= 0.0f) || !(xl.lambda <= 3.0e38f)) return LAE_EINVAL;
     }
     if (N == 0) return LAE_OK;
     if (!rays || !weights_sum || !depth || !image || !bl.nears || !bl.fars || !bl.depth_out || !bl.image_out || !rows_end || !sl.target ||
@@ -833,10 +914,13 @@ int composite_train_step_impl(const float* sigmas, const float* rgbs, const floa
     if constexpr (DEPTH) {
         if (!dl.src || !dl.grad_depth || !dl.partials) return LAE_ENULL;    // dl.inds may be NULL (src holds one value per ray)
     }
+    if constexpr (DIST) {
+        if (!xl.dist || !xl.grad_dist || !xl.partials) return LAE_ENULL;
+    }
     if (M > 0 && (!sigmas || !rgbs || !deltas || !grad_sigmas || !grad_rgbs)) return LAE_ENULL;
     const uint32_t nb = lae::cdiv(N, COMP_WAVES);
-    k_composite_train_step<DEPTH><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth,
-                                                                        image, bl, sl, rows_end, grad_sigmas, grad_rgbs, dl);
+    k_composite_train_step<DEPTH, DIST><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth,
+                                                                              image, bl, sl, rows_end, grad_sigmas, grad_rgbs, dl, xl);
     // defer_loss: the one-block sum of the partials (5.5 us + a kernel boundary on the step's critical path for a number that
     // feeds nothing on the device) is left to lae_loss_finish or to a later launch that takes it along
     // (lae_nerf_head_backward); loss_out holds NaN until then
@@ -844,19 +928,23 @@ int composite_train_step_impl(const float* sigmas, const float* rgbs, const floa
     return lae::check_launch(what);
 }
 
-template <bool DEPTH>
+template <bool DEPTH, bool DIST = false>
 int composite_train_backward_blend_impl(const float* grad_weights_sum, const float* grad_image, const float* sigmas, const float* rgbs,
                                                const float* deltas, const int32_t* rays, const float* weights_sum, const float* image,
                                                uint32_t M, uint32_t N, float T_thresh, const Dense& dn, float* grad_sigmas, float* grad_rgbs,
-                                               const std::conditional_t<DEPTH, DepthGrad, NoArg>& dg, const char* what, void* stream) {
+                                               const std::conditional_t<DEPTH, DepthGrad, NoArg>& dg, const char* what, void* stream,
+                                               const std::conditional_t<DIST, DistGrad, NoArg>& xg = {}) {
     if (N == 0 || M == 0) return LAE_OK;
     if (!grad_image || !sigmas || !rgbs || !deltas || !rays || !weights_sum || !image || !grad_sigmas || !grad_rgbs || !dn.rows_end)
         return LAE_ENULL;                                   // grad_weights_sum may be NULL (= zero)
     if constexpr (DEPTH) {
         if (!dg.grad_depth || !dg.depth) return LAE_ENULL;
     }
-    k_composite_train_bwd<true, DEPTH><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
-        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn, dg);
+    if constexpr (DIST) {
+        if (!xg.grad_dist || !xg.dist || !xg.depth) return LAE_ENULL;
+    }
+    k_composite_train_bwd<true, DEPTH, DIST><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
+        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn, dg, xg);
     return lae::check_launch(what);
 }
 
@@ -974,7 +1062,7 @@ int lae_composite_rays_train_forward(const float* sigmas, const float* rgbs, con
     if (!rays || !weights_sum || !depth || !image) return LAE_ENULL;
     if (M > 0 && (!sigmas || !rgbs || !deltas)) return LAE_ENULL;
     k_composite_train_fwd<false><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N,
-                                                                                               T_thresh, weights_sum, depth, image, Blend{});
+                                                                                               T_thresh, weights_sum, depth, image, Blend{}, NoArg{});
     return lae::check_launch("composite_rays_train_forward");
 }
 
@@ -987,8 +1075,22 @@ int lae_composite_rays_train_forward_blend(const float* sigmas, const float* rgb
     if (M > 0 && (!sigmas || !rgbs || !deltas)) return LAE_ENULL;
     const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
     k_composite_train_fwd<true><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N,
-                                                                                              T_thresh, weights_sum, depth, image, bl);
+                                                                                              T_thresh, weights_sum, depth, image, bl, NoArg{});
     return lae::check_launch("composite_rays_train_forward_blend");
+}
+
+int lae_composite_rays_train_forward_blend_dist(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                                uint32_t M, uint32_t N, float T_thresh, const float* nears, const float* fars,
+                                                const float* bg_rays, float bg_r, float bg_g, float bg_b, float* weights_sum,
+                                                float* depth, float* image, float* depth_out, float* image_out, float* dist,
+                                                void* stream) {
+    if (N == 0) return LAE_OK;
+    if (!rays || !weights_sum || !depth || !image || !nears || !fars || !depth_out || !image_out || !dist) return LAE_ENULL;
+    if (M > 0 && (!sigmas || !rgbs || !deltas)) return LAE_ENULL;
+    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
+    k_composite_train_fwd<true, true><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N,
+                                                                                                    T_thresh, weights_sum, depth, image, bl, dist);
+    return lae::check_launch("composite_rays_train_forward_blend_dist");
 }
 
 int lae_composite_rays_train_step(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
@@ -1015,6 +1117,28 @@ int lae_composite_rays_train_step_depth(const float* sigmas, const float* rgbs, 
                                            image, grad_sigmas, grad_rgbs, loss_out, defer_loss,
                                            DepthLoss{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials},
                                            "composite_rays_train_step_depth", stream);
+}
+
+int lae_composite_rays_train_step_dist(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                       uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
+                                       float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
+                                       const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
+                                       float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
+                                       float* partials, int defer_loss, const void* depth_src, int depth_dtype,
+                                       const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
+                                       float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
+                                       float* dist_partials, void* stream) {
+    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
+    const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
+    const DistLoss xl{dist_lambda, dist_value_only != 0, dist, grad_dist, dist_partials};
+    if (!depth_src)                                       // no depth term: the other depth arguments are not looked at
+        return composite_train_step_impl<false, true>(sigmas, rgbs, deltas, rays, M, N, T_thresh, bl, rows_end, sl, weights_sum, depth, image,
+                                                      grad_sigmas, grad_rgbs, loss_out, defer_loss, NoArg{}, "composite_rays_train_step_dist",
+                                                      stream, xl);
+    return composite_train_step_impl<true, true>(sigmas, rgbs, deltas, rays, M, N, T_thresh, bl, rows_end, sl, weights_sum, depth, image,
+                                                 grad_sigmas, grad_rgbs, loss_out, defer_loss,
+                                                 DepthLoss{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials},
+                                                 "composite_rays_train_step_dist", stream, xl);
 }
 
 int lae_loss_finish(const float* partials, uint32_t n_part, uint32_t n_elem, const float* scale, float* loss_out, void* stream) {
@@ -1046,6 +1170,24 @@ int lae_composite_rays_train_backward_blend_depth(const float* grad_weights_sum,
                                                      DepthGrad{grad_depth, depth}, "composite_rays_train_backward_blend_depth", stream);
 }
 
+int lae_composite_rays_train_backward_blend_dist(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
+                                                 const float* rgbs, const float* deltas, const int32_t* rays,
+                                                 const float* weights_sum, const float* image, uint32_t M, uint32_t N,
+                                                 float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
+                                                 const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
+                                                 float* grad_rgbs, const float* grad_depth, const float* depth, const float* grad_dist,
+                                                 const float* dist, void* stream) {
+    const Dense dn{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale};
+    const DistGrad xg{grad_dist, dist, depth};
+    if (!grad_depth)                                      // no depth gradient; `depth` is still read: q_k needs D
+        return composite_train_backward_blend_impl<false, true>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
+                                                                T_thresh, dn, grad_sigmas, grad_rgbs, NoArg{},
+                                                                "composite_rays_train_backward_blend_dist", stream, xg);
+    return composite_train_backward_blend_impl<true, true>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
+                                                           T_thresh, dn, grad_sigmas, grad_rgbs, DepthGrad{grad_depth, depth},
+                                                           "composite_rays_train_backward_blend_dist", stream, xg);
+}
+
 int lae_composite_rays_train_backward_blend(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
                                             const float* rgbs, const float* deltas, const int32_t* rays,
                                             const float* weights_sum, const float* image, uint32_t M, uint32_t N,
@@ -1067,7 +1209,7 @@ int lae_composite_rays_train_backward(const float* grad_weights_sum, const float
         return LAE_ENULL;
     k_composite_train_bwd<false><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
         grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas,
-        grad_rgbs, Dense{}, NoArg{});
+        grad_rgbs, Dense{}, NoArg{}, NoArg{});
     return lae::check_launch("composite_rays_train_backward");
 }
 

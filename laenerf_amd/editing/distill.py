@@ -239,17 +239,21 @@ def seed_launch(dset, error_map, H, W):
 
 
 def distill_nerf(renderer, optimizer, data, style_enc, views, occluded, steps=3000, lr=1e-2, error_maps=False, trainer_kw=None,
-                 depth_sup=False, depth_weight=1e-3, depth_grad=True, **compose_kw):
+                 depth_sup=False, depth_weight=1e-3, depth_grad=True, distort_weight=None, **compose_kw):
     """the whole stage: distill_images, then a new Trainer(renderer, optimizer, distilled, iters=steps, lr=lr, error_map='ema' with
     error maps) run for distill_steps(steps) steps -> (distilled ResidentImages, Trainer).  views / occluded: extract_views' result;
     compose_kw: distill_images' edit arguments; trainer_kw: further Trainer arguments (num_rays, seed, ...).
     depth_sup: train with the reference's depth term (its `depth_sup = style_weight > 0`, gui.py:202) on the views' extracted
     depths, weight depth_weight (1e-3 and the mask depth > 0: nerf/utils.py:587-589, 635).  depth_grad=True lets the term hold the
-    geometry in place; depth_grad=False is the reference's effective behaviour, where the term only changes the logged loss."""
+    geometry in place; depth_grad=False is the reference's effective behaviour, where the term only changes the logged loss.
+    distort_weight: None, or the weight of the Trainer's distortion regularizer (Trainer(distort_weight=...)): it keeps the
+    fine-tuning from growing floaters around the edited region."""
     from ..trainer import Trainer
     dset = DistillSet.from_views(views, occluded, data.n_img, device=data.images.device)
     distilled = distill_images(data, style_enc, dset, error_maps=error_maps, depth_sup=depth_sup, **compose_kw)
     depth_kw = {"depth_weight": depth_weight, "depth_grad": depth_grad} if depth_sup else {}
+    if distort_weight is not None:
+        depth_kw["distort_weight"] = distort_weight
     tr = Trainer(renderer, optimizer, distilled, iters=steps, lr=lr, error_map="ema" if error_maps else None, **depth_kw,
                  **(trainer_kw or {}))
     tr.train(distill_steps(steps))

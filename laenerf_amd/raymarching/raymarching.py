@@ -15,7 +15,8 @@ from ..backend import raymarching_backend as _backend
 __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", "packbits", "march_rays_train",
            "composite_rays_train", "march_rays", "march_rays_distill", "composite_rays", "composite_rays_distill",
            "compact_rays_alive", "render_frame", "composite_rays_train_blend", "composite_rays_train_blend_mse",
-           "composite_rays_train_blend_depth", "finish_depth_loss", "composite_depth_numpy", "density_grid_positions",
+           "composite_rays_train_blend_depth", "finish_depth_loss", "composite_depth_numpy", "composite_rays_train_blend_distort",
+           "finish_distort_loss", "composite_distort_numpy", "density_grid_positions",
            "density_grid_partial_positions", "density_grid_update", "mark_untrained_grid"]
 
 
@@ -308,6 +309,61 @@ def composite_rays_train_blend_depth(sigmas, rgbs, deltas, rays, nears, fars, bg
     return _composite_rays_train_blend.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh)
 
 
+class _composite_rays_train_blend_dist(Function):
+    """_composite_rays_train_blend with one more differentiable output: dist [N], the distortion l_ray of every ray's weights
+    (`lae_composite_rays_train_forward_blend_dist`; formulas in include/laenerf.h).  Where dist receives a gradient the backward
+    is lae_composite_rays_train_backward_blend_dist, otherwise the one _composite_rays_train_blend would have run."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh):
+        sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
+        M, N = sigmas.shape[0], rays.shape[0]
+        weights_sum, depth, image, depth_out, image_out = _train_outputs(N, sigmas.dtype, sigmas.device)
+        dist = torch.empty(N, dtype=sigmas.dtype, device=sigmas.device)
+        _backend.composite_rays_train_forward_blend_dist(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(),
+                                                         fars.contiguous(), bg_rays, bg, weights_sum, depth, image, depth_out, image_out,
+                                                         dist)
+        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, depth, image, dist, bg_rays, rows_end)
+        ctx.dims = [M, N, T_thresh, bg]
+        ctx.mark_non_differentiable(depth_out)
+        ctx.set_materialize_grads(False)
+        return weights_sum, depth, depth_out, image_out, dist
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, grad_weights_sum, grad_depth, grad_depth_out, grad_image, grad_dist):
+        sigmas, rgbs, deltas, rays, weights_sum, depth, image, dist, bg_rays, rows_end = ctx.saved_tensors
+        M, N, T_thresh, bg = ctx.dims
+        if grad_image is None and grad_weights_sum is None and grad_depth is None and grad_dist is None:
+            return (None,) * 10
+        grad_image = torch.zeros_like(image) if grad_image is None else grad_image.float().contiguous()
+        gws = None if grad_weights_sum is None else grad_weights_sum.float().contiguous()
+        gD = None if grad_depth is None else grad_depth.float().contiguous()
+        grad_sigmas, grad_rgbs = torch.empty_like(sigmas), torch.empty_like(rgbs)
+        if grad_dist is not None:
+            _backend.composite_rays_train_backward_blend_dist(gws, grad_image, gD, grad_dist.float().contiguous(), sigmas, rgbs, deltas,
+                                                              rays, weights_sum, depth, dist, image, M, N, T_thresh, bg_rays, bg,
+                                                              rows_end, grad_sigmas, grad_rgbs)
+        elif gD is not None:
+            _backend.composite_rays_train_backward_blend_depth(gws, grad_image, gD, sigmas, rgbs, deltas, rays, weights_sum, depth, image,
+                                                               M, N, T_thresh, bg_rays, bg, rows_end, grad_sigmas, grad_rgbs)
+        else:
+            _backend.composite_rays_train_backward_blend(gws, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh,
+                                                         bg_rays, bg, rows_end, grad_sigmas, grad_rgbs)
+        return (grad_sigmas, grad_rgbs) + (None,) * 8
+
+
+def composite_rays_train_blend_distort(sigmas, rgbs, deltas, rays, nears, fars, bg_color=1, T_thresh=1e-4):
+    """-> weights_sum [N], depth_raw [N], depth_out [N] (no gradient), image blended over bg_color [N,3], dist [N].
+    composite_rays_train_blend_depth plus the raw per-ray distortion of the weights (mip-NeRF 360, the O(n) form of the reference's
+    loss.py eff_distloss with m = t, interval = deltas[:,0]; lengths in the march's units, not divided by far - near):
+    dist = (1/3) sum_k delta_k w_k^2 + sum_ij w_i w_j |t_i - t_j|, differentiable towards the densities: the building block of
+    custom regularizers (dist.mean() is the L_dist of composite_rays_train_blend_mse(distort_weight=...))."""
+    rows_end, bg_rays, bg = _blend_args("composite_rays_train_blend_distort", rays, bg_color, sigmas.device)
+    return _composite_rays_train_blend_dist.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh)
+
+
 # root gradients known to be all ones (laenerf_amd.optim.FusedAdam.backward registers the tensor it passes to
 # loss.backward): for them the fused node below hands its stored sample gradients on unchanged.  address -> weak reference:
 # an address whose tensor has died may belong to anything by now
@@ -342,12 +398,15 @@ class _composite_rays_train_blend_mse(Function):
     backward() returns them -- multiplied by the upstream gradient unless that is known to be ones.
     depth_sup = (_DepthPlane, depth_inds, depth_weight, value_only) adds the depth criterion in the same kernel
     (`lae_composite_rays_train_step_depth`): loss = MSE + depth_weight * mean(((D - (z - nears)) * (z > 0))^2), z gathered from the
-    depth plane by the kernel; the last two outputs (the depth partial sums, d loss / d D) are None without it."""
+    depth plane by the kernel; the outputs depth_partials, grad_depth (the depth partial sums, d loss / d D) are None without it.
+    dist_sup = (distort_weight, value_only) adds distort_weight * mean(l_ray), the distortion term
+    (`lae_composite_rays_train_step_dist`, with or without depth_sup); the last three outputs (its partial sums, d loss / d l_ray,
+    l_ray per ray) are None without it."""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, defer_loss=False,
-                depth_sup=None):
+                depth_sup=None, dist_sup=None):
         sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
         M, N = sigmas.shape[0], rays.shape[0]
         dev = sigmas.device
@@ -365,20 +424,27 @@ class _composite_rays_train_blend_mse(Function):
             grad_depth = torch.empty(N, dtype=torch.float32, device=dev)
             depth_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
             depth_sup = (plane.t, depth_inds, depth_weight, value_only, grad_depth, depth_partials)
+        dist = grad_dist = dist_partials = None
+        if dist_sup is not None:
+            dist, grad_dist = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
+            dist_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
+            dist_sup = dist_sup + (dist, grad_dist, dist_partials)
         _backend.composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(), fars.contiguous(), bg_rays,
                                            bg, rows_end, target, scale, weights_sum, depth, image, depth_out, image_out, grad_image,
-                                           grad_sigmas, grad_rgbs, out, partials, defer_loss=defer_loss, depth_sup=depth_sup)
+                                           grad_sigmas, grad_rgbs, out, partials, defer_loss=defer_loss, depth_sup=depth_sup,
+                                           dist_sup=dist_sup)
         ctx.save_for_backward(grad_sigmas, grad_rgbs)
-        aux = (weights_sum, depth_out, image_out, out) + (() if depth_sup is None else (depth_partials, grad_depth))
+        aux = (weights_sum, depth_out, image_out, out) + (() if depth_sup is None else (depth_partials, grad_depth)) + \
+              (() if dist_sup is None else (dist_partials, grad_dist, dist))
         ctx.mark_non_differentiable(*aux)
         ctx.set_materialize_grads(False)                 # no zero-filled gradients for the auxiliary outputs (a fill launch each)
-        return out[0], weights_sum, depth_out, image_out, out, depth_partials, grad_depth
+        return out[0], weights_sum, depth_out, image_out, out, depth_partials, grad_depth, dist_partials, grad_dist, dist
 
     @staticmethod
     @custom_bwd(device_type="cuda")
     def backward(ctx, grad_loss, *_):
         if grad_loss is None:
-            return (None,) * 14
+            return (None,) * 15
         grad_sigmas, grad_rgbs = ctx.saved_tensors
         if not _is_unit_root_grad(grad_loss):              # a general upstream gradient: d(loss) scales every sample gradient
             gl = grad_loss.float()
@@ -386,7 +452,7 @@ class _composite_rays_train_blend_mse(Function):
             from ..backend import retarget_pending_loss
             retarget_pending_loss(grad_sigmas, scaled)     # a deferred loss value follows the tensor the head backward will receive
             grad_sigmas, grad_rgbs = scaled, grad_rgbs * gl
-        return (grad_sigmas, grad_rgbs) + (None,) * 12
+        return (grad_sigmas, grad_rgbs) + (None,) * 13
 
 
 def finish_depth_loss(loss, out=None):
@@ -402,8 +468,30 @@ def finish_depth_loss(loss, out=None):
     return out[1]
 
 
+def finish_distort_loss(loss, out=None):
+    """the distortion term alone, L_dist = mean over all rays of l_ray without its weight, of a `loss` made by
+    composite_rays_train_blend_mse(distort_weight=...): one lae_loss_finish launch over the step's distortion partial sums, off the
+    gradient path.  out: a float32 tensor of 2 elements to write to (both receive the value); -> out[1] as a 0-dim tensor"""
+    parts = getattr(loss, "dist_partials", None)
+    if parts is None:
+        raise RuntimeError("finish_distort_loss: the loss was made without a distortion term")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=parts.device)
+    _backend.loss_finish(parts, parts.numel(), loss.dist_rays, None, out)
+    return out[1]
+
+
+def check_distort_weight(who, distort_weight):
+    """-> float(distort_weight); ValueError unless it is finite and >= 0"""
+    w = float(distort_weight)
+    if not (w >= 0.0) or w == float("inf"):
+        raise ValueError(f"{who}: distort_weight must be finite and >= 0")
+    return w
+
+
 def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, target, bg_color=1, T_thresh=1e-4, scaler=None,
-                                   defer_loss=None, depth=None, depth_inds=None, depth_weight=0.0, depth_grad=True):
+                                   defer_loss=None, depth=None, depth_inds=None, depth_weight=0.0, depth_grad=True,
+                                   distort_weight=None, distort_grad=True):
     """-> (loss, weights_sum, depth, image): loss = MSE(image, target) times the loss scale of `scaler` (a FusedAdam, a
     1-element fp32 cuda tensor, or None); `loss.unscaled` holds the plain MSE.  Only `loss` carries a gradient.
     defer_loss (default: True when `scaler` is a FusedAdam): the VALUE of loss / loss.unscaled is NaN until the backward pass
@@ -416,7 +504,16 @@ def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, targ
     (nears == fars, the sentinel of near_far_from_aabb) is unsupervised whatever the plane holds: it has no near.  depth_grad=True carries the
     term's gradient to the densities -- the reference's backward drops it (raymarching.py:273-275), depth_grad=False restates
     that: the value only, the sample gradients of the call without depth bit for bit.  `loss.grad_depth` [N] holds d loss / d D,
-    finish_depth_loss(loss) the unweighted depth term."""
+    finish_depth_loss(loss) the unweighted depth term.
+    distort_weight (default None: today's call, bit for bit): the distortion regularizer of mip-NeRF 360 in the same kernel, with or
+    without depth.  loss becomes ... + distort_weight * L_dist, L_dist = mean over all rays of
+    l_ray = (1/3) sum_k delta_k w_k^2 + sum_ij w_i w_j |t_i - t_j| (the O(n) form of the reference's loss.py eff_distloss, called
+    with m = t and interval = deltas[:,0]: lengths in the march's own units, not divided by far - near, so the weight that suits a
+    scene scales with 1 / its extent).  distort_grad=False: the value only, the sample gradients of the call without the term bit
+    for bit.  `loss.dist` [N] holds l_ray, `loss.grad_dist` [N] d loss / d l_ray, finish_distort_loss(loss) L_dist."""
+    dist_sup = None
+    if distort_weight is not None:
+        dist_sup = (check_distort_weight("composite_rays_train_blend_mse", distort_weight), not distort_grad)
     rows_end, bg_rays, bg = _blend_args("composite_rays_train_blend_mse", rays, bg_color, sigmas.device)
     scale = None
     if scaler is not None:
@@ -431,9 +528,12 @@ def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, targ
             raise ValueError("composite_rays_train_blend_mse: depth_weight must be finite and >= 0")
         depth_sup = (_DepthPlane(depth.contiguous()), None if depth_inds is None else depth_inds.contiguous(), float(depth_weight),
                      not depth_grad)
-    loss, weights_sum, depth_o, image, both, depth_partials, grad_depth = _composite_rays_train_blend_mse.apply(
-        sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, bool(defer_loss), depth_sup)
+    loss, weights_sum, depth_o, image, both, depth_partials, grad_depth, dist_partials, grad_dist, dist = \
+        _composite_rays_train_blend_mse.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale,
+                                              bool(defer_loss), depth_sup, dist_sup)
     loss.unscaled = both[1]
+    if dist_sup is not None:
+        loss.dist_partials, loss.grad_dist, loss.dist, loss.dist_rays = dist_partials, grad_dist, dist, rays.shape[0]
     if depth_sup is not None:
         loss.depth_partials, loss.grad_depth, loss.depth_rays = depth_partials, grad_depth, rays.shape[0]
     return loss, weights_sum, depth_o, image
@@ -621,7 +721,7 @@ def mark_untrained_grid(density_grid, poses, intrinsics, bound, min_near=0.2, fi
 # ---------------------------------------------------------------- numpy restatement of the depth-supervised compositing
 def composite_depth_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=None, bg=None, grad_weights_sum=None, grad_image=None,
                           grad_depth=None, target=None, z=None, nears=None, depth_weight=0.0, scale=1.0, depth_grad=True, n_rays=None,
-                          fars=None):
+                          fars=None, samples=False):
     """The training compositing with the depth gradient, restated sample by sample in `dtype` (default float64): the forward
     (k_composite_train_fwd: early stop after the first sample with T_post < T_thresh, that sample included; rays with
     num_steps == 0 or offset + num_steps > M dropped), optionally the criterion of lae_composite_rays_train_step_depth
@@ -632,7 +732,8 @@ def composite_depth_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=None,
     -> dict weights_sum, depth (raw D), image [N,3], stop [N] (index of the last sample used, -1 for a ray without samples),
     margin (the smallest |T_post / T_thresh - 1| over the samples used: how far the early stop is from flipping), and with
     gradients grad_sigmas [M], grad_rgbs [M,3] (zero on rows no ray uses); with a criterion also image_out, res, grad_image,
-    grad_depth, mse, depth_mse, loss (= mse + depth_weight * depth_mse)."""
+    grad_depth, mse, depth_mse, loss (= mse + depth_weight * depth_mse).  samples=True: also `samples`, {row of rays: (w, t, T_post)}
+    of the samples each ray uses."""
     import numpy as np
     dt = np.dtype(np.float64 if dtype is None else dtype).type
     sig, col, dl = np.asarray(sigmas).astype(dt), np.asarray(rgbs).astype(dt).reshape(-1, 3), np.asarray(deltas).astype(dt).reshape(-1, 2)
@@ -665,6 +766,8 @@ def composite_depth_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=None,
                 break
         per_ray[n] = (np.array(w_l, dt), np.array(t_l, dt), np.array(tp_l, dt))
     res = {"weights_sum": ws, "depth": D, "image": img, "stop": stop, "margin": margin}
+    if samples:
+        res["samples"] = per_ray
     bgv = None if bg is None else np.broadcast_to(np.asarray(bg).astype(dt).reshape(-1, 3), (N, 3))
     if target is not None:
         lam, sc = dt(depth_weight), dt(scale)
@@ -700,4 +803,59 @@ def composite_depth_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=None,
             br = (g * (tp_l[k] * col[i] - (img[index] - c_run))).sum() + tail
             gs[i] = dl[i, 0] * (br + g_D[index] * (tp_l[k] * t_l[k] - (D[index] - d_run)))
     res.update(grad_sigmas=gs, grad_rgbs=gc)
+    return res
+
+
+def composite_distort_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=None, bg=None, grad_weights_sum=None, grad_image=None,
+                            grad_depth=None, grad_dist=None, target=None, z=None, nears=None, depth_weight=0.0, distort_weight=0.0,
+                            scale=1.0, depth_grad=True, distort_grad=True, n_rays=None, fars=None):
+    """composite_depth_numpy with the distortion term of lae_composite_rays_train_*_dist, restated sample by sample in `dtype`
+    (default float64).  Per ray, over the samples the forward uses, lengths in the march's units (m = t, interval = deltas[:,0]):
+      dist = l_ray = (1/3) sum_k delta_k w_k^2 + 2 sum_k w_k (t_k W_<k - WT_<k)
+      q_k  = dl / dw_k = (2/3) delta_k w_k + 2 (t_k (W_<k - (W - W_k)) + ((D - WT_k) - WT_<k))
+      grad_sigmas_k += delta_k * g * (T_post_k * q_k - (Q - Q_k)),  Q_k = sum_{j<=k} q_j w_j,  Q = 2 l_ray (l is of degree 2 in w)
+    With a criterion (target; z / nears optional: no depth term without z) loss = mse + depth_weight * depth_mse + distort_weight *
+    dist_mean and g = grad_dist = (distort_weight / N) * scale for every ray (zeros with distort_grad=False); otherwise g is the
+    grad_dist [N] handed in.  -> the dict of composite_depth_numpy plus dist [N], q [M] (zero on rows no ray uses), dist_mean
+    (= sum(dist) / N, all rays), grad_dist [N]; grad_sigmas / grad_rgbs whenever any gradient is present."""
+    import numpy as np
+    dt = np.dtype(np.float64 if dtype is None else dtype).type
+    dl = np.asarray(deltas).astype(dt).reshape(-1, 2)
+    rays_a = np.asarray(rays).astype(np.int64).reshape(-1, 3)
+    M, N = dl.shape[0], rays_a.shape[0] if n_rays is None else int(n_rays)
+    if target is not None and z is None:
+        z, nears, depth_weight = np.zeros(N, dt), np.zeros(N, dt), 0.0
+    res = composite_depth_numpy(sigmas, rgbs, deltas, rays, T_thresh, dtype=dtype, bg=bg, grad_weights_sum=grad_weights_sum,
+                                grad_image=grad_image, grad_depth=grad_depth, target=target, z=z, nears=nears, depth_weight=depth_weight,
+                                scale=scale, depth_grad=depth_grad, n_rays=n_rays, fars=fars, samples=True)
+    per_ray = res.pop("samples")
+    dist, q = np.zeros(N, dt), np.zeros(M, dt)
+    third, two = dt(1) / dt(3), dt(2)
+    pre = {}
+    for n, (w, t, tp) in per_ray.items():
+        index, offset, _ = (int(v) for v in rays_a[n])
+        d0 = dl[offset:offset + len(w), 0]
+        W_k, WT_k = np.cumsum(w), np.cumsum(w * t)
+        W_lt, WT_lt = np.concatenate([[dt(0)], W_k[:-1]]), np.concatenate([[dt(0)], WT_k[:-1]])      # exclusive prefixes
+        dist[index] = (third * d0 * w * w).sum() + (two * w * (t * W_lt - WT_lt)).sum()
+        q[offset:offset + len(w)] = two * third * d0 * w + two * (t * (W_lt - (W_k[-1] - W_k)) + ((WT_k[-1] - WT_k) - WT_lt))
+        pre[n] = (w, tp, d0)
+    res.update(dist=dist, q=q, dist_mean=dist.sum() / dt(N))
+    if target is not None:
+        lam = dt(distort_weight)
+        grad_dist = np.full(N, (lam / dt(N)) * dt(scale), dt) if distort_grad else np.zeros(N, dt)
+        res["loss"] = res["loss"] + lam * res["dist_mean"]
+    res["grad_dist"] = None if grad_dist is None else np.asarray(grad_dist).astype(dt).reshape(N)
+    if res["grad_dist"] is None and "grad_sigmas" not in res:
+        return res
+    if res["grad_dist"] is None:
+        res["grad_dist"] = np.zeros(N, dt)
+    if "grad_sigmas" not in res:
+        res.update(grad_sigmas=np.zeros(M, dt), grad_rgbs=np.zeros((M, 3), dt))
+    gs = res["grad_sigmas"]
+    for n, (w, tp, d0) in pre.items():
+        index, offset, _ = (int(v) for v in rays_a[n])
+        qr = q[offset:offset + len(w)]
+        Q_k = np.cumsum(qr * w)
+        gs[offset:offset + len(w)] += d0 * res["grad_dist"][index] * (tp * qr - (two * dist[index] - Q_k))
     return res

@@ -297,14 +297,19 @@ class NeRFRenderer(nn.Module):
         return xyzs, dirs, deltas, rays, nears, fars
 
     def shade_train(self, marched, bg_color=1, T_thresh=1e-4, gt=None, scaler=None, depth=None, depth_inds=None, depth_weight=0.0,
-                    depth_grad=True):
+                    depth_grad=True, distort_weight=None, distort_grad=True):
         """second half: network on the samples, compositing, background blend, depth normalisation (renderer.py:313-334).
         gt [N,3] (optional, MI355X-native): also evaluate the trainer's criterion MSE(image, gt) (scaled by `scaler`'s
         loss scale) inside the compositing op -> result["loss"]; call loss.backward() on it.
         depth / depth_inds / depth_weight / depth_grad (with gt and fused_post_ops only): the depth criterion of
-        raymarching.composite_rays_train_blend_mse in the same kernel; depth=None leaves the call as it was."""
+        raymarching.composite_rays_train_blend_mse in the same kernel; depth=None leaves the call as it was.
+        distort_weight / distort_grad (with gt and fused_post_ops only): the distortion regularizer of the same function, with or
+        without depth; distort_weight=None leaves the call as it was."""
         if depth is not None and not (self.fused_post_ops and gt is not None):
             raise RuntimeError("shade_train: depth supervision needs gt and fused_post_ops (it lives in the fused criterion kernel)")
+        if distort_weight is not None and not (self.fused_post_ops and gt is not None):
+            raise RuntimeError("shade_train: the distortion term needs gt and fused_post_ops (it lives in the fused criterion kernel)")
+        dist_kw = {} if distort_weight is None else {"distort_weight": distort_weight, "distort_grad": distort_grad}
         xyzs, dirs, deltas, rays, nears, fars = marched[:6]
         plan = marched[6] if len(marched) > 6 else None
         sigmas, rgbs = self.model(xyzs, dirs, plan=plan) if plan is not None else self.model(xyzs, dirs)
@@ -314,11 +319,11 @@ class NeRFRenderer(nn.Module):
         if self.fused_post_ops and gt is not None:
             if depth is None:
                 loss, weights_sum, depth, image = raymarching.composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars,
-                                                                                            gt, bg_color, T_thresh, scaler)
+                                                                                            gt, bg_color, T_thresh, scaler, **dist_kw)
             else:
                 loss, weights_sum, depth, image = raymarching.composite_rays_train_blend_mse(
                     sigmas, rgbs, deltas, rays, nears, fars, gt, bg_color, T_thresh, scaler, depth=depth, depth_inds=depth_inds,
-                    depth_weight=depth_weight, depth_grad=depth_grad)
+                    depth_weight=depth_weight, depth_grad=depth_grad, **dist_kw)
         elif self.fused_post_ops:    # composite + bg blend + depth normalisation in one kernel, gradients without zero fills
             weights_sum, depth, image = raymarching.composite_rays_train_blend(sigmas, rgbs, deltas, rays, nears, fars,
                                                                                bg_color, T_thresh)

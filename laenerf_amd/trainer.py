@@ -30,6 +30,11 @@ distillation) to the step's loss inside the fused compositing kernel, which gath
 captured 16-step groups, every pointer constant, nothing new on the host inside a group.  depth_grad=True carries the term's gradient
 to the densities; the reference's compositing backward drops it (raymarching/raymarching.py:273-275), so there the term changes the
 logged loss and nothing else -- depth_grad=False restates that, with parameters bit-equal to a run without depth.
+
+distort_weight adds the distortion regularizer of mip-NeRF 360, `distort_weight * mean over the batch's rays of
+(1/3) sum_k delta_k w_k^2 + sum_ij w_i w_j |t_i - t_j|` (the O(n) form of the reference's loss.py eff_distloss, which its CUDA-ray
+path never calls; lengths in the march's own units), inside the same kernel and the same captured groups, alone or together with
+depth_weight.  distort_grad=False computes the value only: parameters bit-equal to a run without the term.
 """
 import contextlib
 import math
@@ -106,11 +111,15 @@ class Trainer:
     needs data.depths; depth_grad: whether its gradient reaches the densities (False: the reference's value-only behaviour).
     With it losses() holds the total, MSE + depth_weight * depth term, and depth_losses() the per-step depth term without its
     weight: one lae_loss_finish node per step, off the gradient path.
+    distort_weight: None (no distortion term; the step is the one without this argument, bit for bit) or the weight of the
+    distortion regularizer (module docstring); distort_grad: whether its gradient reaches the densities.  With it losses() holds the
+    total and distort_losses() the per-step term without its weight, finished like the depth term's.
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
     def __init__(self, renderer, optimizer, data, iters, lr, num_rays=4096, seed=0, graph=True, capacity="bucket",
-                 max_steps=1024, dt_gamma=0.0, error_map=None, ema_decay=None, epoch_len=None, depth_weight=None, depth_grad=True):
+                 max_steps=1024, dt_gamma=0.0, error_map=None, ema_decay=None, epoch_len=None, depth_weight=None, depth_grad=True,
+                 distort_weight=None, distort_grad=True):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
         if error_map not in (None, "ema", "fixed"):
@@ -130,6 +139,11 @@ class Trainer:
                 raise ValueError("Trainer: depth supervision needs the renderer's fused_post_ops")
         self.depth_weight = None if depth_weight is None else float(depth_weight)
         self.depth_grad = bool(depth_grad)
+        if distort_weight is not None:
+            distort_weight = raymarching.check_distort_weight("Trainer", distort_weight)
+            if not renderer.fused_post_ops:
+                raise ValueError("Trainer: the distortion term needs the renderer's fused_post_ops")
+        self.distort_weight, self.distort_grad = distort_weight, bool(distort_grad)
         dev = renderer.density_grid.device
         data.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         data.aabb = renderer.aabb_train.to(dev, torch.float32).contiguous()      # the batch's near / far = the march's
@@ -141,6 +155,8 @@ class Trainer:
         self.loss_slots = torch.zeros(GROUP, dtype=torch.float32, device=dev)
         self.depth_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.depth_weight is not None else None
         self._depth_hist = []
+        self.distort_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.distort_weight is not None else None
+        self._distort_hist = []
         self.global_step = 0
         self.started = False
         self.graphs = {}
@@ -182,17 +198,20 @@ class Trainer:
                     perturb=True, dt_gamma=self.dt_gamma, max_steps=self.max_steps, m_limit=self.m_limit, capacity=m_cap)
             if not torch.cuda.is_current_stream_capturing():
                 self._rows_seen = max(self._rows_seen, xyzs.shape[0])
+            dist_kw = {} if self.distort_weight is None else {"distort_weight": self.distort_weight, "distort_grad": self.distort_grad}
             if self.depth_weight is None:
-                res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt)
+                res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt, **dist_kw)
             else:
                 res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt,
                                     depth=self.data.depths, depth_inds=b["inds"], depth_weight=self.depth_weight,
-                                    depth_grad=self.depth_grad)
+                                    depth_grad=self.depth_grad, **dist_kw)
         if self.error_map == "ema":
             self.data.update_error_map(res["image"], b)
         loss = res["loss"]
         if self.depth_weight is not None:
             raymarching.finish_depth_loss(loss, out=self.depth_slots[k])
+        if self.distort_weight is not None:
+            raymarching.finish_distort_loss(loss, out=self.distort_slots[k])
         opt.backward(loss)
         opt.step()
         if self.ema is not None:
@@ -252,6 +271,8 @@ class Trainer:
             self._loss_hist.append(self.loss_slots[pos:pos + n].clone())
             if self.depth_slots is not None:
                 self._depth_hist.append(self.depth_slots[pos:pos + n, 1].clone())
+            if self.distort_slots is not None:
+                self._distort_hist.append(self.distort_slots[pos:pos + n, 1].clone())
             done += n
             self.global_step += n
         return self
@@ -259,7 +280,7 @@ class Trainer:
     # ------------------------------------------------------------------ results
     def losses(self):
         """per-step losses (the unscaled loss of every step so far: the MSE, plus depth_weight * the depth term with depth
-        supervision) as a float32 numpy array"""
+        supervision, plus distort_weight * the distortion term with it) as a float32 numpy array"""
         if not self._loss_hist:
             return np.zeros(0, np.float32)
         return torch.cat(self._loss_hist).cpu().numpy()
@@ -270,6 +291,13 @@ class Trainer:
         if not self._depth_hist:
             return np.zeros(0, np.float32)
         return torch.cat(self._depth_hist).cpu().numpy()
+
+    def distort_losses(self):
+        """per-step distortion term L_dist (the batch's mean of l_ray), without its weight, as a float32 numpy array (empty without
+        distort_weight).  Each step finishes it with one lae_loss_finish node off the gradient path."""
+        if not self._distort_hist:
+            return np.zeros(0, np.float32)
+        return torch.cat(self._distort_hist).cpu().numpy()
 
     @property
     def steps_skipped(self):

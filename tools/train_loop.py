@@ -5,13 +5,16 @@ RGBA views from cameras on a sphere: colour = image over a black background / we
 weights_sum; 8-bit like a real dataset.  A fresh student trains on them with the reference's loop (random background,
 refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated on held-out views over white.
 
-    python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed] [--ema] [--depth]
+    python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed] [--ema] [--depth] [--distort W]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
 ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR.
 --depth: a second, identically seeded student trains with depth supervision (Trainer(depth_weight=...)) on the teacher's own depth
 (its rendered ray-origin distance where the view is opaque, zero elsewhere); the line then carries ms/step with and without the
-term ("depth": {...}) and the replay time of five windows for each."""
+term ("depth": {...}) and the replay time of five windows for each.
+--distort W: every student of the run trains with the distortion regularizer (Trainer(distort_weight=W)); the line then carries the
+term's first and last 16-step mean ("distort": {...}).  Compare ms/step with a run without the option (and `--depth --distort W`
+with `--depth`) for the term's cost: the runs differ in nothing else, though their mean_count drifts apart as the geometry does."""
 import argparse
 import json
 import os
@@ -80,7 +83,7 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
 
 
 def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=True, capacity="bucket", seed=0, student_seed=0,
-                 error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True):
+                 error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True, distort_weight=None):
     from laenerf_amd.data import ResidentImages
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.optim import FusedAdam
@@ -92,6 +95,8 @@ def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=Tr
     opt = FusedAdam(net, param_groups=net.get_params(lr), betas=(0.9, 0.99), eps=1e-15, device_lr=True)
     data = ResidentImages.from_arrays(images, poses, intr, bg="random", device=dev, depths=depths)
     depth_kw = {} if depth_weight is None else {"depth_weight": depth_weight, "depth_grad": depth_grad}
+    if distort_weight is not None:
+        depth_kw["distort_weight"] = distort_weight
     return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map,
                    ema_decay=ema_decay, **depth_kw)
 
@@ -137,6 +142,7 @@ def main():
     ap.add_argument("--depth", action="store_true", help="also train a second student with depth supervision on the teacher's depth")
     ap.add_argument("--depth-weight", type=float, default=1e-3)
     ap.add_argument("--depth-value-only", action="store_true", help="depth_grad=False: the reference's value-only depth term")
+    ap.add_argument("--distort", type=float, default=None, metavar="W", help="Trainer(distort_weight=W) for every student of the run")
     args = ap.parse_args()
     error_map = None if args.error_map == "none" else args.error_map
     dev = torch.device("cuda:0")
@@ -145,7 +151,7 @@ def main():
     images, poses, intr = teacher_views(dev, args.views, args.res, args.res)
     held = 4
     tr = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
-                      capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None)
+                      capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, distort_weight=args.distort)
     all_in, steady = _timed_run(tr, args.steps)
     from laenerf_amd.data import ResidentImages
     test = ResidentImages.from_arrays(images[:held], poses[:held], intr, device=dev)
@@ -158,7 +164,7 @@ def main():
         planes = teacher_depths(dev, poses[held:], intr, args.res, args.res)
         td = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
                           capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, depths=planes,
-                          depth_weight=args.depth_weight, depth_grad=not args.depth_value_only)
+                          depth_weight=args.depth_weight, depth_grad=not args.depth_value_only, distort_weight=args.distort)
         d_all_in, d_steady = _timed_run(td, args.steps)
         d_psnr = td.evaluate(range(held), data=test, bg_color=1.0)
         _, d_group_ms = _replay_windows(td)
@@ -166,7 +172,9 @@ def main():
                  "depth_grad": not args.depth_value_only, "supervised_pixels_frac": round(float((planes > 0).mean()), 4),
                  "replay_ms_per_step_windows": [round(v, 4) for v in d_group_ms], "mean_count": td.r.mean_count,
                  "first_depth_loss": float(td.depth_losses()[:16].mean()), "final_depth_loss": float(td.depth_losses()[-16:].mean()),
-                 "final_loss": float(td.losses()[-16:].mean()), "heldout_psnr_white": round(d_psnr, 3), "steps_skipped": td.steps_skipped}
+                 "final_loss": float(td.losses()[-16:].mean()), "heldout_psnr_white": round(d_psnr, 3), "steps_skipped": td.steps_skipped,
+                 **({"first_distort_loss": float(td.distort_losses()[:16].mean()),
+                     "final_distort_loss": float(td.distort_losses()[-16:].mean())} if args.distort is not None else {})}
     print(json.dumps({
         "ms_per_step_all_in": round(all_in, 4), "ms_per_step_after_64": round(steady, 4), "steps": args.steps, "rays": args.rays,
         "ratio_to_headline": round(all_in / HEADLINE_MS, 3), "ratio_after_64_to_headline": round(steady / HEADLINE_MS, 3),
@@ -180,6 +188,8 @@ def main():
                       "replay_ms_per_step": round(float(np.median(group_ms)), 4) if group_ms else None,
                       "replay_ms_per_step_windows": [round(v, 4) for v in group_ms],
                       "padding_rows_frac": round(1 - tr._m() / tr._m_cap(), 4) if tr.r.mean_count > 0 else None},
+        **({"distort": {"distort_weight": args.distort, "first_distort_loss": float(tr.distort_losses()[:16].mean()),
+                        "final_distort_loss": float(tr.distort_losses()[-16:].mean())}} if args.distort is not None else {}),
         **({"depth": depth} if depth is not None else {}),
         "scene": f"{args.views - held} training + {held} held-out {args.res}x{args.res} RGBA uint8 views of a teacher network"}), flush=True)
 
