@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi17"
+#define LAE_ABI_TAG "abi18"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -967,6 +967,37 @@ LAE_API int lae_marching_cubes_count(const float* u, uint32_t nx, uint32_t ny, u
                              int32_t* counts, void* stream);
 LAE_API int lae_marching_cubes_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void* scratch, float* verts,
                             int32_t* tris, void* stream);
+
+/* ---- mesh export: per-vertex attributes of a marching-cubes mesh and the binary PLY bodies, on the device.
+ * lae_mesh_vertex_attrs: u [nx, ny, nz] fp32 (the field marching cubes ran on), verts [V, 3] fp32 in index space (as
+ *   lae_marching_cubes_emit writes them), the box (bmin, bmax) by value.  Outputs, each of which may be NULL: pos [V, 3],
+ *   normals [V, 3], dirs [V, 3], fp32.  One thread per vertex; deterministic (no atomics).  Sizes outside 2..512: LAE_EINVAL;
+ *   V == 0: LAE_OK before any launch; NULL u / verts: LAE_ENULL.
+ *   Position: v / (n_a - 1) * (bmax_a - bmin_a) + bmin_a per axis a (n_a: that axis's lattice size), with (bmax_a - bmin_a) formed
+ *     in fp32, the division, product and sum in fp64 without contraction, and one rounding to fp32.  On a cubic lattice this is
+ *     the reference's float64 scaling (nerf/utils.py:214-217) rounded to the fp32 a PLY stores.
+ *   Lattice gradient at a point p: d_a(p) = (u[p + e_a] - u[p - e_a]) * 0.5f; on a border the one-sided difference
+ *     u[p + e_a] - u[p] or u[p] - u[p - e_a].
+ *   Locating a vertex: a non-finite coordinate is treated as 0 (for the position too).  base = floor(v) clamped into [0, n - 1] per
+ *     axis, frac = v - base.  A vertex lies on a lattice edge, so at most one axis has frac > 0: the first such axis a (x < y < z)
+ *     gives t = frac_a and the edge's other end q = base + e_a, clamped; with no such axis t = 0.  Every index is clamped before any
+ *     load: garbage in verts can give garbage attributes, never a read outside u.
+ *   Normal: g_a = d_a(base) + t * (d_a(q) - d_a(base)); w_a = g_a * s_a with s_a = float(n_a - 1) / (bmax_a - bmin_a) in fp32 (the
+ *     gradient moved from index space to the box); len = sqrtf(w.w); normals = -w / len, dirs = w / len -- the normal points
+ *     towards lower values, which agrees with the face orientation above, and dirs is the direction along which a camera looking
+ *     straight at the surface sees it.  Where len is 0 or not finite: normals = 0, dirs = (0, 0, 1).
+ * lae_mesh_pack_ply: the bodies of a binary little-endian PLY.  vertex_bytes [V * stride]: per vertex `float x y z` from pos [V, 3],
+ *   then `float nx ny nz` if normals != NULL, then `uchar red green blue` if rgb != NULL (fp32 [V, 3]; a byte is
+ *   clip(x, 0, 1) * 255 truncated as in lae_eval_view's rgb_u8, NaN -> 0); stride = 12, 24, 15 or 27.  face_bytes [T * 13]: per
+ *   triangle `uchar 3` and three little-endian int from tris [T, 3].  Either half is skipped when its output is NULL or its count
+ *   is 0.  The bytes are those of the matching packed numpy structured arrays.  A workgroup stages its records in LDS and stores
+ *   whole dwords (bytes only for a buffer's last 1-3), so both output bases must be 4-byte aligned (LAE_EINVAL otherwise); a
+ *   present half with a NULL input is LAE_ENULL. */
+LAE_API int lae_mesh_vertex_attrs(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, const float* verts, uint32_t V, float bmin_x,
+                          float bmin_y, float bmin_z, float bmax_x, float bmax_y, float bmax_z, float* pos, float* normals, float* dirs,
+                          void* stream);
+LAE_API int lae_mesh_pack_ply(const float* pos, const float* normals, const float* rgb, uint32_t V, const int32_t* tris, uint32_t T,
+                      uint8_t* vertex_bytes, uint8_t* face_bytes, void* stream);
 
 /* ---- fused Adam + GradScaler (torch.optim.Adam / torch.cuda.amp.GradScaler in the reference: main_nerf.py:223,
  * nerf/utils.py:1474-1482).  `state` is a 64-byte device block:

@@ -101,6 +101,8 @@ SIGNATURES = {
     "lae_marching_cubes_scratch_bytes": [u32, u32, u32],
     "lae_marching_cubes_count": [vp, u32, u32, u32, f32, vp, vp, vp],
     "lae_marching_cubes_emit": [vp, u32, u32, u32, f32, vp, vp, vp, vp],
+    "lae_mesh_vertex_attrs": [vp, u32, u32, u32, vp, u32, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp],
+    "lae_mesh_pack_ply": [vp, vp, vp, u32, vp, u32, vp, vp, vp],
     "lae_style_loss_scratch_bytes": [u32],
     "lae_style_loss_forward": [vp, vp, vp, vp, u32, u32, f32, f32, f32, vp, vp, vp, vp, u32, f32, f32, vp],
     "lae_style_loss_backward": [vp, vp, vp, u32, u32, u32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, i32, f32, f32, vp],
@@ -152,7 +154,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi17"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi18"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

@@ -9,6 +9,9 @@
 //   vertices:  positions; per point the packed word base | mask << 29 (base = the point's first vertex id)
 //   triangles: each cube-local edge -> base[owner] + rank of its axis in the owner's mask; runs after the vertex pass, since
 //              a cube reads the words of points in other blocks
+//
+// Export (lae_mesh_vertex_attrs, lae_mesh_pack_ply): per-vertex position in the box, normal and view direction from the field
+// the mesh was cut from, and the binary PLY bodies assembled on the device.  The specification is in include/laenerf.h.
 #include "lae_common.h"
 
 namespace {
@@ -209,6 +212,146 @@ __global__ void __launch_bounds__(MC_THREADS) k_mc_triangles(const float* __rest
     }
 }
 
+// ---- vertex attributes: one thread per vertex
+constexpr int VA_THREADS = 256;
+
+struct Box {
+    float bmin[3], bmax[3];
+};
+
+// central difference of u along every axis at the lattice point p (one-sided on a border); p is inside the lattice, so is
+// every index read here
+__device__ __forceinline__ void lattice_gradient(const float* __restrict__ u, const Dims& d, const int (&p)[3], float (&g)[3]) {
+    const int n[3] = {(int)d.nx, (int)d.ny, (int)d.nz};
+    const uint32_t step[3] = {d.nyz, d.nz, 1u};
+    const uint32_t at = ((uint32_t)p[0] * d.ny + (uint32_t)p[1]) * d.nz + (uint32_t)p[2];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const bool lo = p[a] > 0, hi = p[a] + 1 < n[a];
+        const float diff = __fsub_rn(u[hi ? at + step[a] : at], u[lo ? at - step[a] : at]);
+        g[a] = lo && hi ? __fmul_rn(diff, 0.5f) : diff;
+    }
+}
+
+__global__ void __launch_bounds__(VA_THREADS) k_mesh_vertex_attrs(const float* __restrict__ u, Dims d, const float* __restrict__ verts,
+                                                                  uint32_t V, Box box, float* __restrict__ pos,
+                                                                  float* __restrict__ normals, float* __restrict__ dirs) {
+    const uint32_t i = blockIdx.x * VA_THREADS + threadIdx.x;
+    if (i >= V) return;
+    const int n[3] = {(int)d.nx, (int)d.ny, (int)d.nz};
+    float v[3], ext[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        v[a] = verts[3 * (uint64_t)i + a];
+        if (!__builtin_isfinite(v[a])) v[a] = 0.0f;
+        ext[a] = __fsub_rn(box.bmax[a], box.bmin[a]);
+    }
+    if (pos) {
+#pragma unroll
+        for (int a = 0; a < 3; a++)      // v / (n - 1) * (bmax - bmin) + bmin in fp64, each step rounded, one rounding to fp32
+            pos[3 * (uint64_t)i + a] = (float)__dadd_rn(__dmul_rn(__ddiv_rn((double)v[a], (double)(n[a] - 1)), (double)ext[a]), (double)box.bmin[a]);
+    }
+    if (!normals && !dirs) return;
+    int base[3], q[3];
+    float t = 0.0f;
+    int axis = -1;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float b = fminf(fmaxf(floorf(v[a]), 0.0f), (float)(n[a] - 1));      // clamped as a float: the conversion cannot overflow
+        base[a] = q[a] = (int)b;
+        const float frac = __fsub_rn(v[a], b);
+        if (axis < 0 && frac > 0.0f) { axis = a; t = frac; }
+    }
+    float g0[3], w[3];
+    lattice_gradient(u, d, base, g0);
+    if (axis >= 0) {
+        q[axis] = min(base[axis] + 1, n[axis] - 1);
+        float g1[3];
+        lattice_gradient(u, d, q, g1);
+#pragma unroll
+        for (int a = 0; a < 3; a++) g0[a] = __fadd_rn(g0[a], __fmul_rn(t, __fsub_rn(g1[a], g0[a])));
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) w[a] = __fmul_rn(g0[a], __fdiv_rn((float)(n[a] - 1), ext[a]));
+    const float len = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(w[0], w[0]), __fmul_rn(w[1], w[1])), __fmul_rn(w[2], w[2])));
+    const bool ok = len > 0.0f && __builtin_isfinite(len);
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float r = ok ? __fdiv_rn(w[a], len) : (a == 2 ? 1.0f : 0.0f);
+        if (dirs) dirs[3 * (uint64_t)i + a] = r;
+        if (normals) normals[3 * (uint64_t)i + a] = ok ? -r : 0.0f;
+    }
+}
+
+// ---- PLY bodies: a workgroup builds PK_RECORDS records in an LDS image and stores the image as whole dwords.  PK_RECORDS is a
+// multiple of 4, so every workgroup's part of the buffer starts on a dword whatever the record size; only the buffer's last
+// 1-3 bytes (last workgroup) go out as bytes.
+constexpr int PK_THREADS = 256;
+constexpr uint32_t PK_RECORDS = PK_THREADS;
+constexpr uint32_t PK_MAX_STRIDE = 27;
+
+// `clip(x, 0, 1) * 255`, truncated (evaluate.hip to_u8); NaN -> 0
+__device__ __forceinline__ uint32_t color_u8(float x) { return (uint32_t)(int)__fmul_rn(lae::clampf(x, 0.0f, 1.0f), 255.0f); }
+
+// a little-endian 32-bit word at byte offset `at` of the image: one dword store where it is aligned, four byte stores where not
+__device__ __forceinline__ void put32(uint32_t* img, uint32_t at, uint32_t w) {
+    if ((at & 3u) == 0u) {
+        img[at >> 2] = w;
+    } else {
+        uint8_t* b = reinterpret_cast<uint8_t*>(img) + at;
+        b[0] = (uint8_t)w; b[1] = (uint8_t)(w >> 8); b[2] = (uint8_t)(w >> 16); b[3] = (uint8_t)(w >> 24);
+    }
+}
+
+// FACES: records of 13 bytes (uchar 3, int[3]) from rec_a = tris; else vertex records of `stride` bytes from rec_a = pos,
+// rec_b = normals or NULL, rec_c = rgb or NULL
+template <bool FACES>
+__global__ void __launch_bounds__(PK_THREADS) k_mesh_pack(const void* __restrict__ rec_a, const float* __restrict__ rec_b,
+                                                          const float* __restrict__ rec_c, uint32_t count, uint32_t stride,
+                                                          uint8_t* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) uint32_t img[PK_RECORDS * (FACES ? 13u : PK_MAX_STRIDE) / 4];
+    const uint32_t first = blockIdx.x * PK_RECORDS;
+    const uint32_t here = min(PK_RECORDS, count - first);                 // the grid has no empty workgroup
+    const uint32_t r = threadIdx.x;
+    if (r < here) {
+        const uint64_t rec = (uint64_t)first + r;
+        uint32_t at = r * stride;
+        if (FACES) {
+            const int32_t* tri = static_cast<const int32_t*>(rec_a) + 3 * rec;
+            reinterpret_cast<uint8_t*>(img)[at] = 3;
+#pragma unroll
+            for (int c = 0; c < 3; c++) put32(img, at + 1 + 4 * c, (uint32_t)tri[c]);
+        } else {
+            const float* p = static_cast<const float*>(rec_a) + 3 * rec;
+#pragma unroll
+            for (int c = 0; c < 3; c++) put32(img, at + 4 * c, __float_as_uint(p[c]));
+            at += 12;
+            if (rec_b) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) put32(img, at + 4 * c, __float_as_uint(rec_b[3 * rec + c]));
+                at += 12;
+            }
+            if (rec_c) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) reinterpret_cast<uint8_t*>(img)[at + c] = (uint8_t)color_u8(rec_c[3 * rec + c]);
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t bytes = here * stride, dwords = bytes >> 2;
+    uint8_t* dst = out + (uint64_t)first * stride;                        // 4-byte aligned: first % 4 == 0 and so is `out`
+    uint32_t w0 = 0;
+    if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {                   // 16-byte stores while whole quads are left
+        const uint32_t quads = dwords >> 2;
+        for (uint32_t w = threadIdx.x; w < quads; w += PK_THREADS)
+            reinterpret_cast<uint4*>(dst)[w] = reinterpret_cast<const uint4*>(img)[w];
+        w0 = quads << 2;
+    }
+    for (uint32_t w = w0 + threadIdx.x; w < dwords; w += PK_THREADS) reinterpret_cast<uint32_t*>(dst)[w] = img[w];
+    const uint32_t tail = dwords << 2;
+    if (tail + threadIdx.x < bytes) dst[tail + threadIdx.x] = reinterpret_cast<const uint8_t*>(img)[tail + threadIdx.x];
+}
+
 int check_dims(uint32_t nx, uint32_t ny, uint32_t nz, Dims& d) {
     if (nx < 2 || ny < 2 || nz < 2 || nx > 512 || ny > 512 || nz > 512) return LAE_EINVAL;
     d = Dims{nx, ny, nz, ny * nz, nx * ny * nz};
@@ -259,6 +402,38 @@ int lae_marching_cubes_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t n
     if (vec_ok(u, d)) k_mc_triangles<true><<<nb, MC_THREADS, 0, s>>>(u, d, threshold, cv + nb, words, tris);
     else k_mc_triangles<false><<<nb, MC_THREADS, 0, s>>>(u, d, threshold, cv + nb, words, tris);
     return lae::check_launch("marching_cubes/triangles");
+}
+
+int lae_mesh_vertex_attrs(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, const float* verts, uint32_t V, float bmin_x,
+                          float bmin_y, float bmin_z, float bmax_x, float bmax_y, float bmax_z, float* pos, float* normals, float* dirs,
+                          void* stream) {
+    Dims d;
+    if (check_dims(nx, ny, nz, d)) return LAE_EINVAL;
+    if (V == 0) return LAE_OK;
+    if (!u || !verts) return LAE_ENULL;
+    if (!pos && !normals && !dirs) return LAE_OK;
+    const Box box{{bmin_x, bmin_y, bmin_z}, {bmax_x, bmax_y, bmax_z}};
+    k_mesh_vertex_attrs<<<lae::cdiv(V, VA_THREADS), VA_THREADS, 0, reinterpret_cast<hipStream_t>(stream)>>>(u, d, verts, V, box, pos,
+                                                                                                             normals, dirs);
+    return lae::check_launch("mesh_vertex_attrs");
+}
+
+int lae_mesh_pack_ply(const float* pos, const float* normals, const float* rgb, uint32_t V, const int32_t* tris, uint32_t T,
+                      uint8_t* vertex_bytes, uint8_t* face_bytes, void* stream) {
+    if ((reinterpret_cast<uintptr_t>(vertex_bytes) & 3) || (reinterpret_cast<uintptr_t>(face_bytes) & 3)) return LAE_EINVAL;
+    if ((vertex_bytes && V && !pos) || (face_bytes && T && !tris)) return LAE_ENULL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (vertex_bytes && V) {
+        const uint32_t stride = 12u + (normals ? 12u : 0u) + (rgb ? 3u : 0u);
+        k_mesh_pack<false><<<lae::cdiv(V, PK_RECORDS), PK_THREADS, 0, s>>>(pos, normals, rgb, V, stride, vertex_bytes);
+        int rc = lae::check_launch("mesh_pack_ply/vertices");
+        if (rc) return rc;
+    }
+    if (face_bytes && T) {
+        k_mesh_pack<true><<<lae::cdiv(T, PK_RECORDS), PK_THREADS, 0, s>>>(tris, nullptr, nullptr, T, 13u, face_bytes);
+        return lae::check_launch("mesh_pack_ply/faces");
+    }
+    return LAE_OK;
 }
 
 }  // extern "C"

@@ -6,11 +6,21 @@ instead of trimesh.
     marching_cubes_numpy(u, threshold)  the same specification restated in numpy (what the tests compare against)
     extract_fields / extract_geometry   the reference's lattice sweep and scaling, with the field kept on the device
     write_ply(path, vertices, triangles)
+    vertex_attributes(u, verts, bmin, bmax)  per-vertex position in the box, normal and view direction on the device
+    vertex_attributes_numpy(...)             the same specification restated in numpy
+    pack_ply / write_ply_packed              the PLY bodies assembled on the device; the file is a header plus two buffers
+    read_ply(path)                           reads what write_ply and write_ply_packed write
 
 The specification (include/laenerf.h, lae_marching_cubes_*): corner inside iff value > threshold (NaN outside); one vertex
 per crossed lattice edge, ordered by (lower point's linear index, axis x < y < z), at lower + t along the axis with
 t = (thr - a) / (b - a) in fp32 (non-finite -> 0.5, clamped to [0, 1]); triangles ordered by (cube linear index, table
 order) with welded vertex ids; the case table is tools/gen_mc_table.py's (csrc/mc_table.inc).
+
+Vertex attributes (include/laenerf.h, lae_mesh_vertex_attrs): position = v / (n - 1) * (bmax - bmin) + bmin in fp64 with fp32
+bounds, rounded once to fp32; the normal is the central-difference lattice gradient (one-sided on a border), interpolated
+along the vertex's lattice edge, moved to the box by (n - 1) / (bmax - bmin), normalised and negated (it points towards lower
+density, like the faces' right-hand normals); dirs = -normal is the direction a camera looking straight at the surface sees
+it along (fallback (0, 0, 1) where the gradient vanishes).
 """
 import os
 import re
@@ -177,3 +187,206 @@ def write_ply(path, vertices, triangles):
         f.write(head.encode("ascii"))
         f.write(v.tobytes())
         f.write(faces.tobytes())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# export with per-vertex attributes: lae_mesh_vertex_attrs, lae_mesh_pack_ply
+
+ATTRS = ("pos", "normals", "dirs")
+
+
+def _bounds32(b):
+    return np.asarray(torch.as_tensor(b).detach().cpu(), dtype=np.float32).reshape(3)
+
+
+def vertex_attributes(u, verts, bound_min, bound_max, want=ATTRS):
+    """u [nx,ny,nz] fp32 CUDA (the field marching cubes ran on), verts [V,3] fp32 CUDA in index space -> a dict with the entries
+    of `want` ("pos", "normals", "dirs"), each [V,3] fp32 on the device"""
+    need_cuda(u, verts)
+    if u.dtype != torch.float32 or verts.dtype != torch.float32:
+        raise RuntimeError("laenerf_amd.vertex_attributes: field and vertices must be float32")
+    need_contig(u, verts)
+    _check_shape(u.shape)
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise RuntimeError("laenerf_amd.vertex_attributes: vertices must be [V, 3]")
+    unknown = set(want) - set(ATTRS)
+    if unknown:
+        raise ValueError(f"laenerf_amd.vertex_attributes: unknown attribute(s) {sorted(unknown)}")
+    bmin, bmax = _bounds32(bound_min), _bounds32(bound_max)
+    V = verts.shape[0]
+    out = {k: torch.empty(V, 3, dtype=torch.float32, device=u.device) for k in ATTRS if k in want}
+    nx, ny, nz = u.shape
+    check(_lib.load().lae_mesh_vertex_attrs(ptr(u), nx, ny, nz, ptr(verts), V, *(float(x) for x in bmin), *(float(x) for x in bmax),
+                                            ptr(out.get("pos")), ptr(out.get("normals")), ptr(out.get("dirs")), stream()),
+          "mesh_vertex_attrs")
+    return out
+
+
+def edge_gradients_numpy(u, verts, dtype=np.float32):
+    """where lae_mesh_vertex_attrs looks for a vertex's gradient: -> (d(base) [V,3], d(q) [V,3], t [V]) in `dtype`, with base the
+    vertex's lower lattice point, q the other end of its lattice edge and t its fraction along it (index space)"""
+    u32 = np.ascontiguousarray(u, dtype=np.float32)
+    _check_shape(u32.shape)
+    f = np.dtype(dtype).type
+    n = np.array(u32.shape)
+    v = np.array(verts, dtype=np.float32).reshape(-1, 3)
+    v[~np.isfinite(v)] = 0
+    base_f = np.clip(np.floor(v), np.float32(0), (n - 1).astype(np.float32)[None, :])
+    base = base_f.astype(np.int64)
+    frac = v - base_f                                                        # fp32
+    has = frac > 0
+    on_edge = has.any(axis=1)
+    axis = np.argmax(has, axis=1)                                            # the first axis with frac > 0
+    rows = np.arange(len(v))
+    t = np.where(on_edge, frac[rows, axis], np.float32(0)).astype(f)
+    q = base.copy()
+    q[rows[on_edge], axis[on_edge]] = np.minimum(base[on_edge, axis[on_edge]] + 1, n[axis[on_edge]] - 1)
+    uu = u32.astype(f)
+
+    def grad(p):
+        g = np.empty((len(p), 3), f)
+        for a in range(3):
+            lo, hi = p.copy(), p.copy()
+            lo[:, a] = np.maximum(p[:, a] - 1, 0)
+            hi[:, a] = np.minimum(p[:, a] + 1, n[a] - 1)
+            diff = uu[hi[:, 0], hi[:, 1], hi[:, 2]] - uu[lo[:, 0], lo[:, 1], lo[:, 2]]
+            g[:, a] = np.where(hi[:, a] - lo[:, a] == 2, diff * f(0.5), diff)
+        return g
+
+    with np.errstate(all="ignore"):
+        return grad(base), grad(q), t
+
+
+def vertex_attributes_numpy(u, verts, bound_min, bound_max, dtype=np.float32):
+    """numpy restatement of lae_mesh_vertex_attrs -> dict(pos, normals, dirs), each [V,3], with fp32 operations in the kernel's
+    order.  dtype=np.float64 evaluates the gradient, normal and direction formulas in float64 instead (what the device's
+    normals are compared against); pos is fp32 and the same either way."""
+    f = np.dtype(dtype).type
+    n = np.array(np.shape(u))
+    bmin, bmax = _bounds32(bound_min), _bounds32(bound_max)
+    ext = bmax - bmin                                                        # fp32
+    g0, g1, t = edge_gradients_numpy(u, verts, dtype)
+    v = np.array(verts, dtype=np.float32).reshape(-1, 3)
+    v[~np.isfinite(v)] = 0
+    pos = (v.astype(np.float64) / (n - 1.0)[None, :] * ext.astype(np.float64)[None, :] + bmin.astype(np.float64)[None, :]).astype(np.float32)
+    with np.errstate(all="ignore"):
+        g = g0 + t[:, None] * (g1 - g0)
+        s = (n - 1).astype(np.float32).astype(f) / ext.astype(f)             # fp32: float(n - 1) / (bmax - bmin)
+        w = g * s[None, :]
+        length = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
+        ok = (length > 0) & np.isfinite(length)
+        unit = w / length[:, None]
+    dirs = np.where(ok[:, None], unit, np.array([0, 0, 1], f)[None, :]).astype(f)
+    normals = np.where(ok[:, None], -unit, f(0)).astype(f)
+    return dict(pos=pos, normals=normals, dirs=dirs)
+
+
+def color_bytes_numpy(rgb):
+    """lae_eval_view's rgb_u8 rule in numpy: clip(x, 0, 1) * 255 in fp32, truncated; NaN -> 0"""
+    x = np.asarray(rgb, dtype=np.float32)
+    x = np.where(np.isnan(x), np.float32(0), np.clip(x, np.float32(0), np.float32(1)))
+    return (x * np.float32(255)).astype(np.uint8)
+
+
+def vertex_dtype(normals=False, colors=False):
+    """the packed numpy record of one PLY vertex"""
+    fields = [("pos", "<f4", (3,))]
+    if normals:
+        fields.append(("normals", "<f4", (3,)))
+    if colors:
+        fields.append(("colors", "u1", (3,)))
+    return np.dtype(fields)
+
+
+FACE_DTYPE = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+
+
+def ply_header(V, T, normals=False, colors=False):
+    head = f"ply\nformat binary_little_endian 1.0\nelement vertex {V}\nproperty float x\nproperty float y\nproperty float z\n"
+    if normals:
+        head += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors:
+        head += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    return (head + f"element face {T}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
+
+
+def pack_ply(pos, tris, normals=None, colors=None):
+    """pos [V,3] fp32, tris [T,3] int32, optional normals [V,3] fp32 and colors [V,3] fp32 in [0, 1], all on the device ->
+    (header bytes, vertex_bytes [V * stride] uint8, face_bytes [T * 13] uint8); the two buffers stay on the device.  Triangle
+    indices are range-checked first (one host read; ValueError as in write_ply)."""
+    need_cuda(pos, tris, normals, colors)
+    need_contig(pos, tris, normals, colors)
+    for name, x in (("pos", pos), ("normals", normals), ("colors", colors)):
+        if x is not None and (x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3 or x.shape[0] != pos.shape[0]):
+            raise RuntimeError(f"laenerf_amd.pack_ply: {name} must be float32 [V, 3]")
+    if tris.dtype != torch.int32 or tris.dim() != 2 or tris.shape[1] != 3:
+        raise RuntimeError("laenerf_amd.pack_ply: tris must be int32 [T, 3]")
+    V, T = pos.shape[0], tris.shape[0]
+    if T and bool(((tris < 0) | (tris >= V)).any()):
+        raise ValueError("pack_ply: a triangle index is out of range")
+    stride = vertex_dtype(normals is not None, colors is not None).itemsize
+    vb = torch.empty(V * stride, dtype=torch.uint8, device=pos.device)
+    fb = torch.empty(T * FACE_DTYPE.itemsize, dtype=torch.uint8, device=pos.device)
+    check(_lib.load().lae_mesh_pack_ply(ptr(pos), ptr(normals), ptr(colors), V, ptr(tris), T, ptr(vb) if V else None,
+                                        ptr(fb) if T else None, stream()), "mesh_pack_ply")
+    return ply_header(V, T, normals is not None, colors is not None), vb, fb
+
+
+def write_ply_packed(path, header, vertex_bytes, face_bytes):
+    """one copy to the host and one write per buffer"""
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header)
+        for buf in (vertex_bytes, face_bytes):
+            f.write(memoryview(buf.cpu().numpy()))
+
+
+_PLY_PROPS = {("x", "y", "z"): ("vertices", "float", "<f4"), ("nx", "ny", "nz"): ("normals", "float", "<f4"),
+              ("red", "green", "blue"): ("colors", "uchar", "u1")}
+
+
+def read_ply(path):
+    """a binary little-endian PLY as write_ply / write_ply_packed write it -> dict(vertices [V,3] fp32, triangles [T,3] int32,
+    and normals [V,3] fp32 / colors [V,3] uint8 where the file has them)"""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or lines[1] != "format binary_little_endian 1.0":
+        raise ValueError("read_ply: not a binary little-endian PLY 1.0")
+    V = T = None
+    props, element = [], None
+    for ln in lines[2:]:
+        w = ln.split()
+        if w[:1] == ["element"]:
+            element = w[1]
+            if element == "vertex":
+                V = int(w[2])
+            elif element == "face":
+                T = int(w[2])
+            else:
+                raise ValueError(f"read_ply: unknown element {element}")
+        elif w[:1] == ["property"]:
+            if element == "vertex":
+                props.append((w[1], w[2]))
+            elif w[1:] != ["list", "uchar", "int", "vertex_indices"]:
+                raise ValueError(f"read_ply: unsupported face property `{ln}`")
+    if V is None or T is None or len(props) % 3:
+        raise ValueError("read_ply: the header names no vertex / face element or an unknown vertex layout")
+    fields = []
+    for i in range(0, len(props), 3):
+        names, types = tuple(n for _, n in props[i:i + 3]), {t for t, _ in props[i:i + 3]}
+        if names not in _PLY_PROPS or types != {_PLY_PROPS[names][1]}:
+            raise ValueError(f"read_ply: unknown vertex properties {names}")
+        fields.append((_PLY_PROPS[names][0], _PLY_PROPS[names][2], (3,)))
+    vdt = np.dtype(fields)
+    if len(data) != end + V * vdt.itemsize + T * FACE_DTYPE.itemsize:
+        raise ValueError("read_ply: the file's size does not match its header")
+    verts = np.frombuffer(data, vdt, V, end)
+    faces = np.frombuffer(data, FACE_DTYPE, T, end + V * vdt.itemsize)
+    if T and not (faces["n"] == 3).all():
+        raise ValueError("read_ply: a face is not a triangle")
+    out = {name: np.ascontiguousarray(verts[name]) for name in vdt.names}
+    out["triangles"] = np.ascontiguousarray(faces["i"]).astype(np.int32)
+    return out

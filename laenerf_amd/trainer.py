@@ -304,9 +304,11 @@ class Trainer:
         """optimizer steps the GradScaler skipped (non-finite gradients)"""
         return self.opt.steps_skipped
 
-    def save_mesh(self, path, resolution=256, threshold=10):
-        """nerf/utils.py:722-741: the renderer's mesh as a binary PLY"""
-        return self.r.save_mesh(path, resolution=resolution, threshold=threshold)
+    def save_mesh(self, path, resolution=256, threshold=10, normals=False, colors=False, **kwargs):
+        """nerf/utils.py:722-741: the renderer's mesh as a binary PLY; normals / colors add per-vertex attributes"""
+        if not normals and not colors:
+            return self.r.save_mesh(path, resolution=resolution, threshold=threshold)
+        return self.r.save_mesh(path, resolution=resolution, threshold=threshold, normals=normals, colors=colors, **kwargs)
 
     @torch.no_grad()
     def evaluate(self, views, data=None, bg_color=1.0):

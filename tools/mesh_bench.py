@@ -9,6 +9,16 @@ teacher.  Prints one JSON line with, per resolution R:
     mc_bytes         bytes the marching-cubes passes must move: the field read by three passes, the per-point words written and
                      read, block counts, vertices and triangles written; mc_floor_us = mc_bytes / 6.29 TB/s
     ref_loop_ms      for contrast: the reference-shaped field loop (host lattice per chunk, a .cpu() copy per 128^3 chunk)
+    attrs_us         lae_mesh_vertex_attrs (pos, normals, dirs) from HIP events: [median, min, max] of --reps launches;
+                     attrs_bytes = 12 in + 36 out per vertex + the field once (every line touched, each counted once),
+                     attrs_floor_us = attrs_bytes / 6.29 TB/s
+    pack_us          lae_mesh_pack_ply (27-byte vertex records and the 13-byte face records), same form;
+                     pack_bytes = (36 + 27) V + (12 + 13) T, pack_floor_us
+    color_ms         the colour query model(pos, dirs) over all vertices in 1 << 20-row chunks
+    save_mesh_color_ms   save_mesh(normals=True, colors=True): attributes and PLY bodies on the device
+    host_color_ms    the same file the host-shaped way: field and mesh downloaded, vertex_attributes_numpy, the colour query on
+                     the device from uploaded positions, numpy structured arrays, one write per array
+    Each *_ms value of the three save paths comes with *_ms_range = [min, max]; the three are timed alternately, in one run.
 Host clocks around work that ends in a device synchronise; medians of --reps runs after one warm-up.  Kernel times per pass: run
 this under `rocprofv3 --kernel-trace --stats` (k_mc_count, k_mc_scan, k_mc_vertices, k_mc_triangles).
 
@@ -51,6 +61,58 @@ def timed(fn, reps):
         torch.cuda.synchronize()
         out.append((time.perf_counter() - t0) * 1e3)
     return float(np.median(out)), res
+
+
+def timed_range(fns, reps):
+    """several host-timed paths, alternated: one warm-up each, then reps rounds -> [(median, min, max)]"""
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(reps):
+        for o, fn in zip(out, fns):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            o.append((time.perf_counter() - t0) * 1e3)
+    return [(float(np.median(o)), float(min(o)), float(max(o))) for o in out]
+
+
+def event_us(fn, reps):
+    """one launch between two HIP events, reps times after two warm-ups -> [median, min, max] us"""
+    fn(); fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) * 1e3)
+    return [round(float(np.median(out)), 1), round(min(out), 1), round(max(out), 1)]
+
+
+def host_colored_save(r, path, R, thr, query, bmin, bmax):
+    """save_mesh(normals=True, colors=True) the host-shaped way"""
+    from laenerf_amd import mesh
+    u = mesh.extract_fields(bmin, bmax, R, query)
+    v, t = mesh.marching_cubes(u, thr)
+    un, vn, tn = u.cpu().numpy(), v.cpu().numpy(), t.cpu().numpy()
+    a = mesh.vertex_attributes_numpy(un, vn, bmin, bmax)
+    pos, dirs = torch.from_numpy(a["pos"]).cuda(), torch.from_numpy(a["dirs"]).cuda()
+    rgb = torch.empty_like(pos)
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+        for i in range(0, len(vn), 1 << 20):
+            rgb[i:i + (1 << 20)] = r.model(pos[i:i + (1 << 20)], dirs[i:i + (1 << 20)])[1].float()
+    verts = np.empty(len(vn), mesh.vertex_dtype(True, True))
+    verts["pos"], verts["normals"], verts["colors"] = a["pos"], a["normals"], mesh.color_bytes_numpy(rgb.cpu().numpy())
+    faces = np.empty(len(tn), mesh.FACE_DTYPE)
+    faces["n"], faces["i"] = 3, tn
+    with open(path, "wb") as f:
+        f.write(mesh.ply_header(len(vn), len(tn), True, True))
+        f.write(verts.tobytes())
+        f.write(faces.tobytes())
 
 
 def reference_loop(bmin, bmax, R, query, S=128):
@@ -111,12 +173,45 @@ def main():
         P, nb = R ** 3, (R ** 3 + 1023) // 1024
         row["mc_bytes"] = 3 * 4 * P + 4 * P + 4 * P + 4 * 4 * nb + 12 * V + 12 * T
         row["mc_floor_us"] = round(row["mc_bytes"] / (HBM_TBS * 1e12) * 1e6, 1)
+        if V:
+            verts, tris = verts[:V], tris[:T]
+            at = {k: torch.empty(V, 3, device=dev) for k in ("pos", "normals", "dirs")}
+            box = [float(x) for x in bmin] + [float(x) for x in bmax]
+            row["attrs_us"] = event_us(lambda: _lib.check(lib.lae_mesh_vertex_attrs(
+                u.data_ptr(), nx, ny, nz, verts.data_ptr(), V, *box, at["pos"].data_ptr(), at["normals"].data_ptr(),
+                at["dirs"].data_ptr(), _lib.stream()), "attrs"), args.reps)
+            row["attrs_bytes"] = (12 + 36) * V + 4 * P
+            row["attrs_floor_us"] = round(row["attrs_bytes"] / (HBM_TBS * 1e12) * 1e6, 1)
+            rgb = torch.rand(V, 3, device=dev)
+            vb = torch.empty(V * 27, dtype=torch.uint8, device=dev)
+            fb = torch.empty(T * 13, dtype=torch.uint8, device=dev)
+            row["pack_us"] = event_us(lambda: _lib.check(lib.lae_mesh_pack_ply(
+                at["pos"].data_ptr(), at["normals"].data_ptr(), rgb.data_ptr(), V, tris.data_ptr(), T, vb.data_ptr(), fb.data_ptr(),
+                _lib.stream()), "pack"), args.reps)
+            row["pack_bytes"] = (36 + 27) * V + (12 + 13) * T
+            row["pack_floor_us"] = round(row["pack_bytes"] / (HBM_TBS * 1e12) * 1e6, 1)
+
+            @torch.no_grad()
+            def colors():
+                out = torch.empty(V, 3, device=dev)
+                with torch.autocast("cuda", dtype=torch.float16):
+                    for i in range(0, V, 1 << 20):
+                        out[i:i + (1 << 20)] = r.model(at["pos"][i:i + (1 << 20)], at["dirs"][i:i + (1 << 20)])[1].float()
+                return out
+
+            row["color_ms"], _ = timed(colors, args.reps)
+            del at, rgb, vb, fb
         del u, scratch, verts, tris
         row["extract_mesh_ms"], _ = timed(lambda: r.extract_mesh(resolution=R, threshold=thr), args.reps)
         if not args.no_ply:
             with tempfile.TemporaryDirectory() as d:
-                row["save_mesh_ms"], _ = timed(lambda: r.save_mesh(os.path.join(d, "m.ply"), resolution=R, threshold=thr),
-                                               max(1, args.reps // 2))
+                f = os.path.join(d, "m.ply")
+                res = timed_range([lambda: r.save_mesh(f, resolution=R, threshold=thr),
+                                   lambda: r.save_mesh(f, resolution=R, threshold=thr, normals=True, colors=True),
+                                   lambda: host_colored_save(r, f, R, thr, query, bmin, bmax)], max(1, args.reps // 2))
+                for name, (med, lo, hi) in zip(("save_mesh_ms", "save_mesh_color_ms", "host_color_ms"), res):
+                    row[name], row[name + "_range"] = med, [round(lo, 3), round(hi, 3)]
+                row["ply_color_bytes"] = os.path.getsize(f)
         row["ref_loop_ms"], _ = timed(lambda: reference_loop(bmin, bmax, R, query), max(1, args.reps // 2))
         out[str(R)] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in row.items()}
         torch.cuda.empty_cache()
