@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi18"
+#define LAE_ABI_TAG "abi19"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -998,6 +998,38 @@ LAE_API int lae_mesh_vertex_attrs(const float* u, uint32_t nx, uint32_t ny, uint
                           void* stream);
 LAE_API int lae_mesh_pack_ply(const float* pos, const float* normals, const float* rgb, uint32_t V, const int32_t* tris, uint32_t T,
                       uint8_t* vertex_bytes, uint8_t* face_bytes, void* stream);
+
+/* ---- nearest-neighbour feature matching (NNFM: ARF, Ref-NPR; editing/semantic_encoder.py:83-164 nn_feat_replace /
+ * argmin_cos_distance / cos_loss, editing/ref_loss.py NNFMLoss) without the Na x Nb distance matrix (csrc/nnfm.hip).
+ * Features are fp32, channel-major [n, C, N]; n independent matching problems (n = 1, C = L * C': the layers concatenated;
+ * n = L: one matching per layer).  1 <= n <= 65535, 1 <= C <= 65536, N <= 2^23 (LAE_EINVAL otherwise); a required NULL pointer is
+ * LAE_ENULL; Na == 0 (pack: N == 0) returns LAE_OK before any pointer is looked at.  No host read, no allocation: capturable.
+ * lae_nnfm_pack: per position v / (sqrt(sum v^2 + 1e-8) + 1e-8), rounded to fp16, position-major [n, N_pad, C_pad] (channel
+ *   contiguous; N_pad = N rounded up to 64, C_pad = C rounded up to 32; the padding is zero-filled by the kernel).  packed:
+ *   lae_nnfm_packed_bytes(n, C, N) bytes, 16-byte aligned.
+ * lae_nnfm_match: z [n, Na] int32 = argmax_j of the cosine of packed content row i and packed style column j < Nb (fp16 operands,
+ *   fp32 accumulation on the matrix cores); d_best [n, Na] (may be NULL) = 1 - that cosine.  Among equal cosines the lowest index
+ *   wins; the result does not depend on the schedule (fixed-order combination of per-chunk partial results, no atomics).
+ *   workspace: lae_nnfm_match_bytes(n, Na, Nb) bytes, 8-byte aligned.  Non-finite features give z = 0 and d_best = NaN.
+ * lae_nnfm_workspace_bytes: the match workspace (rounded up to 256) + the packed content side, what one loss evaluation needs
+ *   beside its inputs; the three *_bytes helpers are host functions and need no GPU.
+ * lae_nnfm_loss_forward: cos_loss(x, gather(s, z)) on the fp32 features: with a = x[:, i], t = s[:, z_i], a^ = a / (|a| + 1e-8),
+ *   t^ = t / (|t| + 1e-8): loss[0] = mean over the n * Na positions of (1 - a^ . t^), summed in a fixed order (two runs give the same
+ *   bits).  stats [4, n * Na] fp32 (written; the backward reads it): a . t^, |a|, |t|, the position's term.  z outside 0..Nb-1 is
+ *   clamped before any load.
+ * lae_nnfm_loss_backward: dx [n, C, Na] = -(g / (n Na)) (t^ / s_a - (a . t^) a / (|a| s_a^2)), s_a = |a| + 1e-8, g = g_loss_dev[0]
+ *   (a device scalar).  One departure from the reference: a content position whose vector is exactly zero contributes 1 to the
+ *   loss and a zero gradient (autograd gives NaN there through sqrt at 0). */
+LAE_API uint64_t lae_nnfm_packed_bytes(uint32_t n, uint32_t C, uint32_t N);
+LAE_API uint64_t lae_nnfm_match_bytes(uint32_t n, uint32_t Na, uint32_t Nb);
+LAE_API uint64_t lae_nnfm_workspace_bytes(uint32_t n, uint32_t C, uint32_t Na, uint32_t Nb);
+LAE_API int lae_nnfm_pack(const float* feats, uint32_t n, uint32_t C, uint32_t N, void* packed, void* stream);
+LAE_API int lae_nnfm_match(const void* a_packed, const void* b_packed, uint32_t n, uint32_t Na, uint32_t Nb, uint32_t C, int32_t* z,
+                   float* d_best, void* workspace, void* stream);
+LAE_API int lae_nnfm_loss_forward(const float* x, const float* s, const int32_t* z, uint32_t n, uint32_t C, uint32_t Na, uint32_t Nb,
+                          float* loss, float* stats, void* stream);
+LAE_API int lae_nnfm_loss_backward(const float* x, const float* s, const int32_t* z, const float* stats, const float* g_loss_dev, uint32_t n,
+                           uint32_t C, uint32_t Na, uint32_t Nb, float* dx, void* stream);
 
 /* ---- fused Adam + GradScaler (torch.optim.Adam / torch.cuda.amp.GradScaler in the reference: main_nerf.py:223,
  * nerf/utils.py:1474-1482).  `state` is a 64-byte device block:

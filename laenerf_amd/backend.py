@@ -1024,6 +1024,61 @@ class _Style:
 
 style_backend = _Style
 
+
+class _Nnfm:
+    """nearest-neighbour feature matching (include/laenerf.h lae_nnfm_*; csrc/nnfm.hip).  Features fp32 [n, C, N], contiguous."""
+
+    @staticmethod
+    def packed_bytes(n, C, N):
+        return int(_lib.load().lae_nnfm_packed_bytes(n, C, N))
+
+    @staticmethod
+    def match_bytes(n, Na, Nb):
+        return int(_lib.load().lae_nnfm_match_bytes(n, Na, Nb))
+
+    @staticmethod
+    def workspace_bytes(n, C, Na, Nb):
+        return int(_lib.load().lae_nnfm_workspace_bytes(n, C, Na, Nb))
+
+    @staticmethod
+    def pack(feats, n, C, N, packed):
+        need_cuda(feats, packed); need_contig(feats, packed)
+        if feats.dtype != torch.float32 or feats.numel() < n * C * N or packed.numel() * packed.element_size() < _Nnfm.packed_bytes(n, C, N):
+            raise RuntimeError("nnfm_pack: features float32 [n, C, N], packed at least lae_nnfm_packed_bytes(n, C, N) bytes")
+        check(_lib.load().lae_nnfm_pack(ptr(feats), n, C, N, ptr(packed), stream()), "nnfm_pack")
+
+    @staticmethod
+    def match(a_packed, b_packed, n, Na, Nb, C, z, d_best, workspace):
+        ts = (a_packed, b_packed, z, d_best, workspace)
+        need_cuda(*ts); need_contig(*ts)
+        nbytes = lambda t: t.numel() * t.element_size()
+        if z.dtype != torch.int32 or z.numel() < n * Na or (d_best is not None and (d_best.dtype != torch.float32 or d_best.numel() < n * Na)) \
+                or nbytes(a_packed) < _Nnfm.packed_bytes(n, C, Na) or nbytes(b_packed) < _Nnfm.packed_bytes(n, C, Nb) \
+                or nbytes(workspace) < _Nnfm.match_bytes(n, Na, Nb):
+            raise RuntimeError("nnfm_match: z int32 [n, Na], d_best float32 [n, Na], packed sides and workspace of their *_bytes sizes")
+        check(_lib.load().lae_nnfm_match(ptr(a_packed), ptr(b_packed), n, Na, Nb, C, ptr(z), ptr(d_best), ptr(workspace), stream()), "nnfm_match")
+
+    @staticmethod
+    def loss_forward(x, s, z, n, C, Na, Nb, loss, stats):
+        ts = (x, s, z, loss, stats)
+        need_cuda(*ts); need_contig(*ts)
+        if x.dtype != torch.float32 or s.dtype != torch.float32 or z.dtype != torch.int32 or loss.dtype != torch.float32 or \
+                stats.dtype != torch.float32 or x.numel() < n * C * Na or s.numel() < n * C * Nb or z.numel() < n * Na or stats.numel() < 4 * n * Na:
+            raise RuntimeError("nnfm_loss_forward: x [n, C, Na], s [n, C, Nb] float32, z [n, Na] int32, stats [4, n * Na] float32")
+        check(_lib.load().lae_nnfm_loss_forward(ptr(x), ptr(s), ptr(z), n, C, Na, Nb, ptr(loss), ptr(stats), stream()), "nnfm_loss_forward")
+
+    @staticmethod
+    def loss_backward(x, s, z, stats, g_loss, n, C, Na, Nb, dx):
+        ts = (x, s, z, stats, g_loss, dx)
+        need_cuda(*ts); need_contig(*ts)
+        if g_loss.dtype != torch.float32 or dx.dtype != torch.float32 or dx.numel() < n * C * Na:
+            raise RuntimeError("nnfm_loss_backward: g_loss a float32 device scalar, dx float32 [n, C, Na]")
+        check(_lib.load().lae_nnfm_loss_backward(ptr(x), ptr(s), ptr(z), ptr(stats), ptr(g_loss), n, C, Na, Nb, ptr(dx), stream()),
+              "nnfm_loss_backward")
+
+
+nnfm_backend = _Nnfm
+
 for _cls in (_RayMarching, _GridEncoder, _SHEncoder, _FFMLP):
     for _k, _v in list(vars(_cls).items()):
         if isinstance(_v, staticmethod) and not _k.startswith("_") and _k not in ("fused_backward_available", "ffmlp_set_mode", "set_backward_mode",

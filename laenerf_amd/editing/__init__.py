@@ -5,3 +5,4 @@ from .recolor import RecolorView, compose_numpy, recolor_views, render_recolored
 from .style_trainer import EditSet, StyleTrainer, image_terms_on, jitter_numpy  # noqa: F401
 from .distill import DistillSet, compose_distill_numpy, distill_images, distill_nerf, distill_steps, error_map_seed_numpy  # noqa: F401
 from .style_network import StyleNetwork, load_style_image, load_vgg19_features  # noqa: F401
+from .nnfm import nnfm_loss, nnfm_match, nnfm_numpy, nnfm_pack, nnfm_workspace_bytes  # noqa: F401

@@ -195,7 +195,8 @@ class LAENeRF(nn.Module):
     """style_encoder.py:20-90.  `params` needs `.bound` and `.num_palette_bases`.  With style_weight > 0 and a style image and
     VGG weights (the arguments `style_img` [3,H,W] / `vgg` (a load_vgg19_features module, a path or a state dict), or `params.style_image` /
     `params.vgg_weights` paths) it builds `style_transfer_net` (editing/style_network.py StyleNetwork with params.style_layers, default
-    (10, 12, 14), and crop size `size`); otherwise style_transfer_net is None."""
+    (10, 12, 14), crop size `size`, and the style loss `params.style_loss` ("gram", the default, or "nnfm" with `params.nnfm_match`
+    "concat" / "layer": editing/nnfm.py); otherwise style_transfer_net is None."""
 
     def __init__(self, params, encoding="hashgrid", dir_encoding=None, num_layers=3, hidden_dim=64, color_palette=None, size=256,
                  style_img=None, vgg=None, style_generator=None):
@@ -232,7 +233,9 @@ class LAENeRF(nn.Module):
                 layers = tuple(getattr(params, "style_layers", None) or (10, 12, 14))
                 if not isinstance(vgg, nn.Module):
                     vgg = sn.load_vgg19_features(vgg, max(layers))
-                self.style_transfer_net = sn.StyleNetwork(style_img, vgg, style_layers=layers, size=size, generator=style_generator)
+                self.style_transfer_net = sn.StyleNetwork(style_img, vgg, style_layers=layers, size=size, generator=style_generator,
+                                                          loss=getattr(params, "style_loss", None) or "gram",
+                                                          nnfm_match=getattr(params, "nnfm_match", None) or "concat")
 
     def style_loss(self, img):
         """style_encoder.py: the VGG Gram loss of the [3,h,w] image `img` (StyleNetwork.forward)"""

@@ -120,12 +120,25 @@ def gram_matrix(feats):
 
 
 class StyleNetwork(nn.Module):
-    """StyleNetwork(style_image [3,H,W], vgg, style_layers=(10, 12, 14), size=256, crop_offset=None, generator=None).
+    """StyleNetwork(style_image [3,H,W], vgg, style_layers=(10, 12, 14), size=256, crop_offset=None, generator=None, loss="gram",
+    nnfm_match="concat").
     `vgg`: load_vgg19_features(...) (at least max(style_layers) + 1 layers).  Buffers: gram_style (of the random crop) and gram_target
-    (what the loss compares against: gram_style, or the colour-matched Gram after match_color)."""
+    (what the loss compares against: gram_style, or the colour-matched Gram after match_color).
+    The chosen loss is kept as `loss_kind`.  loss="nnfm": loss_from_input is the nearest-neighbour feature matching loss
+    (editing/nnfm.py) against the crop's features;
+    further buffers nnfm_style [L,C,h'w'] (the crop's features), nnfm_target (what the loss matches against) and nnfm_packed (the
+    matcher's fp16 copy of nnfm_target in the `nnfm_match` arrangement: "concat" = the layers concatenated, one matching; "layer" =
+    one matching per layer).  match_color then also re-derives the NNFM target: the features of the SAME crop of the matched
+    image, normalized as at construction, so the buffers keep their shapes and addresses (captured steps read them)."""
 
-    def __init__(self, style_image, vgg, style_layers=(10, 12, 14), size=256, crop_offset=None, generator=None):
+    def __init__(self, style_image, vgg, style_layers=(10, 12, 14), size=256, crop_offset=None, generator=None, loss="gram",
+                 nnfm_match="concat"):
         super().__init__()
+        if loss not in ("gram", "nnfm"):
+            raise ValueError(f"StyleNetwork: loss must be 'gram' or 'nnfm', not {loss!r}")
+        if nnfm_match not in ("concat", "layer"):
+            raise ValueError(f"StyleNetwork: nnfm_match must be 'concat' or 'layer', not {nnfm_match!r}")
+        self.loss_kind, self.nnfm_match = loss, nnfm_match
         self.style_layers = tuple(int(i) for i in style_layers)
         if not self.style_layers:
             raise ValueError("StyleNetwork: no style layers")
@@ -146,10 +159,20 @@ class StyleNetwork(nn.Module):
         self.register_buffer("mean", torch.tensor(IMAGENET_MEAN, device=dev).view(3, 1, 1))
         self.register_buffer("std", torch.tensor(IMAGENET_STD, device=dev).view(3, 1, 1))
         with torch.no_grad():
-            crop = random_crop(img, self.size, generator=generator, crop_offset=crop_offset)
-            gs = gram_matrix(self.features(self.normalize(crop)))
+            if crop_offset is None:                    # the draw random_crop would make, kept for match_color's NNFM target
+                crop_offset = random_crop_params(img.shape[1], img.shape[2], self.size, generator)[2:]
+            self.crop_offset = (int(crop_offset[0]), int(crop_offset[1]))
+            crop = random_crop(img, self.size, crop_offset=self.crop_offset)
+            feats = self.features(self.normalize(crop))
+            gs = gram_matrix(feats)
         self.register_buffer("gram_style", gs)
         self.register_buffer("gram_target", gs.clone())
+        if loss == "nnfm":
+            from .nnfm import nnfm_pack, _as_problems
+            fs = feats.flatten(2).float().contiguous()
+            self.register_buffer("nnfm_style", fs)
+            self.register_buffer("nnfm_target", fs.clone())
+            self.register_buffer("nnfm_packed", nnfm_pack(_as_problems(fs, nnfm_match)))
 
     def normalize(self, img):
         return (img - self.mean) / self.std
@@ -171,7 +194,11 @@ class StyleNetwork(nn.Module):
         return torch.stack(outs)
 
     def loss_from_input(self, vgg_in):
-        """MSE(gram(vgg(vgg_in)), gram_target) for the normalized [3,S,S] VGG input"""
+        """the style loss of the normalized [3,S,S] VGG input: MSE(gram(vgg(vgg_in)), gram_target), or with loss="nnfm" the
+        nearest-neighbour feature matching loss of vgg(vgg_in) against nnfm_target"""
+        if self.loss_kind == "nnfm":
+            from .nnfm import nnfm_loss
+            return nnfm_loss(self.features(vgg_in), self.nnfm_target, packed_style=self.nnfm_packed, match=self.nnfm_match)
         return F.mse_loss(gram_matrix(self.features(vgg_in)), self.gram_target)
 
     def forward(self, img):
@@ -199,9 +226,22 @@ class StyleNetwork(nn.Module):
         ts = Qs @ torch.linalg.inv(Qt) @ t
         matched = torch.clamp(ts.reshape(img.shape) + mu_s, 0, 1)
         self.gram_target.copy_(gram_matrix(self.features(matched)))
+        if self.loss_kind == "nnfm":
+            crop = random_crop(matched, self.size, crop_offset=self.crop_offset)
+            self._set_nnfm_target(self.features(self.normalize(crop)).flatten(2).float())
         return matched
 
+    def _set_nnfm_target(self, feats):
+        """nnfm_target and its packed copy, in place"""
+        from ..backend import nnfm_backend
+        from .nnfm import _as_problems
+        self.nnfm_target.copy_(feats)
+        f = _as_problems(self.nnfm_target, self.nnfm_match)
+        nnfm_backend.pack(f, f.shape[0], f.shape[1], f.shape[2], self.nnfm_packed)
+
     def reset_target(self):
-        """gram_target = gram_style"""
+        """gram_target = gram_style (and the NNFM target = the crop's features)"""
         with torch.no_grad():
             self.gram_target.copy_(self.gram_style)
+            if self.loss_kind == "nnfm":
+                self._set_nnfm_target(self.nnfm_style)
