@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi19"
+#define LAE_ABI_TAG "abi20"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -1030,6 +1030,39 @@ LAE_API int lae_nnfm_loss_forward(const float* x, const float* s, const int32_t*
                           float* loss, float* stats, void* stream);
 LAE_API int lae_nnfm_loss_backward(const float* x, const float* s, const int32_t* z, const float* stats, const float* g_loss_dev, uint32_t n,
                            uint32_t C, uint32_t Na, uint32_t Nb, float* dx, void* stream);
+
+/* ---- ray registration of the single-reference-view stylization (Ref-NPR; editing/single_view_edit_dataset.py:317-349
+ * get_ref_supervision and its caller :219-232) as a truncated nearest-neighbour search in a uniform cell grid (csrc/rayreg.hip).
+ * All points fp32 [.,3]; M cloud points, n query rows, both <= 2^30; radius > 0 and finite (LAE_EINVAL otherwise); a required NULL
+ * pointer is LAE_ENULL; n == 0 returns LAE_OK before any pointer is looked at.  No host read, no allocation: capturable.
+ * lae_rayreg_build: the grid of the cloud ref_x [M,3] into `grid` (lae_rayreg_build_bytes(M) bytes, 16-byte aligned): a 256-byte
+ *   record (fp32 lo[3], s, 1/s; uint32 G[3], cells, ...), the table of cell ends and the cell-sorted copy of the FINITE points as
+ *   float4 (x, y, z, bits of the original index).  The cell side s >= radius * (1 + 2^-10) and the cells per axis G <= 1024 are
+ *   chosen on the device from the bounding box (rayreg.hip derives the margin).  M == 0 builds the empty grid (ref_x may be NULL).
+ * lae_rayreg_query: per row of x [n,3]: d = min(radius, distance to the nearest cloud point), nn = that point's original index or
+ *   -1 where no point lies within radius (d < radius in fp32 <=> nn >= 0).  The squared distance is
+ *   fmaf(dz, dz, fmaf(dy, dy, dx * dx)) on fp32 differences, d its sqrtf; among equal squared distances the lowest original index
+ *   wins, so the result does not depend on the schedule.  d is exact over ALL M points whenever it is below radius.  Non-finite
+ *   rows and M == 0 give d = radius, nn = -1.  radius and M must be the build's.  mode: LAE_RAYREG_BINNED (queries binned by cell, a
+ *   workgroup per cell chunk, neighbour cells streamed through LDS) or LAE_RAYREG_GATHER (a lane per query; the A/B predecessor,
+ *   same results).  workspace: lae_rayreg_query_bytes(n, M) bytes, 16-byte aligned; after a BINNED call its last 256 bytes start
+ *   with a uint64: the distance evaluations of the call.
+ * lae_rayreg_supervise: row i is registered iff nn[i] >= 0 and d[i] < reg_dist (0 < reg_dist <= radius, guide_min < radius).
+ *   stats (4 uint32, written): R = registered rows, bits of dmin and of dmax over them (+inf / 0 when R == 0).  Dense outputs:
+ *   nn_reg [n] = nn or -1; target [n,3] = ref_rgb[nn] (zeros when unregistered); weight [n] = |(d - dmin) / (dmax - dmin) - 1| * f,
+ *   f = (clamp(cos(ref_dirs[nn], dirs[i]), -1, -0.5) + 1) / 0.5 with torch's cosine_similarity (eps 1e-8), 0 when unregistered; one
+ *   departure from the reference: dmax == dmin gives weight = f (the reference divides 0 by 0);
+ *   guide [n] = max(min_tv_factor, (clamp(d, guide_min, radius) - guide_min) / (radius - guide_min)). */
+#define LAE_RAYREG_BINNED 0
+#define LAE_RAYREG_GATHER 1
+LAE_API uint64_t lae_rayreg_build_bytes(uint32_t M);
+LAE_API int lae_rayreg_build(const float* ref_x, uint32_t M, float radius, void* grid, void* stream);
+LAE_API uint64_t lae_rayreg_query_bytes(uint32_t n, uint32_t M);
+LAE_API int lae_rayreg_query(const void* grid, uint32_t M, const float* x, uint32_t n, float radius, int mode, float* d, int32_t* nn,
+                     void* workspace, void* stream);
+LAE_API int lae_rayreg_supervise(const float* d, const int32_t* nn, uint32_t n, const float* ref_rgb, const float* ref_dirs, uint32_t M,
+                         const float* dirs, float reg_dist, float radius, float guide_min, float min_tv_factor, int32_t* nn_reg,
+                         float* target, float* weight, float* guide, uint32_t* stats, void* stream);
 
 /* ---- fused Adam + GradScaler (torch.optim.Adam / torch.cuda.amp.GradScaler in the reference: main_nerf.py:223,
  * nerf/utils.py:1474-1482).  `state` is a 64-byte device block:

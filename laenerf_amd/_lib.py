@@ -110,6 +110,11 @@ SIGNATURES = {
     "lae_nnfm_match": [vp, vp, u32, u32, u32, u32, vp, vp, vp, vp],
     "lae_nnfm_loss_forward": [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp],
     "lae_nnfm_loss_backward": [vp, vp, vp, vp, vp, u32, u32, u32, u32, vp, vp],
+    "lae_rayreg_build_bytes": [u32],
+    "lae_rayreg_build": [vp, u32, f32, vp, vp],
+    "lae_rayreg_query_bytes": [u32, u32],
+    "lae_rayreg_query": [vp, u32, vp, u32, f32, i32, vp, vp, vp, vp],
+    "lae_rayreg_supervise": [vp, vp, u32, vp, vp, u32, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp],
     "lae_style_loss_scratch_bytes": [u32],
     "lae_style_loss_forward": [vp, vp, vp, vp, u32, u32, f32, f32, f32, vp, vp, vp, vp, u32, f32, f32, vp],
     "lae_style_loss_backward": [vp, vp, vp, u32, u32, u32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, i32, f32, f32, vp],
@@ -151,6 +156,8 @@ _RESTYPES = {
     "lae_nnfm_packed_bytes": u64,
     "lae_nnfm_match_bytes": u64,
     "lae_nnfm_workspace_bytes": u64,
+    "lae_rayreg_build_bytes": u64,
+    "lae_rayreg_query_bytes": u64,
     "lae_recolor_compact_scratch_bytes": u64,
     "lae_marching_cubes_scratch_bytes": u64,
     "lae_style_image_scratch_bytes": u64,
@@ -164,7 +171,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi19"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi20"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

@@ -1079,6 +1079,53 @@ class _Nnfm:
 
 nnfm_backend = _Nnfm
 
+
+class _RayReg:
+    """ray registration in a cell grid (include/laenerf.h lae_rayreg_*; csrc/rayreg.hip).  Points fp32 [.,3], contiguous."""
+    BINNED, GATHER = 0, 1
+
+    @staticmethod
+    def build_bytes(M):
+        return int(_lib.load().lae_rayreg_build_bytes(M))
+
+    @staticmethod
+    def query_bytes(n, M):
+        return int(_lib.load().lae_rayreg_query_bytes(n, M))
+
+    @staticmethod
+    def build(ref_x, M, radius, grid):
+        need_cuda(ref_x, grid); need_contig(ref_x, grid)
+        if ref_x.dtype != torch.float32 or ref_x.numel() < 3 * M or grid.numel() * grid.element_size() < _RayReg.build_bytes(M):
+            raise RuntimeError("rayreg_build: ref_x float32 [M,3], grid at least lae_rayreg_build_bytes(M) bytes")
+        check(_lib.load().lae_rayreg_build(ptr(ref_x) if M else None, M, float(radius), ptr(grid), stream()), "rayreg_build")
+
+    @staticmethod
+    def query(grid, M, x, n, radius, mode, d, nn, workspace):
+        ts = (grid, x, d, nn, workspace)
+        need_cuda(*ts); need_contig(*ts)
+        nbytes = lambda t: t.numel() * t.element_size()
+        if x.dtype != torch.float32 or x.numel() < 3 * n or d.dtype != torch.float32 or d.numel() < n or nn.dtype != torch.int32 or \
+                nn.numel() < n or nbytes(grid) < _RayReg.build_bytes(M) or nbytes(workspace) < _RayReg.query_bytes(n, M):
+            raise RuntimeError("rayreg_query: x float32 [n,3], d float32 [n], nn int32 [n], grid and workspace of their *_bytes sizes")
+        check(_lib.load().lae_rayreg_query(ptr(grid), M, ptr(x), n, float(radius), int(mode), ptr(d), ptr(nn), ptr(workspace), stream()),
+              "rayreg_query")
+
+    @staticmethod
+    def supervise(d, nn, n, ref_rgb, ref_dirs, M, dirs, reg_dist, radius, guide_min, min_tv_factor, nn_reg, target, weight, guide, stats):
+        ts = (d, nn, ref_rgb, ref_dirs, dirs, nn_reg, target, weight, guide, stats)
+        need_cuda(*ts); need_contig(*ts)
+        _need_f32(d, ref_rgb, ref_dirs, dirs, target, weight, guide)
+        if nn.dtype != torch.int32 or nn_reg.dtype != torch.int32 or stats.dtype not in (torch.int32, torch.uint32) or stats.numel() < 4 or \
+                d.numel() < n or nn.numel() < n or dirs.numel() < 3 * n or ref_rgb.numel() < 3 * M or ref_dirs.numel() < 3 * M or \
+                nn_reg.numel() < n or target.numel() < 3 * n or weight.numel() < n or guide.numel() < n:
+            raise RuntimeError("rayreg_supervise: nn / nn_reg int32 [n], stats 4 int32 words, every array at least its n (M) rows")
+        check(_lib.load().lae_rayreg_supervise(ptr(d), ptr(nn), n, ptr(ref_rgb) if M else None, ptr(ref_dirs) if M else None, M, ptr(dirs),
+                                               float(reg_dist), float(radius), float(guide_min), float(min_tv_factor), ptr(nn_reg), ptr(target),
+                                               ptr(weight), ptr(guide), ptr(stats), stream()), "rayreg_supervise")
+
+
+rayreg_backend = _RayReg
+
 for _cls in (_RayMarching, _GridEncoder, _SHEncoder, _FFMLP):
     for _k, _v in list(vars(_cls).items()):
         if isinstance(_v, staticmethod) and not _k.startswith("_") and _k not in ("fused_backward_available", "ffmlp_set_mode", "set_backward_mode",
