@@ -374,8 +374,8 @@ __global__ __launch_bounds__(1024) void k_style_loss_final(const float* __restri
     if (reg.palette) reg.palette = spal;                                 // (written before the barrier above)
     const float regv = reg.palette ? pal_reg_value(reg, (int)threadIdx.x) : 0.0f;      // wave 0, all lanes
     if (threadIdx.x != 0) return;
-    uint32_t jmax = 0;
-    for (uint32_t j = 1; j < na; j++) if (tot[3 + j] > tot[3 + jmax]) jmax = j;
+    uint32_t jmax = 0;                                   // FIRST maximal column: it takes the whole gradient of the uniform term (torch's
+    for (uint32_t j = 1; j < na; j++) if (tot[3 + j] > tot[3 + jmax]) jmax = j;      // full-reduction max splits it over tied columns)
     const float s = scale ? scale[0] : 1.0f;
     const float mse = tot[0] / (3.0f * (float)M), uni = lw.w_uniform * tot[3 + jmax], non = lw.w_non_uniform * tot[2],
                 off = lw.c_offset * tot[1];

@@ -6,4 +6,6 @@ from .style_trainer import EditSet, StyleTrainer, image_terms_on, jitter_numpy  
 from .distill import DistillSet, compose_distill_numpy, distill_images, distill_nerf, distill_steps, error_map_seed_numpy  # noqa: F401
 from .style_network import StyleNetwork, load_style_image, load_vgg19_features  # noqa: F401
 from .nnfm import nnfm_loss, nnfm_match, nnfm_numpy, nnfm_pack, nnfm_workspace_bytes  # noqa: F401
+from .palette_reference import (palet_reg_numpy, palette_backward_numpy, palette_forward_numpy, palette_recompose_bits,  # noqa: F401
+                                style_loss_numpy)
 from .ray_registration import RefCloud, extract_ref_cloud, ray_registration_numpy, register_rays, register_views  # noqa: F401
