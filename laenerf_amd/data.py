@@ -392,6 +392,39 @@ class ResidentImages:
         check(_lib.load().lae_error_map_update(ptr(self.error_map), self.n_img, self.H, self.W, ptr(inds), ptr(cells), ptr(pred),
                                                ptr(gt), n, stream()), "error_map_update")
 
+    def state_dict(self):
+        """what a resumed run needs of the sampler, never the images: seed (int), step (the device counter, int64 [1], on the host)
+        and error_map (a host copy, or None)"""
+        return {"seed": int(self.seed), "step": self.step.detach().cpu().clone(),
+                "error_map": None if self.error_map is None else self.error_map.detach().cpu().clone()}
+
+    def check_state_dict(self, sd):
+        """the reasons load_state_dict would refuse `sd` (a list of strings, empty when it fits); nothing is changed"""
+        bad = []
+        step = sd.get("step")
+        if not torch.is_tensor(step) or step.numel() != 1:
+            bad.append("data.step: one int64 value expected")
+        m = sd.get("error_map")
+        if m is not None and (not torch.is_tensor(m) or tuple(m.shape) != (self.n_img, ERROR_MAP_CELLS)):
+            bad.append(f"data.error_map: saved {list(m.shape) if torch.is_tensor(m) else type(m).__name__}, "
+                       f"current {[self.n_img, ERROR_MAP_CELLS]}")
+        return bad
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """state_dict()'s counterpart, written in place (a captured graph keeps reading the same counter and the same map).  A file
+        without a map leaves the current one alone; a map in the file creates one where there is none."""
+        bad = self.check_state_dict(sd)
+        if bad:
+            raise ValueError("ResidentImages.load_state_dict: " + "; ".join(bad))
+        self.seed = int(sd["seed"]) & 0xFFFFFFFFFFFFFFFF
+        self.step.copy_(sd["step"].to(self.step.device, torch.int64).view(1))
+        m = sd.get("error_map")
+        if m is not None:
+            if self.error_map is None:
+                self.enable_error_map()
+            self.error_map.copy_(m.to(self.error_map.device, torch.float32))
+
     def view_rays(self, i):
         """every pixel of image i (scanline order) -> rays_o, rays_d [H*W, 3] and its colour [H*W, C] as fp32 on the device"""
         from .rays import get_rays

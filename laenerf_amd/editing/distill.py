@@ -64,6 +64,22 @@ class DistillSet:
     def device(self):
         return self.w.device
 
+    def save(self, path):
+        """one .npz of the packed arrays, like EditSet.save; dist / depth only when the set has them"""
+        cpu = lambda a: a.detach().cpu().numpy()
+        extra = {k: cpu(getattr(self, k)) for k in ("dist", "depth") if getattr(self, k) is not None}
+        np.savez(path, img_idx=cpu(self.img_idx), pix=cpu(self.pix), w=cpu(self.w), pred=cpu(self.pred), x_term=cpu(self.x_term),
+                 dirs=cpu(self.dirs), counts=self.counts_host.astype(np.int64), view_img=self.view_img_host.astype(np.int64),
+                 occluded=np.asarray(self.occluded, np.int64), n_img=np.int64(self.n_img), **extra)
+
+    @classmethod
+    def load(cls, path, device=None):
+        """a set written by save()"""
+        with np.load(path) as z:
+            t = lambda k: torch.from_numpy(np.ascontiguousarray(z[k])) if k in z.files else None
+            return cls(t("img_idx"), t("pix"), t("w"), t("pred"), t("x_term"), t("dirs"), t("dist"), z["counts"], z["view_img"],
+                       z["occluded"].tolist(), int(z["n_img"]), device=device, depth=t("depth"))
+
     @classmethod
     def from_views(cls, views, occluded, n_img, device=None):
         """the per-view dicts of extract_views (CPU or device tensors; `pose_idx` is the target image) and its occluded list.

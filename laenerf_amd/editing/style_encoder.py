@@ -213,7 +213,9 @@ class LAENeRF(nn.Module):
         self._active_mask = (1 << self.num_color_bases) - 1                    # host copy of active_palets (no sync per step)
         pal = color_palette if color_palette is not None else torch.rand(self.num_color_bases, 3, dtype=torch.float32)
         self.color_palette = nn.Parameter(pal.detach().clone().float())         # style_encoder.py:46-50 (a leaf with requires_grad)
-        self.original_color_palette = None
+        # the palette as it was before the first set_color_palette (a palette edit): a buffer, None until then, so that it
+        # travels in state_dict() with the palette and the active-base mask -- RecolorView and the distillation read all three
+        self.register_buffer("original_color_palette", None)
         self.size = size
         self.dir_encoding, self.in_dim_dir = None, 0
         if dir_encoding is not None:
@@ -236,6 +238,15 @@ class LAENeRF(nn.Module):
                 self.style_transfer_net = sn.StyleNetwork(style_img, vgg, style_layers=layers, size=size, generator=style_generator,
                                                           loss=getattr(params, "style_loss", None) or "gram",
                                                           nnfm_match=getattr(params, "nnfm_match", None) or "concat")
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        """nn.Module.load_state_dict, plus what a state dict cannot say by itself: original_color_palette exists exactly when the
+        dict has it, and the host copy of the active-base mask follows the loaded buffer"""
+        og = state_dict.get("original_color_palette")
+        self.original_color_palette = None if og is None else og.detach().clone().float().to(self.color_palette.device)
+        res = super().load_state_dict(state_dict, strict=strict, assign=assign)
+        self._active_mask = sum(1 << k for k, on in enumerate(self.active_palets.tolist()) if on)
+        return res
 
     def style_loss(self, img):
         """style_encoder.py: the VGG Gram loss of the [3,h,w] image `img` (StyleNetwork.forward)"""

@@ -382,6 +382,7 @@ class StyleTrainer:
         self.S = int(getattr(params, "crop_size", None) or (net.size if net is not None else 256))
         if net is not None and w["style_weight"] > 0 and net.size != self.S:
             raise ValueError(f"StyleTrainer: crop_size {self.S} differs from the style network's size {net.size}")
+        self.lr = float(lr)
         self.opt = FusedAdam(style_enc, param_groups=style_enc.get_params(lr), betas=(0.9, 0.999), eps=1e-8)
         self.gen = torch.Generator().manual_seed(int(seed))
         edit_set.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -547,6 +548,136 @@ class StyleTrainer:
         becomes the style network's target (a buffer the captured steps read)"""
         v = int(self._colour[group])
         self.style_net.match_color(self.es.view_arrays(v)[2].T)
+
+    # ------------------------------------------------------------------ checkpoints
+    _POINT_WEIGHTS = ("weight_loss_uniform", "weight_loss_non_uniform", "offset_loss", "palette_loss_valid", "palette_loss_distinct")
+
+    def config(self):
+        """what a checkpoint is checked against (checkpoint.check_config): everything the drawn schedule and the step's arithmetic depend on"""
+        p = self.params
+        return {"iters": self.iters, "capacity": self.capacity, "lr": self.lr, "warmup_iterations": self.warmup, "distill_step": self.s_d,
+                "weights": dict(self.weights), "point_weights": {k: float(getattr(p, k, 0) or 0) for k in self._POINT_WEIGHTS},
+                "tv_depth_guide": bool(getattr(p, "tv_depth_guide", False)), "preserve_color": self.preserve_color, "flags": int(self.flags),
+                "crop_size": self.S, "edit_set": {"V": self.es.V, "counts": [int(c) for c in self.es.counts_host]}}
+
+    def state_dict(self):
+        """everything a bit-exact resume needs, on the host: the network's state_dict (palette, original palette and
+        active-base mask included), the optimizer in torch.optim.Adam's layout with its GradScaler and its sixteen raw state words, the
+        host generator's state (further schedule groups and the distillation's views are drawn from it), the drawn view schedule and
+        colour schedule, global_step, the edit set's seed and device step, the `distilled` flag, the style network's fixed crop offset
+        and its target buffers (match_color rewrites them per group), and config()."""
+        from .. import _lib, checkpoint as C
+        from ..trainer import _to_host
+        o = self.opt.state_dict()
+        sc = o.pop("scaler")
+        net = self.style_net
+        return {"format": C.FORMAT, "lae_version": _lib.load().lae_version().decode(), "config": self.config(),
+                "model": _to_host(dict(self.enc.state_dict())), "optimizer": _to_host(o),
+                "scaler": C.scaler_to_reference(sc["scale"], sc["growth_tracker"], self.opt.growth_factor, self.opt.backoff_factor,
+                                                self.opt.growth_interval),
+                "optimizer_words": self.opt.raw_state(), "generator": self.gen.get_state().clone(),
+                "sched": torch.from_numpy(np.ascontiguousarray(self._sched, dtype=np.int32).copy()),
+                "colour": None if self._colour is None else torch.from_numpy(np.ascontiguousarray(self._colour, dtype=np.int32).copy()),
+                "global_step": int(self.global_step), "edit_set": {"seed": int(self.es.seed), "step": self.es.step.detach().cpu().clone()},
+                "distilled": bool(self.distilled), "crop_offset": None if net is None else [int(v) for v in net.crop_offset],
+                "style_net": None if net is None else _to_host({k: v for k, v in net.state_dict().items()
+                                                                if not k.startswith("vgg.") and k != "image"})}
+
+    def _check_load(self, ck, model_only):
+        from .. import checkpoint as C
+        if not isinstance(ck, dict) or not isinstance(ck.get("model"), dict) or "sched" not in ck:
+            raise ValueError("StyleTrainer.load_checkpoint: not a StyleTrainer checkpoint")
+        if int(ck.get("format", 0)) > C.FORMAT:
+            raise ValueError(f"StyleTrainer.load_checkpoint: checkpoint format {ck.get('format')} is newer than this package's {C.FORMAT}")
+        optional = {"model.original_color_palette"}
+        cur, saved = C.shapes_of(dict(self.enc.state_dict()), "model."), C.shapes_of(ck["model"], "model.")
+        diffs = [(k, saved.get(k, "<missing>"), cur.get(k, "<missing>")) for k in sorted(set(cur) | set(saved))
+                 if cur.get(k) != saved.get(k) and not (k in optional and (k not in cur or k not in saved))]
+        if model_only:
+            return diffs
+        diffs += C.check_config(ck["config"], self.config())
+        st = ck["optimizer"].get("state", {})
+        if sorted(st) != list(range(len(self.opt.items))):
+            diffs.append(("optimizer.state", sorted(st), list(range(len(self.opt.items)))))
+        else:
+            for i, (p, *_) in enumerate(self.opt.items):
+                for key in ("exp_avg", "exp_avg_sq"):
+                    t = st[i].get(key)
+                    if not torch.is_tensor(t) or list(t.shape) != list(p.shape):
+                        diffs.append((f"optimizer.state.{i}.{key}", list(t.shape) if torch.is_tensor(t) else "<missing>", list(p.shape)))
+        w = ck.get("optimizer_words")
+        if not torch.is_tensor(w) or w.dtype != torch.int32 or w.numel() != 16:
+            diffs.append(("optimizer_words", "malformed", [16]))
+        g = ck.get("generator")
+        if not torch.is_tensor(g) or g.dtype != torch.uint8 or g.numel() != self.gen.get_state().numel():
+            diffs.append(("generator", "malformed", [int(self.gen.get_state().numel())]))
+        sched = ck["sched"]
+        if not torch.is_tensor(sched) or sched.numel() == 0 or int(sched.min()) < 0 or int(sched.max()) >= self.es.V:
+            diffs.append(("sched", "view indices outside the edit set", self.es.V))
+        if (ck.get("colour") is None) != (self._colour is None):
+            diffs.append(("colour", ck.get("colour") is not None, self._colour is not None))
+        if (ck.get("style_net") is None) != (self.style_net is None):
+            diffs.append(("style_net", ck.get("style_net") is not None, self.style_net is not None))
+        elif self.style_net is not None:
+            have = C.shapes_of(dict(self.style_net.state_dict()), "style_net.")
+            diffs += [(k, v, have.get(k, "<missing>")) for k, v in C.shapes_of(ck["style_net"], "style_net.").items() if have.get(k) != v]
+        return diffs
+
+    @torch.no_grad()
+    def load_state_dict(self, ck, model_only=False, strict_config=True):
+        """state_dict()'s counterpart: the dict is checked first (configuration and every shape; a refused load changes nothing; with
+        strict_config a difference raises ValueError naming the fields, without it a warning is issued and the load goes on where the
+        shapes fit), then everything is restored in place, the records are reallocated for the loaded schedule, the captured graphs are
+        dropped and `started` is set.  model_only=True restores the network alone (enough for forward, RecolorView and distill).
+        losses() / terms() of a resumed trainer hold the steps since the resume."""
+        import warnings
+        from .. import checkpoint as C
+        diffs = self._check_load(ck, model_only)
+        shape_diffs = [d for d in diffs if d[0].split(".")[0] in ("model", "optimizer", "optimizer_words", "generator", "sched", "colour", "style_net")]
+        if diffs and (strict_config or shape_diffs):
+            raise ValueError("StyleTrainer.load_checkpoint: the checkpoint does not fit this trainer -- " + C.format_differences(diffs))
+        if diffs:
+            warnings.warn("StyleTrainer.load_checkpoint: the configuration differs -- " + C.format_differences(diffs))
+        self.enc.load_state_dict(ck["model"])
+        self.opt.sync_shadows()
+        self.graphs.clear()
+        self._pool = None
+        if model_only:
+            return self
+        o = dict(ck["optimizer"])
+        sc = C.scaler_from_reference(ck.get("scaler") or {})
+        if sc is not None:
+            o["scaler"] = {"scale": sc["scale"], "growth_tracker": sc["growth_tracker"]}
+        self.opt.load_state_dict(o)
+        self.opt.load_raw_state(ck["optimizer_words"])
+        self.gen.set_state(ck["generator"])
+        self._sched = ck["sched"].numpy().astype(np.int32)
+        self._colour = None if ck.get("colour") is None else ck["colour"].numpy().astype(np.int32)
+        self.global_step = int(ck["global_step"])
+        self.es.seed = int(ck["edit_set"]["seed"]) & 0xFFFFFFFFFFFFFFFF
+        self.es.set_schedule(self._sched)
+        self.es.step.copy_(ck["edit_set"]["step"].to(self.es.step.device).view(1))
+        self.distilled = bool(ck["distilled"])
+        if self.style_net is not None:
+            self.style_net.crop_offset = tuple(int(v) for v in ck["crop_offset"])
+            own = dict(self.style_net.state_dict())
+            for k, v in ck["style_net"].items():
+                own[k].copy_(v.to(own[k].device))
+        self.rec = torch.zeros(self._sched.size, 2, dtype=torch.float32, device=self.es.device)
+        self.trec = torch.zeros(self._sched.size, 4, dtype=torch.float32, device=self.es.device)
+        self._hist, self._thist = [], []
+        self.started = True
+        return self
+
+    def save_checkpoint(self, path):
+        """state_dict() written with checkpoint.atomic_save (blocking, between train() calls) -> path"""
+        from .. import checkpoint as C
+        return C.atomic_save(self.state_dict(), path)
+
+    def load_checkpoint(self, path, model_only=False, strict_config=True):
+        """read `path` (torch.load(weights_only=True)) and load_state_dict it"""
+        from .. import checkpoint as C
+        return self.load_state_dict(C.read_checkpoint(path), model_only=model_only, strict_config=strict_config)
 
     # ------------------------------------------------------------------ results
     def _records(self):

@@ -305,6 +305,20 @@ class FusedAdam(torch.optim.Optimizer):
             self._scale_view[0] = scaler["scale"]
             self.dev_state[1] = scaler["growth_tracker"]
 
+    # ---- the raw device state, for a bit-exact resume (laenerf_amd.trainer / editing.style_trainer checkpoints)
+    def raw_state(self):
+        """the sixteen device state words (include/laenerf.h: scale, tracker, found_inf, skip, step, the bias corrections of this step
+        and of the next with the step they are for, 1/scale, the skipped count), verbatim, as an int32 [16] host tensor.  The
+        torch-compatible state_dict() carries three of them (scale, tracker, step); a resumed run that is to repeat an uninterrupted one
+        bit for bit -- its skipped count and diagnostics included -- loads these after it."""
+        return self.dev_state.detach().cpu().clone()
+
+    def load_raw_state(self, words):
+        """raw_state()'s counterpart, written in place"""
+        if not torch.is_tensor(words) or words.dtype != torch.int32 or words.numel() != 16:
+            raise ValueError("FusedAdam.load_raw_state: an int32 tensor of 16 words expected")
+        self.dev_state.copy_(words.to(self.dev_state.device).view(16))
+
 
 class EMA:
     """`torch_ema.ExponentialMovingAverage(parameters, decay)` of the reference's trainer (nerf/utils.py:407-408; `update()`

@@ -37,6 +37,7 @@ path never calls; lengths in the march's own units), inside the same kernel and 
 depth_weight.  distort_grad=False computes the value only: parameters bit-equal to a run without the term.
 """
 import contextlib
+import copy
 import math
 import os
 
@@ -76,6 +77,17 @@ def psnr(pred, gt):
     """PSNRMeter (nerf/utils.py:222): -10 log10(mean squared error)"""
     mse = float(((pred.float() - gt.float()) ** 2).mean())
     return -10.0 * math.log10(max(mse, 1e-20))
+
+
+def _to_host(obj):
+    """a checkpoint's containers with every tensor cloned to the host"""
+    if torch.is_tensor(obj):
+        return obj.detach().cpu().clone()
+    if isinstance(obj, dict):
+        return {k: _to_host(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_host(v) for v in obj)
+    return obj
 
 
 class _TrainerEMA(EMA):
@@ -128,6 +140,7 @@ class Trainer:
             data.enable_error_map()
         self.r, self.opt, self.data = renderer, optimizer, data
         self.iters, self.num_rays, self.graph, self.capacity = int(iters), int(num_rays), bool(graph), capacity
+        self.lr = [float(v) for v in np.asarray(lr, dtype=np.float64).reshape(-1)]
         self.max_steps, self.dt_gamma = int(max_steps), float(dt_gamma)
         self.error_map = error_map
         if depth_weight is not None:
@@ -164,6 +177,8 @@ class Trainer:
         self._rows_seen = 0
         self.captures = self.cache_misses = self.warm_groups = 0
         self._loss_hist = []
+        from .checkpoint import new_stats
+        self.stats = new_stats()                 # the reference Trainer's stats; 'results' and 'checkpoints' are kept (checkpoints below)
         self.epoch_len = int(epoch_len) if epoch_len is not None else data.n_img
         if self.epoch_len < 1:
             raise ValueError("Trainer: epoch_len must be at least 1")
@@ -280,7 +295,9 @@ class Trainer:
     # ------------------------------------------------------------------ results
     def losses(self):
         """per-step losses (the unscaled loss of every step so far: the MSE, plus depth_weight * the depth term with depth
-        supervision, plus distort_weight * the distortion term with it) as a float32 numpy array"""
+        supervision, plus distort_weight * the distortion term with it) as a float32 numpy array.  After load_checkpoint /
+        load_state_dict: the steps since the resume (the history is not part of a checkpoint); likewise depth_losses() and
+        distort_losses()"""
         if not self._loss_hist:
             return np.zeros(0, np.float32)
         return torch.cat(self._loss_hist).cpu().numpy()
@@ -303,6 +320,222 @@ class Trainer:
     def steps_skipped(self):
         """optimizer steps the GradScaler skipped (non-finite gradients)"""
         return self.opt.steps_skipped
+
+    # ------------------------------------------------------------------ checkpoints
+    def config(self, model_only=False):
+        """the run configuration a checkpoint is checked against (checkpoint.check_config); model_only: the renderer's part alone"""
+        d, r = self.data, self.r
+        rend = {"bound": r.bound, "grid_size": int(r.grid_size), "density_thresh": float(r.density_thresh), "min_near": float(r.min_near),
+                "density_scale": r.density_scale}
+        if model_only:
+            return {"renderer": rend}
+        return {"iters": self.iters, "lr": list(self.lr), "num_rays": self.num_rays, "capacity": self.capacity, "max_steps": self.max_steps,
+                "dt_gamma": self.dt_gamma, "error_map": self.error_map, "ema_decay": None if self.ema is None else float(self.ema.decay),
+                "epoch_len": self.epoch_len, "depth_weight": self.depth_weight, "depth_grad": self.depth_grad,
+                "distort_weight": self.distort_weight, "distort_grad": self.distort_grad,
+                "data": {"n_img": d.n_img, "H": d.H, "W": d.W, "C": d.C, "mode": d.mode, "bg": d.bg, "color_space": d.color_space},
+                "renderer": rend}
+
+    def state_dict(self, full=True):
+        """everything save_checkpoint writes, on the host: the reference Trainer's dict (nerf/utils.py:1631-1655: epoch = global_step //
+        epoch_len, global_step, stats, mean_count, mean_density, model in the reference's key layout; with `full` also optimizer in
+        torch.optim.Adam's layout, lr_scheduler as a LambdaLR dict, scaler in GradScaler's layout and ema in torch_ema's) plus the
+        entry `laenerf_amd` with what a bit-exact resume needs beyond it: a format number, lae_version(), config(), the
+        tensor shapes, the renderer's iter_density and local_step, the data's seed, step and error map, the device's generator state
+        (the march's perturbation and the refresh's jitter are torch.rand draws) and, with `full`, the optimizer's sixteen state
+        words and the EMA's device count.  The touched-lines bitmaps are not written: load marks every line touched, which is exact
+        (a line whose gradient and moments are zero is left unchanged by the update)."""
+        from . import _lib, checkpoint as C
+        r, opt = self.r, self.opt
+        dev = r.density_grid.device
+        model = _to_host(dict(r.state_dict(reference_layout=True)))
+        sd = {"epoch": self.global_step // self.epoch_len, "global_step": self.global_step, "stats": copy.deepcopy(self.stats),
+              "mean_count": int(r.mean_count), "mean_density": r.mean_density, "model": model}
+        extra = {"format": C.FORMAT, "lae_version": _lib.load().lae_version().decode(), "config": self.config(),
+                 "shapes": C.shapes_of(model, "model."), "iter_density": int(r.iter_density), "local_step": int(r.local_step),
+                 "data": self.data.state_dict(), "rng_state": torch.cuda.get_rng_state(dev).clone(), "touched_lines": None}
+        if full:
+            o = opt.state_dict()
+            sc = o.pop("scaler")
+            sd["optimizer"] = _to_host(o)
+            base = self.lr if len(self.lr) > 1 else self.lr * len(opt.param_groups)
+            sd["lr_scheduler"] = C.scheduler_to_reference(self.global_step, base, self.iters)
+            sd["scaler"] = C.scaler_to_reference(sc["scale"], sc["growth_tracker"], opt.growth_factor, opt.backoff_factor,
+                                                 opt.growth_interval) if opt.use_scaler else {}
+            extra["optimizer_words"] = opt.raw_state()
+            if self.ema is not None:
+                sd["ema"] = _to_host(self.ema.state_dict())
+                extra["ema_count"] = self.ema.device_count().detach().cpu().clone()
+        sd[C.KEY] = extra
+        return sd
+
+    def _check_load(self, ck, model_only):
+        """-> the differences [(name, saved, current)] between the checkpoint dict and this trainer; nothing is changed"""
+        from . import checkpoint as C
+        if not isinstance(ck, dict) or not isinstance(ck.get("model"), dict):
+            raise ValueError("Trainer.load_checkpoint: not a Trainer checkpoint (a dict with a 'model' entry expected)")
+        extra = ck.get(C.KEY)
+        diffs = []
+        if extra is not None:
+            if int(extra.get("format", 0)) > C.FORMAT:
+                raise ValueError(f"Trainer.load_checkpoint: checkpoint format {extra.get('format')} is newer than this package's {C.FORMAT}")
+            saved_cfg = extra["config"] if not model_only else {"renderer": extra["config"]["renderer"]}
+            diffs += C.check_config(saved_cfg, self.config(model_only))
+        cur = C.shapes_of(dict(self.r.state_dict(reference_layout=True)), "model.")
+        saved = C.shapes_of(ck["model"], "model.")
+        for k in sorted(set(cur) | set(saved)):
+            if k in cur and k in saved:
+                if cur[k] != saved[k]:
+                    diffs.append((k, saved[k], cur[k]))
+            elif extra is not None and k != "model.density_grid":          # own files are complete, but for the grid of a `best` file;
+                diffs.append((k, saved.get(k, "<missing>"), cur.get(k, "<missing>")))   # reference files load with strict=False
+        if self.ema is not None and "ema" in ck:
+            sh = ck["ema"].get("shadow_params") or []
+            want = [list(p.shape) for p in self.ema.shadow_params]
+            if [list(t.shape) for t in sh] != want:
+                diffs.append(("ema.shadow_params", [list(t.shape) for t in sh], want))
+            cnt = None if extra is None else extra.get("ema_count")
+            if cnt is not None and (not torch.is_tensor(cnt) or cnt.numel() != 2):
+                diffs.append(("ema.count", "malformed", [2]))
+        if model_only:
+            return diffs
+        if "optimizer" in ck:
+            st = ck["optimizer"].get("state", {})
+            groups = ck["optimizer"].get("param_groups", [])
+            want_groups = [len(g["params"]) for g in self.opt.param_groups]
+            if [len(g.get("params", [])) for g in groups] != want_groups:
+                diffs.append(("optimizer.param_groups", [len(g.get("params", [])) for g in groups], want_groups))
+            elif sorted(st) != list(range(len(self.opt.items))):
+                diffs.append(("optimizer.state", sorted(st), list(range(len(self.opt.items)))))
+            else:
+                for i, (p, *_) in enumerate(self.opt.items):
+                    for key in ("exp_avg", "exp_avg_sq"):
+                        t = st[i].get(key)
+                        if not torch.is_tensor(t) or list(t.shape) != list(p.shape):
+                            diffs.append((f"optimizer.state.{i}.{key}", list(t.shape) if torch.is_tensor(t) else "<missing>", list(p.shape)))
+        if extra is not None:
+            w = extra.get("optimizer_words")
+            if w is not None and (not torch.is_tensor(w) or w.dtype != torch.int32 or w.numel() != 16):
+                diffs.append(("optimizer_words", "malformed", [16]))
+            diffs += [("data", msg, "") for msg in self.data.check_state_dict(extra["data"])]
+            rng = extra.get("rng_state")
+            n_rng = int(torch.cuda.get_rng_state(self.r.density_grid.device).numel())
+            if not torch.is_tensor(rng) or rng.dtype != torch.uint8 or rng.numel() != n_rng:
+                diffs.append(("rng_state", "malformed", [n_rng]))
+        return diffs
+
+    @torch.no_grad()
+    def load_state_dict(self, ck, model_only=False, strict_config=True):
+        """state_dict()'s counterpart.  The whole dict is checked against this trainer first -- the run configuration and every tensor
+        shape (checkpoint.check_config) -- and a refused load leaves the trainer exactly as it was: with strict_config a difference
+        raises ValueError naming the fields; without it a warning is issued and what fits is loaded (fine-tuning with another
+        num_rays).  Then everything listed at state_dict() is restored in place, what is derived is re-derived (the fp16 shadow
+        tables, the bitfield from the grid when the file has none, m_limit), the captured graphs are dropped (the next group is
+        captured afresh) and `started` is set, so mark_untrained_grid does not run over a trained grid.  The trainer may have trained
+        before.  losses() / depth_losses() / distort_losses() of a resumed trainer hold the steps since the resume.
+        A file without the `laenerf_amd` entry, as the reference's save_checkpoint writes it, restores what it has as the reference
+        does: the model through strict=False, mean_count and mean_density, a torch.optim.Adam state, a GradScaler state, a torch_ema
+        state, global_step (also the data's step) and stats; iter_density becomes global_step // 16 and local_step 0.  Such a resume
+        is not bit-exact: the file carries neither the generator state nor the sampler's seed.
+        model_only=True restores the model, the two means and the EMA shadows: enough for evaluate*, test, save_mesh and the editing
+        stages."""
+        import warnings
+        from . import checkpoint as C
+        diffs = self._check_load(ck, model_only)
+        if diffs:
+            if strict_config:
+                raise ValueError("Trainer.load_checkpoint: the checkpoint does not fit this trainer -- " + C.format_differences(diffs))
+            warnings.warn("Trainer.load_checkpoint: loading what fits -- " + C.format_differences(diffs))
+        bad = {n for n, _, _ in diffs}
+        skip = lambda prefix: any(n == prefix or n.startswith(prefix + ".") for n in bad)
+        r, opt = self.r, self.opt
+        extra = ck.get(C.KEY)
+        cur = C.shapes_of(dict(r.state_dict(reference_layout=True)), "model.")
+        model = {k: v for k, v in ck["model"].items() if "model." + k not in bad and "model." + k in cur}
+        r.load_state_dict(model, strict=False)                               # in place; the fp16 shadow tables follow
+        opt.sync_shadows()
+        r.mean_count = int(ck.get("mean_count", r.mean_count))
+        r.mean_density = ck.get("mean_density", r.mean_density)
+        if "density_bitfield" not in model and "density_grid" in model:
+            r.density_bitfield = raymarching.packbits(r.density_grid, min(r.mean_density, r.density_thresh), r.density_bitfield)
+        if self.ema is not None and "ema" in ck and not skip("ema"):
+            self.ema.load_state_dict(ck["ema"])
+            if extra is not None and extra.get("ema_count") is not None:
+                self.ema.device_count().copy_(extra["ema_count"].to(self.ema.device_count().device))
+        if model_only:
+            return self
+        if "optimizer" in ck and not skip("optimizer"):
+            o = dict(ck["optimizer"])
+            sc = C.scaler_from_reference(ck.get("scaler") or {})
+            if sc is not None and opt.use_scaler:
+                o["scaler"] = {"scale": sc["scale"], "growth_tracker": sc["growth_tracker"]}
+            opt.load_state_dict(o)                                           # moments in place, step count, every line touched
+            if extra is not None and extra.get("optimizer_words") is not None and not skip("optimizer_words"):
+                opt.load_raw_state(extra["optimizer_words"])
+        self.global_step = int(ck.get("global_step", 0))
+        if isinstance(ck.get("stats"), dict):
+            self.stats = {**C.new_stats(), **copy.deepcopy(ck["stats"])}
+        if extra is not None:
+            r.iter_density, r.local_step = int(extra["iter_density"]), int(extra["local_step"])
+            if not skip("data"):
+                self.data.load_state_dict(extra["data"])
+            if not skip("rng_state"):
+                torch.cuda.set_rng_state(extra["rng_state"], r.density_grid.device)
+        else:
+            r.iter_density, r.local_step = self.global_step // GROUP, 0
+            self.data.step.fill_(self.global_step)
+        if r.mean_count > 0:
+            self.m_limit.fill_(self._m())
+        self.graphs = {}
+        self._pool = None
+        self._loss_hist, self._depth_hist, self._distort_hist = [], [], []
+        self.started = True
+        return self
+
+    def save_checkpoint(self, path_or_dir, name="ngp", full=True, best=False, remove_old=True, max_keep_ckpt=2):
+        """write state_dict(full) with checkpoint.atomic_save, blocking, between train() calls -> the path written (None when a `best`
+        save had nothing to write).  path_or_dir: a `.pth` path, or a directory, where the file is `{name}_ep{epoch:04d}.pth` and
+        (remove_old) stats['checkpoints'] keeps the newest max_keep_ckpt files, the older ones being removed (nerf/utils.py:1659-1665).
+        full: the reference's flag -- optimizer, scheduler, scaler and EMA are written only with it; a file without them restores the
+        model and the counters, not an exact resume.
+        best=True (nerf/utils.py:1669-1689): written (to `{name}.pth` in a directory) only when stats['results'][-1] improves on
+        stats['best_result'] (lower is better: evaluate_one_epoch appends a mean squared error), with the EMA weights swapped in for the
+        write and restored after, and without density_grid."""
+        from . import checkpoint as C
+        path, in_dir = C.resolve_path(path_or_dir, name, self.global_step // self.epoch_len, best=best)
+        if best:
+            res = self.stats["results"]
+            if not res or (self.stats["best_result"] is not None and not res[-1] < self.stats["best_result"]):
+                return None
+            self.stats["best_result"] = res[-1]
+            if self.ema is not None:
+                self.ema.store()
+                self.ema.copy_to()
+            try:
+                sd = self.state_dict(full)
+            finally:
+                if self.ema is not None:
+                    self.ema.restore()
+            del sd["model"]["density_grid"]
+            del sd[C.KEY]["shapes"]["model.density_grid"]
+            return C.atomic_save(sd, path)
+        if in_dir and remove_old:
+            C.rotate(self.stats, path, max_keep_ckpt)
+        return C.atomic_save(self.state_dict(full), path)
+
+    def load_checkpoint(self, path_or_dir=None, name="ngp", model_only=False, strict_config=True, trusted=False):
+        """read a checkpoint file and load_state_dict it (see there for what is checked and restored).  path_or_dir: a file; a
+        directory, or None for the current one, means its latest `{name}_ep*.pth` (the reference's sorted-glob rule, --ckpt latest).
+        The file is read with torch.load(weights_only=True); trusted=True switches to a full unpickle, for reference files that
+        carry other objects."""
+        from . import checkpoint as C
+        path = "." if path_or_dir is None else os.fspath(path_or_dir)
+        if os.path.isdir(path):
+            found = C.latest_checkpoint(path, name)
+            if found is None:
+                raise FileNotFoundError(f"Trainer.load_checkpoint: no {name}_ep*.pth in {path!r}")
+            path = found
+        return self.load_state_dict(C.read_checkpoint(path, trusted=trusted), model_only=model_only, strict_config=strict_config)
 
     def save_mesh(self, path, resolution=256, threshold=10, normals=False, colors=False, **kwargs):
         """nerf/utils.py:722-741: the renderer's mesh as a binary PLY; normals / colors add per-vertex attributes"""
@@ -375,7 +608,10 @@ class Trainer:
         squared error into a device slot; with `lpips` (metrics.LPIPS) its input, then the trunk and the head; with `masks` (a list
         of uint8 [H, W] or None per view, metrics.load_masks) eval_masked's MSE); one host read for the whole split.  out_dir:
         `{name}_{i:04d}_rgb.png` / `_depth.png` (uint8, clipped).  -> dict psnr [n], lpips [n] or None, masked_mse [n] (NaN where
-        a view has no mask) or None, mean_psnr, mean_lpips, mean_masked_mse (over the views with a mask)"""
+        a view has no mask) or None, mean_psnr, mean_lpips, mean_masked_mse (over the views with a mask).
+        Also appends the mean squared error over the evaluated views to stats['results'], which save_checkpoint(best=True) compares:
+        lower is better.  (The reference appends its PSNR there and still keeps the minimum, nerf/utils.py:1606-1611, :1671 -- a quirk
+        not kept.)"""
         from . import metrics as M
         n, H, W = data.n_img, data.H, data.W
         if masks is not None and len(masks) != n:
@@ -411,6 +647,7 @@ class Trainer:
         res["mean_psnr"] = float(np.mean(res["psnr"]))
         res["mean_lpips"] = None if lp is None else float(np.mean(res["lpips"]))
         res["mean_masked_mse"] = float(np.mean(res["masked_mse"][has_mask])) if has_mask.any() else None
+        self.stats["results"].append(float(s[:, 0].sum() / (n * 3 * H * W)))
         return res
 
     @torch.no_grad()

@@ -14,7 +14,11 @@ ratio to the README's train-step headline, captures / cache misses / eager warm 
 term ("depth": {...}) and the replay time of five windows for each.
 --distort W: every student of the run trains with the distortion regularizer (Trainer(distort_weight=W)); the line then carries the
 term's first and last 16-step mean ("distort": {...}).  Compare ms/step with a run without the option (and `--depth --distort W`
-with `--depth`) for the term's cost: the runs differ in nothing else, though their mean_count drifts apart as the geometry does."""
+with `--depth`) for the term's cost: the runs differ in nothing else, though their mean_count drifts apart as the geometry does.
+--save PATH: the first student's checkpoint is written after the run (Trainer.save_checkpoint; a `.pth` path or a directory);
+--resume PATH: the first student loads it before training and then trains --steps further steps (the same --steps as the saved run
+keeps the learning-rate horizon, which the load checks).  The line then carries "checkpoint": the file size in bytes and the save /
+load wall times in ms -- plain numbers, bounded by nothing."""
 import argparse
 import json
 import os
@@ -143,6 +147,8 @@ def main():
     ap.add_argument("--depth-weight", type=float, default=1e-3)
     ap.add_argument("--depth-value-only", action="store_true", help="depth_grad=False: the reference's value-only depth term")
     ap.add_argument("--distort", type=float, default=None, metavar="W", help="Trainer(distort_weight=W) for every student of the run")
+    ap.add_argument("--save", default=None, metavar="PATH", help="write the first student's checkpoint after the run")
+    ap.add_argument("--resume", default=None, metavar="PATH", help="load a checkpoint into the first student before training")
     args = ap.parse_args()
     error_map = None if args.error_map == "none" else args.error_map
     dev = torch.device("cuda:0")
@@ -152,7 +158,18 @@ def main():
     held = 4
     tr = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
                       capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, distort_weight=args.distort)
+    ckpt = {}
+    if args.resume:
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        tr.load_checkpoint(args.resume)
+        torch.cuda.synchronize()
+        ckpt.update(load_ms=round((time.perf_counter() - t0) * 1e3, 2), resumed_at_step=tr.global_step)
     all_in, steady = _timed_run(tr, args.steps)
+    if args.save:
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        path = tr.save_checkpoint(args.save)
+        ckpt.update(save_ms=round((time.perf_counter() - t0) * 1e3, 2), file_bytes=os.path.getsize(path), path=path,
+                    saved_at_step=tr.global_step)
     from laenerf_amd.data import ResidentImages
     test = ResidentImages.from_arrays(images[:held], poses[:held], intr, device=dev)
     p = tr.evaluate(range(held), data=test, bg_color=1.0)
@@ -190,7 +207,7 @@ def main():
                       "padding_rows_frac": round(1 - tr._m() / tr._m_cap(), 4) if tr.r.mean_count > 0 else None},
         **({"distort": {"distort_weight": args.distort, "first_distort_loss": float(tr.distort_losses()[:16].mean()),
                         "final_distort_loss": float(tr.distort_losses()[-16:].mean())}} if args.distort is not None else {}),
-        **({"depth": depth} if depth is not None else {}),
+        **({"depth": depth} if depth is not None else {}), **({"checkpoint": ckpt} if ckpt else {}),
         "scene": f"{args.views - held} training + {held} held-out {args.res}x{args.res} RGBA uint8 views of a teacher network"}), flush=True)
 
 
