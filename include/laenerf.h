@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi20"
+#define LAE_ABI_TAG "abi21"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -824,6 +824,59 @@ LAE_API int lae_style_loss_backward_image_dev(const void* w_logits, const void* 
                                       uint32_t cap, const uint32_t* m_dev, const float* target, const float* fin, const float* upstream,
                                       float w_uniform, float w_non_uniform, float c_offset, const float* g_pred, void* g_w_logits,
                                       void* g_o_raw, float* g_palette, void* scratch, int flags, float w_valid, float w_distinct, void* stream);
+
+/* lae_style_loss_forward_dev / lae_style_loss_backward_image_dev with the factor of the MSE as one more scalar, mse_w >= 0 (the
+ * Ref-NPR second stage, whose colour term is lae_ref_terms_* below): loss = mse_w * MSE + the regularisers, and the per-point
+ * gradient carries mse_w times the MSE's part.  fin[2] is the unweighted MSE against `target` in every case (a diagnostic when
+ * mse_w == 0).  mse_w == 1 gives the bits of the entry points above (a multiplication by 1.0f is exact). */
+LAE_API int lae_style_loss_forward_dev_w(const void* pred, const float* target, const float* w_hat, const void* o_hat, uint32_t cap,
+                                 const uint32_t* m_dev, uint32_t n_active, float w_uniform, float w_non_uniform, float c_offset,
+                                 float mse_w, const float* scale, float* fin, void* scratch, const float* reg_palette, uint32_t reg_P,
+                                 float w_valid, float w_distinct, void* stream);
+LAE_API int lae_style_loss_backward_image_dev_w(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask,
+                                        uint32_t cap, const uint32_t* m_dev, const float* target, const float* fin, const float* upstream,
+                                        float w_uniform, float w_non_uniform, float c_offset, float mse_w, const float* g_pred,
+                                        void* g_w_logits, void* g_o_raw, float* g_palette, void* scratch, int flags, float w_valid,
+                                        float w_distinct, void* stream);
+
+/* The registered terms of the Ref-NPR second stage (the reference's train_styleenc_step_npr, nerf/utils.py:1096-1104, :1120-1122;
+ * laenerf_amd.editing.ref_stage) on the step's view, everything read from device memory (capturable: no host read, no allocation;
+ * one graph serves every view):
+ *   v = schedule[(*step_counter - 1) mod n_sched] (the sampler advanced the counter), K = min(*m_dev, cap, counts[v]), o = row_off[v].
+ * Per-row arrays of the packed set (view v's rows at row_off[v]): w8s [sum K] fp16 (the view's opacity weights), ref_target
+ * [sum K, 3] fp32 and ref_weight [sum K] fp32 (the registration, dense: weight 0 = the row is not registered and its target is
+ * not read), ref_count [V] int32 (R: the registered rows), row_tap [sum K] int32 (backward: the one tap that reads the row, or -1).
+ * Per-view arrays of the colour patch, n_out = ph * pw outputs: tap_row [V, n_out, 4] int32 (a row of the view, -1: no tap /
+ * the source pixel is off the mask), tap_w [V, n_out, 4] fp32, color_patch [V, 3, n_out] fp32.
+ * forward, rows i < K:
+ *   pred'[i][c] = fp16(pred[i][c] * w8s[o + i]) -- the fp32 product of two fp16 values is exact, so this is ONE rounding (the
+ *     reference's in-place half multiply) -- written as fp16 predw16 [cap,3] and as the same values in fp32 predw32 [cap,3];
+ *     rows >= K of both are zeros (rows >= K of pred / target are never read).
+ *   terms[0], mode LAE_REF_MODE_GT:  sum_i sum_c (target[i][c] - pred'[i][c])^2 / (3 K)     (`target`: the step's [cap,3] buffer)
+ *             mode LAE_REF_MODE_REF: sum_i ref_weight[o+i] sum_c (ref_target[o+i][c] - pred'[i][c])^2 / (3 R); R == 0 gives 0 and
+ *             a zero gradient (DEPARTURE: the reference takes the mean of an empty tensor there, NaN).
+ *   terms[1], mode LAE_REF_MODE_REF: mean over the 3 n_out values of (patch[o'][c] - color_patch[v][c][o'])^2 with
+ *             patch[o'][c] = sum_t tap_w[v][o'][t] * pred'[tap_row[v][o'][t]][c] (taps with a row outside 0..K-1 add nothing);
+ *             resid [n_out, 3] fp64 keeps patch - color_patch for the backward.  Mode GT: 0, nothing else is touched.
+ *   Residuals, squares and sums run in fp64 in a fixed order without atomics (ref_stage.hip's header) and are rounded to fp32
+ *   once: two runs give the same bits.  scratch: lae_ref_terms_scratch_bytes(cap, n_out).
+ * backward: g_pred [cap,3] fp32 = w8s[o+i] * (g_predw[i][c] + g_terms[0] * d terms[0]/d pred' + g_terms[1] * d terms[1]/d pred')
+ *   (the fp16 rounding is passed straight through, as autograd passes a half multiply); g_predw [cap,3] fp32 (the gradient the
+ *   image block returns for predw32) may be NULL; g_terms [2] fp32 (device).  Every row is under at most one tap (the packing
+ *   guarantees it for a resize scale >= 2), so the patch gradient is one gather per row.  Rows >= K get exact zeros. */
+#define LAE_REF_MODE_GT 0
+#define LAE_REF_MODE_REF 1
+LAE_API uint64_t lae_ref_terms_scratch_bytes(uint32_t cap, uint32_t n_out);
+LAE_API int lae_ref_terms_forward(const void* pred, uint32_t cap, const uint32_t* m_dev, const float* target, const int32_t* schedule,
+                          uint32_t n_sched, const int64_t* step_counter, uint32_t V, const int64_t* row_off, const int32_t* counts,
+                          const void* w8s, const float* ref_target, const float* ref_weight, const int32_t* ref_count,
+                          const int32_t* tap_row, const float* tap_w, const float* color_patch, uint32_t n_out, int mode, void* predw16,
+                          float* predw32, double* resid, void* scratch, float* terms, void* stream);
+LAE_API int lae_ref_terms_backward(const void* pred, uint32_t cap, const uint32_t* m_dev, const float* target, const int32_t* schedule,
+                           uint32_t n_sched, const int64_t* step_counter, uint32_t V, const int64_t* row_off, const int32_t* counts,
+                           const void* w8s, const float* ref_target, const float* ref_weight, const int32_t* ref_count,
+                           const int32_t* row_tap, const float* tap_w, const double* resid, uint32_t n_out, int mode, const float* g_predw,
+                           const float* g_terms, float* g_pred, void* stream);
 
 /* The image-space terms of LAENeRF's stylization step (nerf/utils.py:997-1033; editing/style_encoder.py:207-235,
  * editing/style_network.py:129-191) on the step's view, everything read from device memory (capturable; one graph serves every view):

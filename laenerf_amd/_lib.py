@@ -122,6 +122,11 @@ SIGNATURES = {
     "lae_style_loss_backward_dev": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, i32, f32, f32, vp],
     "lae_sample_edit_view": [vp, vp, vp, vp, vp, vp, u32, vp, u32, u32, u64, vp, vp, vp, vp, vp, vp],
     "lae_style_loss_backward_image_dev": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, i32, f32, f32, vp],
+    "lae_style_loss_forward_dev_w": [vp, vp, vp, vp, u32, vp, u32, f32, f32, f32, f32, vp, vp, vp, vp, u32, f32, f32, vp],
+    "lae_style_loss_backward_image_dev_w": [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, i32, f32, f32, vp],
+    "lae_ref_terms_scratch_bytes": [u32, u32],
+    "lae_ref_terms_forward": [vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp],
+    "lae_ref_terms_backward": [vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp],
     "lae_style_image_scratch_bytes": [u32],
     "lae_style_image_forward": [vp, u32, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, i32, u32, vp, vp, vp],
     "lae_style_image_backward": [vp, u32, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, i32, vp, vp],
@@ -161,6 +166,7 @@ _RESTYPES = {
     "lae_recolor_compact_scratch_bytes": u64,
     "lae_marching_cubes_scratch_bytes": u64,
     "lae_style_image_scratch_bytes": u64,
+    "lae_ref_terms_scratch_bytes": u64,
     "lae_render_frame_workspace_bytes": u64,
     "lae_workspace_bytes": u64,
     "lae_grid_backward_workspace_bytes": u64,
@@ -171,7 +177,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi20"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi21"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

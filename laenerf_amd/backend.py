@@ -897,16 +897,23 @@ class _Style:
         check(_lib.load().lae_style_assemble_backward(ptr(g_feat), ptr(g_off), M, off_cols, ptr(grad_lm), stream()), "style_assemble_backward")
 
     @staticmethod
-    def style_loss_forward(pred, target, w_hat, o_hat, M, n_active, lw, scale, fin, reg_palette=None, reg_w=(0.0, 0.0), m_dev=None):
+    def style_loss_forward(pred, target, w_hat, o_hat, M, n_active, lw, scale, fin, reg_palette=None, reg_w=(0.0, 0.0), m_dev=None, mse_w=None):
         """reg_palette [P,3] fp32 + reg_w = (palette_loss_valid, palette_loss_distinct): `palet_loss` joins the criterion (include/laenerf.h).
-        m_dev (a 1-element int32 / uint32 device tensor): M is the buffers' capacity and *m_dev the live rows (lae_style_loss_forward_dev)"""
+        m_dev (a 1-element int32 / uint32 device tensor): M is the buffers' capacity and *m_dev the live rows (lae_style_loss_forward_dev).
+        mse_w (needs m_dev): the MSE's factor in the loss (lae_style_loss_forward_dev_w); None: the entry points without it"""
         ts = (pred, target, w_hat, o_hat, scale, fin, reg_palette, m_dev)
         need_cuda(*ts); need_contig(*ts)
         assert fin.numel() >= 12
         lib = _lib.load()
         ws = _workspace(pred.device, lib.lae_style_loss_scratch_bytes(M))
         reg = (ptr(reg_palette), 0 if reg_palette is None else reg_palette.shape[0], float(reg_w[0]), float(reg_w[1]))
-        if m_dev is None:
+        if mse_w is not None:
+            if m_dev is None:
+                raise RuntimeError("style_loss_forward: mse_w needs the device row count m_dev")
+            check(lib.lae_style_loss_forward_dev_w(ptr(pred), ptr(target), ptr(w_hat), ptr(o_hat), M, ptr(m_dev), n_active, float(lw[0]),
+                                                   float(lw[1]), float(lw[2]), float(mse_w), ptr(scale), ptr(fin), ptr(ws), *reg, stream()),
+                  "style_loss_forward_dev_w")
+        elif m_dev is None:
             check(lib.lae_style_loss_forward(ptr(pred), ptr(target), ptr(w_hat), ptr(o_hat), M, n_active, float(lw[0]), float(lw[1]), float(lw[2]),
                                              ptr(scale), ptr(fin), ptr(ws), *reg, stream()), "style_loss_forward")
         else:
@@ -933,15 +940,23 @@ class _Style:
 
     @staticmethod
     def style_loss_backward_image(w_logits, o_raw, palette, P, active_mask, M, target, fin, upstream, lw, g_pred, g_w_logits, g_o_raw,
-                                  g_palette, m_dev, reg_w=None, accumulate=False):
+                                  g_palette, m_dev, reg_w=None, accumulate=False, mse_w=None):
         """style_loss_backward with a device row count and the image terms' fp32 dL/dpred [M,3] added before the clamp mask
-        (lae_style_loss_backward_image_dev; g_pred None: lae_style_loss_backward_dev)"""
+        (lae_style_loss_backward_image_dev; g_pred None: lae_style_loss_backward_dev).  mse_w: the MSE's factor
+        (lae_style_loss_backward_image_dev_w); None: the entry point without it"""
         ts = (w_logits, o_raw, palette, target, fin, upstream, g_pred, g_w_logits, g_o_raw, g_palette, m_dev)
         need_cuda(*ts); need_contig(*ts)
         if g_pred is not None and (g_pred.dtype != torch.float32 or g_pred.numel() < 3 * M):
             raise RuntimeError("style_loss_backward_image: g_pred must be float32 [M,3]")
         lib = _lib.load()
         ws = _workspace(w_logits.device, max(lib.lae_palette_backward_scratch_bytes(M), lib.lae_style_loss_scratch_bytes(M)))
+        if mse_w is not None:
+            check(lib.lae_style_loss_backward_image_dev_w(ptr(w_logits), ptr(o_raw), ptr(palette), P, active_mask, M, ptr(m_dev), ptr(target),
+                                                          ptr(fin), ptr(upstream), float(lw[0]), float(lw[1]), float(lw[2]), float(mse_w),
+                                                          ptr(g_pred), ptr(g_w_logits), ptr(g_o_raw), ptr(g_palette), ptr(ws),
+                                                          int(reg_w is not None) | (2 if accumulate else 0), float(reg_w[0]) if reg_w else 0.0,
+                                                          float(reg_w[1]) if reg_w else 0.0, stream()), "style_loss_backward_image_dev_w")
+            return
         check(lib.lae_style_loss_backward_image_dev(ptr(w_logits), ptr(o_raw), ptr(palette), P, active_mask, M, ptr(m_dev), ptr(target),
                                                     ptr(fin), ptr(upstream), float(lw[0]), float(lw[1]), float(lw[2]), ptr(g_pred),
                                                     ptr(g_w_logits), ptr(g_o_raw), ptr(g_palette), ptr(ws),
@@ -1125,6 +1140,54 @@ class _RayReg:
 
 
 rayreg_backend = _RayReg
+
+
+class _RefStage:
+    """the registered terms of the Ref-NPR second stage (include/laenerf.h lae_ref_terms_*; csrc/ref_stage.hip) on the current step's
+    view of a RefEditSet `es` (editing/ref_stage.py)"""
+    GT, REF = 0, 1
+
+    @staticmethod
+    def _args(es, pred, cap, m_dev, target, mode):
+        r = es.ref
+        if pred.dtype != _F16 or pred.numel() < 3 * cap or m_dev.dtype not in (torch.int32, torch.uint32):
+            raise RuntimeError("ref_terms: pred float16 [cap,3], m_dev int32")
+        if mode == _RefStage.GT and (target is None or target.dtype != torch.float32 or target.numel() < 3 * cap):
+            raise RuntimeError("ref_terms: the gt phase needs the step's float32 [cap,3] target buffer")
+        return (ptr(pred), int(cap), ptr(m_dev), ptr(target), ptr(es.schedule), es.schedule.numel(), ptr(es.step), es.V, ptr(es.offsets),
+                ptr(es.counts), ptr(r["w8s16"]), ptr(r["ref_target"]), ptr(r["ref_weight"]), ptr(r["ref_count"]))
+
+    @staticmethod
+    def forward(es, pred, cap, m_dev, target, mode, predw16, predw32, resid, terms):
+        """-> predw16 / predw32 [cap,3], resid [n_out,3] fp64 (ref phase), terms [2] fp32 (lae_ref_terms_forward)"""
+        r = es.ref
+        ts = (pred, m_dev, target, predw16, predw32, resid, terms)
+        need_cuda(*ts); need_contig(*ts)
+        n_out = int(es.n_out)
+        if predw16.dtype != _F16 or predw32.dtype != torch.float32 or predw16.numel() < 3 * cap or predw32.numel() < 3 * cap or \
+                terms.dtype != torch.float32 or terms.numel() < 2 or (mode == _RefStage.REF and (resid.dtype != torch.float64 or resid.numel() < 3 * n_out)):
+            raise RuntimeError("ref_terms_forward: predw16 float16 / predw32 float32 [cap,3], resid float64 [n_out,3], terms float32 [2]")
+        lib = _lib.load()
+        ws = _workspace(pred.device, lib.lae_ref_terms_scratch_bytes(int(cap), n_out))
+        check(lib.lae_ref_terms_forward(*_RefStage._args(es, pred, cap, m_dev, target, mode), ptr(r["tap_row"]), ptr(r["tap_w"]),
+                                        ptr(r["color_patch"]), n_out, int(mode), ptr(predw16), ptr(predw32), ptr(resid), ptr(ws), ptr(terms),
+                                        stream()), "ref_terms_forward")
+
+    @staticmethod
+    def backward(es, pred, cap, m_dev, target, mode, resid, g_predw, g_terms, g_pred):
+        """g_pred [cap,3] fp32 (lae_ref_terms_backward); g_predw may be None"""
+        r = es.ref
+        ts = (pred, m_dev, target, resid, g_predw, g_terms, g_pred)
+        need_cuda(*ts); need_contig(*ts)
+        if g_pred.dtype != torch.float32 or g_pred.numel() < 3 * cap or g_terms.dtype != torch.float32 or g_terms.numel() < 2 or \
+                (g_predw is not None and (g_predw.dtype != torch.float32 or g_predw.numel() < 3 * cap)):
+            raise RuntimeError("ref_terms_backward: g_pred / g_predw float32 [cap,3], g_terms float32 [2]")
+        check(_lib.load().lae_ref_terms_backward(*_RefStage._args(es, pred, cap, m_dev, target, mode), ptr(r["row_tap"]), ptr(r["tap_w"]),
+                                                 ptr(resid), int(es.n_out), int(mode), ptr(g_predw), ptr(g_terms), ptr(g_pred), stream()),
+              "ref_terms_backward")
+
+
+ref_stage_backend = _RefStage
 
 for _cls in (_RayMarching, _GridEncoder, _SHEncoder, _FFMLP):
     for _k, _v in list(vars(_cls).items()):

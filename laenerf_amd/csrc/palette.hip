@@ -107,7 +107,8 @@ __global__ __launch_bounds__(PAL_BLOCK) void k_palette_fwd(const half_t* __restr
 // Point-wise losses of train_LAENeRF_step (nerf/utils.py:990-996) fused behind the recomposition:
 //   loss = MSE(pred, target) + w_uniform * max_j sum_i w_ij + w_non_uniform * sum_i (1 - max_j w_ij) + c_offset * sum o^2
 // (style_encoder.py:183-205).  `fin` is the result block of k_style_loss_final (totals, arg-max column, loss scale).
-struct StyleLossW { float w_uniform, w_non_uniform, c_offset; };
+struct StyleLossW { float w_uniform, w_non_uniform, c_offset;
+                    float mse_w = 1.0f; };       // mse_w: factor of the MSE in the loss and its gradient (1.0f: exact; the *_w entry points)
 struct LossSrc { const float* target; const float* fin; const float* upstream; StyleLossW lw;
                  const float* g_pred; };         // g_pred: fp32 [M,3] dL/dpred of the image terms (scaled), added before the clamp mask, or NULL
 constexpr int SL_COLS = 3 + PAL_MAX;             // partial sums per workgroup: squared error, o^2, 1 - max w, column sums
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(PAL_BLOCK) void k_palette_bwd(const half_t* __restr
             const bool pass = p >= 0.0f && p <= 1.0f;                                                   // clamp backward (inclusive)
             if constexpr (LOSS) {
                 const float pc = fminf(fmaxf(p, 0.0f), 1.0f);
-                gpc[c] = pass ? gmul * 2.0f * (pc - ls.target[(size_t)i * 3 + c]) / (3.0f * (float)M) : 0.0f;
+                gpc[c] = pass ? ls.lw.mse_w * (gmul * 2.0f * (pc - ls.target[(size_t)i * 3 + c]) / (3.0f * (float)M)) : 0.0f;
                 if (ls.g_pred && pass) gpc[c] += ls.g_pred[(size_t)i * 3 + c];
                 got[c] = gpc[c] + gmul * 2.0f * ls.lw.c_offset * (float)o[c];
             } else {
@@ -383,7 +384,7 @@ __global__ __launch_bounds__(1024) void k_style_loss_final(const float* __restri
     // `+= palet_loss(params).half()` -- each added term rounded to fp16 first (the casts' backward is the identity, so only the
     // reported / scaled VALUE sees it; fin[] keeps the unrounded terms).  ADVICE r4.
     const auto h = [](float v) { return (float)(half_t)v; };
-    const float loss = ((mse + h(uni + non)) + h(off)) + h(regv);
+    const float loss = ((lw.mse_w * mse + h(uni + non)) + h(off)) + h(regv);      // fin[FIN_MSE] stays the unweighted diagnostic
     fin[FIN_REG] = regv;
     fin[FIN_LOSS_SCALED] = loss * s; fin[FIN_LOSS] = loss; fin[FIN_MSE] = mse; fin[FIN_UNIFORM] = uni; fin[FIN_NON_UNIFORM] = non;
     fin[FIN_OFFSET] = off; fin[FIN_JMAX] = (float)jmax; fin[FIN_SCALE] = s;
@@ -494,13 +495,14 @@ __global__ __launch_bounds__(SA_BLOCK) void k_style_assemble_bwd(const uint32_t*
 // the fused criterion's two launches each way; m_dev == NULL: M rows, else M is the buffers' capacity and *m_dev (<= M) the live rows
 int style_loss_forward_impl(const void* pred, const float* target, const float* w_hat, const void* o_hat, uint32_t M, const uint32_t* m_dev,
                             uint32_t n_active, float w_uniform, float w_non_uniform, float c_offset, const float* scale, float* fin,
-                            void* scratch, const float* reg_palette, uint32_t reg_P, float w_valid, float w_distinct, void* stream) {
+                            void* scratch, const float* reg_palette, uint32_t reg_P, float w_valid, float w_distinct, void* stream,
+                            float mse_w = 1.0f) {
     if (!pred || !target || !w_hat || !o_hat || !fin || !scratch) return LAE_ENULL;
     if (M == 0 || n_active == 0 || n_active > PAL_MAX || (reg_palette && (reg_P == 0 || reg_P > PAL_MAX))) return LAE_EINVAL;
     hipStream_t s = STREAM(stream);
     const uint32_t nb = lae::cdiv(M, PAL_BLOCK);
     k_style_loss_partial<<<nb, PAL_BLOCK, 0, s>>>((const half_t*)pred, target, w_hat, (const half_t*)o_hat, M, n_active, (float*)scratch, m_dev);
-    k_style_loss_final<<<1, 1024, 0, s>>>((const float*)scratch, nb, M, n_active, StyleLossW{w_uniform, w_non_uniform, c_offset},
+    k_style_loss_final<<<1, 1024, 0, s>>>((const float*)scratch, nb, M, n_active, StyleLossW{w_uniform, w_non_uniform, c_offset, mse_w},
                                                   scale, fin, PalReg{reg_palette, reg_P, w_valid, w_distinct}, m_dev);
     return lae::check_launch("style_loss_forward");
 }
@@ -508,14 +510,14 @@ int style_loss_forward_impl(const void* pred, const float* target, const float* 
 int style_loss_backward_impl(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask, uint32_t M,
                              const uint32_t* m_dev, const float* target, const float* fin, const float* upstream, float w_uniform,
                              float w_non_uniform, float c_offset, void* g_w_logits, void* g_o_raw, float* g_palette, void* scratch, int flags,
-                             float w_valid, float w_distinct, void* stream, const float* g_pred = nullptr) {
+                             float w_valid, float w_distinct, void* stream, const float* g_pred = nullptr, float mse_w = 1.0f) {
     if (!w_logits || !o_raw || !palette || !target || !fin || !upstream || !g_w_logits || !g_o_raw || !g_palette || !scratch) return LAE_ENULL;
     if (M == 0) return LAE_EINVAL;
     const int rc = check_palette(P, active_mask);
     if (rc) return rc;
     hipStream_t s = STREAM(stream);
     const uint32_t nb = lae::cdiv(M, PAL_BLOCK);
-    const LossSrc ls{target, fin, upstream, StyleLossW{w_uniform, w_non_uniform, c_offset}, g_pred};
+    const LossSrc ls{target, fin, upstream, StyleLossW{w_uniform, w_non_uniform, c_offset, mse_w}, g_pred};
     k_palette_bwd<true><<<nb, PAL_BLOCK, 0, s>>>((const half_t*)w_logits, (const half_t*)o_raw, palette, P, active_mask, M, nullptr, nullptr,
                                                  nullptr, (half_t*)g_w_logits, (half_t*)g_o_raw, (float*)scratch, ls, m_dev);
     k_palette_grad_reduce<<<PAL_MAX * 3, 64, 0, s>>>((const float*)scratch, nb, P, active_mask, g_palette,
@@ -628,6 +630,29 @@ int lae_style_loss_backward_image_dev(const void* w_logits, const void* o_raw, c
     if (!m_dev) return LAE_ENULL;
     return style_loss_backward_impl(w_logits, o_raw, palette, P, active_mask, cap, m_dev, target, fin, upstream, w_uniform, w_non_uniform,
                                     c_offset, g_w_logits, g_o_raw, g_palette, scratch, flags, w_valid, w_distinct, stream, g_pred);
+}
+
+// the two _dev entry points with the MSE's factor as an argument (mse_w = 1: the bits of the entry points above; mse_w = 0: the
+// loss and the per-point gradient carry the regularisers and g_pred alone, fin[FIN_MSE] is still the MSE against `target`)
+int lae_style_loss_forward_dev_w(const void* pred, const float* target, const float* w_hat, const void* o_hat, uint32_t cap,
+                                 const uint32_t* m_dev, uint32_t n_active, float w_uniform, float w_non_uniform, float c_offset, float mse_w,
+                                 const float* scale, float* fin, void* scratch, const float* reg_palette, uint32_t reg_P, float w_valid,
+                                 float w_distinct, void* stream) {
+    if (!m_dev) return LAE_ENULL;
+    if (!(mse_w >= 0.0f)) return LAE_EINVAL;
+    return style_loss_forward_impl(pred, target, w_hat, o_hat, cap, m_dev, n_active, w_uniform, w_non_uniform, c_offset, scale, fin, scratch,
+                                   reg_palette, reg_P, w_valid, w_distinct, stream, mse_w);
+}
+
+int lae_style_loss_backward_image_dev_w(const void* w_logits, const void* o_raw, const float* palette, uint32_t P, uint32_t active_mask,
+                                        uint32_t cap, const uint32_t* m_dev, const float* target, const float* fin, const float* upstream,
+                                        float w_uniform, float w_non_uniform, float c_offset, float mse_w, const float* g_pred,
+                                        void* g_w_logits, void* g_o_raw, float* g_palette, void* scratch, int flags, float w_valid,
+                                        float w_distinct, void* stream) {
+    if (!m_dev) return LAE_ENULL;
+    if (!(mse_w >= 0.0f)) return LAE_EINVAL;
+    return style_loss_backward_impl(w_logits, o_raw, palette, P, active_mask, cap, m_dev, target, fin, upstream, w_uniform, w_non_uniform,
+                                    c_offset, g_w_logits, g_o_raw, g_palette, scratch, flags, w_valid, w_distinct, stream, g_pred, mse_w);
 }
 
 }  // extern "C"

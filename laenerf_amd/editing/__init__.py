@@ -8,4 +8,8 @@ from .style_network import StyleNetwork, load_style_image, load_vgg19_features  
 from .nnfm import nnfm_loss, nnfm_match, nnfm_numpy, nnfm_pack, nnfm_workspace_bytes  # noqa: F401
 from .palette_reference import (palet_reg_numpy, palette_backward_numpy, palette_forward_numpy, palette_recompose_bits,  # noqa: F401
                                 style_loss_numpy)
-from .ray_registration import RefCloud, extract_ref_cloud, ray_registration_numpy, register_rays, register_views  # noqa: F401
+from .ray_registration import (RefCloud, extract_ref_cloud, extract_ref_template, ray_registration_numpy, register_rays,  # noqa: F401
+                               register_views)
+from .semantic_encoder import SemanticEncoder, build_ref_supervision, load_vgg16_features, vgg16_features  # noqa: F401
+from .ref_stage import (RefEditSet, RefStyleTrainer, pack_ref_arrays, ref_phase, ref_stage_numpy, ref_terms,  # noqa: F401
+                        reference_ref_step, reference_ref_terms)

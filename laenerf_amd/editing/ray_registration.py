@@ -21,10 +21,9 @@ computes 0 / 0 = NaN weights; here the normalised term is 0 and weight_i = f_i.
 
 `ray_registration_numpy` restates this in float64 on the CPU (brute force in chunks); every test compares against it.
 
-Not here yet (the next step): the second-stage training terms that consume these arrays -- the weighted registered
-MSE, the template feature term on nn_feat_replace targets (nnfm_match supplies the matching), the colour-patch term -- and
-`dataloader_nerf`.  The first stage (`dataloader_gt`: fit the palette network to the unedited views) runs through StyleTrainer on
-the views `register_views` returns.
+The second-stage training terms that consume these arrays -- the weighted registered MSE, the template feature term, the
+colour-patch term -- are editing/ref_stage.py (RefEditSet, RefStyleTrainer) with editing/semantic_encoder.py's supervision.  Not
+here yet: the guided Gram loss and `dataloader_nerf` with the NeRF distillation that follows it.
 """
 import numpy as np
 import torch
@@ -32,7 +31,7 @@ import torch
 from ..rays import get_rays
 from .edit_dataset import _crop_terms, _render_views
 
-__all__ = ["RefCloud", "register_rays", "ray_registration_numpy", "extract_ref_cloud", "register_views"]
+__all__ = ["RefCloud", "register_rays", "ray_registration_numpy", "extract_ref_cloud", "extract_ref_template", "register_views"]
 
 
 def _backend():
@@ -204,13 +203,42 @@ def extract_ref_cloud(renderer, pose, intrinsics, H, W, ref_image, alpha, n_jitt
 
 
 @torch.no_grad()
+def extract_ref_template(renderer, pose, intrinsics, H, W, ref_image, image):
+    """single_view_edit_dataset.py:120-153: the template view rendered as extract_ref_cloud renders it; its mask is alpha > 0 of
+    `image` [H,W,3|4] (the template's training image; every pixel of an RGB one), its crop box the bounding box of the masked
+    pixels of non-zero opacity (exclusive upper bounds at the maxima, the reference's slicing).
+    -> {painted [H,W,3]: ref_image's colours on the mask (RGBA premultiplied), zero elsewhere; original [H,W,3]: image's first
+        three channels; box: (x_min, x_max, y_min, y_max)} -- build_ref_supervision's `template`"""
+    dev = renderer.density_bitfield.device
+    pose = torch.as_tensor(pose).to(dev).reshape(1, 4, 4)
+    img = torch.as_tensor(image).to(dev).float()
+    if img.shape[-1] == 4:
+        mask = (img[..., -1].reshape(-1) > 0).nonzero(as_tuple=True)[0]
+    else:
+        mask = torch.arange(H * W, device=dev)
+    rgb = _premultiplied(ref_image, dev)
+    if rgb.shape[0] != H * W or img.shape[0] * img.shape[1] != H * W:
+        raise ValueError("extract_ref_template: ref_image and image must be [H, W, 3|4]")
+    (out, _, _), = _render_views(renderer, pose, intrinsics, H, W, renderer.density_bitfield, None)
+    m = torch.zeros(H * W, dtype=torch.float32, device=dev)
+    m[mask] = out["weights"][mask].float()
+    x, y = m.view(H, W).nonzero(as_tuple=True)
+    if x.numel() == 0:
+        raise ValueError("extract_ref_template: the template view has no masked pixel of non-zero opacity")
+    painted = torch.zeros(H * W, 3, dtype=torch.float32, device=dev)
+    painted[mask] = rgb[mask]
+    return {"painted": painted.view(H, W, 3), "original": img[..., :3].reshape(H, W, 3).contiguous(),
+            "box": (int(x.min()), int(x.max()), int(y.min()), int(y.max()))}
+
+
+@torch.no_grad()
 def register_views(renderer, poses, intrinsics, H, W, images, cloud, reg_dist=2e-2, min_tv_factor=0.1, num_steps=512, batch_views=4):
     """single_view_edit_dataset.py:188-315: every training view rendered against the density bitfield (`batch_views` views per ray
     launch and render, like extract_views), its masked rows (alpha > 0; every pixel of an RGB image) registered to `cloud`.
     -> (views, skipped pose indices).  A view dict carries what EditSet.from_views(views, image_hw=(H, W)) needs with `targets` =
     the premultiplied ground truth (the reference's targets_gt: the dataloader_gt stage), and the registration: ref_targets [R,3],
     target_weights [R], indices_ray_reg [R] (rows of the view), min_dist [K], style_guide (the guide scattered into the crop, zeros
-    off the mask).  A view without a masked pixel of non-zero opacity is skipped."""
+    off the mask), image (the caller's images[i], not copied: build_ref_supervision reads its first three channels).  A view without a masked pixel of non-zero opacity is skipped."""
     dev = renderer.density_bitfield.device
     poses = torch.as_tensor(poses).to(dev).reshape(-1, 4, 4)
     step = max(1, int(batch_views))
@@ -233,7 +261,7 @@ def register_views(renderer, poses, intrinsics, H, W, images, cloud, reg_dist=2e
             v = {"w8s": w_sel, "targets": target, "x_term": x_term, "dirs": dirs, "depths": d_mask, "indices": mask,
                  "depth_factor": (d_mask.max() - d_mask.min()) / num_steps, "weights_densitygrid": out["weights"], "pred_imgs": out["image"],
                  "ref_targets": reg["targets"], "target_weights": reg["target_weights"], "indices_ray_reg": reg["indices_ray_reg"],
-                 "min_dist": reg["min_dist"], "pose_idx": i0 + j}
+                 "min_dist": reg["min_dist"], "pose_idx": i0 + j, "image": images[i0 + j]}
             v.update(_crop_terms(H, W, mask, w_sel, target, d_mask))
             x0, x1, y0, y1 = (int(t) for t in v["cut_min_max_xy"])
             g = torch.zeros(H * W, dtype=torch.float32, device=dev)

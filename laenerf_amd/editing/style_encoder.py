@@ -64,7 +64,7 @@ class _palette_point_loss(Function):
 
     @staticmethod
     @custom_fwd(device_type="cuda")
-    def forward(ctx, w_logits, o_raw, palette, active_mask, target, lw, scale, reg_w=None, m_dev=None, with_pred32=False):
+    def forward(ctx, w_logits, o_raw, palette, active_mask, target, lw, scale, reg_w=None, m_dev=None, with_pred32=False, mse_w=None):
         M = w_logits.shape[0]
         w_logits, o_raw = w_logits.half().contiguous(), o_raw.half().contiguous()
         palette_in = palette
@@ -79,9 +79,10 @@ class _palette_point_loss(Function):
         fin = torch.empty(12, dtype=torch.float32, device=dev)
         # reg_w = (palette_loss_valid, palette_loss_distinct): the palette-only term `palet_loss` rides in the same two launches
         _backend.style_loss_forward(pred, target, w_hat, o_hat, M, n_active, lw, scale, fin,
-                                    reg_palette=palette if reg_w is not None else None, reg_w=reg_w or (0.0, 0.0), m_dev=m_dev)
+                                    reg_palette=palette if reg_w is not None else None, reg_w=reg_w or (0.0, 0.0), m_dev=m_dev, mse_w=mse_w)
         ctx.save_for_backward(w_logits, o_raw, palette, target, fin)
         ctx.meta = (P, active_mask, M, lw, reg_w)
+        ctx.mse_w = mse_w                                # None: the entry points without the MSE's factor (the bits of before)
         ctx.m_dev = m_dev                                # device row count: rows >= *m_dev of the M-row buffers are excluded
         # a palette parameter whose fp32 .grad is a FusedAdam's persistent buffer takes its gradient by an add inside the
         # reduction launch (round 5) instead of through autograd's AccumulateGrad (one more launch on the step's critical path)
@@ -102,7 +103,7 @@ class _palette_point_loss(Function):
     def backward(ctx, g_loss, *rest):
         g_pred = rest[-1] if ctx.with_pred32 else None
         if g_loss is None and g_pred is None:
-            return (None,) * 10
+            return (None,) * 11
         w_logits, o_raw, palette, target, fin = ctx.saved_tensors
         if g_loss is None:
             g_loss = torch.zeros(1, dtype=torch.float32, device=fin.device)
@@ -117,13 +118,14 @@ class _palette_point_loss(Function):
             and owner.grad.is_contiguous() and owner.grad.shape == palette.shape and not owner._backward_hooks \
             and not getattr(owner, "_post_accumulate_grad_hooks", None)
         g_pal = owner.grad if direct else torch.empty_like(palette)
-        if g_pred is not None:
+        if g_pred is not None or ctx.mse_w is not None:
             _backend.style_loss_backward_image(w_logits, o_raw, palette, P, active_mask, M, target, fin, g_loss.float().reshape(1).contiguous(), lw,
-                                               g_pred.float().contiguous(), g_wl, g_ol, g_pal, ctx.m_dev, reg_w=reg_w, accumulate=direct)
+                                               None if g_pred is None else g_pred.float().contiguous(), g_wl, g_ol, g_pal, ctx.m_dev, reg_w=reg_w,
+                                               accumulate=direct, mse_w=ctx.mse_w)
         else:
             _backend.style_loss_backward(w_logits, o_raw, palette, P, active_mask, M, target, fin, g_loss.float().reshape(1).contiguous(), lw,
                                          g_wl, g_ol, g_pal, reg_w=reg_w, accumulate=direct, m_dev=ctx.m_dev)
-        return g_wl, g_ol, (None if direct else g_pal), None, None, None, None, None, None, None
+        return g_wl, g_ol, (None if direct else g_pal), None, None, None, None, None, None, None, None
 
 
 def palette_recompose(w_logits, o_raw, palette, active_mask):
@@ -337,7 +339,8 @@ class LAENeRF(nn.Module):
         """style_encoder.py:111-133"""
         return self.forward_train(x, d)[0]
 
-    def forward_train_loss(self, x, d, target, params, scaler=None, with_palet_loss=False, plan=None, m_dev=None, with_pred32=False):
+    def forward_train_loss(self, x, d, target, params, scaler=None, with_palet_loss=False, plan=None, m_dev=None, with_pred32=False,
+                           mse_weight=1.0):
         """MI355X-native: forward_train + the point-wise losses of train_LAENeRF_step (nerf/utils.py:990-996) in one node:
         loss = MSE(pred, target) + weights_loss(w_hat) + offset_loss(o_hat) [+ palet_loss(params) with with_palet_loss=True: the
         palette-only term and its gradient then ride in the criterion's own launches instead of ~40 tiny torch kernels per step],
@@ -347,7 +350,10 @@ class LAENeRF(nn.Module):
         buffers of M rows (a multiple of 16) of which the first K count -- the losses, their mean and the gradients see only those,
         with the bits of the call on the K rows alone (include/laenerf.h lae_style_loss_*_dev).
         with_pred32=True (needs m_dev): a fifth result, pred as a differentiable fp32 [M,3] tensor for the image terms of the stylization
-        step (their gradient joins the criterion's in the same palette-backward launch)."""
+        step (their gradient joins the criterion's in the same palette-backward launch).
+        mse_weight (other than 1: needs m_dev): the factor of the MSE in the loss and its gradient; 0 leaves the regularisers (and the
+        gradient that comes back through pred32) -- the Ref-NPR second stage computes its own colour term (editing/ref_stage.py).
+        loss.terms[2] stays the unweighted MSE against `target`."""
         if self.dir_encoding is not None:
             assert d is not None
         w_logits, o_raw, M = self._logits(x, d, plan)
@@ -359,7 +365,11 @@ class LAENeRF(nn.Module):
             scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
         lw = (float(params.weight_loss_uniform), float(params.weight_loss_non_uniform), float(params.offset_loss))
         reg_w = (float(params.palette_loss_valid), float(params.palette_loss_distinct)) if with_palet_loss else None
-        out = _palette_point_loss.apply(w_logits, o_raw, self.color_palette, self._active_mask, target, lw, scale, reg_w, m_dev, bool(with_pred32))
+        mse_w = None if float(mse_weight) == 1.0 else float(mse_weight)
+        if mse_w is not None and (m_dev is None or not mse_w >= 0.0):
+            raise RuntimeError("forward_train_loss: mse_weight other than 1 needs m_dev and must be >= 0")
+        out = _palette_point_loss.apply(w_logits, o_raw, self.color_palette, self._active_mask, target, lw, scale, reg_w, m_dev, bool(with_pred32),
+                                        mse_w)
         loss, pred, w_hat, o_hat, fin = out[:5]
         loss.terms = fin
         return (loss, pred, w_hat, o_hat, out[5]) if with_pred32 else (loss, pred, w_hat, o_hat)

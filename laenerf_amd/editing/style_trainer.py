@@ -344,6 +344,8 @@ class StyleTrainer:
     Counters: captures (graphs captured), cache_misses (steps that found no graph for their capacity), steps_skipped (GradScaler);
     capture_error: why image steps run eagerly (None: they are graph-replayed)."""
 
+    _N_TERMS = 4                        # columns of terms(); a subclass with further terms widens the record
+
     def __init__(self, style_enc, edit_set, params, iters, distill_palette_steps=1500, seed=0, graph=True, capacity="bucket", lr=1e-3,
                  style_net=None):
         from ..optim import FusedAdam
@@ -389,7 +391,7 @@ class StyleTrainer:
         self._sched, self._colour = self._draw(max(self.iters, 1))
         edit_set.set_schedule(self._sched)
         self.rec = torch.zeros(self._sched.size, 2, dtype=torch.float32, device=edit_set.device)     # per step: loss, mse
-        self.trec = torch.zeros(self._sched.size, 4, dtype=torch.float32, device=edit_set.device)    # style, tv, smooth, disc
+        self.trec = torch.zeros(self._sched.size, self._N_TERMS, dtype=torch.float32, device=edit_set.device)    # style, tv, smooth, disc
         self.s_d = distill_step(self.iters, distill_palette_steps)
         self.distilled = False
         self.distill_ms = None
@@ -495,7 +497,7 @@ class StyleTrainer:
         rec = torch.zeros(self._sched.size, 2, dtype=torch.float32, device=self.es.device)
         rec[:self.rec.shape[0]].copy_(self.rec)
         self.rec = rec
-        trec = torch.zeros(self._sched.size, 4, dtype=torch.float32, device=self.es.device)
+        trec = torch.zeros(self._sched.size, self._N_TERMS, dtype=torch.float32, device=self.es.device)
         trec[:self.trec.shape[0]].copy_(self.trec)
         self.trec = trec
         self.graphs.clear()
@@ -664,7 +666,7 @@ class StyleTrainer:
             for k, v in ck["style_net"].items():
                 own[k].copy_(v.to(own[k].device))
         self.rec = torch.zeros(self._sched.size, 2, dtype=torch.float32, device=self.es.device)
-        self.trec = torch.zeros(self._sched.size, 4, dtype=torch.float32, device=self.es.device)
+        self.trec = torch.zeros(self._sched.size, self._N_TERMS, dtype=torch.float32, device=self.es.device)
         self._hist, self._thist = [], []
         self.started = True
         return self
@@ -686,7 +688,7 @@ class StyleTrainer:
     def terms(self):
         """per-step unweighted image terms [n,4] float32: style (Gram MSE), tv, smooth transition, depth discontinuity (0 on steps
         without the image terms or with the term's weight at 0)"""
-        return np.concatenate(self._thist) if self._thist else np.zeros((0, 4), np.float32)
+        return np.concatenate(self._thist) if self._thist else np.zeros((0, self._N_TERMS), np.float32)
 
     def losses(self):
         """per-step unscaled losses (MSE + weight + offset + palette terms, nerf/utils.py:990-995, + the weighted image terms on
