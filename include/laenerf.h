@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi21"
+#define LAE_ABI_TAG "abi22"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -168,6 +168,12 @@ LAE_API int lae_sample_train_batch_weighted(const void* images, int dtype, uint3
  * a ray whose image is >= n_img or cell >= 16384 is skipped.  pred, gt [N,3] fp32. */
 LAE_API int lae_error_map_update(float* error_map, uint32_t n_img, uint32_t H, uint32_t W, const int64_t* inds, const int32_t* cells,
                                  const float* pred, const float* gt, uint32_t N, void* stream);
+/* lae_error_map_update for a step trained with another colour criterion: the reference's rule is error = loss.detach(), the trained
+ * criterion's per-ray mean over RGB (nerf/utils.py:592, 624), so err = ((v0 + v1) + v2) / 3 with the element loss v of loss_kind
+ * (LAE_LOSS_*, at lae_composite_rays_train_step_crit; e = pred - gt rounded, every operation rounded).  LAE_LOSS_MSE gives
+ * lae_error_map_update's bits.  LAE_EINVAL additionally: loss_kind out of range, a Huber delta that is not finite and > 0. */
+LAE_API int lae_error_map_update_crit(float* error_map, uint32_t n_img, uint32_t H, uint32_t W, const int64_t* inds, const int32_t* cells,
+                                      const float* pred, const float* gt, uint32_t N, int loss_kind, float loss_param, void* stream);
 
 /* raymarching.cu:201-209  sph_from_ray(rays_o, rays_d, radius, N, coords[N,2]) */
 LAE_API int lae_sph_from_ray(const float* rays_o, const float* rays_d, float radius, uint32_t N,
@@ -353,6 +359,47 @@ LAE_API int lae_composite_rays_train_step_dist(const float* sigmas, const float*
                                        const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
                                        float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
                                        float* dist_partials, void* stream);
+
+/* The colour criteria of the fused step, lae_colour_loss_forward and lae_error_map_update_crit.  Per element, with e = pred - target
+ * rounded to fp32 and r = |e|, the element loss v and dv = d v / d pred (sign(0) = 0):
+ *   LAE_LOSS_MSE    v = e * e                                                  dv = 2 e
+ *   LAE_LOSS_L1     v = r                                                      dv = sign(e)
+ *   LAE_LOSS_HUBER  v = r > delta ? r - 0.5 delta : ((0.5 / delta) * r) * r    dv = r > delta ? sign(e) : e / delta
+ *                   (the reference's loss.py:18-26 huber_loss = torch's HuberLoss(delta) / delta; delta = loss_param, finite, > 0)
+ *   LAE_LOSS_MAPE   v = r * k,  k = 1 / (|target| + 1e-2)                      dv = sign(e) * k     (loss.py:7-16 mape_loss)
+ * the loss is the mean of v over all elements.  loss_param is read by LAE_LOSS_HUBER only. */
+#define LAE_LOSS_MSE 0
+#define LAE_LOSS_L1 1
+#define LAE_LOSS_HUBER 2
+#define LAE_LOSS_MAPE 3
+/* lae_composite_rays_train_step_dist with the colour criterion chosen by loss_kind and an opacity-entropy term on weights_sum
+ * (torch-ngp's lambda_entropy) in the same launch:
+ *   loss = mean(v) [+ lambda * mean(res^2)] [+ dist_lambda * L_dist] [+ opac_lambda * L_op]
+ *   grad_image = ((e * (2 / (3 N))) * *scale) under LAE_LOSS_MSE -- the statements and the bits of lae_composite_rays_train_step --
+ *                and ((dv * (1 / (3 N))) * *scale) otherwise.
+ *   o = min(max(weights_sum, 1e-5f), 1 - 1e-5f),  opac[ray] = h = -(o * log2(o) + (1 - o) * log2(1 - o)),
+ *   L_op = (1/N) sum over ALL N rays of h (a ray without samples has weights_sum = 0: it adds h(1e-5) and has no gradient),
+ *   grad_ws[ray] = ((opac_lambda / N) * (log2(1 - o) - log2(o))) * *scale where 1e-5f <= weights_sum <= 1 - 1e-5f and 0 outside
+ *   (torch.clamp's gradient, bounds included); opac_value_only != 0 computes the value and forces grad_ws = 0.  The backward takes
+ *   it where lae_composite_rays_train_backward_blend_ex takes grad_weights_sum: the fused call equals the forward plus that call
+ *   with (grad_ws, grad_image).  It costs no work per sample: it joins the ray's constant of the bracket.
+ * dist == NULL switches the distortion term off (the other dist arguments are then not looked at), opac == NULL the entropy term
+ * (likewise), depth_src == NULL the depth term.  With LAE_LOSS_MSE and opac == NULL every output has the bits of
+ * lae_composite_rays_train_step_dist (of lae_composite_rays_train_step[_depth] without dist).
+ * partials[b] = sum over the workgroup's rays of (v0 + v1 + v2 + 3 * opac_lambda * h + the depth and distortion parts), so every
+ * finisher (n_elem = 3 N) yields the total loss unchanged; opac_partials [cdiv(N, 4)] receive sum(h):
+ * lae_loss_finish(opac_partials, cdiv(N, 4), N, NULL, out) gives L_op alone.  opac, grad_ws [N].
+ * LAE_EINVAL: loss_kind out of range, a Huber delta that is not finite and > 0, opac_lambda not finite and >= 0. */
+LAE_API int lae_composite_rays_train_step_crit(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                       uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
+                                       float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
+                                       const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
+                                       float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
+                                       float* partials, int defer_loss, const void* depth_src, int depth_dtype,
+                                       const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
+                                       float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
+                                       float* dist_partials, int loss_kind, float loss_param, float opac_lambda, int opac_value_only,
+                                       float* opac, float* grad_ws, float* opac_partials, void* stream);
 
 /* raymarching.cu:929-936 */
 LAE_API int lae_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive,
@@ -1143,6 +1190,12 @@ LAE_API int lae_adam_apply(float* param, float* exp_avg, float* exp_avg_sq, void
  * grad[i] = d loss_out[0] / d pred[i].  scale: device float (FusedAdam state word 0) or NULL (= 1).  fp32, n elements. */
 LAE_API int lae_mse_loss_forward(const float* pred, const float* target, uint32_t n, const float* scale, float* loss_out, float* grad,
                          void* stream);
+/* lae_mse_loss_forward with the colour criterion chosen by loss_kind (LAE_LOSS_*, at lae_composite_rays_train_step_crit): the
+ * criterion of a step that does not run the fused compositing step.  loss_out[1] = mean(v), loss_out[0] = that * scale,
+ * grad[i] = ((dv * (1 / n)) * scale).  LAE_LOSS_MSE runs lae_mse_loss_forward's statements and gives its bits.  LAE_EINVAL: n == 0,
+ * loss_kind out of range, a Huber delta (loss_param) that is not finite and > 0. */
+LAE_API int lae_colour_loss_forward(const float* pred, const float* target, uint32_t n, int loss_kind, float loss_param, const float* scale,
+                            float* loss_out, float* grad, void* stream);
 
 /* multi-tensor forms of check / apply: host arrays of n_tensors (<= 8) device pointers / sizes; one launch each.
  * touched_lines (may be NULL, entries may be NULL): per tensor the bitmap lae_grid_encode_backward_ex maintains (one bit per 16

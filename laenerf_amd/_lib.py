@@ -34,6 +34,7 @@ SIGNATURES = {
     "lae_sample_train_batch_weighted": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, vp, f32, u64, vp, i32, i32, vp, vp,
                                         vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_error_map_update": [vp, u32, u32, u32, vp, vp, vp, vp, u32, vp],
+    "lae_error_map_update_crit": [vp, u32, u32, u32, vp, vp, vp, vp, u32, i32, f32, vp],
     "lae_composite_rays_train_forward": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, vp],
     "lae_composite_rays_train_backward": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, vp, vp],
     "lae_composite_rays_train_forward_blend": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp],
@@ -42,6 +43,7 @@ SIGNATURES = {
     "lae_composite_rays_train_backward_blend_depth": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
     "lae_composite_rays_train_forward_blend_dist": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
     "lae_composite_rays_train_step_dist": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, f32, i32, vp, vp, vp, vp],
+    "lae_composite_rays_train_step_crit": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, f32, i32, vp, vp, vp, i32, f32, f32, i32, vp, vp, vp, vp],
     "lae_composite_rays_train_backward_blend_dist": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_loss_finish": [vp, u32, u32, vp, vp, vp],
     "lae_composite_rays_train_backward_blend": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp],
@@ -135,6 +137,7 @@ SIGNATURES = {
     "lae_style_assemble_backward": [vp, vp, u32, u32, vp, vp],
     "lae_min_dist_to_points": [vp, u32, vp, u32, f32, vp, vp, vp, vp],
     "lae_mse_loss_forward": [vp, vp, u32, vp, vp, vp, vp],
+    "lae_colour_loss_forward": [vp, vp, u32, i32, f32, vp, vp, vp, vp],
     "lae_adam_check": [vp, i32, u64, vp, vp],
     "lae_adam_check_multi": [u32, vp, vp, vp, vp, vp],
     "lae_adam_apply_multi": [u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp],
@@ -177,7 +180,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi21"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi22"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

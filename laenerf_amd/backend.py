@@ -45,6 +45,20 @@ def _need_f32(*ts):
             raise RuntimeError("laenerf_amd.raymarching: float32 tensors required (the reference's wrappers cast to fp32)")
 
 
+LOSS_KINDS = {"mse": 0, "l1": 1, "huber": 2, "mape": 3}       # include/laenerf.h LAE_LOSS_*
+
+
+def loss_kind(who, loss, huber_delta=0.1):
+    """-> (LAE_LOSS_* code, loss_param) of the colour criterion `loss`; ValueError for an unknown name or, under 'huber', a delta
+    that is not finite and > 0"""
+    if loss not in LOSS_KINDS:
+        raise ValueError(f"{who}: loss must be one of {sorted(LOSS_KINDS)}")
+    d = float(huber_delta)
+    if loss == "huber" and (not (d > 0.0) or d == float("inf")):
+        raise ValueError(f"{who}: huber_delta must be finite and > 0")
+    return LOSS_KINDS[loss], d if loss == "huber" else 0.0
+
+
 _scratch = {}
 _scratch_retired = []
 
@@ -266,7 +280,7 @@ class _RayMarching:
     @staticmethod
     def composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears, fars, bg_rays, bg, rows_end, target, scale,
                                   weights_sum, depth, image, depth_out, image_out, grad_image, grad_sigmas, grad_rgbs, loss_out,
-                                  partials, defer_loss=False, depth_sup=None, dist_sup=None):
+                                  partials, defer_loss=False, depth_sup=None, dist_sup=None, crit=None):
         """MI355X extension: compositing forward (+ blend) + MSE criterion + compositing backward in one launch.
         defer_loss: the loss VALUE (loss_out, NaN until then) is summed later -- by the fused head's backward, which takes it
         along in its reduction launch, or by flush_pending_loss() (laenerf_amd.optim.FusedAdam.backward / step call it).
@@ -275,7 +289,10 @@ class _RayMarching:
         then holds MSE + weight * depth MSE whoever finishes it.
         dist_sup: None, or (weight, value_only, dist, grad_dist, dist_partials): the distortion term of
         lae_composite_rays_train_step_dist in the same launch, with or without depth_sup; the loss value then also holds
-        weight * mean(l_ray)."""
+        weight * mean(l_ray).
+        crit: None, or (loss_kind, loss_param, opac_sup) with opac_sup None or (weight, value_only, opac, grad_ws, opac_partials): the
+        colour criterion LOSS_KINDS[...] and the opacity-entropy term of lae_composite_rays_train_step_crit in the same launch, with or
+        without depth_sup and dist_sup; the loss value then holds mean(v) of that criterion plus weight * mean(h)."""
         ts = (sigmas, rgbs, deltas, rays, nears, fars, bg_rays, rows_end, target, scale, weights_sum, depth, image, depth_out,
               image_out, grad_image, grad_sigmas, grad_rgbs, loss_out, partials)
         need_cuda(*ts); need_contig(*ts)
@@ -301,15 +318,28 @@ class _RayMarching:
                 raise RuntimeError("composite_rays_train_step: grad_depth needs N, depth_partials cdiv(N, 4) floats")
             dargs = (ptr(depth_src), _DEPTH_DTYPES[depth_src.dtype], ptr(depth_inds), float(weight), int(bool(value_only)),
                      ptr(grad_depth), ptr(depth_partials))
+        xargs = (0.0, 0, None, None, None)                # lae_composite_rays_train_step_crit without a distortion term
         if dist_sup is not None:
             dist_weight, dist_value_only, dist, grad_dist, dist_partials = dist_sup
             xs = (dist, grad_dist, dist_partials)
             need_cuda(*xs); need_contig(*xs); _need_f32(*xs)
             if any(x is None for x in xs) or dist.numel() < N or grad_dist.numel() < N or dist_partials.numel() < (N + 3) // 4:
                 raise RuntimeError("composite_rays_train_step: dist and grad_dist need N, dist_partials cdiv(N, 4) floats")
-            check(_lib.load().lae_composite_rays_train_step_dist(
-                *args, *dargs, float(dist_weight), int(bool(dist_value_only)), ptr(dist), ptr(grad_dist), ptr(dist_partials), stream()),
-                "composite_rays_train_step_dist")
+            xargs = (float(dist_weight), int(bool(dist_value_only)), ptr(dist), ptr(grad_dist), ptr(dist_partials))
+        if crit is not None:
+            loss_kind, loss_param, opac_sup = crit
+            oargs = (0.0, 0, None, None, None)            # ... and without the entropy term
+            if opac_sup is not None:
+                opac_weight, opac_value_only, opac, grad_ws, opac_partials = opac_sup
+                os_ = (opac, grad_ws, opac_partials)
+                need_cuda(*os_); need_contig(*os_); _need_f32(*os_)
+                if any(x is None for x in os_) or opac.numel() < N or grad_ws.numel() < N or opac_partials.numel() < (N + 3) // 4:
+                    raise RuntimeError("composite_rays_train_step: opac and grad_ws need N, opac_partials cdiv(N, 4) floats")
+                oargs = (float(opac_weight), int(bool(opac_value_only)), ptr(opac), ptr(grad_ws), ptr(opac_partials))
+            check(_lib.load().lae_composite_rays_train_step_crit(*args, *dargs, *xargs, int(loss_kind), float(loss_param), *oargs, stream()),
+                  "composite_rays_train_step_crit")
+        elif dist_sup is not None:
+            check(_lib.load().lae_composite_rays_train_step_dist(*args, *dargs, *xargs, stream()), "composite_rays_train_step_dist")
         elif depth_sup is not None:
             check(_lib.load().lae_composite_rays_train_step_depth(*args, *dargs, stream()), "composite_rays_train_step_depth")
         else:
@@ -363,6 +393,26 @@ class _RayMarching:
             raise RuntimeError("composite_rays_train_backward_blend_dist: depth, grad_dist, dist (and grad_depth) need a value per ray")
         check(_lib.load().lae_composite_rays_train_backward_blend_dist(*args, ptr(grad_depth), ptr(depth), ptr(grad_dist), ptr(dist),
                                                                        stream()), "composite_rays_train_backward_blend_dist")
+
+    @staticmethod
+    def colour_loss_forward(pred, target, n, loss_kind, loss_param, scale, loss_out, grad):
+        """lae_colour_loss_forward: loss_out[1] = mean(v) of the criterion loss_kind (LOSS_KINDS), loss_out[0] = that * scale, grad [n]"""
+        ts = (pred, target, scale, loss_out, grad)
+        need_cuda(*ts); need_contig(*ts); _need_f32(*ts)
+        if pred.numel() < n or target.numel() < n or grad.numel() < n or loss_out.numel() < 2:
+            raise RuntimeError("colour_loss_forward: pred, target and grad need n floats, loss_out 2")
+        check(_lib.load().lae_colour_loss_forward(ptr(pred), ptr(target), n, int(loss_kind), float(loss_param), ptr(scale), ptr(loss_out),
+                                                  ptr(grad), stream()), "colour_loss_forward")
+
+    @staticmethod
+    def error_map_update(error_map, n_img, H, W, inds, cells, pred, gt, N, kind=0, param=0.0):
+        """lae_error_map_update_crit: the map's EMA with the per-ray mean of the criterion `kind` (LOSS_KINDS; 0 = the squared error)"""
+        ts = (error_map, inds, cells, pred, gt)
+        need_cuda(*ts); need_contig(*ts); _need_f32(error_map, pred, gt)
+        if inds.dtype != torch.int64 or cells.dtype != torch.int32 or min(inds.numel(), cells.numel()) < N or min(pred.numel(), gt.numel()) < 3 * N:
+            raise RuntimeError("error_map_update: inds int64 [N], cells int32 [N], pred and gt [N,3] expected")
+        check(_lib.load().lae_error_map_update_crit(ptr(error_map), n_img, H, W, ptr(inds), ptr(cells), ptr(pred), ptr(gt), N, int(kind),
+                                                    float(param), stream()), "error_map_update_crit")
 
     @staticmethod
     def loss_finish(partials, n_part, n_elem, scale, loss_out):

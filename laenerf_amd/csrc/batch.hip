@@ -260,6 +260,27 @@ __global__ __launch_bounds__(256) void k_error_map_update(
     *m = __fadd_rn(__fmul_rn(0.1f, *m), __fmul_rn(0.9f, err));
 }
 
+// k_error_map_update with the element loss of another colour criterion in the squared error's place (lae::colour_elem_loss)
+__global__ __launch_bounds__(256) void k_error_map_update_crit(
+    float* __restrict__ error_map, uint32_t n_img, uint64_t HW, const int64_t* __restrict__ inds, const int32_t* __restrict__ cells,
+    const float* __restrict__ pred, const float* __restrict__ gt, uint32_t N, int kind, float delta) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float g = gt[3 * (size_t)n + k];
+        const float v = lae::colour_elem_loss(kind, delta, __fsub_rn(pred[3 * (size_t)n + k], g), g).v;
+        s = k == 0 ? v : __fadd_rn(s, v);
+    }
+    const float err = __fdiv_rn(s, 3.0f);
+    const uint64_t img = (uint64_t)inds[n] / HW;
+    const uint32_t c = (uint32_t)cells[n];
+    if (img >= n_img || c >= EM_CELLS) return;
+    float* m = error_map + (size_t)img * EM_CELLS + c;
+    *m = __fadd_rn(__fmul_rn(0.1f, *m), __fmul_rn(0.9f, err));
+}
+
 __global__ void k_advance_step(int64_t* __restrict__ step_counter) { step_counter[0] += 1; }
 
 }  // namespace
@@ -327,6 +348,19 @@ int lae_error_map_update(float* error_map, uint32_t n_img, uint32_t H, uint32_t 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     k_error_map_update<<<lae::cdiv(N, 256), 256, 0, s>>>(error_map, n_img, (uint64_t)H * W, inds, cells, pred, gt, N);
     return lae::check_launch("error_map_update");
+}
+
+int lae_error_map_update_crit(float* error_map, uint32_t n_img, uint32_t H, uint32_t W, const int64_t* inds, const int32_t* cells,
+                              const float* pred, const float* gt, uint32_t N, int loss_kind, float loss_param, void* stream) {
+    if (!lae::colour_loss_kind_ok(loss_kind, loss_param)) return LAE_EINVAL;
+    if (loss_kind == LAE_LOSS_MSE) return lae_error_map_update(error_map, n_img, H, W, inds, cells, pred, gt, N, stream);
+    if (N == 0) return LAE_OK;
+    if (!error_map || !inds || !cells || !pred || !gt) return LAE_ENULL;
+    if (n_img == 0 || H == 0 || W == 0 || N > EM_CELLS) return LAE_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    k_error_map_update_crit<<<lae::cdiv(N, 256), 256, 0, s>>>(error_map, n_img, (uint64_t)H * W, inds, cells, pred, gt, N, loss_kind,
+                                                              loss_param);
+    return lae::check_launch("error_map_update_crit");
 }
 
 }  // extern "C"

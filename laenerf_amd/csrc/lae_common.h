@@ -102,6 +102,29 @@ static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b -
 
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }
 
+// The colour criteria (include/laenerf.h, LAE_LOSS_*) on one element: e = pred - target as the caller rounded it, r = |e|.
+// -> the element loss v and dv = d v / d pred; sign(0) = 0.  One statement each, shared by the fused compositing step
+// (raymarching.hip), lae_colour_loss_forward (loss.hip) and lae_error_map_update_crit (batch.hip).  `delta`: Huber's, > 0.
+struct ElemLoss { float v, dv; };
+__device__ __forceinline__ ElemLoss colour_elem_loss(int kind, float delta, float e, float target) {
+    const float r = fabsf(e);
+    const float sg = e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f);
+    if (kind == LAE_LOSS_L1) return {r, sg};
+    if (kind == LAE_LOSS_HUBER) {                                            // loss.py:18-26
+        if (r > delta) return {r - 0.5f * delta, sg};
+        return {(__fdiv_rn(0.5f, delta) * r) * r, __fdiv_rn(e, delta)};
+    }
+    if (kind == LAE_LOSS_MAPE) {                                             // loss.py:7-16
+        const float k = __fdiv_rn(1.0f, fabsf(target) + 1e-2f);
+        return {r * k, sg * k};
+    }
+    return {e * e, 2.0f * e};
+}
+__host__ __device__ __forceinline__ bool colour_loss_kind_ok(int kind, float delta) {
+    if (kind < LAE_LOSS_MSE || kind > LAE_LOSS_MAPE) return false;
+    return kind != LAE_LOSS_HUBER || (delta > 0.0f && delta <= 3.0e38f);  // NaN, zero, negative and infinite deltas
+}
+
 // wave64 inclusive scan on the DPP data path: row shifts 1, 2, 4, 8 inside the 16-lane rows, then row_bcast:15 / :31
 // across them (GFX9 controls); lanes a shift leaves without a source add 0.  (__shfl_up compiles to ds_bpermute_b32, an
 // LDS round trip per step.)

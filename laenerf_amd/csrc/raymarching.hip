@@ -646,16 +646,26 @@ struct DepthLoss { const void* src; int dtype; const int64_t* inds; float lambda
 // the term alone go to DistLoss::partials (lae_loss_finish with n_elem = N gives L_dist).
 struct DistLoss { float lambda; int value_only; float* dist; float* grad_dist; float* partials; };
 
-template <bool DEPTH, bool DIST>
+// CRIT: the colour criterion is chosen by `kind` (lae::colour_elem_loss; LAE_LOSS_MSE runs the statements above), and with
+// opac != NULL the opacity entropy of the ray's weights_sum W joins the loss: o = clamp(W, 1e-5, 1 - 1e-5),
+// h = -(o log2 o + (1 - o) log2(1 - o)), loss += lambda * mean over ALL N rays of h, grad_ws[index] = ((lambda / N) * (log2(1 - o)
+// - log2 o)) * scale where W lies in [1e-5, 1 - 1e-5] (torch.clamp's gradient) and 0 outside or with value_only.  The backward takes
+// it where k_composite_train_bwd<true> takes grad_weights_sum -- the ray's constant of the bracket, nothing per sample.  partials[]
+// additionally receive 3 * lambda * sum(h), CritLoss::partials sum(h).  The CRIT = false instantiations are the kernels they were.
+struct CritLoss { int kind; float delta; float lambda; int value_only; float* opac; float* grad_ws; float* partials; };
+
+template <bool DEPTH, bool DIST, bool CRIT = false>
 __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
     const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum,
     float* __restrict__ depth, float* __restrict__ image, Blend bl, StepLoss sl, const uint32_t* __restrict__ rows_end_p,
     float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, std::conditional_t<DEPTH, DepthLoss, NoArg> dl,
-    std::conditional_t<DIST, DistLoss, NoArg> xl) {
+    std::conditional_t<DIST, DistLoss, NoArg> xl, std::conditional_t<CRIT, CritLoss, NoArg> cl) {
     __shared__ float s_sq[COMP_WAVES];
     [[maybe_unused]] __shared__ float s_dq[COMP_WAVES];
     [[maybe_unused]] __shared__ float s_xq[COMP_WAVES];
+    [[maybe_unused]] __shared__ float s_oq[COMP_WAVES];
+    [[maybe_unused]] float oq = 0.0f, gws_in = 0.0f;                        // CRIT: the ray's entropy h and its grad_ws
     [[maybe_unused]] DepthState<DEPTH> ds;
     [[maybe_unused]] DistState<DIST> xs;
     [[maybe_unused]] DistAcc<DIST> xa;
@@ -690,7 +700,27 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
         const float e0 = o[0] - sl.target[3 * (size_t)index], e1 = o[1] - sl.target[3 * (size_t)index + 1],
                     e2 = o[2] - sl.target[3 * (size_t)index + 2];
         sq = fmaf(e2, e2, fmaf(e1, e1, e0 * e0));
-        const float g0 = (e0 * gk) * s, g1 = (e1 * gk) * s, g2 = (e2 * gk) * s;
+        float g0 = (e0 * gk) * s, g1 = (e1 * gk) * s, g2 = (e2 * gk) * s;
+        if constexpr (CRIT) {
+            if (cl.kind != LAE_LOSS_MSE) {                                  // uniform over the launch
+                const float g1n = 1.0f / (float)(3u * N);
+                const lae::ElemLoss l0 = lae::colour_elem_loss(cl.kind, cl.delta, e0, sl.target[3 * (size_t)index]),
+                                    l1 = lae::colour_elem_loss(cl.kind, cl.delta, e1, sl.target[3 * (size_t)index + 1]),
+                                    l2 = lae::colour_elem_loss(cl.kind, cl.delta, e2, sl.target[3 * (size_t)index + 2]);
+                sq = (l0.v + l1.v) + l2.v;
+                g0 = (l0.dv * g1n) * s; g1 = (l1.dv * g1n) * s; g2 = (l2.dv * g1n) * s;
+            }
+            if (cl.opac) {
+                const float hi = 1.0f - 1e-5f;
+                const float oc = fminf(fmaxf(a.ws, 1e-5f), hi);
+                const float la = log2f(oc), lb = log2f(1.0f - oc);
+                oq = -(oc * la + (1.0f - oc) * lb);
+                sq = sq + (3.0f * cl.lambda) * oq;
+                const bool inside = a.ws >= 1e-5f && a.ws <= hi;
+                gws_in = cl.value_only || !inside ? 0.0f : ((cl.lambda / (float)N) * (lb - la)) * s;
+                if (lane == 0) { cl.opac[index] = oq; cl.grad_ws[index] = gws_in; }
+            }
+        }
         if constexpr (DEPTH) {
             const size_t zi = dl.inds ? (size_t)dl.inds[index] : (size_t)index;
             const float z = dl.dtype == LAE_IMG_F16 ? __half2float(((const __half*)dl.src)[zi]) : ((const float*)dl.src)[zi];
@@ -719,7 +749,8 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
         }
         // ---- backward (DENSE, grad_weights_sum = 0, grad_scale = 1)
         if (h.has) {
-            const float gws = 0.0f - ((g0 * bg[0] + g1 * bg[1]) + g2 * bg[2]);
+            float gws = 0.0f - ((g0 * bg[0] + g1 * bg[1]) + g2 * bg[2]);
+            if constexpr (CRIT) gws = gws_in - ((g0 * bg[0] + g1 * bg[1]) + g2 * bg[2]);      // grad_ws enters where the blend's term does
             const BwdRay c{g0, g1, g2, a.r, a.g, a.b, gws * (1 - a.ws)};
             BwdRun st;
             bool stopped = false;
@@ -740,6 +771,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
     if (lane == 0) s_sq[wv] = sq;
     if constexpr (DEPTH) { if (lane == 0) s_dq[wv] = ds.dq; }
     if constexpr (DIST) { if (lane == 0) s_xq[wv] = xa.l; }
+    if constexpr (CRIT) { if (lane == 0) s_oq[wv] = oq; }
     __syncthreads();
     if (threadIdx.x == 0) {
         float t = 0.0f;
@@ -757,6 +789,14 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
 #pragma unroll
             for (int w = 0; w < COMP_WAVES; w++) u += s_xq[w];
             xl.partials[blockIdx.x] = u;
+        }
+        if constexpr (CRIT) {
+            if (cl.opac) {
+                float u = 0.0f;
+#pragma unroll
+                for (int w = 0; w < COMP_WAVES; w++) u += s_oq[w];
+                cl.partials[blockIdx.x] = u;
+            }
         }
         // deferred loss value (lae_composite_rays_train_step with poison_loss): whoever reads it before the finishing
         // launch (lae_loss_finish, or the extra block of lae_nerf_head_backward) sees NaN, not a stale number
@@ -893,13 +933,18 @@ __global__ __launch_bounds__(COMPACT_BLOCK) void k_compact_scatter(const int32_t
 }
 
 // ---------------------------------------------------------------- host side of K7 / K8: one body per pair of C entries
-// lae_composite_rays_train_step[_depth | _dist]: the depth- and dist-only arguments are checked first, before the N == 0 return
-template <bool DEPTH, bool DIST = false>
+// lae_composite_rays_train_step[_depth | _dist | _crit]: the depth-, dist- and crit-only arguments are checked first, before the N == 0 return
+template <bool DEPTH, bool DIST = false, bool CRIT = false>
 int composite_train_step_impl(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
                                      float T_thresh, const Blend& bl, const uint32_t* rows_end, const StepLoss& sl, float* weights_sum,
                                      float* depth, float* image, float* grad_sigmas, float* grad_rgbs, float* loss_out, int defer_loss,
                                      const std::conditional_t<DEPTH, DepthLoss, NoArg>& dl, const char* what, void* stream,
-                                     const std::conditional_t<DIST, DistLoss, NoArg>& xl = {}) {
+                                     const std::conditional_t<DIST, DistLoss, NoArg>& xl = {},
+                                     const std::conditional_t<CRIT, CritLoss, NoArg>& cl = {}) {
+    if constexpr (CRIT) {
+        if (!lae::colour_loss_kind_ok(cl.kind, cl.delta)) return LAE_EINVAL;
+        if (cl.opac && (!(cl.lambda >= 0.0f) || !(cl.lambda <= 3.0e38f))) return LAE_EINVAL;
+    }
     if constexpr (DEPTH) {
         if (dl.dtype != LAE_IMG_F16 && dl.dtype != LAE_IMG_F32) return LAE_EINVAL;
         if (!(dl.lambda >= 0.0f) || !(dl.lambda <= 3.0e38f)) return LAE_EINVAL;      // NaN, negative and infinite weights
@@ -917,10 +962,14 @@ int composite_train_step_impl(const float* sigmas, const float* rgbs, const floa
     if constexpr (DIST) {
         if (!xl.dist || !xl.grad_dist || !xl.partials) return LAE_ENULL;
     }
+    if constexpr (CRIT) {
+        if (cl.opac && (!cl.grad_ws || !cl.partials)) return LAE_ENULL;
+    }
     if (M > 0 && (!sigmas || !rgbs || !deltas || !grad_sigmas || !grad_rgbs)) return LAE_ENULL;
     const uint32_t nb = lae::cdiv(N, COMP_WAVES);
-    k_composite_train_step<DEPTH, DIST><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth,
-                                                                              image, bl, sl, rows_end, grad_sigmas, grad_rgbs, dl, xl);
+    k_composite_train_step<DEPTH, DIST, CRIT><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum,
+                                                                                    depth, image, bl, sl, rows_end, grad_sigmas, grad_rgbs, dl,
+                                                                                    xl, cl);
     // defer_loss: the one-block sum of the partials (5.5 us + a kernel boundary on the step's critical path for a number that
     // feeds nothing on the device) is left to lae_loss_finish or to a later launch that takes it along
     // (lae_nerf_head_backward); loss_out holds NaN until then
@@ -1139,6 +1188,34 @@ int lae_composite_rays_train_step_dist(const float* sigmas, const float* rgbs, c
                                                  grad_sigmas, grad_rgbs, loss_out, defer_loss,
                                                  DepthLoss{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials},
                                                  "composite_rays_train_step_dist", stream, xl);
+}
+
+int lae_composite_rays_train_step_crit(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                       uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
+                                       float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
+                                       const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
+                                       float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
+                                       float* partials, int defer_loss, const void* depth_src, int depth_dtype,
+                                       const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
+                                       float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
+                                       float* dist_partials, int loss_kind, float loss_param, float opac_lambda, int opac_value_only,
+                                       float* opac, float* grad_ws, float* opac_partials, void* stream) {
+    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
+    const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
+    const DistLoss xl{dist_lambda, dist_value_only != 0, dist, grad_dist, dist_partials};
+    const DepthLoss dl{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials};
+    const CritLoss cl{loss_kind, loss_param, opac_lambda, opac_value_only != 0, opac, grad_ws, opac_partials};
+    const char* what = "composite_rays_train_step_crit";
+    // depth_src == NULL: no depth term; dist == NULL: no distortion term (their other arguments are not looked at)
+    auto run = [&](auto with_depth, auto with_dist, const auto& dla, const auto& xla) {
+        return composite_train_step_impl<decltype(with_depth)::value, decltype(with_dist)::value, true>(
+            sigmas, rgbs, deltas, rays, M, N, T_thresh, bl, rows_end, sl, weights_sum, depth, image, grad_sigmas, grad_rgbs, loss_out,
+            defer_loss, dla, what, stream, xla, cl);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (!depth_src) return dist ? run(no, yes, NoArg{}, xl) : run(no, no, NoArg{}, NoArg{});
+    return dist ? run(yes, yes, dl, xl) : run(yes, no, dl, NoArg{});
 }
 
 int lae_loss_finish(const float* partials, uint32_t n_part, uint32_t n_elem, const float* scale, float* loss_out, void* stream) {

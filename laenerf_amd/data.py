@@ -170,12 +170,18 @@ def cell_span(cells, H, W):
     return lo[0], hi[0], lo[1], hi[1]
 
 
-def ema_update(error_map, inds, cells, pred, gt, H, W):
-    """numpy restatement of lae_error_map_update on a copy of error_map [n_img, 16384] -> the updated map"""
+def ema_update(error_map, inds, cells, pred, gt, H, W, loss="mse", huber_delta=0.1):
+    """numpy restatement of lae_error_map_update[_crit] on a copy of error_map [n_img, 16384] -> the updated map; loss: the colour
+    criterion whose element loss takes the squared error's place (raymarching.colour_loss_numpy in float32)"""
     out = np.array(error_map, dtype=np.float32, copy=True)
     f32 = np.float32
     d = np.asarray(pred, f32) - np.asarray(gt, f32)
-    err = ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]) / f32(3)
+    if loss == "mse":
+        err = ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]) / f32(3)
+    else:
+        from .raymarching.raymarching import colour_loss_numpy
+        v = colour_loss_numpy(d, np.asarray(gt, f32), loss, huber_delta, dtype=f32)[0]
+        err = ((v[:, 0] + v[:, 1]) + v[:, 2]) / f32(3)
     img = np.asarray(inds, np.int64) // (H * W)
     c = np.asarray(cells, np.int64)
     out[img, c] = f32(0.1) * out[img, c] + f32(0.9) * err
@@ -376,9 +382,11 @@ class ResidentImages:
         return res
 
     @torch.no_grad()
-    def update_error_map(self, pred, batch):
+    def update_error_map(self, pred, batch, loss="mse", huber_delta=0.1):
         """the reference's EMA after a step (nerf/utils.py:609-631): map[image][cell] = 0.1 * map + 0.9 * mean over RGB of
-        (pred - gt)^2 for every ray of `batch` (a result of sample() with the map); pred [N,3] is the step's image"""
+        (pred - gt)^2 for every ray of `batch` (a result of sample() with the map); pred [N,3] is the step's image.
+        loss / huber_delta: the colour criterion the step trained on ('mse', 'l1', 'huber', 'mape'); its element loss takes the squared
+        error's place, the reference's `error = loss.detach()` (`lae_error_map_update_crit`)"""
         if self.error_map is None:
             raise ValueError("ResidentImages.update_error_map: no error map (error_map=True or enable_error_map())")
         cells, inds, gt = batch["cells"], batch["inds"], batch["gt"]
@@ -389,8 +397,10 @@ class ResidentImages:
         if pred.shape[0] != n:
             raise ValueError("ResidentImages.update_error_map: pred must be [N, 3] for the batch's N rays")
         _lib.need_cuda(self.error_map, pred, gt)
-        check(_lib.load().lae_error_map_update(ptr(self.error_map), self.n_img, self.H, self.W, ptr(inds), ptr(cells), ptr(pred),
-                                               ptr(gt), n, stream()), "error_map_update")
+        from .backend import loss_kind
+        kind, param = loss_kind("ResidentImages.update_error_map", loss, huber_delta)
+        check(_lib.load().lae_error_map_update_crit(ptr(self.error_map), self.n_img, self.H, self.W, ptr(inds), ptr(cells), ptr(pred),
+                                                    ptr(gt), n, kind, param, stream()), "error_map_update_crit")
 
     def state_dict(self):
         """what a resumed run needs of the sampler, never the images: seed (int), step (the device counter, int64 [1], on the host)

@@ -401,12 +401,15 @@ class _composite_rays_train_blend_mse(Function):
     depth plane by the kernel; the outputs depth_partials, grad_depth (the depth partial sums, d loss / d D) are None without it.
     dist_sup = (distort_weight, value_only) adds distort_weight * mean(l_ray), the distortion term
     (`lae_composite_rays_train_step_dist`, with or without depth_sup); the last three outputs (its partial sums, d loss / d l_ray,
-    l_ray per ray) are None without it."""
+    l_ray per ray) are None without it.
+    crit = (loss_kind, loss_param, None or (opacity_weight, value_only)) chooses the colour criterion and adds the opacity-entropy term
+    (`lae_composite_rays_train_step_crit`, with or without the other two); the last three outputs (the entropy's partial sums,
+    d loss / d weights_sum, the entropy per ray) are None without the term.  crit=None is the call as it was."""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, defer_loss=False,
-                depth_sup=None, dist_sup=None):
+                depth_sup=None, dist_sup=None, crit=None):
         sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
         M, N = sigmas.shape[0], rays.shape[0]
         dev = sigmas.device
@@ -429,22 +432,28 @@ class _composite_rays_train_blend_mse(Function):
             dist, grad_dist = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
             dist_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
             dist_sup = dist_sup + (dist, grad_dist, dist_partials)
+        opac = grad_ws = opac_partials = None
+        if crit is not None and crit[2] is not None:
+            opac, grad_ws = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
+            opac_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
+            crit = (crit[0], crit[1], crit[2] + (opac, grad_ws, opac_partials))
         _backend.composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(), fars.contiguous(), bg_rays,
                                            bg, rows_end, target, scale, weights_sum, depth, image, depth_out, image_out, grad_image,
                                            grad_sigmas, grad_rgbs, out, partials, defer_loss=defer_loss, depth_sup=depth_sup,
-                                           dist_sup=dist_sup)
+                                           dist_sup=dist_sup, crit=crit)
         ctx.save_for_backward(grad_sigmas, grad_rgbs)
         aux = (weights_sum, depth_out, image_out, out) + (() if depth_sup is None else (depth_partials, grad_depth)) + \
-              (() if dist_sup is None else (dist_partials, grad_dist, dist))
+              (() if dist_sup is None else (dist_partials, grad_dist, dist)) + (() if opac is None else (opac_partials, grad_ws, opac))
         ctx.mark_non_differentiable(*aux)
         ctx.set_materialize_grads(False)                 # no zero-filled gradients for the auxiliary outputs (a fill launch each)
-        return out[0], weights_sum, depth_out, image_out, out, depth_partials, grad_depth, dist_partials, grad_dist, dist
+        return out[0], weights_sum, depth_out, image_out, out, depth_partials, grad_depth, dist_partials, grad_dist, dist, opac_partials, \
+            grad_ws, opac
 
     @staticmethod
     @custom_bwd(device_type="cuda")
     def backward(ctx, grad_loss, *_):
         if grad_loss is None:
-            return (None,) * 15
+            return (None,) * 16
         grad_sigmas, grad_rgbs = ctx.saved_tensors
         if not _is_unit_root_grad(grad_loss):              # a general upstream gradient: d(loss) scales every sample gradient
             gl = grad_loss.float()
@@ -452,7 +461,7 @@ class _composite_rays_train_blend_mse(Function):
             from ..backend import retarget_pending_loss
             retarget_pending_loss(grad_sigmas, scaled)     # a deferred loss value follows the tensor the head backward will receive
             grad_sigmas, grad_rgbs = scaled, grad_rgbs * gl
-        return (grad_sigmas, grad_rgbs) + (None,) * 13
+        return (grad_sigmas, grad_rgbs) + (None,) * 14
 
 
 def finish_depth_loss(loss, out=None):
@@ -489,9 +498,31 @@ def check_distort_weight(who, distort_weight):
     return w
 
 
+def finish_opacity_loss(loss, out=None):
+    """the opacity-entropy term alone, L_op = mean over all rays of h(weights_sum) without its weight, of a `loss` made by
+    composite_rays_train_blend_mse(opacity_weight=...): one lae_loss_finish launch over the step's entropy partial sums, off the
+    gradient path.  out: a float32 tensor of 2 elements to write to (both receive the value); -> out[1] as a 0-dim tensor"""
+    parts = getattr(loss, "opac_partials", None)
+    if parts is None:
+        raise RuntimeError("finish_opacity_loss: the loss was made without an opacity term")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=parts.device)
+    _backend.loss_finish(parts, parts.numel(), loss.opac_rays, None, out)
+    return out[1]
+
+
+def check_opacity_weight(who, opacity_weight):
+    """-> float(opacity_weight); ValueError unless it is finite and >= 0"""
+    w = float(opacity_weight)
+    if not (w >= 0.0) or w == float("inf"):
+        raise ValueError(f"{who}: opacity_weight must be finite and >= 0")
+    return w
+
+
 def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, target, bg_color=1, T_thresh=1e-4, scaler=None,
                                    defer_loss=None, depth=None, depth_inds=None, depth_weight=0.0, depth_grad=True,
-                                   distort_weight=None, distort_grad=True):
+                                   distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None,
+                                   opacity_grad=True):
     """-> (loss, weights_sum, depth, image): loss = MSE(image, target) times the loss scale of `scaler` (a FusedAdam, a
     1-element fp32 cuda tensor, or None); `loss.unscaled` holds the plain MSE.  Only `loss` carries a gradient.
     defer_loss (default: True when `scaler` is a FusedAdam): the VALUE of loss / loss.unscaled is NaN until the backward pass
@@ -510,7 +541,21 @@ def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, targ
     l_ray = (1/3) sum_k delta_k w_k^2 + sum_ij w_i w_j |t_i - t_j| (the O(n) form of the reference's loss.py eff_distloss, called
     with m = t and interval = deltas[:,0]: lengths in the march's own units, not divided by far - near, so the weight that suits a
     scene scales with 1 / its extent).  distort_grad=False: the value only, the sample gradients of the call without the term bit
-    for bit.  `loss.dist` [N] holds l_ray, `loss.grad_dist` [N] d loss / d l_ray, finish_distort_loss(loss) L_dist."""
+    for bit.  `loss.dist` [N] holds l_ray, `loss.grad_dist` [N] d loss / d l_ray, finish_distort_loss(loss) L_dist.
+    loss (default 'mse': today's call, bit for bit): the colour criterion, the mean over the 3 N elements of 'mse' (e^2), 'l1' (|e|),
+    'huber' (the reference's loss.py huber_loss, = torch's HuberLoss(huber_delta) / huber_delta) or 'mape' (|e| / (|target| + 1e-2),
+    loss.py mape_loss); `loss.unscaled` then holds that criterion in the MSE's place.
+    opacity_weight (default None: today's call, bit for bit): the opacity-entropy regularizer (torch-ngp's lambda_entropy) in the same
+    kernel.  loss becomes ... + opacity_weight * L_op, L_op = mean over all rays of h = -(o log2 o + (1 - o) log2(1 - o)) with
+    o = clamp(weights_sum, 1e-5, 1 - 1e-5); its gradient reaches a ray whose weights_sum lies inside the clamp (bounds included).
+    opacity_grad=False: the value only, the sample gradients of the call without the term bit for bit.  `loss.opac` [N] holds h,
+    `loss.grad_ws` [N] d loss / d weights_sum, finish_opacity_loss(loss) L_op."""
+    from ..backend import loss_kind
+    kind, param = loss_kind("composite_rays_train_blend_mse", loss, huber_delta)
+    crit = None
+    if kind != 0 or opacity_weight is not None:
+        crit = (kind, param, None if opacity_weight is None else
+                (check_opacity_weight("composite_rays_train_blend_mse", opacity_weight), not opacity_grad))
     dist_sup = None
     if distort_weight is not None:
         dist_sup = (check_distort_weight("composite_rays_train_blend_mse", distort_weight), not distort_grad)
@@ -528,10 +573,12 @@ def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, targ
             raise ValueError("composite_rays_train_blend_mse: depth_weight must be finite and >= 0")
         depth_sup = (_DepthPlane(depth.contiguous()), None if depth_inds is None else depth_inds.contiguous(), float(depth_weight),
                      not depth_grad)
-    loss, weights_sum, depth_o, image, both, depth_partials, grad_depth, dist_partials, grad_dist, dist = \
+    loss, weights_sum, depth_o, image, both, depth_partials, grad_depth, dist_partials, grad_dist, dist, opac_partials, grad_ws, opac = \
         _composite_rays_train_blend_mse.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale,
-                                              bool(defer_loss), depth_sup, dist_sup)
+                                              bool(defer_loss), depth_sup, dist_sup, crit)
     loss.unscaled = both[1]
+    if opac is not None:
+        loss.opac_partials, loss.grad_ws, loss.opac, loss.opac_rays = opac_partials, grad_ws, opac, rays.shape[0]
     if dist_sup is not None:
         loss.dist_partials, loss.grad_dist, loss.dist, loss.dist_rays = dist_partials, grad_dist, dist, rays.shape[0]
     if depth_sup is not None:
@@ -858,4 +905,80 @@ def composite_distort_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=Non
         qr = q[offset:offset + len(w)]
         Q_k = np.cumsum(qr * w)
         gs[offset:offset + len(w)] += d0 * res["grad_dist"][index] * (tp * qr - (two * dist[index] - Q_k))
+    return res
+
+
+# ---------------------------------------------------------------- numpy restatement of the fused step's criteria
+OPAC_LO, OPAC_HI = 1e-5, 1.0 - 1e-5          # the clamp of the opacity entropy; the kernel holds both as float32
+
+
+def colour_loss_numpy(e, target, loss="mse", huber_delta=0.1, dtype=None):
+    """the element loss v and dv = d v / d pred of the colour criteria (include/laenerf.h LAE_LOSS_*) for e = pred - target, in `dtype`
+    (default float64); huber_delta is taken at its float32 value, as the kernels receive it.  -> (v, dv), shaped like e"""
+    import numpy as np
+    dt = np.dtype(np.float64 if dtype is None else dtype).type
+    e, t = np.asarray(e).astype(dt), np.asarray(target).astype(dt)
+    r, sg = np.abs(e), np.sign(e)
+    if loss == "mse":
+        return e * e, dt(2) * e
+    if loss == "l1":
+        return r, sg
+    if loss == "huber":
+        d = dt(np.float32(huber_delta))
+        return np.where(r > d, r - dt(0.5) * d, (dt(0.5) / d * r) * r), np.where(r > d, sg, e / d)
+    if loss == "mape":
+        k = dt(1) / (np.abs(t) + dt(np.float32(1e-2)))
+        return r * k, sg * k
+    raise ValueError("colour_loss_numpy: loss must be 'mse', 'l1', 'huber' or 'mape'")
+
+
+def opacity_entropy_numpy(weights_sum, dtype=None):
+    """h = -(o log2 o + (1 - o) log2(1 - o)), o = clamp(weights_sum, 1e-5, 1 - 1e-5) (the bounds at their float32 values), and
+    dh = d h / d weights_sum = log2(1 - o) - log2 o inside the clamp (bounds included), 0 outside, in `dtype` -> (h, dh)"""
+    import numpy as np
+    dt = np.dtype(np.float64 if dtype is None else dtype).type
+    w = np.asarray(weights_sum).astype(dt)
+    lo, hi = dt(np.float32(OPAC_LO)), dt(np.float32(1) - np.float32(OPAC_LO))
+    o = np.minimum(np.maximum(w, lo), hi)
+    la, lb = np.log2(o), np.log2(dt(1) - o)
+    return -(o * la + (dt(1) - o) * lb), np.where((w >= lo) & (w <= hi), lb - la, dt(0))
+
+
+def composite_train_step_numpy(sigmas, rgbs, deltas, rays, target, T_thresh=1e-4, dtype=None, bg=None, z=None, nears=None, fars=None,
+                               depth_weight=0.0, distort_weight=0.0, scale=1.0, depth_grad=True, distort_grad=True, n_rays=None,
+                               loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True):
+    """lae_composite_rays_train_step_crit restated in `dtype` (default float64): the forward, the colour criterion `loss`, the depth
+    term (with z), the distortion term and the opacity entropy, then the backward with the criterion's gradients
+      grad_image = ((dv * (1 / (3 N))) * scale)  (mse: (e * (2 / (3 N))) * scale),   grad_ws = ((opacity_weight / N) * dh) * scale.
+    -> the dict of composite_distort_numpy (grad_sigmas, grad_rgbs, weights_sum, depth, image, dist, ...) plus image_out, grad_image,
+    grad_depth, grad_dist, grad_ws, opac [N], colour (= mean(v)), depth_mse, dist_mean, opac_mean (all N rays) and
+    loss = colour + depth_weight * depth_mse + distort_weight * dist_mean + opacity_weight * opac_mean."""
+    import numpy as np
+    dt = np.dtype(np.float64 if dtype is None else dtype).type
+    f = composite_distort_numpy(sigmas, rgbs, deltas, rays, T_thresh, dtype=dtype, bg=bg, n_rays=n_rays)
+    N = f["weights_sum"].shape[0]
+    one, sc = dt(1), dt(scale)
+    bgv = dt(0) if bg is None else np.broadcast_to(np.asarray(bg).astype(dt).reshape(-1, 3), (N, 3))
+    out = f["image"] + (one - f["weights_sum"])[:, None] * bgv
+    tgt = np.asarray(target).astype(dt).reshape(N, 3)
+    e = out - tgt
+    v, dv = colour_loss_numpy(e, tgt, loss, huber_delta, dtype)
+    grad_image = (e * (dt(2) / dt(3 * N))) * sc if loss == "mse" else (dv * (one / dt(3 * N))) * sc
+    res_d, grad_depth = np.zeros(N, dt), None
+    if z is not None:
+        zz, nr = np.asarray(z).astype(dt).reshape(N), np.asarray(nears).astype(dt).reshape(N)
+        sup = zz > 0 if fars is None else (zz > 0) & (nr < np.asarray(fars).astype(dt).reshape(N))
+        with np.errstate(over="ignore"):
+            res_d = np.where(sup, f["depth"] - (zz - nr), dt(0))
+        grad_depth = (res_d * (dt(2) * dt(depth_weight) / dt(N))) * sc if depth_grad else np.zeros(N, dt)
+    lam_x = dt(distort_weight)
+    grad_dist = np.full(N, (lam_x / dt(N)) * sc, dt) if distort_grad else np.zeros(N, dt)
+    h, dh = opacity_entropy_numpy(f["weights_sum"], dtype)
+    lam_o = dt(0 if opacity_weight is None else opacity_weight)
+    grad_ws = ((lam_o / dt(N)) * dh) * sc if opacity_grad else np.zeros(N, dt)
+    res = composite_distort_numpy(sigmas, rgbs, deltas, rays, T_thresh, dtype=dtype, bg=bg, grad_weights_sum=grad_ws, grad_image=grad_image,
+                                  grad_depth=grad_depth, grad_dist=grad_dist, n_rays=n_rays)
+    colour, dmse, omean = v.sum() / dt(3 * N), (res_d * res_d).sum() / dt(N), h.sum() / dt(N)
+    res.update(image_out=out, grad_image=grad_image, grad_depth=grad_depth, grad_ws=grad_ws, opac=h, colour=colour, depth_mse=dmse,
+               opac_mean=omean, loss=colour + dt(depth_weight) * dmse + lam_x * res["dist_mean"] + lam_o * omean)
     return res

@@ -343,19 +343,30 @@ class NeRFRenderer(nn.Module):
         return xyzs, dirs, deltas, rays, nears, fars
 
     def shade_train(self, marched, bg_color=1, T_thresh=1e-4, gt=None, scaler=None, depth=None, depth_inds=None, depth_weight=0.0,
-                    depth_grad=True, distort_weight=None, distort_grad=True):
+                    depth_grad=True, distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None,
+                    opacity_grad=True):
         """second half: network on the samples, compositing, background blend, depth normalisation (renderer.py:313-334).
         gt [N,3] (optional, MI355X-native): also evaluate the trainer's criterion MSE(image, gt) (scaled by `scaler`'s
         loss scale) inside the compositing op -> result["loss"]; call loss.backward() on it.
         depth / depth_inds / depth_weight / depth_grad (with gt and fused_post_ops only): the depth criterion of
         raymarching.composite_rays_train_blend_mse in the same kernel; depth=None leaves the call as it was.
         distort_weight / distort_grad (with gt and fused_post_ops only): the distortion regularizer of the same function, with or
-        without depth; distort_weight=None leaves the call as it was."""
+        without depth; distort_weight=None leaves the call as it was.
+        loss / huber_delta / opacity_weight / opacity_grad (with gt only): the colour criterion and the opacity-entropy term of the same
+        function; the defaults leave the call as it was.  Without fused_post_ops a non-default criterion is evaluated operator by
+        operator -- losses.colour_loss_scaled on the blended image, the entropy written with torch operators -- where the default
+        leaves the criterion to the caller, as before."""
         if depth is not None and not (self.fused_post_ops and gt is not None):
             raise RuntimeError("shade_train: depth supervision needs gt and fused_post_ops (it lives in the fused criterion kernel)")
         if distort_weight is not None and not (self.fused_post_ops and gt is not None):
             raise RuntimeError("shade_train: the distortion term needs gt and fused_post_ops (it lives in the fused criterion kernel)")
         dist_kw = {} if distort_weight is None else {"distort_weight": distort_weight, "distort_grad": distort_grad}
+        crit_on = loss != "mse" or opacity_weight is not None
+        if crit_on and gt is None:
+            raise RuntimeError("shade_train: a colour criterion or an opacity term needs gt")
+        kind = loss
+        if crit_on:
+            dist_kw.update(loss=kind, huber_delta=huber_delta, opacity_weight=opacity_weight, opacity_grad=opacity_grad)
         xyzs, dirs, deltas, rays, nears, fars = marched[:6]
         plan = marched[6] if len(marched) > 6 else None
         sigmas, rgbs = self.model(xyzs, dirs, plan=plan) if plan is not None else self.model(xyzs, dirs)
@@ -377,10 +388,31 @@ class NeRFRenderer(nn.Module):
             weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh)
             image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
             depth = torch.clamp(depth - nears, min=0) / (fars - nears)
+        if crit_on and not self.fused_post_ops:
+            loss = self._criterion_unfused(image, weights_sum, gt, scaler, kind, huber_delta, opacity_weight, opacity_grad)
         res = {"image": image, "depth": depth, "weights_sum": weights_sum, "nears": nears, "n_samples": xyzs.shape[0]}
         if loss is not None:
             res["loss"] = loss
         return res
+
+    @staticmethod
+    def _criterion_unfused(image, weights_sum, gt, scaler, loss, huber_delta, opacity_weight, opacity_grad):
+        """shade_train's criterion without fused_post_ops: the colour loss in one kernel, the entropy term operator by operator"""
+        from .losses import colour_loss_scaled
+        from .raymarching.raymarching import OPAC_LO, check_opacity_weight
+        out = colour_loss_scaled(image, gt, scaler, loss, huber_delta)
+        if opacity_weight is None:
+            return out
+        w = check_opacity_weight("shade_train", opacity_weight)
+        ws = weights_sum if opacity_grad else weights_sum.detach()
+        o = ws.float().clamp(OPAC_LO, 1 - OPAC_LO)
+        l_op = (-(o * torch.log2(o) + (1 - o) * torch.log2(1 - o))).mean()
+        scale = None
+        if scaler is not None:
+            scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
+        total = out + (w * l_op if scale is None else (w * l_op) * scale[0])
+        total.unscaled, total.opacity = out.unscaled + w * l_op.detach(), l_op.detach()
+        return total
 
     # ------------------------------------------------------------------ inference render (renderer.py:335-387)
     def _frame_loop_ok(self, rays_o):

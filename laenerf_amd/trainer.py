@@ -35,6 +35,12 @@ distort_weight adds the distortion regularizer of mip-NeRF 360, `distort_weight 
 (1/3) sum_k delta_k w_k^2 + sum_ij w_i w_j |t_i - t_j|` (the O(n) form of the reference's loss.py eff_distloss, which its CUDA-ray
 path never calls; lengths in the march's own units), inside the same kernel and the same captured groups, alone or together with
 depth_weight.  distort_grad=False computes the value only: parameters bit-equal to a run without the term.
+
+loss chooses the colour criterion of the same kernel -- 'mse', 'l1', 'huber' (the reference's loss.py huber_loss with huber_delta,
+torch-ngp's HuberLoss(beta=0.1) / Instant-NGP's NeRF preset) or 'mape' -- and opacity_weight adds the opacity-entropy regularizer
+`opacity_weight * mean over the batch's rays of -(o log2 o + (1 - o) log2(1 - o))`, o = clamp(weights_sum, 1e-5, 1 - 1e-5) (torch-ngp's
+lambda_entropy), alone or together with the depth and distortion terms, inside the same captured groups.  opacity_grad=False computes
+the value only.  With error_map='ema' the map holds the trained criterion's per-ray mean, the reference's `error = loss.detach()`.
 """
 import contextlib
 import copy
@@ -126,12 +132,16 @@ class Trainer:
     distort_weight: None (no distortion term; the step is the one without this argument, bit for bit) or the weight of the
     distortion regularizer (module docstring); distort_grad: whether its gradient reaches the densities.  With it losses() holds the
     total and distort_losses() the per-step term without its weight, finished like the depth term's.
+    loss: the colour criterion, 'mse' (the step without this argument, bit for bit), 'l1', 'huber' (with huber_delta) or 'mape'; the
+    error map follows it.  opacity_weight: None (no term; the step without this argument, bit for bit) or the weight of the
+    opacity-entropy regularizer (module docstring); opacity_grad: whether its gradient reaches the densities.  With it losses() holds
+    the total and opacity_losses() the per-step term without its weight, finished like the other two.
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
     def __init__(self, renderer, optimizer, data, iters, lr, num_rays=4096, seed=0, graph=True, capacity="bucket",
                  max_steps=1024, dt_gamma=0.0, error_map=None, ema_decay=None, epoch_len=None, depth_weight=None, depth_grad=True,
-                 distort_weight=None, distort_grad=True):
+                 distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
         if error_map not in (None, "ema", "fixed"):
@@ -157,6 +167,14 @@ class Trainer:
             if not renderer.fused_post_ops:
                 raise ValueError("Trainer: the distortion term needs the renderer's fused_post_ops")
         self.distort_weight, self.distort_grad = distort_weight, bool(distort_grad)
+        from .backend import loss_kind
+        loss_kind("Trainer", loss, huber_delta)
+        if opacity_weight is not None:
+            opacity_weight = raymarching.check_opacity_weight("Trainer", opacity_weight)
+            if not renderer.fused_post_ops:
+                raise ValueError("Trainer: the opacity term needs the renderer's fused_post_ops")
+        self.loss, self.huber_delta = loss, float(huber_delta)
+        self.opacity_weight, self.opacity_grad = opacity_weight, bool(opacity_grad)
         dev = renderer.density_grid.device
         data.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         data.aabb = renderer.aabb_train.to(dev, torch.float32).contiguous()      # the batch's near / far = the march's
@@ -170,6 +188,8 @@ class Trainer:
         self._depth_hist = []
         self.distort_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.distort_weight is not None else None
         self._distort_hist = []
+        self.opacity_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.opacity_weight is not None else None
+        self._opacity_hist = []
         self.global_step = 0
         self.started = False
         self.graphs = {}
@@ -214,6 +234,9 @@ class Trainer:
             if not torch.cuda.is_current_stream_capturing():
                 self._rows_seen = max(self._rows_seen, xyzs.shape[0])
             dist_kw = {} if self.distort_weight is None else {"distort_weight": self.distort_weight, "distort_grad": self.distort_grad}
+            if self.loss != "mse" or self.opacity_weight is not None:
+                dist_kw.update(loss=self.loss, huber_delta=self.huber_delta, opacity_weight=self.opacity_weight,
+                               opacity_grad=self.opacity_grad)
             if self.depth_weight is None:
                 res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt, **dist_kw)
             else:
@@ -221,12 +244,14 @@ class Trainer:
                                     depth=self.data.depths, depth_inds=b["inds"], depth_weight=self.depth_weight,
                                     depth_grad=self.depth_grad, **dist_kw)
         if self.error_map == "ema":
-            self.data.update_error_map(res["image"], b)
+            self.data.update_error_map(res["image"], b, loss=self.loss, huber_delta=self.huber_delta)
         loss = res["loss"]
         if self.depth_weight is not None:
             raymarching.finish_depth_loss(loss, out=self.depth_slots[k])
         if self.distort_weight is not None:
             raymarching.finish_distort_loss(loss, out=self.distort_slots[k])
+        if self.opacity_weight is not None:
+            raymarching.finish_opacity_loss(loss, out=self.opacity_slots[k])
         opt.backward(loss)
         opt.step()
         if self.ema is not None:
@@ -288,16 +313,19 @@ class Trainer:
                 self._depth_hist.append(self.depth_slots[pos:pos + n, 1].clone())
             if self.distort_slots is not None:
                 self._distort_hist.append(self.distort_slots[pos:pos + n, 1].clone())
+            if self.opacity_slots is not None:
+                self._opacity_hist.append(self.opacity_slots[pos:pos + n, 1].clone())
             done += n
             self.global_step += n
         return self
 
     # ------------------------------------------------------------------ results
     def losses(self):
-        """per-step losses (the unscaled loss of every step so far: the MSE, plus depth_weight * the depth term with depth
-        supervision, plus distort_weight * the distortion term with it) as a float32 numpy array.  After load_checkpoint /
-        load_state_dict: the steps since the resume (the history is not part of a checkpoint); likewise depth_losses() and
-        distort_losses()"""
+        """per-step losses (the unscaled loss of every step so far: the colour criterion's mean -- the MSE under loss='mse', else the
+        mean of the L1 / Huber / MAPE element loss --, plus depth_weight * the depth term with depth supervision, plus distort_weight *
+        the distortion term and opacity_weight * the opacity entropy with them) as a float32 numpy array.  After load_checkpoint /
+        load_state_dict: the steps since the resume (the history is not part of a checkpoint); likewise depth_losses(),
+        distort_losses() and opacity_losses()"""
         if not self._loss_hist:
             return np.zeros(0, np.float32)
         return torch.cat(self._loss_hist).cpu().numpy()
@@ -316,6 +344,13 @@ class Trainer:
             return np.zeros(0, np.float32)
         return torch.cat(self._distort_hist).cpu().numpy()
 
+    def opacity_losses(self):
+        """per-step opacity entropy L_op (the batch's mean of h(weights_sum)), without its weight, as a float32 numpy array (empty
+        without opacity_weight).  Each step finishes it with one lae_loss_finish node off the gradient path."""
+        if not self._opacity_hist:
+            return np.zeros(0, np.float32)
+        return torch.cat(self._opacity_hist).cpu().numpy()
+
     @property
     def steps_skipped(self):
         """optimizer steps the GradScaler skipped (non-finite gradients)"""
@@ -329,12 +364,21 @@ class Trainer:
                 "density_scale": r.density_scale}
         if model_only:
             return {"renderer": rend}
-        return {"iters": self.iters, "lr": list(self.lr), "num_rays": self.num_rays, "capacity": self.capacity, "max_steps": self.max_steps,
-                "dt_gamma": self.dt_gamma, "error_map": self.error_map, "ema_decay": None if self.ema is None else float(self.ema.decay),
-                "epoch_len": self.epoch_len, "depth_weight": self.depth_weight, "depth_grad": self.depth_grad,
-                "distort_weight": self.distort_weight, "distort_grad": self.distort_grad,
-                "data": {"n_img": d.n_img, "H": d.H, "W": d.W, "C": d.C, "mode": d.mode, "bg": d.bg, "color_space": d.color_space},
-                "renderer": rend}
+        cfg = {"iters": self.iters, "lr": list(self.lr), "num_rays": self.num_rays, "capacity": self.capacity, "max_steps": self.max_steps,
+               "dt_gamma": self.dt_gamma, "error_map": self.error_map, "ema_decay": None if self.ema is None else float(self.ema.decay),
+               "epoch_len": self.epoch_len, "depth_weight": self.depth_weight, "depth_grad": self.depth_grad,
+               "distort_weight": self.distort_weight, "distort_grad": self.distort_grad,
+               "data": {"n_img": d.n_img, "H": d.H, "W": d.W, "C": d.C, "mode": d.mode, "bg": d.bg, "color_space": d.color_space},
+               "renderer": rend}
+        # the criterion's keys only where they differ from the defaults: check_config counts a key missing on one side as a difference,
+        # and files written before these arguments existed -- and a default trainer's file -- stay as they were
+        if self.loss != "mse":
+            cfg["loss"] = self.loss
+            if self.loss == "huber":
+                cfg["huber_delta"] = self.huber_delta
+        if self.opacity_weight is not None:
+            cfg["opacity_weight"], cfg["opacity_grad"] = self.opacity_weight, self.opacity_grad
+        return cfg
 
     def state_dict(self, full=True):
         """everything save_checkpoint writes, on the host: the reference Trainer's dict (nerf/utils.py:1631-1655: epoch = global_step //
@@ -488,7 +532,7 @@ class Trainer:
             self.m_limit.fill_(self._m())
         self.graphs = {}
         self._pool = None
-        self._loss_hist, self._depth_hist, self._distort_hist = [], [], []
+        self._loss_hist, self._depth_hist, self._distort_hist, self._opacity_hist = [], [], [], []
         self.started = True
         return self
 

@@ -6,6 +6,7 @@ weights_sum; 8-bit like a real dataset.  A fresh student trains on them with the
 refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated on held-out views over white.
 
     python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed] [--ema] [--depth] [--distort W]
+                                [--loss mse|l1|huber|mape] [--huber-delta D] [--entropy W] [--outliers P]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
 ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR.
@@ -15,6 +16,12 @@ term ("depth": {...}) and the replay time of five windows for each.
 --distort W: every student of the run trains with the distortion regularizer (Trainer(distort_weight=W)); the line then carries the
 term's first and last 16-step mean ("distort": {...}).  Compare ms/step with a run without the option (and `--depth --distort W`
 with `--depth`) for the term's cost: the runs differ in nothing else, though their mean_count drifts apart as the geometry does.
+--loss / --huber-delta: every student of the run trains with that colour criterion (Trainer(loss=..., huber_delta=...)); final_loss is
+then that criterion's mean.  --entropy W: ... with the opacity-entropy regularizer (Trainer(opacity_weight=W)); the line then carries the
+term's first and last 16-step mean ("opacity": {...}).  Compare ms/step with a run without the options for their cost.
+--outliers P: the share P of the training pixels (never the held-out views) is overwritten with opaque uniformly random colours before
+training, the specular / exposure outliers of a real capture in their crudest form; the held-out PSNR under --loss mse and --loss huber
+is what the robust criterion buys.
 --save PATH: the first student's checkpoint is written after the run (Trainer.save_checkpoint; a `.pth` path or a directory);
 --resume PATH: the first student loads it before training and then trains --steps further steps (the same --steps as the saved run
 keeps the learning-rate horizon, which the load checks).  The line then carries "checkpoint": the file size in bytes and the save /
@@ -87,7 +94,8 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
 
 
 def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=True, capacity="bucket", seed=0, student_seed=0,
-                 error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True, distort_weight=None):
+                 error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True, distort_weight=None, loss="mse",
+                 huber_delta=0.1, opacity_weight=None):
     from laenerf_amd.data import ResidentImages
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.optim import FusedAdam
@@ -101,6 +109,8 @@ def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=Tr
     depth_kw = {} if depth_weight is None else {"depth_weight": depth_weight, "depth_grad": depth_grad}
     if distort_weight is not None:
         depth_kw["distort_weight"] = distort_weight
+    if loss != "mse" or opacity_weight is not None:
+        depth_kw.update(loss=loss, huber_delta=huber_delta, opacity_weight=opacity_weight)
     return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map,
                    ema_decay=ema_decay, **depth_kw)
 
@@ -147,6 +157,10 @@ def main():
     ap.add_argument("--depth-weight", type=float, default=1e-3)
     ap.add_argument("--depth-value-only", action="store_true", help="depth_grad=False: the reference's value-only depth term")
     ap.add_argument("--distort", type=float, default=None, metavar="W", help="Trainer(distort_weight=W) for every student of the run")
+    ap.add_argument("--loss", default="mse", choices=["mse", "l1", "huber", "mape"], help="Trainer(loss=...) for every student of the run")
+    ap.add_argument("--huber-delta", type=float, default=0.1, metavar="D")
+    ap.add_argument("--entropy", type=float, default=None, metavar="W", help="Trainer(opacity_weight=W) for every student of the run")
+    ap.add_argument("--outliers", type=float, default=0.0, metavar="P", help="share of training pixels overwritten with random colours")
     ap.add_argument("--save", default=None, metavar="PATH", help="write the first student's checkpoint after the run")
     ap.add_argument("--resume", default=None, metavar="PATH", help="load a checkpoint into the first student before training")
     args = ap.parse_args()
@@ -156,8 +170,16 @@ def main():
     build.build()
     images, poses, intr = teacher_views(dev, args.views, args.res, args.res)
     held = 4
+    if args.outliers > 0:
+        rng = np.random.default_rng(17)
+        hit = rng.random(images[held:].shape[:3]) < args.outliers
+        noise = rng.integers(0, 256, size=images[held:].shape, dtype=np.uint8)
+        noise[..., 3] = 255
+        images[held:][hit] = noise[hit]
+    crit_kw = dict(loss=args.loss, huber_delta=args.huber_delta, opacity_weight=args.entropy)
     tr = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
-                      capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, distort_weight=args.distort)
+                      capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, distort_weight=args.distort,
+                      **crit_kw)
     ckpt = {}
     if args.resume:
         torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -181,7 +203,7 @@ def main():
         planes = teacher_depths(dev, poses[held:], intr, args.res, args.res)
         td = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
                           capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, depths=planes,
-                          depth_weight=args.depth_weight, depth_grad=not args.depth_value_only, distort_weight=args.distort)
+                          depth_weight=args.depth_weight, depth_grad=not args.depth_value_only, distort_weight=args.distort, **crit_kw)
         d_all_in, d_steady = _timed_run(td, args.steps)
         d_psnr = td.evaluate(range(held), data=test, bg_color=1.0)
         _, d_group_ms = _replay_windows(td)
@@ -207,6 +229,10 @@ def main():
                       "padding_rows_frac": round(1 - tr._m() / tr._m_cap(), 4) if tr.r.mean_count > 0 else None},
         **({"distort": {"distort_weight": args.distort, "first_distort_loss": float(tr.distort_losses()[:16].mean()),
                         "final_distort_loss": float(tr.distort_losses()[-16:].mean())}} if args.distort is not None else {}),
+        **({"loss": args.loss, **({"huber_delta": args.huber_delta} if args.loss == "huber" else {})} if args.loss != "mse" else {}),
+        **({"opacity": {"opacity_weight": args.entropy, "first_opacity_loss": float(tr.opacity_losses()[:16].mean()),
+                        "final_opacity_loss": float(tr.opacity_losses()[-16:].mean())}} if args.entropy is not None else {}),
+        **({"outliers": args.outliers} if args.outliers > 0 else {}),
         **({"depth": depth} if depth is not None else {}), **({"checkpoint": ckpt} if ckpt else {}),
         "scene": f"{args.views - held} training + {held} held-out {args.res}x{args.res} RGBA uint8 views of a teacher network"}), flush=True)
 
