@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi22"
+#define LAE_ABI_TAG "abi23"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -400,6 +400,43 @@ LAE_API int lae_composite_rays_train_step_crit(const float* sigmas, const float*
                                        float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
                                        float* dist_partials, int loss_kind, float loss_param, float opac_lambda, int opac_value_only,
                                        float* opac, float* grad_ws, float* opac_partials, void* stream);
+/* lae_composite_rays_train_step_crit with a per-pixel weight on the colour residual and a second colour target with its own weight
+ * in the same launch -- the reference's train_step_npr (nerf/utils.py:523-526: loss = mean((w (pred - gt))^2) + style_weight_d *
+ * mean(((1 - w / 2) (gt_style - pred))^2) + the depth term), and mask- / confidence-weighted training in general.
+ *   w_src: a weight plane, fp16 or fp32 (w_dtype = LAE_IMG_F16 / LAE_IMG_F32), gathered at pix_inds[ray] (int64, the sampler's
+ *     inds = image * H * W + pixel) or at `ray` when pix_inds is NULL -- the rule of depth_inds.  NULL: no weights (w = 1).
+ *   t2_src: a second target plane [.., t2_channels] (3 or 4; t2_dtype as w_dtype), gathered the same way.  NULL: no second term, the
+ *     other t2 arguments are then not looked at.  With 4 channels it is blended over the ray's own background as the sampler blends
+ *     gt, three roundings, no contraction: t_c = s_c * s_a + bg_c * (1 - s_a); with 3, t_c = s_c.
+ * Per ray, after the forward and the blend (o = image_out[ray], gt = target[ray]), every operation one fp32 rounding:
+ *   u = 1 - 0.5 * w,   a_c = w * (o_c - gt_c),   v1 = fmaf(a2, a2, fmaf(a1, a1, a0 * a0)),
+ *   b_c = u * (t_c - o_c),   v2 = (b0 * b0 + b1 * b1) + b2 * b2,
+ *   loss = (1 / (3 N)) sum over the rays of (v1 + t2_lambda * v2) [+ the depth, distortion and entropy terms of _crit, unchanged]
+ *   grad_image_c = (((w * a_c) - t2_lambda * (u * b_c)) * (2 / (3 N))) * *scale     (no second target: ((w * a_c) * (2 / (3 N))) * *scale)
+ *   With a second target the two parts of grad_image cancel where the pixel lies between its targets (where the training converges):
+ *   there the expression is evaluated in double on the fp32 operands (w, o, gt, t, *scale) and rounded to fp32 once, so that
+ *   grad_image keeps the relative accuracy of the step without a second target (about 1e-7) instead of an unbounded relative error.
+ *   The loss values (v1, v2) stay fp32.
+ * The backward is that of _crit on this grad_image: nothing is added per sample.  A weight of 0 makes a_c and the first term's
+ * gradient exact zeros: the pixel's colour cannot matter.
+ * partials[b] receive v1 + t2_lambda * v2 (+ the other parts), so every finisher (n_elem = 3 N) yields the total loss; t2_partials
+ * [cdiv(N, 4)] receive sum(v2): lae_loss_finish(t2_partials, cdiv(N, 4), 3 N, NULL, out) gives mean(v2 / 3), the second term alone.
+ * With w_src == NULL and t2_src == NULL the call IS lae_composite_rays_train_step_crit (same kernels, same bits); with a plane of
+ * ones and no second target every output has those bits too (1 * x is exact).
+ * LAE_EINVAL: weights or a second target with loss_kind != LAE_LOSS_MSE (the reference has no weighted L1 / Huber / MAPE; out of scope),
+ * t2_lambda not finite and >= 0, t2_channels not 3 or 4, a dtype that is not LAE_IMG_F16 / LAE_IMG_F32. */
+LAE_API int lae_composite_rays_train_step_weighted(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                           uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
+                                           float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
+                                           const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
+                                           float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
+                                           float* partials, int defer_loss, const void* depth_src, int depth_dtype,
+                                           const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
+                                           float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
+                                           float* dist_partials, int loss_kind, float loss_param, float opac_lambda, int opac_value_only,
+                                           float* opac, float* grad_ws, float* opac_partials, const void* w_src, int w_dtype,
+                                           const void* t2_src, int t2_dtype, int t2_channels, const int64_t* pix_inds, float t2_lambda,
+                                           float* t2_partials, void* stream);
 
 /* raymarching.cu:929-936 */
 LAE_API int lae_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive,
@@ -823,6 +860,30 @@ LAE_API int lae_distill_compose(uint32_t R, const int32_t* img_idx, const int32_
                                 uint32_t n_img, uint32_t HW, uint32_t C, void* stream);
 LAE_API int lae_error_map_seed(uint32_t R, const int32_t* img_idx, const int32_t* pix, const float* w, const int32_t* view_img,
                                uint32_t V, uint32_t n_img, uint32_t H, uint32_t W, float* dense, float* error_map, void* stream);
+
+/* The data set of the Ref-NPR distillation (the reference's dataloader_nerf, editing/single_view_edit_dataset.py:447-519), built on
+ * the device over all views at once.  src_images [n_img, HW, C] (C = 3 or 4; LAE_IMG_U8 / _F16 / _F32) are the training images, read
+ * for their alpha only: a = src[.., 3] (uint8 as value / 255, correctly rounded), a = 1 for C == 3 (the reference reads the blue
+ * channel there, a bug that is not reproduced).  Outputs, dtype LAE_IMG_F16 / LAE_IMG_F32 (values are computed in fp32, every
+ * operation one rounding, and rounded to nearest even on the store): images [n_img, HW, 4], weights [n_img, HW], second
+ * [n_img, HW, 4]; depths [n_img, HW] is always fp32.
+ *
+ * lae_ref_distill_init: the dense pass, one thread per pixel: images = (0, 0, 0, a), weights = 1 - a, second = 0, depths = 0 -- what
+ *   a view skipped by the registration, or an image no view points at, keeps.
+ * lae_ref_distill_scatter: one thread per packed row, after the init.
+ *   registered rows (R_reg): images[reg_img, reg_pix, :3] = reg_rgb [R_reg, 3] (ref_targets),
+ *                            weights[reg_img, reg_pix] = max(reg_w, 0) + (1 - a)     (target_weights; :466-469)
+ *   extracted rows (R_ext):  second[ext_img, ext_pix] = (ext_rgb [R_ext, 3], a)      (the palette network's colour; :493-498)
+ *                            depths[ext_img, ext_pix] = ext_depth                    (:503-504)
+ *   A row whose image or pixel lies outside the planes is skipped.  Two rows of one kind that name the same pixel of one image leave
+ *   an unspecified one of the two values there (the packing asserts that there are none).
+ * LAE_EINVAL: C not 3 or 4, a dtype out of range. */
+LAE_API int lae_ref_distill_init(const void* src_images, int src_dtype, uint32_t n_img, uint32_t HW, uint32_t C, int dtype, void* images,
+                                 void* weights, void* second, float* depths, void* stream);
+LAE_API int lae_ref_distill_scatter(uint32_t R_reg, const int32_t* reg_img, const int32_t* reg_pix, const float* reg_rgb, const float* reg_w,
+                                    uint32_t R_ext, const int32_t* ext_img, const int32_t* ext_pix, const float* ext_rgb,
+                                    const float* ext_depth, const void* src_images, int src_dtype, uint32_t n_img, uint32_t HW, uint32_t C,
+                                    int dtype, void* images, void* weights, void* second, float* depths, void* stream);
 
 /* The point-wise losses of train_LAENeRF_step (nerf/utils.py:990-996; style_encoder.py:183-205) fused behind the
  * recomposition: loss = MSE(pred, target) + w_uniform * max_j sum_i w_hat[i,j] + w_non_uniform * sum_i (1 - max_j w_hat[i,j])

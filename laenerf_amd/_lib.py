@@ -44,6 +44,8 @@ SIGNATURES = {
     "lae_composite_rays_train_forward_blend_dist": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
     "lae_composite_rays_train_step_dist": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, f32, i32, vp, vp, vp, vp],
     "lae_composite_rays_train_step_crit": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, f32, i32, vp, vp, vp, i32, f32, f32, i32, vp, vp, vp, vp],
+    "lae_composite_rays_train_step_weighted": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, f32, i32, vp, vp, vp, i32, f32, f32, i32, vp, vp, vp,
+                                               vp, i32, vp, i32, i32, vp, f32, vp, vp],
     "lae_composite_rays_train_backward_blend_dist": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_loss_finish": [vp, u32, u32, vp, vp, vp],
     "lae_composite_rays_train_backward_blend": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp],
@@ -100,6 +102,8 @@ SIGNATURES = {
     "lae_recolor_compose": [vp, u32, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, i32, u32, i32, vp, vp, vp],
     "lae_distill_compose": [u32, vp, vp, vp, vp, vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, f32, i32, vp, i32, u32, u32, u32, vp],
     "lae_error_map_seed": [u32, vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp],
+    "lae_ref_distill_init": [vp, i32, u32, u32, u32, i32, vp, vp, vp, vp, vp],
+    "lae_ref_distill_scatter": [u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, i32, u32, u32, u32, i32, vp, vp, vp, vp, vp],
     "lae_marching_cubes_scratch_bytes": [u32, u32, u32],
     "lae_marching_cubes_count": [vp, u32, u32, u32, f32, vp, vp, vp],
     "lae_marching_cubes_emit": [vp, u32, u32, u32, f32, vp, vp, vp, vp],
@@ -180,7 +184,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi22"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi23"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

@@ -280,7 +280,7 @@ class _RayMarching:
     @staticmethod
     def composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears, fars, bg_rays, bg, rows_end, target, scale,
                                   weights_sum, depth, image, depth_out, image_out, grad_image, grad_sigmas, grad_rgbs, loss_out,
-                                  partials, defer_loss=False, depth_sup=None, dist_sup=None, crit=None):
+                                  partials, defer_loss=False, depth_sup=None, dist_sup=None, crit=None, weight_sup=None):
         """MI355X extension: compositing forward (+ blend) + MSE criterion + compositing backward in one launch.
         defer_loss: the loss VALUE (loss_out, NaN until then) is summed later -- by the fused head's backward, which takes it
         along in its reduction launch, or by flush_pending_loss() (laenerf_amd.optim.FusedAdam.backward / step call it).
@@ -292,7 +292,12 @@ class _RayMarching:
         weight * mean(l_ray).
         crit: None, or (loss_kind, loss_param, opac_sup) with opac_sup None or (weight, value_only, opac, grad_ws, opac_partials): the
         colour criterion LOSS_KINDS[...] and the opacity-entropy term of lae_composite_rays_train_step_crit in the same launch, with or
-        without depth_sup and dist_sup; the loss value then holds mean(v) of that criterion plus weight * mean(h)."""
+        without depth_sup and dist_sup; the loss value then holds mean(v) of that criterion plus weight * mean(h).
+        weight_sup: None, or (pixel_weights, second_target, pix_inds, second_weight, second_partials): the per-pixel weight plane
+        (fp16 / fp32, or None) and the second colour target (fp16 / fp32 [.., 3 or 4], or None) of
+        lae_composite_rays_train_step_weighted in the same launch, both gathered at pix_inds (int64 [N], or None: one entry per ray),
+        with or without the other terms; MSE only.  The loss value then holds mean((w e)^2) + second_weight * mean(((1 - w / 2)
+        (t - pred))^2) plus the other terms."""
         ts = (sigmas, rgbs, deltas, rays, nears, fars, bg_rays, rows_end, target, scale, weights_sum, depth, image, depth_out,
               image_out, grad_image, grad_sigmas, grad_rgbs, loss_out, partials)
         need_cuda(*ts); need_contig(*ts)
@@ -326,6 +331,35 @@ class _RayMarching:
             if any(x is None for x in xs) or dist.numel() < N or grad_dist.numel() < N or dist_partials.numel() < (N + 3) // 4:
                 raise RuntimeError("composite_rays_train_step: dist and grad_dist need N, dist_partials cdiv(N, 4) floats")
             xargs = (float(dist_weight), int(bool(dist_value_only)), ptr(dist), ptr(grad_dist), ptr(dist_partials))
+        wargs = None
+        if weight_sup is not None:
+            w_plane, t2_plane, pix_inds, t2_weight, t2_partials = weight_sup
+            ws_ = (w_plane, t2_plane, pix_inds, t2_partials)
+            need_cuda(*ws_); need_contig(*ws_)
+            if crit is not None and int(crit[0]) != 0:
+                raise RuntimeError("composite_rays_train_step: pixel weights and a second target need the MSE criterion")
+            if pix_inds is not None and (pix_inds.dtype != torch.int64 or pix_inds.numel() < N):
+                raise RuntimeError("composite_rays_train_step: pix_inds must be int64 with an entry per ray")
+            wa = (None, 0)
+            if w_plane is not None:
+                if w_plane.dtype not in _DEPTH_DTYPES:
+                    raise RuntimeError("composite_rays_train_step: the weight plane must be float16 or float32")
+                if pix_inds is None and w_plane.numel() < N:
+                    raise RuntimeError("composite_rays_train_step: without pix_inds the weights need a value per ray")
+                wa = (ptr(w_plane), _DEPTH_DTYPES[w_plane.dtype])
+            ta = (None, 0, 0)
+            if t2_plane is not None:
+                if t2_plane.dtype not in _DEPTH_DTYPES or t2_plane.dim() < 2 or t2_plane.shape[-1] not in (3, 4):
+                    raise RuntimeError("composite_rays_train_step: the second target must be float16 or float32 [.., 3 or 4]")
+                if pix_inds is None and t2_plane.numel() < N * t2_plane.shape[-1]:
+                    raise RuntimeError("composite_rays_train_step: without pix_inds the second target needs a row per ray")
+                _need_f32(t2_partials)
+                if t2_partials is None or t2_partials.numel() < (N + 3) // 4:
+                    raise RuntimeError("composite_rays_train_step: second_partials needs cdiv(N, 4) floats")
+                ta = (ptr(t2_plane), _DEPTH_DTYPES[t2_plane.dtype], int(t2_plane.shape[-1]))
+            wargs = wa + ta + (ptr(pix_inds), float(t2_weight), ptr(t2_partials))
+            if crit is None:
+                crit = (0, 0.0, None)
         if crit is not None:
             loss_kind, loss_param, opac_sup = crit
             oargs = (0.0, 0, None, None, None)            # ... and without the entropy term
@@ -336,8 +370,12 @@ class _RayMarching:
                 if any(x is None for x in os_) or opac.numel() < N or grad_ws.numel() < N or opac_partials.numel() < (N + 3) // 4:
                     raise RuntimeError("composite_rays_train_step: opac and grad_ws need N, opac_partials cdiv(N, 4) floats")
                 oargs = (float(opac_weight), int(bool(opac_value_only)), ptr(opac), ptr(grad_ws), ptr(opac_partials))
-            check(_lib.load().lae_composite_rays_train_step_crit(*args, *dargs, *xargs, int(loss_kind), float(loss_param), *oargs, stream()),
-                  "composite_rays_train_step_crit")
+            if wargs is not None:
+                check(_lib.load().lae_composite_rays_train_step_weighted(*args, *dargs, *xargs, int(loss_kind), float(loss_param), *oargs,
+                                                                         *wargs, stream()), "composite_rays_train_step_weighted")
+            else:
+                check(_lib.load().lae_composite_rays_train_step_crit(*args, *dargs, *xargs, int(loss_kind), float(loss_param), *oargs,
+                                                                     stream()), "composite_rays_train_step_crit")
         elif dist_sup is not None:
             check(_lib.load().lae_composite_rays_train_step_dist(*args, *dargs, *xargs, stream()), "composite_rays_train_step_dist")
         elif depth_sup is not None:

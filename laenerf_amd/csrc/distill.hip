@@ -6,6 +6,9 @@
 //   distill render, written into the row's training image where the edit weight exceeds the threshold.
 // lae_error_map_seed: LAENeRF's --use_error_maps seed: the dense edit-weight image of every view, bilinearly resized to 128 x 128
 //   (torch's align_corners=False rule, no antialiasing), + 0.15, clamped (include/laenerf.h states the rules).
+// lae_ref_distill_init / lae_ref_distill_scatter: the data set of the Ref-NPR distillation (the reference's dataloader_nerf,
+//   editing/single_view_edit_dataset.py:447-519: a per-view host loop of scatters and a host copy of five planes per view) over all
+//   views at once: a dense pass that writes the background rule of the four planes, then one thread per packed row.
 #include "lae_common.h"
 #include "palette_edit.h"
 
@@ -132,6 +135,63 @@ __global__ void k_seed_resize(const int32_t* __restrict__ view_img, uint32_t V, 
     error_map[(uint64_t)img * SEED_CELLS + cell] = lae::clampf(__fadd_rn(x, 0.15f), 0.0f, 1.0f);
 }
 
+// ---- Ref-NPR distillation data.  a = the training image's alpha (1 for 3-channel data)
+__device__ __forceinline__ float src_alpha(const void* src, int dtype, uint32_t C, uint64_t p) {
+    if (C != 4) return 1.0f;
+    const uint64_t i = 4 * p + 3;
+    if (dtype == LAE_IMG_U8) return __fdiv_rn((float)static_cast<const uint8_t*>(src)[i], 255.0f);
+    return dtype == LAE_IMG_F16 ? (float)static_cast<const half_t*>(src)[i] : static_cast<const float*>(src)[i];
+}
+
+struct RefPlanes { void* images; void* weights; void* second; float* depths; };
+
+// every pixel: images = (0, 0, 0, a), weights = 1 - a, second = 0, depths = 0
+template <typename T>
+__global__ void __launch_bounds__(DC_THREADS) k_ref_distill_init(const void* __restrict__ src, int src_dtype, uint32_t C, uint64_t n_pix,
+                                                                 RefPlanes o) {
+    const uint64_t p = (uint64_t)blockIdx.x * DC_THREADS + threadIdx.x;
+    if (p >= n_pix) return;
+    const float a = src_alpha(src, src_dtype, C, p);
+    const T z = from_f32<T>(0.0f);
+    T* im = static_cast<T*>(o.images) + 4 * p;
+    T* s2 = static_cast<T*>(o.second) + 4 * p;
+    im[0] = z; im[1] = z; im[2] = z; im[3] = from_f32<T>(a);
+    s2[0] = z; s2[1] = z; s2[2] = z; s2[3] = z;
+    static_cast<T*>(o.weights)[p] = from_f32<T>(__fsub_rn(1.0f, a));
+    o.depths[p] = 0.0f;
+}
+
+struct RefRows {
+    uint32_t R_reg; const int32_t* reg_img; const int32_t* reg_pix; const float* reg_rgb; const float* reg_w;
+    uint32_t R_ext; const int32_t* ext_img; const int32_t* ext_pix; const float* ext_rgb; const float* ext_depth;
+};
+
+// thread r < R_reg: a registered row -> images rgb = the registered colour, weights = max(w, 0) + (1 - a);
+// thread R_reg + r: an extracted row -> second = (the network's colour, a), depths = the row's depth.  The two kinds write different
+// planes; two rows of one kind on the same pixel are the caller's error (the last writer wins, unspecified).
+template <typename T>
+__global__ void __launch_bounds__(DC_THREADS) k_ref_distill_scatter(RefRows rw, const void* __restrict__ src, int src_dtype, uint32_t C,
+                                                                    uint32_t n_img, uint32_t HW, RefPlanes o) {
+    const uint32_t r = blockIdx.x * DC_THREADS + threadIdx.x;
+    if (r >= rw.R_reg + rw.R_ext) return;
+    const bool reg = r < rw.R_reg;
+    const uint32_t q = reg ? r : r - rw.R_reg;
+    const uint32_t img = (uint32_t)(reg ? rw.reg_img[q] : rw.ext_img[q]), pix = (uint32_t)(reg ? rw.reg_pix[q] : rw.ext_pix[q]);
+    if (img >= n_img || pix >= HW) return;
+    const uint64_t p = (uint64_t)img * HW + pix;
+    const float a = src_alpha(src, src_dtype, C, p);
+    if (reg) {
+        T* im = static_cast<T*>(o.images) + 4 * p;
+        for (int c = 0; c < 3; c++) im[c] = from_f32<T>(rw.reg_rgb[3 * (uint64_t)q + c]);
+        static_cast<T*>(o.weights)[p] = from_f32<T>(__fadd_rn(fmaxf(rw.reg_w[q], 0.0f), __fsub_rn(1.0f, a)));
+    } else {
+        T* s2 = static_cast<T*>(o.second) + 4 * p;
+        for (int c = 0; c < 3; c++) s2[c] = from_f32<T>(rw.ext_rgb[3 * (uint64_t)q + c]);
+        s2[3] = from_f32<T>(a);
+        o.depths[p] = rw.ext_depth[q];
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -172,6 +232,42 @@ int lae_error_map_seed(uint32_t R, const int32_t* img_idx, const int32_t* pix, c
     }
     k_seed_resize<<<lae::cdiv((uint64_t)V * SEED_CELLS, DC_THREADS), DC_THREADS, 0, s>>>(view_img, V, n_img, H, W, dense, error_map);
     return lae::check_launch("error_map_seed/resize");
+}
+
+int lae_ref_distill_init(const void* src_images, int src_dtype, uint32_t n_img, uint32_t HW, uint32_t C, int dtype, void* images,
+                         void* weights, void* second, float* depths, void* stream) {
+    if (n_img == 0 || HW == 0) return LAE_OK;
+    if ((C != 3 && C != 4) || (dtype != LAE_IMG_F16 && dtype != LAE_IMG_F32)) return LAE_EINVAL;
+    if (src_dtype != LAE_IMG_U8 && src_dtype != LAE_IMG_F16 && src_dtype != LAE_IMG_F32) return LAE_EINVAL;
+    if (!src_images || !images || !weights || !second || !depths) return LAE_ENULL;
+    const uint64_t n_pix = (uint64_t)n_img * HW;
+    if ((n_pix + DC_THREADS - 1) / DC_THREADS > 0x7fffffffull) return LAE_EINVAL;
+    const uint32_t nb = lae::cdiv(n_pix, DC_THREADS);
+    const RefPlanes o{images, weights, second, depths};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == LAE_IMG_F16) k_ref_distill_init<half_t><<<nb, DC_THREADS, 0, s>>>(src_images, src_dtype, C, n_pix, o);
+    else k_ref_distill_init<float><<<nb, DC_THREADS, 0, s>>>(src_images, src_dtype, C, n_pix, o);
+    return lae::check_launch("ref_distill_init");
+}
+
+int lae_ref_distill_scatter(uint32_t R_reg, const int32_t* reg_img, const int32_t* reg_pix, const float* reg_rgb, const float* reg_w,
+                            uint32_t R_ext, const int32_t* ext_img, const int32_t* ext_pix, const float* ext_rgb, const float* ext_depth,
+                            const void* src_images, int src_dtype, uint32_t n_img, uint32_t HW, uint32_t C, int dtype, void* images,
+                            void* weights, void* second, float* depths, void* stream) {
+    if ((uint64_t)R_reg + R_ext == 0) return LAE_OK;
+    if ((uint64_t)R_reg + R_ext > 0xffffffffull) return LAE_EINVAL;
+    if ((C != 3 && C != 4) || (dtype != LAE_IMG_F16 && dtype != LAE_IMG_F32) || n_img == 0 || HW == 0) return LAE_EINVAL;
+    if (src_dtype != LAE_IMG_U8 && src_dtype != LAE_IMG_F16 && src_dtype != LAE_IMG_F32) return LAE_EINVAL;
+    if (!src_images || !images || !weights || !second || !depths) return LAE_ENULL;
+    if (R_reg && (!reg_img || !reg_pix || !reg_rgb || !reg_w)) return LAE_ENULL;
+    if (R_ext && (!ext_img || !ext_pix || !ext_rgb || !ext_depth)) return LAE_ENULL;
+    const RefRows rw{R_reg, reg_img, reg_pix, reg_rgb, reg_w, R_ext, ext_img, ext_pix, ext_rgb, ext_depth};
+    const RefPlanes o{images, weights, second, depths};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t nb = lae::cdiv(R_reg + R_ext, (uint32_t)DC_THREADS);
+    if (dtype == LAE_IMG_F16) k_ref_distill_scatter<half_t><<<nb, DC_THREADS, 0, s>>>(rw, src_images, src_dtype, C, n_img, HW, o);
+    else k_ref_distill_scatter<float><<<nb, DC_THREADS, 0, s>>>(rw, src_images, src_dtype, C, n_img, HW, o);
+    return lae::check_launch("ref_distill_scatter");
 }
 
 }  // extern "C"

@@ -654,18 +654,38 @@ struct DistLoss { float lambda; int value_only; float* dist; float* grad_dist; f
 // additionally receive 3 * lambda * sum(h), CritLoss::partials sum(h).  The CRIT = false instantiations are the kernels they were.
 struct CritLoss { int kind; float delta; float lambda; int value_only; float* opac; float* grad_ws; float* partials; };
 
-template <bool DEPTH, bool DIST, bool CRIT = false>
+// WGT (with CRIT, LAE_LOSS_MSE only): a per-pixel weight w on the colour residual and a second colour target t with its own weight,
+// the reference's train_step_npr (nerf/utils.py:523-526).  Both are gathered at inds[index] (or index) BEFORE the forward scan -- two
+// wave-uniform requests whose latency the scan hides -- and enter the criterion after it, per ray, nothing per sample:
+//   u = 1 - 0.5 w,  a_c = w * (o_c - gt_c),  v1 = fmaf(a2, a2, fmaf(a1, a1, a0 * a0)),  b_c = u * (t_c - o_c),  v2 = (b0 b0 + b1 b1) + b2 b2
+//   sq = v1 + lambda * v2,   grad_image_c = (((w * a_c) - lambda * (u * b_c)) * (2 / (3 N))) * scale
+// (with a second target the bracket of grad_image is evaluated in double and rounded once: its two parts cancel, see below)
+// t is blended over the ray's own background when it has an alpha (rgb * a + bg * (1 - a), three roundings, the sampler's blend of gt).
+// With w == 1 and no second target the statements reduce to those above bit for bit (1 * x is exact).  partials[] receive sq,
+// WeightLoss::partials sum(v2) (lae_loss_finish with n_elem = 3 N gives the second term alone).  The WGT = false instantiations are
+// the kernels they were.
+struct WeightLoss { const void* w_src; int w_dtype; const void* t2_src; int t2_dtype; int t2_channels; const int64_t* inds; float lambda;
+                    float* partials; };
+__device__ __forceinline__ float load_plane(const void* src, int dtype, size_t i) {
+    return dtype == LAE_IMG_F16 ? __half2float(((const __half*)src)[i]) : ((const float*)src)[i];
+}
+
+template <bool DEPTH, bool DIST, bool CRIT = false, bool WGT = false>
 __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
     const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum,
     float* __restrict__ depth, float* __restrict__ image, Blend bl, StepLoss sl, const uint32_t* __restrict__ rows_end_p,
     float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, std::conditional_t<DEPTH, DepthLoss, NoArg> dl,
-    std::conditional_t<DIST, DistLoss, NoArg> xl, std::conditional_t<CRIT, CritLoss, NoArg> cl) {
+    std::conditional_t<DIST, DistLoss, NoArg> xl, std::conditional_t<CRIT, CritLoss, NoArg> cl,
+    std::conditional_t<WGT, WeightLoss, NoArg> wl) {
+    static_assert(CRIT || !WGT, "the weighted flavours are built on the CRIT ones");
     __shared__ float s_sq[COMP_WAVES];
     [[maybe_unused]] __shared__ float s_dq[COMP_WAVES];
     [[maybe_unused]] __shared__ float s_xq[COMP_WAVES];
     [[maybe_unused]] __shared__ float s_oq[COMP_WAVES];
+    [[maybe_unused]] __shared__ float s_tq[COMP_WAVES];
     [[maybe_unused]] float oq = 0.0f, gws_in = 0.0f;                        // CRIT: the ray's entropy h and its grad_ws
+    [[maybe_unused]] float pw = 1.0f, t2[4] = {0.0f, 0.0f, 0.0f, 1.0f}, tq = 0.0f;   // WGT: the weight, the second target (alpha 1 without one), v2
     [[maybe_unused]] DepthState<DEPTH> ds;
     [[maybe_unused]] DistState<DIST> xs;
     [[maybe_unused]] DistAcc<DIST> xa;
@@ -679,6 +699,16 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
         zero_tail_rows(rows_end, M, n, N, lane, grad_rgbs, 3);
         const RayHead h = load_ray_head(rays, n, M);
         const uint32_t index = h.index;
+        if constexpr (WGT) {                                                    // requested here, used after the forward scan
+            const size_t pi = wl.inds ? (size_t)wl.inds[index] : (size_t)index;
+            if (wl.w_src) pw = load_plane(wl.w_src, wl.w_dtype, pi);
+            if (wl.t2_src) {
+                const size_t ti = (size_t)wl.t2_channels * pi;
+                t2[0] = load_plane(wl.t2_src, wl.t2_dtype, ti); t2[1] = load_plane(wl.t2_src, wl.t2_dtype, ti + 1);
+                t2[2] = load_plane(wl.t2_src, wl.t2_dtype, ti + 2);
+                if (wl.t2_channels == 4) t2[3] = load_plane(wl.t2_src, wl.t2_dtype, ti + 3);
+            }
+        }
         // ---- forward.  The next pass of 64 samples is requested before the current one is scanned: the kernel's time is that of
         // its longest rays (several passes, forward and backward), one memory latency per pass otherwise
         FwdAcc a{0.f, 0.f, 0.f, 0.f, 0.f};
@@ -701,6 +731,32 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
                     e2 = o[2] - sl.target[3 * (size_t)index + 2];
         sq = fmaf(e2, e2, fmaf(e1, e1, e0 * e0));
         float g0 = (e0 * gk) * s, g1 = (e1 * gk) * s, g2 = (e2 * gk) * s;
+        if constexpr (WGT) {                                                    // LAE_LOSS_MSE only (checked on the host)
+            const float a0 = pw * e0, a1 = pw * e1, a2 = pw * e2;
+            sq = fmaf(a2, a2, fmaf(a1, a1, a0 * a0));
+            if (wl.t2_src) {                                                    // uniform over the launch
+                const float u = 1.0f - 0.5f * pw;
+                float tc[3] = {t2[0], t2[1], t2[2]};
+                if (wl.t2_channels == 4) {
+                    const float rest = __fsub_rn(1.0f, t2[3]);
+                    for (int c = 0; c < 3; c++) tc[c] = __fadd_rn(__fmul_rn(t2[c], t2[3]), __fmul_rn(bg[c], rest));
+                }
+                const float b0 = u * (tc[0] - o[0]), b1 = u * (tc[1] - o[1]), b2 = u * (tc[2] - o[2]);
+                tq = (b0 * b0 + b1 * b1) + b2 * b2;
+                sq = sq + wl.lambda * tq;
+                // grad_image = (((w * a) - lambda * (u * b)) * (2 / (3 N))) * scale.  The two parts cancel where the pixel lies between its
+                // two targets -- where the training converges --, and rounded to fp32 one by one they would leave the difference with an
+                // unbounded relative error.  Three values per ray: the bracket is evaluated in double on the fp32 operands (w, o, gt, t,
+                // scale) and rounded once, so grad_image keeps the relative bound of the step without a second target everywhere
+                const double wd = pw, ud = 1.0 - 0.5 * wd, ld = wl.lambda, kd = (2.0 / (double)(3u * N)) * (double)s;
+                const float* gt = sl.target + 3 * (size_t)index;
+                g0 = (float)(((wd * (wd * ((double)o[0] - (double)gt[0]))) - ld * (ud * (ud * ((double)tc[0] - (double)o[0])))) * kd);
+                g1 = (float)(((wd * (wd * ((double)o[1] - (double)gt[1]))) - ld * (ud * (ud * ((double)tc[1] - (double)o[1])))) * kd);
+                g2 = (float)(((wd * (wd * ((double)o[2] - (double)gt[2]))) - ld * (ud * (ud * ((double)tc[2] - (double)o[2])))) * kd);
+            } else {
+                g0 = ((pw * a0) * gk) * s; g1 = ((pw * a1) * gk) * s; g2 = ((pw * a2) * gk) * s;
+            }
+        }
         if constexpr (CRIT) {
             if (cl.kind != LAE_LOSS_MSE) {                                  // uniform over the launch
                 const float g1n = 1.0f / (float)(3u * N);
@@ -772,6 +828,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
     if constexpr (DEPTH) { if (lane == 0) s_dq[wv] = ds.dq; }
     if constexpr (DIST) { if (lane == 0) s_xq[wv] = xa.l; }
     if constexpr (CRIT) { if (lane == 0) s_oq[wv] = oq; }
+    if constexpr (WGT) { if (lane == 0) s_tq[wv] = tq; }
     __syncthreads();
     if (threadIdx.x == 0) {
         float t = 0.0f;
@@ -796,6 +853,14 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
 #pragma unroll
                 for (int w = 0; w < COMP_WAVES; w++) u += s_oq[w];
                 cl.partials[blockIdx.x] = u;
+            }
+        }
+        if constexpr (WGT) {
+            if (wl.t2_src) {
+                float u = 0.0f;
+#pragma unroll
+                for (int w = 0; w < COMP_WAVES; w++) u += s_tq[w];
+                wl.partials[blockIdx.x] = u;
             }
         }
         // deferred loss value (lae_composite_rays_train_step with poison_loss): whoever reads it before the finishing
@@ -933,14 +998,25 @@ __global__ __launch_bounds__(COMPACT_BLOCK) void k_compact_scatter(const int32_t
 }
 
 // ---------------------------------------------------------------- host side of K7 / K8: one body per pair of C entries
-// lae_composite_rays_train_step[_depth | _dist | _crit]: the depth-, dist- and crit-only arguments are checked first, before the N == 0 return
-template <bool DEPTH, bool DIST = false, bool CRIT = false>
+// lae_composite_rays_train_step[_depth | _dist | _crit | _weighted]: the depth-, dist-, crit- and weight-only arguments are checked first,
+// before the N == 0 return
+template <bool DEPTH, bool DIST = false, bool CRIT = false, bool WGT = false>
 int composite_train_step_impl(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
                                      float T_thresh, const Blend& bl, const uint32_t* rows_end, const StepLoss& sl, float* weights_sum,
                                      float* depth, float* image, float* grad_sigmas, float* grad_rgbs, float* loss_out, int defer_loss,
                                      const std::conditional_t<DEPTH, DepthLoss, NoArg>& dl, const char* what, void* stream,
                                      const std::conditional_t<DIST, DistLoss, NoArg>& xl = {},
-                                     const std::conditional_t<CRIT, CritLoss, NoArg>& cl = {}) {
+                                     const std::conditional_t<CRIT, CritLoss, NoArg>& cl = {},
+                                     const std::conditional_t<WGT, WeightLoss, NoArg>& wl = {}) {
+    if constexpr (WGT) {
+        if (cl.kind != LAE_LOSS_MSE) return LAE_EINVAL;                     // the reference has no weighted L1 / Huber / MAPE
+        if (wl.w_src && wl.w_dtype != LAE_IMG_F16 && wl.w_dtype != LAE_IMG_F32) return LAE_EINVAL;
+        if (wl.t2_src) {
+            if (wl.t2_dtype != LAE_IMG_F16 && wl.t2_dtype != LAE_IMG_F32) return LAE_EINVAL;
+            if (wl.t2_channels != 3 && wl.t2_channels != 4) return LAE_EINVAL;
+            if (!(wl.lambda >= 0.0f) || !(wl.lambda <= 3.0e38f)) return LAE_EINVAL;
+        }
+    }
     if constexpr (CRIT) {
         if (!lae::colour_loss_kind_ok(cl.kind, cl.delta)) return LAE_EINVAL;
         if (cl.opac && (!(cl.lambda >= 0.0f) || !(cl.lambda <= 3.0e38f))) return LAE_EINVAL;
@@ -965,11 +1041,14 @@ int composite_train_step_impl(const float* sigmas, const float* rgbs, const floa
     if constexpr (CRIT) {
         if (cl.opac && (!cl.grad_ws || !cl.partials)) return LAE_ENULL;
     }
+    if constexpr (WGT) {
+        if (wl.t2_src && !wl.partials) return LAE_ENULL;                    // wl.inds may be NULL (the planes hold one value per ray)
+    }
     if (M > 0 && (!sigmas || !rgbs || !deltas || !grad_sigmas || !grad_rgbs)) return LAE_ENULL;
     const uint32_t nb = lae::cdiv(N, COMP_WAVES);
-    k_composite_train_step<DEPTH, DIST, CRIT><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum,
-                                                                                    depth, image, bl, sl, rows_end, grad_sigmas, grad_rgbs, dl,
-                                                                                    xl, cl);
+    k_composite_train_step<DEPTH, DIST, CRIT, WGT><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh,
+                                                                                         weights_sum, depth, image, bl, sl, rows_end, grad_sigmas,
+                                                                                         grad_rgbs, dl, xl, cl, wl);
     // defer_loss: the one-block sum of the partials (5.5 us + a kernel boundary on the step's critical path for a number that
     // feeds nothing on the device) is left to lae_loss_finish or to a later launch that takes it along
     // (lae_nerf_head_backward); loss_out holds NaN until then
@@ -1211,6 +1290,43 @@ int lae_composite_rays_train_step_crit(const float* sigmas, const float* rgbs, c
         return composite_train_step_impl<decltype(with_depth)::value, decltype(with_dist)::value, true>(
             sigmas, rgbs, deltas, rays, M, N, T_thresh, bl, rows_end, sl, weights_sum, depth, image, grad_sigmas, grad_rgbs, loss_out,
             defer_loss, dla, what, stream, xla, cl);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (!depth_src) return dist ? run(no, yes, NoArg{}, xl) : run(no, no, NoArg{}, NoArg{});
+    return dist ? run(yes, yes, dl, xl) : run(yes, no, dl, NoArg{});
+}
+
+int lae_composite_rays_train_step_weighted(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                           uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
+                                           float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
+                                           const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
+                                           float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
+                                           float* partials, int defer_loss, const void* depth_src, int depth_dtype,
+                                           const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
+                                           float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
+                                           float* dist_partials, int loss_kind, float loss_param, float opac_lambda, int opac_value_only,
+                                           float* opac, float* grad_ws, float* opac_partials, const void* w_src, int w_dtype,
+                                           const void* t2_src, int t2_dtype, int t2_channels, const int64_t* pix_inds, float t2_lambda,
+                                           float* t2_partials, void* stream) {
+    if (!w_src && !t2_src)                                // neither: the call, the instantiations and the bits of _crit
+        return lae_composite_rays_train_step_crit(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears, fars, bg_rays, bg_r, bg_g, bg_b, rows_end,
+                                                  target, scale, weights_sum, depth, image, depth_out, image_out, grad_image, grad_sigmas,
+                                                  grad_rgbs, loss_out, partials, defer_loss, depth_src, depth_dtype, depth_inds, lambda,
+                                                  depth_value_only, grad_depth, depth_partials, dist_lambda, dist_value_only, dist, grad_dist,
+                                                  dist_partials, loss_kind, loss_param, opac_lambda, opac_value_only, opac, grad_ws,
+                                                  opac_partials, stream);
+    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
+    const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
+    const DistLoss xl{dist_lambda, dist_value_only != 0, dist, grad_dist, dist_partials};
+    const DepthLoss dl{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials};
+    const CritLoss cl{loss_kind, loss_param, opac_lambda, opac_value_only != 0, opac, grad_ws, opac_partials};
+    const WeightLoss wl{w_src, w_dtype, t2_src, t2_dtype, t2_channels, pix_inds, t2_lambda, t2_partials};
+    const char* what = "composite_rays_train_step_weighted";
+    auto run = [&](auto with_depth, auto with_dist, const auto& dla, const auto& xla) {
+        return composite_train_step_impl<decltype(with_depth)::value, decltype(with_dist)::value, true, true>(
+            sigmas, rgbs, deltas, rays, M, N, T_thresh, bl, rows_end, sl, weights_sum, depth, image, grad_sigmas, grad_rgbs, loss_out,
+            defer_loss, dla, what, stream, xla, cl, wl);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};

@@ -196,10 +196,15 @@ class ResidentImages:
     C = 3); default by C.  color_space 'linear' converts the colour to linear before the blend (nerf/utils.py:564).
     depths (optional, or set_depths): a per-pixel depth plane [n, H, W], fp16 or fp32, resident on the device: the distance
     along the pixel's ray from its origin, zero = no supervision (the reference's `d_` planes, nerf/gui.py:406, 508-511).
-    sample() does not read it: the Trainer's compositing kernel gathers it by the batch's `inds`."""
+    sample() does not read it: the Trainer's compositing kernel gathers it by the batch's `inds`.
+    pixel_weights (optional, or set_pixel_weights): a per-pixel weight plane [n, H, W], fp16 or fp32, on the images' device: the weight
+    of the pixel's colour residual under Trainer(pixel_weights=True) -- a mask (0 = the pixel's colour cannot matter), a confidence
+    map, the Ref-NPR distillation's target weights.  second_target (optional, or set_second_target): a second colour target
+    [n, H, W, 3 or 4], fp16 or fp32, for Trainer(second_weight=...); with 4 channels it is blended over the batch's background like
+    the images.  sample() reads neither: the compositing kernel gathers both by the batch's `inds`."""
 
     def __init__(self, images, poses, intrinsics, bound=1.0, min_near=0.2, mode="image", bg=None, color_space="srgb", seed=0,
-                 device=None, error_map=False, depths=None):
+                 device=None, error_map=False, depths=None, pixel_weights=None, second_target=None):
         device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         # (device="cpu" holds the arrays on the host -- loaders and tests without a GPU; sample() needs the GPU)
         images = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))
@@ -231,6 +236,35 @@ class ResidentImages:
         self.depths = None
         if depths is not None:
             self.set_depths(depths)
+        self.pixel_weights = self.second_target = None
+        if pixel_weights is not None:
+            self.set_pixel_weights(pixel_weights)
+        if second_target is not None:
+            self.set_second_target(second_target)
+
+    def _float_plane(self, name, plane, shapes):
+        """a plane as set_depths stores it: fp16 / fp32 kept, other float dtypes as fp32, integers refused, on the images' device"""
+        plane = plane if torch.is_tensor(plane) else torch.from_numpy(np.ascontiguousarray(plane))
+        if tuple(plane.shape) not in shapes:
+            raise ValueError(f"ResidentImages: {name} must be " + " or ".join(str(list(s)) for s in shapes))
+        if not plane.dtype.is_floating_point:
+            raise ValueError(f"ResidentImages: {name} must be a floating-point plane")
+        if plane.dtype not in (torch.float16, torch.float32):
+            plane = plane.to(torch.float32)
+        return plane.to(self.images.device).contiguous()
+
+    def set_pixel_weights(self, plane):
+        """set .pixel_weights: the weight plane [n_img, H, W] (fp16 / fp32 tensor or array; other float arrays are stored as fp32, uint8
+        is refused), copied to the images' device; None removes it"""
+        self.pixel_weights = None if plane is None else self._float_plane("pixel_weights", plane, [(self.n_img, self.H, self.W)])
+        return self.pixel_weights
+
+    def set_second_target(self, images):
+        """set .second_target: the second colour target [n_img, H, W, 3 or 4] (fp16 / fp32 tensor or array; other float arrays are
+        stored as fp32, uint8 is refused), copied to the images' device; None removes it"""
+        self.second_target = None if images is None else self._float_plane(
+            "second_target", images, [(self.n_img, self.H, self.W, 3), (self.n_img, self.H, self.W, 4)])
+        return self.second_target
 
     def set_depths(self, plane):
         """set .depths: the depth plane [n_img, H, W] (fp16 / fp32 tensor or array; other float arrays are stored as fp32), copied

@@ -13,3 +13,4 @@ from .ray_registration import (RefCloud, extract_ref_cloud, extract_ref_template
 from .semantic_encoder import SemanticEncoder, build_ref_supervision, load_vgg16_features, vgg16_features  # noqa: F401
 from .ref_stage import (RefEditSet, RefStyleTrainer, pack_ref_arrays, ref_phase, ref_stage_numpy, ref_terms,  # noqa: F401
                         reference_ref_step, reference_ref_terms)
+from .ref_distill import build_ref_distill_data, distill_ref_npr, pack_ref_rows, ref_distill_numpy  # noqa: F401

@@ -21,7 +21,7 @@ of an empty tensor, NaN); the crop is resized and then normalized (the reference
 weights sum to one, so the two differ by roundings); the template term keeps the relation z and one shared style_feat instead of
 the gathered features.  Refused with NotImplementedError: style_weight > 0 (the guided Gram loss), smooth_trans_weight > 0 (the
 reference passes cut_smooth=None there), intensity_weight, and cos_loss_factor / color_patch_loss > 0 without the supervision.
-Not here: `train_step_npr` (the NeRF distillation that follows).
+The NeRF distillation that follows (`train_step_npr`) is editing/ref_distill.py.
 """
 import numpy as np
 import torch

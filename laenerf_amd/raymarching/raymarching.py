@@ -16,7 +16,7 @@ __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", 
            "composite_rays_train", "march_rays", "march_rays_distill", "composite_rays", "composite_rays_distill",
            "compact_rays_alive", "render_frame", "composite_rays_train_blend", "composite_rays_train_blend_mse",
            "composite_rays_train_blend_depth", "finish_depth_loss", "composite_depth_numpy", "composite_rays_train_blend_distort",
-           "finish_distort_loss", "composite_distort_numpy", "density_grid_positions",
+           "finish_distort_loss", "finish_second_loss", "composite_distort_numpy", "density_grid_positions",
            "density_grid_partial_positions", "density_grid_update", "mark_untrained_grid"]
 
 
@@ -404,12 +404,15 @@ class _composite_rays_train_blend_mse(Function):
     l_ray per ray) are None without it.
     crit = (loss_kind, loss_param, None or (opacity_weight, value_only)) chooses the colour criterion and adds the opacity-entropy term
     (`lae_composite_rays_train_step_crit`, with or without the other two); the last three outputs (the entropy's partial sums,
-    d loss / d weights_sum, the entropy per ray) are None without the term.  crit=None is the call as it was."""
+    d loss / d weights_sum, the entropy per ray) are None without the term.  crit=None is the call as it was.
+    weight_sup = (_DepthPlane or None, _DepthPlane or None, pix_inds, second_weight) adds the per-pixel weights and the second colour
+    target (`lae_composite_rays_train_step_weighted`, MSE only); the last output (the second term's partial sums) is None without a
+    second target.  weight_sup=None is the call as it was."""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale, defer_loss=False,
-                depth_sup=None, dist_sup=None, crit=None):
+                depth_sup=None, dist_sup=None, crit=None, weight_sup=None):
         sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
         M, N = sigmas.shape[0], rays.shape[0]
         dev = sigmas.device
@@ -437,23 +440,31 @@ class _composite_rays_train_blend_mse(Function):
             opac, grad_ws = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
             opac_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
             crit = (crit[0], crit[1], crit[2] + (opac, grad_ws, opac_partials))
+        second_partials = None
+        if weight_sup is not None:
+            w_plane, t2_plane, pix_inds, second_weight = weight_sup
+            if t2_plane is not None:
+                second_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
+            weight_sup = (None if w_plane is None else w_plane.t, None if t2_plane is None else t2_plane.t, pix_inds, second_weight,
+                          second_partials)
         _backend.composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(), fars.contiguous(), bg_rays,
                                            bg, rows_end, target, scale, weights_sum, depth, image, depth_out, image_out, grad_image,
                                            grad_sigmas, grad_rgbs, out, partials, defer_loss=defer_loss, depth_sup=depth_sup,
-                                           dist_sup=dist_sup, crit=crit)
+                                           dist_sup=dist_sup, crit=crit, weight_sup=weight_sup)
         ctx.save_for_backward(grad_sigmas, grad_rgbs)
         aux = (weights_sum, depth_out, image_out, out) + (() if depth_sup is None else (depth_partials, grad_depth)) + \
-              (() if dist_sup is None else (dist_partials, grad_dist, dist)) + (() if opac is None else (opac_partials, grad_ws, opac))
+              (() if dist_sup is None else (dist_partials, grad_dist, dist)) + (() if opac is None else (opac_partials, grad_ws, opac)) + \
+              (() if second_partials is None else (second_partials,))
         ctx.mark_non_differentiable(*aux)
         ctx.set_materialize_grads(False)                 # no zero-filled gradients for the auxiliary outputs (a fill launch each)
         return out[0], weights_sum, depth_out, image_out, out, depth_partials, grad_depth, dist_partials, grad_dist, dist, opac_partials, \
-            grad_ws, opac
+            grad_ws, opac, second_partials
 
     @staticmethod
     @custom_bwd(device_type="cuda")
     def backward(ctx, grad_loss, *_):
         if grad_loss is None:
-            return (None,) * 16
+            return (None,) * 17
         grad_sigmas, grad_rgbs = ctx.saved_tensors
         if not _is_unit_root_grad(grad_loss):              # a general upstream gradient: d(loss) scales every sample gradient
             gl = grad_loss.float()
@@ -461,7 +472,7 @@ class _composite_rays_train_blend_mse(Function):
             from ..backend import retarget_pending_loss
             retarget_pending_loss(grad_sigmas, scaled)     # a deferred loss value follows the tensor the head backward will receive
             grad_sigmas, grad_rgbs = scaled, grad_rgbs * gl
-        return (grad_sigmas, grad_rgbs) + (None,) * 14
+        return (grad_sigmas, grad_rgbs) + (None,) * 15
 
 
 def finish_depth_loss(loss, out=None):
@@ -511,6 +522,27 @@ def finish_opacity_loss(loss, out=None):
     return out[1]
 
 
+def finish_second_loss(loss, out=None):
+    """the second colour term alone, mean over the 3 N elements of ((1 - w / 2) (second_target - pred))^2 without its weight, of a
+    `loss` made by composite_rays_train_blend_mse(second_target=...): one lae_loss_finish launch over the step's partial sums of the
+    term, off the gradient path.  out: a float32 tensor of 2 elements to write to (both receive the value); -> out[1] as a 0-dim tensor"""
+    parts = getattr(loss, "second_partials", None)
+    if parts is None:
+        raise RuntimeError("finish_second_loss: the loss was made without a second target")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=parts.device)
+    _backend.loss_finish(parts, parts.numel(), 3 * loss.second_rays, None, out)
+    return out[1]
+
+
+def check_second_weight(who, second_weight):
+    """-> float(second_weight); ValueError unless it is finite and >= 0"""
+    w = float(second_weight)
+    if not (w >= 0.0) or w == float("inf"):
+        raise ValueError(f"{who}: second_weight must be finite and >= 0")
+    return w
+
+
 def check_opacity_weight(who, opacity_weight):
     """-> float(opacity_weight); ValueError unless it is finite and >= 0"""
     w = float(opacity_weight)
@@ -522,7 +554,7 @@ def check_opacity_weight(who, opacity_weight):
 def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, target, bg_color=1, T_thresh=1e-4, scaler=None,
                                    defer_loss=None, depth=None, depth_inds=None, depth_weight=0.0, depth_grad=True,
                                    distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None,
-                                   opacity_grad=True):
+                                   opacity_grad=True, pixel_weights=None, pixel_inds=None, second_target=None, second_weight=0.0):
     """-> (loss, weights_sum, depth, image): loss = MSE(image, target) times the loss scale of `scaler` (a FusedAdam, a
     1-element fp32 cuda tensor, or None); `loss.unscaled` holds the plain MSE.  Only `loss` carries a gradient.
     defer_loss (default: True when `scaler` is a FusedAdam): the VALUE of loss / loss.unscaled is NaN until the backward pass
@@ -549,9 +581,29 @@ def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, targ
     kernel.  loss becomes ... + opacity_weight * L_op, L_op = mean over all rays of h = -(o log2 o + (1 - o) log2(1 - o)) with
     o = clamp(weights_sum, 1e-5, 1 - 1e-5); its gradient reaches a ray whose weights_sum lies inside the clamp (bounds included).
     opacity_grad=False: the value only, the sample gradients of the call without the term bit for bit.  `loss.opac` [N] holds h,
-    `loss.grad_ws` [N] d loss / d weights_sum, finish_opacity_loss(loss) L_op."""
+    `loss.grad_ws` [N] d loss / d weights_sum, finish_opacity_loss(loss) L_op.
+    pixel_weights / second_target (default None: today's call, bit for bit; loss='mse' only): a per-pixel weight w on the colour
+    residual and a second colour target t with its own weight, in the same kernel (`lae_composite_rays_train_step_weighted`), alone,
+    together, and with every other term: the colour criterion becomes mean((w (image - target))^2) + second_weight *
+    mean(((1 - w / 2) (t - image))^2), the reference's train_step_npr (nerf/utils.py:523-526).  Both are float16 / float32 tensors --
+    pixel_weights one value per ray, second_target [N, 3 or 4] -- or, with pixel_inds [N] int64 (ResidentImages.sample's `inds`), any
+    planes they index.  A 4-channel second target is blended over the ray's background, as the sampler blends `target`.  A weight of
+    0 removes the pixel's colour from the step exactly.  finish_second_loss(loss) is the second term without its weight."""
     from ..backend import loss_kind
     kind, param = loss_kind("composite_rays_train_blend_mse", loss, huber_delta)
+    weight_sup = None
+    if pixel_weights is not None or second_target is not None:
+        if kind != 0:
+            raise ValueError("composite_rays_train_blend_mse: pixel_weights / second_target need loss='mse'")
+        for name, t in (("pixel_weights", pixel_weights), ("second_target", second_target)):
+            if t is not None and (not torch.is_tensor(t) or t.dtype not in (torch.float16, torch.float32)):
+                raise RuntimeError(f"composite_rays_train_blend_mse: {name} must be a float16 or float32 tensor")
+        if second_target is not None and second_target.shape[-1] not in (3, 4):
+            raise RuntimeError("composite_rays_train_blend_mse: second_target must be [.., 3 or 4]")
+        weight_sup = (None if pixel_weights is None else _DepthPlane(pixel_weights.contiguous()),
+                      None if second_target is None else _DepthPlane(second_target.contiguous()),
+                      None if pixel_inds is None else pixel_inds.contiguous(),
+                      check_second_weight("composite_rays_train_blend_mse", second_weight))
     crit = None
     if kind != 0 or opacity_weight is not None:
         crit = (kind, param, None if opacity_weight is None else
@@ -573,10 +625,12 @@ def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, targ
             raise ValueError("composite_rays_train_blend_mse: depth_weight must be finite and >= 0")
         depth_sup = (_DepthPlane(depth.contiguous()), None if depth_inds is None else depth_inds.contiguous(), float(depth_weight),
                      not depth_grad)
-    loss, weights_sum, depth_o, image, both, depth_partials, grad_depth, dist_partials, grad_dist, dist, opac_partials, grad_ws, opac = \
-        _composite_rays_train_blend_mse.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale,
-                                              bool(defer_loss), depth_sup, dist_sup, crit)
+    (loss, weights_sum, depth_o, image, both, depth_partials, grad_depth, dist_partials, grad_dist, dist, opac_partials, grad_ws, opac,
+     second_partials) = _composite_rays_train_blend_mse.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh,
+                                                              target, scale, bool(defer_loss), depth_sup, dist_sup, crit, weight_sup)
     loss.unscaled = both[1]
+    if second_partials is not None:
+        loss.second_partials, loss.second_rays = second_partials, rays.shape[0]
     if opac is not None:
         loss.opac_partials, loss.grad_ws, loss.opac, loss.opac_rays = opac_partials, grad_ws, opac, rays.shape[0]
     if dist_sup is not None:
@@ -946,13 +1000,18 @@ def opacity_entropy_numpy(weights_sum, dtype=None):
 
 def composite_train_step_numpy(sigmas, rgbs, deltas, rays, target, T_thresh=1e-4, dtype=None, bg=None, z=None, nears=None, fars=None,
                                depth_weight=0.0, distort_weight=0.0, scale=1.0, depth_grad=True, distort_grad=True, n_rays=None,
-                               loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True):
-    """lae_composite_rays_train_step_crit restated in `dtype` (default float64): the forward, the colour criterion `loss`, the depth
-    term (with z), the distortion term and the opacity entropy, then the backward with the criterion's gradients
+                               loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True, pixel_weights=None, second_target=None,
+                               second_weight=0.0):
+    """lae_composite_rays_train_step_crit / _weighted restated in `dtype` (default float64): the forward, the colour criterion `loss`,
+    the depth term (with z), the distortion term and the opacity entropy, then the backward with the criterion's gradients
       grad_image = ((dv * (1 / (3 N))) * scale)  (mse: (e * (2 / (3 N))) * scale),   grad_ws = ((opacity_weight / N) * dh) * scale.
+    pixel_weights [N] (the gathered weights w) and second_target [N, 3 or 4] (the gathered second target s; 4 channels are blended
+    over bg: t = s_rgb * s_a + bg * (1 - s_a)), loss='mse' only: with u = 1 - w / 2, a = w e, b = u (t - pred),
+      colour = mean(a^2),  second = mean(b^2) (both over the 3 N elements),  grad_image = (((w a) - second_weight * (u b)) * (2 / (3 N))) * scale.
+    (The kernel evaluates that bracket in double when a second target is present -- its two parts cancel -- and in fp32 otherwise.)
     -> the dict of composite_distort_numpy (grad_sigmas, grad_rgbs, weights_sum, depth, image, dist, ...) plus image_out, grad_image,
-    grad_depth, grad_dist, grad_ws, opac [N], colour (= mean(v)), depth_mse, dist_mean, opac_mean (all N rays) and
-    loss = colour + depth_weight * depth_mse + distort_weight * dist_mean + opacity_weight * opac_mean."""
+    grad_depth, grad_dist, grad_ws, opac [N], colour (= mean(v)), second, depth_mse, dist_mean, opac_mean (all N rays) and
+    loss = colour + second_weight * second + depth_weight * depth_mse + distort_weight * dist_mean + opacity_weight * opac_mean."""
     import numpy as np
     dt = np.dtype(np.float64 if dtype is None else dtype).type
     f = composite_distort_numpy(sigmas, rgbs, deltas, rays, T_thresh, dtype=dtype, bg=bg, n_rays=n_rays)
@@ -964,6 +1023,22 @@ def composite_train_step_numpy(sigmas, rgbs, deltas, rays, target, T_thresh=1e-4
     e = out - tgt
     v, dv = colour_loss_numpy(e, tgt, loss, huber_delta, dtype)
     grad_image = (e * (dt(2) / dt(3 * N))) * sc if loss == "mse" else (dv * (one / dt(3 * N))) * sc
+    second, lam_2 = dt(0), dt(second_weight)
+    if pixel_weights is not None or second_target is not None:
+        if loss != "mse":
+            raise ValueError("composite_train_step_numpy: pixel_weights / second_target need loss='mse'")
+        pw = np.ones(N, dt) if pixel_weights is None else np.asarray(pixel_weights).astype(dt).reshape(N)
+        a = pw[:, None] * e
+        v = a * a
+        g = pw[:, None] * a
+        if second_target is not None:
+            s2 = np.asarray(second_target).astype(dt).reshape(N, -1)
+            t2 = s2[:, :3] * s2[:, 3:] + bgv * (one - s2[:, 3:]) if s2.shape[1] == 4 else s2
+            u = (one - dt(0.5) * pw)[:, None]
+            b = u * (t2 - out)
+            second = (b * b).sum() / dt(3 * N)
+            g = g - lam_2 * (u * b)
+        grad_image = (g * (dt(2) / dt(3 * N))) * sc
     res_d, grad_depth = np.zeros(N, dt), None
     if z is not None:
         zz, nr = np.asarray(z).astype(dt).reshape(N), np.asarray(nears).astype(dt).reshape(N)
@@ -979,6 +1054,7 @@ def composite_train_step_numpy(sigmas, rgbs, deltas, rays, target, T_thresh=1e-4
     res = composite_distort_numpy(sigmas, rgbs, deltas, rays, T_thresh, dtype=dtype, bg=bg, grad_weights_sum=grad_ws, grad_image=grad_image,
                                   grad_depth=grad_depth, grad_dist=grad_dist, n_rays=n_rays)
     colour, dmse, omean = v.sum() / dt(3 * N), (res_d * res_d).sum() / dt(N), h.sum() / dt(N)
-    res.update(image_out=out, grad_image=grad_image, grad_depth=grad_depth, grad_ws=grad_ws, opac=h, colour=colour, depth_mse=dmse,
-               opac_mean=omean, loss=colour + dt(depth_weight) * dmse + lam_x * res["dist_mean"] + lam_o * omean)
+    res.update(image_out=out, grad_image=grad_image, grad_depth=grad_depth, grad_ws=grad_ws, opac=h, colour=colour, second=second,
+               depth_mse=dmse, opac_mean=omean,
+               loss=colour + lam_2 * second + dt(depth_weight) * dmse + lam_x * res["dist_mean"] + lam_o * omean)
     return res

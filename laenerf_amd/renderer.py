@@ -344,7 +344,7 @@ class NeRFRenderer(nn.Module):
 
     def shade_train(self, marched, bg_color=1, T_thresh=1e-4, gt=None, scaler=None, depth=None, depth_inds=None, depth_weight=0.0,
                     depth_grad=True, distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None,
-                    opacity_grad=True):
+                    opacity_grad=True, pixel_weights=None, pixel_inds=None, second_target=None, second_weight=0.0):
         """second half: network on the samples, compositing, background blend, depth normalisation (renderer.py:313-334).
         gt [N,3] (optional, MI355X-native): also evaluate the trainer's criterion MSE(image, gt) (scaled by `scaler`'s
         loss scale) inside the compositing op -> result["loss"]; call loss.backward() on it.
@@ -355,7 +355,16 @@ class NeRFRenderer(nn.Module):
         loss / huber_delta / opacity_weight / opacity_grad (with gt only): the colour criterion and the opacity-entropy term of the same
         function; the defaults leave the call as it was.  Without fused_post_ops a non-default criterion is evaluated operator by
         operator -- losses.colour_loss_scaled on the blended image, the entropy written with torch operators -- where the default
-        leaves the criterion to the caller, as before."""
+        leaves the criterion to the caller, as before.
+        pixel_weights / pixel_inds / second_target / second_weight (with gt and loss='mse' only): the per-pixel weights and the second
+        colour target of the same function (`lae_composite_rays_train_step_weighted`); None leaves the call as it was.  Without
+        fused_post_ops the same criterion, mean((w (image - gt))^2) + second_weight * mean(((1 - w / 2) (t - image))^2), is written
+        with torch operators."""
+        weighted = pixel_weights is not None or second_target is not None
+        if weighted and gt is None:
+            raise RuntimeError("shade_train: pixel weights and a second target need gt")
+        if weighted and loss != "mse":
+            raise ValueError("shade_train: pixel_weights / second_target need loss='mse'")
         if depth is not None and not (self.fused_post_ops and gt is not None):
             raise RuntimeError("shade_train: depth supervision needs gt and fused_post_ops (it lives in the fused criterion kernel)")
         if distort_weight is not None and not (self.fused_post_ops and gt is not None):
@@ -367,6 +376,8 @@ class NeRFRenderer(nn.Module):
         kind = loss
         if crit_on:
             dist_kw.update(loss=kind, huber_delta=huber_delta, opacity_weight=opacity_weight, opacity_grad=opacity_grad)
+        if weighted and self.fused_post_ops:
+            dist_kw.update(pixel_weights=pixel_weights, pixel_inds=pixel_inds, second_target=second_target, second_weight=second_weight)
         xyzs, dirs, deltas, rays, nears, fars = marched[:6]
         plan = marched[6] if len(marched) > 6 else None
         sigmas, rgbs = self.model(xyzs, dirs, plan=plan) if plan is not None else self.model(xyzs, dirs)
@@ -388,19 +399,49 @@ class NeRFRenderer(nn.Module):
             weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh)
             image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
             depth = torch.clamp(depth - nears, min=0) / (fars - nears)
-        if crit_on and not self.fused_post_ops:
-            loss = self._criterion_unfused(image, weights_sum, gt, scaler, kind, huber_delta, opacity_weight, opacity_grad)
+        if (crit_on or weighted) and not self.fused_post_ops:
+            wsup = (pixel_weights, pixel_inds, second_target, second_weight, bg_color) if weighted else None
+            loss = self._criterion_unfused(image, weights_sum, gt, scaler, kind, huber_delta, opacity_weight, opacity_grad, wsup)
         res = {"image": image, "depth": depth, "weights_sum": weights_sum, "nears": nears, "n_samples": xyzs.shape[0]}
         if loss is not None:
             res["loss"] = loss
         return res
 
     @staticmethod
-    def _criterion_unfused(image, weights_sum, gt, scaler, loss, huber_delta, opacity_weight, opacity_grad):
-        """shade_train's criterion without fused_post_ops: the colour loss in one kernel, the entropy term operator by operator"""
+    def _weighted_unfused(image, gt, scaler, wsup):
+        """the weighted criterion of lae_composite_rays_train_step_weighted written with torch operators"""
+        from .raymarching.raymarching import check_second_weight
+        plane, inds, second, second_weight, bg = wsup
+        pick = (lambda t, c: t.reshape(-1, c)) if inds is None else (lambda t, c: t.reshape(-1, c).index_select(0, inds))
+        pred, gt = image.float(), gt.float()
+        w = pred.new_ones(pred.shape[0], 1) if plane is None else pick(plane, 1).float()
+        colour = ((w * (pred - gt)) ** 2).mean()
+        total = colour
+        second_term = None
+        if second is not None:
+            s2 = pick(second, int(second.shape[-1])).float()
+            t = s2[:, :3] * s2[:, 3:] + bg * (1 - s2[:, 3:]) if s2.shape[1] == 4 else s2
+            second_term = (((1 - 0.5 * w) * (t - pred)) ** 2).mean()
+            total = colour + check_second_weight("shade_train", second_weight) * second_term
+        scale = None
+        if scaler is not None:
+            scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
+        out = total if scale is None else total * scale[0]
+        out.unscaled = total.detach()
+        if second_term is not None:
+            out.second = second_term.detach()
+        return out
+
+    @staticmethod
+    def _criterion_unfused(image, weights_sum, gt, scaler, loss, huber_delta, opacity_weight, opacity_grad, wsup=None):
+        """shade_train's criterion without fused_post_ops: the colour loss in one kernel (with pixel weights or a second target: torch
+        operators), the entropy term operator by operator"""
         from .losses import colour_loss_scaled
         from .raymarching.raymarching import OPAC_LO, check_opacity_weight
-        out = colour_loss_scaled(image, gt, scaler, loss, huber_delta)
+        if wsup is not None:
+            out = NeRFRenderer._weighted_unfused(image, gt, scaler, wsup)
+        else:
+            out = colour_loss_scaled(image, gt, scaler, loss, huber_delta)
         if opacity_weight is None:
             return out
         w = check_opacity_weight("shade_train", opacity_weight)

@@ -41,6 +41,13 @@ torch-ngp's HuberLoss(beta=0.1) / Instant-NGP's NeRF preset) or 'mape' -- and op
 `opacity_weight * mean over the batch's rays of -(o log2 o + (1 - o) log2(1 - o))`, o = clamp(weights_sum, 1e-5, 1 - 1e-5) (torch-ngp's
 lambda_entropy), alone or together with the depth and distortion terms, inside the same captured groups.  opacity_grad=False computes
 the value only.  With error_map='ema' the map holds the trained criterion's per-ray mean, the reference's `error = loss.detach()`.
+
+pixel_weights=True (with a weight plane on the data, ResidentImages.pixel_weights) weights every pixel's colour residual,
+`mean((w * (pred - gt))^2)`, and second_weight (with ResidentImages.second_target) adds a second colour target,
+`second_weight * mean(((1 - w / 2) * (gt2 - pred))^2)` -- the reference's train_step_npr (nerf/utils.py:523-526), and mask- or
+confidence-weighted training in general -- inside the same kernel, which gathers both planes by the batch's pixel indices, and the same
+captured groups, alone or with the depth, distortion and opacity terms.  MSE only, and not with error_map='ema': the reference's
+rule would put the weighted loss into the map, and nothing in the reference does that.
 """
 import contextlib
 import copy
@@ -136,16 +143,29 @@ class Trainer:
     error map follows it.  opacity_weight: None (no term; the step without this argument, bit for bit) or the weight of the
     opacity-entropy regularizer (module docstring); opacity_grad: whether its gradient reaches the densities.  With it losses() holds
     the total and opacity_losses() the per-step term without its weight, finished like the other two.
+    pixel_weights: False (the step without this argument, bit for bit) or True: the colour residual of every pixel is multiplied by
+    data.pixel_weights (a weight of 0 removes the pixel's colour from the run exactly; a plane of ones is the default run bit for bit).
+    second_weight: None (no second term) or the weight of the second colour target data.second_target (module docstring); with it
+    losses() holds the total and second_losses() the per-step term without its weight, finished like the others.  Both need
+    loss='mse' and are refused with error_map='ema' (ValueError).
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
     def __init__(self, renderer, optimizer, data, iters, lr, num_rays=4096, seed=0, graph=True, capacity="bucket",
                  max_steps=1024, dt_gamma=0.0, error_map=None, ema_decay=None, epoch_len=None, depth_weight=None, depth_grad=True,
-                 distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True):
+                 distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True,
+                 pixel_weights=False, second_weight=None):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
         if error_map not in (None, "ema", "fixed"):
             raise ValueError("Trainer: error_map must be None, 'ema' or 'fixed'")
+        if pixel_weights or second_weight is not None:                # refused before anything is changed on the data
+            from .backend import loss_kind
+            loss_kind("Trainer", loss, huber_delta)
+            if loss != "mse":
+                raise ValueError("Trainer: pixel_weights / second_weight need loss='mse' (the reference has no weighted L1 / Huber / MAPE)")
+            if error_map == "ema":
+                raise ValueError("Trainer: pixel_weights / second_weight cannot be combined with error_map='ema'")
         if error_map is not None and data.error_map is None:
             data.enable_error_map()
         self.r, self.opt, self.data = renderer, optimizer, data
@@ -175,6 +195,18 @@ class Trainer:
                 raise ValueError("Trainer: the opacity term needs the renderer's fused_post_ops")
         self.loss, self.huber_delta = loss, float(huber_delta)
         self.opacity_weight, self.opacity_grad = opacity_weight, bool(opacity_grad)
+        if pixel_weights or second_weight is not None:
+            if pixel_weights and getattr(data, "pixel_weights", None) is None:
+                raise ValueError("Trainer: pixel_weights=True needs a weight plane on the data (ResidentImages(pixel_weights=...) / "
+                                 "set_pixel_weights)")
+            if second_weight is not None:
+                second_weight = raymarching.check_second_weight("Trainer", second_weight)
+                if getattr(data, "second_target", None) is None:
+                    raise ValueError("Trainer: second_weight needs a second target on the data (ResidentImages(second_target=...) / "
+                                     "set_second_target)")
+            if not renderer.fused_post_ops:
+                raise ValueError("Trainer: pixel weights and a second target need the renderer's fused_post_ops")
+        self.pixel_weights, self.second_weight = bool(pixel_weights), second_weight
         dev = renderer.density_grid.device
         data.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         data.aabb = renderer.aabb_train.to(dev, torch.float32).contiguous()      # the batch's near / far = the march's
@@ -190,6 +222,8 @@ class Trainer:
         self._distort_hist = []
         self.opacity_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.opacity_weight is not None else None
         self._opacity_hist = []
+        self.second_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.second_weight is not None else None
+        self._second_hist = []
         self.global_step = 0
         self.started = False
         self.graphs = {}
@@ -237,6 +271,10 @@ class Trainer:
             if self.loss != "mse" or self.opacity_weight is not None:
                 dist_kw.update(loss=self.loss, huber_delta=self.huber_delta, opacity_weight=self.opacity_weight,
                                opacity_grad=self.opacity_grad)
+            if self.pixel_weights or self.second_weight is not None:
+                dist_kw.update(pixel_weights=self.data.pixel_weights if self.pixel_weights else None, pixel_inds=b["inds"],
+                               second_target=self.data.second_target if self.second_weight is not None else None,
+                               second_weight=0.0 if self.second_weight is None else self.second_weight)
             if self.depth_weight is None:
                 res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt, **dist_kw)
             else:
@@ -252,6 +290,8 @@ class Trainer:
             raymarching.finish_distort_loss(loss, out=self.distort_slots[k])
         if self.opacity_weight is not None:
             raymarching.finish_opacity_loss(loss, out=self.opacity_slots[k])
+        if self.second_weight is not None:
+            raymarching.finish_second_loss(loss, out=self.second_slots[k])
         opt.backward(loss)
         opt.step()
         if self.ema is not None:
@@ -315,6 +355,8 @@ class Trainer:
                 self._distort_hist.append(self.distort_slots[pos:pos + n, 1].clone())
             if self.opacity_slots is not None:
                 self._opacity_hist.append(self.opacity_slots[pos:pos + n, 1].clone())
+            if self.second_slots is not None:
+                self._second_hist.append(self.second_slots[pos:pos + n, 1].clone())
             done += n
             self.global_step += n
         return self
@@ -351,6 +393,13 @@ class Trainer:
             return np.zeros(0, np.float32)
         return torch.cat(self._opacity_hist).cpu().numpy()
 
+    def second_losses(self):
+        """per-step second colour term mean(((1 - w / 2) * (second_target - pred))^2), without its weight, as a float32 numpy array
+        (empty without second_weight).  Each step finishes it with one lae_loss_finish node off the gradient path."""
+        if not self._second_hist:
+            return np.zeros(0, np.float32)
+        return torch.cat(self._second_hist).cpu().numpy()
+
     @property
     def steps_skipped(self):
         """optimizer steps the GradScaler skipped (non-finite gradients)"""
@@ -378,6 +427,10 @@ class Trainer:
                 cfg["huber_delta"] = self.huber_delta
         if self.opacity_weight is not None:
             cfg["opacity_weight"], cfg["opacity_grad"] = self.opacity_weight, self.opacity_grad
+        if self.pixel_weights:
+            cfg["pixel_weights"] = True
+        if self.second_weight is not None:
+            cfg["second_weight"] = self.second_weight
         return cfg
 
     def state_dict(self, full=True):
@@ -532,7 +585,7 @@ class Trainer:
             self.m_limit.fill_(self._m())
         self.graphs = {}
         self._pool = None
-        self._loss_hist, self._depth_hist, self._distort_hist, self._opacity_hist = [], [], [], []
+        self._loss_hist, self._depth_hist, self._distort_hist, self._opacity_hist, self._second_hist = [], [], [], [], []
         self.started = True
         return self
 

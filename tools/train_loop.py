@@ -7,6 +7,7 @@ refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated o
 
     python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed] [--ema] [--depth] [--distort W]
                                 [--loss mse|l1|huber|mape] [--huber-delta D] [--entropy W] [--outliers P]
+                                [--mask-outliers P]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
 ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR.
@@ -22,6 +23,9 @@ term's first and last 16-step mean ("opacity": {...}).  Compare ms/step with a r
 --outliers P: the share P of the training pixels (never the held-out views) is overwritten with opaque uniformly random colours before
 training, the specular / exposure outliers of a real capture in their crudest form; the held-out PSNR under --loss mse and --loss huber
 is what the robust criterion buys.
+--mask-outliers P: --outliers P with a weight plane that is 0 on the overwritten pixels and 1 elsewhere (Trainer(pixel_weights=True)): the
+outliers cannot matter, and the held-out PSNR is that of the clean pixels alone.  Compare ms/step with a run without the option for
+the cost of the weighted step.
 --save PATH: the first student's checkpoint is written after the run (Trainer.save_checkpoint; a `.pth` path or a directory);
 --resume PATH: the first student loads it before training and then trains --steps further steps (the same --steps as the saved run
 keeps the learning-rate horizon, which the load checks).  The line then carries "checkpoint": the file size in bytes and the save /
@@ -95,7 +99,7 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
 
 def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=True, capacity="bucket", seed=0, student_seed=0,
                  error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True, distort_weight=None, loss="mse",
-                 huber_delta=0.1, opacity_weight=None):
+                 huber_delta=0.1, opacity_weight=None, pixel_weights=None):
     from laenerf_amd.data import ResidentImages
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.optim import FusedAdam
@@ -105,12 +109,14 @@ def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=Tr
     net = NeRFNetwork(bound=1).to(dev)
     r = NeRFRenderer(net, bound=1, density_thresh=10).to(dev)
     opt = FusedAdam(net, param_groups=net.get_params(lr), betas=(0.9, 0.99), eps=1e-15, device_lr=True)
-    data = ResidentImages.from_arrays(images, poses, intr, bg="random", device=dev, depths=depths)
+    data = ResidentImages.from_arrays(images, poses, intr, bg="random", device=dev, depths=depths, pixel_weights=pixel_weights)
     depth_kw = {} if depth_weight is None else {"depth_weight": depth_weight, "depth_grad": depth_grad}
     if distort_weight is not None:
         depth_kw["distort_weight"] = distort_weight
     if loss != "mse" or opacity_weight is not None:
         depth_kw.update(loss=loss, huber_delta=huber_delta, opacity_weight=opacity_weight)
+    if pixel_weights is not None:
+        depth_kw["pixel_weights"] = True
     return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map,
                    ema_decay=ema_decay, **depth_kw)
 
@@ -161,6 +167,7 @@ def main():
     ap.add_argument("--huber-delta", type=float, default=0.1, metavar="D")
     ap.add_argument("--entropy", type=float, default=None, metavar="W", help="Trainer(opacity_weight=W) for every student of the run")
     ap.add_argument("--outliers", type=float, default=0.0, metavar="P", help="share of training pixels overwritten with random colours")
+    ap.add_argument("--mask-outliers", type=float, default=0.0, metavar="P", help="--outliers P with weight 0 on the overwritten pixels")
     ap.add_argument("--save", default=None, metavar="PATH", help="write the first student's checkpoint after the run")
     ap.add_argument("--resume", default=None, metavar="PATH", help="load a checkpoint into the first student before training")
     args = ap.parse_args()
@@ -170,13 +177,19 @@ def main():
     build.build()
     images, poses, intr = teacher_views(dev, args.views, args.res, args.res)
     held = 4
-    if args.outliers > 0:
+    if args.mask_outliers > 0 and args.outliers > 0:
+        ap.error("--mask-outliers P implies --outliers P: give one of the two")
+    share = max(args.outliers, args.mask_outliers)
+    mask = None
+    if share > 0:
         rng = np.random.default_rng(17)
-        hit = rng.random(images[held:].shape[:3]) < args.outliers
+        hit = rng.random(images[held:].shape[:3]) < share
         noise = rng.integers(0, 256, size=images[held:].shape, dtype=np.uint8)
         noise[..., 3] = 255
         images[held:][hit] = noise[hit]
-    crit_kw = dict(loss=args.loss, huber_delta=args.huber_delta, opacity_weight=args.entropy)
+        if args.mask_outliers > 0:
+            mask = np.where(hit, 0.0, 1.0).astype(np.float16)
+    crit_kw = dict(loss=args.loss, huber_delta=args.huber_delta, opacity_weight=args.entropy, pixel_weights=mask)
     tr = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
                       capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, distort_weight=args.distort,
                       **crit_kw)
@@ -233,6 +246,7 @@ def main():
         **({"opacity": {"opacity_weight": args.entropy, "first_opacity_loss": float(tr.opacity_losses()[:16].mean()),
                         "final_opacity_loss": float(tr.opacity_losses()[-16:].mean())}} if args.entropy is not None else {}),
         **({"outliers": args.outliers} if args.outliers > 0 else {}),
+        **({"mask_outliers": args.mask_outliers, "masked_pixels_frac": round(float((mask == 0).mean()), 4)} if mask is not None else {}),
         **({"depth": depth} if depth is not None else {}), **({"checkpoint": ckpt} if ckpt else {}),
         "scene": f"{args.views - held} training + {held} held-out {args.res}x{args.res} RGBA uint8 views of a teacher network"}), flush=True)
 
