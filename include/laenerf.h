@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi23"
+#define LAE_ABI_TAG "abi24"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -1309,6 +1309,43 @@ LAE_API int lae_eval_view(const float* pred, const float* depth, const void* gt,
  * accumulated in fp64 with a fixed-order reduction.  scratch: n_pairs * sum_l ceil(hw[l] / 256) doubles. */
 LAE_API int lae_lpips_head(uint32_t n_layers, const float* const* feats, const float* const* weights, const uint32_t* channels,
                            const uint32_t* hw, uint32_t n_pairs, double* scratch, double* out, void* stream);
+
+/* ---- training-camera pose refinement (csrc/gridencoder.hip, csrc/pose.hip; laenerf_amd/poses.py restates all three in float64)
+ *
+ * lae_grid_input_grad: d loss / d x of the samples, without the reference's dy_dx buffer (K13 + K15, gridencoder.cu:201-243, 343-369:
+ * L * D * C values per sample written by the forward and summed in fp16).  inputs fp32 [M,3]; embeddings the fp16 table; grad_feats
+ * fp16 [L, M, 2], level-major (what lae_nerf_field_backward leaves in grad_enc); in_shift / in_scale the map of
+ * lae_grid_encode_forward_ex; grad_x fp32 [M,3], overwritten.  Every (sample, level) recomputes its cell and fractional position with
+ * the forward's statements, gathers the forward's eight corners and sums per axis, in fp32,
+ *     scale * w(other two axes) * (table[right] - table[left]) * grad_feats[l, b, ch]   over the 4 corner pairs and 2 channels;
+ * the sum over the levels is multiplied by in_scale.  A row with a coordinate outside [0,1] after the map gives zeros.  One owner per
+ * output row, no atomics: two calls give the same bits.  Supported: D = 3, C = 2, dtype LAE_F16, linear interpolation, both grid
+ * types, both align_corners values, 1 <= L <= 32; anything else is LAE_EINVAL before the first launch. */
+LAE_API int lae_grid_input_grad(const float* inputs, const void* embeddings, const int32_t* offsets, const void* grad_feats, float* grad_x,
+                                uint32_t M, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
+                                int align_corners, uint32_t interp, int dtype, float in_shift, float in_scale, void* stream);
+/* per ray, the gradient of the loss with respect to a rigid motion of the ray's camera in the world-frame tangent space: moving the
+ * camera (R, T) to (Exp(w) R, T + t) moves every sample x of its rays to T + t + Exp(w)(x - T), so d loss / d t = sum_k g_k and
+ * d loss / d w = sum_k (x_k - T) x g_k.  rays int32 [N,3] (ray id, offset, count: lae_march_rays_train's), xyzs and grad_x fp32
+ * [M,3], rays_o fp32 [N,3] (indexed by ray id); out double [N,6] indexed by ray id = (sum g, sum (x - o) x g), products and sums in
+ * fp64: lane j of the ray's wave adds its samples j, j + 64, ... in order, then the 64 lanes are added as a fixed tree (same bits on
+ * every run).  A ray with count 0, or whose samples do not fit into M (offset + count > M: the compositing kernels drop it), writes
+ * zeros.  The gradient through the view direction, through nears / fars and through the occupancy decisions is not part of it. */
+LAE_API int lae_pose_ray_grad(const int32_t* rays, const float* xyzs, const float* grad_x, const float* rays_o, uint32_t N, uint32_t M,
+                              double* out, void* stream);
+/* one launch, one workgroup per image: (a) the per-ray vectors of the rays whose image is this one (image = inds[n] / hw; inds int64
+ * [N] as lae_sample_train_batch writes it, either sampler mode) are added in fp64 in a fixed order; (b) a sparse Adam step in the
+ * tangent space: g = sum * (double)opt_state[7] (1 / loss scale, a float), count += 1, m = beta1 m + (1 - beta1) g,
+ * v = beta2 v + (1 - beta2) g^2, delta = -(lr / (1 - beta1^count)) * m / (sqrt(v) / sqrt(1 - beta2^count) + eps), torch.optim.Adam's
+ * formulas in fp64 with the image's own count; lr is *lr (a float in device memory).  An image without a ray in the batch is not
+ * touched at all; with opt_state[3] (skip) non-zero nothing is touched; an image whose g is not finite is skipped on its own;
+ * (c) R <- Exp(delta[3:6]) R, tau <- tau + delta[0:3] on the fp64 master [n_img, 12] (rows of [R | tau]); Rodrigues' formula in fp64,
+ * the series sin x / x = 1 - x^2 / 6, (1 - cos x) / x^2 = 1 / 2 - x^2 / 24 for x^2 < 1e-12; a zero rotation or translation component
+ * leaves the operand's bits alone; (d) train_poses fp32 [n_img, 4, 4]: the 3 x 4 top of the image's matrix is rewritten from the
+ * master.  m, v double [n_img, 6]; counts int32 [n_img]; opt_state the 16 words of the main optimizer (read only). */
+LAE_API int lae_pose_step(const double* ray_grads, const int64_t* inds, uint32_t N, uint64_t hw, uint32_t n_img, double* master,
+                          double* m, double* v, int32_t* counts, float* train_poses, const int32_t* opt_state, const float* lr,
+                          double beta1, double beta2, double eps, void* stream);
 
 /* MI355X-native: 0 (default) = fused backward (activations recomputed in registers, forward_buffer /
  * backward_buffer untouched: both are scratch the reference's Python never reads), every wave accumulating all dW tiles

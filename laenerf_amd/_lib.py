@@ -75,6 +75,9 @@ SIGNATURES = {
     "lae_grid_set_backward_mode": [i32],
     "lae_grid_set_forward_mode": [i32],
     "lae_grid_forward_schedule": [vp, u32, f32, u32, u32, vp, vp],
+    "lae_grid_input_grad": [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, u32, i32, u32, i32, f32, f32, vp],
+    "lae_pose_ray_grad": [vp, vp, vp, vp, u32, u32, vp, vp],
+    "lae_pose_step": [vp, vp, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, f64, f64, f64, vp],
     "lae_grad_total_variation": [vp, vp, vp, vp, f32, u32, u32, u32, u32, f32, u32, u32, i32, i32, vp],
     "lae_sh_encode_forward": [vp, vp, u32, u32, u32, vp, vp],
     "lae_sh_encode_backward": [vp, vp, u32, u32, u32, vp, vp, vp],
@@ -184,7 +187,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi23"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi24"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

@@ -617,6 +617,23 @@ class _GridEncoder:
             check(lib.lae_grid_encode_forward(*args, stream()), "grid_encode_forward")
 
     @staticmethod
+    def grid_input_grad(inputs, embeddings, offsets, grad_feats, grad_x, M, D, C, L, S, H, gridtype, align_corners, interp,
+                        in_map=(0.0, 1.0)):
+        """MI355X extension (lae_grid_input_grad): d loss / d inputs [M,3] fp32 (overwritten) from the level-major feature gradients
+        grad_feats [L, M, 2] fp16 and the fp16 table, without a dy_dx buffer; in_map as grid_encode_forward's"""
+        ts = (inputs, embeddings, offsets, grad_feats, grad_x)
+        need_cuda(*ts); need_contig(*ts)
+        if inputs.dtype != torch.float32 or grad_x.dtype != torch.float32 or offsets.dtype != torch.int32:
+            raise RuntimeError("grid_input_grad: inputs and grad_x must be float32, offsets int32")
+        if grad_feats.dtype != embeddings.dtype:
+            raise RuntimeError("grid_input_grad: grad_feats must have the embeddings dtype")
+        if inputs.numel() != 3 * M or grad_x.numel() != 3 * M or grad_feats.numel() != L * M * C:
+            raise RuntimeError("grid_input_grad: inputs / grad_x must hold M rows of 3, grad_feats L * M * C values")
+        check(_lib.load().lae_grid_input_grad(ptr(inputs), ptr(embeddings), ptr(offsets), ptr(grad_feats), ptr(grad_x), M, D, C, L,
+                                              float(S), H, gridtype, int(bool(align_corners)), interp, _dtype_code(embeddings),
+                                              float(in_map[0]), float(in_map[1]), stream()), "grid_input_grad")
+
+    @staticmethod
     def grid_backward_plan(inputs, offsets, B, D, C, L, S, H, gridtype, align_corners, interp, half, in_map=(0.0, 1.0),
                            offsets_host=None, touched_lines=None):
         """first half of the binned grid backward (positions only: count pass + scans) -> plan tensor for

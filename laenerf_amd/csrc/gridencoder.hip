@@ -1336,6 +1336,86 @@ __global__ void k_grid_input_bwd(const T* __restrict__ grad, const T* __restrict
     grad_inputs[t] = r;
 }
 
+// ---------------------------------------------------------------- input gradient without dy_dx (lae_grid_input_grad)
+// d loss / d x of the samples from the level-major feature gradients [L, M, 2] (what lae_nerf_field_backward leaves in grad_enc), for
+// the fp16 table, D = 3, C = 2, linear interpolation.  K13 + K15 need a dy_dx buffer of L * D * C values per sample and sum in fp16;
+// here every (sample, level) recomputes its cell and fractional position with the forward's statements (level_info, cell_index, the
+// fmaf of k_grid_fwd), gathers the forward's eight corners again and sums, per axis gd and in fp32,
+//     scale * w(other two axes) * (table[right] - table[left]) * grad_feats[l, b, ch]      over the 4 corner pairs and 2 channels.
+// Layout: a workgroup owns IG_ROWS = 64 consecutive samples; lane = sample, wave w takes the levels w, w + IG_WAVES, ... (a coarse and
+// a fine level for L = 16, as the (l, l + 8) pairing of k_grid_fwd), so that every load of x and of grad_feats is one contiguous run
+// per wave and all lanes of a wave gather from the same level's table.  The waves' partial sums meet in LDS and wave 0 adds them in
+// wave order: one owner per output row, no atomics, the same bits on every run.  A row outside [0,1]^3 gives zeros (the forward's rule).
+constexpr int IG_ROWS = 64, IG_WAVES = 8;
+
+__global__ __launch_bounds__(IG_ROWS * IG_WAVES) void k_grid_input_grad(
+    const float* __restrict__ inputs, const half_t* __restrict__ grid, const int32_t* __restrict__ offsets,
+    const half_t* __restrict__ grad_feats, float* __restrict__ grad_x, uint32_t M, uint32_t L, LevelScales sc, uint32_t gridtype,
+    bool align_corners) {
+    __shared__ float part[IG_WAVES][3][IG_ROWS];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t b = blockIdx.x * IG_ROWS + lane;
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    if (b < M) {
+        float x01[3];
+        bool oob = false;
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            x01[d] = (inputs[(size_t)b * 3 + d] + sc.in_shift) * sc.in_scale;
+            oob |= (x01[d] < 0.0f) | (x01[d] > 1.0f);
+        }
+        if (!oob) {
+            for (uint32_t level = wave; level < L; level += IG_WAVES) {
+                const LevelInfo<3> li = level_info<3>(sc, offsets, level, gridtype, align_corners);
+                const uint32_t* __restrict__ tab = reinterpret_cast<const uint32_t*>(grid) + li.table_off;   // one word = the entry's two halves
+                float fr[3];
+                uint32_t pg[3];
+#pragma unroll
+                for (int d = 0; d < 3; d++) {
+                    const float p = fmaf(x01[d], li.scale, align_corners ? 0.0f : 0.5f);
+                    pg[d] = (uint32_t)floorf(p);
+                    fr[d] = p - (float)pg[d];
+                }
+                float v[8][2];                             // corner idx = x + 2y + 4z
+#pragma unroll
+                for (int idx = 0; idx < 8; idx++) {
+                    const uint32_t pl[3] = {pg[0] + (idx & 1), pg[1] + ((idx >> 1) & 1), pg[2] + (idx >> 2)};
+                    const half2_t h = __builtin_bit_cast(half2_t, tab[cell_index<3>(li, pl)]);
+                    v[idx][0] = (float)h[0]; v[idx][1] = (float)h[1];
+                }
+                const half2_t gh = *reinterpret_cast<const half2_t*>(grad_feats + ((size_t)level * M + b) * 2);
+                const float g0 = (float)gh[0], g1 = (float)gh[1];
+#pragma unroll
+                for (int gd = 0; gd < 3; gd++) {
+                    const int da = gd == 0 ? 1 : 0, db = gd == 2 ? 1 : 2;              // the other two axes, in order
+#pragma unroll
+                    for (int pr = 0; pr < 4; pr++) {
+                        const float wa = (pr & 1) ? fr[da] : 1.0f - fr[da];
+                        const float wb = (pr & 2) ? fr[db] : 1.0f - fr[db];
+                        const float w = li.scale * (wa * wb);
+                        const int il = ((pr & 1) << da) | (((pr >> 1) & 1) << db), ir = il | (1 << gd);
+                        acc[gd] = fmaf(w, (v[ir][0] - v[il][0]) * g0, acc[gd]);
+                        acc[gd] = fmaf(w, (v[ir][1] - v[il][1]) * g1, acc[gd]);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; d++) part[wave][d][lane] = acc[d];
+    __syncthreads();
+    if (wave == 0 && b < M) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            float s = part[0][d][lane];
+#pragma unroll
+            for (int w = 1; w < IG_WAVES; w++) s += part[w][d][lane];
+            grad_x[(size_t)b * 3 + d] = s * sc.in_scale;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- K16
 // gridencoder.cu:506-610 (fp32 only: grid.py:165 runs it with autocast disabled)
 template <int D, int C>
@@ -2034,6 +2114,21 @@ int lae_nerf_field_backward(const float* grad_sigmas, const float* grad_rgbs, co
     return grid_backward(grad_enc, inputs, nullptr, offsets, grad_embeddings, M, 3, 2, L, S, H, nullptr, nullptr, gridtype, align_corners,
                          interp, LAE_F16, false, stream, in_shift, in_scale, offsets_host, plan, table_nonfinite_flag,
                          plan ? nullptr : touched_lines, grad_dirty, ride ? &tail : nullptr);
+}
+
+int lae_grid_input_grad(const float* inputs, const void* embeddings, const int32_t* offsets, const void* grad_feats, float* grad_x,
+                        uint32_t M, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
+                        uint32_t interp, int dtype, float in_shift, float in_scale, void* stream) {
+    if (D != 3 || C != 2 || dtype != LAE_F16 || interp != LAE_INTERP_LINEAR || gridtype > 1) return LAE_EINVAL;
+    LevelScales sc;
+    if (const int rc = fill_scales(sc, L, S, H)) return rc;                     // L = 0 or L > 32
+    if (M == 0) return LAE_OK;
+    if (!inputs || !embeddings || !offsets || !grad_feats || !grad_x) return LAE_ENULL;
+    sc.in_shift = in_shift; sc.in_scale = in_scale;
+    hipLaunchKernelGGL(k_grid_input_grad, dim3(lae::cdiv(M, IG_ROWS)), dim3(IG_ROWS * IG_WAVES), 0, reinterpret_cast<hipStream_t>(stream),
+                       inputs, (const half_t*)embeddings, offsets, (const half_t*)grad_feats, grad_x, M, L, sc, gridtype,
+                       align_corners != 0);
+    return lae::check_launch("grid_input_grad");
 }
 
 int lae_grid_forward_schedule(const int32_t* offsets_host, uint32_t L, float S, uint32_t H, uint32_t n_chunks, uint32_t* nseg_out,

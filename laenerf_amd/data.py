@@ -236,6 +236,7 @@ class ResidentImages:
         self.depths = None
         if depths is not None:
             self.set_depths(depths)
+        self.train_poses = self.pose_master = self.pose_m = self.pose_v = self.pose_counts = None      # enable_pose_refinement
         self.pixel_weights = self.second_target = None
         if pixel_weights is not None:
             self.set_pixel_weights(pixel_weights)
@@ -291,6 +292,58 @@ class ResidentImages:
         self.error_map = torch.full((self.n_img, ERROR_MAP_CELLS), float(init), dtype=torch.float32, device=self.images.device)
         self._out = {}
         return self.error_map
+
+    def enable_pose_refinement(self):
+        """create the state of the camera refinement (Trainer(pose_refine=True)): .pose_master fp64 [n_img, 12] (the rows of [R | T]),
+        .pose_m / .pose_v fp64 [n_img, 6] and .pose_counts int32 [n_img] (a sparse Adam in the world-frame tangent space, translation
+        first) and .train_poses fp32 [n_img, 4, 4], equal to .poses bit for bit until the first update.  From then on sample() builds
+        its rays from .train_poses; .poses stays the caller's input.  A second call changes nothing."""
+        if self.train_poses is None:
+            dev = self.poses.device
+            self.train_poses = self.poses.clone()
+            self.pose_master = self.poses[:, :3, :4].to(torch.float64).reshape(self.n_img, 12).contiguous()
+            self.pose_m = torch.zeros(self.n_img, 6, dtype=torch.float64, device=dev)
+            self.pose_v = torch.zeros(self.n_img, 6, dtype=torch.float64, device=dev)
+            self.pose_counts = torch.zeros(self.n_img, dtype=torch.int32, device=dev)
+        return self.train_poses
+
+    def _sample_poses(self):
+        return self.poses if self.train_poses is None else self.train_poses
+
+    @staticmethod
+    def pose_ray_grad(rays, xyzs, grad_x, rays_o, out=None):
+        """lae_pose_ray_grad: per ray (sum g, sum (x - o) x g) as fp64 [N, 6] at the ray id's row (poses.pose_ray_grad_numpy)"""
+        ts = (rays, xyzs, grad_x, rays_o)
+        _lib.need_cuda(*ts); _lib.need_contig(*ts)
+        if rays.dtype != torch.int32 or any(t.dtype != torch.float32 for t in ts[1:]):
+            raise RuntimeError("pose_ray_grad: rays must be int32, xyzs / grad_x / rays_o float32")
+        N, M = int(rays.shape[0]), int(xyzs.shape[0])
+        if tuple(grad_x.shape) != (M, 3) or tuple(xyzs.shape) != (M, 3) or tuple(rays_o.shape) != (N, 3) or tuple(rays.shape) != (N, 3):
+            raise RuntimeError("pose_ray_grad: rays [N,3], xyzs and grad_x [M,3], rays_o [N,3] expected")
+        if out is None:
+            out = torch.empty(N, 6, dtype=torch.float64, device=rays.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (N, 6) or not out.is_contiguous() or out.device != rays.device:
+            raise RuntimeError("pose_ray_grad: out must be a contiguous float64 [N, 6] tensor on the rays' device")
+        check(_lib.load().lae_pose_ray_grad(ptr(rays), ptr(xyzs), ptr(grad_x), ptr(rays_o), N, M, ptr(out), stream()), "pose_ray_grad")
+        return out
+
+    @torch.no_grad()
+    def pose_step(self, ray_grads, inds, opt_state, lr, betas=(0.9, 0.99), eps=1e-15):
+        """lae_pose_step: reduce ray_grads fp64 [N, 6] by the image of inds [N], one sparse Adam step per image that received a ray,
+        composed onto .pose_master; .train_poses is rewritten.  opt_state: the main optimizer's 16 device state words (skip decision
+        and 1 / loss scale); lr: a float32 tensor on the device (poses.pose_step_numpy)"""
+        if self.train_poses is None:
+            raise ValueError("ResidentImages.pose_step: enable_pose_refinement() first")
+        ts = (ray_grads, inds, opt_state, lr)
+        _lib.need_cuda(*ts); _lib.need_contig(*ts)
+        N = int(inds.shape[0])
+        if ray_grads.dtype != torch.float64 or tuple(ray_grads.shape) != (N, 6) or inds.dtype != torch.int64:
+            raise RuntimeError("pose_step: ray_grads must be float64 [N, 6], inds int64 [N]")
+        if opt_state.dtype != torch.int32 or opt_state.numel() != 16 or lr.dtype != torch.float32 or lr.numel() < 1:
+            raise RuntimeError("pose_step: opt_state must be the optimizer's 16 int32 words, lr a float32 tensor")
+        check(_lib.load().lae_pose_step(ptr(ray_grads), ptr(inds), N, self.H * self.W, self.n_img, ptr(self.pose_master), ptr(self.pose_m),
+                                        ptr(self.pose_v), ptr(self.pose_counts), ptr(self.train_poses), ptr(opt_state), ptr(lr),
+                                        float(betas[0]), float(betas[1]), float(eps), stream()), "pose_step")
 
     @classmethod
     def from_arrays(cls, images, poses, intrinsics, **kw):
@@ -377,7 +430,7 @@ class ResidentImages:
         o = out if out is not None else self._buffers(int(n_rays))
         fx, fy, cx, cy = self.intrinsics
         check(_lib.load().lae_sample_train_batch(
-            ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self.poses), fx, fy, cx, cy,
+            ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self._sample_poses()), fx, fy, cx, cy,
             int(n_rays), ptr(self.aabb), self.min_near, self.seed, ptr(self.step), _MODES[self.mode], _BGS[self.bg],
             int(self.color_space == "linear"), ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]),
             ptr(o["bg"]), ptr(o["inds"]), stream()), "sample_train_batch")
@@ -406,7 +459,7 @@ class ResidentImages:
         o = out if out is not None else self._buffers(int(n_rays))
         fx, fy, cx, cy = self.intrinsics
         check(_lib.load().lae_sample_train_batch_weighted(
-            ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self.poses), fx, fy, cx, cy,
+            ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self._sample_poses()), fx, fy, cx, cy,
             int(n_rays), ptr(self.aabb), self.min_near, self.seed, ptr(self.step), _BGS[self.bg], int(self.color_space == "linear"),
             ptr(self.error_map), ptr(o["cells"]), ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]),
             ptr(o["bg"]), ptr(o["inds"]), stream()), "sample_train_batch_weighted")
@@ -439,8 +492,12 @@ class ResidentImages:
     def state_dict(self):
         """what a resumed run needs of the sampler, never the images: seed (int), step (the device counter, int64 [1], on the host)
         and error_map (a host copy, or None)"""
-        return {"seed": int(self.seed), "step": self.step.detach().cpu().clone(),
-                "error_map": None if self.error_map is None else self.error_map.detach().cpu().clone()}
+        sd = {"seed": int(self.seed), "step": self.step.detach().cpu().clone(),
+              "error_map": None if self.error_map is None else self.error_map.detach().cpu().clone()}
+        if self.train_poses is not None:             # the refinement's state (only with it: files of other runs stay as they were)
+            sd["pose"] = {"master": self.pose_master.detach().cpu().clone(), "m": self.pose_m.detach().cpu().clone(),
+                          "v": self.pose_v.detach().cpu().clone(), "counts": self.pose_counts.detach().cpu().clone()}
+        return sd
 
     def check_state_dict(self, sd):
         """the reasons load_state_dict would refuse `sd` (a list of strings, empty when it fits); nothing is changed"""
@@ -452,6 +509,13 @@ class ResidentImages:
         if m is not None and (not torch.is_tensor(m) or tuple(m.shape) != (self.n_img, ERROR_MAP_CELLS)):
             bad.append(f"data.error_map: saved {list(m.shape) if torch.is_tensor(m) else type(m).__name__}, "
                        f"current {[self.n_img, ERROR_MAP_CELLS]}")
+        ps = sd.get("pose")
+        if ps is not None:
+            want = {"master": (self.n_img, 12), "m": (self.n_img, 6), "v": (self.n_img, 6), "counts": (self.n_img,)}
+            for k, shape in want.items():
+                t = ps.get(k) if isinstance(ps, dict) else None
+                if not torch.is_tensor(t) or tuple(t.shape) != shape:
+                    bad.append(f"data.pose.{k}: saved {list(t.shape) if torch.is_tensor(t) else type(t).__name__}, current {list(shape)}")
         return bad
 
     @torch.no_grad()
@@ -468,6 +532,16 @@ class ResidentImages:
             if self.error_map is None:
                 self.enable_error_map()
             self.error_map.copy_(m.to(self.error_map.device, torch.float32))
+        ps = sd.get("pose")
+        if ps is not None:
+            self.enable_pose_refinement()
+            dev = self.train_poses.device
+            self.pose_master.copy_(ps["master"].to(dev, torch.float64))
+            self.pose_m.copy_(ps["m"].to(dev, torch.float64))
+            self.pose_v.copy_(ps["v"].to(dev, torch.float64))
+            self.pose_counts.copy_(ps["counts"].to(dev, torch.int32))
+            # the kernel's own conversion (round to nearest); the bottom row stays the input's
+            self.train_poses[:, :3, :4].copy_(self.pose_master.view(self.n_img, 3, 4).to(torch.float32))
 
     def view_rays(self, i):
         """every pixel of image i (scanline order) -> rays_o, rays_d [H*W, 3] and its colour [H*W, C] as fp32 on the device"""

@@ -20,7 +20,7 @@ class _nerf_field(Function):
 
     @staticmethod
     @custom_fwd(device_type="cuda")
-    def forward(ctx, x, dirs, embeddings, sigma_weights, color_weights, enc, sigma_shadow, color_shadow, bound, density_scale, plan=None):
+    def forward(ctx, x, dirs, embeddings, sigma_weights, color_weights, enc, sigma_shadow, color_shadow, bound, density_scale, plan=None, grad_x=None):
         _nerf_field.calls += 1
         M = x.shape[0]
         L = enc.num_levels
@@ -45,6 +45,7 @@ class _nerf_field(Function):
         ctx.enc, ctx.shadows, ctx.in_map, ctx.geom = enc, shadows, in_map, (M, L, S, H)
         ctx.density_scale = density_scale
         ctx.plan = plan
+        ctx.grad_x = grad_x
         ctx.wdtypes = (sigma_weights.dtype, color_weights.dtype)
         return sigmas, rgbs
 
@@ -79,9 +80,15 @@ class _nerf_field(Function):
                                  accumulate=ctx.shadows is not None, weights_nonfinite_flag=wflag, in_map=ctx.in_map,
                                  offsets_host=enc.offsets_host, plan=ctx.plan, table_nonfinite_flag=flag, touched_lines=touched,
                                  grad_dirty=dirty)
-        return (None, None, None if enc.shadow is not None else grad_table,
+        gx = None
+        if ctx.grad_x is not None or ctx.needs_input_grad[0]:
+            # d loss / d x from the feature gradients the call above left in grad_feats: the cells are recomputed, no dy_dx buffer
+            gx = ctx.grad_x if ctx.grad_x is not None else torch.empty_like(x)
+            _grid.grid_input_grad(x, table, enc.offsets, grad_feats, gx, M, 3, 2, L, S, H, enc.gridtype_id, enc.align_corners,
+                                  enc.interp_id, in_map=ctx.in_map)
+        return (gx if ctx.needs_input_grad[0] else None, None, None if enc.shadow is not None else grad_table,
                 None if ctx.shadows is not None else gws.to(ctx.wdtypes[0]),
-                None if ctx.shadows is not None else gwc.to(ctx.wdtypes[1]), None, None, None, None, None, None)
+                None if ctx.shadows is not None else gwc.to(ctx.wdtypes[1]), None, None, None, None, None, None, None)
 
 
 def _weights_flag(shadows):
@@ -99,14 +106,22 @@ def field_supported(enc, sigma_net, color_net):
             and sigma_net.weights.numel() == SIGMA_NET_PARAMS and color_net.weights.numel() == COLOR_NET_PARAMS)
 
 
-def nerf_field(x, dirs, enc, sigma_net, color_net, bound=1, density_scale=1.0, plan=None):
+def nerf_field(x, dirs, enc, sigma_net, color_net, bound=1, density_scale=1.0, plan=None, grad_x=None):
     """x [M,3] in [-bound, bound], dirs [M,3] unit -> sigmas [M] fp32, rgbs [M,3] fp32 (fp16 table and MLPs; M % 16 == 0).
     plan: `field_backward_plan(x, enc, bound)` computed earlier (positions only) -- the table-gradient pass then skips
-    its counting half."""
+    its counting half.
+    grad_x: an fp32 [M,3] buffer the backward overwrites with d loss / d x (`lae_grid_input_grad`: through the hash grid only, not
+    through the view direction) -- the pose refinement reads it; an x that requires grad receives the same gradient from autograd.
+    Linear interpolation only."""
+    if grad_x is not None:
+        if grad_x.dtype != torch.float32 or not grad_x.is_contiguous() or tuple(grad_x.shape) != (x.shape[0], 3) or grad_x.device != x.device:
+            raise RuntimeError("nerf_field: grad_x must be a contiguous float32 [M, 3] tensor on the samples' device")
+    if (grad_x is not None or x.requires_grad) and enc.interp_id != 0:
+        raise RuntimeError("nerf_field: the input gradient is implemented for linear interpolation only")
     if x.shape[0] % 16 != 0:
         raise RuntimeError("nerf_field: the number of samples must be a multiple of 16")
     return _nerf_field.apply(x, dirs, enc.embeddings, sigma_net.weights, color_net.weights, enc, sigma_net.shadow,
-                             color_net.shadow, float(bound), float(density_scale), plan)
+                             color_net.shadow, float(bound), float(density_scale), plan, grad_x)
 
 
 @torch.no_grad()

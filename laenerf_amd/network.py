@@ -50,8 +50,14 @@ class NeRFNetwork(nn.Module):
             return None
         return field_backward_plan(x.view(-1, 3), self.encoder, self.bound)
 
-    def forward(self, x, d, plan=None):
-        """x [N,3] in [-bound,bound], d [N,3] unit -> sigma [N] fp32, rgb [N,3]   (network_ff.py:51-81)"""
+    def forward(self, x, d, plan=None, grad_x=None):
+        """x [N,3] in [-bound,bound], d [N,3] unit -> sigma [N] fp32, rgb [N,3]   (network_ff.py:51-81)
+        grad_x (MI355X-native, fused field op only): an fp32 [N,3] buffer the backward overwrites with d loss / d x through the hash
+        grid (field.nerf_field); with it an x that requires grad also receives that gradient from autograd"""
+        if grad_x is not None:
+            if not (self._field_ok(x.detach(), d)):
+                raise RuntimeError("NeRFNetwork: grad_x needs the fused field op (hash grid, fp16 autocast, a multiple of 16 samples on the GPU)")
+            return nerf_field(x.view(-1, 3), d, self.encoder, self.sigma_net, self.color_net, self.bound, plan=plan, grad_x=grad_x)
         if self._field_ok(x, d):
             # encoder + head as one op: features stay level-major between the grid and MLP kernels (field.py)
             return nerf_field(x.view(-1, 3), d, self.encoder, self.sigma_net, self.color_net, self.bound, plan=plan)

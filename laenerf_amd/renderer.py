@@ -344,7 +344,7 @@ class NeRFRenderer(nn.Module):
 
     def shade_train(self, marched, bg_color=1, T_thresh=1e-4, gt=None, scaler=None, depth=None, depth_inds=None, depth_weight=0.0,
                     depth_grad=True, distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None,
-                    opacity_grad=True, pixel_weights=None, pixel_inds=None, second_target=None, second_weight=0.0):
+                    opacity_grad=True, pixel_weights=None, pixel_inds=None, second_target=None, second_weight=0.0, grad_x=None):
         """second half: network on the samples, compositing, background blend, depth normalisation (renderer.py:313-334).
         gt [N,3] (optional, MI355X-native): also evaluate the trainer's criterion MSE(image, gt) (scaled by `scaler`'s
         loss scale) inside the compositing op -> result["loss"]; call loss.backward() on it.
@@ -359,7 +359,9 @@ class NeRFRenderer(nn.Module):
         pixel_weights / pixel_inds / second_target / second_weight (with gt and loss='mse' only): the per-pixel weights and the second
         colour target of the same function (`lae_composite_rays_train_step_weighted`); None leaves the call as it was.  Without
         fused_post_ops the same criterion, mean((w (image - gt))^2) + second_weight * mean(((1 - w / 2) (t - image))^2), is written
-        with torch operators."""
+        with torch operators.
+        grad_x: an fp32 [M,3] buffer the backward overwrites with the loss's gradient with respect to the sample positions (through the
+        hash grid; NeRFNetwork.forward) -- what the Trainer's pose refinement reduces per camera; None leaves the call as it was."""
         weighted = pixel_weights is not None or second_target is not None
         if weighted and gt is None:
             raise RuntimeError("shade_train: pixel weights and a second target need gt")
@@ -380,7 +382,10 @@ class NeRFRenderer(nn.Module):
             dist_kw.update(pixel_weights=pixel_weights, pixel_inds=pixel_inds, second_target=second_target, second_weight=second_weight)
         xyzs, dirs, deltas, rays, nears, fars = marched[:6]
         plan = marched[6] if len(marched) > 6 else None
-        sigmas, rgbs = self.model(xyzs, dirs, plan=plan) if plan is not None else self.model(xyzs, dirs)
+        if grad_x is not None:
+            sigmas, rgbs = self.model(xyzs, dirs, plan=plan, grad_x=grad_x)
+        else:
+            sigmas, rgbs = self.model(xyzs, dirs, plan=plan) if plan is not None else self.model(xyzs, dirs)
         if self.density_scale != 1:
             sigmas = self.density_scale * sigmas
         loss = None

@@ -48,6 +48,15 @@ pixel_weights=True (with a weight plane on the data, ResidentImages.pixel_weight
 confidence-weighted training in general -- inside the same kernel, which gathers both planes by the batch's pixel indices, and the same
 captured groups, alone or with the depth, distortion and opacity terms.  MSE only, and not with error_map='ema': the reference's
 rule would put the weighted loss into the map, and nothing in the reference does that.
+
+pose_refine=True refines the training cameras by gradient descent inside the same captured groups (Instant-NGP's extrinsics
+optimisation; the reference takes its poses as exact).  After the backward, `lae_grid_input_grad` turns the feature gradients the field
+backward left into the gradient of the sample positions (the cells are recomputed: no dy_dx buffer), `lae_pose_ray_grad` reduces it per
+ray to (sum g, sum (x - o) x g) in fp64 and, after the optimizer's step, `lae_pose_step` adds the rays of every image, takes a sparse
+Adam step per image in the world-frame tangent space (skipped with the optimizer's step, divided by its loss scale) and composes it onto
+an fp64 master, R <- Exp(dw) R, T <- T + dt, from which the fp32 poses the next batch is built from are rewritten
+(ResidentImages.enable_pose_refinement; laenerf_amd/poses.py restates the three kernels).  pose_lr follows the network's decay table.
+Not part of the gradient: the view direction, nears / fars and the occupancy decisions of the march.
 """
 import contextlib
 import copy
@@ -148,13 +157,17 @@ class Trainer:
     second_weight: None (no second term) or the weight of the second colour target data.second_target (module docstring); with it
     losses() holds the total and second_losses() the per-step term without its weight, finished like the others.  Both need
     loss='mse' and are refused with error_map='ema' (ValueError).
+    pose_refine: False (every path as it is, bit for bit) or True: the training cameras are refined with learning rate pose_lr (decayed
+    like lr; pose_betas / pose_eps are its Adam's) inside the same groups (module docstring); refined_poses() and pose_deltas() report
+    them, a checkpoint carries their state (the data's entry), pose_lr=0 leaves the run's losses and parameters bit for bit as without it.
+    Needs the renderer's fused_post_ops and the fused field op (ValueError); combines with every other term.
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
     def __init__(self, renderer, optimizer, data, iters, lr, num_rays=4096, seed=0, graph=True, capacity="bucket",
                  max_steps=1024, dt_gamma=0.0, error_map=None, ema_decay=None, epoch_len=None, depth_weight=None, depth_grad=True,
                  distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True,
-                 pixel_weights=False, second_weight=None):
+                 pixel_weights=False, second_weight=None, pose_refine=False, pose_lr=1e-3, pose_betas=(0.9, 0.99), pose_eps=1e-15):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
         if error_map not in (None, "ema", "fixed"):
@@ -166,6 +179,13 @@ class Trainer:
                 raise ValueError("Trainer: pixel_weights / second_weight need loss='mse' (the reference has no weighted L1 / Huber / MAPE)")
             if error_map == "ema":
                 raise ValueError("Trainer: pixel_weights / second_weight cannot be combined with error_map='ema'")
+        if pose_refine:                                               # refused before anything is changed on the data
+            if not renderer.fused_post_ops:
+                raise ValueError("Trainer: pose_refine needs the renderer's fused_post_ops")
+            if not getattr(renderer.model, "fused_field", False) or renderer.model.encoder.interp_id != 0:
+                raise ValueError("Trainer: pose_refine needs the fused field op (hash grid with linear interpolation, fused heads)")
+            if not (float(pose_lr) >= 0.0) or float(pose_lr) == float("inf"):
+                raise ValueError("Trainer: pose_lr must be finite and >= 0")
         if error_map is not None and data.error_map is None:
             data.enable_error_map()
         self.r, self.opt, self.data = renderer, optimizer, data
@@ -224,6 +244,13 @@ class Trainer:
         self._opacity_hist = []
         self.second_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.second_weight is not None else None
         self._second_hist = []
+        self.pose_refine, self.pose_lr = bool(pose_refine), float(pose_lr)
+        self.pose_betas, self.pose_eps = (float(pose_betas[0]), float(pose_betas[1])), float(pose_eps)
+        if self.pose_refine:
+            data.enable_pose_refinement()
+            self.pose_lr_table = torch.from_numpy(lr_schedule(self.pose_lr, self.iters, self.iters + 1, 1)).to(dev)
+            self.pose_lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+            self._pose_ray_grads = torch.zeros(self.num_rays, 6, dtype=torch.float64, device=dev)
         self.global_step = 0
         self.started = False
         self.graphs = {}
@@ -252,6 +279,8 @@ class Trainer:
         with torch.no_grad():
             row = torch.clamp(self.data.step, max=self.iters)
             opt.lrs.copy_(self.lr_table.index_select(0, row).view(-1))
+            if self.pose_refine:
+                self.pose_lr_dev.copy_(self.pose_lr_table.index_select(0, row).view(-1))
         b = self.data.sample(self.num_rays)
         counter = r.step_counter[r.local_step % GROUP]
         counter.zero_()
@@ -275,6 +304,9 @@ class Trainer:
                 dist_kw.update(pixel_weights=self.data.pixel_weights if self.pixel_weights else None, pixel_inds=b["inds"],
                                second_target=self.data.second_target if self.second_weight is not None else None,
                                second_weight=0.0 if self.second_weight is None else self.second_weight)
+            grad_x = None
+            if self.pose_refine:
+                grad_x = dist_kw["grad_x"] = torch.empty(xyzs.shape, dtype=torch.float32, device=xyzs.device)
             if self.depth_weight is None:
                 res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt, **dist_kw)
             else:
@@ -293,7 +325,11 @@ class Trainer:
         if self.second_weight is not None:
             raymarching.finish_second_loss(loss, out=self.second_slots[k])
         opt.backward(loss)
+        if self.pose_refine:                                           # grad_x holds d (scaled loss) / d xyzs now
+            self.data.pose_ray_grad(rays, xyzs, grad_x, b["rays_o"], out=self._pose_ray_grads)
         opt.step()
+        if self.pose_refine:                                           # after the step: its skip decision and 1 / scale are in the state words
+            self.data.pose_step(self._pose_ray_grads, b["inds"], opt.dev_state, self.pose_lr_dev, self.pose_betas, self.pose_eps)
         if self.ema is not None:
             self.ema.update_gated(self.data.step, self.epoch_len)      # sample() has advanced the counter to this step's index
         with torch.no_grad():
@@ -400,6 +436,20 @@ class Trainer:
             return np.zeros(0, np.float32)
         return torch.cat(self._second_hist).cpu().numpy()
 
+    def refined_poses(self):
+        """the training cameras as the next batch reads them, [n_img, 4, 4] fp32 on the device (a copy; data.poses without pose_refine)"""
+        d = self.data
+        return (d.poses if d.train_poses is None else d.train_poses).clone()
+
+    def pose_deltas(self):
+        """(rotation angle in radians [n_img], translation distance [n_img]) of the refined cameras against data.poses, as float64
+        numpy arrays (from the fp64 master with pose_refine; zeros without)"""
+        from .poses import pose_error
+        d = self.data
+        ref = d.poses.detach().cpu().numpy().astype(np.float64)
+        cur = ref if d.pose_master is None else d.pose_master.detach().cpu().numpy().reshape(d.n_img, 3, 4)
+        return pose_error(cur, ref)
+
     @property
     def steps_skipped(self):
         """optimizer steps the GradScaler skipped (non-finite gradients)"""
@@ -431,6 +481,9 @@ class Trainer:
             cfg["pixel_weights"] = True
         if self.second_weight is not None:
             cfg["second_weight"] = self.second_weight
+        if self.pose_refine:
+            cfg["pose_refine"], cfg["pose_lr"] = True, self.pose_lr
+            cfg["pose_betas"], cfg["pose_eps"] = list(self.pose_betas), self.pose_eps
         return cfg
 
     def state_dict(self, full=True):

@@ -7,7 +7,7 @@ refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated o
 
     python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed] [--ema] [--depth] [--distort W]
                                 [--loss mse|l1|huber|mape] [--huber-delta D] [--entropy W] [--outliers P]
-                                [--mask-outliers P]
+                                [--mask-outliers P] [--pose-noise DEG,DIST] [--pose-lr LR]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
 ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR.
@@ -26,6 +26,11 @@ is what the robust criterion buys.
 --mask-outliers P: --outliers P with a weight plane that is 0 on the overwritten pixels and 1 elsewhere (Trainer(pixel_weights=True)): the
 outliers cannot matter, and the held-out PSNR is that of the clean pixels alone.  Compare ms/step with a run without the option for
 the cost of the weighted step.
+--pose-noise DEG,DIST: every training camera (never the held-out ones) is rotated by DEG degrees about a random axis through its origin
+and moved by DIST in a random direction before training, the pose error of a real capture.  --pose-lr LR: the student refines its
+cameras (Trainer(pose_refine=True, pose_lr=LR)).  With either the line carries "pose": the mean rotation (degrees) and translation
+error of the training cameras against the true ones before and after the run; compare heldout_psnr_white with and without --pose-lr
+for what the refinement buys, and breakdown.replay_ms_per_step for its cost.
 --save PATH: the first student's checkpoint is written after the run (Trainer.save_checkpoint; a `.pth` path or a directory);
 --resume PATH: the first student loads it before training and then trains --steps further steps (the same --steps as the saved run
 keeps the learning-rate horizon, which the load checks).  The line then carries "checkpoint": the file size in bytes and the save /
@@ -99,7 +104,7 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
 
 def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=True, capacity="bucket", seed=0, student_seed=0,
                  error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True, distort_weight=None, loss="mse",
-                 huber_delta=0.1, opacity_weight=None, pixel_weights=None):
+                 huber_delta=0.1, opacity_weight=None, pixel_weights=None, pose_lr=None):
     from laenerf_amd.data import ResidentImages
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.optim import FusedAdam
@@ -117,6 +122,8 @@ def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=Tr
         depth_kw.update(loss=loss, huber_delta=huber_delta, opacity_weight=opacity_weight)
     if pixel_weights is not None:
         depth_kw["pixel_weights"] = True
+    if pose_lr is not None:
+        depth_kw.update(pose_refine=True, pose_lr=pose_lr)
     return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map,
                    ema_decay=ema_decay, **depth_kw)
 
@@ -168,6 +175,8 @@ def main():
     ap.add_argument("--entropy", type=float, default=None, metavar="W", help="Trainer(opacity_weight=W) for every student of the run")
     ap.add_argument("--outliers", type=float, default=0.0, metavar="P", help="share of training pixels overwritten with random colours")
     ap.add_argument("--mask-outliers", type=float, default=0.0, metavar="P", help="--outliers P with weight 0 on the overwritten pixels")
+    ap.add_argument("--pose-noise", default=None, metavar="DEG,DIST", help="perturb every training camera by DEG degrees and DIST")
+    ap.add_argument("--pose-lr", type=float, default=None, metavar="LR", help="Trainer(pose_refine=True, pose_lr=LR)")
     ap.add_argument("--save", default=None, metavar="PATH", help="write the first student's checkpoint after the run")
     ap.add_argument("--resume", default=None, metavar="PATH", help="load a checkpoint into the first student before training")
     args = ap.parse_args()
@@ -189,7 +198,13 @@ def main():
         images[held:][hit] = noise[hit]
         if args.mask_outliers > 0:
             mask = np.where(hit, 0.0, 1.0).astype(np.float16)
-    crit_kw = dict(loss=args.loss, huber_delta=args.huber_delta, opacity_weight=args.entropy, pixel_weights=mask)
+    crit_kw = dict(loss=args.loss, huber_delta=args.huber_delta, opacity_weight=args.entropy, pixel_weights=mask, pose_lr=args.pose_lr)
+    true_poses = poses.copy()
+    if args.pose_noise:
+        from laenerf_amd.poses import perturb_poses
+        deg, dist = (float(v) for v in args.pose_noise.split(","))
+        poses = poses.copy()
+        poses[held:] = perturb_poses(poses[held:], deg, dist, seed=23)
     tr = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
                       capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, distort_weight=args.distort,
                       **crit_kw)
@@ -208,6 +223,14 @@ def main():
     from laenerf_amd.data import ResidentImages
     test = ResidentImages.from_arrays(images[:held], poses[:held], intr, device=dev)
     p = tr.evaluate(range(held), data=test, bg_color=1.0)
+    pose = None
+    if args.pose_noise or args.pose_lr is not None:
+        from laenerf_amd.poses import pose_error
+        a0, d0 = pose_error(poses[held:], true_poses[held:])
+        a1, d1 = pose_error(tr.refined_poses().cpu().numpy(), true_poses[held:])
+        pose = {"noise": args.pose_noise, "pose_lr": args.pose_lr, "start_rotation_deg": round(float(np.rad2deg(a0.mean())), 5),
+                "end_rotation_deg": round(float(np.rad2deg(a1.mean())), 5), "start_translation": round(float(d0.mean()), 6),
+                "end_translation": round(float(d1.mean()), 6)}
     # where the time goes (after the measurement; each part synchronised on its own): the refresh with its host read, a
     # 16-step replay at the current capacity, and the padding rows of that capacity
     refresh_ms, group_ms = _replay_windows(tr)
@@ -247,6 +270,7 @@ def main():
                         "final_opacity_loss": float(tr.opacity_losses()[-16:].mean())}} if args.entropy is not None else {}),
         **({"outliers": args.outliers} if args.outliers > 0 else {}),
         **({"mask_outliers": args.mask_outliers, "masked_pixels_frac": round(float((mask == 0).mean()), 4)} if mask is not None else {}),
+        **({"pose": pose} if pose is not None else {}),
         **({"depth": depth} if depth is not None else {}), **({"checkpoint": ckpt} if ckpt else {}),
         "scene": f"{args.views - held} training + {held} held-out {args.res}x{args.res} RGBA uint8 views of a teacher network"}), flush=True)
 
