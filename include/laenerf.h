@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi24"
+#define LAE_ABI_TAG "abi25"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -161,6 +161,24 @@ LAE_API int lae_sample_train_batch_weighted(const void* images, int dtype, uint3
                                     const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int bg_mode,
                                     int srgb_to_linear, const float* error_map, int32_t* cells_out, float* rays_o, float* rays_d,
                                     float* nears, float* fars, float* gt, float* bg_out, int64_t* inds, void* stream);
+/* The two samplers with a per-image, per-channel gain on the target colour (exposure and white balance, see lae_exposure_step):
+ * gains fp32 [n_img,3] is read, fg fp32 [N,3] is one more output.  In the shared per-ray body, after the optional srgb_to_linear and
+ * before the blend, every operation one fp32 rounding in this order (v_c the texel, a the alpha, bg_c the background):
+ *     s_c = v_c * gains[img][c];   C == 4: fg_c = s_c * a, gt_c = fg_c + bg_c * (1 - a);   C == 3: fg_c = gt_c = s_c.
+ * fg is the part of the target that scales with the gain (the background does not).  A gain of exactly 1.0f gives the gt of the entry
+ * point without a gain bit for bit; rays, nears / fars, bg_out, inds, cells_out and the step protocol are those entry points'.
+ * LAE_ENULL additionally: gains or fg NULL. */
+LAE_API int lae_sample_train_batch_gain(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                                        const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
+                                        const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int mode, int bg_mode,
+                                        int srgb_to_linear, const float* gains, float* rays_o, float* rays_d, float* nears, float* fars,
+                                        float* gt, float* fg, float* bg_out, int64_t* inds, void* stream);
+LAE_API int lae_sample_train_batch_weighted_gain(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                                                 const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
+                                                 const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int bg_mode,
+                                                 int srgb_to_linear, const float* error_map, int32_t* cells_out, const float* gains,
+                                                 float* rays_o, float* rays_d, float* nears, float* fars, float* gt, float* fg,
+                                                 float* bg_out, int64_t* inds, void* stream);
 
 /* The error map's EMA after a step (nerf/utils.py:609-631), one thread per ray: image = inds[n] / (H * W),
  * d = pred[n] - gt[n], err = ((d0 * d0 + d1 * d1) + d2 * d2) / 3, map[image][cells[n]] = 0.1 * old + 0.9 * err (fp32, each
@@ -1346,6 +1364,32 @@ LAE_API int lae_pose_ray_grad(const int32_t* rays, const float* xyzs, const floa
 LAE_API int lae_pose_step(const double* ray_grads, const int64_t* inds, uint32_t N, uint64_t hw, uint32_t n_img, double* master,
                           double* m, double* v, int32_t* counts, float* train_poses, const int32_t* opt_state, const float* lr,
                           double beta1, double beta2, double eps, void* stream);
+
+/* ---- per-image exposure and white balance (csrc/exposure.hip; laenerf_amd/exposure.py restates both kernels in float64)
+ *
+ * Image i carries a log2 gain e[i][c] per colour channel; the *_gain samplers multiply the target colour by
+ * gains[i][c] = 2^(e[i][c] - mean_i e[.][c]).  Every colour criterion is a function of pred - gt (MAPE's denominator is detached), so
+ * d loss / d gt = -d loss / d pred and, with d gt / d e = ln 2 * fg,
+ *     G[i][c] = -(ln 2 / (3 N)) * sum over the rays n with inds[n] / hw == i of  w_n^2 * dv(pred_nc - gt_nc) * fg_nc.
+ * lae_exposure_step, one launch, one workgroup per image: (a) the sum in fp64 and in a fixed order (thread t of 1024 adds its rays
+ * t, t + 1024, ... in order, then the partial sums are added as a fixed tree).  pred (the step's image), gt and fg (the sampler's) fp32
+ * [N,3]; dv the element derivative of loss_kind (LAE_LOSS_*, loss_param Huber's delta) on the fp32 residual e = pred - gt, with one
+ * difference: a NaN residual gives a NaN dv under every criterion (sign(NaN) = 0 must not hide it); w_n = weights[inds[n]] (a plane of
+ * weights_dtype LAE_IMG_F16 / LAE_IMG_F32, [n_img * hw]) or 1 with weights NULL; N is the divisor of the fused step's mean.  The gradient
+ * is analytic: no loss scale enters.  gray != 0: the three components are replaced by (G0 + G1) + G2 (one exposure per image, three
+ * equal columns).  (b) a sparse Adam step per image: count += 1, m = beta1 m + (1 - beta1) G, v = beta2 v + (1 - beta2) G^2,
+ * delta = -(lr / (1 - beta1^count)) * m / (sqrt(v) / sqrt(1 - beta2^count) + eps), torch.optim.Adam's formulas in fp64 with the image's
+ * own count, lr = *lr (a float in device memory).  An image without a ray in the batch is not touched at all; with opt_state[3] (the
+ * main optimizer's skip word) non-zero nothing is touched; an image whose G is not finite is skipped on its own.  (c) e <- e + delta on
+ * the fp64 master [n_img,3] (a zero delta leaves the bits alone).  m, v double [n_img,3]; counts int32 [n_img].
+ * lae_exposure_publish, one workgroup: mean_c = (sum over the images of master[i][c], fp64, fixed order) / n_img, or 0 with center == 0;
+ * gains[i][c] = (float)exp2(master[i][c] - mean_c).  The master is not re-centred (the moments stay consistent with it) and the gradient
+ * ignores the -1/n coupling through the mean: the centring is a projection after the step.  A master of zeros publishes exactly 1.0f. */
+LAE_API int lae_exposure_step(const float* pred, const float* gt, const float* fg, const int64_t* inds, uint32_t N, uint64_t hw,
+                              uint32_t n_img, const void* weights, int weights_dtype, int loss_kind, float loss_param, int gray,
+                              double* master, double* m, double* v, int32_t* counts, const int32_t* opt_state, const float* lr,
+                              double beta1, double beta2, double eps, void* stream);
+LAE_API int lae_exposure_publish(const double* master, uint32_t n_img, int center, float* gains, void* stream);
 
 /* MI355X-native: 0 (default) = fused backward (activations recomputed in registers, forward_buffer /
  * backward_buffer untouched: both are scratch the reference's Python never reads), every wave accumulating all dW tiles

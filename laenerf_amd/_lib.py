@@ -33,6 +33,12 @@ SIGNATURES = {
                                vp, vp, vp],
     "lae_sample_train_batch_weighted": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, vp, f32, u64, vp, i32, i32, vp, vp,
                                         vp, vp, vp, vp, vp, vp, vp, vp],
+    "lae_sample_train_batch_gain": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, vp, f32, u64, vp, i32, i32, i32, vp, vp, vp,
+                                    vp, vp, vp, vp, vp, vp, vp],
+    "lae_sample_train_batch_weighted_gain": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, vp, f32, u64, vp, i32, i32, vp,
+                                             vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "lae_exposure_step": [vp, vp, vp, vp, u32, u64, u32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, f64, f64, f64, vp],
+    "lae_exposure_publish": [vp, u32, i32, vp, vp],
     "lae_error_map_update": [vp, u32, u32, u32, vp, vp, vp, vp, u32, vp],
     "lae_error_map_update_crit": [vp, u32, u32, u32, vp, vp, vp, vp, u32, i32, f32, vp],
     "lae_composite_rays_train_forward": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, vp],
@@ -187,7 +193,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi24"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi25"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

@@ -7,6 +7,10 @@
 // and blends; the step is read from device memory and advanced by a second one-thread launch, so a captured graph
 // draws a fresh batch on every replay.
 //
+// The *_gain entry points (lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain) multiply the colour by a per-image,
+// per-channel gain before the blend and also write fg, the part of the target that scales with it: the exposure refinement of
+// exposure.hip.  They are the same kernels instantiated with GAIN = true; the entry points without a gain compile without the multiply.
+//
 // Compiled with -ffp-contract=off like every file of the library: the blend is rgb * a + bg * (1 - a) with three
 // roundings, in the reference's order.
 #include "lae_common.h"
@@ -46,13 +50,16 @@ __device__ __forceinline__ float texel(const void* __restrict__ images, size_t e
 }
 
 // the per-ray body shared by both samplers: ray and near / far of pixel `pix` of image `img`, the texel gather, the
-// background draw (words 2..4 of ray n) and the blend
-template <int DT>
+// background draw (words 2..4 of ray n) and the blend.  GAIN (the *_gain entry points): the colour is multiplied by the image's
+// gain before the blend, one rounding, and fg receives the part of the target that scales with it (the background does not); a
+// gain of 1.0f gives the bits of GAIN = false, whose instantiations hold no multiply
+template <int DT, bool GAIN>
 __device__ __forceinline__ void batch_ray(
     const void* __restrict__ images, uint64_t HW, uint32_t W, uint32_t C, const float* __restrict__ poses, float fx, float fy,
     float cx, float cy, const float* __restrict__ aabb, float min_near, const BatchRng& rng, uint32_t n, uint32_t img, uint32_t pix,
     int bg_mode, int linear, float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears,
-    float* __restrict__ fars, float* __restrict__ gt, float* __restrict__ bg_out, int64_t* __restrict__ inds) {
+    float* __restrict__ fars, float* __restrict__ gt, float* __restrict__ bg_out, int64_t* __restrict__ inds,
+    const float* __restrict__ gains, float* __restrict__ fg) {
     inds[n] = (int64_t)img * (int64_t)HW + pix;
 
     float o[3], d[3];
@@ -67,6 +74,7 @@ __device__ __forceinline__ void batch_ray(
     for (int c = 0; c < 3; c++) {
         rgb[c] = texel<DT>(images, e + c);
         if (linear) rgb[c] = srgb_to_linear(rgb[c]);
+        if constexpr (GAIN) rgb[c] = __fmul_rn(rgb[c], gains[3 * (size_t)img + c]);
     }
     float bg[3] = {1.f, 1.f, 1.f};
     if (bg_mode == LAE_BG_RANDOM) {
@@ -80,27 +88,35 @@ __device__ __forceinline__ void batch_ray(
         const float a = texel<DT>(images, e + 3);
         const float one_minus_a = __fsub_rn(1.0f, a);
 #pragma unroll
-        for (int c = 0; c < 3; c++) rgb[c] = __fadd_rn(__fmul_rn(rgb[c], a), __fmul_rn(bg[c], one_minus_a));
+        for (int c = 0; c < 3; c++) {
+            const float f = __fmul_rn(rgb[c], a);
+            if constexpr (GAIN) fg[3 * (size_t)n + c] = f;
+            rgb[c] = __fadd_rn(f, __fmul_rn(bg[c], one_minus_a));
+        }
+    } else if constexpr (GAIN) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) fg[3 * (size_t)n + c] = rgb[c];
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) gt[3 * (size_t)n + c] = rgb[c];
 }
 
-template <int DT>
+template <int DT, bool GAIN>
 __global__ __launch_bounds__(256) void k_sample_train_batch(
     const void* __restrict__ images, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
     const float* __restrict__ poses, float fx, float fy, float cx, float cy, uint32_t N, const float* __restrict__ aabb,
     float min_near, uint32_t k0, uint32_t k1, const int64_t* __restrict__ step_counter, int mode, int bg_mode, int linear,
     float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears, float* __restrict__ fars,
-    float* __restrict__ gt, float* __restrict__ bg_out, int64_t* __restrict__ inds) {
+    float* __restrict__ gt, float* __restrict__ bg_out, int64_t* __restrict__ inds, const float* __restrict__ gains,
+    float* __restrict__ fg) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     const BatchRng rng{(uint32_t)(uint64_t)step_counter[0], k0, k1};
     const uint64_t HW = (uint64_t)H * W;
     const uint32_t pix = scale_u32(rng.u(n, 0), HW);                                 // < H * W
     const uint32_t img = scale_u32(rng.u(mode == LAE_BATCH_IMAGE ? 0xFFFFFFFFu : n, 1), n_img);   // < n_img
-    batch_ray<DT>(images, HW, W, C, poses, fx, fy, cx, cy, aabb, min_near, rng, n, img, pix, bg_mode, linear, rays_o, rays_d,
-                  nears, fars, gt, bg_out, inds);
+    batch_ray<DT, GAIN>(images, HW, W, C, poses, fx, fy, cx, cy, aabb, min_near, rng, n, img, pix, bg_mode, linear, rays_o, rays_d,
+                        nears, fars, gt, bg_out, inds, gains, fg);
 }
 
 // ---------------------------------------------------------------- the weighted draw (lae_sample_train_batch_weighted)
@@ -218,14 +234,14 @@ __global__ __launch_bounds__(SEL_THREADS) void k_select_cells(
 }
 
 // one thread per ray: the pixel drawn inside its cell, then the uniform sampler's per-ray body
-template <int DT>
+template <int DT, bool GAIN>
 __global__ __launch_bounds__(256) void k_sample_train_batch_weighted(
     const void* __restrict__ images, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
     const float* __restrict__ poses, float fx, float fy, float cx, float cy, uint32_t N, const float* __restrict__ aabb,
     float min_near, uint32_t k0, uint32_t k1, const int64_t* __restrict__ step_counter, int bg_mode, int linear,
     float sx, float sy, const int32_t* __restrict__ cells, float* __restrict__ rays_o, float* __restrict__ rays_d,
     float* __restrict__ nears, float* __restrict__ fars, float* __restrict__ gt, float* __restrict__ bg_out,
-    int64_t* __restrict__ inds) {
+    int64_t* __restrict__ inds, const float* __restrict__ gains, float* __restrict__ fg) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     const BatchRng rng{(uint32_t)(uint64_t)step_counter[0], k0, k1};
@@ -236,8 +252,8 @@ __global__ __launch_bounds__(256) void k_sample_train_batch_weighted(
     const float fr = __fadd_rn(__fmul_rn((float)(c / EM_SIDE), sx), __fmul_rn(rx, sx));
     const float fc = __fadd_rn(__fmul_rn((float)(c % EM_SIDE), sy), __fmul_rn(ry, sy));
     const uint32_t r = min((uint32_t)fr, H - 1), col = min((uint32_t)fc, W - 1);    // trunc of a value >= 0
-    batch_ray<DT>(images, HW, W, C, poses, fx, fy, cx, cy, aabb, min_near, rng, n, img, r * W + col, bg_mode, linear, rays_o,
-                  rays_d, nears, fars, gt, bg_out, inds);
+    batch_ray<DT, GAIN>(images, HW, W, C, poses, fx, fy, cx, cy, aabb, min_near, rng, n, img, r * W + col, bg_mode, linear, rays_o,
+                        rays_d, nears, fars, gt, bg_out, inds, gains, fg);
 }
 
 // one thread per ray: map[image][cell] = 0.1 * map + 0.9 * mean over RGB of (pred - gt)^2
@@ -283,15 +299,12 @@ __global__ __launch_bounds__(256) void k_error_map_update_crit(
 
 __global__ void k_advance_step(int64_t* __restrict__ step_counter) { step_counter[0] += 1; }
 
-}  // namespace
-
-extern "C" {
-
-int lae_sample_train_batch(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
-                           const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
-                           const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int mode, int bg_mode,
-                           int srgb_to_linear, float* rays_o, float* rays_d, float* nears, float* fars, float* gt,
-                           float* bg_out, int64_t* inds, void* stream) {
+// the bodies of the sampler entry points; GAIN: the *_gain siblings (gains [n_img,3] read, fg [N,3] written)
+template <bool GAIN>
+int sample_uniform(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C, const float* poses, float fx,
+                   float fy, float cx, float cy, uint32_t N, const float* aabb, float min_near, uint64_t seed, int64_t* step_counter,
+                   int mode, int bg_mode, int srgb_to_linear, const float* gains, float* rays_o, float* rays_d, float* nears,
+                   float* fars, float* gt, float* fg, float* bg_out, int64_t* inds, void* stream) {
     if (N == 0) return LAE_OK;
     if (!images || !poses || !aabb || !step_counter || !rays_o || !rays_d || !nears || !fars || !gt || !inds) return LAE_ENULL;
     if (bg_mode == LAE_BG_RANDOM && !bg_out) return LAE_ENULL;
@@ -303,20 +316,20 @@ int lae_sample_train_batch(const void* images, int dtype, uint32_t n_img, uint32
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     const dim3 grid(lae::cdiv(N, 256)), block(256);
 #define LAE_BATCH_ARGS images, n_img, H, W, C, poses, fx, fy, cx, cy, N, aabb, min_near, k0, k1, step_counter, mode, bg_mode, \
-                       srgb_to_linear, rays_o, rays_d, nears, fars, gt, bg_out, inds
-    if (dtype == LAE_IMG_U8) k_sample_train_batch<LAE_IMG_U8><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
-    else if (dtype == LAE_IMG_F16) k_sample_train_batch<LAE_IMG_F16><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
-    else k_sample_train_batch<LAE_IMG_F32><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+                       srgb_to_linear, rays_o, rays_d, nears, fars, gt, bg_out, inds, gains, fg
+    if (dtype == LAE_IMG_U8) k_sample_train_batch<LAE_IMG_U8, GAIN><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+    else if (dtype == LAE_IMG_F16) k_sample_train_batch<LAE_IMG_F16, GAIN><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+    else k_sample_train_batch<LAE_IMG_F32, GAIN><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
 #undef LAE_BATCH_ARGS
     k_advance_step<<<1, 1, 0, s>>>(step_counter);
     return lae::check_launch("sample_train_batch");
 }
 
-int lae_sample_train_batch_weighted(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
-                                    const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
-                                    const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int bg_mode,
-                                    int srgb_to_linear, const float* error_map, int32_t* cells_out, float* rays_o, float* rays_d,
-                                    float* nears, float* fars, float* gt, float* bg_out, int64_t* inds, void* stream) {
+template <bool GAIN>
+int sample_weighted(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C, const float* poses, float fx,
+                    float fy, float cx, float cy, uint32_t N, const float* aabb, float min_near, uint64_t seed, int64_t* step_counter,
+                    int bg_mode, int srgb_to_linear, const float* error_map, int32_t* cells_out, const float* gains, float* rays_o,
+                    float* rays_d, float* nears, float* fars, float* gt, float* fg, float* bg_out, int64_t* inds, void* stream) {
     if (N == 0) return LAE_OK;
     if (!images || !poses || !aabb || !step_counter || !error_map || !cells_out || !rays_o || !rays_d || !nears || !fars || !gt ||
         !inds) return LAE_ENULL;
@@ -331,13 +344,57 @@ int lae_sample_train_batch_weighted(const void* images, int dtype, uint32_t n_im
     k_select_cells<<<1, SEL_THREADS, 0, s>>>(error_map, n_img, N, k0, k1, step_counter, cells_out);
     const dim3 grid(lae::cdiv(N, 256)), block(256);
 #define LAE_BATCH_ARGS images, n_img, H, W, C, poses, fx, fy, cx, cy, N, aabb, min_near, k0, k1, step_counter, bg_mode, \
-                       srgb_to_linear, sx, sy, cells_out, rays_o, rays_d, nears, fars, gt, bg_out, inds
-    if (dtype == LAE_IMG_U8) k_sample_train_batch_weighted<LAE_IMG_U8><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
-    else if (dtype == LAE_IMG_F16) k_sample_train_batch_weighted<LAE_IMG_F16><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
-    else k_sample_train_batch_weighted<LAE_IMG_F32><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+                       srgb_to_linear, sx, sy, cells_out, rays_o, rays_d, nears, fars, gt, bg_out, inds, gains, fg
+    if (dtype == LAE_IMG_U8) k_sample_train_batch_weighted<LAE_IMG_U8, GAIN><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+    else if (dtype == LAE_IMG_F16) k_sample_train_batch_weighted<LAE_IMG_F16, GAIN><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+    else k_sample_train_batch_weighted<LAE_IMG_F32, GAIN><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
 #undef LAE_BATCH_ARGS
     k_advance_step<<<1, 1, 0, s>>>(step_counter);
     return lae::check_launch("sample_train_batch_weighted");
+}
+
+}  // namespace
+
+extern "C" {
+
+int lae_sample_train_batch(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                           const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
+                           const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int mode, int bg_mode,
+                           int srgb_to_linear, float* rays_o, float* rays_d, float* nears, float* fars, float* gt,
+                           float* bg_out, int64_t* inds, void* stream) {
+    return sample_uniform<false>(images, dtype, n_img, H, W, C, poses, fx, fy, cx, cy, N, aabb, min_near, seed, step_counter, mode, bg_mode,
+                                 srgb_to_linear, nullptr, rays_o, rays_d, nears, fars, gt, nullptr, bg_out, inds, stream);
+}
+
+int lae_sample_train_batch_gain(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                                const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
+                                const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int mode, int bg_mode,
+                                int srgb_to_linear, const float* gains, float* rays_o, float* rays_d, float* nears, float* fars,
+                                float* gt, float* fg, float* bg_out, int64_t* inds, void* stream) {
+    if (N > 0 && (!gains || !fg)) return LAE_ENULL;
+    return sample_uniform<true>(images, dtype, n_img, H, W, C, poses, fx, fy, cx, cy, N, aabb, min_near, seed, step_counter, mode, bg_mode,
+                                srgb_to_linear, gains, rays_o, rays_d, nears, fars, gt, fg, bg_out, inds, stream);
+}
+
+int lae_sample_train_batch_weighted(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                                    const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
+                                    const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int bg_mode,
+                                    int srgb_to_linear, const float* error_map, int32_t* cells_out, float* rays_o, float* rays_d,
+                                    float* nears, float* fars, float* gt, float* bg_out, int64_t* inds, void* stream) {
+    return sample_weighted<false>(images, dtype, n_img, H, W, C, poses, fx, fy, cx, cy, N, aabb, min_near, seed, step_counter, bg_mode,
+                                  srgb_to_linear, error_map, cells_out, nullptr, rays_o, rays_d, nears, fars, gt, nullptr, bg_out, inds,
+                                  stream);
+}
+
+int lae_sample_train_batch_weighted_gain(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                                         const float* poses, float fx, float fy, float cx, float cy, uint32_t N,
+                                         const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int bg_mode,
+                                         int srgb_to_linear, const float* error_map, int32_t* cells_out, const float* gains,
+                                         float* rays_o, float* rays_d, float* nears, float* fars, float* gt, float* fg, float* bg_out,
+                                         int64_t* inds, void* stream) {
+    if (N > 0 && (!gains || !fg)) return LAE_ENULL;
+    return sample_weighted<true>(images, dtype, n_img, H, W, C, poses, fx, fy, cx, cy, N, aabb, min_near, seed, step_counter, bg_mode,
+                                 srgb_to_linear, error_map, cells_out, gains, rays_o, rays_d, nears, fars, gt, fg, bg_out, inds, stream);
 }
 
 int lae_error_map_update(float* error_map, uint32_t n_img, uint32_t H, uint32_t W, const int64_t* inds, const int32_t* cells,

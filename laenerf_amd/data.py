@@ -15,6 +15,10 @@ With an error map (`error_map=True` / `enable_error_map`: the reference's --erro
 pixels of a batch are drawn by 128 x 128 cell weights per image (`lae_sample_train_batch_weighted`: torch.multinomial's
 without-replacement algorithm, then a uniform pixel inside each cell), and `update_error_map` writes the per-ray error back
 (`lae_error_map_update`).  `draw_cells`, `cell_pixels` and `ema_update` restate both rules in numpy.
+
+After `enable_exposure_refinement()` the batch's targets are multiplied by a per-image, per-channel gain before the blend
+(`lae_sample_train_batch_gain` / `_weighted_gain`) and `exposure_step` learns those gains from the step's image (csrc/exposure.hip;
+laenerf_amd/exposure.py restates it).
 """
 import json
 import math
@@ -237,6 +241,8 @@ class ResidentImages:
         if depths is not None:
             self.set_depths(depths)
         self.train_poses = self.pose_master = self.pose_m = self.pose_v = self.pose_counts = None      # enable_pose_refinement
+        self.gains = self.exposure_master = self.exposure_m = self.exposure_v = self.exposure_counts = None   # enable_exposure_refinement
+        self.exposure_mode = None
         self.pixel_weights = self.second_target = None
         if pixel_weights is not None:
             self.set_pixel_weights(pixel_weights)
@@ -345,6 +351,67 @@ class ResidentImages:
                                         ptr(self.pose_v), ptr(self.pose_counts), ptr(self.train_poses), ptr(opt_state), ptr(lr),
                                         float(betas[0]), float(betas[1]), float(eps), stream()), "pose_step")
 
+    def enable_exposure_refinement(self, mode="rgb"):
+        """create the state of the exposure / white-balance refinement (Trainer(exposure_refine=True)): a log2 gain per image and colour
+        channel as .exposure_master fp64 [n_img, 3], its sparse Adam's .exposure_m / .exposure_v fp64 [n_img, 3] and .exposure_counts
+        int32 [n_img], and .gains fp32 [n_img, 3], all ones.  From then on sample() multiplies the target colour by the image's gains
+        before the blend (`lae_sample_train_batch_gain` / `_weighted_gain`) and also returns fg [N,3], the part of gt that scales with
+        them.  mode 'rgb': three gains per image; 'gray': one exposure per image (three equal columns).  A second call changes only the
+        mode.  Gains are a physical exposure when training in linear colour, a per-image colour compensation on sRGB data."""
+        from .exposure import MODES
+        if mode not in MODES:
+            raise ValueError(f"ResidentImages: exposure mode must be one of {sorted(MODES)}")
+        if self.gains is None:
+            dev = self.images.device
+            self.exposure_master = torch.zeros(self.n_img, 3, dtype=torch.float64, device=dev)
+            self.exposure_m = torch.zeros(self.n_img, 3, dtype=torch.float64, device=dev)
+            self.exposure_v = torch.zeros(self.n_img, 3, dtype=torch.float64, device=dev)
+            self.exposure_counts = torch.zeros(self.n_img, dtype=torch.int32, device=dev)
+            self.gains = torch.ones(self.n_img, 3, dtype=torch.float32, device=dev)
+            self._out = {}                                                    # the batch buffers gain an fg
+        self.exposure_mode = mode
+        return self.gains
+
+    @torch.no_grad()
+    def exposure_step(self, pred, batch, opt_state, lr, loss="mse", huber_delta=0.1, pixel_weights=None, betas=(0.9, 0.99), eps=1e-15,
+                      center=True):
+        """lae_exposure_step + lae_exposure_publish: the gradient of the step's colour criterion with respect to every image's log2
+        gains from pred [N,3] (the step's image) and the batch's gt / fg / inds, one sparse Adam step per image that received a ray on
+        .exposure_master, then .gains = 2^(master - mean over the images) (center=False: 2^master).  opt_state: the main optimizer's
+        16 device state words (its skip decision); lr: a float32 tensor on the device; loss / huber_delta: the criterion the step
+        trained on; pixel_weights: the weight plane the step used ([n_img, H, W], fp16 or fp32) or None
+        (exposure.exposure_step_numpy / exposure_publish_numpy)"""
+        if self.gains is None:
+            raise ValueError("ResidentImages.exposure_step: enable_exposure_refinement() first")
+        from .backend import loss_kind
+        from .exposure import MODES
+        kind, param = loss_kind("ResidentImages.exposure_step", loss, huber_delta)
+        gt, fg, inds = batch["gt"], batch["fg"], batch["inds"]
+        n = int(inds.shape[0])
+        pred = pred.detach().reshape(-1, 3)
+        if pred.dtype != torch.float32 or not pred.is_contiguous():
+            pred = pred.float().contiguous()
+        if pred.shape[0] != n or tuple(gt.shape) != (n, 3) or tuple(fg.shape) != (n, 3):
+            raise ValueError("ResidentImages.exposure_step: pred, gt and fg must be [N, 3] for the batch's N rays")
+        ts = (pred, gt, fg, inds, opt_state, lr)
+        _lib.need_cuda(*ts); _lib.need_contig(*ts)
+        if gt.dtype != torch.float32 or fg.dtype != torch.float32 or inds.dtype != torch.int64:
+            raise RuntimeError("exposure_step: gt and fg must be float32, inds int64")
+        if opt_state.dtype != torch.int32 or opt_state.numel() != 16 or lr.dtype != torch.float32 or lr.numel() < 1:
+            raise RuntimeError("exposure_step: opt_state must be the optimizer's 16 int32 words, lr a float32 tensor")
+        w = pixel_weights
+        if w is not None:
+            _lib.need_cuda(w); _lib.need_contig(w)
+            if w.dtype not in (torch.float16, torch.float32) or w.numel() != self.n_img * self.H * self.W:
+                raise RuntimeError("exposure_step: pixel_weights must be an fp16 / fp32 plane [n_img, H, W]")
+        lib = _lib.load()
+        check(lib.lae_exposure_step(ptr(pred), ptr(gt), ptr(fg), ptr(inds), n, self.H * self.W, self.n_img, ptr(w),
+                                    0 if w is None else _DTYPES[w.dtype], kind, param, MODES[self.exposure_mode], ptr(self.exposure_master),
+                                    ptr(self.exposure_m), ptr(self.exposure_v), ptr(self.exposure_counts), ptr(opt_state), ptr(lr),
+                                    float(betas[0]), float(betas[1]), float(eps), stream()), "exposure_step")
+        check(lib.lae_exposure_publish(ptr(self.exposure_master), self.n_img, int(bool(center)), ptr(self.gains), stream()),
+              "exposure_publish")
+
     @classmethod
     def from_arrays(cls, images, poses, intrinsics, **kw):
         return cls(images, poses, intrinsics, **kw)
@@ -414,6 +481,8 @@ class ResidentImages:
             }
             if self.error_map is not None:
                 out["cells"] = torch.empty(n, dtype=torch.int32, device=dev)
+            if self.gains is not None:
+                out["fg"] = torch.empty(n, 3, dtype=torch.float32, device=dev)
         return out
 
     @torch.no_grad()
@@ -429,11 +498,17 @@ class ResidentImages:
             self.step.fill_(int(step))
         o = out if out is not None else self._buffers(int(n_rays))
         fx, fy, cx, cy = self.intrinsics
-        check(_lib.load().lae_sample_train_batch(
-            ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self._sample_poses()), fx, fy, cx, cy,
-            int(n_rays), ptr(self.aabb), self.min_near, self.seed, ptr(self.step), _MODES[self.mode], _BGS[self.bg],
-            int(self.color_space == "linear"), ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]),
-            ptr(o["bg"]), ptr(o["inds"]), stream()), "sample_train_batch")
+        head = (ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self._sample_poses()), fx, fy, cx, cy,
+                int(n_rays), ptr(self.aabb), self.min_near, self.seed, ptr(self.step), _MODES[self.mode], _BGS[self.bg],
+                int(self.color_space == "linear"))
+        if self.gains is not None:
+            check(_lib.load().lae_sample_train_batch_gain(
+                *head, ptr(self.gains), ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]), ptr(o["fg"]),
+                ptr(o["bg"]), ptr(o["inds"]), stream()), "sample_train_batch_gain")
+        else:
+            check(_lib.load().lae_sample_train_batch(
+                *head, ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]), ptr(o["bg"]), ptr(o["inds"]),
+                stream()), "sample_train_batch")
         res = dict(o)
         if res["bg"] is None:
             res["bg"] = 1
@@ -458,11 +533,17 @@ class ResidentImages:
             self.step.fill_(int(step))
         o = out if out is not None else self._buffers(int(n_rays))
         fx, fy, cx, cy = self.intrinsics
-        check(_lib.load().lae_sample_train_batch_weighted(
-            ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self._sample_poses()), fx, fy, cx, cy,
-            int(n_rays), ptr(self.aabb), self.min_near, self.seed, ptr(self.step), _BGS[self.bg], int(self.color_space == "linear"),
-            ptr(self.error_map), ptr(o["cells"]), ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]),
-            ptr(o["bg"]), ptr(o["inds"]), stream()), "sample_train_batch_weighted")
+        head = (ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self._sample_poses()), fx, fy, cx, cy,
+                int(n_rays), ptr(self.aabb), self.min_near, self.seed, ptr(self.step), _BGS[self.bg], int(self.color_space == "linear"),
+                ptr(self.error_map), ptr(o["cells"]))
+        if self.gains is not None:
+            check(_lib.load().lae_sample_train_batch_weighted_gain(
+                *head, ptr(self.gains), ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]), ptr(o["fg"]),
+                ptr(o["bg"]), ptr(o["inds"]), stream()), "sample_train_batch_weighted_gain")
+        else:
+            check(_lib.load().lae_sample_train_batch_weighted(
+                *head, ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]), ptr(o["bg"]), ptr(o["inds"]),
+                stream()), "sample_train_batch_weighted")
         res = dict(o)
         if res["bg"] is None:
             res["bg"] = 1
@@ -491,12 +572,16 @@ class ResidentImages:
 
     def state_dict(self):
         """what a resumed run needs of the sampler, never the images: seed (int), step (the device counter, int64 [1], on the host)
-        and error_map (a host copy, or None)"""
+        and error_map (a host copy, or None); with pose or exposure refinement enabled also `pose` / `exposure`, their state"""
         sd = {"seed": int(self.seed), "step": self.step.detach().cpu().clone(),
               "error_map": None if self.error_map is None else self.error_map.detach().cpu().clone()}
         if self.train_poses is not None:             # the refinement's state (only with it: files of other runs stay as they were)
             sd["pose"] = {"master": self.pose_master.detach().cpu().clone(), "m": self.pose_m.detach().cpu().clone(),
                           "v": self.pose_v.detach().cpu().clone(), "counts": self.pose_counts.detach().cpu().clone()}
+        if self.gains is not None:                   # likewise the exposure refinement's (the gains as published: center is the trainer's)
+            sd["exposure"] = {"master": self.exposure_master.detach().cpu().clone(), "m": self.exposure_m.detach().cpu().clone(),
+                              "v": self.exposure_v.detach().cpu().clone(), "counts": self.exposure_counts.detach().cpu().clone(),
+                              "gains": self.gains.detach().cpu().clone()}
         return sd
 
     def check_state_dict(self, sd):
@@ -516,6 +601,13 @@ class ResidentImages:
                 t = ps.get(k) if isinstance(ps, dict) else None
                 if not torch.is_tensor(t) or tuple(t.shape) != shape:
                     bad.append(f"data.pose.{k}: saved {list(t.shape) if torch.is_tensor(t) else type(t).__name__}, current {list(shape)}")
+        ex = sd.get("exposure")
+        if ex is not None:
+            want = {"master": (self.n_img, 3), "m": (self.n_img, 3), "v": (self.n_img, 3), "counts": (self.n_img,), "gains": (self.n_img, 3)}
+            for k, shape in want.items():
+                t = ex.get(k) if isinstance(ex, dict) else None
+                if not torch.is_tensor(t) or tuple(t.shape) != shape:
+                    bad.append(f"data.exposure.{k}: saved {list(t.shape) if torch.is_tensor(t) else type(t).__name__}, current {list(shape)}")
         return bad
 
     @torch.no_grad()
@@ -542,6 +634,16 @@ class ResidentImages:
             self.pose_counts.copy_(ps["counts"].to(dev, torch.int32))
             # the kernel's own conversion (round to nearest); the bottom row stays the input's
             self.train_poses[:, :3, :4].copy_(self.pose_master.view(self.n_img, 3, 4).to(torch.float32))
+        ex = sd.get("exposure")
+        if ex is not None:
+            if self.gains is None:
+                self.enable_exposure_refinement()
+            dev = self.gains.device
+            self.exposure_master.copy_(ex["master"].to(dev, torch.float64))
+            self.exposure_m.copy_(ex["m"].to(dev, torch.float64))
+            self.exposure_v.copy_(ex["v"].to(dev, torch.float64))
+            self.exposure_counts.copy_(ex["counts"].to(dev, torch.int32))
+            self.gains.copy_(ex["gains"].to(dev, torch.float32))
 
     def view_rays(self, i):
         """every pixel of image i (scanline order) -> rays_o, rays_d [H*W, 3] and its colour [H*W, C] as fp32 on the device"""

@@ -57,6 +57,16 @@ Adam step per image in the world-frame tangent space (skipped with the optimizer
 an fp64 master, R <- Exp(dw) R, T <- T + dt, from which the fp32 poses the next batch is built from are rewritten
 (ResidentImages.enable_pose_refinement; laenerf_amd/poses.py restates the three kernels).  pose_lr follows the network's decay table.
 Not part of the gradient: the view direction, nears / fars and the occupancy decisions of the march.
+
+exposure_refine=True learns a log2 gain per training image and colour channel -- exposure and white balance, Instant-NGP's per-image
+exposure; the reference takes every image as shot alike -- inside the same captured groups.  The gain multiplies the TARGET colour in
+the sampler (`lae_sample_train_batch_gain`), so the compositing kernels are untouched; every criterion is a function of pred - gt, hence
+d loss / d gt = -d loss / d pred, which `lae_exposure_step` recomputes per ray from the step's image and the batch's gt, reduces per image
+in fp64 and a fixed order and feeds to a sparse Adam step on an fp64 master (skipped with the optimizer's step); `lae_exposure_publish`
+rewrites the fp32 gains the next batch reads as 2^(e - mean over the images): the mean fixes the gauge (a common gain is a brighter
+scene), the master is not re-centred, and the -1/n coupling through the mean is left out of the gradient -- a projection after the step
+(ResidentImages.enable_exposure_refinement; laenerf_amd/exposure.py restates both kernels).  exposure_lr follows the network's decay
+table.  Gains are a physical exposure only on color_space='linear' data; on sRGB data they are a per-image colour compensation.
 """
 import contextlib
 import copy
@@ -161,13 +171,20 @@ class Trainer:
     like lr; pose_betas / pose_eps are its Adam's) inside the same groups (module docstring); refined_poses() and pose_deltas() report
     them, a checkpoint carries their state (the data's entry), pose_lr=0 leaves the run's losses and parameters bit for bit as without it.
     Needs the renderer's fused_post_ops and the fused field op (ValueError); combines with every other term.
+    exposure_refine: False (every path as it is, bit for bit) or True: a log2 gain per training image and channel is learned with learning
+    rate exposure_lr (default 1e-2, measured against 1e-3: DESIGN.md 4g; decayed like lr; exposure_betas / exposure_eps are its
+    Adam's; exposure_mode 'rgb' or 'gray': three gains or one per image; exposure_center: publish 2^(e - mean) rather than 2^e) inside the same groups (module docstring); exposures() and gains()
+    report them, a checkpoint carries their state (the data's entry), exposure_lr=0 leaves the run's losses and parameters bit for bit
+    as without it.  Combines with every other term but second_weight, whose second target is synthetic and is not gained (ValueError).
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
     def __init__(self, renderer, optimizer, data, iters, lr, num_rays=4096, seed=0, graph=True, capacity="bucket",
                  max_steps=1024, dt_gamma=0.0, error_map=None, ema_decay=None, epoch_len=None, depth_weight=None, depth_grad=True,
                  distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True,
-                 pixel_weights=False, second_weight=None, pose_refine=False, pose_lr=1e-3, pose_betas=(0.9, 0.99), pose_eps=1e-15):
+                 pixel_weights=False, second_weight=None, pose_refine=False, pose_lr=1e-3, pose_betas=(0.9, 0.99), pose_eps=1e-15,
+                 exposure_refine=False, exposure_lr=1e-2, exposure_mode="rgb", exposure_betas=(0.9, 0.99), exposure_eps=1e-15,
+                 exposure_center=True):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
         if error_map not in (None, "ema", "fixed"):
@@ -186,6 +203,14 @@ class Trainer:
                 raise ValueError("Trainer: pose_refine needs the fused field op (hash grid with linear interpolation, fused heads)")
             if not (float(pose_lr) >= 0.0) or float(pose_lr) == float("inf"):
                 raise ValueError("Trainer: pose_lr must be finite and >= 0")
+        if exposure_refine:                                           # refused before anything is changed on the data
+            from .exposure import MODES
+            if second_weight is not None:
+                raise ValueError("Trainer: exposure_refine cannot be combined with second_weight (the second target is not gained)")
+            if not (float(exposure_lr) >= 0.0) or float(exposure_lr) == float("inf"):
+                raise ValueError("Trainer: exposure_lr must be finite and >= 0")
+            if exposure_mode not in MODES:
+                raise ValueError(f"Trainer: exposure_mode must be one of {sorted(MODES)}")
         if error_map is not None and data.error_map is None:
             data.enable_error_map()
         self.r, self.opt, self.data = renderer, optimizer, data
@@ -251,6 +276,13 @@ class Trainer:
             self.pose_lr_table = torch.from_numpy(lr_schedule(self.pose_lr, self.iters, self.iters + 1, 1)).to(dev)
             self.pose_lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
             self._pose_ray_grads = torch.zeros(self.num_rays, 6, dtype=torch.float64, device=dev)
+        self.exposure_refine, self.exposure_lr, self.exposure_mode = bool(exposure_refine), float(exposure_lr), exposure_mode
+        self.exposure_betas, self.exposure_eps = (float(exposure_betas[0]), float(exposure_betas[1])), float(exposure_eps)
+        self.exposure_center = bool(exposure_center)
+        if self.exposure_refine:
+            data.enable_exposure_refinement(exposure_mode)
+            self.exposure_lr_table = torch.from_numpy(lr_schedule(self.exposure_lr, self.iters, self.iters + 1, 1)).to(dev)
+            self.exposure_lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.global_step = 0
         self.started = False
         self.graphs = {}
@@ -281,6 +313,8 @@ class Trainer:
             opt.lrs.copy_(self.lr_table.index_select(0, row).view(-1))
             if self.pose_refine:
                 self.pose_lr_dev.copy_(self.pose_lr_table.index_select(0, row).view(-1))
+            if self.exposure_refine:
+                self.exposure_lr_dev.copy_(self.exposure_lr_table.index_select(0, row).view(-1))
         b = self.data.sample(self.num_rays)
         counter = r.step_counter[r.local_step % GROUP]
         counter.zero_()
@@ -330,6 +364,10 @@ class Trainer:
         opt.step()
         if self.pose_refine:                                           # after the step: its skip decision and 1 / scale are in the state words
             self.data.pose_step(self._pose_ray_grads, b["inds"], opt.dev_state, self.pose_lr_dev, self.pose_betas, self.pose_eps)
+        if self.exposure_refine:                                       # likewise after the step; the analytic gradient needs no 1 / scale
+            self.data.exposure_step(res["image"], b, opt.dev_state, self.exposure_lr_dev, loss=self.loss, huber_delta=self.huber_delta,
+                                    pixel_weights=self.data.pixel_weights if self.pixel_weights else None, betas=self.exposure_betas,
+                                    eps=self.exposure_eps, center=self.exposure_center)
         if self.ema is not None:
             self.ema.update_gated(self.data.step, self.epoch_len)      # sample() has advanced the counter to this step's index
         with torch.no_grad():
@@ -450,6 +488,20 @@ class Trainer:
         cur = ref if d.pose_master is None else d.pose_master.detach().cpu().numpy().reshape(d.n_img, 3, 4)
         return pose_error(cur, ref)
 
+    def exposures(self):
+        """the log2 gains of the training images as published, master - mean over the images (the master itself with
+        exposure_center=False), as a float64 numpy array [n_img, 3]; zeros without exposure_refine"""
+        d = self.data
+        if d.exposure_master is None:
+            return np.zeros((d.n_img, 3))
+        from .exposure import exposure_publish_numpy
+        return exposure_publish_numpy(d.exposure_master.detach().cpu().numpy(), center=self.exposure_center, full=True)[1]
+
+    def gains(self):
+        """the gains the next batch's targets are multiplied by, [n_img, 3] fp32 on the device (a copy; ones without exposure_refine)"""
+        d = self.data
+        return torch.ones(d.n_img, 3, dtype=torch.float32, device=d.images.device) if d.gains is None else d.gains.clone()
+
     @property
     def steps_skipped(self):
         """optimizer steps the GradScaler skipped (non-finite gradients)"""
@@ -484,6 +536,10 @@ class Trainer:
         if self.pose_refine:
             cfg["pose_refine"], cfg["pose_lr"] = True, self.pose_lr
             cfg["pose_betas"], cfg["pose_eps"] = list(self.pose_betas), self.pose_eps
+        if self.exposure_refine:
+            cfg["exposure_refine"], cfg["exposure_lr"], cfg["exposure_mode"] = True, self.exposure_lr, self.exposure_mode
+            cfg["exposure_betas"], cfg["exposure_eps"] = list(self.exposure_betas), self.exposure_eps
+            cfg["exposure_center"] = self.exposure_center
         return cfg
 
     def state_dict(self, full=True):

@@ -8,6 +8,7 @@ refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated o
     python tools/train_loop.py [--steps 1024] [--rays 4096] [--capacity bucket|exact] [--no-graph] [--error-map none|ema|fixed] [--ema] [--depth] [--distort W]
                                 [--loss mse|l1|huber|mape] [--huber-delta D] [--entropy W] [--outliers P]
                                 [--mask-outliers P] [--pose-noise DEG,DIST] [--pose-lr LR]
+                                [--exposure-noise STOPS] [--exposure-lr LR]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
 ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR.
@@ -31,6 +32,12 @@ and moved by DIST in a random direction before training, the pose error of a rea
 cameras (Trainer(pose_refine=True, pose_lr=LR)).  With either the line carries "pose": the mean rotation (degrees) and translation
 error of the training cameras against the true ones before and after the run; compare heldout_psnr_white with and without --pose-lr
 for what the refinement buys, and breakdown.replay_ms_per_step for its cost.
+--exposure-noise STOPS: the colour of every training image (never the held-out ones) is multiplied by 2^u, u uniform in [-STOPS, STOPS]
+and centred over the images (exposure.perturb_exposures; the images become float32, nothing clips): the auto-exposure of a hand-held
+capture.  --exposure-lr LR: the student learns a gain per image and channel (Trainer(exposure_refine=True, exposure_lr=LR)).  With
+either the line carries "exposure": the RMS of the training images' log2 exposure error before and after the run (after: learned +
+applied, 0 = compensated) and the time of the two launches per step; compare heldout_psnr_white with and without --exposure-lr for
+what the refinement buys, and breakdown.replay_ms_per_step for its cost.
 --save PATH: the first student's checkpoint is written after the run (Trainer.save_checkpoint; a `.pth` path or a directory);
 --resume PATH: the first student loads it before training and then trains --steps further steps (the same --steps as the saved run
 keeps the learning-rate horizon, which the load checks).  The line then carries "checkpoint": the file size in bytes and the save /
@@ -104,7 +111,7 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
 
 def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=True, capacity="bucket", seed=0, student_seed=0,
                  error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True, distort_weight=None, loss="mse",
-                 huber_delta=0.1, opacity_weight=None, pixel_weights=None, pose_lr=None):
+                 huber_delta=0.1, opacity_weight=None, pixel_weights=None, pose_lr=None, exposure_lr=None):
     from laenerf_amd.data import ResidentImages
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.optim import FusedAdam
@@ -124,6 +131,8 @@ def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=Tr
         depth_kw["pixel_weights"] = True
     if pose_lr is not None:
         depth_kw.update(pose_refine=True, pose_lr=pose_lr)
+    if exposure_lr is not None:
+        depth_kw.update(exposure_refine=True, exposure_lr=exposure_lr)
     return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map,
                    ema_decay=ema_decay, **depth_kw)
 
@@ -142,6 +151,22 @@ def _replay_windows(tr, n=5):
             tr.global_step += 16
             refresh_ms.append((b - a) * 1e3); group_ms.append((c - b) * 1e3 / 16)
     return refresh_ms, group_ms
+
+
+def _exposure_launch_us(tr, n=200):
+    """after a run: the time of lae_exposure_step + lae_exposure_publish on one batch, n calls between two events (the state moves on)"""
+    b = tr.data.sample(tr.num_rays)
+    pred = torch.zeros_like(b["gt"])
+    call = lambda: tr.data.exposure_step(pred, b, tr.opt.dev_state, tr.exposure_lr_dev, loss=tr.loss, huber_delta=tr.huber_delta)
+    for _ in range(10):
+        call()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / n
 
 
 def _timed_run(tr, steps):
@@ -177,6 +202,8 @@ def main():
     ap.add_argument("--mask-outliers", type=float, default=0.0, metavar="P", help="--outliers P with weight 0 on the overwritten pixels")
     ap.add_argument("--pose-noise", default=None, metavar="DEG,DIST", help="perturb every training camera by DEG degrees and DIST")
     ap.add_argument("--pose-lr", type=float, default=None, metavar="LR", help="Trainer(pose_refine=True, pose_lr=LR)")
+    ap.add_argument("--exposure-noise", type=float, default=None, metavar="STOPS", help="multiply every training image by 2^u, |u| <= STOPS")
+    ap.add_argument("--exposure-lr", type=float, default=None, metavar="LR", help="Trainer(exposure_refine=True, exposure_lr=LR)")
     ap.add_argument("--save", default=None, metavar="PATH", help="write the first student's checkpoint after the run")
     ap.add_argument("--resume", default=None, metavar="PATH", help="load a checkpoint into the first student before training")
     args = ap.parse_args()
@@ -198,14 +225,19 @@ def main():
         images[held:][hit] = noise[hit]
         if args.mask_outliers > 0:
             mask = np.where(hit, 0.0, 1.0).astype(np.float16)
-    crit_kw = dict(loss=args.loss, huber_delta=args.huber_delta, opacity_weight=args.entropy, pixel_weights=mask, pose_lr=args.pose_lr)
+    crit_kw = dict(loss=args.loss, huber_delta=args.huber_delta, opacity_weight=args.entropy, pixel_weights=mask, pose_lr=args.pose_lr,
+                   exposure_lr=args.exposure_lr)
     true_poses = poses.copy()
     if args.pose_noise:
         from laenerf_amd.poses import perturb_poses
         deg, dist = (float(v) for v in args.pose_noise.split(","))
         poses = poses.copy()
         poses[held:] = perturb_poses(poses[held:], deg, dist, seed=23)
-    tr = make_trainer(dev, images[held:], poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
+    train_images, stops = images[held:], None
+    if args.exposure_noise:
+        from laenerf_amd.exposure import perturb_exposures
+        train_images, stops = perturb_exposures(images[held:], args.exposure_noise, seed=29)
+    tr = make_trainer(dev, train_images, poses[held:], intr, iters=args.steps, n_rays=args.rays, graph=not args.no_graph,
                       capacity=args.capacity, error_map=error_map, ema_decay=0.95 if args.ema else None, distort_weight=args.distort,
                       **crit_kw)
     ckpt = {}
@@ -231,9 +263,17 @@ def main():
         pose = {"noise": args.pose_noise, "pose_lr": args.pose_lr, "start_rotation_deg": round(float(np.rad2deg(a0.mean())), 5),
                 "end_rotation_deg": round(float(np.rad2deg(a1.mean())), 5), "start_translation": round(float(d0.mean()), 6),
                 "end_translation": round(float(d1.mean()), 6)}
+    exposure = None
+    if args.exposure_noise or args.exposure_lr is not None:
+        u = np.zeros((args.views - held, 3)) if stops is None else stops
+        rms = lambda a: round(float(np.sqrt(np.mean(a * a))), 5)
+        exposure = {"noise_stops": args.exposure_noise, "exposure_lr": args.exposure_lr, "start_rms_stops": rms(u),
+                    "end_rms_stops": rms(tr.exposures() + u)}
     # where the time goes (after the measurement; each part synchronised on its own): the refresh with its host read, a
     # 16-step replay at the current capacity, and the padding rows of that capacity
     refresh_ms, group_ms = _replay_windows(tr)
+    if exposure is not None and args.exposure_lr is not None:
+        exposure["step_and_publish_us"] = round(_exposure_launch_us(tr), 2)
     depth = None
     if args.depth:
         planes = teacher_depths(dev, poses[held:], intr, args.res, args.res)
@@ -270,7 +310,7 @@ def main():
                         "final_opacity_loss": float(tr.opacity_losses()[-16:].mean())}} if args.entropy is not None else {}),
         **({"outliers": args.outliers} if args.outliers > 0 else {}),
         **({"mask_outliers": args.mask_outliers, "masked_pixels_frac": round(float((mask == 0).mean()), 4)} if mask is not None else {}),
-        **({"pose": pose} if pose is not None else {}),
+        **({"pose": pose} if pose is not None else {}), **({"exposure": exposure} if exposure is not None else {}),
         **({"depth": depth} if depth is not None else {}), **({"checkpoint": ckpt} if ckpt else {}),
         "scene": f"{args.views - held} training + {held} held-out {args.res}x{args.res} RGBA uint8 views of a teacher network"}), flush=True)
 
