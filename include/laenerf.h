@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi25"
+#define LAE_ABI_TAG "abi26"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -1327,6 +1327,26 @@ LAE_API int lae_eval_view(const float* pred, const float* depth, const void* gt,
  * accumulated in fp64 with a fixed-order reduction.  scratch: n_pairs * sum_l ceil(hw[l] / 256) doubles. */
 LAE_API int lae_lpips_head(uint32_t n_layers, const float* const* feats, const float* const* weights, const uint32_t* channels,
                            const uint32_t* hw, uint32_t n_pairs, double* scratch, double* out, void* stream);
+#define LAE_CONSISTENCY_SCRATCH_DOUBLES 16384
+/* multi-view consistency of two rendered views (the reference's scripts/eval/consistency_metrics.py with the optical flow
+ * replaced by the reprojection through the views' own depth; the metric is written down above k_consistency_pair in
+ * csrc/evaluate.hip and in DESIGN.md section 4i).  a is the source view, b the target.  frame_a / frame_b [H*W,3] as stored
+ * (frame_dtype 0 uint8 = value / 255, 2 fp32; both frames of one dtype); depth_* the raw sum w t and opacity_* the weights_sum of
+ * render_eval(scale_depth=False), fp32 [H*W]; pose_* device fp32 [4,4] cam2world, row-major; one set of intrinsics; a pixel has
+ * geometry iff opacity >= min_opacity (> 0).  One gather pass, one lane per pixel of b; the flows are recomputed in registers.
+ *   sse_out / count_out  one double each: the sum over the valid pixels of sum_c (warped_c - frame_b_c)^2 (differences and sum in
+ *                   fp64) and the number of valid pixels; per-block partials in scratch (LAE_CONSISTENCY_SCRATCH_DOUBLES doubles)
+ *                   added in a fixed order, no atomics: two calls give the same bits.  count == 0 is a legal result (sse = 0);
+ *                   warp_mse = sse / count is the caller's division.
+ *   valid           optional uint8 [H*W]: 1 where the pixel counts
+ *   warped          optional fp32 [H*W,3]: frame a warped onto b, 0 where invalid
+ *   lpips_in        optional fp32 [2,3,H*W] planes with lae_eval_view's scaling: index 0 valid ? warped : frame_b, index 1 frame_b
+ * NULL inputs / slots: LAE_ENULL; another dtype, H or W < 2, H * W >= 2^31, fx, fy or min_opacity <= 0: LAE_EINVAL; both before
+ * any launch. */
+LAE_API int lae_consistency_pair(const void* frame_a, const void* frame_b, int frame_dtype, const float* depth_a, const float* opacity_a,
+                                 const float* depth_b, const float* opacity_b, const float* pose_a, const float* pose_b, float fx,
+                                 float fy, float cx, float cy, uint32_t H, uint32_t W, float min_opacity, double* scratch,
+                                 double* sse_out, double* count_out, uint8_t* valid, float* warped, float* lpips_in, void* stream);
 
 /* ---- training-camera pose refinement (csrc/gridencoder.hip, csrc/pose.hip; laenerf_amd/poses.py restates all three in float64)
  *

@@ -159,6 +159,7 @@ SIGNATURES = {
     "lae_ema_update_gated": [u32, vp, vp, vp, vp, i64, vp, f64, i32, vp],
     "lae_eval_view": [vp, vp, vp, i32, u32, u32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_lpips_head": [u32, vp, vp, vp, vp, u32, vp, vp, vp],
+    "lae_consistency_pair": [vp, vp, i32, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, u32, u32, f32, vp, vp, vp, vp, vp, vp, vp],
     "lae_adam_apply": [vp, vp, vp, vp, i32, vp, u64, vp, vp, f32, f32, f32, f32, vp],
     "lae_ffmlp_set_mode": [i32],
     "lae_allocate_splitk": [u64],
@@ -193,7 +194,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi25"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi26"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

@@ -9,15 +9,18 @@
 //                   five layers and a batch of pairs in one launch: one lane per pixel of one layer, a loop over the channels
 //                   (NCHW: every load coalesced across the wave), fp64 sums; per-block partials / (h w), k_lpips_finish sums a
 //                   pair's partials in a fixed order.
+//   k_consistency_pair  multi-view consistency of two rendered views (the metric is written down above the kernel): ONE gather pass
+//                   per pair, one lane per pixel of the target view, both flows recomputed in registers from the views' depth
+//                   and the two poses; per-block fp64 partials of the squared error and the valid count, summed by k_sum_partials.
 #include "lae_common.h"
+#include "raymarch_common.h"                 // pinhole_ray, STREAM
 #include <algorithm>
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 namespace {
 
 constexpr int EV_THREADS = 256;
 constexpr uint32_t EV_MAX_BLOCKS = LAE_EVAL_VIEW_SCRATCH_DOUBLES / 2;
+constexpr uint32_t CONS_MAX_BLOCKS = LAE_CONSISTENCY_SCRATCH_DOUBLES / 2;   // one lane per pixel up to 2 M pixels: no second trip through the gather chain at 1920 x 1080
 
 // `img.float() / 255` on the device: torch divides by a CPU scalar as a multiplication by its fp32 reciprocal
 // (div_true_kernel_cuda), which is what Trainer.evaluate's ground truth went through
@@ -240,6 +243,187 @@ __global__ __launch_bounds__(EV_THREADS) void k_lpips_head(LpipsArgs a, uint32_t
     if (threadIdx.x == 0) partials[(size_t)pair * blocks_per_pair + b] = s_red[0] / (double)hw;
 }
 
+// ---------------------------------------------------------------- multi-view consistency of a pair of rendered views
+// LAENeRF, ARF and Ref-NPR score a result without ground truth by its short- and long-range view consistency (the reference's
+// scripts/eval/consistency_metrics.py: frame i warped onto frame i + step by an optical flow, occlusions masked, the masked
+// squared error and the LPIPS of the warped frame against the target).  The script takes the flow from a RAFT network; here
+// the model that rendered the frames also rendered their depth and the cameras are known, so the flow is a reprojection.
+//
+// a is the source view and b the target view.  Each view v has a cam2world pose P_v = [R_v | T_v]; all views share the
+// intrinsics (fx, fy, cx, cy).  Each view has a frame F_v [H, W, 3], a depth D_v (the raw sum w t of
+// render_eval(scale_depth=False)) and an opacity A_v (weights_sum).
+//   Geometry     defined at pixel p = (x, y) of view v iff A_v[p] >= min_opacity (default 0.5, a choice: below one half the
+//                expected termination is not a surface).  Then t = D_v[p] / A_v[p] and X_v(p) = o + t d with (o, d) from
+//                pinhole_ray (pixel centre = index + 0.5, unit direction).
+//   Projection   proj_v(X): q = R_v^T (X - T_v), defined iff q.z > 0; (fx q.x / q.z + cx - 0.5, fy q.y / q.z + cy - 0.5), in
+//                pixel-index coordinates.
+//   Flows        fw(p) = proj_a(X_b(p)) - p for pixels p of b;  bw(r) = proj_b(X_a(r)) - r for pixels r of a.
+//   Landing      l = p + fw(p) must satisfy 0 <= l.x <= W-1 and 0 <= l.y <= H-1.  The taps are x0 = min(floor(l.x), W-2),
+//                y0 = min(floor(l.y), H-2) and the three neighbours; bw must be defined at all four.  bw~ and the warped colour
+//                Fw are the bilinear means of bw and F_a over those taps (cv2.INTER_LINEAR away from the border; the border
+//                case is invalid, not zero-filled).
+//   Occlusion    (detect_occlusion's constants) occluded iff |fw + bw~|^2 > 0.01 (|fw|^2 + |bw~|^2) + 0.5.
+//   Boundary     (compute_flow_gradients' constants) du = fw(x,y) - fw(x+1,y), 0 in the last column; dv = fw(x,y) - fw(x,y+1),
+//                0 in the last row; a neighbour whose fw is undefined makes the pixel invalid; on a motion boundary iff
+//                |du|^2 + |dv|^2 > 0.01 |fw|^2 + 0.002.
+//   Validity     valid(p) = everything above is defined and neither rule fires.
+//   Error        err(p) = sum_c (Fw_c - F_b(p)_c)^2;  sse = sum over valid of err, count = sum of valid;
+//                warp_mse = sse / count (the number the script prints as "RSME": it takes no root), formed by the caller.
+//   LPIPS input  [2, 3, H, W] with k_eval_view's scaling: index 0 is valid ? Fw : F_b(p), index 1 is F_b(p); invalid pixels
+//                contribute nothing.
+// Two deliberate departures from the script: it multiplies the error by the occlusion mask itself where the metric it follows
+// (Lai et al.) uses the complement, as here; and it feeds LPIPS the warped frame with remap's zero border where invalid pixels
+// are filled from the target here.
+// The flows are never stored: a lane recomputes fw at its pixel and the right and lower neighbours and bw at the four taps --
+// seven ray / projection evaluations against about 60 bytes of traffic per pixel.
+struct ConsIn {
+    const float *Da, *Aa, *Db, *Ab, *Pa, *Pb;
+    float fx, fy, cx, cy, min_opacity;
+    uint32_t H, W;
+};
+struct ConsOut {
+    double* scratch;             // [2 * CONS_MAX_BLOCKS]: per-block sse | count
+    uint8_t* valid;              // [HW] or NULL
+    float* warped;               // [HW,3] or NULL (0 where invalid)
+    float* lpips_in;             // [2,3,H,W] or NULL
+};
+
+// X_v(pix); false where the geometry is undefined
+__device__ __forceinline__ bool cons_point(const float* __restrict__ P, const float* __restrict__ D, const float* __restrict__ A,
+                                           const ConsIn& g, uint32_t pix, float X[3]) {
+    const float a = A[pix];
+    if (!(a >= g.min_opacity)) return false;
+    const float t = D[pix] / a;
+    float o[3], d[3];
+    pinhole_ray(P, g.fx, g.fy, g.cx, g.cy, g.W, (int64_t)pix, 0, 0.0f, 0.0f, o, d);
+#pragma unroll
+    for (int k = 0; k < 3; k++) X[k] = fmaf(t, d[k], o[k]);
+    return true;
+}
+
+// proj_v(X) in pixel-index coordinates; false where q.z <= 0 (or not a number)
+__device__ __forceinline__ bool cons_project(const float* __restrict__ P, const ConsIn& g, const float X[3], float& u, float& v) {
+    const float v0 = X[0] - P[3], v1 = X[1] - P[7], v2 = X[2] - P[11];
+    const float qx = fmaf(P[8], v2, fmaf(P[4], v1, P[0] * v0));
+    const float qy = fmaf(P[9], v2, fmaf(P[5], v1, P[1] * v0));
+    const float qz = fmaf(P[10], v2, fmaf(P[6], v1, P[2] * v0));
+    if (!(qz > 0.0f)) return false;
+    u = g.fx * qx / qz + g.cx - 0.5f;
+    v = g.fy * qy / qz + g.cy - 0.5f;
+    return true;
+}
+
+// where pixel `pix` of b lands in a: l = p + fw(p)
+__device__ __forceinline__ bool cons_land(const ConsIn& g, uint32_t pix, float& lx, float& ly) {
+    float X[3];
+    return cons_point(g.Pb, g.Db, g.Ab, g, pix, X) && cons_project(g.Pa, g, X, lx, ly);
+}
+
+template <typename T>
+__global__ __launch_bounds__(EV_THREADS) void k_consistency_pair(const T* __restrict__ Fa, const T* __restrict__ Fb, ConsIn g, ConsOut o) {
+    __shared__ double s_red[2][EV_THREADS];
+    const float shift[3] = {-0.030f, -0.088f, -0.188f};          // lpips ScalingLayer, as in k_eval_view
+    const float scale[3] = {0.458f, 0.448f, 0.450f};
+    const uint32_t HW = g.H * g.W;
+    double sse = 0.0, cnt = 0.0;
+    for (uint32_t p = blockIdx.x * EV_THREADS + threadIdx.x; p < HW; p += gridDim.x * EV_THREADS) {
+        const uint32_t x = p % g.W, y = p / g.W;
+        const float xf = (float)x, yf = (float)y;
+        float fb[3], fw_c[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int c = 0; c < 3; c++) fb[c] = to_f(Fb[(size_t)p * 3 + c]);
+        float lx = 0.0f, ly = 0.0f;
+        bool ok = cons_land(g, p, lx, ly);
+        ok = ok && lx >= 0.0f && lx <= (float)(g.W - 1) && ly >= 0.0f && ly <= (float)(g.H - 1);     // a NaN fails here
+        const float fwx = lx - xf, fwy = ly - yf;
+        float dux = 0.0f, duy = 0.0f, dvx = 0.0f, dvy = 0.0f;
+        if (ok && x + 1 < g.W) {                                 // motion boundary: the right and the lower neighbour's fw
+            float nx, ny;
+            ok = cons_land(g, p + 1, nx, ny);
+            if (ok) { dux = fwx - (nx - (xf + 1.0f)); duy = fwy - (ny - yf); }
+        }
+        if (ok && y + 1 < g.H) {
+            float nx, ny;
+            ok = cons_land(g, p + g.W, nx, ny);
+            if (ok) { dvx = fwx - (nx - xf); dvy = fwy - (ny - (yf + 1.0f)); }
+        }
+        if (ok) {
+            const float grad = (dux * dux + dvx * dvx) + (duy * duy + dvy * dvy);
+            const float mag = fwx * fwx + fwy * fwy;
+            ok = !(grad > 0.01f * mag + 0.002f);
+            if (ok) {
+                // 0 <= l <= W-1 / H-1 was checked above: x0 in [0, W-2], y0 in [0, H-2], all four taps inside the frame
+                const uint32_t x0 = min((uint32_t)floorf(lx), g.W - 2u), y0 = min((uint32_t)floorf(ly), g.H - 2u);
+                const float wx = lx - (float)x0, wy = ly - (float)y0;
+                float tap[4][5];                                 // per tap: bw.x, bw.y, F_a
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const uint32_t rx = x0 + (k & 1), ry = y0 + (k >> 1);
+                    const uint32_t r = ry * g.W + rx;
+                    float X[3], u = 0.0f, v = 0.0f;
+                    ok = ok && cons_point(g.Pa, g.Da, g.Aa, g, r, X) && cons_project(g.Pb, g, X, u, v);
+                    if (!ok) break;
+                    tap[k][0] = u - (float)rx;
+                    tap[k][1] = v - (float)ry;
+#pragma unroll
+                    for (int c = 0; c < 3; c++) tap[k][2 + c] = to_f(Fa[(size_t)r * 3 + c]);
+                }
+                if (ok) {
+                    // the bilinear mean as two lerps along x and one along y: a constant over the taps comes back as it is
+                    float m[5];
+#pragma unroll
+                    for (int c = 0; c < 5; c++) {
+                        const float top = fmaf(wx, tap[1][c] - tap[0][c], tap[0][c]);
+                        const float bot = fmaf(wx, tap[3][c] - tap[2][c], tap[2][c]);
+                        m[c] = fmaf(wy, bot - top, top);
+                    }
+                    const float bwx = m[0], bwy = m[1];
+#pragma unroll
+                    for (int c = 0; c < 3; c++) fw_c[c] = m[2 + c];
+                    const float sx = fwx + bwx, sy = fwy + bwy;
+                    ok = !(sx * sx + sy * sy > 0.01f * (mag + (bwx * bwx + bwy * bwy)) + 0.5f);
+                }
+            }
+        }
+        if (ok) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const double d = (double)fw_c[c] - (double)fb[c];
+                sse = fma(d, d, sse);
+            }
+            cnt += 1.0;
+        }
+        if (o.valid) o.valid[p] = ok ? 1 : 0;
+        if (o.warped) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) o.warped[(size_t)p * 3 + c] = ok ? fw_c[c] : 0.0f;
+        }
+        if (o.lpips_in) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float u = __fsub_rn(__fmul_rn(2.0f, ok ? fw_c[c] : fb[c]), 1.0f);
+                const float v = __fsub_rn(__fmul_rn(2.0f, fb[c]), 1.0f);
+                o.lpips_in[(size_t)c * HW + p] = __fdiv_rn(__fsub_rn(u, shift[c]), scale[c]);
+                o.lpips_in[(size_t)(3 + c) * HW + p] = __fdiv_rn(__fsub_rn(v, shift[c]), scale[c]);
+            }
+        }
+    }
+    s_red[0][threadIdx.x] = sse;
+    s_red[1][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int s = EV_THREADS / 2; s > 0; s >>= 1) {               // fixed-order tree
+        if ((int)threadIdx.x < s) {
+            s_red[0][threadIdx.x] += s_red[0][threadIdx.x + s];
+            s_red[1][threadIdx.x] += s_red[1][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        o.scratch[blockIdx.x] = s_red[0][0];
+        o.scratch[CONS_MAX_BLOCKS + blockIdx.x] = s_red[1][0];
+    }
+}
+
 template <typename T, int C>
 void launch_eval(bool vec, uint32_t blocks, const float* pred, const float* depth, const void* gt, uint32_t HW, float bg,
                  const uint8_t* mask, const EvalOut& o, hipStream_t s) {
@@ -302,6 +486,29 @@ int lae_lpips_head(uint32_t n_layers, const float* const* feats, const float* co
     if (rc != LAE_OK) return rc;
     k_sum_partials<<<n_pairs, EV_THREADS, 0, s>>>(scratch, nb, nb, out, nullptr);     // one block per pair
     return lae::check_launch("lpips_head_sum");
+}
+
+int lae_consistency_pair(const void* frame_a, const void* frame_b, int frame_dtype, const float* depth_a, const float* opacity_a,
+                         const float* depth_b, const float* opacity_b, const float* pose_a, const float* pose_b, float fx, float fy,
+                         float cx, float cy, uint32_t H, uint32_t W, float min_opacity, double* scratch, double* sse_out,
+                         double* count_out, uint8_t* valid, float* warped, float* lpips_in, void* stream) {
+    if (!frame_a || !frame_b || !depth_a || !opacity_a || !depth_b || !opacity_b || !pose_a || !pose_b || !scratch || !sse_out ||
+        !count_out) return LAE_ENULL;
+    if (frame_dtype != 0 && frame_dtype != 2) return LAE_EINVAL;                 // uint8 or fp32, lae_eval_view's codes
+    if (H < 2 || W < 2 || (uint64_t)H * W > 0x7fffffffull) return LAE_EINVAL;      // four taps need a 2 x 2 frame; 32-bit pixel index
+    if (!(fx > 0.0f) || !(fy > 0.0f) || !(min_opacity > 0.0f)) return LAE_EINVAL;  // t = D / A needs A > 0
+    const uint32_t HW = H * W;
+    const uint32_t blocks = std::min<uint32_t>(lae::cdiv(HW, EV_THREADS), CONS_MAX_BLOCKS);
+    hipStream_t s = STREAM(stream);
+    ConsIn g{depth_a, opacity_a, depth_b, opacity_b, pose_a, pose_b, fx, fy, cx, cy, min_opacity, H, W};
+    ConsOut o{scratch, valid, warped, lpips_in};
+    if (frame_dtype == 0) k_consistency_pair<uint8_t><<<blocks, EV_THREADS, 0, s>>>((const uint8_t*)frame_a, (const uint8_t*)frame_b, g, o);
+    else k_consistency_pair<float><<<blocks, EV_THREADS, 0, s>>>((const float*)frame_a, (const float*)frame_b, g, o);
+    int rc = lae::check_launch("consistency_pair");
+    if (rc != LAE_OK) return rc;
+    // row 0 of the partials -> sse_out, row 1 -> count_out; no pixel valid: both 0, the division is the caller's
+    k_sum_partials<<<2, EV_THREADS, 0, s>>>(scratch, blocks, CONS_MAX_BLOCKS, sse_out, count_out);
+    return lae::check_launch("consistency_pair_sum");
 }
 
 }  // extern "C"

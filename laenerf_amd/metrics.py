@@ -12,6 +12,11 @@ and a batch of view pairs is ONE launch (`lae_lpips_head`).
     lp = load_lpips_alex("alexnet-owt-7be5be79.pth", "alex.pth")     # torchvision trunk + the lpips package's v0.1 heads
     res = trainer.evaluate_one_epoch(test_data, lpips=lp, masks=load_masks("scene", "test"))
 
+A result without ground truth -- a recolored, stylized or distilled NeRF -- is scored by its view consistency instead (the
+reference's scripts/eval/consistency_metrics.py): `trainer.evaluate_consistency(test_data, step=1 | 7, frames=...)` warps frame i
+onto frame i + step through the model's own depth, ONE gather kernel per pair (`lae_consistency_pair`), and reports the masked
+squared error and the LPIPS of the warped frame against the target; `consistency_numpy` restates the kernel in float64.
+
 Nothing is downloaded: the weights come from files (or dicts) the user already has.  `LPIPS.random(seed)` builds seeded
 weights for tests and benchmarks.  Parity with the lpips package itself is pinned only by a restatement (tests/lpips_util.py):
 neither the package nor its pretrained weights were available to test against.
@@ -29,7 +34,7 @@ from . import _lib
 from ._lib import check, ptr, stream
 
 __all__ = ["LPIPS", "alexnet_trunk", "load_lpips_alex", "load_masks", "eval_view", "eval_view_numpy", "psnr_from_sse",
-           "ALEX_CHANNELS", "ALEX_TAPS", "LPIPS_SHIFT", "LPIPS_SCALE", "EVAL_SCRATCH_DOUBLES"]
+           "consistency_pair", "consistency_numpy", "ALEX_CHANNELS", "ALEX_TAPS", "LPIPS_SHIFT", "LPIPS_SCALE", "EVAL_SCRATCH_DOUBLES", "CONSISTENCY_SCRATCH_DOUBLES"]
 
 ALEX_CHANNELS = (64, 192, 384, 256, 256)
 ALEX_TAPS = (1, 4, 7, 9, 11)                  # relu1..relu5 of torchvision's alexnet().features (lpips' pretrained alexnet slices)
@@ -37,6 +42,7 @@ ALEX_CONVS = {0: (64, 3, 11), 3: (192, 64, 5), 6: (384, 192, 3), 8: (256, 384, 3
 LPIPS_SHIFT = (-0.030, -0.088, -0.188)        # lpips ScalingLayer
 LPIPS_SCALE = (0.458, 0.448, 0.450)
 EVAL_SCRATCH_DOUBLES = 2048                   # include/laenerf.h LAE_EVAL_VIEW_SCRATCH_DOUBLES
+CONSISTENCY_SCRATCH_DOUBLES = 16384           # include/laenerf.h LAE_CONSISTENCY_SCRATCH_DOUBLES
 _DTYPES = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
 
 
@@ -282,3 +288,175 @@ def eval_view_numpy(pred, gt, depth=None, bg=1.0, mask=None):
     shift, scale = np.array(LPIPS_SHIFT, f32)[:, None], np.array(LPIPS_SCALE, f32)[:, None]
     out["lpips_in"] = np.stack([((f32(2) * v.T - f32(1)) - shift) / scale for v in (blend, pred)]).astype(f32)
     return out
+
+
+def consistency_pair(frame_a, frame_b, depth_a, opacity_a, depth_b, opacity_b, pose_a, pose_b, intrinsics, H, W, min_opacity=0.5,
+                     sse=None, count=None, valid=None, warped=None, lpips_in=None, scratch=None):
+    """multi-view consistency of two rendered views in one pass (lae_consistency_pair): the source frame `a` is warped onto the
+    target frame `b` by the reprojection through the views' own depth, occlusions and motion boundaries are masked, and the
+    squared error of the warped frame against the target is summed over the pixels that are left.  The metric follows the
+    reference's scripts/eval/consistency_metrics.py (short- and long-range consistency as LAENeRF, ARF and Ref-NPR report it)
+    with RAFT's optical flow replaced by the exact flow of the model's geometry; it is written down in full above
+    k_consistency_pair (csrc/evaluate.hip) and in DESIGN.md section 4i, and restated by `consistency_numpy`.
+
+    frame_a / frame_b uint8 or fp32 with HW x 3 values (read as stored; uint8 = value / 255); depth_* the raw `sum w t` and
+    opacity_* the `weights_sum` of render_eval(scale_depth=False), fp32 [HW]; pose_* fp32 [4,4] cam2world on the device;
+    intrinsics (fx, fy, cx, cy).  A pixel has geometry iff its opacity >= min_opacity (default 0.5: a choice, below one half the
+    expected termination is not a surface).  Outputs, written in place:
+      sse, count  float64 slots (allocated when None): the sum of err over the valid pixels and their number; warp_mse =
+                  sse / count -- the number the script prints as "RSME", although it takes no root.  count == 0 gives sse == 0.
+      valid       uint8 [HW];  warped  fp32 [HW,3], 0 where invalid
+      lpips_in    fp32 [2,3,H,W] for LPIPS: index 0 the warped frame with invalid pixels filled from b, index 1 frame b
+    Two deliberate departures from the script: (1) it multiplies the error by the occlusion mask itself, whereas the metric it
+    follows (Lai et al.) uses the complement, and so does this; (2) it feeds LPIPS the warped frame with remap's zero border,
+    whereas invalid pixels are filled from the target here, so that they contribute nothing.
+    -> (sse, count)"""
+    lib = _lib.load()
+    H, W = int(H), int(W)
+    HW = H * W
+    if H < 2 or W < 2:
+        raise ValueError("consistency_pair: H and W must be at least 2")
+    if len(intrinsics) != 4:
+        raise ValueError("consistency_pair: intrinsics = (fx, fy, cx, cy)")
+    for name, t in (("frame_a", frame_a), ("frame_b", frame_b)):
+        if not torch.is_tensor(t) or t.dtype not in (torch.uint8, torch.float32) or t.numel() != 3 * HW or not t.is_contiguous():
+            raise ValueError(f"consistency_pair: {name} must be a contiguous uint8 or fp32 tensor of H x W x 3 values")
+    if frame_a.dtype != frame_b.dtype:
+        raise ValueError("consistency_pair: both frames must have one dtype")
+    dev = frame_a.device
+    if sse is None:
+        sse = torch.zeros(1, dtype=torch.float64, device=dev)
+    if count is None:
+        count = torch.zeros(1, dtype=torch.float64, device=dev)
+    for name, t, dt, n, opt in (("depth_a", depth_a, torch.float32, HW, False), ("opacity_a", opacity_a, torch.float32, HW, False),
+                                ("depth_b", depth_b, torch.float32, HW, False), ("opacity_b", opacity_b, torch.float32, HW, False),
+                                ("pose_a", pose_a, torch.float32, 16, False), ("pose_b", pose_b, torch.float32, 16, False),
+                                ("sse", sse, torch.float64, 1, False), ("count", count, torch.float64, 1, False),
+                                ("valid", valid, torch.uint8, HW, True), ("warped", warped, torch.float32, 3 * HW, True),
+                                ("lpips_in", lpips_in, torch.float32, 6 * HW, True)):
+        if t is None and opt:
+            continue
+        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"consistency_pair: {name} must be a contiguous {dt} tensor of {n} values")
+    if not float(min_opacity) > 0.0:
+        raise ValueError("consistency_pair: min_opacity must be positive")
+    if scratch is None:
+        scratch = torch.empty(CONSISTENCY_SCRATCH_DOUBLES, dtype=torch.float64, device=dev)
+    if scratch.dtype != torch.float64 or scratch.numel() < CONSISTENCY_SCRATCH_DOUBLES or not scratch.is_contiguous():
+        raise ValueError(f"consistency_pair: scratch must be a contiguous float64 tensor of {CONSISTENCY_SCRATCH_DOUBLES} values")
+    _lib.need_cuda(frame_a, frame_b, depth_a, opacity_a, depth_b, opacity_b, pose_a, pose_b, sse, count, valid, warped, lpips_in, scratch)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    check(lib.lae_consistency_pair(ptr(frame_a), ptr(frame_b), _DTYPES[frame_a.dtype], ptr(depth_a), ptr(opacity_a), ptr(depth_b),
+                                   ptr(opacity_b), ptr(pose_a), ptr(pose_b), fx, fy, cx, cy, H, W, float(min_opacity), ptr(scratch),
+                                   ptr(sse), ptr(count), ptr(valid), ptr(warped), ptr(lpips_in), stream()), "consistency_pair")
+    return sse, count
+
+
+def consistency_numpy(frame_a, frame_b, depth_a, opacity_a, depth_b, opacity_b, pose_a, pose_b, intrinsics, H, W, min_opacity=0.5,
+                      dtype=np.float64, valid=None):
+    """numpy restatement of lae_consistency_pair with every quantity in `dtype` (float64 by default; np.float32 follows the
+    kernel's precision, not its bits).  uint8 frames are taken as the kernel reads them, value * fp32(1 / 255); every other
+    input is converted to `dtype` as it comes (fp32 arrays: exactly what the kernel reads).  `valid` (bool [H, W]) replaces the restatement's own decision in sse, count and lpips_in.
+    -> dict, per pixel of b as [H, W, ...] arrays:
+      valid     bool;  reason uint8: 0 valid, 1 no geometry at the pixel (transparent or behind a), 2 lands outside the frame,
+                3 a right / lower neighbour without fw, 4 a tap without bw, 5 motion boundary, 6 occluded (the first that applies)
+      fw        the forward flow (NaN where undefined);  landing = p + fw;  taps (x0, y0) int;  bw_mean the bilinear mean of bw
+      warped    the bilinear mean of frame a at the landing point wherever that is inside the frame (whatever `valid`), else 0
+      err       sum_c (warped_c - frame_b_c)^2 in float64 of the `dtype` values, wherever `warped` is defined, else 0
+      occ_lhs / occ_rhs, bnd_lhs / bnd_rhs   the two sides of the two rules
+      margin    the distance of the nearest decision from its threshold, each in its own units (the two rules: |lhs - rhs|; the
+                four frame edges: pixels); inf where an undefined input decides
+      lpips_in  [2, 3, H, W]
+    and sse, count (float64 / int), warp_mse (NaN when count == 0)."""
+    dt = np.dtype(dtype).type
+    f32 = np.float32
+    H, W = int(H), int(W)
+
+    def frame(f):
+        f = np.asarray(f)
+        f = f.reshape(H, W, 3)
+        return (f.astype(f32) * (f32(1.0) / f32(255.0)) if f.dtype == np.uint8 else f).astype(dt)
+
+    Fa, Fb = frame(frame_a), frame(frame_b)
+    fx, fy, cx, cy = (dt(v) for v in intrinsics)
+    mo = dt(min_opacity)
+    gx, gy = np.meshgrid(np.arange(W, dtype=dt), np.arange(H, dtype=dt))
+    half, one = dt(0.5), dt(1.0)
+
+    def points(P, D, A):
+        P = np.asarray(P).reshape(4, 4).astype(dt)
+        D, A = np.asarray(D).reshape(H, W).astype(dt), np.asarray(A).reshape(H, W).astype(dt)
+        ok = A >= mo
+        t = D / np.where(ok, A, one)
+        xs, ys = ((gx + half) - cx) / fx, ((gy + half) - cy) / fy              # pinhole_ray
+        nrm = np.sqrt((ys * ys + xs * xs) + one)
+        dx, dy, dz = xs / nrm, ys / nrm, one / nrm
+        X = np.stack([t * ((dz * P[k, 2] + dy * P[k, 1]) + dx * P[k, 0]) + P[k, 3] for k in range(3)], -1)
+        return X, ok
+
+    def project(P, X, ok):
+        P = np.asarray(P).reshape(4, 4).astype(dt)
+        v = X - P[:3, 3]
+        q = [(P[2, k] * v[..., 2] + P[1, k] * v[..., 1]) + P[0, k] * v[..., 0] for k in range(3)]
+        ok = ok & (q[2] > 0)
+        qz = np.where(ok, q[2], one)
+        return (fx * q[0] / qz + cx) - half, (fy * q[1] / qz + cy) - half, ok
+
+    with np.errstate(all="ignore"):
+        Xb, okb = points(pose_b, depth_b, opacity_b)
+        lx, ly, def_b = project(pose_a, Xb, okb)
+        Xa, oka = points(pose_a, depth_a, opacity_a)
+        ux, uy, def_a = project(pose_b, Xa, oka)
+        bwx, bwy = ux - gx, uy - gy
+        fwx, fwy = lx - gx, ly - gy
+        in_frame = def_b & (lx >= 0) & (lx <= dt(W - 1)) & (ly >= 0) & (ly <= dt(H - 1))
+        x0 = np.where(in_frame, np.minimum(np.floor(np.where(in_frame, lx, 0)), W - 2), 0).astype(np.int64)
+        y0 = np.where(in_frame, np.minimum(np.floor(np.where(in_frame, ly, 0)), H - 2), 0).astype(np.int64)
+        wx, wy = lx - x0.astype(dt), ly - y0.astype(dt)
+        taps_def = np.ones((H, W), bool)
+        tap = []
+        for k in range(4):
+            rx, ry = x0 + (k & 1), y0 + (k >> 1)
+            taps_def &= def_a[ry, rx]
+            tap.append(np.concatenate([np.where(def_a[ry, rx], bwx[ry, rx], 0)[..., None],
+                                       np.where(def_a[ry, rx], bwy[ry, rx], 0)[..., None], Fa[ry, rx]], -1))
+        # the bilinear mean as two lerps along x and one along y, as the kernel forms it
+        top = tap[0] + wx[..., None] * (tap[1] - tap[0])
+        bot = tap[2] + wx[..., None] * (tap[3] - tap[2])
+        mean = top + wy[..., None] * (bot - top)
+        bmx, bmy = mean[..., 0], mean[..., 1]
+        Fw = np.where(in_frame[..., None], mean[..., 2:], 0).astype(dt)
+        # motion boundary: fw of the pixel against its right and lower neighbour, 0 in the last column / row
+        right_def, down_def = np.ones((H, W), bool), np.ones((H, W), bool)
+        right_def[:, :-1], down_def[:-1] = def_b[:, 1:], def_b[1:]
+        nb_def = def_b & right_def & down_def
+        dux, duy, dvx, dvy = (np.zeros((H, W), dt) for _ in range(4))
+        dux[:, :-1], duy[:, :-1] = fwx[:, :-1] - fwx[:, 1:], fwy[:, :-1] - fwy[:, 1:]
+        dvx[:-1], dvy[:-1] = fwx[:-1] - fwx[1:], fwy[:-1] - fwy[1:]
+        mag = fwx * fwx + fwy * fwy
+        bnd_lhs = (dux * dux + dvx * dvx) + (duy * duy + dvy * dvy)
+        bnd_rhs = dt(0.01) * mag + dt(0.002)
+        sx, sy = fwx + bmx, fwy + bmy
+        occ_lhs = sx * sx + sy * sy
+        occ_rhs = dt(0.01) * (mag + (bmx * bmx + bmy * bmy)) + dt(0.5)
+        decided = in_frame & nb_def & taps_def
+        bnd, occ = decided & (bnd_lhs > bnd_rhs), decided & (occ_lhs > occ_rhs)
+        own_valid = decided & ~bnd & ~occ
+        reason = np.select([~def_b, ~in_frame, ~nb_def, ~taps_def, bnd, occ], [1, 2, 3, 4, 5, 6], 0).astype(np.uint8)
+        edge = np.minimum(np.minimum(np.abs(lx), np.abs(dt(W - 1) - lx)), np.minimum(np.abs(ly), np.abs(dt(H - 1) - ly)))
+        rules = np.minimum(np.abs(bnd_lhs - bnd_rhs), np.abs(occ_lhs - occ_rhs))
+        margin = np.full((H, W), np.inf)
+        margin[def_b & ~in_frame] = edge[def_b & ~in_frame]
+        margin[decided] = np.minimum(edge, rules)[decided]
+        err = np.where(in_frame, ((Fw.astype(np.float64) - Fb.astype(np.float64)) ** 2).sum(-1), 0.0)
+        use = own_valid if valid is None else np.asarray(valid).reshape(H, W).astype(bool)
+        sse, count = float(err[use].sum()), int(use.sum())
+        shift, scale = np.array(LPIPS_SHIFT, f32).astype(dt), np.array(LPIPS_SCALE, f32).astype(dt)
+        x0_img = np.where(use[..., None], Fw, Fb)
+        lp = np.stack([(((dt(2) * v - one) - shift) / scale).transpose(2, 0, 1) for v in (x0_img, Fb)]).astype(dt)
+    nan = dt(np.nan)
+    return {"valid": own_valid, "reason": reason, "fw": np.stack([np.where(def_b, fwx, nan), np.where(def_b, fwy, nan)], -1),
+            "landing": np.stack([np.where(def_b, lx, nan), np.where(def_b, ly, nan)], -1), "taps": np.stack([x0, y0], -1),
+            "bw_mean": np.stack([bmx, bmy], -1), "warped": Fw, "err": err, "occ_lhs": occ_lhs, "occ_rhs": occ_rhs,
+            "bnd_lhs": bnd_lhs, "bnd_rhs": bnd_rhs, "margin": margin, "lpips_in": lp, "sse": sse, "count": count,
+            "warp_mse": sse / count if count else float("nan")}

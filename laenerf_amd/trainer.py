@@ -856,6 +856,78 @@ class Trainer:
         self.stats["results"].append(float(s[:, 0].sum() / (n * 3 * H * W)))
         return res
 
+    def _render_view_geometry(self, data, i):
+        """_render_view's render of view i with scale_depth=False, and its opacity -> image [HW,3], depth [HW] (the raw sum w t),
+        weights_sum [HW], fp32"""
+        from .rays import get_rays
+        ray = get_rays(data.poses[i:i + 1], data.intrinsics, data.H, data.W)
+        with torch.autocast("cuda", dtype=torch.float16):
+            res = self.r.render_eval(ray["rays_o"][0], ray["rays_d"][0], bg_color=1.0, perturb=False, scale_depth=False,
+                                     image_hw=(data.H, data.W))
+        return res["image"].float().contiguous(), res["depth"].float().contiguous(), res["weights_sum"].float().contiguous()
+
+    @torch.no_grad()
+    def evaluate_consistency(self, data, step=1, frames=None, lpips=None, min_opacity=0.5, out_dir=None, name="ngp"):
+        """short-range (step=1) and long-range (step=7) view consistency as LAENeRF, ARF and Ref-NPR report it (the reference's
+        scripts/eval/consistency_metrics.py), for results that have no ground truth: frame i is warped onto frame i + step and
+        compared with it where neither an occlusion nor a motion boundary is in the way (metrics.consistency_pair; the flow is
+        the reprojection through this trainer's model, not RAFT's).  The views of `data` (a ResidentImages) are taken as a camera
+        path in the data's order (the script sorts file names; from_transforms keeps the file's order).  Every view is rendered
+        ONCE with the EMA weights over white (perturb=False, scale_depth=False) and kept in a ring of step + 1 views on the device;
+        the pairs (i, i + step), i < n - step, are one kernel call each into a device [n - step, 2] float64 tensor, plus one
+        `lpips(lp_in, out=...)` with `lpips` (metrics.LPIPS); one host read for the whole split.
+        frames: [n, H, W, 3] uint8 or fp32 on the device, in the data's camera order (recolor_views(...), render_recolored,
+        tr.test(...)[0], ...): they replace the colours, the geometry still comes from the model; None scores the model's own
+        renders.  out_dir: `{name}_{i:04d}_warp.png`, frame i warped onto i + step, invalid pixels black.
+        -> dict warp_mse [n - step] (sse / count, the script's "RSME", which takes no root; NaN where no pixel is valid),
+        valid_share [n - step], lpips [n - step] or None, mean_warp_mse and mean_lpips (over the pairs as in the script, the NaN
+        pairs left out of mean_warp_mse), empty_pairs (their number)."""
+        from . import metrics as M
+        n, H, W = data.n_img, data.H, data.W
+        step = int(step)
+        if step < 1 or step >= n:
+            raise ValueError(f"evaluate_consistency: step must be in [1, {n - 1}] for {n} views")
+        if data.color_space == "linear":
+            raise ValueError("evaluate_consistency: color_space='linear' data is not supported here (every shipped config uses srgb)")
+        dev = data.images.device
+        if frames is not None:
+            if not torch.is_tensor(frames) or tuple(frames.shape) != (n, H, W, 3) or frames.dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"evaluate_consistency: frames must be a uint8 or fp32 tensor of shape {(n, H, W, 3)}")
+            frames = frames.to(dev).contiguous()
+        pairs = n - step
+        sums = torch.zeros(pairs, 2, dtype=torch.float64, device=dev)
+        scratch = torch.empty(M.CONSISTENCY_SCRATCH_DOUBLES, dtype=torch.float64, device=dev)
+        lp = torch.zeros(pairs, dtype=torch.float64, device=dev) if lpips is not None else None
+        lp_in = torch.empty(2, 3, H, W, dtype=torch.float32, device=dev) if lpips is not None else None
+        warped = torch.empty(H, W, 3, dtype=torch.float32, device=dev) if out_dir else None
+        ring = [None] * (step + 1)
+        with self._eval_weights():
+            for j in range(n):
+                image, depth, opacity = self._render_view_geometry(data, j)
+                ring[j % (step + 1)] = (frames[j] if frames is not None else image, depth, opacity)
+                i = j - step
+                if i < 0:
+                    continue
+                (fa, da, aa), (fb, db, ab) = ring[i % (step + 1)], ring[j % (step + 1)]
+                M.consistency_pair(fa, fb, da, aa, db, ab, data.poses[i], data.poses[j], data.intrinsics, H, W,
+                                   min_opacity=min_opacity, sse=sums[i, 0:1], count=sums[i, 1:2], warped=warped, lpips_in=lp_in,
+                                   scratch=scratch)
+                if lpips is not None:
+                    lpips(lp_in, out=lp[i:i + 1])
+                if out_dir:
+                    from PIL import Image
+                    os.makedirs(out_dir, exist_ok=True)
+                    u8 = (warped.clamp(0, 1) * 255).to(torch.uint8)
+                    Image.fromarray(u8.cpu().numpy()).save(os.path.join(out_dir, f"{name}_{i:04d}_warp.png"))
+        s = sums.cpu().numpy()
+        sse, count = s[:, 0], s[:, 1]
+        empty = count == 0
+        res = {"warp_mse": np.where(empty, np.nan, sse / np.where(empty, 1.0, count)), "valid_share": count / (H * W),
+               "lpips": None if lp is None else lp.cpu().numpy(), "empty_pairs": int(empty.sum())}
+        res["mean_warp_mse"] = float(np.mean(res["warp_mse"][~empty])) if not empty.all() else float("nan")
+        res["mean_lpips"] = None if lp is None else float(np.mean(res["lpips"]))
+        return res
+
     @torch.no_grad()
     def test(self, data, out_dir=None, name="ngp"):
         """the reference's test (nerf/utils.py:777-827, test_step :701-719): every view of `data` rendered with the EMA weights
