@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi26"
+#define LAE_ABI_TAG "abi27"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -1146,6 +1146,38 @@ LAE_API int lae_marching_cubes_count(const float* u, uint32_t nx, uint32_t ny, u
                              int32_t* counts, void* stream);
 LAE_API int lae_marching_cubes_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void* scratch, float* verts,
                             int32_t* tris, void* stream);
+
+/* ---- connected components of a lattice's inside set (csrc/components.hip): what drops floaters between the density sweep and
+ * marching cubes, and from the occupancy grid (laenerf_amd/components.py; the reference exports through trimesh and stops).
+ * u [nx, ny, nz] fp32, C order, any 4-byte-aligned base; 2 <= nx, ny, nz <= 512 as for lae_marching_cubes_* (else LAE_EINVAL).
+ * `threshold` is a double cast once to fp32; every compare is fp32.
+ *   Inside rule: lae_marching_cubes_*'s: a lattice point is inside iff u > threshold (strictly; NaN is outside, +inf inside).
+ *   Connectivity: two inside points are connected iff they differ by 1 in exactly one coordinate (6-connectivity); contact along
+ *     an edge or at a corner does not connect.  An inside point face-adjacent to a kept inside point is therefore kept as well:
+ *     removing other components changes neither end of a crossed lattice edge of a kept component, and the kept surface's
+ *     marching-cubes vertices are the unfiltered mesh's, bit for bit.
+ *   The result is canonical -- it does not depend on the algorithm or the schedule:
+ *     labels [nx, ny, nz] int32: the smallest linear index (i * ny + j) * nz + k of the point's component (its root); -1 outside.
+ *     sizes [N] int32 (N = nx * ny * nz): at a root, the number of points of its component; 0 everywhere else.
+ *     stats int32[4]: {n_components, largest_root, largest_size, n_inside}; ties for the largest go to the lowest root; with no
+ *       inside point {0, -1, 0, 0}.
+ * lae_components_label: three launches (per-tile union-find in LDS; a lock-free merge across tile faces with agent-scope
+ *   atomicMin, in which no wave waits for another; flatten).  `labels` is the only storage: no scratch.
+ * lae_components_sizes: labels as written by lae_components_label (N <= 512^3, else LAE_EINVAL; a value outside [0, N) counts as
+ *   outside).  Four launches; sizes and stats are zeroed by the first, the counts are integer atomics (exact, the same bits on
+ *   every run), one add per label a workgroup's waves end with, not one per point; the largest component is one 64-bit atomic
+ *   max of size << 32 | (0x7fffffff - root) per workgroup, kept in stats[0..1] between the passes: stats must be 8-byte aligned
+ *   (LAE_EINVAL otherwise).
+ * lae_components_filter: out[p] = u[p] bitwise (NaN payloads included) unless labels[p] >= 0 and p's component is not kept; then
+ *   out[p] = (float)threshold, which is not > threshold: outside.  A component is kept iff sizes[root] >= min_size and
+ *   (keep_root < 0 or root == keep_root).  out may alias u.  One launch (16-byte accesses where u, labels and out are 16-byte
+ *   aligned, 4-byte ones otherwise).
+ * No entry point reads back, allocates or synchronises: all three can be captured.  N == 0 (sizes, filter): LAE_OK before any
+ * pointer is looked at; a NULL pointer: LAE_ENULL; both before any launch. */
+LAE_API int lae_components_label(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, double threshold, int32_t* labels, void* stream);
+LAE_API int lae_components_sizes(const int32_t* labels, uint64_t N, int32_t* sizes, int32_t* stats, void* stream);
+LAE_API int lae_components_filter(const float* u, const int32_t* labels, const int32_t* sizes, uint64_t N, double threshold,
+                          int32_t min_size, int32_t keep_root, float* out, void* stream);
 
 /* ---- mesh export: per-vertex attributes of a marching-cubes mesh and the binary PLY bodies, on the device.
  * lae_mesh_vertex_attrs: u [nx, ny, nz] fp32 (the field marching cubes ran on), verts [V, 3] fp32 in index space (as

@@ -118,6 +118,9 @@ SIGNATURES = {
     "lae_marching_cubes_emit": [vp, u32, u32, u32, f32, vp, vp, vp, vp],
     "lae_mesh_vertex_attrs": [vp, u32, u32, u32, vp, u32, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp],
     "lae_mesh_pack_ply": [vp, vp, vp, u32, vp, u32, vp, vp, vp],
+    "lae_components_label": [vp, u32, u32, u32, f64, vp, vp],
+    "lae_components_sizes": [vp, u64, vp, vp, vp],
+    "lae_components_filter": [vp, vp, vp, u64, f64, i32, i32, vp, vp],
     "lae_nnfm_packed_bytes": [u32, u32, u32],
     "lae_nnfm_match_bytes": [u32, u32, u32],
     "lae_nnfm_workspace_bytes": [u32, u32, u32, u32],
@@ -194,7 +197,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi26"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi27"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

@@ -5,6 +5,7 @@ instead of trimesh.
     marching_cubes(u, threshold)        the contract of mcubes.marching_cubes: vertices in index space, triangles
     marching_cubes_numpy(u, threshold)  the same specification restated in numpy (what the tests compare against)
     extract_fields / extract_geometry   the reference's lattice sweep and scaling, with the field kept on the device
+    drop_components(u, threshold, ...)  the field without its floaters (components.py), for marching cubes only
     write_ply(path, vertices, triangles)
     vertex_attributes(u, verts, bmin, bmax)  per-vertex position in the box, normal and view direction on the device
     vertex_attributes_numpy(...)             the same specification restated in numpy
@@ -162,10 +163,27 @@ def scale_vertices(vertices, bound_min, bound_max, resolution):
     return np.asarray(vertices, dtype=np.float64) / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
 
 
-def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, S=128):
-    """nerf/utils.py:207-219: -> vertices [V,3] float64 in the box, triangles [T,3] int32 (numpy)"""
+def has_component_rule(keep_largest=False, min_component=None, min_component_fraction=None):
+    return bool(keep_largest) or min_component is not None or min_component_fraction is not None
+
+
+def drop_components(u, threshold, keep_largest=False, min_component=None, min_component_fraction=None):
+    """the field marching cubes should run on: u itself with no rule (nothing is labelled, nothing launched), else a filtered copy
+    (components.filter_components: keep_largest keeps the largest connected component of {u > threshold}, min_component those of
+    at least that many lattice points, min_component_fraction those of at least that fraction of the largest).  u is not
+    modified: vertex normals are taken from it, so a removed blob next to a kept surface does not bend that surface's normals."""
+    if not has_component_rule(keep_largest, min_component, min_component_fraction):
+        return u
+    from . import components
+    return components.filter_components(u, threshold, largest=keep_largest, min_size=min_component, min_fraction=min_component_fraction)[0]
+
+
+def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, S=128, keep_largest=False, min_component=None,
+                     min_component_fraction=None):
+    """nerf/utils.py:207-219: -> vertices [V,3] float64 in the box, triangles [T,3] int32 (numpy).  keep_largest / min_component /
+    min_component_fraction: drop_components between the sweep and marching cubes (the kept surfaces keep their bits)"""
     u = extract_fields(bound_min, bound_max, resolution, query_func, S=S)
-    v, t = marching_cubes(u, threshold)
+    v, t = marching_cubes(drop_components(u, threshold, keep_largest, min_component, min_component_fraction), threshold)
     return scale_vertices(v.cpu().numpy(), bound_min, bound_max, resolution), t.cpu().numpy()
 
 

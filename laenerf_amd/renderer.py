@@ -110,9 +110,11 @@ class NeRFRenderer(nn.Module):
 
     # ------------------------------------------------------------------ mesh (nerf/utils.py:722-741 save_mesh)
     @torch.no_grad()
-    def extract_mesh(self, resolution=256, threshold=10, chunk=128):
+    def extract_mesh(self, resolution=256, threshold=10, chunk=128, keep_largest=False, min_component=None, min_component_fraction=None):
         """the reference's extract_geometry over aabb_infer: sigma of model.density under fp16 autocast (not multiplied by
-        density_scale) on a resolution^3 lattice, marching cubes on the device -> vertices [V,3] float64, triangles [T,3] int32"""
+        density_scale) on a resolution^3 lattice, marching cubes on the device -> vertices [V,3] float64, triangles [T,3] int32.
+        keep_largest / min_component (lattice points) / min_component_fraction (of the largest): floaters are dropped from the
+        field before marching cubes (mesh.drop_components); the kept surfaces are the unfiltered mesh's, bit for bit."""
         from . import mesh
         sigma = getattr(self.model, "density_sigma", None) or (lambda x: self.model.density(x)["sigma"])
 
@@ -120,20 +122,26 @@ class NeRFRenderer(nn.Module):
             with torch.autocast("cuda", dtype=torch.float16):
                 return sigma(pts)
 
-        return mesh.extract_geometry(self.aabb_infer[:3], self.aabb_infer[3:], resolution, threshold, query, S=chunk)
+        return mesh.extract_geometry(self.aabb_infer[:3], self.aabb_infer[3:], resolution, threshold, query, S=chunk,
+                                     keep_largest=keep_largest, min_component=min_component, min_component_fraction=min_component_fraction)
 
     @torch.no_grad()
-    def extract_mesh_attributes(self, resolution=256, threshold=10, chunk=128, normals=True, colors=True, color_chunk=1 << 20):
+    def extract_mesh_attributes(self, resolution=256, threshold=10, chunk=128, normals=True, colors=True, color_chunk=1 << 20,
+                                keep_largest=False, min_component=None, min_component_fraction=None):
         """extract_mesh with everything kept on the device, plus per-vertex attributes (mesh.vertex_attributes): -> a dict of
         device tensors, `vertices` [V,3] fp32 in the box (the float64 scaling of extract_mesh rounded once to fp32), `triangles`
         [T,3] int32, and on request `normals` [V,3] fp32 (unit, towards lower density) and `colors` [V,3] fp32 in [0, 1]: the
         radiance self.model(vertex, -normal) under the sweep's fp16 autocast, queried color_chunk vertices at a time.  Only the
-        box and (V, T) are read back."""
-        out = self._mesh_attributes(resolution, threshold, chunk, normals, colors, color_chunk)
+        box and (V, T) are read back.  keep_largest / min_component / min_component_fraction as in extract_mesh (one more read of
+        16 bytes); normals still come from the unfiltered field, so a kept vertex has the position, normal and colour bits it has
+        without the rule."""
+        out = self._mesh_attributes(resolution, threshold, chunk, normals, colors, color_chunk, keep_largest, min_component,
+                                    min_component_fraction)
         del out["index_vertices"]
         return out
 
-    def _mesh_attributes(self, resolution, threshold, chunk, normals, colors, color_chunk):
+    def _mesh_attributes(self, resolution, threshold, chunk, normals, colors, color_chunk, keep_largest=False, min_component=None,
+                         min_component_fraction=None):
         """extract_mesh_attributes plus `index_vertices`, the marching-cubes vertices in index space"""
         from . import mesh
         sigma = getattr(self.model, "density_sigma", None) or (lambda x: self.model.density(x)["sigma"])
@@ -145,7 +153,7 @@ class NeRFRenderer(nn.Module):
         aabb = self.aabb_infer.cpu()
         bmin, bmax = aabb[:3], aabb[3:]
         u = mesh.extract_fields(bmin, bmax, resolution, query, S=chunk, device=self.aabb_infer.device)
-        v, t = mesh.marching_cubes(u, threshold)
+        v, t = mesh.marching_cubes(mesh.drop_components(u, threshold, keep_largest, min_component, min_component_fraction), threshold)
         want = ("pos",) + (("normals",) if normals else ()) + (("dirs",) if colors else ())
         attrs = mesh.vertex_attributes(u, v, bmin, bmax, want=want)
         out = {"vertices": attrs["pos"], "triangles": t, "index_vertices": v}
@@ -159,17 +167,20 @@ class NeRFRenderer(nn.Module):
             out["colors"] = rgb
         return out
 
-    def save_mesh(self, path, resolution=256, threshold=10, normals=False, colors=False, color_chunk=1 << 20):
+    def save_mesh(self, path, resolution=256, threshold=10, normals=False, colors=False, color_chunk=1 << 20, keep_largest=False,
+                  min_component=None, min_component_fraction=None):
         """extract_mesh written as a binary PLY (the reference exports through trimesh).  normals / colors: per-vertex
         `float nx ny nz` / `uchar red green blue` from extract_mesh_attributes, the file's bodies packed on the device
-        (mesh.pack_ply).  -> (vertices [V,3] float64, triangles [T,3] int32) on the host either way"""
+        (mesh.pack_ply).  keep_largest / min_component / min_component_fraction: as in extract_mesh, the file without its floaters.
+        -> (vertices [V,3] float64, triangles [T,3] int32) on the host either way"""
         from . import mesh
+        rule = dict(keep_largest=keep_largest, min_component=min_component, min_component_fraction=min_component_fraction)
         if not normals and not colors:
-            v, t = self.extract_mesh(resolution, threshold)
+            v, t = self.extract_mesh(resolution, threshold, **rule)
             mesh.write_ply(path, v, t)
             return v, t
         with torch.no_grad():
-            m = self._mesh_attributes(resolution, threshold, 128, normals, colors, color_chunk)
+            m = self._mesh_attributes(resolution, threshold, 128, normals, colors, color_chunk, **rule)
         head, vb, fb = mesh.pack_ply(m["vertices"], m["triangles"], normals=m.get("normals"), colors=m.get("colors"))
         mesh.write_ply_packed(path, head, vb, fb)
         v = mesh.scale_vertices(m["index_vertices"].cpu().numpy(), self.aabb_infer[:3], self.aabb_infer[3:], resolution)
@@ -255,6 +266,47 @@ class NeRFRenderer(nn.Module):
         if total_step > 0:
             self.mean_count = int(int(cnt_v) / total_step)
         self.local_step = 0
+
+    def _morton_index(self):
+        """[H^3] int64, cached: the Morton index of cell (x, y, z) in C order, so density_grid[0][index] is the grid as [H, H, H]"""
+        H, dev = self.grid_size, self.density_grid.device
+        cached = getattr(self, "_morton_cache", None)
+        if cached is None or cached[0] != (H, dev):
+            ax = torch.arange(H, device=dev, dtype=torch.int32)
+            coords = torch.stack(torch.meshgrid(ax, ax, ax, indexing="ij"), dim=-1).reshape(-1, 3).contiguous()
+            cached = ((H, dev), raymarching.morton3D(coords).long())
+            self._morton_cache = cached
+        return cached[1]
+
+    @torch.no_grad()
+    def prune_floaters(self, keep_largest=True, min_cells=None, min_fraction=None, persist=True):
+        """Drop floaters from the occupancy grid, so that render_eval / test / the frame loop never sample them: the connected
+        components (components.py; 6-connectivity) of the occupied cells -- density above min(mean_density, density_thresh), the
+        threshold update_extra_state packs the bitfield with -- are labelled on the device, and the cells of the components the
+        rule rejects are taken out of density_grid and density_bitfield.  keep_largest keeps the largest component alone,
+        min_cells those of at least that many cells, min_fraction those of at least that fraction of the largest.
+
+        persist=True: removed cells get density -1, the value mark_untrained_grid gives cells that must never be sampled;
+        lae_density_grid_update leaves them alone (csrc/densitygrid.hip k_ema writes a cell only where grid >= 0), so they stay
+        dead through every later update_extra_state: called in the middle of training, the cells stay dead.  persist=False:
+        they get 0 and the next refresh may revive them.  mean_density, mean_count and the training state are not touched.
+        Meant for a trained model before test / evaluate_*.  -> the info dict of components.filter_components (one host read
+        of 16 bytes).
+
+        cascade > 1 (bound > 1) raises ValueError: the cascades nest, connectivity across them is a separate design and out of
+        scope here."""
+        if self.cascade > 1:
+            raise ValueError("prune_floaters: one cascade (bound <= 1) only; connectivity across nested cascades is not defined here")
+        from . import components
+        H = self.grid_size
+        index = self._morton_index()
+        thr = min(self.mean_density, self.density_thresh)
+        u = self.density_grid[0][index].reshape(H, H, H)
+        f, info = components.filter_components(u, thr, largest=keep_largest, min_size=min_cells, min_fraction=min_fraction)
+        removed = f.view(torch.int32) != u.view(torch.int32)                  # kept and outside cells keep their bits
+        self.density_grid[0][index] = torch.where(removed, -1.0 if persist else 0.0, u).reshape(-1)
+        self.density_bitfield = raymarching.packbits(self.density_grid, thr, self.density_bitfield)
+        return info
 
     def update_mean_count(self):
         """the mean_count refresh of update_extra_state (renderer.py:644-647); one D2H read every 16 steps"""
