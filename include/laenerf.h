@@ -75,7 +75,7 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad -- a binding that needs them also checks that the library exports them).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
 #define LAE_ABI_TAG "abi27"
@@ -179,6 +179,22 @@ LAE_API int lae_sample_train_batch_weighted_gain(const void* images, int dtype, 
                                                  int srgb_to_linear, const float* error_map, int32_t* cells_out, const float* gains,
                                                  float* rays_o, float* rays_d, float* nears, float* fars, float* gt, float* fg,
                                                  float* bg_out, int64_t* inds, void* stream);
+/* The patch sampler (the reference's --patch_size, nerf/utils.py:88-105): lae_sample_train_batch with the batch drawn as
+ * n_patch = N / P^2 square patches of P x P pixels, P = patch_size.  u(ray, word) and the step protocol as there.
+ *   patch q: top row  = (u(q, 5) * (uint64)(H - P)) >> 32, left column = (u(q, 6) * (uint64)(W - P)) >> 32 -- the reference's
+ *            exclusive bounds, so the last image row and column are never drawn
+ *   image:   (u(r, 1) * (uint64)n_img) >> 32 with r = 0xffffffff in LAE_BATCH_IMAGE mode and r = q in LAE_BATCH_ALL mode (an image
+ *            per patch)
+ *   ray n:   patch q = n / P^2, pixel (row + (n % P^2) / P, col + n % P) (row-major, the reference's 'ij' meshgrid),
+ *            inds[n] = image * H * W + y * W + x
+ * Everything per ray -- origin, direction, nears / fars, the gather, the colour space, the alpha blend, the background from words
+ * 2..4 of ray n -- is what lae_sample_train_batch writes for that (image, pixel): one shared per-ray device function.
+ * LAE_EINVAL before any launch: P < 2, P >= min(H, W), N == 0 or N not a multiple of P^2. */
+LAE_API int lae_sample_train_batch_patch(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                                         const float* poses, float fx, float fy, float cx, float cy, uint32_t N, uint32_t patch_size,
+                                         const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int mode,
+                                         int bg_mode, int srgb_to_linear, float* rays_o, float* rays_d, float* nears, float* fars,
+                                         float* gt, float* bg_out, int64_t* inds, void* stream);
 
 /* The error map's EMA after a step (nerf/utils.py:609-631), one thread per ray: image = inds[n] / (H * W),
  * d = pred[n] - gt[n], err = ((d0 * d0 + d1 * d1) + d2 * d2) / 3, map[image][cells[n]] = 0.1 * old + 0.9 * err (fp32, each
@@ -1359,6 +1375,33 @@ LAE_API int lae_eval_view(const float* pred, const float* depth, const void* gt,
  * accumulated in fp64 with a fixed-order reduction.  scratch: n_pairs * sum_l ceil(hw[l] / 256) doubles. */
 LAE_API int lae_lpips_head(uint32_t n_layers, const float* const* feats, const float* const* weights, const uint32_t* channels,
                            const uint32_t* hw, uint32_t n_pairs, double* scratch, double* out, void* stream);
+/* The gradient of lae_lpips_head with respect to the features (LPIPS as a training term: the reference's patch loss, nerf/utils.py:
+ * 594-603), all n_layers <= 5 layers and all pairs in ONE launch.  feats, weights, channels, hw, n_pairs as lae_lpips_head
+ * (channels[l] <= 512, else LAE_EINVAL); gout double [n_pairs] on the device, the upstream gradient of out[p]; grad_feats[l] fp32
+ * [2 * n_pairs, channels[l], hw[l]] (a host array of device pointers), every element written.  Per layer, pair and pixel, with
+ *   n_i = sqrt(sum_c f_i,c^2), u_i = f_i / (n_i + 1e-10), d = u_0 - u_1, a_i = sum_c w_c d_c f_i,c:
+ *   d out / d f_1,k = -(2 gout[p] / hw) * (w_k d_k / (n_1 + 1e-10) - f_1,k a_1 / (n_1 (n_1 + 1e-10)^2))
+ *   d out / d f_0,k = the same expression with index 0 and the opposite sign when both != 0; with both == 0 the x_0 rows (2p) are
+ *   written as zeros (the ground truth needs no gradient).
+ * Zero-norm rule: a pixel whose n_i is exactly 0 gets a zero gradient on that side.  The true slope there is 1 / 1e-10, an artefact
+ * of the epsilon; torch's autograd returns NaN (sqrt'(0) * 0), which would make a GradScaler skip the step.  The other side of such a
+ * pixel is computed as stated, with u_i = 0.
+ * Arithmetic: norms, dot products and the expression in fp64 from the fp32 features, gout multiplied in before the single rounding
+ * to fp32.  One owner per output element, fixed-order wave reductions, no atomics: two calls give the same bits. */
+LAE_API int lae_lpips_head_grad(uint32_t n_layers, const float* const* feats, const float* const* weights, const uint32_t* channels,
+                                const uint32_t* hw, uint32_t n_pairs, const double* gout, float* const* grad_feats, int both,
+                                void* stream);
+/* A patch batch's rows as the input of LPIPS' trunk.  pred, gt fp32 [n_patch * P^2, 3], row r = pixel (r % P^2) / P, r % P (row-major)
+ * of patch r / P^2, as lae_sample_train_batch_patch orders them; x fp32 [2 * n_patch, 3, P, P]: image 2p the ground truth of patch p,
+ * 2p + 1 its prediction, the pair layout of lae_lpips_head.  x = ((normalize ? 2 v - 1 : v) - shift_c) / scale_c with lae_eval_view's
+ * constants and statement order, every operation one fp32 rounding.  normalize = 0 is the reference's call ([0, 1] images into lpips
+ * with its default normalize=False), normalize = 1 lpips' documented range.  P in [1, 4096], n_patch * P^2 < 2^31, else LAE_EINVAL. */
+LAE_API int lae_patch_pack(const float* pred, const float* gt, uint32_t n_patch, uint32_t patch_size, int normalize, float* x,
+                           void* stream);
+/* lae_patch_pack's transpose onto the prediction: grad_pred[r, c] = grad_x[2p + 1, c, i, j] * (normalize ? 2 : 1) / scale_c, fp32
+ * [n_patch * P^2, 3]; every row is written, no zero fill needed. */
+LAE_API int lae_patch_unpack_grad(const float* grad_x, uint32_t n_patch, uint32_t patch_size, int normalize, float* grad_pred,
+                                  void* stream);
 #define LAE_CONSISTENCY_SCRATCH_DOUBLES 16384
 /* multi-view consistency of two rendered views (the reference's scripts/eval/consistency_metrics.py with the optical flow
  * replaced by the reprojection through the views' own depth; the metric is written down above k_consistency_pair in

@@ -31,6 +31,8 @@ SIGNATURES = {
     "lae_march_rays_train_limit": [vp, vp, vp, f32, f32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_sample_train_batch": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, vp, f32, u64, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                vp, vp, vp],
+    "lae_sample_train_batch_patch": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, u32, vp, f32, u64, vp, i32, i32, i32, vp, vp, vp,
+                                     vp, vp, vp, vp, vp],
     "lae_sample_train_batch_weighted": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, vp, f32, u64, vp, i32, i32, vp, vp,
                                         vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_sample_train_batch_gain": [vp, i32, u32, u32, u32, u32, vp, f32, f32, f32, f32, u32, vp, f32, u64, vp, i32, i32, i32, vp, vp, vp,
@@ -162,6 +164,9 @@ SIGNATURES = {
     "lae_ema_update_gated": [u32, vp, vp, vp, vp, i64, vp, f64, i32, vp],
     "lae_eval_view": [vp, vp, vp, i32, u32, u32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_lpips_head": [u32, vp, vp, vp, vp, u32, vp, vp, vp],
+    "lae_lpips_head_grad": [u32, vp, vp, vp, vp, u32, vp, vp, i32, vp],
+    "lae_patch_pack": [vp, vp, u32, u32, i32, vp, vp],
+    "lae_patch_unpack_grad": [vp, u32, u32, i32, vp, vp],
     "lae_consistency_pair": [vp, vp, i32, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, u32, u32, f32, vp, vp, vp, vp, vp, vp, vp],
     "lae_adam_apply": [vp, vp, vp, vp, i32, vp, u64, vp, vp, f32, f32, f32, f32, vp],
     "lae_ffmlp_set_mode": [i32],
@@ -201,10 +206,14 @@ ABI_TAG = b"abi27"            # include/laenerf.h LAE_ABI_TAG: the prototypes in
 
 
 def _abi_of(path):
+    """-> (library, its ABI tag); a library that lacks a bound symbol (entry points added without a tag change) counts as stale"""
     lib = ctypes.CDLL(path)
     fn = lib.lae_version
     fn.argtypes, fn.restype = [], ctypes.c_char_p
-    return lib, fn().split()[-1]
+    tag = fn().split()[-1]
+    if tag == ABI_TAG and not all(hasattr(lib, name) for name in SIGNATURES):
+        tag += b"-incomplete"
+    return lib, tag
 
 
 def load():

@@ -7,6 +7,9 @@
 // and blends; the step is read from device memory and advanced by a second one-thread launch, so a captured graph
 // draws a fresh batch on every replay.
 //
+// lae_sample_train_batch_patch draws square pixel patches instead of independent pixels (the reference's --patch_size,
+// nerf/utils.py:88-105): the same per-ray body, another pixel rule.
+//
 // The *_gain entry points (lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain) multiply the colour by a per-image,
 // per-channel gain before the blend and also write fg, the part of the target that scales with it: the exposure refinement of
 // exposure.hip.  They are the same kernels instantiated with GAIN = true; the entry points without a gain compile without the multiply.
@@ -256,6 +259,29 @@ __global__ __launch_bounds__(256) void k_sample_train_batch_weighted(
                         rays_d, nears, fars, gt, bg_out, inds, gains, fg);
 }
 
+// ---------------------------------------------------------------- the patch draw (lae_sample_train_batch_patch)
+// one thread per ray: ray n is pixel (n % P^2) of patch q = n / P^2, row-major inside the patch; the patch's top-left corner comes from
+// words 5 and 6 of "ray" q with the reference's exclusive bounds H - P and W - P (nerf/utils.py:93-94), its image from word 1 of
+// 0xFFFFFFFF (LAE_BATCH_IMAGE) or of q (LAE_BATCH_ALL: an image per patch); then the uniform sampler's per-ray body
+template <int DT>
+__global__ __launch_bounds__(256) void k_sample_train_batch_patch(
+    const void* __restrict__ images, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+    const float* __restrict__ poses, float fx, float fy, float cx, float cy, uint32_t N, uint32_t P, const float* __restrict__ aabb,
+    float min_near, uint32_t k0, uint32_t k1, const int64_t* __restrict__ step_counter, int mode, int bg_mode, int linear,
+    float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears, float* __restrict__ fars,
+    float* __restrict__ gt, float* __restrict__ bg_out, int64_t* __restrict__ inds) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const BatchRng rng{(uint32_t)(uint64_t)step_counter[0], k0, k1};
+    const uint64_t HW = (uint64_t)H * W;
+    const uint32_t PP = P * P, q = n / PP, rem = n % PP;
+    const uint32_t row = scale_u32(rng.u(q, 5), H - P), col = scale_u32(rng.u(q, 6), W - P);      // < H - P, < W - P
+    const uint32_t pix = (row + rem / P) * W + (col + rem % P);                                   // row + P - 1 < H - 1: inside the image
+    const uint32_t img = scale_u32(rng.u(mode == LAE_BATCH_IMAGE ? 0xFFFFFFFFu : q, 1), n_img);
+    batch_ray<DT, false>(images, HW, W, C, poses, fx, fy, cx, cy, aabb, min_near, rng, n, img, pix, bg_mode, linear, rays_o, rays_d,
+                         nears, fars, gt, bg_out, inds, nullptr, nullptr);
+}
+
 // one thread per ray: map[image][cell] = 0.1 * map + 0.9 * mean over RGB of (pred - gt)^2
 __global__ __launch_bounds__(256) void k_error_map_update(
     float* __restrict__ error_map, uint32_t n_img, uint64_t HW, const int64_t* __restrict__ inds, const int32_t* __restrict__ cells,
@@ -395,6 +421,33 @@ int lae_sample_train_batch_weighted_gain(const void* images, int dtype, uint32_t
     if (N > 0 && (!gains || !fg)) return LAE_ENULL;
     return sample_weighted<true>(images, dtype, n_img, H, W, C, poses, fx, fy, cx, cy, N, aabb, min_near, seed, step_counter, bg_mode,
                                  srgb_to_linear, error_map, cells_out, gains, rays_o, rays_d, nears, fars, gt, fg, bg_out, inds, stream);
+}
+
+int lae_sample_train_batch_patch(const void* images, int dtype, uint32_t n_img, uint32_t H, uint32_t W, uint32_t C,
+                                 const float* poses, float fx, float fy, float cx, float cy, uint32_t N, uint32_t patch_size,
+                                 const float* aabb, float min_near, uint64_t seed, int64_t* step_counter, int mode, int bg_mode,
+                                 int srgb_to_linear, float* rays_o, float* rays_d, float* nears, float* fars, float* gt,
+                                 float* bg_out, int64_t* inds, void* stream) {
+    const uint32_t P = patch_size;
+    if (P < 2 || P >= H || P >= W || P > 0xFFFFu) return LAE_EINVAL;
+    if (N == 0 || N % (P * P) != 0) return LAE_EINVAL;                     // whole patches only
+    if (!images || !poses || !aabb || !step_counter || !rays_o || !rays_d || !nears || !fars || !gt || !inds) return LAE_ENULL;
+    if (bg_mode == LAE_BG_RANDOM && !bg_out) return LAE_ENULL;
+    if (n_img == 0 || (C != 3 && C != 4) || (uint64_t)H * W > 0xFFFFFFFFull) return LAE_EINVAL;
+    if (dtype != LAE_IMG_U8 && dtype != LAE_IMG_F16 && dtype != LAE_IMG_F32) return LAE_EINVAL;
+    if (mode != LAE_BATCH_IMAGE && mode != LAE_BATCH_ALL) return LAE_EINVAL;
+    if (bg_mode != LAE_BG_WHITE && bg_mode != LAE_BG_RANDOM) return LAE_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const dim3 grid(lae::cdiv(N, 256)), block(256);
+#define LAE_BATCH_ARGS images, n_img, H, W, C, poses, fx, fy, cx, cy, N, P, aabb, min_near, k0, k1, step_counter, mode, bg_mode, \
+                       srgb_to_linear, rays_o, rays_d, nears, fars, gt, bg_out, inds
+    if (dtype == LAE_IMG_U8) k_sample_train_batch_patch<LAE_IMG_U8><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+    else if (dtype == LAE_IMG_F16) k_sample_train_batch_patch<LAE_IMG_F16><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+    else k_sample_train_batch_patch<LAE_IMG_F32><<<grid, block, 0, s>>>(LAE_BATCH_ARGS);
+#undef LAE_BATCH_ARGS
+    k_advance_step<<<1, 1, 0, s>>>(step_counter);
+    return lae::check_launch("sample_train_batch_patch");
 }
 
 int lae_error_map_update(float* error_map, uint32_t n_img, uint32_t H, uint32_t W, const int64_t* inds, const int32_t* cells,

@@ -9,6 +9,9 @@
 //                   five layers and a batch of pairs in one launch: one lane per pixel of one layer, a loop over the channels
 //                   (NCHW: every load coalesced across the wave), fp64 sums; per-block partials / (h w), k_lpips_finish sums a
 //                   pair's partials in a fixed order.
+//   k_lpips_head_grad   the head's gradient with respect to the features, again one launch for all layers and pairs: one wave per
+//                   pixel, lanes over the channels; k_patch_pack / k_patch_unpack_grad move a patch batch's rows into the trunk's
+//                   input layout and its gradient back (LPIPS as a training term, losses.lpips_patch_loss).
 //   k_consistency_pair  multi-view consistency of two rendered views (the metric is written down above the kernel): ONE gather pass
 //                   per pair, one lane per pixel of the target view, both flows recomputed in registers from the views' depth
 //                   and the two poses; per-block fp64 partials of the squared error and the valid count, summed by k_sum_partials.
@@ -241,6 +244,112 @@ __global__ __launch_bounds__(EV_THREADS) void k_lpips_head(LpipsArgs a, uint32_t
         __syncthreads();
     }
     if (threadIdx.x == 0) partials[(size_t)pair * blocks_per_pair + b] = s_red[0] / (double)hw;
+}
+
+// ---------------------------------------------------------------- LPIPS as a training term (losses.lpips_patch_loss)
+// the sum of one fp64 value per lane over the wave, every lane receiving it; a fixed butterfly: two calls give the same bits
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+constexpr int LG_WAVES = EV_THREADS / 64;    // pixels per block
+constexpr int LG_PER_LANE = 8;               // channels a lane keeps in registers: C <= 512
+struct LpipsGradArgs {
+    const float* f[LP_MAX_LAYERS];
+    const float* w[LP_MAX_LAYERS];
+    float* g[LP_MAX_LAYERS];                // [2 * n_pairs, C, hw], every element written
+    uint32_t C[LP_MAX_LAYERS], hw[LP_MAX_LAYERS];
+    uint32_t blk0[LP_MAX_LAYERS + 1];
+    uint32_t n_layers;
+};
+
+// the gradient of k_lpips_head with respect to the features, all layers and pairs in one launch: one wave per (pair, layer, pixel),
+// lanes over the channels (the features of both sides stay in registers), two wave reductions (the norms, then a_0 and a_1).  The
+// sizes it sees -- hw from 1 to a few hundred, C from 64 to 384 -- are latency-bound; with hw = 1 the loads and stores are
+// coalesced.  fp64 throughout, gout multiplied in before the single rounding to fp32; one owner per output element.
+__global__ __launch_bounds__(EV_THREADS) void k_lpips_head_grad(LpipsGradArgs a, const double* __restrict__ gout, int both) {
+    const uint32_t pair = blockIdx.y, b = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t l = 0;
+    while (l + 1 < a.n_layers && b >= a.blk0[l + 1]) l++;
+    const uint32_t hw = a.hw[l], C = a.C[l];
+    const uint32_t px = (b - a.blk0[l]) * LG_WAVES + wave;
+    if (px >= hw) return;                                        // the whole wave: no lane of it reaches a shuffle
+    const size_t row = (size_t)C * hw;
+    const float* __restrict__ f0 = a.f[l] + (size_t)(2 * pair) * row + px;
+    const float* __restrict__ f1 = f0 + row;
+    const float* __restrict__ w = a.w[l];
+    double x0[LG_PER_LANE], x1[LG_PER_LANE], wc[LG_PER_LANE];
+    double s00 = 0.0, s11 = 0.0;
+#pragma unroll
+    for (int j = 0; j < LG_PER_LANE; j++) {
+        const uint32_t c = lane + 64u * j;
+        const bool in = c < C;
+        x0[j] = in ? (double)f0[(size_t)c * hw] : 0.0;
+        x1[j] = in ? (double)f1[(size_t)c * hw] : 0.0;
+        wc[j] = in ? (double)w[c] : 0.0;
+        s00 += x0[j] * x0[j];
+        s11 += x1[j] * x1[j];
+    }
+    const double n0 = sqrt(wave_sum(s00)), n1 = sqrt(wave_sum(s11));
+    const double e0 = n0 + 1e-10, e1 = n1 + 1e-10;
+    double a0 = 0.0, a1 = 0.0, wd[LG_PER_LANE];
+#pragma unroll
+    for (int j = 0; j < LG_PER_LANE; j++) {
+        wd[j] = wc[j] * (x0[j] / e0 - x1[j] / e1);
+        a0 += wd[j] * x0[j];
+        a1 += wd[j] * x1[j];
+    }
+    a0 = wave_sum(a0);
+    a1 = wave_sum(a1);
+    const double k = 2.0 * gout[pair] / (double)hw;
+    // a side whose norm is exactly 0 gets a zero gradient: the slope there is 1 / eps, an artefact of eps (include/laenerf.h)
+    const bool on0 = both && n0 != 0.0, on1 = n1 != 0.0;
+    const double q0 = on0 ? a0 / (n0 * e0 * e0) : 0.0, q1 = on1 ? a1 / (n1 * e1 * e1) : 0.0;
+    float* __restrict__ g0 = a.g[l] + (size_t)(2 * pair) * row + px;
+    float* __restrict__ g1 = g0 + row;
+#pragma unroll
+    for (int j = 0; j < LG_PER_LANE; j++) {
+        const uint32_t c = lane + 64u * j;
+        if (c < C) {
+            g0[(size_t)c * hw] = on0 ? (float)(k * (wd[j] / e0 - x0[j] * q0)) : 0.0f;
+            g1[(size_t)c * hw] = on1 ? (float)(-k * (wd[j] / e1 - x1[j] * q1)) : 0.0f;
+        }
+    }
+}
+
+// pred / gt rows [n_patch * P^2, 3] -> the trunk's input [2 * n_patch, 3, P, P] (row 2p the ground truth, 2p + 1 the prediction) with
+// k_eval_view's statements; normalize = 0 leaves out the 2v - 1
+__global__ __launch_bounds__(EV_THREADS) void k_patch_pack(const float* __restrict__ pred, const float* __restrict__ gt, uint32_t n_rows,
+                                                           uint32_t PP, int normalize, float* __restrict__ x) {
+    const float shift[3] = {-0.030f, -0.088f, -0.188f};          // lpips ScalingLayer, as in k_eval_view
+    const float scale[3] = {0.458f, 0.448f, 0.450f};
+    const uint32_t r = blockIdx.x * EV_THREADS + threadIdx.x;
+    if (r >= n_rows) return;
+    const uint32_t p = r / PP, px = r % PP;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float u = gt[(size_t)r * 3 + c], v = pred[(size_t)r * 3 + c];
+        if (normalize) { u = __fsub_rn(__fmul_rn(2.0f, u), 1.0f); v = __fsub_rn(__fmul_rn(2.0f, v), 1.0f); }
+        x[((size_t)(2 * p) * 3 + c) * PP + px] = __fdiv_rn(__fsub_rn(u, shift[c]), scale[c]);
+        x[((size_t)(2 * p + 1) * 3 + c) * PP + px] = __fdiv_rn(__fsub_rn(v, shift[c]), scale[c]);
+    }
+}
+
+// k_patch_pack's transpose onto the prediction: every row of grad_pred is written
+__global__ __launch_bounds__(EV_THREADS) void k_patch_unpack_grad(const float* __restrict__ grad_x, uint32_t n_rows, uint32_t PP,
+                                                                  int normalize, float* __restrict__ grad_pred) {
+    const float scale[3] = {0.458f, 0.448f, 0.450f};
+    const uint32_t r = blockIdx.x * EV_THREADS + threadIdx.x;
+    if (r >= n_rows) return;
+    const uint32_t p = r / PP, px = r % PP;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float g = grad_x[((size_t)(2 * p + 1) * 3 + c) * PP + px];
+        if (normalize) g = __fmul_rn(g, 2.0f);
+        grad_pred[(size_t)r * 3 + c] = __fdiv_rn(g, scale[c]);
+    }
 }
 
 // ---------------------------------------------------------------- multi-view consistency of a pair of rendered views
@@ -486,6 +595,44 @@ int lae_lpips_head(uint32_t n_layers, const float* const* feats, const float* co
     if (rc != LAE_OK) return rc;
     k_sum_partials<<<n_pairs, EV_THREADS, 0, s>>>(scratch, nb, nb, out, nullptr);     // one block per pair
     return lae::check_launch("lpips_head_sum");
+}
+
+int lae_lpips_head_grad(uint32_t n_layers, const float* const* feats, const float* const* weights, const uint32_t* channels,
+                        const uint32_t* hw, uint32_t n_pairs, const double* gout, float* const* grad_feats, int both, void* stream) {
+    if (n_pairs == 0) return LAE_OK;
+    if (!feats || !weights || !channels || !hw || !gout || !grad_feats) return LAE_ENULL;
+    if (n_layers == 0 || n_layers > (uint32_t)LP_MAX_LAYERS || n_pairs > 65535u) return LAE_EINVAL;
+    LpipsGradArgs a{};
+    uint32_t nb = 0;
+    for (uint32_t l = 0; l < n_layers; l++) {
+        if (!feats[l] || !weights[l] || !grad_feats[l]) return LAE_ENULL;
+        if (channels[l] == 0 || channels[l] > 64u * LG_PER_LANE || hw[l] == 0) return LAE_EINVAL;
+        a.f[l] = feats[l]; a.w[l] = weights[l]; a.g[l] = grad_feats[l]; a.C[l] = channels[l]; a.hw[l] = hw[l];
+        a.blk0[l] = nb;
+        nb += lae::cdiv(hw[l], LG_WAVES);
+    }
+    a.blk0[n_layers] = nb;
+    a.n_layers = n_layers;
+    k_lpips_head_grad<<<dim3(nb, n_pairs), EV_THREADS, 0, STREAM(stream)>>>(a, gout, both != 0);
+    return lae::check_launch("lpips_head_grad");
+}
+
+int lae_patch_pack(const float* pred, const float* gt, uint32_t n_patch, uint32_t patch_size, int normalize, float* x, void* stream) {
+    if (n_patch == 0) return LAE_OK;
+    if (!pred || !gt || !x) return LAE_ENULL;
+    if (patch_size == 0 || patch_size > 4096u || (uint64_t)n_patch * patch_size * patch_size > 0x7fffffffull) return LAE_EINVAL;
+    const uint32_t PP = patch_size * patch_size, n_rows = n_patch * PP;
+    k_patch_pack<<<lae::cdiv(n_rows, EV_THREADS), EV_THREADS, 0, STREAM(stream)>>>(pred, gt, n_rows, PP, normalize != 0, x);
+    return lae::check_launch("patch_pack");
+}
+
+int lae_patch_unpack_grad(const float* grad_x, uint32_t n_patch, uint32_t patch_size, int normalize, float* grad_pred, void* stream) {
+    if (n_patch == 0) return LAE_OK;
+    if (!grad_x || !grad_pred) return LAE_ENULL;
+    if (patch_size == 0 || patch_size > 4096u || (uint64_t)n_patch * patch_size * patch_size > 0x7fffffffull) return LAE_EINVAL;
+    const uint32_t PP = patch_size * patch_size, n_rows = n_patch * PP;
+    k_patch_unpack_grad<<<lae::cdiv(n_rows, EV_THREADS), EV_THREADS, 0, STREAM(stream)>>>(grad_x, n_rows, PP, normalize != 0, grad_pred);
+    return lae::check_launch("patch_unpack_grad");
 }
 
 int lae_consistency_pair(const void* frame_a, const void* frame_b, int frame_dtype, const float* depth_a, const float* opacity_a,

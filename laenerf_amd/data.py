@@ -16,6 +16,9 @@ pixels of a batch are drawn by 128 x 128 cell weights per image (`lae_sample_tra
 without-replacement algorithm, then a uniform pixel inside each cell), and `update_error_map` writes the per-ray error back
 (`lae_error_map_update`).  `draw_cells`, `cell_pixels` and `ema_update` restate both rules in numpy.
 
+`sample(n_rays, patch_size=P)` draws n_rays / P^2 square patches of P x P pixels instead of independent pixels (the reference's
+--patch_size, nerf/utils.py:88-105; `lae_sample_train_batch_patch`, restated by `draw_patches`): the batch the Trainer's LPIPS term needs.
+
 After `enable_exposure_refinement()` the batch's targets are multiplied by a per-image, per-channel gain before the blend
 (`lae_sample_train_batch_gain` / `_weighted_gain`) and `exposure_step` learns those gains from the step's image (csrc/exposure.hip;
 laenerf_amd/exposure.py restates it).
@@ -30,7 +33,7 @@ import torch
 from . import _lib
 from ._lib import check, ptr, stream
 
-__all__ = ["ResidentImages", "nerf_matrix_to_ngp", "philox4x32_10", "draw_indices", "draw_background", "neg_log_u", "cell_keys",
+__all__ = ["ResidentImages", "nerf_matrix_to_ngp", "philox4x32_10", "draw_indices", "draw_patches", "draw_background", "neg_log_u", "cell_keys",
            "draw_cells", "cell_pixels", "cell_span", "ema_update", "ERROR_MAP_CELLS"]
 
 _DTYPES = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
@@ -88,6 +91,24 @@ def draw_indices(seed, step, n_rays, n_img, H, W, mode="image"):
     img_ray = np.full(n_rays, 0xFFFFFFFF, dtype=np.uint64) if mode == "image" else rays
     img = _scale(_u32(seed, step, img_ray, 1), n_img)
     return img, pix
+
+
+def draw_patches(seed, step, n_patch, P, n_img, H, W, mode="image"):
+    """numpy restatement of the patch sampler's draw (lae_sample_train_batch_patch) -> (image [n_patch], row [n_patch],
+    col [n_patch], inds [n_patch * P^2]), all int64: the top-left corner of patch q from words 5 and 6 of "ray" q with the
+    reference's exclusive bounds H - P and W - P (nerf/utils.py:93-94), its image from word 1 of 0xFFFFFFFF ('image') or of q
+    ('all'), and inds = image * H * W + y * W + x of its pixels in row-major order"""
+    P = int(P)
+    if not 2 <= P < min(H, W):
+        raise ValueError("draw_patches: 2 <= P < min(H, W) expected")
+    q = np.arange(n_patch, dtype=np.uint64)
+    row = _scale(_u32(seed, step, q, 5), H - P)
+    col = _scale(_u32(seed, step, q, 6), W - P)
+    img_ray = np.full(n_patch, 0xFFFFFFFF, dtype=np.uint64) if mode == "image" else q
+    img = _scale(_u32(seed, step, img_ray, 1), n_img)
+    i, j = np.divmod(np.arange(P * P, dtype=np.int64), P)
+    inds = img[:, None] * (H * W) + (row[:, None] + i[None]) * W + (col[:, None] + j[None])
+    return img, row, col, inds.reshape(-1)
 
 
 def draw_background(seed, step, n_rays):
@@ -486,11 +507,51 @@ class ResidentImages:
         return out
 
     @torch.no_grad()
-    def sample(self, n_rays, step=None, out=None):
+    def check_patch_size(self, n_rays, patch_size):
+        """the reasons sample(n_rays, patch_size=...) refuses (ValueError); nothing is changed"""
+        P = int(patch_size)
+        if self.error_map is not None:
+            raise ValueError("ResidentImages: patches cannot be drawn by an error map (the reference ignores the map under --patch_size; "
+                             "this sampler refuses)")
+        if self.gains is not None:
+            raise ValueError("ResidentImages: patches cannot be combined with exposure gains (there is no gained patch sampler)")
+        if not 2 <= P < min(self.H, self.W):
+            raise ValueError(f"ResidentImages: patch_size must be in [2, min(H, W)) = [2, {min(self.H, self.W)}), got {P}")
+        if int(n_rays) < P * P or int(n_rays) % (P * P):
+            raise ValueError(f"ResidentImages: with patch_size {P}, n_rays must be a positive multiple of {P * P}, got {int(n_rays)}")
+        return P
+
+    def _sample_patch(self, n_rays, P, step, out):
+        """sample() with patch_size > 1: lae_sample_train_batch_patch; the result also holds "patch_size" """
+        P = self.check_patch_size(n_rays, P)
+        _lib.need_cuda(self.images)
+        if step is not None:
+            self.step.fill_(int(step))
+        o = out if out is not None else self._buffers(int(n_rays))
+        fx, fy, cx, cy = self.intrinsics
+        check(_lib.load().lae_sample_train_batch_patch(
+            ptr(self.images), _DTYPES[self.images.dtype], self.n_img, self.H, self.W, self.C, ptr(self._sample_poses()), fx, fy, cx, cy,
+            int(n_rays), P, ptr(self.aabb), self.min_near, self.seed, ptr(self.step), _MODES[self.mode], _BGS[self.bg],
+            int(self.color_space == "linear"), ptr(o["rays_o"]), ptr(o["rays_d"]), ptr(o["nears"]), ptr(o["fars"]), ptr(o["gt"]),
+            ptr(o["bg"]), ptr(o["inds"]), stream()), "sample_train_batch_patch")
+        res = {k: v for k, v in o.items() if k != "patch_size"}
+        if res["bg"] is None:
+            res["bg"] = 1
+        res["patch_size"] = P
+        return res
+
+    @torch.no_grad()
+    def sample(self, n_rays, step=None, out=None, patch_size=1):
         """one batch of n_rays -> dict rays_o, rays_d [N,3], nears, fars [N], gt [N,3] (blended), bg [N,3] ('random') or the
         number 1 ('white'), inds [N] (image * H * W + pixel).  step=None: the device counter's value, which the call then
         advances (capturable); step=k: the counter is set to k first.  The result tensors are reused by the next call with
-        the same n_rays unless `out` (a dict of tensors from an earlier call) is passed."""
+        the same n_rays unless `out` (a dict of tensors from an earlier call) is passed.
+        patch_size=P > 1 (the reference's --patch_size): the batch is n_rays / P^2 square patches of P x P pixels, ray r being pixel
+        (r % P^2) / P, r % P of patch r / P^2 (`lae_sample_train_batch_patch`; `draw_patches` restates the draw); the result gains
+        "patch_size".  In mode 'all' every patch draws its own image.  Refused (ValueError) with an error map or exposure gains on
+        the data."""
+        if int(patch_size) != 1:
+            return self._sample_patch(n_rays, patch_size, step, out)
         if self.error_map is not None:
             return self._sample_weighted(n_rays, step, out)
         _lib.need_cuda(self.images)

@@ -73,6 +73,58 @@ class _colour_scaled(Function):
         return grad * grad_out, None, None, None, None
 
 
+class _patch_pack(Function):
+    """lae_patch_pack forward, lae_patch_unpack_grad backward: a patch batch's rows <-> the input of LPIPS' trunk"""
+
+    @staticmethod
+    def forward(ctx, pred, gt, P, normalize):
+        pred = pred.float().contiguous()
+        gt = gt.float().contiguous()
+        _lib.need_cuda(pred, gt)
+        n = pred.shape[0] // (P * P)
+        x = torch.empty(2 * n, 3, P, P, dtype=torch.float32, device=pred.device)
+        _lib.check(_lib.load().lae_patch_pack(pred.data_ptr(), gt.data_ptr(), n, P, int(normalize), x.data_ptr(), _lib.stream()),
+                   "patch_pack")
+        ctx.dims = (n, P, int(normalize))
+        return x
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        n, P, normalize = ctx.dims
+        grad_x = grad_x.float().contiguous()
+        grad_pred = torch.empty(n * P * P, 3, dtype=torch.float32, device=grad_x.device)
+        _lib.check(_lib.load().lae_patch_unpack_grad(grad_x.data_ptr(), n, P, normalize, grad_pred.data_ptr(), _lib.stream()),
+                   "patch_unpack_grad")
+        return grad_pred, None, None, None
+
+
+def patch_pack(pred_rows, gt_rows, patch_size, normalize=False):
+    """pred_rows / gt_rows [n_patch * P^2, 3] (the rows of a patch batch, ResidentImages.sample(patch_size=P)) -> the trunk's input
+    [2 * n_patch, 3, P, P] (image 2p the ground truth, 2p + 1 the prediction) with autograd onto pred_rows"""
+    P = int(patch_size)
+    if pred_rows.dim() != 2 or pred_rows.shape[1] != 3 or pred_rows.shape != gt_rows.shape or P < 1 or pred_rows.shape[0] % (P * P) \
+            or pred_rows.shape[0] == 0:
+        raise ValueError("patch_pack: pred_rows and gt_rows must be [n_patch * patch_size^2, 3]")
+    return _patch_pack.apply(pred_rows, gt_rows, P, bool(normalize))
+
+
+def lpips_patch_loss(pred_rows, gt_rows, patch_size, lpips, normalize=False):
+    """the reference's perceptual term on a patch batch (nerf/utils.py:594-603): the mean over the patches of
+    LPIPS_alex(pred_patch, gt_patch) as an fp32 scalar with autograd onto pred_rows; `.per_patch` holds the float64 distances.
+    The chain: lae_patch_pack -> `lpips`' AlexNet trunk through torch autograd (MIOpen) -> lae_lpips_head, and back through
+    lae_lpips_head_grad -> the trunk -> lae_patch_unpack_grad: one launch per kernel, no host read, capturable.
+    normalize=False is the reference's call ([0, 1] images into lpips with its default normalize=False); True is lpips' documented
+    input range.  patch_size >= 32: below it AlexNet's second max-pool has no output."""
+    from .metrics import lpips_features, lpips_head
+    if int(patch_size) < 32:
+        raise ValueError("lpips_patch_loss: patch_size must be at least 32 (below it AlexNet's second max-pool has no output)")
+    x = patch_pack(pred_rows, gt_rows, patch_size, normalize)
+    d = lpips_head(lpips, lpips_features(lpips, x), both=False)
+    out = d.mean().float()
+    out.per_patch = d.detach()
+    return out
+
+
 def colour_loss_scaled(pred, target, scaler=None, loss="mse", huber_delta=0.1):
     """mse_loss_scaled with the criterion chosen by `loss`: 'mse', 'l1', 'huber' (the reference's loss.py huber_loss =
     torch's HuberLoss(huber_delta) / huber_delta) or 'mape' (loss.py mape_loss), the mean over all elements

@@ -21,6 +21,7 @@ Nothing is downloaded: the weights come from files (or dicts) the user already h
 weights for tests and benchmarks.  Parity with the lpips package itself is pinned only by a restatement (tests/lpips_util.py):
 neither the package nor its pretrained weights were available to test against.
 """
+import contextlib
 import ctypes
 import json
 import math
@@ -34,7 +35,7 @@ from . import _lib
 from ._lib import check, ptr, stream
 
 __all__ = ["LPIPS", "alexnet_trunk", "load_lpips_alex", "load_masks", "eval_view", "eval_view_numpy", "psnr_from_sse",
-           "consistency_pair", "consistency_numpy", "ALEX_CHANNELS", "ALEX_TAPS", "LPIPS_SHIFT", "LPIPS_SCALE", "EVAL_SCRATCH_DOUBLES", "CONSISTENCY_SCRATCH_DOUBLES"]
+           "consistency_pair", "consistency_numpy", "lpips_head", "lpips_head_numpy", "lpips_head_grad_numpy", "patch_pack_numpy", "ALEX_CHANNELS", "ALEX_TAPS", "LPIPS_SHIFT", "LPIPS_SCALE", "EVAL_SCRATCH_DOUBLES", "CONSISTENCY_SCRATCH_DOUBLES"]
 
 ALEX_CHANNELS = (64, 192, 384, 256, 256)
 ALEX_TAPS = (1, 4, 7, 9, 11)                  # relu1..relu5 of torchvision's alexnet().features (lpips' pretrained alexnet slices)
@@ -135,6 +136,155 @@ class LPIPS(nn.Module):
 
     def forward(self, x, out=None):
         return self.head(self.features(x.reshape(-1, *x.shape[-3:])), out=out)
+
+    def features_grad(self, x):
+        """features() without no_grad: the five taps as part of x's autograd graph (fp32, autocast off; the trunk's weights stay
+        frozen, so its backward computes input gradients only) -- LPIPS as a training term, losses.lpips_patch_loss"""
+        out = []
+        with _deterministic_convs(), torch.autocast("cuda", enabled=False):
+            h = x.float()
+            for i, layer in enumerate(self.trunk):
+                h = layer(h)
+                if i in ALEX_TAPS:
+                    out.append(h.contiguous())
+        return out
+
+    def head_grad(self, feats, gout, both=False):
+        """the gradient of head() with respect to the taps (lae_lpips_head_grad, one launch): gout float64 [B] on the device ->
+        five fp32 tensors shaped like feats; both=False writes zeros into the x0 (ground-truth) rows.  A pixel whose feature
+        norm is exactly 0 gets a zero gradient on that side (include/laenerf.h; `lpips_head_grad_numpy` restates it)"""
+        n2 = int(feats[0].shape[0])
+        B = n2 // 2
+        if len(feats) != 5 or n2 % 2:
+            raise ValueError("LPIPS.head_grad: five feature maps of 2B images expected")
+        for f, c in zip(feats, ALEX_CHANNELS):
+            if f.dim() != 4 or f.shape[0] != n2 or f.shape[1] != c or f.dtype != torch.float32 or not f.is_contiguous():
+                raise ValueError("LPIPS.head_grad: contiguous fp32 [2B, C, h, w] feature maps expected")
+        if gout.dtype != torch.float64 or gout.numel() != B or not gout.is_contiguous():
+            raise ValueError("LPIPS.head_grad: gout must be a contiguous float64 tensor of B values")
+        _lib.need_cuda(*feats, *self.lins, gout)
+        hw = [int(f.shape[2] * f.shape[3]) for f in feats]
+        grads = [torch.empty_like(f) for f in feats]
+        arr = lambda ts: (ctypes.c_void_p * 5)(*[t.data_ptr() for t in ts])
+        check(_lib.load().lae_lpips_head_grad(5, arr(feats), arr(self.lins), (ctypes.c_uint32 * 5)(*ALEX_CHANNELS),
+                                              (ctypes.c_uint32 * 5)(*hw), B, ptr(gout), arr(grads), int(bool(both)), stream()),
+              "lpips_head_grad")
+        return grads
+
+
+@contextlib.contextmanager
+def _deterministic_convs():
+    """torch's request for deterministic convolution algorithms, for the block's duration.  On maps as small as a patch's, the
+    trunk's convolutions were seen to differ in their last bits from call to call on the same input (measured: features of the
+    last two taps, about 4e-9), and a training run is to repeat bit for bit -- graph replay against eager steps, a
+    resumed run against the uninterrupted one.  The flag is read when a convolution runs, forward or backward."""
+    was = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    try:
+        yield
+    finally:
+        torch.backends.cudnn.deterministic = was
+
+
+class _LpipsTrunk(torch.autograd.Function):
+    """LPIPS.features_grad as one autograd node, so that the trunk's backward runs under _deterministic_convs like its forward"""
+
+    @staticmethod
+    def forward(ctx, lp, x):
+        with torch.enable_grad():
+            xd = x.detach().requires_grad_(True)
+            feats = lp.features_grad(xd)
+        ctx.xd, ctx.feats = xd, feats
+        return tuple(f.detach() for f in feats)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        with _deterministic_convs():
+            (gx,) = torch.autograd.grad(ctx.feats, ctx.xd, grads)
+        return None, gx
+
+
+def lpips_features(lp, x):
+    """lp.features_grad(x) with the trunk's backward as deterministic as its forward -> the five taps, part of x's autograd graph"""
+    return list(_LpipsTrunk.apply(lp, x))
+
+
+class _LpipsHead(torch.autograd.Function):
+    """LPIPS.head with a gradient: lae_lpips_head forward, lae_lpips_head_grad backward (one launch each over the five layers)"""
+
+    @staticmethod
+    def forward(ctx, lp, both, *feats):
+        feats = [f.detach() for f in feats]
+        ctx.lp, ctx.both = lp, both
+        ctx.save_for_backward(*feats)
+        return lp.head(feats)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return (None, None, *ctx.lp.head_grad(list(ctx.saved_tensors), gout.to(torch.float64).contiguous(), ctx.both))
+
+
+def lpips_head(lp, feats, both=True):
+    """lp.head(feats) -> [B] float64 with autograd onto the taps (both=False: onto the x1 rows only, zeros for the x0 rows)"""
+    return _LpipsHead.apply(lp, bool(both), *feats)
+
+
+def _pairs(f):
+    f = np.asarray(f, dtype=np.float64)
+    f = f.reshape(f.shape[0], f.shape[1], -1)
+    return f, f[0::2], f[1::2]
+
+
+def lpips_head_numpy(feats, weights):
+    """float64 restatement of lae_lpips_head: feats a list of [2B, C, ...] arrays (pairs = consecutive rows), weights a list of
+    [C] -> [B] float64, sum_l mean_px sum_c w_c (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2"""
+    total = 0.0
+    for f, w in zip(feats, weights):
+        _, f0, f1 = _pairs(f)
+        w = np.asarray(w, dtype=np.float64).reshape(1, -1, 1)
+        n0, n1 = np.sqrt((f0 * f0).sum(1, keepdims=True)), np.sqrt((f1 * f1).sum(1, keepdims=True))
+        d = f0 / (n0 + 1e-10) - f1 / (n1 + 1e-10)
+        total = total + (w * d * d).sum(1).mean(-1)
+    return total
+
+
+def lpips_head_grad_numpy(feats, weights, gout, both=True):
+    """float64 restatement of lae_lpips_head_grad -> a list of arrays shaped like feats: the gradient of
+    sum_p gout[p] * lpips_head_numpy(...)[p] with respect to the features, the zero-norm rule included (a pixel whose norm is
+    exactly 0 gets a zero gradient on that side); both=False: zeros in the x0 rows"""
+    gout = np.asarray(gout, dtype=np.float64).reshape(-1, 1, 1)
+    out = []
+    for f, w in zip(feats, weights):
+        shape = np.asarray(f).shape
+        f, f0, f1 = _pairs(f)
+        hw = f.shape[2]
+        w = np.asarray(w, dtype=np.float64).reshape(1, -1, 1)
+        n0, n1 = np.sqrt((f0 * f0).sum(1, keepdims=True)), np.sqrt((f1 * f1).sum(1, keepdims=True))
+        e0, e1 = n0 + 1e-10, n1 + 1e-10
+        wd = w * (f0 / e0 - f1 / e1)
+        a0, a1 = (wd * f0).sum(1, keepdims=True), (wd * f1).sum(1, keepdims=True)
+        k = 2.0 * gout / hw
+        g = np.zeros_like(f)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if both:
+                g[0::2] = np.where(n0 != 0, k * (wd / e0 - f0 * (a0 / (n0 * e0 * e0))), 0.0)
+            g[1::2] = np.where(n1 != 0, -k * (wd / e1 - f1 * (a1 / (n1 * e1 * e1))), 0.0)
+        out.append(g.reshape(shape))
+    return out
+
+
+def patch_pack_numpy(pred, gt, patch_size, normalize=False):
+    """float32 restatement of lae_patch_pack: pred / gt [n_patch * P^2, 3] -> [2 * n_patch, 3, P, P], image 2p the ground truth of patch
+    p, 2p + 1 its prediction, ((2v - 1 if normalize else v) - shift) / scale with eval_view_numpy's statements"""
+    f32 = np.float32
+    P = int(patch_size)
+    shift, scale = np.array(LPIPS_SHIFT, f32)[:, None], np.array(LPIPS_SCALE, f32)[:, None]
+    planes = []
+    for v in (gt, pred):
+        v = np.asarray(v, dtype=f32).reshape(-1, P * P, 3)
+        u = f32(2) * v - f32(1) if normalize else v
+        planes.append(((u.transpose(0, 2, 1) - shift) / scale).astype(f32))
+    return np.stack(planes, 1).reshape(-1, 3, P, P)
 
 
 def _state_dict(src):

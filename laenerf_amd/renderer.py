@@ -64,6 +64,9 @@ class NeRFRenderer(nn.Module):
         self.register_buffer("step_counter", torch.zeros(16, 2, dtype=torch.int32))
         self.mean_count = 0
         self.local_step = 0
+        # patch training (Trainer(patch_size > 1)): count_limit, a device int32 holding the sample limit the steps march under, makes
+        # update_extra_state also keep the largest per-step count and the number of steps that asked for more than their limit
+        self.count_limit, self.peak_count, self.truncated_steps = None, 0, 0
 
     # ---- checkpoints of the reference: there NeRFNetwork IS the renderer (class NeRFNetwork(NeRFRenderer)), so its
     # state_dict has `encoder.embeddings`, `sigma_net.weights`, ... next to `density_grid`, `aabb_train`, ...; here the network
@@ -104,6 +107,7 @@ class NeRFRenderer(nn.Module):
         self.step_counter.zero_()
         self.mean_count = 0
         self.local_step = 0
+        self.peak_count = self.truncated_steps = 0
 
     def density(self, x):
         return self.model.density(x)
@@ -258,7 +262,16 @@ class NeRFRenderer(nn.Module):
         total_step = min(16, self.local_step)
         mean_t = torch.mean(self.density_grid.clamp(min=0)).double()
         cnt_t = self.step_counter[:total_step, 0].sum().double() if total_step > 0 else mean_t.new_zeros(())
-        mean_v, cnt_v = torch.stack([mean_t, cnt_t]).tolist()
+        count_limit = getattr(self, "count_limit", None)
+        if count_limit is not None and total_step > 0:
+            # the Trainer's patch mode sizes its march from the LARGEST per-step count: it and the number of steps whose count
+            # exceeded the limit they marched under (count_limit, a device int32) travel in the same copy
+            c = self.step_counter[:total_step, 0]
+            mean_v, cnt_v, peak_v, trunc_v = torch.stack([mean_t, cnt_t, c.max().double(), (c > count_limit).sum().double()]).tolist()
+            self.peak_count = max(int(getattr(self, "peak_count", 0)), int(peak_v))
+            self.truncated_steps = int(getattr(self, "truncated_steps", 0)) + int(trunc_v)
+        else:
+            mean_v, cnt_v = torch.stack([mean_t, cnt_t]).tolist()
         self.mean_density = mean_v                                             # the fp32 mean, exactly what `.item()` returned
         self.iter_density += 1
         density_thresh = min(self.mean_density, self.density_thresh)

@@ -176,6 +176,17 @@ class Trainer:
     Adam's; exposure_mode 'rgb' or 'gray': three gains or one per image; exposure_center: publish 2^(e - mean) rather than 2^e) inside the same groups (module docstring); exposures() and gains()
     report them, a checkpoint carries their state (the data's entry), exposure_lr=0 leaves the run's losses and parameters bit for bit
     as without it.  Combines with every other term but second_weight, whose second target is synthetic and is not gained (ValueError).
+    patch_size: 1 (every path as it is, bit for bit) or P >= 32, the reference's --patch_size: a step trains num_rays // P^2 square patches
+    of P x P pixels (ResidentImages.sample(patch_size=P)) on `colour criterion + perceptual_weight * LPIPS_alex(pred patches, gt patches)`
+    (nerf/utils.py:594-603), with lpips a metrics.LPIPS (required; its frozen weights are not part of a checkpoint: pass the same object
+    again on a resume) and perceptual_normalize lpips' `normalize` flag (False: the reference's call).  The step renders the
+    differentiable image (shade_train without gt; the fused criterion kernel is not used) and evaluates losses.colour_loss_scaled and
+    losses.lpips_patch_loss on it.  The march's limit is min(N * max_steps, round_up(patch_headroom * the largest per-step sample
+    count seen so far, 128)) -- a patch on empty space has no samples, one on the object many, so the mean would truncate -- and the
+    steps before any count exists march with force_all_rays.  perceptual_losses() holds the per-step LPIPS mean without its weight,
+    truncated_steps() the steps that asked for more samples than their limit, peak_to_mean() the largest count over the mean.  All
+    four `loss` kinds and ema_decay work; error_map, depth_weight, distort_weight, opacity_weight, pixel_weights, second_weight,
+    pose_refine and exposure_refine are refused (ValueError) before anything is changed on the data.
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
@@ -184,11 +195,37 @@ class Trainer:
                  distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True,
                  pixel_weights=False, second_weight=None, pose_refine=False, pose_lr=1e-3, pose_betas=(0.9, 0.99), pose_eps=1e-15,
                  exposure_refine=False, exposure_lr=1e-2, exposure_mode="rgb", exposure_betas=(0.9, 0.99), exposure_eps=1e-15,
-                 exposure_center=True):
+                 exposure_center=True, patch_size=1, perceptual_weight=1e-3, lpips=None, perceptual_normalize=False, patch_headroom=2.0):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
         if error_map not in (None, "ema", "fixed"):
             raise ValueError("Trainer: error_map must be None, 'ema' or 'fixed'")
+        patch_size = int(patch_size)
+        if patch_size != 1:                                           # refused before anything is changed on the data
+            from .metrics import LPIPS
+            if patch_size < 32:
+                raise ValueError("Trainer: patch_size must be 1 or at least 32 (below 32 AlexNet's second max-pool has no output, "
+                                 "so the LPIPS term does not exist)")
+            if not isinstance(lpips, LPIPS):
+                raise ValueError("Trainer: patch_size > 1 needs lpips=, a metrics.LPIPS (load_lpips_alex(...) or LPIPS.random(seed))")
+            on = {"error_map": error_map is not None or getattr(data, "error_map", None) is not None, "depth_weight": depth_weight is not None,
+                  "distort_weight": distort_weight is not None, "opacity_weight": opacity_weight is not None,
+                  "pixel_weights": bool(pixel_weights), "second_weight": second_weight is not None, "pose_refine": bool(pose_refine),
+                  "exposure_refine": bool(exposure_refine) or getattr(data, "gains", None) is not None}
+            bad = [k for k, v in on.items() if v]
+            if bad:
+                raise ValueError("Trainer: patch_size > 1 cannot be combined with " + ", ".join(bad) + " (they live in or around the fused "
+                                 "criterion kernel, which a patch step does not use)")
+            if patch_size >= min(data.H, data.W):
+                raise ValueError(f"Trainer: patch_size must be smaller than the images ({data.H} x {data.W})")
+            if int(num_rays) // (patch_size * patch_size) < 1:
+                raise ValueError(f"Trainer: num_rays = {int(num_rays)} holds no patch of {patch_size} x {patch_size} pixels")
+            if not (float(perceptual_weight) >= 0.0) or float(perceptual_weight) == float("inf"):
+                raise ValueError("Trainer: perceptual_weight must be finite and >= 0")
+            if not (float(patch_headroom) >= 1.0) or float(patch_headroom) == float("inf"):
+                raise ValueError("Trainer: patch_headroom must be finite and >= 1")
+            from .backend import loss_kind
+            loss_kind("Trainer", loss, huber_delta)
         if pixel_weights or second_weight is not None:                # refused before anything is changed on the data
             from .backend import loss_kind
             loss_kind("Trainer", loss, huber_delta)
@@ -283,6 +320,18 @@ class Trainer:
             data.enable_exposure_refinement(exposure_mode)
             self.exposure_lr_table = torch.from_numpy(lr_schedule(self.exposure_lr, self.iters, self.iters + 1, 1)).to(dev)
             self.exposure_lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.patch_size, self.perceptual_weight = patch_size, float(perceptual_weight)
+        self.perceptual_normalize, self.patch_headroom = bool(perceptual_normalize), float(patch_headroom)
+        self.lpips = None
+        self.skip_perceptual = False             # patch mode only: leave the LPIPS chain out of the step (what perceptual_weight=0 must equal)
+        self.n_rays = self.num_rays              # the rays a step trains
+        self.perceptual_slots = None
+        self._perceptual_hist = []
+        if patch_size != 1:
+            self.lpips = lpips.to(dev)
+            self.n_rays = (self.num_rays // (patch_size * patch_size)) * patch_size * patch_size
+            self.perceptual_slots = torch.zeros(GROUP, dtype=torch.float32, device=dev)
+            renderer.count_limit = self.m_limit  # the refresh keeps the largest per-step count and the truncated steps (renderer.py)
         self.global_step = 0
         self.started = False
         self.graphs = {}
@@ -298,7 +347,19 @@ class Trainer:
         self.ema = None if ema_decay is None else _TrainerEMA(renderer, optimizer, float(ema_decay))
 
     # ------------------------------------------------------------------ one step
+    def _sized(self):
+        """whether a sample count of earlier steps exists to size the march from (else: a host-sized march)"""
+        return self.r.mean_count > 0 if self.patch_size == 1 else self.r.peak_count > 0
+
+    def _all_rows(self):
+        return self.n_rays * self.max_steps      # force_all_rays' buffer: no ray can be truncated
+
     def _m(self):
+        if self.patch_size != 1:
+            # patch batches differ far more in samples per step than uniform ones (a patch on empty space has none): the limit is
+            # patch_headroom times the LARGEST count seen so far, not the mean
+            want = int(math.ceil(self.patch_headroom * self.r.peak_count))
+            return min(self._all_rows(), -(-want // 128) * 128)
         return round_up_always(self.r.mean_count, 128)
 
     def _m_cap(self):
@@ -315,6 +376,8 @@ class Trainer:
                 self.pose_lr_dev.copy_(self.pose_lr_table.index_select(0, row).view(-1))
             if self.exposure_refine:
                 self.exposure_lr_dev.copy_(self.exposure_lr_table.index_select(0, row).view(-1))
+        if self.patch_size != 1:
+            return self._patch_step(k, m_cap)
         b = self.data.sample(self.num_rays)
         counter = r.step_counter[r.local_step % GROUP]
         counter.zero_()
@@ -373,6 +436,44 @@ class Trainer:
         with torch.no_grad():
             self.loss_slots[k].copy_(loss.unscaled.view(()))
 
+    def _patch_step(self, k, m_cap):
+        """_step with patch_size > 1: a patch batch, the differentiable image of composite_rays_train_blend (shade_train without gt),
+        then colour criterion + perceptual_weight * LPIPS on the patches (losses.lpips_patch_loss), operator by operator"""
+        from .losses import colour_loss_scaled, lpips_patch_loss
+        r, opt = self.r, self.opt
+        b = self.data.sample(self.n_rays, patch_size=self.patch_size)
+        counter = r.step_counter[r.local_step % GROUP]
+        counter.zero_()
+        r.local_step += 1
+        with torch.autocast("cuda", dtype=torch.float16):
+            if m_cap is None:                                          # no count yet: every ray keeps all its samples
+                xyzs, dirs, deltas, rays = raymarching.march_rays_train(
+                    b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
+                    r.mean_count, True, 128, True, self.dt_gamma, self.max_steps)
+            else:
+                xyzs, dirs, deltas, rays = raymarching.march_rays_train(
+                    b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
+                    perturb=True, dt_gamma=self.dt_gamma, max_steps=self.max_steps, m_limit=self.m_limit, capacity=m_cap)
+            if not torch.cuda.is_current_stream_capturing():
+                self._rows_seen = max(self._rows_seen, xyzs.shape[0])
+            res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"])
+        image = res["image"]
+        loss = colour_loss_scaled(image, b["gt"], opt, self.loss, self.huber_delta)
+        total = loss.unscaled
+        if not self.skip_perceptual:
+            lp = lpips_patch_loss(image, b["gt"], self.patch_size, self.lpips, self.perceptual_normalize)
+            term = self.perceptual_weight * lp
+            total = total + term.detach()
+            loss = loss + (term * opt._scale_view[0] if opt.use_scaler else term)
+            with torch.no_grad():
+                self.perceptual_slots[k].copy_(lp.detach())
+        opt.backward(loss)
+        opt.step()
+        if self.ema is not None:
+            self.ema.update_gated(self.data.step, self.epoch_len)
+        with torch.no_grad():
+            self.loss_slots[k].copy_(total.view(()))
+
     def _refresh(self):
         with torch.autocast("cuda", dtype=torch.float16):
             self.r.update_extra_state()
@@ -414,15 +515,20 @@ class Trainer:
             if self.global_step % GROUP == 0:
                 self._refresh()
             pos = self.global_step % GROUP
-            if r.mean_count > 0:
+            sized = self._sized()
+            if sized:
                 self.m_limit.fill_(self._m())
-            if self.graph and r.mean_count > 0 and pos == 0 and n_steps - done >= GROUP:
+            elif self.patch_size != 1:
+                self.m_limit.fill_(self._all_rows())                   # what a force_all_rays step marches under
+            if self.graph and sized and pos == 0 and n_steps - done >= GROUP:
                 self._run_group(self._m_cap())
                 n = GROUP
             else:
-                self._step(pos, self._m_cap() if r.mean_count > 0 else None)
+                self._step(pos, self._m_cap() if sized else None)
                 n = 1
             self._loss_hist.append(self.loss_slots[pos:pos + n].clone())
+            if self.perceptual_slots is not None:
+                self._perceptual_hist.append(self.perceptual_slots[pos:pos + n].clone())
             if self.depth_slots is not None:
                 self._depth_hist.append(self.depth_slots[pos:pos + n, 1].clone())
             if self.distort_slots is not None:
@@ -473,6 +579,29 @@ class Trainer:
         if not self._second_hist:
             return np.zeros(0, np.float32)
         return torch.cat(self._second_hist).cpu().numpy()
+
+    def perceptual_losses(self):
+        """per-step LPIPS term (the mean over the step's patches), without its weight, as a float32 numpy array (empty without
+        patch_size > 1; zeros for steps run with skip_perceptual)"""
+        if not self._perceptual_hist:
+            return np.zeros(0, np.float32)
+        return torch.cat(self._perceptual_hist).cpu().numpy()
+
+    def truncated_steps(self):
+        """patch mode: the number of steps so far whose requested sample count exceeded the limit they marched under, so that rays
+        inside patches lost samples (0 is what patch_headroom is chosen for); from the step counters: the groups already refreshed
+        were counted with the refresh's host read, the steps since then cost one read here.  Always 0 without patch_size > 1."""
+        if self.patch_size == 1:
+            return 0
+        r = self.r
+        n = min(GROUP, r.local_step)
+        tail = int((r.step_counter[:n, 0] > self.m_limit).sum().item()) if n > 0 else 0
+        return int(r.truncated_steps) + tail
+
+    def peak_to_mean(self):
+        """patch mode: the largest per-step sample count seen so far over the last refresh's mean count (0.0 before either exists)"""
+        r = self.r
+        return float(r.peak_count) / float(r.mean_count) if self.patch_size != 1 and r.mean_count > 0 else 0.0
 
     def refined_poses(self):
         """the training cameras as the next batch reads them, [n_img, 4, 4] fp32 on the device (a copy; data.poses without pose_refine)"""
@@ -540,6 +669,9 @@ class Trainer:
             cfg["exposure_refine"], cfg["exposure_lr"], cfg["exposure_mode"] = True, self.exposure_lr, self.exposure_mode
             cfg["exposure_betas"], cfg["exposure_eps"] = list(self.exposure_betas), self.exposure_eps
             cfg["exposure_center"] = self.exposure_center
+        if self.patch_size != 1:
+            cfg["patch_size"], cfg["perceptual_weight"] = self.patch_size, self.perceptual_weight
+            cfg["perceptual_normalize"], cfg["patch_headroom"] = self.perceptual_normalize, self.patch_headroom
         return cfg
 
     def state_dict(self, full=True):
@@ -560,6 +692,8 @@ class Trainer:
         extra = {"format": C.FORMAT, "lae_version": _lib.load().lae_version().decode(), "config": self.config(),
                  "shapes": C.shapes_of(model, "model."), "iter_density": int(r.iter_density), "local_step": int(r.local_step),
                  "data": self.data.state_dict(), "rng_state": torch.cuda.get_rng_state(dev).clone(), "touched_lines": None}
+        if self.patch_size != 1:                     # the march's size follows the largest count seen (only with patches: other files stay)
+            extra["patch"] = {"peak_count": int(r.peak_count), "truncated_steps": int(r.truncated_steps)}
         if full:
             o = opt.state_dict()
             sc = o.pop("scaler")
@@ -690,11 +824,16 @@ class Trainer:
         else:
             r.iter_density, r.local_step = self.global_step // GROUP, 0
             self.data.step.fill_(self.global_step)
-        if r.mean_count > 0:
+        if self.patch_size != 1 and extra is not None and isinstance(extra.get("patch"), dict):
+            r.peak_count, r.truncated_steps = int(extra["patch"]["peak_count"]), int(extra["patch"]["truncated_steps"])
+        if self._sized():
             self.m_limit.fill_(self._m())
+        elif self.patch_size != 1:
+            self.m_limit.fill_(self._all_rows())
         self.graphs = {}
         self._pool = None
         self._loss_hist, self._depth_hist, self._distort_hist, self._opacity_hist, self._second_hist = [], [], [], [], []
+        self._perceptual_hist = []
         self.started = True
         return self
 

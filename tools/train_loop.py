@@ -9,6 +9,7 @@ refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated o
                                 [--loss mse|l1|huber|mape] [--huber-delta D] [--entropy W] [--outliers P]
                                 [--mask-outliers P] [--pose-noise DEG,DIST] [--pose-lr LR]
                                 [--exposure-noise STOPS] [--exposure-lr LR]
+                                [--patch-size P] [--lpips-weight W] [--lpips-weights ALEXNET.pth,ALEX.pth]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
 ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR.
@@ -38,6 +39,10 @@ capture.  --exposure-lr LR: the student learns a gain per image and channel (Tra
 either the line carries "exposure": the RMS of the training images' log2 exposure error before and after the run (after: learned +
 applied, 0 = compensated) and the time of the two launches per step; compare heldout_psnr_white with and without --exposure-lr for
 what the refinement buys, and breakdown.replay_ms_per_step for its cost.
+--patch-size P --lpips-weight W [--lpips-weights ALEXNET.pth,ALEX.pth]: the student trains on rays // P^2 patches of P x P pixels per
+step with the LPIPS term (Trainer(patch_size=P, perceptual_weight=W, lpips=...)); without weight files the term uses LPIPS.random(0),
+seeded stand-in weights, and the line says so.  The line then carries "patch": ms_per_step (after the first 64 steps), truncated_steps,
+the peak-to-mean ratio of the per-step sample count, the LPIPS term's first and last 16-step mean and the held-out PSNR.
 --save PATH: the first student's checkpoint is written after the run (Trainer.save_checkpoint; a `.pth` path or a directory);
 --resume PATH: the first student loads it before training and then trains --steps further steps (the same --steps as the saved run
 keeps the learning-rate horizon, which the load checks).  The line then carries "checkpoint": the file size in bytes and the save /
@@ -111,7 +116,8 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
 
 def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=True, capacity="bucket", seed=0, student_seed=0,
                  error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True, distort_weight=None, loss="mse",
-                 huber_delta=0.1, opacity_weight=None, pixel_weights=None, pose_lr=None, exposure_lr=None):
+                 huber_delta=0.1, opacity_weight=None, pixel_weights=None, pose_lr=None, exposure_lr=None, patch_size=1, lpips=None,
+                 perceptual_weight=1e-3):
     from laenerf_amd.data import ResidentImages
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.optim import FusedAdam
@@ -133,6 +139,8 @@ def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=Tr
         depth_kw.update(pose_refine=True, pose_lr=pose_lr)
     if exposure_lr is not None:
         depth_kw.update(exposure_refine=True, exposure_lr=exposure_lr)
+    if patch_size != 1:
+        depth_kw.update(patch_size=patch_size, lpips=lpips, perceptual_weight=perceptual_weight)
     return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map,
                    ema_decay=ema_decay, **depth_kw)
 
@@ -204,6 +212,9 @@ def main():
     ap.add_argument("--pose-lr", type=float, default=None, metavar="LR", help="Trainer(pose_refine=True, pose_lr=LR)")
     ap.add_argument("--exposure-noise", type=float, default=None, metavar="STOPS", help="multiply every training image by 2^u, |u| <= STOPS")
     ap.add_argument("--exposure-lr", type=float, default=None, metavar="LR", help="Trainer(exposure_refine=True, exposure_lr=LR)")
+    ap.add_argument("--patch-size", type=int, default=1, metavar="P", help="Trainer(patch_size=P): rays // P^2 patches per step, LPIPS term")
+    ap.add_argument("--lpips-weight", type=float, default=1e-3, metavar="W", help="Trainer(perceptual_weight=W)")
+    ap.add_argument("--lpips-weights", default=None, metavar="ALEXNET.pth,ALEX.pth", help="torchvision alexnet + lpips v0.1 alex weights")
     ap.add_argument("--save", default=None, metavar="PATH", help="write the first student's checkpoint after the run")
     ap.add_argument("--resume", default=None, metavar="PATH", help="load a checkpoint into the first student before training")
     args = ap.parse_args()
@@ -227,6 +238,16 @@ def main():
             mask = np.where(hit, 0.0, 1.0).astype(np.float16)
     crit_kw = dict(loss=args.loss, huber_delta=args.huber_delta, opacity_weight=args.entropy, pixel_weights=mask, pose_lr=args.pose_lr,
                    exposure_lr=args.exposure_lr)
+    patch = None
+    if args.patch_size != 1:
+        from laenerf_amd.metrics import LPIPS, load_lpips_alex
+        if args.lpips_weights:
+            lp = load_lpips_alex(*args.lpips_weights.split(","), device=dev)
+        else:
+            lp = LPIPS.random(0, device=dev)
+        patch = {"patch_size": args.patch_size, "lpips_weight": args.lpips_weight,
+                 "lpips_weights": args.lpips_weights or "LPIPS.random(0): seeded stand-in weights, not a perceptual metric"}
+        crit_kw.update(patch_size=args.patch_size, lpips=lp, perceptual_weight=args.lpips_weight)
     true_poses = poses.copy()
     if args.pose_noise:
         from laenerf_amd.poses import perturb_poses
@@ -271,6 +292,11 @@ def main():
                     "end_rms_stops": rms(tr.exposures() + u)}
     # where the time goes (after the measurement; each part synchronised on its own): the refresh with its host read, a
     # 16-step replay at the current capacity, and the padding rows of that capacity
+    if patch is not None:
+        perc = tr.perceptual_losses()
+        patch.update(ms_per_step=round(steady, 4), rays_per_step=tr.n_rays, truncated_steps=tr.truncated_steps(),
+                     peak_count=int(tr.r.peak_count), peak_to_mean=round(tr.peak_to_mean(), 3), patch_headroom=tr.patch_headroom,
+                     first_lpips=float(perc[:16].mean()), final_lpips=float(perc[-16:].mean()), heldout_psnr_white=round(p, 3))
     refresh_ms, group_ms = _replay_windows(tr)
     if exposure is not None and args.exposure_lr is not None:
         exposure["step_and_publish_us"] = round(_exposure_launch_us(tr), 2)
@@ -312,6 +338,7 @@ def main():
         **({"mask_outliers": args.mask_outliers, "masked_pixels_frac": round(float((mask == 0).mean()), 4)} if mask is not None else {}),
         **({"pose": pose} if pose is not None else {}), **({"exposure": exposure} if exposure is not None else {}),
         **({"depth": depth} if depth is not None else {}), **({"checkpoint": ckpt} if ckpt else {}),
+        **({"patch": patch} if patch is not None else {}),
         "scene": f"{args.views - held} training + {held} held-out {args.res}x{args.res} RGBA uint8 views of a teacher network"}), flush=True)
 
 
