@@ -1109,6 +1109,28 @@ LAE_API int lae_grow_region(uint8_t* grid, const float* density_grid, uint32_t C
 LAE_API int lae_min_dist_to_points(const float* pts, uint32_t n, const float* set, uint32_t m, float max_dist, float* out,
                            float* out_max, void* scratch, void* stream);
 
+/* ---- the edit grid from 2D masks (csrc/masklift.hip, where the rule is written down in full; DESIGN.md section 4c;
+ * editing/mask_lift.py restates both kernels in numpy) ----
+ * lae_mask_lift_pack: one view's planes into ONE fp32 plane.  depth / opacity fp32 [HW]: the raw sum w t and the weights_sum of
+ *   render_eval(scale_depth=False); mask uint8 [HW], nonzero = selected.  packed[i] = |t_surf| with the sign bit set iff mask[i],
+ *   t_surf = depth / opacity (one correctly rounded division) if opacity >= min_opacity, else +inf; -0, +-inf and NaN are legal values.
+ *   NULL: LAE_ENULL; HW == 0, HW >= 2^31 or min_opacity <= 0: LAE_EINVAL.
+ * lae_mask_lift: the votes of V packed views [V,H,W] (poses fp32 [V,4,4] cam2world, row-major, on the device; one set of
+ *   intrinsics) on the cells of density_bitfield ([C*G^3/8] uint8, Morton order, cascade-major) and the decision per cell.
+ *   grid_out  uint8 [C*G^3/8], the selection in density_bitfield's layout; every byte is written, no zero fill needed
+ *   votes_out optional uint16 [C*G^3, 2]: (in, out) per cell, indexed like density_grid; zeros for cells that are not occupied
+ *   A cell is selected iff it is occupied, in >= min_views and float(in) >= min_share * float(in + out).  Poses go through LDS in
+ *   chunks of LAE_MASK_LIFT_POSE_CHUNK views.  No atomics, no host read, no allocation: capturable, and two calls give the same
+ *   bytes.  NULL packed / poses / density_bitfield / grid_out: LAE_ENULL; G not a power of two in [2, 128], C outside [1, 16],
+ *   V == 0 or V > 65535, H or W < 1, H * W >= 2^31, fx or fy <= 0, bound <= 0, depth_margin < 0, min_share outside [0, 1] or a NaN
+ *   among them: LAE_EINVAL; both before any launch. */
+#define LAE_MASK_LIFT_POSE_CHUNK 64
+LAE_API int lae_mask_lift_pack(const float* depth, const float* opacity, const uint8_t* mask, uint32_t HW, float min_opacity,
+                               float* packed, void* stream);
+LAE_API int lae_mask_lift(const float* packed, const float* poses, uint32_t V, float fx, float fy, float cx, float cy, uint32_t H,
+                          uint32_t W, const uint8_t* density_bitfield, uint32_t C, uint32_t G, float bound, float depth_margin,
+                          uint32_t min_views, float min_share, uint8_t* grid_out, uint16_t* votes_out, void* stream);
+
 /* ---- occupancy-grid maintenance (nerf/renderer.py:482-649, Python in the reference) ----
  * positions: point j -> xyz = (2 c / (H-1) - 1) * (bound_c - bound_c/H) + (noise * 2 - 1) * bound_c/H and its Morton index
  *   (renderer.py:580-592).  coords NULL: c = (j / H^2, (j / H) % H, j % H) (full sweep, n <= H^3); else coords [n,3] int32.

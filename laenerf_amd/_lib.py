@@ -154,6 +154,8 @@ SIGNATURES = {
     "lae_style_assemble_forward": [vp, vp, u32, u32, u32, vp, vp, u32, vp],
     "lae_style_assemble_backward": [vp, vp, u32, u32, vp, vp],
     "lae_min_dist_to_points": [vp, u32, vp, u32, f32, vp, vp, vp, vp],
+    "lae_mask_lift_pack": [vp, vp, vp, u32, f32, vp, vp],
+    "lae_mask_lift": [vp, vp, u32, f32, f32, f32, f32, u32, u32, vp, u32, u32, f32, f32, u32, f32, vp, vp, vp],
     "lae_mse_loss_forward": [vp, vp, u32, vp, vp, vp, vp],
     "lae_colour_loss_forward": [vp, vp, u32, i32, f32, vp, vp, vp, vp],
     "lae_adam_check": [vp, i32, u64, vp, vp],

@@ -1,5 +1,6 @@
 from .style_encoder import LAENeRF, palette_recompose  # noqa: F401
 from .editgrid import EditGrid  # noqa: F401
+from .mask_lift import lift_masks, mask_iou, mask_lift_numpy, mask_lift_pack, mask_lift_pack_numpy, selection_masks  # noqa: F401
 from .edit_dataset import extract_view, extract_views, select_edit_pixels  # noqa: F401
 from .recolor import RecolorView, compose_numpy, recolor_views, render_recolored  # noqa: F401
 from .style_trainer import EditSet, StyleTrainer, image_terms_on, jitter_numpy  # noqa: F401

@@ -170,6 +170,58 @@ class EditGrid:
         self._push(pack_cells(coords[ok], lv[ok]), 0)
 
     @torch.no_grad()
+    def new_from_masks(self, renderer, poses, intrinsics, H, W, masks, depths=None, opacities=None, min_opacity=0.5, depth_margin=2.0,
+                       min_views=1, min_share=0.5):
+        """start a selection from 2D masks instead of seed points (mask_lift.py; the rule: csrc/masklift.hip).
+        poses [n, 4, 4] cam2world on the device, intrinsics (fx, fy, cx, cy); masks: a list with one uint8 [H, W] tensor or None per
+        pose -- what metrics.load_masks returns; a None view is skipped.  Every masked view's geometry is rendered as
+        Trainer._render_view_geometry does (render_eval, perturb=False, scale_depth=False, over white, fp16 autocast, the model
+        in eval mode), packed with its mask into one fp32 plane, and dropped before the next view is rendered.  depths /
+        opacities (lists or tensors indexed like masks; fp32 H*W values per view: sensor depth with opacity 1, or renders the
+        caller already has, as `sum w t` and `weights_sum`) replace the render.  min_opacity, depth_margin, min_views, min_share:
+        lift_masks.  Sets `grid`, clears the queue and `pts`.  -> the number of selected cells (the call's one host read)"""
+        from ..rays import get_rays
+        from .mask_lift import lift_masks, mask_lift_pack
+        H, W = int(H), int(W)
+        poses = poses.reshape(-1, 4, 4)
+        if len(masks) != poses.shape[0]:
+            raise ValueError(f"new_from_masks: {len(masks)} masks for {poses.shape[0]} poses")
+        if (depths is None) != (opacities is None):
+            raise ValueError("new_from_masks: depths and opacities come together")
+        use = [i for i, m in enumerate(masks) if m is not None]
+        if not use:
+            raise ValueError("new_from_masks: no view has a mask")
+        dev = renderer.density_bitfield.device
+        packed = torch.empty(len(use), H, W, dtype=torch.float32, device=dev)
+        was_training = renderer.model.training
+        renderer.model.eval()
+        try:
+            for k, i in enumerate(use):
+                mask = masks[i].to(dev).contiguous()
+                if mask.dtype != torch.uint8 or mask.numel() != H * W:
+                    raise ValueError(f"new_from_masks: mask {i} must be uint8 with {H} x {W} values")
+                if depths is not None:
+                    depth, opacity = (t[i].to(dev).float().contiguous() for t in (depths, opacities))
+                else:
+                    ray = get_rays(poses[i:i + 1], intrinsics, H, W)
+                    with torch.autocast("cuda", dtype=torch.float16):
+                        res = renderer.render_eval(ray["rays_o"][0], ray["rays_d"][0], bg_color=1.0, perturb=False, scale_depth=False,
+                                                   image_hw=(H, W))
+                    depth, opacity = res["depth"].float().contiguous(), res["weights_sum"].float().contiguous()
+                mask_lift_pack(depth, opacity, mask, min_opacity, out=packed[k])
+        finally:
+            renderer.model.train(was_training)
+        idx = torch.tensor(use, device=poses.device)
+        self.grid = lift_masks(packed, poses[idx].to(dev).float().contiguous(), intrinsics, H, W, renderer.density_bitfield,
+                               renderer.cascade, renderer.bound, grid_size=renderer.grid_size, depth_margin=depth_margin,
+                               min_views=min_views, min_share=min_share)
+        self.pts = None
+        self._queue, self._state = None, None
+        # popcount of the bitfield: bytes -> bits through a shift table, one sum, one host read
+        shifts = torch.arange(8, dtype=torch.uint8, device=dev)
+        return int(((self.grid[:, None] >> shifts) & 1).sum().item())
+
+    @torch.no_grad()
     def grow_region_queue(self, density_grid, density_thresh, occ_grid=None, grow_iterations=5000):
         """editgrid.py:274-340.  One kernel launch; returns the number of cells popped."""
         if self._queue is None or self.queue_length() == 0:
