@@ -21,6 +21,7 @@ from torch.amp import custom_bwd, custom_fwd
 from ..backend import style_backend as _backend
 from ..encoding import get_encoder
 from ..ffmlp import FFMLP
+from ..losses import loss_scale_of
 
 
 class _palette_recompose(Function):
@@ -360,9 +361,7 @@ class LAENeRF(nn.Module):
         if w_logits.shape[0] != M:
             raise RuntimeError("forward_train_loss: the number of points must be a multiple of 16"
                                + ("" if m_dev is None else " (the buffers' capacity, with m_dev)"))
-        scale = None
-        if scaler is not None:
-            scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
+        scale = loss_scale_of(scaler)
         lw = (float(params.weight_loss_uniform), float(params.weight_loss_non_uniform), float(params.offset_loss))
         reg_w = (float(params.palette_loss_valid), float(params.palette_loss_distinct)) if with_palet_loss else None
         mse_w = None if float(mse_weight) == 1.0 else float(mse_weight)

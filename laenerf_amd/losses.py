@@ -38,12 +38,17 @@ class _mse_scaled(Function):
         return grad * grad_out, None, None
 
 
+def loss_scale_of(scaler):
+    """the loss scale on the device, a 1-element fp32 tensor or None, of `scaler`: a FusedAdam (its device-side loss scale; None when it
+    scales nothing), such a tensor itself, or None"""
+    if scaler is None or torch.is_tensor(scaler):
+        return scaler
+    return scaler._scale_view[:1] if scaler.use_scaler else None
+
+
 def mse_loss_scaled(pred, target, scaler=None):
     """scaler: a FusedAdam (uses its device-side loss scale), a 1-element fp32 cuda tensor, or None"""
-    scale = None
-    if scaler is not None:
-        scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
-    loss, both = _mse_scaled.apply(pred, target, scale)
+    loss, both = _mse_scaled.apply(pred, target, loss_scale_of(scaler))
     loss.unscaled = both[1]
     return loss
 
@@ -131,9 +136,6 @@ def colour_loss_scaled(pred, target, scaler=None, loss="mse", huber_delta=0.1):
     (`lae_colour_loss_forward`).  The same contract: the scaled loss, `loss.unscaled` the plain one; 'mse' gives mse_loss_scaled's bits."""
     from .backend import loss_kind
     kind, param = loss_kind("colour_loss_scaled", loss, huber_delta)
-    scale = None
-    if scaler is not None:
-        scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
-    out, both = _colour_scaled.apply(pred, target, scale, kind, param)
+    out, both = _colour_scaled.apply(pred, target, loss_scale_of(scaler), kind, param)
     out.unscaled = both[1]
     return out

@@ -11,11 +11,12 @@ from torch.autograd import Function
 from torch.amp import custom_bwd, custom_fwd
 
 from ..backend import raymarching_backend as _backend
+from ..losses import loss_scale_of
 
 __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", "packbits", "march_rays_train",
            "composite_rays_train", "march_rays", "march_rays_distill", "composite_rays", "composite_rays_distill",
            "compact_rays_alive", "render_frame", "composite_rays_train_blend", "composite_rays_train_blend_mse",
-           "composite_rays_train_blend_depth", "finish_depth_loss", "composite_depth_numpy", "composite_rays_train_blend_distort",
+           "composite_rays_train_blend_depth", "finish_term_loss", "finish_depth_loss", "composite_depth_numpy", "composite_rays_train_blend_distort",
            "finish_distort_loss", "finish_second_loss", "composite_distort_numpy", "density_grid_positions",
            "density_grid_partial_positions", "density_grid_update", "mark_untrained_grid"]
 
@@ -389,6 +390,33 @@ class _DepthPlane:
         self.t = t
 
 
+# the auxiliary terms of the fused training step, in the order their buffers are made and their losses finished:
+# term -> (its partial sums' attribute on `loss`, elements per ray, its per-ray buffers' attributes, what a loss without it lacks).
+# The backend takes a term's buffers as the per-ray ones [N] in this order, then the partial sums [cdiv(N, 4)].
+TERMS = {
+    "depth": ("depth_partials", 1, ("grad_depth",), "a depth criterion"),
+    "distort": ("dist_partials", 1, ("dist", "grad_dist"), "a distortion term"),
+    "opacity": ("opac_partials", 1, ("opac", "grad_ws"), "an opacity term"),
+    "second": ("second_partials", 3, (), "a second target"),
+}
+
+
+def _rays_name(parts_name):
+    return parts_name.replace("_partials", "_rays")      # the attribute that holds the ray count the partial sums were taken over
+
+
+def _terms_on(depth_sup, dist_sup, crit, weight_sup):
+    """the terms of TERMS, in its order, that the arguments of _composite_rays_train_blend_mse switch on"""
+    on = {"depth": depth_sup is not None, "distort": dist_sup is not None, "opacity": crit is not None and crit[2] is not None,
+          "second": weight_sup is not None and weight_sup[1] is not None}
+    return [t for t in TERMS if on[t]]
+
+
+def _term_buffers(term, N, dev):
+    per_ray = tuple(torch.empty(N, dtype=torch.float32, device=dev) for _ in TERMS[term][2])
+    return per_ray + (torch.empty((N + 3) // 4, dtype=torch.float32, device=dev),)
+
+
 class _composite_rays_train_blend_mse(Function):
     """composite_rays_train_blend + the trainer's criterion and loss scaling (`MSELoss(pred_rgb, gt).mean()` then
     `scaler.scale(loss)`, nerf/utils.py train_step) as ONE autograd node and ONE kernel: d loss / d pixel of a ray depends on
@@ -398,16 +426,18 @@ class _composite_rays_train_blend_mse(Function):
     backward() returns them -- multiplied by the upstream gradient unless that is known to be ones.
     depth_sup = (_DepthPlane, depth_inds, depth_weight, value_only) adds the depth criterion in the same kernel
     (`lae_composite_rays_train_step_depth`): loss = MSE + depth_weight * mean(((D - (z - nears)) * (z > 0))^2), z gathered from the
-    depth plane by the kernel; the outputs depth_partials, grad_depth (the depth partial sums, d loss / d D) are None without it.
+    depth plane by the kernel; its outputs are grad_depth (d loss / d D) and depth_partials (the depth partial sums).
     dist_sup = (distort_weight, value_only) adds distort_weight * mean(l_ray), the distortion term
-    (`lae_composite_rays_train_step_dist`, with or without depth_sup); the last three outputs (its partial sums, d loss / d l_ray,
-    l_ray per ray) are None without it.
+    (`lae_composite_rays_train_step_dist`, with or without depth_sup); its outputs are l_ray per ray, d loss / d l_ray and its
+    partial sums.
     crit = (loss_kind, loss_param, None or (opacity_weight, value_only)) chooses the colour criterion and adds the opacity-entropy term
-    (`lae_composite_rays_train_step_crit`, with or without the other two); the last three outputs (the entropy's partial sums,
-    d loss / d weights_sum, the entropy per ray) are None without the term.  crit=None is the call as it was.
+    (`lae_composite_rays_train_step_crit`, with or without the other two); the term's outputs are the entropy per ray,
+    d loss / d weights_sum and the entropy's partial sums.  crit=None is the call as it was.
     weight_sup = (_DepthPlane or None, _DepthPlane or None, pix_inds, second_weight) adds the per-pixel weights and the second colour
-    target (`lae_composite_rays_train_step_weighted`, MSE only); the last output (the second term's partial sums) is None without a
-    second target.  weight_sup=None is the call as it was."""
+    target (`lae_composite_rays_train_step_weighted`, MSE only); a second target's output is the term's partial sums.
+    weight_sup=None is the call as it was.
+    -> (loss, weights_sum, depth, image, [scaled loss, loss]) and then, for each term that is on in TERMS' order, the outputs named
+    there (a term that is off has none)."""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -424,41 +454,26 @@ class _composite_rays_train_blend_mse(Function):
         grad_image = torch.empty_like(image_out)
         grad_sigmas, grad_rgbs = torch.empty_like(sigmas), torch.empty_like(rgbs)
         partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
-        grad_depth = depth_partials = None
+        bufs = {t: _term_buffers(t, N, dev) for t in _terms_on(depth_sup, dist_sup, crit, weight_sup)}
         if depth_sup is not None:
-            plane, depth_inds, depth_weight, value_only = depth_sup
-            grad_depth = torch.empty(N, dtype=torch.float32, device=dev)
-            depth_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
-            depth_sup = (plane.t, depth_inds, depth_weight, value_only, grad_depth, depth_partials)
-        dist = grad_dist = dist_partials = None
+            depth_sup = (depth_sup[0].t,) + depth_sup[1:] + bufs["depth"]
         if dist_sup is not None:
-            dist, grad_dist = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
-            dist_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
-            dist_sup = dist_sup + (dist, grad_dist, dist_partials)
-        opac = grad_ws = opac_partials = None
-        if crit is not None and crit[2] is not None:
-            opac, grad_ws = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
-            opac_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
-            crit = (crit[0], crit[1], crit[2] + (opac, grad_ws, opac_partials))
-        second_partials = None
+            dist_sup = dist_sup + bufs["distort"]
+        if "opacity" in bufs:
+            crit = crit[:2] + (crit[2] + bufs["opacity"],)
         if weight_sup is not None:
-            w_plane, t2_plane, pix_inds, second_weight = weight_sup
-            if t2_plane is not None:
-                second_partials = torch.empty((N + 3) // 4, dtype=torch.float32, device=dev)
-            weight_sup = (None if w_plane is None else w_plane.t, None if t2_plane is None else t2_plane.t, pix_inds, second_weight,
-                          second_partials)
+            w_plane, t2_plane = weight_sup[:2]
+            weight_sup = (None if w_plane is None else w_plane.t, None if t2_plane is None else t2_plane.t) + weight_sup[2:] + \
+                bufs.get("second", (None,))
         _backend.composite_rays_train_step(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears.contiguous(), fars.contiguous(), bg_rays,
                                            bg, rows_end, target, scale, weights_sum, depth, image, depth_out, image_out, grad_image,
                                            grad_sigmas, grad_rgbs, out, partials, defer_loss=defer_loss, depth_sup=depth_sup,
                                            dist_sup=dist_sup, crit=crit, weight_sup=weight_sup)
         ctx.save_for_backward(grad_sigmas, grad_rgbs)
-        aux = (weights_sum, depth_out, image_out, out) + (() if depth_sup is None else (depth_partials, grad_depth)) + \
-              (() if dist_sup is None else (dist_partials, grad_dist, dist)) + (() if opac is None else (opac_partials, grad_ws, opac)) + \
-              (() if second_partials is None else (second_partials,))
+        aux = (weights_sum, depth_out, image_out, out) + sum(bufs.values(), ())
         ctx.mark_non_differentiable(*aux)
         ctx.set_materialize_grads(False)                 # no zero-filled gradients for the auxiliary outputs (a fill launch each)
-        return out[0], weights_sum, depth_out, image_out, out, depth_partials, grad_depth, dist_partials, grad_dist, dist, opac_partials, \
-            grad_ws, opac, second_partials
+        return (out[0],) + aux
 
     @staticmethod
     @custom_bwd(device_type="cuda")
@@ -475,79 +490,48 @@ class _composite_rays_train_blend_mse(Function):
         return (grad_sigmas, grad_rgbs) + (None,) * 15
 
 
-def finish_depth_loss(loss, out=None):
-    """the depth term alone, mean(((D - (z - nears)) * (z > 0))^2) without its weight, of a `loss` made by
-    composite_rays_train_blend_mse(depth=...): one lae_loss_finish launch over the step's depth partial sums, off the gradient
-    path.  out: a float32 tensor of 2 elements to write to (both receive the value); -> out[1] as a 0-dim tensor"""
-    parts = getattr(loss, "depth_partials", None)
+def finish_term_loss(loss, term, out=None):
+    """one auxiliary term of TERMS alone, without its weight, of a `loss` made by composite_rays_train_blend_mse with that term: one
+    lae_loss_finish launch over the step's partial sums of the term, off the gradient path.  out: a float32 tensor of 2 elements to
+    write to (both receive the value); -> out[1] as a 0-dim tensor"""
+    parts_name, elems, _, without = TERMS[term]
+    parts = getattr(loss, parts_name, None)
     if parts is None:
-        raise RuntimeError("finish_depth_loss: the loss was made without a depth criterion")
+        raise RuntimeError(f"finish_{term}_loss: the loss was made without {without}")
     if out is None:
         out = torch.empty(2, dtype=torch.float32, device=parts.device)
-    _backend.loss_finish(parts, parts.numel(), loss.depth_rays, None, out)
+    _backend.loss_finish(parts, parts.numel(), elems * getattr(loss, _rays_name(parts_name)), None, out)
     return out[1]
+
+
+def finish_depth_loss(loss, out=None):
+    """finish_term_loss for the depth term of composite_rays_train_blend_mse(depth=...): mean(((D - (z - nears)) * (z > 0))^2)"""
+    return finish_term_loss(loss, "depth", out)
 
 
 def finish_distort_loss(loss, out=None):
-    """the distortion term alone, L_dist = mean over all rays of l_ray without its weight, of a `loss` made by
-    composite_rays_train_blend_mse(distort_weight=...): one lae_loss_finish launch over the step's distortion partial sums, off the
-    gradient path.  out: a float32 tensor of 2 elements to write to (both receive the value); -> out[1] as a 0-dim tensor"""
-    parts = getattr(loss, "dist_partials", None)
-    if parts is None:
-        raise RuntimeError("finish_distort_loss: the loss was made without a distortion term")
-    if out is None:
-        out = torch.empty(2, dtype=torch.float32, device=parts.device)
-    _backend.loss_finish(parts, parts.numel(), loss.dist_rays, None, out)
-    return out[1]
-
-
-def check_distort_weight(who, distort_weight):
-    """-> float(distort_weight); ValueError unless it is finite and >= 0"""
-    w = float(distort_weight)
-    if not (w >= 0.0) or w == float("inf"):
-        raise ValueError(f"{who}: distort_weight must be finite and >= 0")
-    return w
+    """finish_term_loss for the distortion term of composite_rays_train_blend_mse(distort_weight=...): L_dist = mean over all rays
+    of l_ray"""
+    return finish_term_loss(loss, "distort", out)
 
 
 def finish_opacity_loss(loss, out=None):
-    """the opacity-entropy term alone, L_op = mean over all rays of h(weights_sum) without its weight, of a `loss` made by
-    composite_rays_train_blend_mse(opacity_weight=...): one lae_loss_finish launch over the step's entropy partial sums, off the
-    gradient path.  out: a float32 tensor of 2 elements to write to (both receive the value); -> out[1] as a 0-dim tensor"""
-    parts = getattr(loss, "opac_partials", None)
-    if parts is None:
-        raise RuntimeError("finish_opacity_loss: the loss was made without an opacity term")
-    if out is None:
-        out = torch.empty(2, dtype=torch.float32, device=parts.device)
-    _backend.loss_finish(parts, parts.numel(), loss.opac_rays, None, out)
-    return out[1]
+    """finish_term_loss for the opacity-entropy term of composite_rays_train_blend_mse(opacity_weight=...): L_op = mean over all
+    rays of h(weights_sum)"""
+    return finish_term_loss(loss, "opacity", out)
 
 
 def finish_second_loss(loss, out=None):
-    """the second colour term alone, mean over the 3 N elements of ((1 - w / 2) (second_target - pred))^2 without its weight, of a
-    `loss` made by composite_rays_train_blend_mse(second_target=...): one lae_loss_finish launch over the step's partial sums of the
-    term, off the gradient path.  out: a float32 tensor of 2 elements to write to (both receive the value); -> out[1] as a 0-dim tensor"""
-    parts = getattr(loss, "second_partials", None)
-    if parts is None:
-        raise RuntimeError("finish_second_loss: the loss was made without a second target")
-    if out is None:
-        out = torch.empty(2, dtype=torch.float32, device=parts.device)
-    _backend.loss_finish(parts, parts.numel(), 3 * loss.second_rays, None, out)
-    return out[1]
+    """finish_term_loss for the second colour term of composite_rays_train_blend_mse(second_target=...): the mean over the 3 N
+    elements of ((1 - w / 2) (second_target - pred))^2"""
+    return finish_term_loss(loss, "second", out)
 
 
-def check_second_weight(who, second_weight):
-    """-> float(second_weight); ValueError unless it is finite and >= 0"""
-    w = float(second_weight)
+def check_weight(who, name, value):
+    """-> float(value); ValueError unless it is finite and >= 0"""
+    w = float(value)
     if not (w >= 0.0) or w == float("inf"):
-        raise ValueError(f"{who}: second_weight must be finite and >= 0")
-    return w
-
-
-def check_opacity_weight(who, opacity_weight):
-    """-> float(opacity_weight); ValueError unless it is finite and >= 0"""
-    w = float(opacity_weight)
-    if not (w >= 0.0) or w == float("inf"):
-        raise ValueError(f"{who}: opacity_weight must be finite and >= 0")
+        raise ValueError(f"{who}: {name} must be finite and >= 0")
     return w
 
 
@@ -603,40 +587,34 @@ def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, targ
         weight_sup = (None if pixel_weights is None else _DepthPlane(pixel_weights.contiguous()),
                       None if second_target is None else _DepthPlane(second_target.contiguous()),
                       None if pixel_inds is None else pixel_inds.contiguous(),
-                      check_second_weight("composite_rays_train_blend_mse", second_weight))
+                      check_weight("composite_rays_train_blend_mse", "second_weight", second_weight))
     crit = None
     if kind != 0 or opacity_weight is not None:
         crit = (kind, param, None if opacity_weight is None else
-                (check_opacity_weight("composite_rays_train_blend_mse", opacity_weight), not opacity_grad))
+                (check_weight("composite_rays_train_blend_mse", "opacity_weight", opacity_weight), not opacity_grad))
     dist_sup = None
     if distort_weight is not None:
-        dist_sup = (check_distort_weight("composite_rays_train_blend_mse", distort_weight), not distort_grad)
+        dist_sup = (check_weight("composite_rays_train_blend_mse", "distort_weight", distort_weight), not distort_grad)
     rows_end, bg_rays, bg = _blend_args("composite_rays_train_blend_mse", rays, bg_color, sigmas.device)
-    scale = None
-    if scaler is not None:
-        scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
+    scale = loss_scale_of(scaler)
     if defer_loss is None:
         defer_loss = scaler is not None and not torch.is_tensor(scaler) and hasattr(scaler, "finish_loss")
     depth_sup = None
     if depth is not None:
         if not torch.is_tensor(depth) or depth.dtype not in (torch.float16, torch.float32):
             raise RuntimeError("composite_rays_train_blend_mse: depth must be a float16 or float32 tensor")
-        if not (float(depth_weight) >= 0.0) or float(depth_weight) == float("inf"):
-            raise ValueError("composite_rays_train_blend_mse: depth_weight must be finite and >= 0")
-        depth_sup = (_DepthPlane(depth.contiguous()), None if depth_inds is None else depth_inds.contiguous(), float(depth_weight),
-                     not depth_grad)
-    (loss, weights_sum, depth_o, image, both, depth_partials, grad_depth, dist_partials, grad_dist, dist, opac_partials, grad_ws, opac,
-     second_partials) = _composite_rays_train_blend_mse.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh,
-                                                              target, scale, bool(defer_loss), depth_sup, dist_sup, crit, weight_sup)
+        depth_sup = (_DepthPlane(depth.contiguous()), None if depth_inds is None else depth_inds.contiguous(),
+                     check_weight("composite_rays_train_blend_mse", "depth_weight", depth_weight), not depth_grad)
+    out = _composite_rays_train_blend_mse.apply(sigmas, rgbs, deltas, rays, nears, fars, bg_rays, bg, rows_end, T_thresh, target, scale,
+                                                bool(defer_loss), depth_sup, dist_sup, crit, weight_sup)
+    loss, weights_sum, depth_o, image, both = out[:5]
     loss.unscaled = both[1]
-    if second_partials is not None:
-        loss.second_partials, loss.second_rays = second_partials, rays.shape[0]
-    if opac is not None:
-        loss.opac_partials, loss.grad_ws, loss.opac, loss.opac_rays = opac_partials, grad_ws, opac, rays.shape[0]
-    if dist_sup is not None:
-        loss.dist_partials, loss.grad_dist, loss.dist, loss.dist_rays = dist_partials, grad_dist, dist, rays.shape[0]
-    if depth_sup is not None:
-        loss.depth_partials, loss.grad_depth, loss.depth_rays = depth_partials, grad_depth, rays.shape[0]
+    rest = iter(out[5:])                                   # the enabled terms' buffers, as _term_buffers made them
+    for term in _terms_on(depth_sup, dist_sup, crit, weight_sup):
+        parts_name, _, per_ray, _ = TERMS[term]
+        for name in per_ray + (parts_name,):
+            setattr(loss, name, next(rest))
+        setattr(loss, _rays_name(parts_name), rays.shape[0])
     return loss, weights_sum, depth_o, image
 
 

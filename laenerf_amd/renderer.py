@@ -436,15 +436,9 @@ class NeRFRenderer(nn.Module):
             raise RuntimeError("shade_train: depth supervision needs gt and fused_post_ops (it lives in the fused criterion kernel)")
         if distort_weight is not None and not (self.fused_post_ops and gt is not None):
             raise RuntimeError("shade_train: the distortion term needs gt and fused_post_ops (it lives in the fused criterion kernel)")
-        dist_kw = {} if distort_weight is None else {"distort_weight": distort_weight, "distort_grad": distort_grad}
         crit_on = loss != "mse" or opacity_weight is not None
         if crit_on and gt is None:
             raise RuntimeError("shade_train: a colour criterion or an opacity term needs gt")
-        kind = loss
-        if crit_on:
-            dist_kw.update(loss=kind, huber_delta=huber_delta, opacity_weight=opacity_weight, opacity_grad=opacity_grad)
-        if weighted and self.fused_post_ops:
-            dist_kw.update(pixel_weights=pixel_weights, pixel_inds=pixel_inds, second_target=second_target, second_weight=second_weight)
         xyzs, dirs, deltas, rays, nears, fars = marched[:6]
         plan = marched[6] if len(marched) > 6 else None
         if grad_x is not None:
@@ -453,15 +447,13 @@ class NeRFRenderer(nn.Module):
             sigmas, rgbs = self.model(xyzs, dirs, plan=plan) if plan is not None else self.model(xyzs, dirs)
         if self.density_scale != 1:
             sigmas = self.density_scale * sigmas
-        loss = None
-        if self.fused_post_ops and gt is not None:
-            if depth is None:
-                loss, weights_sum, depth, image = raymarching.composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars,
-                                                                                            gt, bg_color, T_thresh, scaler, **dist_kw)
-            else:
-                loss, weights_sum, depth, image = raymarching.composite_rays_train_blend_mse(
-                    sigmas, rgbs, deltas, rays, nears, fars, gt, bg_color, T_thresh, scaler, depth=depth, depth_inds=depth_inds,
-                    depth_weight=depth_weight, depth_grad=depth_grad, **dist_kw)
+        kind, loss = loss, None
+        if self.fused_post_ops and gt is not None:       # every term's default is the call without it
+            loss, weights_sum, depth, image = raymarching.composite_rays_train_blend_mse(
+                sigmas, rgbs, deltas, rays, nears, fars, gt, bg_color, T_thresh, scaler, depth=depth, depth_inds=depth_inds,
+                depth_weight=depth_weight, depth_grad=depth_grad, distort_weight=distort_weight, distort_grad=distort_grad, loss=kind,
+                huber_delta=huber_delta, opacity_weight=opacity_weight, opacity_grad=opacity_grad, pixel_weights=pixel_weights,
+                pixel_inds=pixel_inds, second_target=second_target, second_weight=second_weight)
         elif self.fused_post_ops:    # composite + bg blend + depth normalisation in one kernel, gradients without zero fills
             weights_sum, depth, image = raymarching.composite_rays_train_blend(sigmas, rgbs, deltas, rays, nears, fars,
                                                                                bg_color, T_thresh)
@@ -480,7 +472,8 @@ class NeRFRenderer(nn.Module):
     @staticmethod
     def _weighted_unfused(image, gt, scaler, wsup):
         """the weighted criterion of lae_composite_rays_train_step_weighted written with torch operators"""
-        from .raymarching.raymarching import check_second_weight
+        from .losses import loss_scale_of
+        from .raymarching.raymarching import check_weight
         plane, inds, second, second_weight, bg = wsup
         pick = (lambda t, c: t.reshape(-1, c)) if inds is None else (lambda t, c: t.reshape(-1, c).index_select(0, inds))
         pred, gt = image.float(), gt.float()
@@ -492,10 +485,8 @@ class NeRFRenderer(nn.Module):
             s2 = pick(second, int(second.shape[-1])).float()
             t = s2[:, :3] * s2[:, 3:] + bg * (1 - s2[:, 3:]) if s2.shape[1] == 4 else s2
             second_term = (((1 - 0.5 * w) * (t - pred)) ** 2).mean()
-            total = colour + check_second_weight("shade_train", second_weight) * second_term
-        scale = None
-        if scaler is not None:
-            scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
+            total = colour + check_weight("shade_train", "second_weight", second_weight) * second_term
+        scale = loss_scale_of(scaler)
         out = total if scale is None else total * scale[0]
         out.unscaled = total.detach()
         if second_term is not None:
@@ -506,21 +497,19 @@ class NeRFRenderer(nn.Module):
     def _criterion_unfused(image, weights_sum, gt, scaler, loss, huber_delta, opacity_weight, opacity_grad, wsup=None):
         """shade_train's criterion without fused_post_ops: the colour loss in one kernel (with pixel weights or a second target: torch
         operators), the entropy term operator by operator"""
-        from .losses import colour_loss_scaled
-        from .raymarching.raymarching import OPAC_LO, check_opacity_weight
+        from .losses import colour_loss_scaled, loss_scale_of
+        from .raymarching.raymarching import OPAC_LO, check_weight
         if wsup is not None:
             out = NeRFRenderer._weighted_unfused(image, gt, scaler, wsup)
         else:
             out = colour_loss_scaled(image, gt, scaler, loss, huber_delta)
         if opacity_weight is None:
             return out
-        w = check_opacity_weight("shade_train", opacity_weight)
+        w = check_weight("shade_train", "opacity_weight", opacity_weight)
         ws = weights_sum if opacity_grad else weights_sum.detach()
         o = ws.float().clamp(OPAC_LO, 1 - OPAC_LO)
         l_op = (-(o * torch.log2(o) + (1 - o) * torch.log2(1 - o))).mean()
-        scale = None
-        if scaler is not None:
-            scale = scaler if torch.is_tensor(scaler) else (scaler._scale_view[:1] if scaler.use_scaler else None)
+        scale = loss_scale_of(scaler)
         total = out + (w * l_op if scale is None else (w * l_op) * scale[0])
         total.unscaled, total.opacity = out.unscaled + w * l_op.detach(), l_op.detach()
         return total

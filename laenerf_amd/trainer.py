@@ -220,8 +220,7 @@ class Trainer:
                 raise ValueError(f"Trainer: patch_size must be smaller than the images ({data.H} x {data.W})")
             if int(num_rays) // (patch_size * patch_size) < 1:
                 raise ValueError(f"Trainer: num_rays = {int(num_rays)} holds no patch of {patch_size} x {patch_size} pixels")
-            if not (float(perceptual_weight) >= 0.0) or float(perceptual_weight) == float("inf"):
-                raise ValueError("Trainer: perceptual_weight must be finite and >= 0")
+            raymarching.check_weight("Trainer", "perceptual_weight", perceptual_weight)
             if not (float(patch_headroom) >= 1.0) or float(patch_headroom) == float("inf"):
                 raise ValueError("Trainer: patch_headroom must be finite and >= 1")
             from .backend import loss_kind
@@ -238,14 +237,12 @@ class Trainer:
                 raise ValueError("Trainer: pose_refine needs the renderer's fused_post_ops")
             if not getattr(renderer.model, "fused_field", False) or renderer.model.encoder.interp_id != 0:
                 raise ValueError("Trainer: pose_refine needs the fused field op (hash grid with linear interpolation, fused heads)")
-            if not (float(pose_lr) >= 0.0) or float(pose_lr) == float("inf"):
-                raise ValueError("Trainer: pose_lr must be finite and >= 0")
+            raymarching.check_weight("Trainer", "pose_lr", pose_lr)
         if exposure_refine:                                           # refused before anything is changed on the data
             from .exposure import MODES
             if second_weight is not None:
                 raise ValueError("Trainer: exposure_refine cannot be combined with second_weight (the second target is not gained)")
-            if not (float(exposure_lr) >= 0.0) or float(exposure_lr) == float("inf"):
-                raise ValueError("Trainer: exposure_lr must be finite and >= 0")
+            raymarching.check_weight("Trainer", "exposure_lr", exposure_lr)
             if exposure_mode not in MODES:
                 raise ValueError(f"Trainer: exposure_mode must be one of {sorted(MODES)}")
         if error_map is not None and data.error_map is None:
@@ -258,21 +255,19 @@ class Trainer:
         if depth_weight is not None:
             if getattr(data, "depths", None) is None:
                 raise ValueError("Trainer: depth_weight needs a depth plane on the data (ResidentImages(depths=...) / set_depths)")
-            if not (float(depth_weight) >= 0.0) or float(depth_weight) == float("inf"):
-                raise ValueError("Trainer: depth_weight must be finite and >= 0")
+            depth_weight = raymarching.check_weight("Trainer", "depth_weight", depth_weight)
             if not renderer.fused_post_ops:
                 raise ValueError("Trainer: depth supervision needs the renderer's fused_post_ops")
-        self.depth_weight = None if depth_weight is None else float(depth_weight)
-        self.depth_grad = bool(depth_grad)
+        self.depth_weight, self.depth_grad = depth_weight, bool(depth_grad)
         if distort_weight is not None:
-            distort_weight = raymarching.check_distort_weight("Trainer", distort_weight)
+            distort_weight = raymarching.check_weight("Trainer", "distort_weight", distort_weight)
             if not renderer.fused_post_ops:
                 raise ValueError("Trainer: the distortion term needs the renderer's fused_post_ops")
         self.distort_weight, self.distort_grad = distort_weight, bool(distort_grad)
         from .backend import loss_kind
         loss_kind("Trainer", loss, huber_delta)
         if opacity_weight is not None:
-            opacity_weight = raymarching.check_opacity_weight("Trainer", opacity_weight)
+            opacity_weight = raymarching.check_weight("Trainer", "opacity_weight", opacity_weight)
             if not renderer.fused_post_ops:
                 raise ValueError("Trainer: the opacity term needs the renderer's fused_post_ops")
         self.loss, self.huber_delta = loss, float(huber_delta)
@@ -282,35 +277,40 @@ class Trainer:
                 raise ValueError("Trainer: pixel_weights=True needs a weight plane on the data (ResidentImages(pixel_weights=...) / "
                                  "set_pixel_weights)")
             if second_weight is not None:
-                second_weight = raymarching.check_second_weight("Trainer", second_weight)
+                second_weight = raymarching.check_weight("Trainer", "second_weight", second_weight)
                 if getattr(data, "second_target", None) is None:
                     raise ValueError("Trainer: second_weight needs a second target on the data (ResidentImages(second_target=...) / "
                                      "set_second_target)")
             if not renderer.fused_post_ops:
                 raise ValueError("Trainer: pixel weights and a second target need the renderer's fused_post_ops")
         self.pixel_weights, self.second_weight = bool(pixel_weights), second_weight
+        # the static part of what a step hands through shade_train to composite_rays_train_blend_mse; _step adds the step's tensors.
+        # Every value of a term that is off is that function's default: the call without the term
+        self._term_kw = dict(depth_weight=0.0 if depth_weight is None else depth_weight, depth_grad=self.depth_grad,
+                             distort_weight=distort_weight, distort_grad=self.distort_grad, loss=loss, huber_delta=self.huber_delta,
+                             opacity_weight=opacity_weight, opacity_grad=self.opacity_grad,
+                             second_weight=0.0 if second_weight is None else second_weight)
         dev = renderer.density_grid.device
         data.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         data.aabb = renderer.aabb_train.to(dev, torch.float32).contiguous()      # the batch's near / far = the march's
         data.min_near = float(renderer.min_near)
         optimizer.device_lr = True
         n_groups = len(optimizer.param_groups)
-        self.lr_table = torch.from_numpy(lr_schedule(lr, self.iters, self.iters + 1, n_groups)).to(dev)
+        lr_table = lambda base, groups: torch.from_numpy(lr_schedule(base, self.iters, self.iters + 1, groups)).to(dev)
+        self.lr_table = lr_table(lr, n_groups)
         self.m_limit = torch.zeros(1, dtype=torch.int32, device=dev)
         self.loss_slots = torch.zeros(GROUP, dtype=torch.float32, device=dev)
-        self.depth_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.depth_weight is not None else None
-        self._depth_hist = []
-        self.distort_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.distort_weight is not None else None
-        self._distort_hist = []
-        self.opacity_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.opacity_weight is not None else None
-        self._opacity_hist = []
-        self.second_slots = torch.zeros(GROUP, 2, dtype=torch.float32, device=dev) if self.second_weight is not None else None
-        self._second_hist = []
+        # per-step records: name -> (the group's device slots, the history of their copies); the enabled terms of raymarching.TERMS, in
+        # its order, hold [GROUP, 2] slots that finish_term_loss writes (column 1 is the record)
+        self._records = {"loss": (self.loss_slots, [])}
+        weights = {"depth": depth_weight, "distort": distort_weight, "opacity": opacity_weight, "second": second_weight}
+        self._records.update({t: (torch.zeros(GROUP, 2, dtype=torch.float32, device=dev), []) for t in raymarching.TERMS
+                              if weights[t] is not None})
         self.pose_refine, self.pose_lr = bool(pose_refine), float(pose_lr)
         self.pose_betas, self.pose_eps = (float(pose_betas[0]), float(pose_betas[1])), float(pose_eps)
         if self.pose_refine:
             data.enable_pose_refinement()
-            self.pose_lr_table = torch.from_numpy(lr_schedule(self.pose_lr, self.iters, self.iters + 1, 1)).to(dev)
+            self.pose_lr_table = lr_table(self.pose_lr, 1)
             self.pose_lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
             self._pose_ray_grads = torch.zeros(self.num_rays, 6, dtype=torch.float64, device=dev)
         self.exposure_refine, self.exposure_lr, self.exposure_mode = bool(exposure_refine), float(exposure_lr), exposure_mode
@@ -318,7 +318,7 @@ class Trainer:
         self.exposure_center = bool(exposure_center)
         if self.exposure_refine:
             data.enable_exposure_refinement(exposure_mode)
-            self.exposure_lr_table = torch.from_numpy(lr_schedule(self.exposure_lr, self.iters, self.iters + 1, 1)).to(dev)
+            self.exposure_lr_table = lr_table(self.exposure_lr, 1)
             self.exposure_lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.patch_size, self.perceptual_weight = patch_size, float(perceptual_weight)
         self.perceptual_normalize, self.patch_headroom = bool(perceptual_normalize), float(patch_headroom)
@@ -326,11 +326,11 @@ class Trainer:
         self.skip_perceptual = False             # patch mode only: leave the LPIPS chain out of the step (what perceptual_weight=0 must equal)
         self.n_rays = self.num_rays              # the rays a step trains
         self.perceptual_slots = None
-        self._perceptual_hist = []
         if patch_size != 1:
             self.lpips = lpips.to(dev)
             self.n_rays = (self.num_rays // (patch_size * patch_size)) * patch_size * patch_size
             self.perceptual_slots = torch.zeros(GROUP, dtype=torch.float32, device=dev)
+            self._records["perceptual"] = (self.perceptual_slots, [])
             renderer.count_limit = self.m_limit  # the refresh keeps the largest per-step count and the truncated steps (renderer.py)
         self.global_step = 0
         self.started = False
@@ -338,7 +338,6 @@ class Trainer:
         self._pool = None
         self._rows_seen = 0
         self.captures = self.cache_misses = self.warm_groups = 0
-        self._loss_hist = []
         from .checkpoint import new_stats
         self.stats = new_stats()                 # the reference Trainer's stats; 'results' and 'checkpoints' are kept (checkpoints below)
         self.epoch_len = int(epoch_len) if epoch_len is not None else data.n_img
@@ -366,73 +365,70 @@ class Trainer:
         M = self._m()
         return M if self.capacity == "exact" else bucket_capacity(M)
 
-    def _step(self, k, m_cap):
-        """one training step (eager or under capture); k = its slot in the group.  m_cap None: host-sized march."""
-        r, opt = self.r, self.opt
-        with torch.no_grad():
-            row = torch.clamp(self.data.step, max=self.iters)
-            opt.lrs.copy_(self.lr_table.index_select(0, row).view(-1))
-            if self.pose_refine:
-                self.pose_lr_dev.copy_(self.pose_lr_table.index_select(0, row).view(-1))
-            if self.exposure_refine:
-                self.exposure_lr_dev.copy_(self.exposure_lr_table.index_select(0, row).view(-1))
-        if self.patch_size != 1:
-            return self._patch_step(k, m_cap)
-        b = self.data.sample(self.num_rays)
+    def _lr_tables(self):
+        """(schedule table, the device learning rate a step copies its row into) for the network, the poses and the exposures"""
+        tables = [(self.lr_table, self.opt.lrs)]
+        if self.pose_refine:
+            tables.append((self.pose_lr_table, self.pose_lr_dev))
+        if self.exposure_refine:
+            tables.append((self.exposure_lr_table, self.exposure_lr_dev))
+        return tables
+
+    def _march(self, b, m_cap, force_all_rays=False):
+        """the occupancy march of batch b -> xyzs, dirs, deltas, rays.  m_cap None: host-sized, as in the reference (force_all_rays:
+        every ray keeps all its samples); else a buffer of m_cap rows whose limit is read from m_limit on the device"""
+        r = self.r
         counter = r.step_counter[r.local_step % GROUP]
         counter.zero_()
         r.local_step += 1
+        if m_cap is None:
+            marched = raymarching.march_rays_train(
+                b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
+                r.mean_count, True, 128, force_all_rays, self.dt_gamma, self.max_steps)
+        else:
+            marched = raymarching.march_rays_train(
+                b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
+                perturb=True, dt_gamma=self.dt_gamma, max_steps=self.max_steps, m_limit=self.m_limit, capacity=m_cap)
+        if not torch.cuda.is_current_stream_capturing():
+            self._rows_seen = max(self._rows_seen, marched[0].shape[0])
+        return marched
+
+    def _step(self, k, m_cap):
+        """one training step (eager or under capture); k = its slot in the group.  m_cap None: host-sized march."""
+        r, opt, data = self.r, self.opt, self.data
+        with torch.no_grad():
+            row = torch.clamp(data.step, max=self.iters)
+            for table, dest in self._lr_tables():
+                dest.copy_(table.index_select(0, row).view(-1))
+        if self.patch_size != 1:
+            return self._patch_step(k, m_cap)
+        b = data.sample(self.num_rays)
+        weights = data.pixel_weights if self.pixel_weights else None
         with torch.autocast("cuda", dtype=torch.float16):
-            if m_cap is None:
-                xyzs, dirs, deltas, rays = raymarching.march_rays_train(
-                    b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
-                    r.mean_count, True, 128, False, self.dt_gamma, self.max_steps)
-            else:
-                xyzs, dirs, deltas, rays = raymarching.march_rays_train(
-                    b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
-                    perturb=True, dt_gamma=self.dt_gamma, max_steps=self.max_steps, m_limit=self.m_limit, capacity=m_cap)
-            if not torch.cuda.is_current_stream_capturing():
-                self._rows_seen = max(self._rows_seen, xyzs.shape[0])
-            dist_kw = {} if self.distort_weight is None else {"distort_weight": self.distort_weight, "distort_grad": self.distort_grad}
-            if self.loss != "mse" or self.opacity_weight is not None:
-                dist_kw.update(loss=self.loss, huber_delta=self.huber_delta, opacity_weight=self.opacity_weight,
-                               opacity_grad=self.opacity_grad)
-            if self.pixel_weights or self.second_weight is not None:
-                dist_kw.update(pixel_weights=self.data.pixel_weights if self.pixel_weights else None, pixel_inds=b["inds"],
-                               second_target=self.data.second_target if self.second_weight is not None else None,
-                               second_weight=0.0 if self.second_weight is None else self.second_weight)
-            grad_x = None
-            if self.pose_refine:
-                grad_x = dist_kw["grad_x"] = torch.empty(xyzs.shape, dtype=torch.float32, device=xyzs.device)
-            if self.depth_weight is None:
-                res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt, **dist_kw)
-            else:
-                res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt,
-                                    depth=self.data.depths, depth_inds=b["inds"], depth_weight=self.depth_weight,
-                                    depth_grad=self.depth_grad, **dist_kw)
+            xyzs, dirs, deltas, rays = self._march(b, m_cap)
+            grad_x = torch.empty(xyzs.shape, dtype=torch.float32, device=xyzs.device) if self.pose_refine else None
+            res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"], gt=b["gt"], scaler=opt,
+                                depth=data.depths if self.depth_weight is not None else None, depth_inds=b["inds"],
+                                pixel_weights=weights, pixel_inds=b["inds"],
+                                second_target=data.second_target if self.second_weight is not None else None, grad_x=grad_x,
+                                **self._term_kw)
         if self.error_map == "ema":
-            self.data.update_error_map(res["image"], b, loss=self.loss, huber_delta=self.huber_delta)
+            data.update_error_map(res["image"], b, loss=self.loss, huber_delta=self.huber_delta)
         loss = res["loss"]
-        if self.depth_weight is not None:
-            raymarching.finish_depth_loss(loss, out=self.depth_slots[k])
-        if self.distort_weight is not None:
-            raymarching.finish_distort_loss(loss, out=self.distort_slots[k])
-        if self.opacity_weight is not None:
-            raymarching.finish_opacity_loss(loss, out=self.opacity_slots[k])
-        if self.second_weight is not None:
-            raymarching.finish_second_loss(loss, out=self.second_slots[k])
+        for term in raymarching.TERMS:                                 # the finishing launches in the table's order
+            if term in self._records:
+                raymarching.finish_term_loss(loss, term, out=self._records[term][0][k])
         opt.backward(loss)
         if self.pose_refine:                                           # grad_x holds d (scaled loss) / d xyzs now
-            self.data.pose_ray_grad(rays, xyzs, grad_x, b["rays_o"], out=self._pose_ray_grads)
+            data.pose_ray_grad(rays, xyzs, grad_x, b["rays_o"], out=self._pose_ray_grads)
         opt.step()
         if self.pose_refine:                                           # after the step: its skip decision and 1 / scale are in the state words
-            self.data.pose_step(self._pose_ray_grads, b["inds"], opt.dev_state, self.pose_lr_dev, self.pose_betas, self.pose_eps)
+            data.pose_step(self._pose_ray_grads, b["inds"], opt.dev_state, self.pose_lr_dev, self.pose_betas, self.pose_eps)
         if self.exposure_refine:                                       # likewise after the step; the analytic gradient needs no 1 / scale
-            self.data.exposure_step(res["image"], b, opt.dev_state, self.exposure_lr_dev, loss=self.loss, huber_delta=self.huber_delta,
-                                    pixel_weights=self.data.pixel_weights if self.pixel_weights else None, betas=self.exposure_betas,
-                                    eps=self.exposure_eps, center=self.exposure_center)
+            data.exposure_step(res["image"], b, opt.dev_state, self.exposure_lr_dev, loss=self.loss, huber_delta=self.huber_delta,
+                               pixel_weights=weights, betas=self.exposure_betas, eps=self.exposure_eps, center=self.exposure_center)
         if self.ema is not None:
-            self.ema.update_gated(self.data.step, self.epoch_len)      # sample() has advanced the counter to this step's index
+            self.ema.update_gated(data.step, self.epoch_len)           # sample() has advanced the counter to this step's index
         with torch.no_grad():
             self.loss_slots[k].copy_(loss.unscaled.view(()))
 
@@ -442,20 +438,8 @@ class Trainer:
         from .losses import colour_loss_scaled, lpips_patch_loss
         r, opt = self.r, self.opt
         b = self.data.sample(self.n_rays, patch_size=self.patch_size)
-        counter = r.step_counter[r.local_step % GROUP]
-        counter.zero_()
-        r.local_step += 1
         with torch.autocast("cuda", dtype=torch.float16):
-            if m_cap is None:                                          # no count yet: every ray keeps all its samples
-                xyzs, dirs, deltas, rays = raymarching.march_rays_train(
-                    b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
-                    r.mean_count, True, 128, True, self.dt_gamma, self.max_steps)
-            else:
-                xyzs, dirs, deltas, rays = raymarching.march_rays_train(
-                    b["rays_o"], b["rays_d"], r.bound, r.density_bitfield, r.cascade, r.grid_size, b["nears"], b["fars"], counter,
-                    perturb=True, dt_gamma=self.dt_gamma, max_steps=self.max_steps, m_limit=self.m_limit, capacity=m_cap)
-            if not torch.cuda.is_current_stream_capturing():
-                self._rows_seen = max(self._rows_seen, xyzs.shape[0])
+            xyzs, dirs, deltas, rays = self._march(b, m_cap, force_all_rays=True)      # no count yet: every ray keeps all its samples
             res = r.shade_train((xyzs, dirs, deltas, rays, b["nears"], b["fars"]), bg_color=b["bg"])
         image = res["image"]
         loss = colour_loss_scaled(image, b["gt"], opt, self.loss, self.huber_delta)
@@ -526,66 +510,53 @@ class Trainer:
             else:
                 self._step(pos, self._m_cap() if sized else None)
                 n = 1
-            self._loss_hist.append(self.loss_slots[pos:pos + n].clone())
-            if self.perceptual_slots is not None:
-                self._perceptual_hist.append(self.perceptual_slots[pos:pos + n].clone())
-            if self.depth_slots is not None:
-                self._depth_hist.append(self.depth_slots[pos:pos + n, 1].clone())
-            if self.distort_slots is not None:
-                self._distort_hist.append(self.distort_slots[pos:pos + n, 1].clone())
-            if self.opacity_slots is not None:
-                self._opacity_hist.append(self.opacity_slots[pos:pos + n, 1].clone())
-            if self.second_slots is not None:
-                self._second_hist.append(self.second_slots[pos:pos + n, 1].clone())
+            for slots, hist in self._records.values():
+                hist.append((slots[pos:pos + n] if slots.dim() == 1 else slots[pos:pos + n, 1]).clone())
             done += n
             self.global_step += n
         return self
 
     # ------------------------------------------------------------------ results
+    # the accessors of every per-step record (a resume's test compares them all)
+    RECORDS = ("losses", "depth_losses", "distort_losses", "opacity_losses", "second_losses", "perceptual_losses")
+
+    def _record(self, name):
+        """the history of per-step record `name` as a float32 numpy array; empty when this trainer does not keep it"""
+        _, hist = self._records.get(name, (None, None))
+        return torch.cat(hist).cpu().numpy() if hist else np.zeros(0, np.float32)
+
     def losses(self):
         """per-step losses (the unscaled loss of every step so far: the colour criterion's mean -- the MSE under loss='mse', else the
         mean of the L1 / Huber / MAPE element loss --, plus depth_weight * the depth term with depth supervision, plus distort_weight *
         the distortion term and opacity_weight * the opacity entropy with them) as a float32 numpy array.  After load_checkpoint /
         load_state_dict: the steps since the resume (the history is not part of a checkpoint); likewise depth_losses(),
         distort_losses() and opacity_losses()"""
-        if not self._loss_hist:
-            return np.zeros(0, np.float32)
-        return torch.cat(self._loss_hist).cpu().numpy()
+        return self._record("loss")
 
     def depth_losses(self):
         """per-step depth term mean(((depth - (gt_depth - nears)) * (gt_depth > 0))^2), without its weight, as a float32 numpy
         array (empty without depth supervision).  Each step finishes it with one lae_loss_finish node off the gradient path."""
-        if not self._depth_hist:
-            return np.zeros(0, np.float32)
-        return torch.cat(self._depth_hist).cpu().numpy()
+        return self._record("depth")
 
     def distort_losses(self):
         """per-step distortion term L_dist (the batch's mean of l_ray), without its weight, as a float32 numpy array (empty without
         distort_weight).  Each step finishes it with one lae_loss_finish node off the gradient path."""
-        if not self._distort_hist:
-            return np.zeros(0, np.float32)
-        return torch.cat(self._distort_hist).cpu().numpy()
+        return self._record("distort")
 
     def opacity_losses(self):
         """per-step opacity entropy L_op (the batch's mean of h(weights_sum)), without its weight, as a float32 numpy array (empty
         without opacity_weight).  Each step finishes it with one lae_loss_finish node off the gradient path."""
-        if not self._opacity_hist:
-            return np.zeros(0, np.float32)
-        return torch.cat(self._opacity_hist).cpu().numpy()
+        return self._record("opacity")
 
     def second_losses(self):
         """per-step second colour term mean(((1 - w / 2) * (second_target - pred))^2), without its weight, as a float32 numpy array
         (empty without second_weight).  Each step finishes it with one lae_loss_finish node off the gradient path."""
-        if not self._second_hist:
-            return np.zeros(0, np.float32)
-        return torch.cat(self._second_hist).cpu().numpy()
+        return self._record("second")
 
     def perceptual_losses(self):
         """per-step LPIPS term (the mean over the step's patches), without its weight, as a float32 numpy array (empty without
         patch_size > 1; zeros for steps run with skip_perceptual)"""
-        if not self._perceptual_hist:
-            return np.zeros(0, np.float32)
-        return torch.cat(self._perceptual_hist).cpu().numpy()
+        return self._record("perceptual")
 
     def truncated_steps(self):
         """patch mode: the number of steps so far whose requested sample count exceeded the limit they marched under, so that rays
@@ -832,8 +803,8 @@ class Trainer:
             self.m_limit.fill_(self._all_rows())
         self.graphs = {}
         self._pool = None
-        self._loss_hist, self._depth_hist, self._distort_hist, self._opacity_hist, self._second_hist = [], [], [], [], []
-        self._perceptual_hist = []
+        for _, hist in self._records.values():
+            hist.clear()
         self.started = True
         return self
 

@@ -102,7 +102,7 @@ def assert_same_state(a, b):
 
 def assert_same_tail(full, resumed, m):
     """the resumed trainer's per-step records against the last m of the uninterrupted run's"""
-    for name in ("losses", "depth_losses", "distort_losses"):
+    for name in type(full).RECORDS:                       # every per-step record the Trainer keeps
         a, c = getattr(full, name)(), getattr(resumed, name)()
         if a.size == 0:
             assert c.size == 0, name

@@ -78,16 +78,33 @@ def test_a_plane_of_ones_is_the_default_run(plain_run):
     _assert_same(sn, plain_run[1])
 
 
-def test_resume_with_weights_and_second_target_continues_bit_for_bit(tmp_path):
+def _make(net_seed, torch_seed, seed, graph=True, **kw):
+    """a Trainer on checkpoint_util's scene with the three planes on its data"""
     import checkpoint_util as U
     from laenerf_amd.trainer import Trainer
+    r, opt, data = U.setup(net_seed)
+    w, second, depth = _planes(data)
+    data.set_pixel_weights(w); data.set_second_target(second); data.set_depths(depth)
+    torch.manual_seed(torch_seed)
+    return Trainer(r, opt, data, U.ITERS, U.LR, num_rays=U.RAYS, seed=seed, graph=graph, capacity="bucket", **kw)
 
-    def make(net_seed, torch_seed, seed, **kw):
-        r, opt, data = U.setup(net_seed)
-        w, second, depth = _planes(data)
-        data.set_pixel_weights(w); data.set_second_target(second); data.set_depths(depth)
-        torch.manual_seed(torch_seed)
-        return Trainer(r, opt, data, U.ITERS, U.LR, num_rays=U.RAYS, seed=seed, graph=True, capacity="bucket", **kw)
+
+def test_all_four_auxiliary_terms_at_once_replay_equals_eager():
+    """depth, distortion, opacity entropy and the second target (with pixel weights) in one step, 48 steps: 16 host-sized, a group run
+    eagerly because its capacity is new, a group captured and replayed; the same state and the same per-step records as eager"""
+    import checkpoint_util as U
+    kw = dict(FULL, distort_weight=0.01, opacity_weight=0.01, loss="mse")
+    a, b = _make(0, 7, 1, graph=True, **kw).train(48), _make(0, 7, 1, graph=False, **kw).train(48)
+    assert a.captures >= 1 and b.captures == 0                         # the captured path cannot be skipped silently
+    U.assert_same_state(a, b)
+    for name in ("losses", "depth_losses", "distort_losses", "opacity_losses", "second_losses"):
+        x, y = getattr(a, name)(), getattr(b, name)()
+        assert x.shape == (48,) and np.isfinite(x).all() and np.array_equal(x, y), name
+
+
+def test_resume_with_weights_and_second_target_continues_bit_for_bit(tmp_path):
+    import checkpoint_util as U
+    make = _make
 
     full = make(0, 7, 1, **FULL).train(32)
     want = U.snapshot(full)
