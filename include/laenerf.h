@@ -75,7 +75,7 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad -- a binding that needs them also checks that the library exports them).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward -- a binding that needs them also checks that the library exports them).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
 #define LAE_ABI_TAG "abi27"
@@ -1444,6 +1444,51 @@ LAE_API int lae_consistency_pair(const void* frame_a, const void* frame_b, int f
                                  const float* depth_b, const float* opacity_b, const float* pose_a, const float* pose_b, float fx,
                                  float fy, float cx, float cy, uint32_t H, uint32_t W, float min_opacity, double* scratch,
                                  double* sse_out, double* count_out, uint8_t* valid, float* warped, float* lpips_in, void* stream);
+
+/* ---- SSIM (csrc/ssim.hip): the reference's SSIMMeter (nerf/utils.py:259-293, torchmetrics' structural_similarity_index_measure with
+ * its defaults) as an evaluation metric, and 1 - SSIM as a training term on patches.  laenerf_amd/metrics.py restates all of it in
+ * float64 (ssim_numpy, ssim_grad_numpy).  One definition, used by all three entries:
+ *
+ *   x is the prediction, y the target, both [H, W, 3]; values are used as given, without clamping.
+ *   Window: 11 taps, g[k] = exp(-((k - 5) / 1.5)^2 / 2), normalised to sum 1; the 2-D window is g (x) g.
+ *   Window positions: for every channel and every 0 <= i <= H - 11, 0 <= j <= W - 11 the five weighted sums mx, my, exx, eyy, exy of
+ *   x, y, x^2, y^2, x y over the 11 x 11 pixels from (i, j) on -- only windows that lie fully inside the image count (torchmetrics
+ *   reflect-pads by 5 and crops 5 again, which is the same set).  Then
+ *       A1 = 2 mx my + C1        A2 = 2 (exy - mx my) + C2
+ *       B1 = mx^2 + my^2 + C1    B2 = (exx - mx^2) + (eyy - my^2) + C2
+ *       S  = A1 A2 / (B1 B2)     C1 = (0.01 L)^2,  C2 = (0.03 L)^2          (the variances are not clamped)
+ *   Score: SSIM(x, y) = the mean of S over the 3 (H - 10)(W - 10) values.  H < 11 or W < 11: LAE_EINVAL.
+ *   Data range L: a positive number, or (data_range <= 0) "from the data": max(max x - min x, max y - min y) over the whole pair, all
+ *   channels.  If L from the data is 0 (two constant images) then C1 = C2 = 0 and S = 0 / 0: the score and every map value are NaN, as
+ *   torch's division gives it.
+ *   Gradient with respect to x for a fixed L: per window value
+ *       Dm  = (2 my A2 - 2 my A1) / (B1 B2) - S (2 mx / B1 - 2 mx / B2),   Dxx = -S / B2,   Dxy = 2 A1 / (B1 B2)
+ *       dSSIM / dx[u,v,c] = ((g(x)g * Dm)[u,v,c] + 2 x[u,v,c] (g(x)g * Dxx)[u,v,c] + y[u,v,c] (g(x)g * Dxy)[u,v,c]) / (3 (H - 10)(W - 10))
+ *   where * spreads every window's value back over its 11 x 11 pixels (the transpose of the forward pass).
+ *   Arithmetic: the inputs are fp32; every window sum, S, Dm, Dxx, Dxy and the spread are fp64 (with fp32 sums exx - mx^2 cancels);
+ *   separable passes, horizontal then vertical; fixed-order reductions, no atomics: two calls give the same bits. */
+#define LAE_SSIM_TILE_W 32           /* window positions per workgroup of lae_ssim: 32 columns x 16 rows */
+#define LAE_SSIM_TILE_H 16
+#define LAE_SSIM_MINMAX_BLOCKS 256
+/* doubles of scratch lae_ssim needs for an H x W pair: 4 * LAE_SSIM_MINMAX_BLOCKS min / max partials + one partial per tile */
+LAE_API uint64_t lae_ssim_scratch_doubles(uint32_t H, uint32_t W);
+/* SSIM of one pair.  x, y fp32 [H*W, 3] (pred and gt_out of lae_eval_view as they are); out one double; map optional fp32
+ * [H-10, W-10, 3], S rounded once; data_range <= 0 selects the data rule: a first launch leaves min / max partials in scratch and
+ * the main kernel folds them on the device -- no host read, the call can be captured.  11 <= H, W <= 32768, H * W * 3 < 2^31, a
+ * finite data_range, else LAE_EINVAL; NULL x, y, scratch or out: LAE_ENULL; both before any launch. */
+LAE_API int lae_ssim(const float* x, const float* y, uint32_t H, uint32_t W, double data_range, double* scratch, double* out,
+                     float* map, void* stream);
+/* SSIM of every patch of a patch batch.  pred, gt fp32 [n_patch * P^2, 3] in lae_patch_pack's row order (row r is pixel
+ * ((r % P^2) / P, r % P) of patch r / P^2); per_patch one double per patch, its SSIM(pred patch, gt patch).  One workgroup per patch.
+ * 11 <= P <= 4096, n_patch <= 65535, n_patch * P^2 * 3 < 2^31 and a positive finite data_range (the data rule has no gradient, so
+ * the training term does not offer it), else LAE_EINVAL. */
+LAE_API int lae_ssim_patch_forward(const float* pred, const float* gt, uint32_t n_patch, uint32_t patch_size, double data_range,
+                                   double* per_patch, void* stream);
+/* grad_pred[r, c] = gout[0] * d (mean over the patches of SSIM) / d pred[r, c], fp32 [n_patch * P^2, 3], every element written by its
+ * one owner; gout a device fp32 scalar read by the kernel.  Tiled (16 x 16 pixels per workgroup), so P has no upper limit but
+ * lae_ssim_patch_forward's.  The same argument rules. */
+LAE_API int lae_ssim_patch_backward(const float* pred, const float* gt, uint32_t n_patch, uint32_t patch_size, double data_range,
+                                    const float* gout, float* grad_pred, void* stream);
 
 /* ---- training-camera pose refinement (csrc/gridencoder.hip, csrc/pose.hip; laenerf_amd/poses.py restates all three in float64)
  *

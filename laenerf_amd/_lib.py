@@ -169,6 +169,10 @@ SIGNATURES = {
     "lae_lpips_head_grad": [u32, vp, vp, vp, vp, u32, vp, vp, i32, vp],
     "lae_patch_pack": [vp, vp, u32, u32, i32, vp, vp],
     "lae_patch_unpack_grad": [vp, u32, u32, i32, vp, vp],
+    "lae_ssim_scratch_doubles": [u32, u32],
+    "lae_ssim": [vp, vp, u32, u32, f64, vp, vp, vp, vp],
+    "lae_ssim_patch_forward": [vp, vp, u32, u32, f64, vp, vp],
+    "lae_ssim_patch_backward": [vp, vp, u32, u32, f64, vp, vp, vp],
     "lae_consistency_pair": [vp, vp, i32, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, u32, u32, f32, vp, vp, vp, vp, vp, vp, vp],
     "lae_adam_apply": [vp, vp, vp, vp, i32, vp, u64, vp, vp, f32, f32, f32, f32, vp],
     "lae_ffmlp_set_mode": [i32],
@@ -189,6 +193,7 @@ _RESTYPES = {
     "lae_nnfm_match_bytes": u64,
     "lae_nnfm_workspace_bytes": u64,
     "lae_rayreg_build_bytes": u64,
+    "lae_ssim_scratch_doubles": u64,
     "lae_rayreg_query_bytes": u64,
     "lae_recolor_compact_scratch_bytes": u64,
     "lae_marching_cubes_scratch_bytes": u64,

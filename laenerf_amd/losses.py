@@ -130,6 +130,54 @@ def lpips_patch_loss(pred_rows, gt_rows, patch_size, lpips, normalize=False):
     return out
 
 
+class _ssim_patch(Function):
+    """lae_ssim_patch_forward / lae_ssim_patch_backward: the mean over the patches of SSIM(pred patch, gt patch)"""
+
+    @staticmethod
+    def forward(ctx, pred, gt, P, data_range):
+        pred = pred.float().contiguous()
+        gt = gt.float().contiguous()
+        _lib.need_cuda(pred, gt)
+        n = pred.shape[0] // (P * P)
+        per_patch = torch.empty(n, dtype=torch.float64, device=pred.device)
+        _lib.check(_lib.load().lae_ssim_patch_forward(pred.data_ptr(), gt.data_ptr(), n, P, data_range, per_patch.data_ptr(),
+                                                      _lib.stream()), "ssim_patch_forward")
+        ctx.save_for_backward(pred, gt)
+        ctx.dims = (n, P, data_range)
+        ctx.mark_non_differentiable(per_patch)
+        return per_patch.mean().float(), per_patch
+
+    @staticmethod
+    def backward(ctx, gout, _):
+        n, P, data_range = ctx.dims
+        pred, gt = ctx.saved_tensors
+        gout = gout.float().contiguous()
+        grad_pred = torch.empty_like(pred)
+        _lib.check(_lib.load().lae_ssim_patch_backward(pred.data_ptr(), gt.data_ptr(), n, P, data_range, gout.data_ptr(),
+                                                       grad_pred.data_ptr(), _lib.stream()), "ssim_patch_backward")
+        return grad_pred, None, None, None
+
+
+def ssim_patch_loss(pred_rows, gt_rows, patch_size, data_range=1.0):
+    """the D-SSIM term of a patch batch: 1 - the mean over the patches of SSIM(pred patch, gt patch) (the definition: include/laenerf.h
+    above lae_ssim; 11-tap Gaussian windows inside the patch) as an fp32 scalar with autograd onto pred_rows; `.per_patch` holds the
+    float64 SSIMs.  pred_rows / gt_rows [n_patch * P^2, 3] as patch_pack takes them; patch_size >= 11; data_range positive (the data's
+    own range has no gradient).  One launch forward, one backward, no host read: capturable."""
+    P = int(patch_size)
+    if P < 11:
+        raise ValueError("ssim_patch_loss: patch_size must be at least 11 (the window)")
+    if pred_rows.dim() != 2 or pred_rows.shape[1] != 3 or pred_rows.shape != gt_rows.shape or pred_rows.shape[0] % (P * P) \
+            or pred_rows.shape[0] == 0:
+        raise ValueError("ssim_patch_loss: pred_rows and gt_rows must be [n_patch * patch_size^2, 3]")
+    L = float(data_range) if data_range is not None else 0.0
+    if not (L > 0.0 and L < float("inf")):
+        raise ValueError("ssim_patch_loss: data_range must be a positive finite number")
+    mean, per_patch = _ssim_patch.apply(pred_rows, gt_rows.detach(), P, L)
+    out = 1.0 - mean
+    out.per_patch = per_patch
+    return out
+
+
 def colour_loss_scaled(pred, target, scaler=None, loss="mse", huber_delta=0.1):
     """mse_loss_scaled with the criterion chosen by `loss`: 'mse', 'l1', 'huber' (the reference's loss.py huber_loss =
     torch's HuberLoss(huber_delta) / huber_delta) or 'mape' (loss.py mape_loss), the mean over all elements

@@ -35,7 +35,8 @@ from . import _lib
 from ._lib import check, ptr, stream
 
 __all__ = ["LPIPS", "alexnet_trunk", "load_lpips_alex", "load_masks", "eval_view", "eval_view_numpy", "psnr_from_sse",
-           "consistency_pair", "consistency_numpy", "lpips_head", "lpips_head_numpy", "lpips_head_grad_numpy", "patch_pack_numpy", "ALEX_CHANNELS", "ALEX_TAPS", "LPIPS_SHIFT", "LPIPS_SCALE", "EVAL_SCRATCH_DOUBLES", "CONSISTENCY_SCRATCH_DOUBLES"]
+           "consistency_pair", "consistency_numpy", "lpips_head", "lpips_head_numpy", "lpips_head_grad_numpy", "patch_pack_numpy", "ALEX_CHANNELS", "ALEX_TAPS", "LPIPS_SHIFT", "LPIPS_SCALE", "EVAL_SCRATCH_DOUBLES", "CONSISTENCY_SCRATCH_DOUBLES",
+           "ssim", "ssim_numpy", "ssim_grad_numpy", "ssim_scratch_doubles", "SSIM_TILE_H", "SSIM_TILE_W", "SSIM_MINMAX_BLOCKS"]
 
 ALEX_CHANNELS = (64, 192, 384, 256, 256)
 ALEX_TAPS = (1, 4, 7, 9, 11)                  # relu1..relu5 of torchvision's alexnet().features (lpips' pretrained alexnet slices)
@@ -44,6 +45,8 @@ LPIPS_SHIFT = (-0.030, -0.088, -0.188)        # lpips ScalingLayer
 LPIPS_SCALE = (0.458, 0.448, 0.450)
 EVAL_SCRATCH_DOUBLES = 2048                   # include/laenerf.h LAE_EVAL_VIEW_SCRATCH_DOUBLES
 CONSISTENCY_SCRATCH_DOUBLES = 16384           # include/laenerf.h LAE_CONSISTENCY_SCRATCH_DOUBLES
+SSIM_TILE_H, SSIM_TILE_W = 16, 32             # include/laenerf.h LAE_SSIM_TILE_H / _W: window positions per workgroup of lae_ssim
+SSIM_MINMAX_BLOCKS = 256                      # include/laenerf.h LAE_SSIM_MINMAX_BLOCKS
 _DTYPES = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
 
 
@@ -610,3 +613,113 @@ def consistency_numpy(frame_a, frame_b, depth_a, opacity_a, depth_b, opacity_b, 
             "bw_mean": np.stack([bmx, bmy], -1), "warped": Fw, "err": err, "occ_lhs": occ_lhs, "occ_rhs": occ_rhs,
             "bnd_lhs": bnd_lhs, "bnd_rhs": bnd_rhs, "margin": margin, "lpips_in": lp, "sse": sse, "count": count,
             "warp_mse": sse / count if count else float("nan")}
+
+
+# ---------------------------------------------------------------- SSIM (csrc/ssim.hip; the definition: include/laenerf.h above lae_ssim)
+def ssim_scratch_doubles(H, W):
+    """the float64 values of scratch `ssim` needs for an H x W pair (lae_ssim_scratch_doubles, restated: no library call)"""
+    H, W = int(H), int(W)
+    tiles = -(-(H - 10) // SSIM_TILE_H) * -(-(W - 10) // SSIM_TILE_W) if H >= 11 and W >= 11 else 0
+    return 4 * SSIM_MINMAX_BLOCKS + tiles
+
+
+def ssim(pred, gt, H, W, data_range=None, out=None, map=None, scratch=None):
+    """SSIM of one rendered view against its ground truth (lae_ssim; the reference's SSIMMeter, nerf/utils.py:259-293): pred, gt
+    contiguous fp32 with H*W*3 values (`pred` and `gt_out` of eval_view as they are).  data_range a positive number, or None: from
+    the data, max(max x - min x, max y - min y), on the device (two constant images: NaN).  out a float64 slot (allocated when
+    None), map an optional fp32 [H-10, W-10, 3] that receives S per window position, scratch float64 with
+    ssim_scratch_doubles(H, W) values.  No host read: the call can be captured.  -> out"""
+    H, W = int(H), int(W)
+    if H < 11 or W < 11:
+        raise ValueError(f"ssim: H and W must be at least 11 (the window), got {H} x {W}")
+    if H > 32768 or W > 32768 or 3 * H * W >= 2 ** 31:
+        raise ValueError("ssim: H and W at most 32768 and H * W * 3 < 2^31")
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != 3 * H * W:
+            raise ValueError(f"ssim: {name} must be a contiguous fp32 tensor of H x W x 3 values")
+    L = 0.0
+    if data_range is not None:
+        L = float(data_range)
+        if not (L > 0.0 and L < float("inf")):
+            raise ValueError("ssim: data_range must be a positive finite number, or None for the data's own range")
+    dev = pred.device
+    need = ssim_scratch_doubles(H, W)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=dev)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float64, device=dev)
+    for name, t, dt, n in (("out", out, torch.float64, 1), ("map", map, torch.float32, 3 * (H - 10) * (W - 10))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"ssim: {name} must be a contiguous {dt} tensor of {n} values")
+    if not torch.is_tensor(scratch) or scratch.dtype != torch.float64 or scratch.numel() < need or not scratch.is_contiguous():
+        raise ValueError(f"ssim: scratch must be a contiguous float64 tensor of at least {need} values")
+    _lib.need_cuda(pred, gt, out, map, scratch)
+    check(_lib.load().lae_ssim(ptr(pred), ptr(gt), H, W, L, ptr(scratch), ptr(out), ptr(map), stream()), "ssim")
+    return out
+
+
+def _ssim_window():
+    g = np.exp(-((np.arange(11, dtype=np.float64) - 5.0) / 1.5) ** 2 / 2.0)
+    return g / g.sum()
+
+
+def _ssim_terms(x, y, data_range):
+    """-> x, y as float64 [H, W, C], the window, and A1, A2, B1, B2, mx, my per window position"""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if x.ndim != 3 or x.shape != y.shape:
+        raise ValueError("ssim_numpy: x and y must be two [H, W, C] arrays of one shape")
+    H, W = x.shape[:2]
+    if H < 11 or W < 11:
+        raise ValueError(f"ssim_numpy: H and W must be at least 11 (the window), got {H} x {W}")
+    if data_range is None:
+        L = max(x.max() - x.min(), y.max() - y.min())
+    else:
+        L = float(data_range)
+        if not L > 0.0:
+            raise ValueError("ssim_numpy: data_range must be positive, or None for the data's own range")
+    g = _ssim_window()
+
+    def win(a):                                   # separable, horizontal then vertical, taps in ascending order
+        t = sum(g[k] * a[:, k:k + W - 10] for k in range(11))
+        return sum(g[k] * t[k:k + H - 10] for k in range(11))
+
+    mx, my, exx, eyy, exy = win(x), win(y), win(x * x), win(y * y), win(x * y)
+    C1, C2 = (0.01 * L) ** 2, (0.03 * L) ** 2
+    A1, A2 = 2 * mx * my + C1, 2 * (exy - mx * my) + C2
+    B1, B2 = mx * mx + my * my + C1, (exx - mx * mx) + (eyy - my * my) + C2
+    return x, y, g, L, A1, A2, B1, B2, mx, my
+
+
+def ssim_numpy(x, y, data_range=None, full=False):
+    """float64 restatement of lae_ssim: x, y [H, W, C] -> the mean of S over the C (H - 10)(W - 10) window values (full=True: and the
+    map S [H-10, W-10, C]).  data_range None: from the data; a range of 0 (two constant images) gives NaN, as 0 / 0 does in torch.
+    ValueError below 11 pixels."""
+    _, _, _, L, A1, A2, B1, B2, _, _ = _ssim_terms(x, y, data_range)
+    if L == 0.0:
+        S = np.full(A1.shape, np.nan)
+    else:
+        S = (A1 * A2) / (B1 * B2)
+    return (float(S.mean()), S) if full else float(S.mean())
+
+
+def ssim_grad_numpy(x, y, data_range=1.0):
+    """float64 restatement of lae_ssim_patch_backward for one image: d ssim_numpy(x, y, data_range) / d x, [H, W, C]"""
+    if data_range is None:
+        raise ValueError("ssim_grad_numpy: the data rule has no gradient here; give a positive data_range")
+    x, y, g, _, A1, A2, B1, B2, mx, my = _ssim_terms(x, y, data_range)
+    H, W = x.shape[:2]
+    S = (A1 * A2) / (B1 * B2)
+    Dm = (2 * my * A2 - 2 * my * A1) / (B1 * B2) - S * (2 * mx / B1 - 2 * mx / B2)
+    Dxx = -S / B2
+    Dxy = 2 * A1 / (B1 * B2)
+
+    def spread(D):                                # the transpose of the forward pass: every window's value back over its pixels
+        t = np.zeros((H,) + D.shape[1:])
+        for k in range(11):
+            t[k:k + H - 10] += g[k] * D
+        out = np.zeros(x.shape)
+        for k in range(11):
+            out[:, k:k + W - 10] += g[k] * t
+        return out
+
+    return (spread(Dm) + 2 * x * spread(Dxx) + y * spread(Dxy)) / S.size

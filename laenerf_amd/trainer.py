@@ -187,6 +187,11 @@ class Trainer:
     truncated_steps() the steps that asked for more samples than their limit, peak_to_mean() the largest count over the mean.  All
     four `loss` kinds and ema_decay work; error_map, depth_weight, distort_weight, opacity_weight, pixel_weights, second_weight,
     pose_refine and exposure_refine are refused (ValueError) before anything is changed on the data.
+    ssim_weight: None (every path as it is, bit for bit) or a weight >= 0 of the D-SSIM term `1 - mean over the patches of SSIM(pred
+    patch, gt patch)` (losses.ssim_patch_loss, data range 1; the 1 - SSIM that 3DGS-style recipes add to L1) in a patch step, scaled by
+    the loss scale like the LPIPS term and inside the same captured groups; ssim_losses() holds the per-step term without its weight.
+    With it lpips=None is allowed -- the LPIPS chain is left out, no weights are needed -- and then patch_size >= 11 suffices; with
+    both terms the rule stays patch_size >= 32.  Part of a checkpoint's configuration only when set.
     Counters: captures (graphs captured), cache_misses (groups whose capacity had no graph yet), warm_groups (groups run
     eagerly because their capacity exceeded every size run before: library workspaces cannot grow inside a capture)."""
 
@@ -195,18 +200,25 @@ class Trainer:
                  distort_weight=None, distort_grad=True, loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True,
                  pixel_weights=False, second_weight=None, pose_refine=False, pose_lr=1e-3, pose_betas=(0.9, 0.99), pose_eps=1e-15,
                  exposure_refine=False, exposure_lr=1e-2, exposure_mode="rgb", exposure_betas=(0.9, 0.99), exposure_eps=1e-15,
-                 exposure_center=True, patch_size=1, perceptual_weight=1e-3, lpips=None, perceptual_normalize=False, patch_headroom=2.0):
+                 exposure_center=True, patch_size=1, perceptual_weight=1e-3, lpips=None, perceptual_normalize=False, patch_headroom=2.0,
+                 ssim_weight=None):
         if capacity not in ("bucket", "exact"):
             raise ValueError("Trainer: capacity must be 'bucket' or 'exact'")
         if error_map not in (None, "ema", "fixed"):
             raise ValueError("Trainer: error_map must be None, 'ema' or 'fixed'")
         patch_size = int(patch_size)
+        if ssim_weight is not None:                                   # refused before anything is changed on the data
+            ssim_weight = raymarching.check_weight("Trainer", "ssim_weight", ssim_weight)
+            if patch_size == 1:
+                raise ValueError("Trainer: ssim_weight needs patch_size > 1 (the D-SSIM term is a loss on patches)")
+            if patch_size < 11:
+                raise ValueError("Trainer: ssim_weight needs patch_size >= 11 (SSIM's 11 x 11 window must fit in a patch)")
         if patch_size != 1:                                           # refused before anything is changed on the data
             from .metrics import LPIPS
-            if patch_size < 32:
+            if patch_size < 32 and (ssim_weight is None or lpips is not None):
                 raise ValueError("Trainer: patch_size must be 1 or at least 32 (below 32 AlexNet's second max-pool has no output, "
                                  "so the LPIPS term does not exist)")
-            if not isinstance(lpips, LPIPS):
+            if not isinstance(lpips, LPIPS) and (ssim_weight is None or lpips is not None):
                 raise ValueError("Trainer: patch_size > 1 needs lpips=, a metrics.LPIPS (load_lpips_alex(...) or LPIPS.random(seed))")
             on = {"error_map": error_map is not None or getattr(data, "error_map", None) is not None, "depth_weight": depth_weight is not None,
                   "distort_weight": distort_weight is not None, "opacity_weight": opacity_weight is not None,
@@ -326,8 +338,15 @@ class Trainer:
         self.skip_perceptual = False             # patch mode only: leave the LPIPS chain out of the step (what perceptual_weight=0 must equal)
         self.n_rays = self.num_rays              # the rays a step trains
         self.perceptual_slots = None
+        self.ssim_weight, self.ssim_slots = ssim_weight, None
         if patch_size != 1:
-            self.lpips = lpips.to(dev)
+            if lpips is not None:
+                self.lpips = lpips.to(dev)
+            else:                                # ssim_weight alone: the LPIPS chain is never run
+                self.skip_perceptual = True
+            if ssim_weight is not None:
+                self.ssim_slots = torch.zeros(GROUP, dtype=torch.float32, device=dev)
+                self._records["ssim"] = (self.ssim_slots, [])
             self.n_rays = (self.num_rays // (patch_size * patch_size)) * patch_size * patch_size
             self.perceptual_slots = torch.zeros(GROUP, dtype=torch.float32, device=dev)
             self._records["perceptual"] = (self.perceptual_slots, [])
@@ -451,6 +470,14 @@ class Trainer:
             loss = loss + (term * opt._scale_view[0] if opt.use_scaler else term)
             with torch.no_grad():
                 self.perceptual_slots[k].copy_(lp.detach())
+        if self.ssim_weight is not None:
+            from .losses import ssim_patch_loss
+            ds = ssim_patch_loss(image, b["gt"], self.patch_size)
+            term = self.ssim_weight * ds
+            total = total + term.detach()
+            loss = loss + (term * opt._scale_view[0] if opt.use_scaler else term)
+            with torch.no_grad():
+                self.ssim_slots[k].copy_(ds.detach())
         opt.backward(loss)
         opt.step()
         if self.ema is not None:
@@ -518,7 +545,7 @@ class Trainer:
 
     # ------------------------------------------------------------------ results
     # the accessors of every per-step record (a resume's test compares them all)
-    RECORDS = ("losses", "depth_losses", "distort_losses", "opacity_losses", "second_losses", "perceptual_losses")
+    RECORDS = ("losses", "depth_losses", "distort_losses", "opacity_losses", "second_losses", "perceptual_losses", "ssim_losses")
 
     def _record(self, name):
         """the history of per-step record `name` as a float32 numpy array; empty when this trainer does not keep it"""
@@ -557,6 +584,11 @@ class Trainer:
         """per-step LPIPS term (the mean over the step's patches), without its weight, as a float32 numpy array (empty without
         patch_size > 1; zeros for steps run with skip_perceptual)"""
         return self._record("perceptual")
+
+    def ssim_losses(self):
+        """per-step D-SSIM term (1 - the mean over the step's patches of SSIM), without its weight, as a float32 numpy array (empty
+        without ssim_weight)"""
+        return self._record("ssim")
 
     def truncated_steps(self):
         """patch mode: the number of steps so far whose requested sample count exceeded the limit they marched under, so that rays
@@ -643,6 +675,8 @@ class Trainer:
         if self.patch_size != 1:
             cfg["patch_size"], cfg["perceptual_weight"] = self.patch_size, self.perceptual_weight
             cfg["perceptual_normalize"], cfg["patch_headroom"] = self.perceptual_normalize, self.patch_headroom
+            if self.ssim_weight is not None:         # only when set: files written without it stay as they were
+                cfg["ssim_weight"] = self.ssim_weight
         return cfg
 
     def state_dict(self, full=True):
@@ -923,13 +957,16 @@ class Trainer:
         Image.fromarray(depth_u8.cpu().numpy()).save(os.path.join(out_dir, f"{name}_{i:04d}_depth.png"))
 
     @torch.no_grad()
-    def evaluate_one_epoch(self, data, lpips=None, masks=None, out_dir=None, name="ngp"):
+    def evaluate_one_epoch(self, data, lpips=None, masks=None, out_dir=None, name="ngp", ssim=False, ssim_data_range=None):
         """the reference's evaluate_one_epoch (nerf/utils.py:1526-1624, eval_step :674-698) over every view of `data` (a
         ResidentImages): rendered with the EMA weights over white, scale_depth=False; per view one lae_eval_view pass (PSNRMeter's
         squared error into a device slot; with `lpips` (metrics.LPIPS) its input, then the trunk and the head; with `masks` (a list
         of uint8 [H, W] or None per view, metrics.load_masks) eval_masked's MSE); one host read for the whole split.  out_dir:
         `{name}_{i:04d}_rgb.png` / `_depth.png` (uint8, clipped).  -> dict psnr [n], lpips [n] or None, masked_mse [n] (NaN where
-        a view has no mask) or None, mean_psnr, mean_lpips, mean_masked_mse (over the views with a mask).
+        a view has no mask) or None, mean_psnr, mean_lpips, mean_masked_mse (over the views with a mask), ssim [n] or None, mean_ssim.
+        ssim=True: the reference's SSIMMeter (nerf/utils.py:259-293) -- eval_view also writes the blended ground truth and one
+        metrics.ssim call per view scores it against the render into a device slot, read with the same host read; ssim_data_range None is
+        the reference's call (the range of each view's own pair), else a positive number.  ssim=False launches and allocates nothing new.
         Also appends the mean squared error over the evaluated views to stats['results'], which save_checkpoint(best=True) compares:
         lower is better.  (The reference appends its PSNR there and still keeps the minimum, nerf/utils.py:1606-1611, :1671 -- a quirk
         not kept.)"""
@@ -944,6 +981,15 @@ class Trainer:
         lp_in = torch.empty(2, 3, H, W, dtype=torch.float32, device=dev) if lpips is not None else None
         rgb_u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if out_dir else None
         depth_u8 = torch.empty(H, W, dtype=torch.uint8, device=dev) if out_dir else None
+        ss = gt_out = ss_scratch = None
+        if ssim:
+            if H < 11 or W < 11:
+                raise ValueError(f"evaluate_one_epoch: ssim needs views of at least 11 x 11 pixels, got {H} x {W}")
+            if ssim_data_range is not None and not (0.0 < float(ssim_data_range) < float("inf")):
+                raise ValueError("evaluate_one_epoch: ssim_data_range must be a positive finite number, or None for each view's own range")
+            ss = torch.zeros(n, dtype=torch.float64, device=dev)
+            gt_out = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
+            ss_scratch = torch.empty(M.ssim_scratch_doubles(H, W), dtype=torch.float64, device=dev)
         has_mask = np.zeros(n, bool)
         with self._eval_weights():
             for i in range(n):
@@ -956,18 +1002,25 @@ class Trainer:
                 pred, depth = self._render_view(data, i, scale_depth=False)
                 M.eval_view(pred, data.images[i], depth=depth, bg=1.0, sse=sums[i, 0:1], mask=m,
                             masked_sse=sums[i, 1:2] if m is not None else None, rgb_u8=rgb_u8, depth_u8=depth_u8, lpips_in=lp_in,
-                            scratch=scratch)
+                            scratch=scratch, gt_out=gt_out)
                 if lpips is not None:
                     lpips(lp_in, out=lp[i:i + 1])
+                if ssim:
+                    M.ssim(pred, gt_out, H, W, data_range=ssim_data_range, out=ss[i:i + 1], scratch=ss_scratch)
                 if out_dir:
                     self._write_pngs(out_dir, name, i, rgb_u8, depth_u8)
-        s = sums.cpu().numpy()
+        if ssim:                                                       # one host read for the whole split: the SSIMs ride with the sums
+            s = torch.cat([sums, ss[:, None]], 1).cpu().numpy()
+        else:
+            s = sums.cpu().numpy()
         res = {"psnr": M.psnr_from_sse(s[:, 0], 3 * H * W), "lpips": None if lp is None else lp.cpu().numpy(), "masked_mse": None}
         if masks is not None:
             res["masked_mse"] = np.where(has_mask, s[:, 1] / (3 * H * W), np.nan)
         res["mean_psnr"] = float(np.mean(res["psnr"]))
         res["mean_lpips"] = None if lp is None else float(np.mean(res["lpips"]))
         res["mean_masked_mse"] = float(np.mean(res["masked_mse"][has_mask])) if has_mask.any() else None
+        res["ssim"] = s[:, 2].copy() if ssim else None
+        res["mean_ssim"] = float(np.mean(res["ssim"])) if ssim else None
         self.stats["results"].append(float(s[:, 0].sum() / (n * 3 * H * W)))
         return res
 

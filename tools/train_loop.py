@@ -9,7 +9,7 @@ refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated o
                                 [--loss mse|l1|huber|mape] [--huber-delta D] [--entropy W] [--outliers P]
                                 [--mask-outliers P] [--pose-noise DEG,DIST] [--pose-lr LR]
                                 [--exposure-noise STOPS] [--exposure-lr LR]
-                                [--patch-size P] [--lpips-weight W] [--lpips-weights ALEXNET.pth,ALEX.pth]
+                                [--patch-size P] [--lpips-weight W] [--lpips-weights ALEXNET.pth,ALEX.pth] [--ssim-weight W]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
 ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR.
@@ -43,6 +43,9 @@ what the refinement buys, and breakdown.replay_ms_per_step for its cost.
 step with the LPIPS term (Trainer(patch_size=P, perceptual_weight=W, lpips=...)); without weight files the term uses LPIPS.random(0),
 seeded stand-in weights, and the line says so.  The line then carries "patch": ms_per_step (after the first 64 steps), truncated_steps,
 the peak-to-mean ratio of the per-step sample count, the LPIPS term's first and last 16-step mean and the held-out PSNR.
+--ssim-weight W (with --patch-size P): the D-SSIM term 1 - SSIM of the patches with weight W (Trainer(ssim_weight=W)); "patch" then also
+carries its first and last 16-step mean.  With --lpips-weight 0 and no --lpips-weights the trainer gets lpips=None: D-SSIM alone, and
+P >= 11 is enough.
 --save PATH: the first student's checkpoint is written after the run (Trainer.save_checkpoint; a `.pth` path or a directory);
 --resume PATH: the first student loads it before training and then trains --steps further steps (the same --steps as the saved run
 keeps the learning-rate horizon, which the load checks).  The line then carries "checkpoint": the file size in bytes and the save /
@@ -117,7 +120,7 @@ def teacher_views(dev, n_views, H, W, seed=0, bound=1, opacity=1.5, radius=3.2):
 def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=True, capacity="bucket", seed=0, student_seed=0,
                  error_map=None, ema_decay=None, depths=None, depth_weight=None, depth_grad=True, distort_weight=None, loss="mse",
                  huber_delta=0.1, opacity_weight=None, pixel_weights=None, pose_lr=None, exposure_lr=None, patch_size=1, lpips=None,
-                 perceptual_weight=1e-3):
+                 perceptual_weight=1e-3, ssim_weight=None):
     from laenerf_amd.data import ResidentImages
     from laenerf_amd.network import NeRFNetwork
     from laenerf_amd.optim import FusedAdam
@@ -141,6 +144,8 @@ def make_trainer(dev, images, poses, intr, iters, lr=1e-2, n_rays=4096, graph=Tr
         depth_kw.update(exposure_refine=True, exposure_lr=exposure_lr)
     if patch_size != 1:
         depth_kw.update(patch_size=patch_size, lpips=lpips, perceptual_weight=perceptual_weight)
+        if ssim_weight is not None:
+            depth_kw["ssim_weight"] = ssim_weight
     return Trainer(r, opt, data, iters, lr, num_rays=n_rays, seed=seed, graph=graph, capacity=capacity, error_map=error_map,
                    ema_decay=ema_decay, **depth_kw)
 
@@ -215,6 +220,8 @@ def main():
     ap.add_argument("--patch-size", type=int, default=1, metavar="P", help="Trainer(patch_size=P): rays // P^2 patches per step, LPIPS term")
     ap.add_argument("--lpips-weight", type=float, default=1e-3, metavar="W", help="Trainer(perceptual_weight=W)")
     ap.add_argument("--lpips-weights", default=None, metavar="ALEXNET.pth,ALEX.pth", help="torchvision alexnet + lpips v0.1 alex weights")
+    ap.add_argument("--ssim-weight", type=float, default=None, metavar="W",
+                    help="Trainer(ssim_weight=W), with --patch-size: the D-SSIM term; with --lpips-weight 0 and no --lpips-weights, lpips=None")
     ap.add_argument("--save", default=None, metavar="PATH", help="write the first student's checkpoint after the run")
     ap.add_argument("--resume", default=None, metavar="PATH", help="load a checkpoint into the first student before training")
     args = ap.parse_args()
@@ -239,15 +246,23 @@ def main():
     crit_kw = dict(loss=args.loss, huber_delta=args.huber_delta, opacity_weight=args.entropy, pixel_weights=mask, pose_lr=args.pose_lr,
                    exposure_lr=args.exposure_lr)
     patch = None
+    if args.ssim_weight is not None and args.patch_size == 1:
+        ap.error("--ssim-weight needs --patch-size P")
     if args.patch_size != 1:
         from laenerf_amd.metrics import LPIPS, load_lpips_alex
         if args.lpips_weights:
             lp = load_lpips_alex(*args.lpips_weights.split(","), device=dev)
+        elif args.ssim_weight is not None and args.lpips_weight == 0:
+            lp = None                                                  # D-SSIM alone: no LPIPS chain, no weights
         else:
             lp = LPIPS.random(0, device=dev)
         patch = {"patch_size": args.patch_size, "lpips_weight": args.lpips_weight,
-                 "lpips_weights": args.lpips_weights or "LPIPS.random(0): seeded stand-in weights, not a perceptual metric"}
+                 "lpips_weights": args.lpips_weights or ("none: lpips=None" if lp is None else
+                                                          "LPIPS.random(0): seeded stand-in weights, not a perceptual metric")}
         crit_kw.update(patch_size=args.patch_size, lpips=lp, perceptual_weight=args.lpips_weight)
+        if args.ssim_weight is not None:
+            patch["ssim_weight"] = args.ssim_weight
+            crit_kw["ssim_weight"] = args.ssim_weight
     true_poses = poses.copy()
     if args.pose_noise:
         from laenerf_amd.poses import perturb_poses
@@ -297,6 +312,9 @@ def main():
         patch.update(ms_per_step=round(steady, 4), rays_per_step=tr.n_rays, truncated_steps=tr.truncated_steps(),
                      peak_count=int(tr.r.peak_count), peak_to_mean=round(tr.peak_to_mean(), 3), patch_headroom=tr.patch_headroom,
                      first_lpips=float(perc[:16].mean()), final_lpips=float(perc[-16:].mean()), heldout_psnr_white=round(p, 3))
+        if args.ssim_weight is not None:
+            ds = tr.ssim_losses()
+            patch.update(first_dssim=float(ds[:16].mean()), final_dssim=float(ds[-16:].mean()))
     refresh_ms, group_ms = _replay_windows(tr)
     if exposure is not None and args.exposure_lr is not None:
         exposure["step_and_publish_us"] = round(_exposure_launch_us(tr), 2)
