@@ -75,7 +75,7 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward -- a binding that needs them also checks that the library exports them).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors -- a binding that needs them also checks that the library exports them).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
 #define LAE_ABI_TAG "abi27"
@@ -1130,6 +1130,40 @@ LAE_API int lae_mask_lift_pack(const float* depth, const float* opacity, const u
 LAE_API int lae_mask_lift(const float* packed, const float* poses, uint32_t V, float fx, float fy, float cx, float cy, uint32_t H,
                           uint32_t W, const uint8_t* density_bitfield, uint32_t C, uint32_t G, float bound, float depth_margin,
                           uint32_t min_views, float min_share, uint8_t* grid_out, uint16_t* votes_out, void* stream);
+
+/* ---- TSDF mesh export: fuse rendered depth and colour views on a lattice (csrc/tsdf.hip, where the rule is written down in
+ * full; tsdf.py restates both kernels in numpy).  The reference has no counterpart ----
+ * lae_tsdf_fuse: V packed views [V,H,W] (the plane lae_mask_lift_pack writes: t_surf = |packed|, the sign bit ignored, +inf = a
+ *   transparent pixel, NaN = no observation; poses fp32 [V,4,4] cam2world, row-major, on the device; one set of intrinsics) on
+ *   the lattice of three fp32 axis arrays xs[nx], ys[ny], zs[nz] on the device: voxel (i, j, k) sits at (xs[i], ys[j], zs[k]) and
+ *   the outputs are indexed (i * ny + j) * nz + k.  frames: optional uint8 [V,H,W,3].
+ *   Per (voxel, view), in ascending view order, with lae_mask_lift's projection statement for statement: d = p - o, q = R^T d;
+ *   q.z <= 0 or (u, v) = (fx q.x / q.z + cx, fy q.y / q.z + cy) outside [0, W) x [0, H): no observation.  s = t_surf - |d| at
+ *   pixel (floor u, floor v); a NaN t_surf: no observation; s < -trunc: occluded (n_occ += 1); s > trunc: free (n_free += 1);
+ *   otherwise near: n_near += 1, S += s / trunc (an fp32 running sum), and the pixel's three bytes are added to uint32 sums.
+ *   Per voxel, n_obs = n_near + n_free: tsdf = (S + float(n_free)) / float(n_obs) if n_obs >= min_views, else -1 if n_occ > 0
+ *   (space is solid until seen empty), else +1 (never in any frame).
+ *   u      fp32 [nx*ny*nz] = -tsdf: larger inside, like a density; marching cubes at threshold 0
+ *   counts optional uint16 [nx*ny*nz, 4] = (near, free, occluded, 0); 8-byte aligned
+ *   rgb    optional fp32 [nx*ny*nz, 3] = float(sum) / float(n_near) / 255, zeros where n_near == 0; needs frames
+ *   Poses go through LDS in chunks of LAE_TSDF_POSE_CHUNK views; per (brick of 4 x 4 x 16 voxels, view) a conservative cull
+ *   (the brick's bounding sphere against the camera's half-space and the four frame planes) skips views that contribute
+ *   nothing, so the sums keep their order; LAE_TSDF_CULL=0 in the environment (read per call) turns it off, the bytes are the
+ *   same.  A thread owns its voxel: no atomics, no host read, no allocation, and two calls give the same bytes.
+ *   NULL packed / poses / xs / ys / zs / u, or rgb without frames: LAE_ENULL; V == 0 or V > 65535, H or W < 1, H * W >= 2^31, an
+ *   axis shorter than 2 or longer than 512 (marching cubes' limit), fx or fy <= 0, trunc <= 0 or not finite, min_views == 0, a
+ *   NaN among them, counts not 8-byte aligned: LAE_EINVAL; both before any launch.
+ * lae_tsdf_vertex_colors: colours [V,3] fp32 for marching-cubes vertices verts [V,3] fp32 (index space) from lae_tsdf_fuse's rgb
+ *   and counts.  The vertex's lattice edge (base, axis, t) is located as lae_mesh_vertex_attrs does; both endpoints have
+ *   n_near > 0: c_a + t (c_b - c_a); one has: its colour; neither: 0.5.  n_grey: optional device uint32, set to the number of
+ *   vertices that fell back to grey (zeroed by the call; integer adds).  V == 0: LAE_OK, nothing launched. */
+#define LAE_TSDF_POSE_CHUNK 64
+LAE_API int lae_tsdf_fuse(const float* packed, const float* poses, uint32_t V, float fx, float fy, float cx, float cy, uint32_t H,
+                          uint32_t W, const float* xs, const float* ys, const float* zs, uint32_t nx, uint32_t ny, uint32_t nz,
+                          const uint8_t* frames, float trunc, uint32_t min_views, float* u, uint16_t* counts, float* rgb,
+                          void* stream);
+LAE_API int lae_tsdf_vertex_colors(const float* rgb, const uint16_t* counts, uint32_t nx, uint32_t ny, uint32_t nz, const float* verts,
+                                   uint32_t V, float* colors, uint32_t* n_grey, void* stream);
 
 /* ---- occupancy-grid maintenance (nerf/renderer.py:482-649, Python in the reference) ----
  * positions: point j -> xyz = (2 c / (H-1) - 1) * (bound_c - bound_c/H) + (noise * 2 - 1) * bound_c/H and its Morton index

@@ -190,6 +190,70 @@ class NeRFRenderer(nn.Module):
         v = mesh.scale_vertices(m["index_vertices"].cpu().numpy(), self.aabb_infer[:3], self.aabb_infer[3:], resolution)
         return v, m["triangles"].cpu().numpy()
 
+    # ------------------------------------------------------------------ TSDF mesh export (tsdf.py)
+    @torch.no_grad()
+    def extract_mesh_tsdf(self, poses, intrinsics, H, W, resolution=256, trunc_voxels=3.0, frames=None, depths=None, opacities=None,
+                          min_opacity=0.5, min_views=1, normals=True, colors=True, keep_largest=False, min_component=None,
+                          min_component_fraction=None):
+        """a mesh of the surface the renders show: the views of `poses` ([V, 4, 4] cam2world, one set of intrinsics) are rendered
+        (tsdf.render_packed_views; depths / opacities replace the renders), fused into a truncated signed distance field on a
+        resolution^3 lattice over aabb_infer (tsdf.tsdf_fuse, trunc = trunc_voxels x the largest axis spacing), and marching
+        cubes runs at zero -- no density threshold to guess.  -> a dict of device tensors like extract_mesh_attributes:
+        `vertices` [V,3] fp32 in the box, `triangles` [T,3] int32, on request `normals` [V,3] fp32 (unit, outward) and `colors`
+        [V,3] fp32 in [0, 1] fused from `frames` ([V, H, W, 3] uint8 or fp32 on the device, in the poses' order: recolor_views(...),
+        tr.test(...)[0], ...; None: the model's own renders of the same views), plus `n_grey`, the number of vertices no view
+        coloured (grey 0.5).  keep_largest / min_component / min_component_fraction: mesh.drop_components on the fused field
+        before marching cubes.  The fill rule leaves what is seen only as occluded solid (tsdf.py's docstring): such blobs are
+        what keep_largest=True is for."""
+        out = self._mesh_tsdf(poses, intrinsics, H, W, resolution, trunc_voxels, frames, depths, opacities, min_opacity, min_views,
+                              normals, colors, keep_largest, min_component, min_component_fraction)
+        del out["index_vertices"]
+        return out
+
+    def _mesh_tsdf(self, poses, intrinsics, H, W, resolution, trunc_voxels, frames, depths, opacities, min_opacity, min_views, normals,
+                   colors, keep_largest, min_component, min_component_fraction):
+        """extract_mesh_tsdf plus `index_vertices`, the marching-cubes vertices in index space"""
+        from . import mesh, tsdf
+        resolution = int(resolution)
+        if not float(trunc_voxels) > 0.0:
+            raise ValueError("extract_mesh_tsdf: trunc_voxels must be positive")
+        aabb = self.aabb_infer.cpu()
+        bmin, bmax = aabb[:3], aabb[3:]
+        dev = self.aabb_infer.device
+        poses = poses.reshape(-1, 4, 4).to(dev).float().contiguous()
+        axes = mesh.lattice(bmin, bmax, resolution)
+        trunc = float(trunc_voxels) * max(float(a[1] - a[0]) for a in axes)
+        own = None
+        if colors and frames is None:
+            packed, own = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity, return_frames=True)
+        else:
+            packed = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity)
+        f = tsdf.tsdf_fuse(packed, poses, intrinsics, H, W, axes, trunc, frames=(own if frames is None else frames) if colors else None,
+                           min_views=min_views)
+        u = f["u"]
+        v, t = mesh.marching_cubes(mesh.drop_components(u, 0.0, keep_largest, min_component, min_component_fraction), 0.0)
+        attrs = mesh.vertex_attributes(u, v, bmin, bmax, want=("pos",) + (("normals",) if normals else ()))
+        out = {"vertices": attrs["pos"], "triangles": t, "index_vertices": v}
+        if normals:
+            out["normals"] = attrs["normals"]
+        if colors:
+            out["colors"], out["n_grey"] = tsdf.tsdf_vertex_colors(f["rgb"], f["counts"], v)
+        return out
+
+    def save_mesh_tsdf(self, path, poses, intrinsics, H, W, resolution=256, trunc_voxels=3.0, frames=None, depths=None, opacities=None,
+                       min_opacity=0.5, min_views=1, normals=True, colors=True, keep_largest=False, min_component=None,
+                       min_component_fraction=None):
+        """extract_mesh_tsdf written as a binary PLY, the file's bodies packed on the device (mesh.pack_ply).  An empty result
+        writes a valid PLY with zero elements.  -> (vertices [V,3] float64, triangles [T,3] int32) on the host, like save_mesh"""
+        from . import mesh
+        with torch.no_grad():
+            m = self._mesh_tsdf(poses, intrinsics, H, W, resolution, trunc_voxels, frames, depths, opacities, min_opacity, min_views,
+                                normals, colors, keep_largest, min_component, min_component_fraction)
+        head, vb, fb = mesh.pack_ply(m["vertices"], m["triangles"], normals=m.get("normals"), colors=m.get("colors"))
+        mesh.write_ply_packed(path, head, vb, fb)
+        v = mesh.scale_vertices(m["index_vertices"].cpu().numpy(), self.aabb_infer[:3], self.aabb_infer[3:], int(resolution))
+        return v, m["triangles"].cpu().numpy()
+
     # ------------------------------------------------------------------ occupancy-grid maintenance
     @torch.no_grad()
     def mark_untrained_grid(self, poses, intrinsic):

@@ -898,6 +898,17 @@ class Trainer:
                                     **{k: v for k, v in kwargs.items() if k in ("keep_largest", "min_component", "min_component_fraction")})
         return self.r.save_mesh(path, resolution=resolution, threshold=threshold, normals=normals, colors=colors, **kwargs)
 
+    def save_mesh_tsdf(self, path, data=None, frames=None, **kwargs):
+        """the surface the renders show as a binary PLY with normals and colours (NeRFRenderer.save_mesh_tsdf; DESIGN.md section
+        4h): the views of `data` (a ResidentImages; default the training data) are rendered with the EMA weights, fused into a
+        truncated signed distance field and meshed at zero.  frames: [n, H, W, 3] uint8 or fp32 on the device in the data's
+        camera order (recolor_views(...), tr.test(...)[0], ...) -- their colours are baked into the vertices, so a palette edit
+        or a stylization leaves as a mesh without being distilled first; None bakes the model's own renders.  kwargs:
+        resolution, trunc_voxels, min_views, normals, colors, keep_largest, ... of NeRFRenderer.extract_mesh_tsdf."""
+        data = self.data if data is None else data
+        with self._eval_weights():
+            return self.r.save_mesh_tsdf(path, data.poses, data.intrinsics, data.H, data.W, frames=frames, **kwargs)
+
     @torch.no_grad()
     def evaluate(self, views, data=None, bg_color=1.0):
         """mean PSNR over `views` (image indices of `data`, default the training set) rendered with render_eval over a plain
