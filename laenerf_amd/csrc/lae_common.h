@@ -80,7 +80,7 @@ uint32_t frame_head_max_blocks();
 }  // namespace lae
 namespace lae_dw { struct DwTailJob; }                       // dw_reduce.h
 namespace lae {
-// lae_nerf_head_backward (ffmlp.hip) for the fused field backward (lae_nerf_field_backward, gridencoder.hip): with `tail` the
+// lae_nerf_head_backward (ffmlp.hip) for the fused field backward (lae_nerf_field_backward, gridbackward.hip): with `tail` the
 // reduction of the weight-gradient slabs and the deferred loss value are returned as a job (n_tasks == 0: nothing left to do)
 // for the grid backward's accumulate pass instead of being launched
 int nerf_head_backward(const float* grad_sigmas, const float* grad_rgbs, const void* enc, const float* dirs, const void* h,

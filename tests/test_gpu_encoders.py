@@ -160,6 +160,30 @@ def test_grid_backward_fp16_exact_sum(O, B, gscale):
     assert err.max() < 2e-3 * np.abs(ref32).max() + 1e-6        # one fp16 rounding of the sum (+ per-contribution rounding)
 
 
+@pytest.mark.parametrize("B", [5, 1027])
+@pytest.mark.parametrize("kw", [dict(gridtype=1), dict(align=True), dict(interp=1), dict(gridtype=1, align=True, interp=1)])
+def test_grid_backward_fp16_walk_outside_plain(O, kw, B):
+    """the fp16 walk outside its PLAIN instantiation (tiled grid type, align_corners, smoothstep): the same exact sum, rounded
+    once, and the same bits on every run.  B = 5: less than one group of 4 samples plus a ragged one; B = 1027: one whole unit of
+    1024 samples and a second unit that holds only the 3-sample ragged tail."""
+    from laenerf_amd.backend import gridencoder_backend as G
+    gt, al, interp = kw.get("gridtype", 0), kw.get("align", False), kw.get("interp", 0)
+    offsets, pls, table, x = grid_case(O, L=4, T_log2=14, desired=512, B=B, align=al)
+    L, C = 4, 2
+    g = (np.random.default_rng(2).standard_normal((L, B, C)) * 0.1).astype(np.float32)
+    gh = O.to_f16_bits(g)
+    ges = []
+    for _ in range(2):
+        ge = torch.zeros(table.shape, device=DEV, dtype=torch.half)
+        G.grid_encode_backward(half_from_bits(gh), T(x), T(table).half(), T(offsets), ge, B, 3, C, L, np.log2(pls), 16, None, None, gt, al, interp)
+        ges.append(ge)
+    assert torch.equal(ges[0], ges[1])
+    ref32, _ = O.grid_encode_backward(O.from_f16_bits(gh), x, table.shape, offsets, pls, 16, gridtype=gt, align_corners=al, interp=interp)
+    err = np.abs(N(ges[0]) - ref32)
+    print(f"max err {err.max():.3e} bound {2e-3 * np.abs(ref32).max() + 1e-6:.3e}")
+    assert err.max() < 2e-3 * np.abs(ref32).max() + 1e-6        # one fp16 rounding of the sum (+ per-contribution rounding)
+
+
 @pytest.mark.parametrize("B", [50000, 4099, 400003])
 def test_grid_backward_fp16_bit_exact_on_lattice_points(O, B):
     """samples ON the vertices of a level whose scale is a power of two (resolution 17 -> scale 16, x = (k + 0.5) / 16):

@@ -47,7 +47,7 @@ for _ in range(5):
     run()
 torch.cuda.synchronize()
 lib = _lib.load()
-fn = lib.lae_debug_grid_stamps
+fn = lib.lae_debug_grid_bwd_stamps
 fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
 fn.restype = ctypes.c_int
 buf = np.zeros((8192, 32), dtype=np.uint64)
@@ -86,7 +86,7 @@ offs = enc.offsets_host if hasattr(enc, "offsets_host") else enc.offsets.cpu().n
 offs = np.asarray(offs).astype(np.int64)
 sizes = offs[1:] - offs[:-1]
 P = (sizes + 4095) // 4096
-BK = 64 if M >= 400000 else 32                                   # BK_TARGET of the launch (gridencoder.hip)
+BK = 64 if M >= 400000 else 32                                   # bk_target of the launch (gridbackward.hip)
 SUB = np.where(P >= BK, 1, (BK + P - 1) // np.maximum(P, 1))
 first = np.concatenate([[0], np.cumsum(P * SUB)])
 nacc = 512

@@ -61,7 +61,7 @@ def main():
         # the position-only half (COUNT pass + scans) that the pipelined train step runs on its side stream BESIDE the main stream's
         # MFMA kernels: the plan's counters / offsets as bytes
         plan = G.grid_backward_plan(x, offs, B, 3, C, L, float(np.log2(pls)), 16, 0, False, 0, True, offsets_host=offsets_host)
-        w0 = ((2 + 32 * 64) * 4 + 255) // 256 * 256 // 4          # plan_layout (gridencoder.hip): items per partition, then their queue offsets
+        w0 = ((2 + 32 * 64) * 4 + 255) // 256 * 256 // 4          # plan_layout (gridbackward.hip): items per partition, then their queue offsets
         return plan.view(torch.int32)[w0:w0 + 2 * L * 512].clone()
 
     x32 = x[:30000].contiguous()
