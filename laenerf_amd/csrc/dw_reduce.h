@@ -1,5 +1,5 @@
 // Weight-gradient slab reduction and deferred loss value of the fused NeRF head backward: the device bodies, shared by
-// k_dw_reduce / k_dw_reduce2 (ffmlp.hip) and by the tail tasks of the hash-grid accumulate pass (gridbackward.hip k_bwd_acc),
+// k_dw_reduce (ffmlp.hip) / k_dw_reduce2 (mlpbackward.hip) and by the tail tasks of the hash-grid accumulate pass (gridbackward.hip k_bwd_acc),
 // which takes the reduction along instead of a launch of its own.  Both users run them with 1024 threads per workgroup and
 // execute the same statements in the same order: the fp16 weight gradients and the loss value have the same bits either way.
 #pragma once

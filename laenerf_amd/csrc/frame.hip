@@ -34,11 +34,11 @@ namespace {
 //     positions and deltas are recomputed from the recorded times with the reference's arithmetic, no probing.
 // The lookahead also advances its own copy of rays_t with the compositing kernel's arithmetic (t += deltas[1] per
 // sample), so every iteration starts from bit-identical times to the host loop's.
-using lae::FrameCtrl;                          // lae_common.h (shared with the head kernel, ffmlp.hip)
+using lae::FrameCtrl;                          // lae_common.h (shared with the head kernel, nerfhead.hip)
 using lae::RayAcc;
 struct FrameMirror { volatile uint64_t tag; volatile uint32_t n_alive, done, total_rows, iters, hung; };   // pinned host memory; hung: low 32 bits of the frame number in which a k_frame_wait gave up (0: never)
 constexpr int FRAME_BLOCK = 256;
-constexpr uint32_t FRAME_SEG_MAX = 4096;       // survivor segments = waves of the head + compositing kernel (k_frame_head, ffmlp.hip)
+constexpr uint32_t FRAME_SEG_MAX = 4096;       // survivor segments = waves of the head + compositing kernel (k_frame_head, nerfhead.hip)
 constexpr uint32_t FRAME_SEG_SLACK = 200;      // a segment's stride exceeds bound_alive / segments by < 66 + 63 + 64 (see the stride below)
 constexpr uint32_t FRAME_LA = 8;               // recorded samples per ray (>= max_n_step)
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <initializer_list>
 #include "../../include/laenerf.h"
 
 #define LAE_WAVE 64
@@ -42,7 +44,7 @@ static_assert(sizeof(RayAcc) == 32, "RayAcc layout");
 // One sample of composite_rays / composite_rays_distill (the body of the reference's serial loop) on a ray's running state:
 // -> true when the ray stops here (T below the threshold ends the ray AFTER the sample is taken).  The caller fetches the
 // sample and has looked at delta0 first: a zero delta ends the samples a ray holds, nothing is fetched for it.  Shared by
-// k_composite_infer (raymarching.hip: samples from the global arrays) and k_frame_head (ffmlp.hip: samples from the wave's
+// k_composite_infer (raymarching.hip: samples from the global arrays) and k_frame_head (nerfhead.hip: samples from the wave's
 // LDS scratch); compiled with -ffp-contract=off, the statement order is the reference's.
 template <bool EDIT>
 __device__ __forceinline__ bool composite_infer_sample(RayAcc& a, float sigma, float delta0, float delta1, float cr, float cg,
@@ -80,7 +82,7 @@ uint32_t frame_head_max_blocks();
 }  // namespace lae
 namespace lae_dw { struct DwTailJob; }                       // dw_reduce.h
 namespace lae {
-// lae_nerf_head_backward (ffmlp.hip) for the fused field backward (lae_nerf_field_backward, gridbackward.hip): with `tail` the
+// lae_nerf_head_backward (mlpbackward.hip) for the fused field backward (lae_nerf_field_backward, gridbackward.hip): with `tail` the
 // reduction of the weight-gradient slabs and the deferred loss value are returned as a job (n_tasks == 0: nothing left to do)
 // for the grid backward's accumulate pass instead of being launched
 int nerf_head_backward(const float* grad_sigmas, const float* grad_rgbs, const void* enc, const float* dirs, const void* h,
@@ -89,6 +91,28 @@ int nerf_head_backward(const float* grad_sigmas, const float* grad_rgbs, const v
                        int accumulate_weight_grads, int enc_level_major, int32_t* nonfinite_flag, const float* loss_partials,
                        uint32_t loss_n_part, uint32_t loss_n_elem, const float* loss_scale, float* loss_out, void* stream,
                        lae_dw::DwTailJob* tail);
+// Calls between the MLP translation units.  ffmlp.hip -> mlpbackward.hip: the fused recompute backward of the FFMLP operator
+// (hidden 64, ReLU; owns the choice among the <in_dim 32 / 48 / 64, n_hidden 1 / 2> instantiations, LAE_EINVAL for any other
+// shape; fp16 pointers) and the kernel variant lae_ffmlp_set_mode selects (0 cooperative, 2 wave-private).  mlpbackward.hip ->
+// ffmlp.hip: the launch of k_dw_reduce on the slabs a backward kernel wrote.
+int ffmlp_backward_fused(uint32_t in_dim, uint32_t n_hidden, const void* grad, const void* x, const void* W, uint32_t B,
+                         void* grad_in, void* gw, int accumulate, int32_t* nf_flag, hipStream_t s);
+void set_mlp_bwd_variant(int variant);
+void dw_reduce_launch(const float* slabs, uint32_t n_slices, uint32_t nW, void* gw, int accumulate, int32_t* nf_flag, hipStream_t s);
+
+// hipFuncAttributeMaxDynamicSharedMemorySize = bytes for `kernel`, on the first call with this flag (one flag per kernel)
+static inline int allow_dynamic_lds(bool& done, const void* kernel, size_t bytes) {
+    if (!done && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return LAE_ELAUNCH;
+    done = true;
+    return LAE_OK;
+}
+// integer environment knob: dflt when unset or not one of `accepted`.  Callers read each knob once.
+static inline int env_int(const char* name, int dflt, std::initializer_list<int> accepted) {
+    const char* e = getenv(name);
+    const int v = e ? atoi(e) : dflt;
+    for (const int a : accepted) if (v == a) return v;
+    return dflt;
+}
 
 // every launch is followed by this: the reference never checked its launches
 // (SURVEY 8b "Errors"); we do, and surface the error through the return code.

@@ -1,4 +1,4 @@
-"""exact-arithmetic cases for the MFMA MLP kernels (csrc/ffmlp.hip) and the fused NeRF head.
+"""exact-arithmetic cases for the MFMA MLP kernels (csrc/ffmlp.hip, mlpbackward.hip) and the fused NeRF head (nerfhead.hip).
 
 Every case is built so that every quantity a kernel produces is exactly representable in the format it is stored in and every
 possible fp32 partial sum is exact.  Summation order then does not matter (K = 16 or K = 32 MFMA, one or two tiles per wave,
@@ -29,13 +29,13 @@ HEAD_SPARSE_FROM = 4112          # dense inputs at 4112 rows take |dW| past 2048
 
 
 def fused_shape(IN, H, NL):
-    """the shapes lae_ffmlp_backward serves with the recompute kernels (ffmlp.hip lae_ffmlp_backward_ex)"""
+    """the shapes lae_ffmlp_backward serves with the recompute kernels (ffmlp.hip lae_ffmlp_backward_ex -> mlpbackward.hip)"""
     return H == 64 and NL in (2, 3) and IN in (32, 48, 64)
 
 
 def wrap_sizes(IN, H, NL, cus=MI355X_CUS):
     """one batch size per kernel family at which the grid-stride loop wraps (more row groups than waves), + 48 rows = an odd
-    number of tiles behind the wrap.  From the launch code of ffmlp.hip:
+    number of tiles behind the wrap.  From the launch code of ffmlp.hip and mlpbackward.hip:
       k_mlp_fwd / k_mlp_bwd (launch_fwd, backward_w): cus * 4 blocks x 4 waves x 16 * NT rows, NT = 2 up to width 64, else 1;
       k_mlp_fwd64 (launch_fwd64): cus * 2 blocks x 4 waves x 16 rows;  k_mlp_bwd_wave (launch_bwd_fused): cus blocks x 4 waves x
       32 rows;  k_mlp_bwd_coop: cus * 2 blocks x 8 waves x 16 rows -- the largest of the three wraps all of them."""

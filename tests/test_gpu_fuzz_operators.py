@@ -335,7 +335,7 @@ def test_fuzz_ffmlp_forward_backward(c):
     # within that difference of zero (|z| ~ 1e-5: about one row in a thousand has one) is masked on one side and not on the other; that
     # row's input gradient then differs by the unit's whole contribution.  The deep run of this test (LAE_FUZZ_SCALE=20) found two such
     # draws (IN 64 / H 64 / 2 layers / 608 rows / seed 50; IN 48 / H 64 / 3 layers / 96 rows / seed 2515: ONE mask of 77 824 /
-    # 18 432 each, tools/ffmlp_case_debug2.py).  In such a draw the oracle's backward is fed the KERNEL's forward buffer (the buffer-filling
+    # 18 432 each).  In such a draw the oracle's backward is fed the KERNEL's forward buffer (the buffer-filling
     # mode 1 forward) -- what the reference's own backward reads too (ffmlp.py:35, 56); the recompute backward reproduced those masks.
     fbk = torch.empty(NL, B, H, device=DEV, dtype=torch.half); out1 = torch.empty_like(out)
     try:

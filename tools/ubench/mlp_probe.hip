@@ -1,8 +1,12 @@
-// probe (round 3): where does the fused NeRF head forward spend its time?  Compiles csrc/ffmlp.hip with in-kernel stamps
-// (100 MHz wall clock + shader clock per wave: start, every 64-row group, end) and prints the distribution.
+// probe (round 3): where do the fused NeRF head forward and its backward spend their time?  Compiles csrc/nerfhead.hip and
+// csrc/mlpbackward.hip (with csrc/ffmlp.hip, which owns the slab-reduction launch the backward's host code calls) into this one
+// translation unit with in-kernel stamps (100 MHz wall clock + shader clock per wave: start, every 64-row group, end; one stamp
+// array, mlp_frags.h) and prints the distribution.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1 -DLAE_MLP_STAMPS \
 //         -I include tools/ubench/mlp_probe.hip laenerf_amd/csrc/lae_common.cpp -o tools/ubench/bin/mlp_probe
 #include "../../laenerf_amd/csrc/ffmlp.hip"
+#include "../../laenerf_amd/csrc/nerfhead.hip"
+#include "../../laenerf_amd/csrc/mlpbackward.hip"
 extern "C" int lae_loss_finish(const float*, uint32_t, uint32_t, const float*, float*, void*) { return 0; }   // lives in raymarching.hip; not used here
 #include <stdio.h>
 #include <vector>
