@@ -75,7 +75,7 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors -- a binding that needs them also checks that the library exports them).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors, lae_undistort_map, lae_distort_map, lae_remap -- a binding that needs them also checks that the library exports them).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
 #define LAE_ABI_TAG "abi27"
@@ -1164,6 +1164,59 @@ LAE_API int lae_tsdf_fuse(const float* packed, const float* poses, uint32_t V, f
                           void* stream);
 LAE_API int lae_tsdf_vertex_colors(const float* rgb, const uint16_t* counts, uint32_t nx, uint32_t ny, uint32_t nz, const float* verts,
                                    uint32_t V, float* colors, uint32_t* n_grey, void* stream);
+
+/* ---- undistortion at the door: resample lens-distorted captures into one pinhole camera, and back (csrc/undistort.hip;
+ * DESIGN.md section 4g; undistort.py restates the three kernels in numpy).  The reference's scripts/colmap2nerf.py writes
+ * k1, k2, p1, p2 / is_fisheye into transforms.json; its loader ignores them ----
+ * Pixel (i, j) has normalised coordinates x = (i + 0.5 - cx) / fx, y = (j + 0.5 - cy) / fy (lae_get_rays' convention).
+ * A camera is LAE_CAM_FLOATS fp32 values in HOST memory: model, fx, fy, cx, cy, k1, k2, k3, k4, p1, p2, 0.
+ *   LAE_CAM_OPENCV (COLMAP SIMPLE_RADIAL / RADIAL / OPENCV):  r2 = x x + y y, rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ *     xd = x rad + 2 p1 x y + p2 (r2 + 2 x x), yd = y rad + p1 (r2 + 2 y y) + 2 p2 x y     (k4 unused)
+ *     by hand: x = 0.5, y = -0.25, k1 = 0.1, k2 = -0.05, k3 = 0, p1 = 0.01, p2 = -0.02 -> xd = 0.49443359375, yd = -0.247216796875
+ *   LAE_CAM_FISHEYE (OpenCV fisheye, Instant-NGP's is_fisheye): r = sqrt(r2), theta = atan(r), t2 = theta theta,
+ *     theta_d = theta (1 + t2 (k1 + t2 (k2 + t2 (k3 + t2 k4)))), (xd, yd) = (theta_d / r) (x, y), the factor 1 at r = 0   (p1, p2 unused)
+ * lae_undistort_map: n_cam source cameras, one target pinhole (fx, fy, cx, cy, H, W) -> map fp32 [n_cam, H, W, 2] on the device:
+ *   per target pixel the source position (xd fx_s + cx_s - 0.5, yd fy_s + cy_s - 0.5) in pixel-index units (the forward model).
+ * lae_distort_map: the inverse direction, per pixel of each source camera [n_cam, Hs, Ws, 2] its position in the target camera
+ *   (x fx + cx - 0.5, y fy + cy - 0.5): a Newton iteration from the distorted point, 2-D for LAE_CAM_OPENCV (analytic Jacobian),
+ *   1-D in theta for LAE_CAM_FISHEYE, `iters` steps (0: LAE_UNDISTORT_NEWTON_ITERS; at most 64).  converged: optional uint8
+ *   [n_cam, Hs, Ws], 1 where the forward model's residual at the result is at most LAE_UNDISTORT_TOL_PX source pixels on both
+ *   axes (fisheye: on theta_d times max(fx, fy), and 0 <= theta < pi/2); elsewhere 0 and the map holds NaN.
+ *   LAE_UNDISTORT_NEWTON_ITERS = 8: in float64, 3 steps leave less than 1e-12 px on a 3840 x 2160 camera with fx = 3000,
+ *   k1 = 0.16, k2 = -0.23; a strong barrel (k1 = -0.3, k2 = 0.09) on a wide lens (fx = W / 2, where the start is far from the
+ *   root) has 3e-9 px left after 5 and 1e-12 after 6 (tests/test_undistort_cpu.py).  Newton doubles the digits per step, so 8
+ *   leaves two steps in hand, and the map is computed once per scene: the count costs nothing that matters.
+ *   NULL cams / map: LAE_ENULL; H or W outside [1, 32768], a focal length <= 0, a model other than the two, a value that is
+ *   not finite, map not 8-byte aligned, iters > 64: LAE_EINVAL; both before any launch.  n_cam == 0: LAE_OK.
+ * lae_remap: dst[n, Ht, Wt, C] = src[n, Hs, Ws, C] sampled at map[cam, Ht, Wt, 2]; C in {1, 3, 4}; dtype LAE_IMG_U8 / _F16 / _F32
+ *   (output as input); cam = cam_index[image] (device int32 [n]) or 0 when cam_index is NULL (one map shared by all images); an
+ *   index outside [0, n_cam) makes the image's output invalid.  valid: optional uint8 [n, Ht, Wt].
+ *   LAE_REMAP_BILINEAR: valid iff 0 <= sx <= Ws - 1 and 0 <= sy <= Hs - 1.  x0 = floor(sx), ax = sx - x0 (exact), x1 = min(x0 + 1,
+ *     Ws - 1), likewise y; w00 = (1 - ax)(1 - ay), w01 = ax (1 - ay), w10 = (1 - ax) ay, w11 = ax ay;
+ *     v = ((w00 p00 + w01 p01) + w10 p10) + w11 p11 in fp32 (p01 is the pixel at (x1, y0)).  C == 4: A = the same sum of the
+ *     alphas, P = the same sum of colour x alpha, colour = P / A (0 where A == 0), alpha = A.  uint8 results are floor(v + 0.5),
+ *     fp16 results round to nearest.
+ *   LAE_REMAP_NEAREST (masks, depth and weight planes): the pixel at (floor(sx + 0.5), floor(sy + 0.5)), the sums in fp32; valid
+ *     iff that pixel exists.
+ *   An invalid output is all zeros with valid = 0.  NaN, infinities and magnitudes beyond the int range are invalid (the
+ *   comparison comes before any conversion).  One owner per output element, no atomics, no allocation: two calls give the same
+ *   bytes and the call can be captured.  NULL src / map / dst: LAE_ENULL; another dtype, C or mode, a side outside [1, 32768],
+ *   n_cam == 0, src / dst not aligned to a pixel's widest access (uint8 RGBA 4, fp16 RGBA 8, fp32 RGBA 16 bytes, else the
+ *   element), map not 8-byte aligned: LAE_EINVAL; both before any launch.  n == 0: LAE_OK. */
+#define LAE_CAM_FLOATS 12
+#define LAE_CAM_OPENCV 0
+#define LAE_CAM_FISHEYE 1
+#define LAE_UNDISTORT_NEWTON_ITERS 8
+#define LAE_UNDISTORT_TOL_PX 0.015625f
+#define LAE_REMAP_BILINEAR 0
+#define LAE_REMAP_NEAREST 1
+LAE_API int lae_undistort_map(const float* cams, uint32_t n_cam, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+                              float* map, void* stream);
+LAE_API int lae_distort_map(const float* cams, uint32_t n_cam, uint32_t Hs, uint32_t Ws, float fx, float fy, float cx, float cy,
+                            uint32_t iters, float* map, uint8_t* converged, void* stream);
+LAE_API int lae_remap(const void* src, int dtype, uint32_t n, uint32_t Hs, uint32_t Ws, uint32_t C, const float* map,
+                      const int32_t* cam_index, uint32_t n_cam, uint32_t Ht, uint32_t Wt, int mode, void* dst, uint8_t* valid,
+                      void* stream);
 
 /* ---- occupancy-grid maintenance (nerf/renderer.py:482-649, Python in the reference) ----
  * positions: point j -> xyz = (2 c / (H-1) - 1) * (bound_c - bound_c/H) + (noise * 2 - 1) * bound_c/H and its Morton index

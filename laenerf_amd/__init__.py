@@ -1,11 +1,17 @@
 """laenerf_amd: the package's modules are imported by name (laenerf_amd.trainer, laenerf_amd.mesh, ...); the TSDF mesh export's
-operators are also reachable from here, resolved on first use so that `import laenerf_amd` stays free of torch."""
+and the undistortion's operators are also reachable from here, resolved on first use so that `import laenerf_amd` stays free of
+torch."""
 _TSDF = ("tsdf_fuse", "tsdf_vertex_colors", "render_packed_views", "tsdf_numpy", "tsdf_vertex_colors_numpy")
-__all__ = list(_TSDF)
+_UNDISTORT = ("CameraModel", "Undistorter", "undistort_map", "distort_map", "remap", "target_intrinsics", "undistort_numpy",
+              "undistort_map_numpy", "distort_map_numpy", "remap_numpy")
+__all__ = list(_TSDF + _UNDISTORT)
 
 
 def __getattr__(name):
     if name in _TSDF:
         from . import tsdf
         return getattr(tsdf, name)
+    if name in _UNDISTORT:
+        import importlib
+        return getattr(importlib.import_module(".undistort", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

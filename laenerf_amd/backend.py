@@ -1294,6 +1294,40 @@ class _RefStage:
 
 ref_stage_backend = _RefStage
 
+
+class _Undistort:
+    """undistortion at the door (include/laenerf.h lae_undistort_map / lae_distort_map / lae_remap; csrc/undistort.hip).  cams: a
+    contiguous float32 numpy array [n_cam, LAE_CAM_FLOATS] on the HOST; every tensor on the device, contiguous, allocated by the
+    caller (laenerf_amd/undistort.py checks the shapes)."""
+    BILINEAR, NEAREST = 0, 1
+    DTYPES = {torch.uint8: 0, _F16: 1, torch.float32: 2}               # LAE_IMG_U8 / _F16 / _F32
+
+    @staticmethod
+    def undistort_map(cams, target, H, W, out):
+        need_cuda(out); need_contig(out)
+        _need_f32(out)
+        check(_lib.load().lae_undistort_map(cams.ctypes.data, len(cams), *(float(v) for v in target), int(H), int(W), ptr(out), stream()),
+              "undistort_map")
+
+    @staticmethod
+    def distort_map(cams, Hs, Ws, target, iters, out, converged):
+        need_cuda(out, converged); need_contig(out, converged)
+        _need_f32(out)
+        check(_lib.load().lae_distort_map(cams.ctypes.data, len(cams), int(Hs), int(Ws), *(float(v) for v in target), int(iters), ptr(out),
+                                          ptr(converged), stream()), "distort_map")
+
+    @staticmethod
+    def remap(src, map, cam_index, mode, out, valid):
+        ts = (src, map, cam_index, out, valid)
+        need_cuda(*ts); need_contig(*ts)
+        n, Hs, Ws, C = (int(v) for v in src.shape)
+        n_cam, Ht, Wt = (int(v) for v in map.shape[:3])
+        check(_lib.load().lae_remap(ptr(src), _Undistort.DTYPES[src.dtype], n, Hs, Ws, C, ptr(map), ptr(cam_index), n_cam, Ht, Wt, int(mode),
+                                    ptr(out), ptr(valid), stream()), "remap")
+
+
+undistort_backend = _Undistort
+
 for _cls in (_RayMarching, _GridEncoder, _SHEncoder, _FFMLP):
     for _k, _v in list(vars(_cls).items()):
         if isinstance(_v, staticmethod) and not _k.startswith("_") and _k not in ("fused_backward_available", "ffmlp_set_mode", "set_backward_mode",

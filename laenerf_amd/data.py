@@ -226,7 +226,9 @@ class ResidentImages:
     of the pixel's colour residual under Trainer(pixel_weights=True) -- a mask (0 = the pixel's colour cannot matter), a confidence
     map, the Ref-NPR distillation's target weights.  second_target (optional, or set_second_target): a second colour target
     [n, H, W, 3 or 4], fp16 or fp32, for Trainer(second_weight=...); with 4 channels it is blended over the batch's background like
-    the images.  sample() reads neither: the compositing kernel gathers both by the batch's `inds`."""
+    the images.  sample() reads neither: the compositing kernel gathers both by the batch's `inds`.
+    undistorter: None, or the undistort.Undistorter that from_transforms(undistort=True) resampled the captures with."""
+    undistorter = None
 
     def __init__(self, images, poses, intrinsics, bound=1.0, min_near=0.2, mode="image", bg=None, color_space="srgb", seed=0,
                  device=None, error_map=False, depths=None, pixel_weights=None, second_target=None):
@@ -438,12 +440,24 @@ class ResidentImages:
         return cls(images, poses, intrinsics, **kw)
 
     @classmethod
-    def from_transforms(cls, path, scale=0.33, offset=(0, 0, 0), downscale=1, dtype="uint8", split=None, **kw):
+    def from_transforms(cls, path, scale=0.33, offset=(0, 0, 0), downscale=1, dtype="uint8", split=None, undistort=False, balance=0.0,
+                        **kw):
         """a blender-style scene: `path` is a transforms.json (or a directory holding transforms[_split].json).  Poses go
         through nerf_matrix_to_ngp; focal lengths from fl_x / fl_y or camera_angle_x / _y, cx / cy default to W/2, H/2
         (provider.py:277-290); images are decoded with PIL and resized with a box filter when `downscale` > 1 (the
         reference's cv2 INTER_AREA).  dtype 'uint8' keeps the 8-bit values (4x less memory), 'float16' / 'float32' store
-        value / 255."""
+        value / 255.
+        Lens distortion (the k1, k2, k3, k4, p1, p2, is_fisheye / camera_model keys scripts/colmap2nerf.py writes, globally or per
+        frame): undistort=False ignores it, as the reference's loader does, and warns once when a coefficient is not zero.
+        undistort=True resamples the captures on the device into one pinhole camera (laenerf_amd/undistort.py): global keys and
+        per-frame overrides of fl_x, fl_y, cx, cy and the coefficients are read, `downscale` is applied first (it scales fx, fy,
+        cx, cy; the coefficients are scale-free), frames of different sizes are refused, .intrinsics is the target camera
+        (undistort.target_intrinsics(cams, H, W, balance)) and .undistorter the Undistorter (its .redistort takes rendered frames
+        back to the photographs' geometry).  balance = 0 crops to the pixels every capture covers; balance > 0 keeps more of the
+        captures and leaves invalid pixels (all zeros): .pixel_weights is then set to the valid plane (times the remapped
+        `pixel_weights=` where given) -- train with Trainer(pixel_weights=True), or an invalid RGBA pixel is trained as empty
+        space.  Planes passed in (`depths=`, `pixel_weights=`: nearest; `second_target=`: bilinear) are given in the captures'
+        geometry and are remapped the same way."""
         from PIL import Image
         if os.path.isdir(path):
             path = os.path.join(path, f"transforms_{split}.json" if split else "transforms.json")
@@ -453,7 +467,7 @@ class ResidentImages:
         H = W = None
         if "h" in transform and "w" in transform:
             H, W = int(transform["h"]) // downscale, int(transform["w"]) // downscale
-        poses, images = [], []
+        poses, images, used, sizes = [], [], [], set()
         for fr in transform["frames"]:
             f_path = os.path.join(root, fr["file_path"])
             if "." not in os.path.basename(f_path):
@@ -463,6 +477,8 @@ class ResidentImages:
             poses.append(nerf_matrix_to_ngp(np.array(fr["transform_matrix"], dtype=np.float32), scale=scale, offset=offset))
             im = Image.open(f_path)
             im = im.convert("RGBA" if im.mode in ("RGBA", "LA", "PA") or "transparency" in im.info else "RGB")
+            used.append(fr)
+            sizes.add((im.height, im.width))
             if H is None:
                 H, W = im.height // downscale, im.width // downscale
             if (im.height, im.width) != (H, W):
@@ -488,7 +504,51 @@ class ResidentImages:
             raise RuntimeError("ResidentImages.from_transforms: no focal length in the transforms file")
         cx = transform["cx"] / downscale if "cx" in transform else W / 2
         cy = transform["cy"] / downscale if "cy" in transform else H / 2
-        return cls(images, np.stack(poses), (fl_x, fl_y, cx, cy), **kw)
+        if not undistort:
+            if any(d.get(k, 0) != 0 for d in [transform] + used for k in ("k1", "k2", "k3", "k4", "p1", "p2")):
+                import warnings
+                warnings.warn("ResidentImages.from_transforms: the transforms file has non-zero lens distortion coefficients, which "
+                              "are being ignored; pass undistort=True to resample the captures into a pinhole camera", stacklevel=2)
+            return cls(images, np.stack(poses), (fl_x, fl_y, cx, cy), **kw)
+        return cls._undistorted(images, np.stack(poses), transform, used, sizes, H, W, downscale, balance, kw)
+
+    @classmethod
+    def _undistorted(cls, images, poses, transform, frames, sizes, H, W, downscale, balance, kw):
+        """from_transforms(undistort=True): the captures and the planes of `kw` resampled on the device into one pinhole camera"""
+        from .undistort import CameraModel, Undistorter, target_intrinsics
+        if len(sizes) != 1:
+            raise ValueError(f"ResidentImages.from_transforms(undistort=True): frames of different sizes {sorted(sizes)} (a camera's "
+                             "intrinsics belong to one size)")
+        h0, w0 = next(iter(sizes))
+        cams, index, seen = [], [], {}
+        for fr in frames:
+            cam = CameraModel.from_transforms(transform, fr, H=h0, W=w0, downscale=downscale)
+            key = cam.record().tobytes()
+            if key not in seen:
+                seen[key] = len(cams)
+                cams.append(cam)
+            index.append(seen[key])
+        target = target_intrinsics(cams, H, W, balance)
+        device = kw.get("device")
+        device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        und = Undistorter(cams, index, target, H, W, device=device)
+        planes = {}
+        for name, mode in (("depths", "nearest"), ("pixel_weights", "nearest"), ("second_target", "bilinear")):
+            plane = kw.pop(name, None)
+            if plane is not None:
+                plane = plane if torch.is_tensor(plane) else torch.from_numpy(np.ascontiguousarray(plane))
+                if not plane.dtype.is_floating_point:
+                    raise ValueError(f"ResidentImages: {name} must be a floating-point plane")
+                if plane.dtype not in (torch.float16, torch.float32):
+                    plane = plane.to(torch.float32)
+                planes[name] = und.images(plane) if name == "second_target" else und.plane(plane, mode)
+        valid = und.valid
+        if not bool(valid.all()):                                                 # one host read, at load time
+            w = planes.get("pixel_weights")
+            planes["pixel_weights"] = valid.to(torch.float32) if w is None else w * valid.to(w.dtype)
+        data = cls(und.images(torch.from_numpy(images)), poses, target, **planes, **kw)
+        data.undistorter = und
+        return data
 
     def _buffers(self, n):
         out = self._out.get(n)

@@ -343,11 +343,13 @@ def _mask_plane(im):
     return im.convert("L")
 
 
-def load_masks(transforms_path, split=None, H=None, W=None, device=None):
+def load_masks(transforms_path, split=None, H=None, W=None, device=None, undistorter=None):
     """the `<image>_mask.png` beside each frame of a blender-style scene (provider.py:216-223) -> a list with one uint8 [H, W]
     tensor per frame (None where the frame has no mask), in the frame order of ResidentImages.from_transforms (frames whose
     image is missing are skipped there and here).  A mask of another size is resized to H x W (default: its image's size) with
-    PIL's bilinear filter (the reference: cv2.resize, also bilinear; the two can differ at the mask's edge)."""
+    PIL's bilinear filter (the reference: cv2.resize, also bilinear; the two can differ at the mask's edge).
+    undistorter (the .undistorter of ResidentImages.from_transforms(undistort=True)): every mask is resampled into the pinhole
+    camera with lae_remap's nearest mode, on the undistorter's device; H, W default to the captures' size there."""
     from PIL import Image
     path = transforms_path
     if os.path.isdir(path):
@@ -366,7 +368,9 @@ def load_masks(transforms_path, split=None, H=None, W=None, device=None):
         if not os.path.exists(m_path):
             out.append(None)
             continue
-        if H is None or W is None:
+        if undistorter is not None and (H is None or W is None):
+            h, w = undistorter.Hs, undistorter.Ws
+        elif H is None or W is None:
             with Image.open(f_path) as im:
                 h, w = im.height, im.width
         else:
@@ -377,6 +381,14 @@ def load_masks(transforms_path, split=None, H=None, W=None, device=None):
                 m = m.resize((w, h), Image.BILINEAR)
             t = torch.from_numpy(np.asarray(m, dtype=np.uint8).copy())
         out.append(t.to(device) if device is not None else t)
+    if undistorter is not None:
+        from .undistort import remap
+        idx = undistorter.cam_index
+        for k, t in enumerate(out):
+            if t is not None:
+                ci = None if idx is None else idx[k:k + 1].contiguous()
+                m = remap(t.to(undistorter.device).reshape(1, *t.shape, 1).contiguous(), undistorter.maps, ci, "nearest")
+                out[k] = m.reshape(undistorter.H, undistorter.W)
     return out
 
 

@@ -10,6 +10,7 @@ refresh every 16 steps, lr 1e-2 decaying by 0.1 over `iters`) and is evaluated o
                                 [--mask-outliers P] [--pose-noise DEG,DIST] [--pose-lr LR]
                                 [--exposure-noise STOPS] [--exposure-lr LR]
                                 [--patch-size P] [--lpips-weight W] [--lpips-weights ALEXNET.pth,ALEX.pth] [--ssim-weight W]
+                                [--lens K1,K2]
 
 prints one JSON line: all-in ms/step (refreshes and graph captures included), the same without the first 64 steps, its
 ratio to the README's train-step headline, captures / cache misses / eager warm groups, scaler-skipped steps, PSNR.
@@ -46,6 +47,11 @@ the peak-to-mean ratio of the per-step sample count, the LPIPS term's first and 
 --ssim-weight W (with --patch-size P): the D-SSIM term 1 - SSIM of the patches with weight W (Trainer(ssim_weight=W)); "patch" then also
 carries its first and last 16-step mean.  With --lpips-weight 0 and no --lpips-weights the trainer gets lpips=None: D-SSIM alone, and
 P >= 11 is enough.
+--lens K1,K2 (write `--lens=-0.3,0.09` where K1 is negative): the training views (never the held-out ones) are also captured through an OpenCV radial lens with those coefficients
+(undistort.Undistorter.distort_images of the teacher's pinhole views; what that lens sees beyond the teacher's frame is transparent),
+and two more identically seeded students train: one on the captures with the distortion ignored (the loader's undistort=False), one on
+the captures undistorted on the device (undistort=True's path: target_intrinsics at balance 0, Undistorter.images).  The line then
+carries "lens": the held-out PSNR of the three students on the true pinhole held-out views -- a measurement, not an assertion.
 --save PATH: the first student's checkpoint is written after the run (Trainer.save_checkpoint; a `.pth` path or a directory);
 --resume PATH: the first student loads it before training and then trains --steps further steps (the same --steps as the saved run
 keeps the learning-rate horizon, which the load checks).  The line then carries "checkpoint": the file size in bytes and the save /
@@ -222,6 +228,7 @@ def main():
     ap.add_argument("--lpips-weights", default=None, metavar="ALEXNET.pth,ALEX.pth", help="torchvision alexnet + lpips v0.1 alex weights")
     ap.add_argument("--ssim-weight", type=float, default=None, metavar="W",
                     help="Trainer(ssim_weight=W), with --patch-size: the D-SSIM term; with --lpips-weight 0 and no --lpips-weights, lpips=None")
+    ap.add_argument("--lens", default=None, metavar="K1,K2", help="also train on the views captured through this radial lens: ignored / undistorted")
     ap.add_argument("--save", default=None, metavar="PATH", help="write the first student's checkpoint after the run")
     ap.add_argument("--resume", default=None, metavar="PATH", help="load a checkpoint into the first student before training")
     args = ap.parse_args()
@@ -334,6 +341,26 @@ def main():
                  "final_loss": float(td.losses()[-16:].mean()), "heldout_psnr_white": round(d_psnr, 3), "steps_skipped": td.steps_skipped,
                  **({"first_distort_loss": float(td.distort_losses()[:16].mean()),
                      "final_distort_loss": float(td.distort_losses()[-16:].mean())} if args.distort is not None else {})}
+    lens = None
+    if args.lens:
+        from laenerf_amd.undistort import CameraModel, Undistorter, target_intrinsics, undistort_map_numpy
+        k1, k2 = (float(v) for v in args.lens.split(","))
+        H = W = args.res
+        cam = CameraModel(*intr, k1=k1, k2=k2)
+        captured, cvalid = Undistorter(cam, None, intr, H, W, device=dev).distort_images(torch.from_numpy(images[held:]), return_valid=True)
+        target = target_intrinsics(cam, H, W, 0.0)
+        und = Undistorter(cam, None, target, H, W, device=dev)
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        fixed = und.images(captured)
+        torch.cuda.synchronize()
+        remap_ms = (time.perf_counter() - t0) * 1e3                     # the maps' first use included
+        shift = np.abs(undistort_map_numpy(cam, intr, H, W) - undistort_map_numpy(CameraModel(*intr), intr, H, W)).max()
+        lens = {"k1": k1, "k2": k2, "largest_displacement_px": round(float(shift), 2), "capture_valid_frac": round(float(cvalid.float().mean()), 4),
+                "target_intrinsics": [round(v, 3) for v in target], "undistort_ms": round(remap_ms, 3), "heldout_psnr_white_true_pinhole": round(p, 3)}
+        for name, ims, k in (("ignored", captured, intr), ("undistorted", fixed, target)):
+            tl = make_trainer(dev, ims, poses[held:], k, iters=args.steps, n_rays=args.rays, graph=not args.no_graph, capacity=args.capacity)
+            tl.train(args.steps)
+            lens[f"heldout_psnr_white_{name}"] = round(tl.evaluate(range(held), data=test, bg_color=1.0), 3)
     print(json.dumps({
         "ms_per_step_all_in": round(all_in, 4), "ms_per_step_after_64": round(steady, 4), "steps": args.steps, "rays": args.rays,
         "ratio_to_headline": round(all_in / HEADLINE_MS, 3), "ratio_after_64_to_headline": round(steady / HEADLINE_MS, 3),
@@ -356,7 +383,7 @@ def main():
         **({"mask_outliers": args.mask_outliers, "masked_pixels_frac": round(float((mask == 0).mean()), 4)} if mask is not None else {}),
         **({"pose": pose} if pose is not None else {}), **({"exposure": exposure} if exposure is not None else {}),
         **({"depth": depth} if depth is not None else {}), **({"checkpoint": ckpt} if ckpt else {}),
-        **({"patch": patch} if patch is not None else {}),
+        **({"patch": patch} if patch is not None else {}), **({"lens": lens} if lens is not None else {}),
         "scene": f"{args.views - held} training + {held} held-out {args.res}x{args.res} RGBA uint8 views of a teacher network"}), flush=True)
 
 
