@@ -75,7 +75,7 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors, lae_undistort_map, lae_distort_map, lae_remap -- a binding that needs them also checks that the library exports them).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors, lae_undistort_map, lae_distort_map, lae_remap, lae_atlas_layout, lae_atlas_texels, lae_atlas_fuse_views, lae_atlas_pack -- a binding that needs them also checks that the library exports them).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
 #define LAE_ABI_TAG "abi27"
@@ -1164,6 +1164,44 @@ LAE_API int lae_tsdf_fuse(const float* packed, const float* poses, uint32_t V, f
                           void* stream);
 LAE_API int lae_tsdf_vertex_colors(const float* rgb, const uint16_t* counts, uint32_t nx, uint32_t ny, uint32_t nz, const float* verts,
                                    uint32_t V, float* colors, uint32_t* n_grey, void* stream);
+
+/* ---- textured mesh export: a per-triangle texture atlas baked on the device (csrc/atlas.hip, where the layout and the rules
+ * are written down in full; atlas.py restates the kernels in numpy).  The reference has no counterpart ----
+ * The layout: triangles two to a square cell of cell x cell texels (cell >= 4), cells = ceil(T / 2), cpr = ceil(sqrt(cells)) cells
+ *   per row, the image S x S with S = cpr * cell <= 16384; triangle t in cell t / 2, half t & 1; texels are numbered cell-major,
+ *   id = c * cell^2 + j * cell + i.  lae_atlas_layout (host only) returns cells, cpr and S; LAE_EINVAL where T == 0, cell < 4 or
+ *   S > 16384.
+ * lae_atlas_texels: verts fp32 [V,3], tris int32 [T,3], optional vertex normals fp32 [V,3] -> per texel (cells * cell^2 of them)
+ *   pos [.,3] (the affine extension of the half's UV -> triangle map: b1 = a / (cell - 3), b2 = b / (cell - 3),
+ *   pos = (v0 + b1 (v1 - v0)) + b2 (v2 - v0)), nrm [.,3] the triangle's unit right-hand face normal (0 for a zero-area triangle or
+ *   one with a vertex index outside [0, V): its texels are flagged by it and come out grey), dirs [.,3] = minus the normalised
+ *   interpolated vertex normal (minus the face normal where that vanishes or no normals are given, (0, 0, 1) where both do),
+ *   owner [.] int32 = t, or -1 for the unused half of an odd T's last cell.
+ * lae_atlas_fuse_views: V packed views [V,H,W] and frames uint8 [V,H,W,3] fused into the texels.  Per (texel, view), in ascending
+ *   view order, with lae_tsdf_fuse's projection statement for statement: d = p - o, q = R^T d; q.z <= 0 or (u, v) outside
+ *   [0, W) x [0, H): rejected; s = t_surf - |d| at pixel (floor u, floor v), a NaN t_surf: rejected; the view counts iff
+ *   |s| <= trunc and -(nrm . d) / |d| > min_cos: the pixel's bytes go into three uint32 sums and n += 1.
+ *   rgb    fp32 [n_texels, 3] = float(sum) / float(n) / 255; 0.5 where n == 0; 0 for unowned texels
+ *   counts optional uint16 [n_texels] = n
+ *   n_grey optional device uint32: the owned texels with n == 0 (zeroed by the call; integer adds)
+ *   Poses go through LDS LAE_TSDF_POSE_CHUNK views at a time; per (wave of 64 texels, view) a conservative cull (the bounding
+ *   sphere of the wave's texels against the camera's half-space and the four frame planes, and every triangle of the wave
+ *   back-facing beyond min_cos with the sphere's margin) skips views that contribute nothing; survivors are compacted by ballot,
+ *   so the sums keep their order.  LAE_ATLAS_CULL=0 in the environment (read per call) turns it off, the bytes are the same.  A
+ *   thread owns its texel: no atomics but the grey count, no host read, no allocation, and two calls give the same bytes.
+ * lae_atlas_pack: cell-major fp32 colours -> the image uint8 [S,S,3], row 0 on top, by lae_eval_view's byte rule; unowned texels
+ *   and cells past `cells` are 0.
+ * NULL pointers (normals, counts and n_grey excepted): LAE_ENULL; T == 0, cell < 4, S > 16384, V == 0 (vertices), V == 0 or
+ *   V > 65535 (views), H or W < 1, H * W >= 2^31, n_texels == 0 or > 16384^2, fx or fy <= 0, trunc <= 0 or not finite, min_cos
+ *   outside [0, 1), a NaN among them: LAE_EINVAL; both before any launch. */
+LAE_API int lae_atlas_layout(uint32_t T, uint32_t cell, uint32_t* cells, uint32_t* cpr, uint32_t* S);
+LAE_API int lae_atlas_texels(const float* verts, uint32_t V, const int32_t* tris, uint32_t T, const float* normals, uint32_t cell,
+                             float* pos, float* nrm, float* dirs, int32_t* owner, void* stream);
+LAE_API int lae_atlas_fuse_views(const float* packed, const float* poses, uint32_t V, float fx, float fy, float cx, float cy, uint32_t H,
+                                 uint32_t W, const uint8_t* frames, const float* pos, const float* nrm, const int32_t* owner,
+                                 uint32_t n_texels, float trunc, float min_cos, float* rgb, uint16_t* counts, uint32_t* n_grey,
+                                 void* stream);
+LAE_API int lae_atlas_pack(const float* rgb, const int32_t* owner, uint32_t T, uint32_t cell, uint8_t* image, void* stream);
 
 /* ---- undistortion at the door: resample lens-distorted captures into one pinhole camera, and back (csrc/undistort.hip;
  * DESIGN.md section 4g; undistort.py restates the three kernels in numpy).  The reference's scripts/colmap2nerf.py writes

@@ -158,6 +158,10 @@ SIGNATURES = {
     "lae_mask_lift": [vp, vp, u32, f32, f32, f32, f32, u32, u32, vp, u32, u32, f32, f32, u32, f32, vp, vp, vp],
     "lae_tsdf_fuse": [vp, vp, u32, f32, f32, f32, f32, u32, u32, vp, vp, vp, u32, u32, u32, vp, f32, u32, vp, vp, vp, vp],
     "lae_tsdf_vertex_colors": [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp],
+    "lae_atlas_layout": [u32, u32, vp, vp, vp],
+    "lae_atlas_texels": [vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp],
+    "lae_atlas_fuse_views": [vp, vp, u32, f32, f32, f32, f32, u32, u32, vp, vp, vp, vp, u32, f32, f32, vp, vp, vp, vp],
+    "lae_atlas_pack": [vp, vp, u32, u32, vp, vp],
     "lae_undistort_map": [vp, u32, f32, f32, f32, f32, u32, u32, vp, vp],
     "lae_distort_map": [vp, u32, u32, u32, f32, f32, f32, f32, u32, vp, vp, vp],
     "lae_remap": [vp, i32, u32, u32, u32, u32, vp, vp, u32, u32, u32, i32, vp, vp, vp],

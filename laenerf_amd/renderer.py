@@ -211,8 +211,9 @@ class NeRFRenderer(nn.Module):
         return out
 
     def _mesh_tsdf(self, poses, intrinsics, H, W, resolution, trunc_voxels, frames, depths, opacities, min_opacity, min_views, normals,
-                   colors, keep_largest, min_component, min_component_fraction):
-        """extract_mesh_tsdf plus `index_vertices`, the marching-cubes vertices in index space"""
+                   colors, keep_largest, min_component, min_component_fraction, packed=None):
+        """extract_mesh_tsdf plus `index_vertices`, the marching-cubes vertices in index space.  packed: the views' surface
+        distance planes where the caller has rendered them already (extract_mesh_textured)"""
         from . import mesh, tsdf
         resolution = int(resolution)
         if not float(trunc_voxels) > 0.0:
@@ -224,7 +225,9 @@ class NeRFRenderer(nn.Module):
         axes = mesh.lattice(bmin, bmax, resolution)
         trunc = float(trunc_voxels) * max(float(a[1] - a[0]) for a in axes)
         own = None
-        if colors and frames is None:
+        if packed is not None:
+            pass
+        elif colors and frames is None:
             packed, own = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity, return_frames=True)
         else:
             packed = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity)
@@ -253,6 +256,94 @@ class NeRFRenderer(nn.Module):
         mesh.write_ply_packed(path, head, vb, fb)
         v = mesh.scale_vertices(m["index_vertices"].cpu().numpy(), self.aabb_infer[:3], self.aabb_infer[3:], int(resolution))
         return v, m["triangles"].cpu().numpy()
+
+    # ------------------------------------------------------------------ textured mesh export (atlas.py)
+    @torch.no_grad()
+    def extract_mesh_textured(self, resolution=256, threshold=10, cell=8, texture_size=None, source="field", geometry="density",
+                              poses=None, intrinsics=None, H=None, W=None, frames=None, trunc_voxels=3.0, min_cos=0.25,
+                              fallback="grey", keep_largest=False, min_component=None, min_component_fraction=None, chunk=128,
+                              color_chunk=1 << 20, depths=None, opacities=None, min_opacity=0.5, min_views=1):
+        """a mesh with a texture instead of vertex colours: every triangle gets its own patch of a per-triangle atlas
+        (atlas.atlas_layout: two triangles to a cell of cell x cell texels; texture_size picks the largest cell that fits), and
+        every texel is baked at its point on the triangle -- colour at the texture's rate, not at the lattice's.
+        geometry "density": extract_mesh_attributes' level set of the density at `threshold`; "tsdf": extract_mesh_tsdf's surface of
+        the renders (needs poses, intrinsics, H, W).  source "field": the radiance self.model(texel, dirs) under the sweep's fp16
+        autocast, color_chunk texels at a time, dirs = minus the interpolated vertex normal; "views": the views of `poses` are
+        rendered (tsdf.render_packed_views; depths / opacities replace the renders) and `frames` ([V, H, W, 3] uint8 or fp32 in the
+        poses' order: recolor_views(...), tr.test(...)[0], ...; None: the model's own renders) are fused into the texels
+        (atlas.atlas_fuse_views: a view counts within trunc_voxels lattice spacings of its surface and above the cosine min_cos;
+        0.25 is the best of the three values DESIGN.md section 4h records); texels no view counts for are grey 0.5 (fallback "grey") or take the field's colour
+        (fallback "field").  -> a dict of device tensors: `vertices` [V,3] fp32 in the box, `triangles` [T,3] int32, `normals`
+        [V,3] fp32, `uv` [T,3,2] float64 per corner (atlas.atlas_uv), `texture` uint8 [S,S,3] (row 0 on top), `n_grey` int32 [1]
+        (texels no view counted for; 0 for source "field"), `texels` (pos, dirs, owner and the fp32 colours rgb, cell-major) and
+        `layout`.  keep_largest / min_component / min_component_fraction: as in extract_mesh."""
+        from . import atlas, mesh, tsdf
+        if source not in ("field", "views") or geometry not in ("density", "tsdf") or fallback not in ("grey", "field"):
+            raise ValueError("extract_mesh_textured: source is 'field' or 'views', geometry 'density' or 'tsdf', fallback 'grey' or 'field'")
+        need_views = source == "views" or geometry == "tsdf"
+        if need_views and (poses is None or intrinsics is None or H is None or W is None):
+            raise ValueError("extract_mesh_textured: source='views' and geometry='tsdf' need poses, intrinsics, H and W")
+        resolution = int(resolution)
+        dev = self.aabb_infer.device
+        rule = dict(keep_largest=keep_largest, min_component=min_component, min_component_fraction=min_component_fraction)
+        packed = own = None
+        if need_views:
+            poses = poses.reshape(-1, 4, 4).to(dev).float().contiguous()
+            if source == "views" and frames is None:
+                packed, own = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity, return_frames=True)
+            else:
+                packed = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity)
+        if geometry == "tsdf":
+            m = self._mesh_tsdf(poses, intrinsics, H, W, resolution, trunc_voxels, None, depths, opacities, min_opacity, min_views, True,
+                                False, packed=packed, **rule)
+        else:
+            m = self._mesh_attributes(resolution, threshold, chunk, True, False, color_chunk, **rule)
+        verts, tris, normals = m["vertices"], m["triangles"], m["normals"]
+        T = tris.shape[0]
+        lay = atlas.atlas_layout(T, cell, texture_size)
+        out = {"vertices": verts, "triangles": tris, "normals": normals, "layout": lay,
+               "uv": torch.from_numpy(atlas.atlas_uv(lay)).to(dev), "n_grey": torch.zeros(1, dtype=torch.int32, device=dev)}
+        if T == 0:
+            out["texture"] = torch.zeros(lay.S, lay.S, 3, dtype=torch.uint8, device=dev)
+            out["texels"] = None
+            return out
+        tx = atlas.atlas_texels(verts, tris, normals, lay.cell)
+
+        def field(pos, dirs):
+            rgb = torch.empty_like(pos)
+            for i in range(0, pos.shape[0], color_chunk):
+                with torch.autocast("cuda", dtype=torch.float16):
+                    rgb[i:i + color_chunk] = self.model(pos[i:i + color_chunk], dirs[i:i + color_chunk])[1].float()
+            return rgb
+
+        if source == "field":
+            rgb = field(tx["pos"], tx["dirs"])
+        else:
+            aabb = self.aabb_infer.cpu()
+            axes = mesh.lattice(aabb[:3], aabb[3:], resolution)
+            trunc = float(trunc_voxels) * max(float(a[1] - a[0]) for a in axes)
+            if not trunc > 0.0:
+                raise ValueError("extract_mesh_textured: trunc_voxels must be positive")
+            f = atlas.atlas_fuse_views(packed, poses, intrinsics, H, W, own if frames is None else frames, tx["pos"], tx["nrm"], tx["owner"],
+                                       trunc, min_cos, counts=fallback == "field")
+            rgb, out["n_grey"] = f["rgb"], f["n_grey"]
+            if fallback == "field":
+                unseen = ((f["counts"].to(torch.int32) == 0) & (tx["owner"] >= 0)).nonzero().reshape(-1)
+                if unseen.numel():
+                    rgb[unseen] = field(tx["pos"][unseen].contiguous(), tx["dirs"][unseen].contiguous())
+        out["texture"] = atlas.atlas_pack(rgb, tx["owner"], lay)
+        out["texels"] = {"pos": tx["pos"], "dirs": tx["dirs"], "owner": tx["owner"], "rgb": rgb}
+        return out
+
+    def save_mesh_textured(self, path, **kwargs):
+        """extract_mesh_textured(**kwargs) written as `name.obj` + `name.mtl` + `name.png` (atlas.write_obj: per-corner texture
+        coordinates, vertex normals, the texture through PIL).  An empty result writes valid files with no elements.
+        -> (vertices [V,3] float64, triangles [T,3] int32) on the host, like save_mesh"""
+        from . import atlas
+        m = self.extract_mesh_textured(**kwargs)
+        v, t = m["vertices"].double().cpu().numpy(), m["triangles"].cpu().numpy()
+        atlas.write_obj(path, v, t, m["uv"].cpu().numpy(), m["texture"].cpu().numpy(), normals=m["normals"].cpu().numpy())
+        return v, t
 
     # ------------------------------------------------------------------ occupancy-grid maintenance
     @torch.no_grad()

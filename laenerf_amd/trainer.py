@@ -909,6 +909,17 @@ class Trainer:
         with self._eval_weights():
             return self.r.save_mesh_tsdf(path, data.poses, data.intrinsics, data.H, data.W, frames=frames, **kwargs)
 
+    def save_mesh_textured(self, path, data=None, frames=None, **kwargs):
+        """the mesh as `name.obj` + `name.mtl` + `name.png` with a per-triangle texture atlas (NeRFRenderer.save_mesh_textured;
+        DESIGN.md section 4h), with the EMA weights.  The cameras of `data` (a ResidentImages; default the training data) serve
+        source="views" and geometry="tsdf"; frames: [n, H, W, 3] uint8 or fp32 on the device in the data's camera order
+        (recolor_views(...), tr.test(...)[0], ...) are baked into the texture with source="views" -- a palette edit or a
+        stylization leaves with its detail; None bakes the model's own renders.  kwargs: resolution, cell, texture_size, source,
+        geometry, min_cos, fallback, keep_largest, ... of NeRFRenderer.extract_mesh_textured."""
+        data = self.data if data is None else data
+        with self._eval_weights():
+            return self.r.save_mesh_textured(path, poses=data.poses, intrinsics=data.intrinsics, H=data.H, W=data.W, frames=frames, **kwargs)
+
     @torch.no_grad()
     def evaluate(self, views, data=None, bg_color=1.0):
         """mean PSNR over `views` (image indices of `data`, default the training set) rendered with render_eval over a plain
