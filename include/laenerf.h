@@ -75,10 +75,10 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: lae_composite_rays_train_step_depth, lae_composite_rays_train_backward_blend_depth; abi17: lae_composite_rays_train_forward_blend_dist, lae_composite_rays_train_backward_blend_dist, lae_composite_rays_train_step_dist; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: lae_composite_rays_train_step_crit, lae_colour_loss_forward, lae_error_map_update_crit; abi23: lae_composite_rays_train_step_weighted, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors, lae_undistort_map, lae_distort_map, lae_remap, lae_atlas_layout, lae_atlas_texels, lae_atlas_fuse_views, lae_atlas_pack -- a binding that needs them also checks that the library exports them).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: the depth term of the compositing step and of its backward; abi17: the distortion term of the compositing forward, backward and step; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: the colour criteria and the opacity entropy of the compositing step, lae_colour_loss_forward, lae_error_map_update_crit; abi23: pixel weights and a second target in the compositing step, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors, lae_undistort_map, lae_distort_map, lae_remap, lae_atlas_layout, lae_atlas_texels, lae_atlas_fuse_views, lae_atlas_pack -- a binding that needs them also checks that the library exports them; abi28: one lae_composite_rays_train_step whose loss terms are structs (lae_depth_term, lae_dist_term, lae_crit_term, lae_weight_term) in place of five cumulative entries, grad_depth / depth / grad_dist / dist on lae_composite_rays_train_backward_blend_ex and dist on lae_composite_rays_train_forward_blend in place of their _depth / _dist entries).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
-#define LAE_ABI_TAG "abi27"
+#define LAE_ABI_TAG "abi28"
 LAE_API const char* lae_version(void);
 /* last HIP error string recorded by a failed launch in this thread (or "") */
 LAE_API const char* lae_last_error(void);
@@ -204,7 +204,7 @@ LAE_API int lae_error_map_update(float* error_map, uint32_t n_img, uint32_t H, u
                                  const float* pred, const float* gt, uint32_t N, void* stream);
 /* lae_error_map_update for a step trained with another colour criterion: the reference's rule is error = loss.detach(), the trained
  * criterion's per-ray mean over RGB (nerf/utils.py:592, 624), so err = ((v0 + v1) + v2) / 3 with the element loss v of loss_kind
- * (LAE_LOSS_*, at lae_composite_rays_train_step_crit; e = pred - gt rounded, every operation rounded).  LAE_LOSS_MSE gives
+ * (LAE_LOSS_*, at lae_crit_term; e = pred - gt rounded, every operation rounded).  LAE_LOSS_MSE gives
  * lae_error_map_update's bits.  LAE_EINVAL additionally: loss_kind out of range, a Huber delta that is not finite and > 0. */
 LAE_API int lae_error_map_update_crit(float* error_map, uint32_t n_img, uint32_t H, uint32_t W, const int64_t* inds, const int32_t* cells,
                                       const float* pred, const float* gt, uint32_t N, int loss_kind, float loss_param, void* stream);
@@ -268,29 +268,24 @@ LAE_API int lae_composite_rays_train_backward(const float* grad_weights_sum, con
                                       const float* image, uint32_t M, uint32_t N, float T_thresh,
                                       float* grad_sigmas, float* grad_rgbs, void* stream);
 
+/* The distortion regularizer of mip-NeRF 360 on the ray's weights, in the O(n) form of the reference's loss.py:29-76
+ * (eff_distloss(w, m, interval) with m = t_k and interval = deltas[k,0]; its CUDA-ray path never calls it), inside the compositing
+ * kernels.  Over the samples the forward uses (k = 0 .. the early-stop sample, included), w_k = alpha_k T_k, t_k = the running sum
+ * of deltas[.,1] including sample k, lengths in the march's own units (NOT divided by far - near):
+ *   l_ray = (1/3) sum_k delta0_k w_k^2 + 2 sum_k w_k (t_k W_<k - WT_<k)        W_<k = sum_{j<k} w_j,  WT_<k = sum_{j<k} w_j t_j
+ *         = (1/3) sum_k delta0_k w_k^2 + sum_{i,j} w_i w_j |t_i - t_j|
+ * It is an output of the forward below, an input of the backward and a term of the fused step (lae_dist_term). */
+
 /* MI355X-native: composite + the post-ops run_cuda applies to its result (nerf/renderer.py:321, 325) in one kernel:
  *   image_out = image + (1 - weights_sum) * bg,  depth_out = clamp(depth - nears, min=0) / (fars - nears).
  * bg = bg_rays [N,3] when non-NULL, else the constant (bg_r, bg_g, bg_b).  weights_sum / depth / image receive the
- * un-blended values (saved for the backward). */
+ * un-blended values (saved for the backward).
+ * dist [N], or NULL for none: additionally the output dist[ray] = l_ray (0 for a ray without samples); every other output has the
+ * bits of the call without it. */
 LAE_API int lae_composite_rays_train_forward_blend(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
                                            uint32_t M, uint32_t N, float T_thresh, const float* nears, const float* fars,
                                            const float* bg_rays, float bg_r, float bg_g, float bg_b, float* weights_sum,
-                                           float* depth, float* image, float* depth_out, float* image_out, void* stream);
-/* MI355X-native: lae_composite_rays_train_forward_blend + lae_mse_loss_forward (target [N,3], scale as there) +
- * lae_composite_rays_train_backward_blend (grad_weights_sum = NULL, upstream gradient 1) as ONE launch -- d loss / d pixel of a
- * ray needs that ray's pixel only -- plus a one-block launch that adds the workgroups' squared-error sums in a fixed order into
- * loss_out[0] = MSE * scale, loss_out[1] = MSE.  Same arithmetic as the three calls.  grad_image [N,3], grad_sigmas [M],
- * grad_rgbs [M,3] are outputs (every row written); partials: cdiv(N, 4) floats of scratch. */
-LAE_API int lae_composite_rays_train_step(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
-                                  uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays, float bg_r,
-                                  float bg_g, float bg_b, const uint32_t* rows_end, const float* target, const float* scale,
-                                  float* weights_sum, float* depth, float* image, float* depth_out, float* image_out,
-                                  float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out, float* partials,
-                                  int defer_loss, void* stream);
-/* defer_loss != 0 (round 3): the one-block launch is left out and loss_out[0..1] is set to NaN; the sum is done later by
- * lae_loss_finish(partials, cdiv(N, 4), 3 * N, scale, loss_out) or taken along by lae_nerf_head_backward (its loss_*
- * arguments) -- the value feeds nothing on the device, so it need not sit on the step's critical path. */
-LAE_API int lae_loss_finish(const float* partials, uint32_t n_part, uint32_t n_elem, const float* scale, float* loss_out, void* stream);
+                                           float* depth, float* image, float* depth_out, float* image_out, float* dist, void* stream);
 
 /* Backward of the above w.r.t. (weights_sum, image_out): grad_ws_eff = grad_ws - sum_c grad_image_c * bg_c.  Writes EVERY
  * row of grad_sigmas / grad_rgbs in [0, M) (zeros after the early stop and in [rows_end, M)), so they need no
@@ -302,97 +297,87 @@ LAE_API int lae_composite_rays_train_backward_blend(const float* grad_weights_su
                                             const uint32_t* rows_end, float* grad_sigmas, float* grad_rgbs, void* stream);
 /* same, for a criterion fused in front of it: grad_weights_sum may be NULL (zero) and every incoming gradient is
  * multiplied by the device scalar *grad_scale when grad_scale != NULL (the upstream d(loss), so no elementwise
- * multiplication / zero-fill kernels are needed between the loss and this call). */
+ * multiplication / zero-fill kernels are needed between the loss and this call).
+ *
+ * grad_depth [N], or NULL for none: the gradient of the RAW depth output D = sum_k w_k t_k (`depth` of the forward, not depth_out;
+ * t_k = running sum of deltas[.,1]), which the reference's backward drops (raymarching.py:273-275):
+ *   grad_sigmas_k += delta0_k * grad_depth * (T_post_k * t_k - (D - D_k)),  D_k = the running sum including sample k,
+ * inside the same bracket as the colour terms; grad_rgbs is unchanged.  Zeros are allowed: such a ray takes the path of the call
+ * without grad_depth and gives its bits.
+ *
+ * grad_dist [N], or NULL for none: the gradient of l_ray, with dist [N] the forward's l_ray.  With W = weights_sum, D = depth and
+ * W_k, WT_k the running sums including sample k:
+ *   q_k = d l_ray / d w_k = (2/3) delta0_k w_k + 2 (t_k (W_<k - (W - W_k)) + ((D - WT_k) - WT_<k))
+ *   grad_sigmas_k += delta0_k * grad_dist * (T_post_k * q_k - (Q - Q_k)),   Q_k = sum_{j<=k} q_j w_j,   Q = 2 * dist
+ * (l_ray is homogeneous of degree 2 in w) inside the same bracket as the colour terms; grad_rgbs is unchanged.  A ray whose
+ * grad_dist is zero has the bits of the call without grad_dist (with or without grad_depth).
+ *
+ * depth [N], the forward's raw depth, is read with either (it is the D of both rules) and not looked at without them.  grad_scale
+ * multiplies grad_depth and grad_dist as well.  LAE_ENULL: grad_depth or grad_dist without depth, grad_dist without dist. */
 LAE_API int lae_composite_rays_train_backward_blend_ex(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
                                                const float* rgbs, const float* deltas, const int32_t* rays,
                                                const float* weights_sum, const float* image, uint32_t M, uint32_t N,
                                                float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
                                                const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
-                                               float* grad_rgbs, void* stream);
+                                               float* grad_rgbs, const float* grad_depth, const float* depth, const float* grad_dist,
+                                               const float* dist, void* stream);
 
-/* lae_composite_rays_train_backward_blend_ex that also takes the gradient of the RAW depth output D = sum_k w_k t_k (`depth` of the
- * forward, not depth_out; t_k = running sum of deltas[.,1]), which the reference's backward drops (raymarching.py:273-275):
- *   grad_sigmas_k += delta0_k * grad_depth * (T_post_k * t_k - (D - D_k)),  D_k = the running sum including sample k,
- * inside the same bracket as the colour terms; grad_rgbs is unchanged.  grad_depth [N] (zeros allowed: such a ray takes the path
- * of lae_composite_rays_train_backward_blend_ex and gives its bits), depth [N] the forward's raw depth.  grad_scale multiplies
- * grad_depth as well. */
-LAE_API int lae_composite_rays_train_backward_blend_depth(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
-                                                  const float* rgbs, const float* deltas, const int32_t* rays,
-                                                  const float* weights_sum, const float* image, uint32_t M, uint32_t N,
-                                                  float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
-                                                  const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
-                                                  float* grad_rgbs, const float* grad_depth, const float* depth, void* stream);
+/* ---- The fused training step, lae_composite_rays_train_step (prototype below its terms).
+ * MI355X-native: lae_composite_rays_train_forward_blend + lae_mse_loss_forward (target [N,3], scale as there) +
+ * lae_composite_rays_train_backward_blend_ex (grad_weights_sum = NULL, upstream gradient 1) as ONE launch -- d loss / d pixel of a
+ * ray needs that ray's pixel only -- plus a one-block launch that adds the workgroups' squared-error sums in a fixed order into
+ * loss_out[0] = MSE * scale, loss_out[1] = MSE.  Same arithmetic as the three calls.  grad_image [N,3], grad_sigmas [M],
+ * grad_rgbs [M,3] are outputs (every row written); partials: cdiv(N, 4) floats of scratch.
+ * defer_loss != 0 (round 3): the one-block launch is left out and loss_out[0..1] is set to NaN; the sum is done later by
+ * lae_loss_finish(partials, cdiv(N, 4), 3 * N, scale, loss_out) or taken along by lae_nerf_head_backward (its loss_*
+ * arguments) -- the value feeds nothing on the device, so it need not sit on the step's critical path.
+ *
+ * Four further loss terms join the same launch, each one struct; a NULL struct pointer means the term is absent, and the call
+ * without any is the one above:
+ *   loss = mean(v) [+ depth.lambda * mean(res^2)] [+ dist.lambda * L_dist] [+ crit.opac_lambda * L_op] [+ weight.lambda * mean(v2 / 3)]
+ * Every term adds its part, times 3 and its weight, to partials[b], so every finisher of the base call (n_elem = 3 N) yields the
+ * total loss unchanged, and leaves the partial sums of the term alone in a buffer of its own. */
 
-/* lae_composite_rays_train_step with a second criterion on the ray's raw depth D, the reference's depth supervision
- * (nerf/utils.py:585-589, 634-635: loss += 1e-3 * mean(((depth - (gt_depth - nears)) * (gt_depth > 0))^2)), in the same launch:
- *   z = depth_src[depth_inds ? depth_inds[ray] : ray]   depth_src fp32 or fp16 (depth_dtype LAE_IMG_F32 / LAE_IMG_F16), depth_inds
+/* Depth term: a second criterion on the ray's raw depth D, the reference's depth supervision
+ * (nerf/utils.py:585-589, 634-635: loss += 1e-3 * mean(((depth - (gt_depth - nears)) * (gt_depth > 0))^2)):
+ *   z = src[inds ? inds[ray] : ray]                     src fp32 or fp16 (dtype LAE_IMG_F32 / LAE_IMG_F16), inds
  *                                                       int64 or NULL (the `inds` of lae_sample_train_batch into a [n_img, H, W] plane)
  *   res = (z > 0 && nears[ray] < fars[ray]) * (D - (z - nears[ray]))   zero in the plane = no supervision; neither is a ray that
  *                                                       misses the bounding box (lae_near_far_from_aabb gives it near == far ==
  *                                                       FLT_MAX, the reference's rule would make the loss infinite there)
  *   grad_depth[ray] = g_D = ((res * (2 * lambda / N)) * *scale), carried through the backward as
- *   lae_composite_rays_train_backward_blend_depth does; depth_value_only != 0 computes the value and forces g_D = 0 (the
+ *   lae_composite_rays_train_backward_blend_ex carries its grad_depth; value_only != 0 computes the value and forces g_D = 0 (the
  *   reference's effective behaviour: its backward ignores the gradient of depth).  A ray with g_D == 0 gets the sample gradients
- *   of lae_composite_rays_train_step bit for bit; a ray without samples adds its residual to the value and has no gradient.
- * partials[b] = sum over the workgroup's rays of (squared colour error + 3 * lambda * res^2), so every finisher of
- * lae_composite_rays_train_step (n_elem = 3 N) yields loss_out = MSE + lambda * mean(res^2) unchanged; depth_partials
- * [cdiv(N, 4)] receive sum(res^2): lae_loss_finish(depth_partials, cdiv(N, 4), N, NULL, out) gives mean(res^2) alone.
- * lambda: finite, >= 0 (LAE_EINVAL otherwise). */
-LAE_API int lae_composite_rays_train_step_depth(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
-                                        uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
-                                        float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
-                                        const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
-                                        float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
-                                        float* partials, int defer_loss, const void* depth_src, int depth_dtype,
-                                        const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
-                                        float* depth_partials, void* stream);
+ *   of the step without the term bit for bit; a ray without samples adds its residual to the value and has no gradient.
+ * The step's partials[b] = sum over the workgroup's rays of (squared colour error + 3 * lambda * res^2), so loss_out = MSE + lambda *
+ * mean(res^2); the term's partials [cdiv(N, 4)] receive sum(res^2): lae_loss_finish(partials, cdiv(N, 4), N, NULL, out) gives
+ * mean(res^2) alone.  grad_depth [N].
+ * LAE_EINVAL: lambda not finite and >= 0, a dtype that is not LAE_IMG_F16 / LAE_IMG_F32.  LAE_ENULL: src, grad_depth or partials NULL. */
+typedef struct lae_depth_term {
+    const void* src;
+    int dtype;
+    const int64_t* inds;
+    float lambda;
+    int value_only;
+    float* grad_depth;
+    float* partials;
+} lae_depth_term;
 
-/* The distortion regularizer of mip-NeRF 360 on the ray's weights, in the O(n) form of the reference's loss.py:29-76
- * (eff_distloss(w, m, interval) with m = t_k and interval = deltas[k,0]; its CUDA-ray path never calls it), inside the compositing
- * kernels.  Over the samples the forward uses (k = 0 .. the early-stop sample, included), w_k = alpha_k T_k, t_k = the running sum
- * of deltas[.,1] including sample k, lengths in the march's own units (NOT divided by far - near):
- *   l_ray = (1/3) sum_k delta0_k w_k^2 + 2 sum_k w_k (t_k W_<k - WT_<k)        W_<k = sum_{j<k} w_j,  WT_<k = sum_{j<k} w_j t_j
- *         = (1/3) sum_k delta0_k w_k^2 + sum_{i,j} w_i w_j |t_i - t_j|
- *
- * lae_composite_rays_train_forward_blend plus the output dist [N] = l_ray (0 for a ray without samples); every other output has
- * the bits of lae_composite_rays_train_forward_blend. */
-LAE_API int lae_composite_rays_train_forward_blend_dist(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
-                                                uint32_t M, uint32_t N, float T_thresh, const float* nears, const float* fars,
-                                                const float* bg_rays, float bg_r, float bg_g, float bg_b, float* weights_sum,
-                                                float* depth, float* image, float* depth_out, float* image_out, float* dist,
-                                                void* stream);
-/* lae_composite_rays_train_backward_blend_depth that also takes grad_dist [N], the gradient of l_ray, and dist [N], the forward's
- * l_ray.  With W = weights_sum, D = depth and W_k, WT_k the running sums including sample k:
- *   q_k = d l_ray / d w_k = (2/3) delta0_k w_k + 2 (t_k (W_<k - (W - W_k)) + ((D - WT_k) - WT_<k))
- *   grad_sigmas_k += delta0_k * grad_dist * (T_post_k * q_k - (Q - Q_k)),   Q_k = sum_{j<=k} q_j w_j,   Q = 2 * dist
- * (l_ray is homogeneous of degree 2 in w) inside the same bracket as the colour terms; grad_rgbs is unchanged.  grad_depth may be
- * NULL: no depth gradient.  depth [N], the forward's raw depth, is always read (it is the D of q_k).  A ray whose grad_dist is zero
- * has the bits of lae_composite_rays_train_backward_blend_depth (of _ex without grad_depth).  grad_scale multiplies grad_dist too. */
-LAE_API int lae_composite_rays_train_backward_blend_dist(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
-                                                 const float* rgbs, const float* deltas, const int32_t* rays,
-                                                 const float* weights_sum, const float* image, uint32_t M, uint32_t N,
-                                                 float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
-                                                 const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
-                                                 float* grad_rgbs, const float* grad_depth, const float* depth, const float* grad_dist,
-                                                 const float* dist, void* stream);
-/* lae_composite_rays_train_step_depth with the distortion term in the same launch:
- *   loss = MSE [+ lambda * mean(res^2)] + dist_lambda * L_dist,   L_dist = (1/N) sum over ALL N rays of l_ray
- *   dist[ray] = l_ray (0 without samples),  grad_dist[ray] = g = (dist_lambda / N) * *scale, carried through the backward as
- *   lae_composite_rays_train_backward_blend_dist does; dist_value_only != 0 computes the value and forces g = 0.  With g == 0
- *   (dist_lambda == 0 or dist_value_only) the sample gradients are those of lae_composite_rays_train_step[_depth] bit for bit.
- * depth_src == NULL switches the depth term off: the other depth arguments are then not looked at.
- * partials[b] additionally receive 3 * dist_lambda * sum(l_ray), so every finisher (n_elem = 3 N) yields the total loss unchanged;
- * dist_partials [cdiv(N, 4)] receive sum(l_ray): lae_loss_finish(dist_partials, cdiv(N, 4), N, NULL, out) gives L_dist alone.
- * dist_lambda: finite, >= 0 (LAE_EINVAL otherwise). */
-LAE_API int lae_composite_rays_train_step_dist(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
-                                       uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
-                                       float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
-                                       const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
-                                       float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
-                                       float* partials, int defer_loss, const void* depth_src, int depth_dtype,
-                                       const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
-                                       float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
-                                       float* dist_partials, void* stream);
+/* Distortion term (l_ray: above lae_composite_rays_train_forward_blend):
+ *   loss += lambda * L_dist,   L_dist = (1/N) sum over ALL N rays of l_ray
+ *   dist[ray] = l_ray (0 without samples),  grad_dist[ray] = g = (lambda / N) * *scale, carried through the backward as
+ *   lae_composite_rays_train_backward_blend_ex carries its grad_dist; value_only != 0 computes the value and forces g = 0.  With
+ *   g == 0 (lambda == 0 or value_only) the sample gradients are those of the step without the term bit for bit.
+ * The step's partials[b] additionally receive 3 * lambda * sum(l_ray); the term's partials [cdiv(N, 4)] receive sum(l_ray):
+ * lae_loss_finish(partials, cdiv(N, 4), N, NULL, out) gives L_dist alone.  dist, grad_dist [N].
+ * LAE_EINVAL: lambda not finite and >= 0.  LAE_ENULL: dist, grad_dist or partials NULL. */
+typedef struct lae_dist_term {
+    float lambda;
+    int value_only;
+    float* dist;
+    float* grad_dist;
+    float* partials;
+} lae_dist_term;
 
 /* The colour criteria of the fused step, lae_colour_loss_forward and lae_error_map_update_crit.  Per element, with e = pred - target
  * rounded to fp32 and r = |e|, the element loss v and dv = d v / d pred (sign(0) = 0):
@@ -406,10 +391,9 @@ LAE_API int lae_composite_rays_train_step_dist(const float* sigmas, const float*
 #define LAE_LOSS_L1 1
 #define LAE_LOSS_HUBER 2
 #define LAE_LOSS_MAPE 3
-/* lae_composite_rays_train_step_dist with the colour criterion chosen by loss_kind and an opacity-entropy term on weights_sum
- * (torch-ngp's lambda_entropy) in the same launch:
- *   loss = mean(v) [+ lambda * mean(res^2)] [+ dist_lambda * L_dist] [+ opac_lambda * L_op]
- *   grad_image = ((e * (2 / (3 N))) * *scale) under LAE_LOSS_MSE -- the statements and the bits of lae_composite_rays_train_step --
+/* Criterion term: the colour criterion chosen by kind (param = loss_param above) and, with opac != NULL, an opacity-entropy term on
+ * weights_sum (torch-ngp's lambda_entropy):
+ *   grad_image = ((e * (2 / (3 N))) * *scale) under LAE_LOSS_MSE -- the statements and the bits of the step without the term --
  *                and ((dv * (1 / (3 N))) * *scale) otherwise.
  *   o = min(max(weights_sum, 1e-5f), 1 - 1e-5f),  opac[ray] = h = -(o * log2(o) + (1 - o) * log2(1 - o)),
  *   L_op = (1/N) sum over ALL N rays of h (a ray without samples has weights_sum = 0: it adds h(1e-5) and has no gradient),
@@ -417,60 +401,72 @@ LAE_API int lae_composite_rays_train_step_dist(const float* sigmas, const float*
  *   (torch.clamp's gradient, bounds included); opac_value_only != 0 computes the value and forces grad_ws = 0.  The backward takes
  *   it where lae_composite_rays_train_backward_blend_ex takes grad_weights_sum: the fused call equals the forward plus that call
  *   with (grad_ws, grad_image).  It costs no work per sample: it joins the ray's constant of the bracket.
- * dist == NULL switches the distortion term off (the other dist arguments are then not looked at), opac == NULL the entropy term
- * (likewise), depth_src == NULL the depth term.  With LAE_LOSS_MSE and opac == NULL every output has the bits of
- * lae_composite_rays_train_step_dist (of lae_composite_rays_train_step[_depth] without dist).
- * partials[b] = sum over the workgroup's rays of (v0 + v1 + v2 + 3 * opac_lambda * h + the depth and distortion parts), so every
- * finisher (n_elem = 3 N) yields the total loss unchanged; opac_partials [cdiv(N, 4)] receive sum(h):
- * lae_loss_finish(opac_partials, cdiv(N, 4), N, NULL, out) gives L_op alone.  opac, grad_ws [N].
- * LAE_EINVAL: loss_kind out of range, a Huber delta that is not finite and > 0, opac_lambda not finite and >= 0. */
-LAE_API int lae_composite_rays_train_step_crit(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
-                                       uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
-                                       float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
-                                       const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
-                                       float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
-                                       float* partials, int defer_loss, const void* depth_src, int depth_dtype,
-                                       const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
-                                       float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
-                                       float* dist_partials, int loss_kind, float loss_param, float opac_lambda, int opac_value_only,
-                                       float* opac, float* grad_ws, float* opac_partials, void* stream);
-/* lae_composite_rays_train_step_crit with a per-pixel weight on the colour residual and a second colour target with its own weight
- * in the same launch -- the reference's train_step_npr (nerf/utils.py:523-526: loss = mean((w (pred - gt))^2) + style_weight_d *
- * mean(((1 - w / 2) (gt_style - pred))^2) + the depth term), and mask- / confidence-weighted training in general.
- *   w_src: a weight plane, fp16 or fp32 (w_dtype = LAE_IMG_F16 / LAE_IMG_F32), gathered at pix_inds[ray] (int64, the sampler's
- *     inds = image * H * W + pixel) or at `ray` when pix_inds is NULL -- the rule of depth_inds.  NULL: no weights (w = 1).
- *   t2_src: a second target plane [.., t2_channels] (3 or 4; t2_dtype as w_dtype), gathered the same way.  NULL: no second term, the
- *     other t2 arguments are then not looked at.  With 4 channels it is blended over the ray's own background as the sampler blends
- *     gt, three roundings, no contraction: t_c = s_c * s_a + bg_c * (1 - s_a); with 3, t_c = s_c.
+ * opac == NULL switches the entropy term off: opac_lambda, opac_value_only, grad_ws and opac_partials are then not looked at.  With
+ * LAE_LOSS_MSE and opac == NULL every output has the bits of the step without the term (with or without the depth and distortion
+ * terms); the kernels differ, so the two are not interchangeable for speed.
+ * The step's partials[b] = sum over the workgroup's rays of (v0 + v1 + v2 + 3 * opac_lambda * h + the depth and distortion parts);
+ * opac_partials [cdiv(N, 4)] receive sum(h): lae_loss_finish(opac_partials, cdiv(N, 4), N, NULL, out) gives L_op alone.  opac, grad_ws [N].
+ * LAE_EINVAL: kind out of range, a Huber delta that is not finite and > 0, opac_lambda not finite and >= 0 (with opac != NULL).
+ * LAE_ENULL: opac without grad_ws or opac_partials. */
+typedef struct lae_crit_term {
+    int kind;
+    float param;
+    float opac_lambda;
+    int opac_value_only;
+    float* opac;
+    float* grad_ws;
+    float* opac_partials;
+} lae_crit_term;
+
+/* Weight term: a per-pixel weight on the colour residual and a second colour target with its own weight -- the reference's
+ * train_step_npr (nerf/utils.py:523-526: loss = mean((w (pred - gt))^2) + style_weight_d * mean(((1 - w / 2) (gt_style - pred))^2) +
+ * the depth term), and mask- / confidence-weighted training in general.  LAE_LOSS_MSE only; without a criterion term the criterion
+ * is LAE_LOSS_MSE without the entropy term.
+ *   w_src: a weight plane, fp16 or fp32 (w_dtype = LAE_IMG_F16 / LAE_IMG_F32), gathered at inds[ray] (int64, the sampler's
+ *     inds = image * H * W + pixel) or at `ray` when inds is NULL -- the rule of the depth term's inds.  NULL: no weights (w = 1),
+ *     w_dtype is then not looked at.
+ *   t2_src: a second target plane [.., t2_channels] (3 or 4; t2_dtype as w_dtype), gathered the same way.  NULL: no second term,
+ *     t2_dtype, t2_channels, lambda and partials are then not looked at.  With 4 channels it is blended over the ray's own background
+ *     as the sampler blends gt, three roundings, no contraction: t_c = s_c * s_a + bg_c * (1 - s_a); with 3, t_c = s_c.
  * Per ray, after the forward and the blend (o = image_out[ray], gt = target[ray]), every operation one fp32 rounding:
  *   u = 1 - 0.5 * w,   a_c = w * (o_c - gt_c),   v1 = fmaf(a2, a2, fmaf(a1, a1, a0 * a0)),
  *   b_c = u * (t_c - o_c),   v2 = (b0 * b0 + b1 * b1) + b2 * b2,
- *   loss = (1 / (3 N)) sum over the rays of (v1 + t2_lambda * v2) [+ the depth, distortion and entropy terms of _crit, unchanged]
- *   grad_image_c = (((w * a_c) - t2_lambda * (u * b_c)) * (2 / (3 N))) * *scale     (no second target: ((w * a_c) * (2 / (3 N))) * *scale)
+ *   loss = (1 / (3 N)) sum over the rays of (v1 + lambda * v2) [+ the depth, distortion and entropy terms, unchanged]
+ *   grad_image_c = (((w * a_c) - lambda * (u * b_c)) * (2 / (3 N))) * *scale     (no second target: ((w * a_c) * (2 / (3 N))) * *scale)
  *   With a second target the two parts of grad_image cancel where the pixel lies between its targets (where the training converges):
  *   there the expression is evaluated in double on the fp32 operands (w, o, gt, t, *scale) and rounded to fp32 once, so that
  *   grad_image keeps the relative accuracy of the step without a second target (about 1e-7) instead of an unbounded relative error.
  *   The loss values (v1, v2) stay fp32.
- * The backward is that of _crit on this grad_image: nothing is added per sample.  A weight of 0 makes a_c and the first term's
- * gradient exact zeros: the pixel's colour cannot matter.
- * partials[b] receive v1 + t2_lambda * v2 (+ the other parts), so every finisher (n_elem = 3 N) yields the total loss; t2_partials
- * [cdiv(N, 4)] receive sum(v2): lae_loss_finish(t2_partials, cdiv(N, 4), 3 N, NULL, out) gives mean(v2 / 3), the second term alone.
- * With w_src == NULL and t2_src == NULL the call IS lae_composite_rays_train_step_crit (same kernels, same bits); with a plane of
+ * The backward is that of the step without the term on this grad_image: nothing is added per sample.  A weight of 0 makes a_c and
+ * the first term's gradient exact zeros: the pixel's colour cannot matter.
+ * The step's partials[b] receive v1 + lambda * v2 (+ the other parts); the term's partials [cdiv(N, 4)] receive sum(v2):
+ * lae_loss_finish(partials, cdiv(N, 4), 3 N, NULL, out) gives mean(v2 / 3), the second term alone.
+ * With w_src == NULL and t2_src == NULL the call IS the one with the criterion term alone (same kernels, same bits); with a plane of
  * ones and no second target every output has those bits too (1 * x is exact).
- * LAE_EINVAL: weights or a second target with loss_kind != LAE_LOSS_MSE (the reference has no weighted L1 / Huber / MAPE; out of scope),
- * t2_lambda not finite and >= 0, t2_channels not 3 or 4, a dtype that is not LAE_IMG_F16 / LAE_IMG_F32. */
-LAE_API int lae_composite_rays_train_step_weighted(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
-                                           uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
-                                           float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
-                                           const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
-                                           float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
-                                           float* partials, int defer_loss, const void* depth_src, int depth_dtype,
-                                           const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
-                                           float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
-                                           float* dist_partials, int loss_kind, float loss_param, float opac_lambda, int opac_value_only,
-                                           float* opac, float* grad_ws, float* opac_partials, const void* w_src, int w_dtype,
-                                           const void* t2_src, int t2_dtype, int t2_channels, const int64_t* pix_inds, float t2_lambda,
-                                           float* t2_partials, void* stream);
+ * LAE_EINVAL: weights or a second target with kind != LAE_LOSS_MSE (the reference has no weighted L1 / Huber / MAPE; out of scope),
+ * lambda not finite and >= 0, t2_channels not 3 or 4, a dtype that is not LAE_IMG_F16 / LAE_IMG_F32.  LAE_ENULL: t2_src without partials. */
+typedef struct lae_weight_term {
+    const void* w_src;
+    int w_dtype;
+    const void* t2_src;
+    int t2_dtype;
+    int t2_channels;
+    const int64_t* inds;
+    float lambda;
+    float* partials;
+} lae_weight_term;
+
+/* The step.  The terms' LAE_EINVAL conditions are checked first (weight, criterion, depth, distortion), then N == 0 returns LAE_OK,
+ * then the LAE_ENULL conditions.  The structs are read during the call only. */
+LAE_API int lae_composite_rays_train_step(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                  uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays, float bg_r,
+                                  float bg_g, float bg_b, const uint32_t* rows_end, const float* target, const float* scale,
+                                  float* weights_sum, float* depth, float* image, float* depth_out, float* image_out,
+                                  float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out, float* partials,
+                                  int defer_loss, const lae_depth_term* depth_term, const lae_dist_term* dist_term,
+                                  const lae_crit_term* crit_term, const lae_weight_term* weight_term, void* stream);
+LAE_API int lae_loss_finish(const float* partials, uint32_t n_part, uint32_t n_elem, const float* scale, float* loss_out, void* stream);
+
 
 /* raymarching.cu:929-936 */
 LAE_API int lae_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive,
@@ -1464,7 +1460,7 @@ LAE_API int lae_adam_apply(float* param, float* exp_avg, float* exp_avg_sq, void
  * grad[i] = d loss_out[0] / d pred[i].  scale: device float (FusedAdam state word 0) or NULL (= 1).  fp32, n elements. */
 LAE_API int lae_mse_loss_forward(const float* pred, const float* target, uint32_t n, const float* scale, float* loss_out, float* grad,
                          void* stream);
-/* lae_mse_loss_forward with the colour criterion chosen by loss_kind (LAE_LOSS_*, at lae_composite_rays_train_step_crit): the
+/* lae_mse_loss_forward with the colour criterion chosen by loss_kind (LAE_LOSS_*, at lae_crit_term): the
  * criterion of a step that does not run the fused compositing step.  loss_out[1] = mean(v), loss_out[0] = that * scale,
  * grad[i] = ((dv * (1 / n)) * scale).  LAE_LOSS_MSE runs lae_mse_loss_forward's statements and gives its bits.  LAE_EINVAL: n == 0,
  * loss_kind out of range, a Huber delta (loss_param) that is not finite and > 0. */

@@ -18,6 +18,29 @@ SO_PATH = os.environ.get("LAE_HIP_LIB") or os.path.join(_HERE, "lib", "liblaener
 u32, u64, f32, i32, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p
 i64, f64 = ctypes.c_int64, ctypes.c_double
 
+
+
+# the loss terms of lae_composite_rays_train_step (include/laenerf.h): passed as ctypes.byref(term), or None for an absent term
+class DepthTerm(ctypes.Structure):
+    _fields_ = [("src", vp), ("dtype", i32), ("inds", vp), ("lambda", f32), ("value_only", i32), ("grad_depth", vp), ("partials", vp)]
+
+
+class DistTerm(ctypes.Structure):
+    _fields_ = [("lambda", f32), ("value_only", i32), ("dist", vp), ("grad_dist", vp), ("partials", vp)]
+
+
+class CritTerm(ctypes.Structure):
+    _fields_ = [("kind", i32), ("param", f32), ("opac_lambda", f32), ("opac_value_only", i32), ("opac", vp), ("grad_ws", vp),
+                ("opac_partials", vp)]
+
+
+class WeightTerm(ctypes.Structure):
+    _fields_ = [("w_src", vp), ("w_dtype", i32), ("t2_src", vp), ("t2_dtype", i32), ("t2_channels", i32), ("inds", vp), ("lambda", f32),
+                ("partials", vp)]
+
+
+TERM_STRUCTS = {"lae_depth_term": DepthTerm, "lae_dist_term": DistTerm, "lae_crit_term": CritTerm, "lae_weight_term": WeightTerm}
+
 # name -> argtypes (everything returns int unless listed in _RESTYPES); mirrors include/laenerf.h
 SIGNATURES = {
     "lae_near_far_from_aabb": [vp, vp, vp, u32, f32, vp, vp, vp],
@@ -45,19 +68,12 @@ SIGNATURES = {
     "lae_error_map_update_crit": [vp, u32, u32, u32, vp, vp, vp, vp, u32, i32, f32, vp],
     "lae_composite_rays_train_forward": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, vp],
     "lae_composite_rays_train_backward": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, vp, vp],
-    "lae_composite_rays_train_forward_blend": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp],
-    "lae_composite_rays_train_step": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
-    "lae_composite_rays_train_step_depth": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, vp],
-    "lae_composite_rays_train_backward_blend_depth": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
-    "lae_composite_rays_train_forward_blend_dist": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
-    "lae_composite_rays_train_step_dist": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, f32, i32, vp, vp, vp, vp],
-    "lae_composite_rays_train_step_crit": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, f32, i32, vp, vp, vp, i32, f32, f32, i32, vp, vp, vp, vp],
-    "lae_composite_rays_train_step_weighted": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, f32, i32, vp, vp, vp, i32, f32, f32, i32, vp, vp, vp,
-                                               vp, i32, vp, i32, i32, vp, f32, vp, vp],
-    "lae_composite_rays_train_backward_blend_dist": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "lae_composite_rays_train_forward_blend": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
+    "lae_composite_rays_train_step": [vp, vp, vp, vp, u32, u32, f32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32,
+                                      vp, vp, vp, vp, vp],      # the four term structs (by reference, or None), stream
     "lae_loss_finish": [vp, u32, u32, vp, vp, vp],
     "lae_composite_rays_train_backward_blend": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp],
-    "lae_composite_rays_train_backward_blend_ex": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp],
+    "lae_composite_rays_train_backward_blend_ex": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_march_rays": [u32, u32, vp, vp, vp, vp, f32, f32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_march_rays_distill": [u32, u32, vp, vp, vp, vp, f32, f32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lae_composite_rays": [u32, u32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -218,7 +234,7 @@ _RESTYPES = {
 }
 
 _lib = None
-ABI_TAG = b"abi27"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
+ABI_TAG = b"abi28"            # include/laenerf.h LAE_ABI_TAG: the prototypes in SIGNATURES are written against this tag
 
 
 def _abi_of(path):

@@ -12,6 +12,7 @@ raymarching/raymarching.py:9-12), so nerf/renderer.py and editing/* run unmodifi
 """
 import sys
 import types
+from ctypes import byref
 
 import numpy as np
 import torch
@@ -132,15 +133,16 @@ _DEPTH_DTYPES = {torch.float16: 1, torch.float32: 2}        # include/laenerf.h 
 
 
 def _backward_blend_args(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, bg_rays, bg,
-                         rows_end, grad_sigmas, grad_rgbs, grad_scale, *depth_pair):
-    """checks the tensors of a DENSE backward (depth_pair: grad_depth and depth of the DEPTH flavour) -> the arguments both
-    library entries share"""
-    fs = (grad_weights_sum, grad_image, sigmas, rgbs, deltas, weights_sum, image, bg_rays, grad_sigmas, grad_rgbs, grad_scale) + depth_pair
+                         rows_end, grad_sigmas, grad_rgbs, grad_scale, grad_depth=None, depth=None, grad_dist=None, dist=None):
+    """checks the tensors of a DENSE backward -> the arguments of lae_composite_rays_train_backward_blend_ex (grad_depth, grad_dist:
+    None = the flavour without that gradient)"""
+    fs = (grad_weights_sum, grad_image, sigmas, rgbs, deltas, weights_sum, image, bg_rays, grad_sigmas, grad_rgbs, grad_scale, grad_depth,
+          depth, grad_dist, dist)
     need_cuda(*fs, rays, rows_end); need_contig(*fs, rays, rows_end)
     _need_f32(*fs)
     return (ptr(grad_weights_sum), ptr(grad_image), ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(weights_sum),
             ptr(image), M, N, T_thresh, ptr(bg_rays), bg[0], bg[1], bg[2], ptr(rows_end), ptr(grad_scale), ptr(grad_sigmas),
-            ptr(grad_rgbs))
+            ptr(grad_rgbs), ptr(grad_depth), ptr(depth), ptr(grad_dist), ptr(dist))
 
 
 class _RayMarching:
@@ -260,7 +262,7 @@ class _RayMarching:
         _need_f32(sigmas, rgbs, deltas, nears, fars, bg_rays, weights_sum, depth, image, depth_out, image_out)
         check(_lib.load().lae_composite_rays_train_forward_blend(
             ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1],
-            bg[2], ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out), stream()),
+            bg[2], ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out), None, stream()),
             "composite_rays_train_forward_blend")
 
     @staticmethod
@@ -272,7 +274,7 @@ class _RayMarching:
         _need_f32(sigmas, rgbs, deltas, nears, fars, bg_rays, weights_sum, depth, image, depth_out, image_out, dist)
         if dist.numel() < N:
             raise RuntimeError("composite_rays_train_forward_blend_dist: dist needs a value per ray")
-        check(_lib.load().lae_composite_rays_train_forward_blend_dist(
+        check(_lib.load().lae_composite_rays_train_forward_blend(
             ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1],
             bg[2], ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out), ptr(dist), stream()),
             "composite_rays_train_forward_blend_dist")
@@ -284,18 +286,18 @@ class _RayMarching:
         """MI355X extension: compositing forward (+ blend) + MSE criterion + compositing backward in one launch.
         defer_loss: the loss VALUE (loss_out, NaN until then) is summed later -- by the fused head's backward, which takes it
         along in its reduction launch, or by flush_pending_loss() (laenerf_amd.optim.FusedAdam.backward / step call it).
-        depth_sup: None, or (depth_src, depth_inds, weight, value_only, grad_depth, depth_partials): the depth criterion of
-        lae_composite_rays_train_step_depth in the same launch (depth_src fp16 / fp32, depth_inds int64 or None); the loss value
+        depth_sup: None, or (depth_src, depth_inds, weight, value_only, grad_depth, depth_partials): the depth term
+        (lae_depth_term) in the same launch (depth_src fp16 / fp32, depth_inds int64 or None); the loss value
         then holds MSE + weight * depth MSE whoever finishes it.
-        dist_sup: None, or (weight, value_only, dist, grad_dist, dist_partials): the distortion term of
-        lae_composite_rays_train_step_dist in the same launch, with or without depth_sup; the loss value then also holds
+        dist_sup: None, or (weight, value_only, dist, grad_dist, dist_partials): the distortion term
+        (lae_dist_term) in the same launch, with or without depth_sup; the loss value then also holds
         weight * mean(l_ray).
         crit: None, or (loss_kind, loss_param, opac_sup) with opac_sup None or (weight, value_only, opac, grad_ws, opac_partials): the
-        colour criterion LOSS_KINDS[...] and the opacity-entropy term of lae_composite_rays_train_step_crit in the same launch, with or
+        colour criterion LOSS_KINDS[...] and the opacity-entropy term (lae_crit_term) in the same launch, with or
         without depth_sup and dist_sup; the loss value then holds mean(v) of that criterion plus weight * mean(h).
         weight_sup: None, or (pixel_weights, second_target, pix_inds, second_weight, second_partials): the per-pixel weight plane
-        (fp16 / fp32, or None) and the second colour target (fp16 / fp32 [.., 3 or 4], or None) of
-        lae_composite_rays_train_step_weighted in the same launch, both gathered at pix_inds (int64 [N], or None: one entry per ray),
+        (fp16 / fp32, or None) and the second colour target (fp16 / fp32 [.., 3 or 4], or None;
+        lae_weight_term) in the same launch, both gathered at pix_inds (int64 [N], or None: one entry per ray),
         with or without the other terms; MSE only.  The loss value then holds mean((w e)^2) + second_weight * mean(((1 - w / 2)
         (t - pred))^2) plus the other terms."""
         ts = (sigmas, rgbs, deltas, rays, nears, fars, bg_rays, rows_end, target, scale, weights_sum, depth, image, depth_out,
@@ -308,7 +310,7 @@ class _RayMarching:
         args = (ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), M, N, T_thresh, ptr(nears), ptr(fars), ptr(bg_rays), bg[0], bg[1], bg[2],
                 ptr(rows_end), ptr(target), ptr(scale), ptr(weights_sum), ptr(depth), ptr(image), ptr(depth_out), ptr(image_out),
                 ptr(grad_image), ptr(grad_sigmas), ptr(grad_rgbs), ptr(loss_out), ptr(partials), int(bool(defer_loss)))
-        dargs = (None, 0, None, 0.0, 0, None, None)       # lae_composite_rays_train_step_dist without a depth term
+        dterm = xterm = cterm = wterm = None              # the four terms of the entry, by reference: None = absent
         if depth_sup is not None:
             depth_src, depth_inds, weight, value_only, grad_depth, depth_partials = depth_sup
             ds = (depth_src, depth_inds, grad_depth, depth_partials)
@@ -321,17 +323,15 @@ class _RayMarching:
                 raise RuntimeError("composite_rays_train_step: without depth_inds the depth needs a value per ray")
             if grad_depth.numel() < N or depth_partials.numel() < (N + 3) // 4:
                 raise RuntimeError("composite_rays_train_step: grad_depth needs N, depth_partials cdiv(N, 4) floats")
-            dargs = (ptr(depth_src), _DEPTH_DTYPES[depth_src.dtype], ptr(depth_inds), float(weight), int(bool(value_only)),
-                     ptr(grad_depth), ptr(depth_partials))
-        xargs = (0.0, 0, None, None, None)                # lae_composite_rays_train_step_crit without a distortion term
+            dterm = byref(_lib.DepthTerm(ptr(depth_src), _DEPTH_DTYPES[depth_src.dtype], ptr(depth_inds), float(weight), int(bool(value_only)),
+                                         ptr(grad_depth), ptr(depth_partials)))
         if dist_sup is not None:
             dist_weight, dist_value_only, dist, grad_dist, dist_partials = dist_sup
             xs = (dist, grad_dist, dist_partials)
             need_cuda(*xs); need_contig(*xs); _need_f32(*xs)
             if any(x is None for x in xs) or dist.numel() < N or grad_dist.numel() < N or dist_partials.numel() < (N + 3) // 4:
                 raise RuntimeError("composite_rays_train_step: dist and grad_dist need N, dist_partials cdiv(N, 4) floats")
-            xargs = (float(dist_weight), int(bool(dist_value_only)), ptr(dist), ptr(grad_dist), ptr(dist_partials))
-        wargs = None
+            xterm = byref(_lib.DistTerm(float(dist_weight), int(bool(dist_value_only)), ptr(dist), ptr(grad_dist), ptr(dist_partials)))
         if weight_sup is not None:
             w_plane, t2_plane, pix_inds, t2_weight, t2_partials = weight_sup
             ws_ = (w_plane, t2_plane, pix_inds, t2_partials)
@@ -357,9 +357,7 @@ class _RayMarching:
                 if t2_partials is None or t2_partials.numel() < (N + 3) // 4:
                     raise RuntimeError("composite_rays_train_step: second_partials needs cdiv(N, 4) floats")
                 ta = (ptr(t2_plane), _DEPTH_DTYPES[t2_plane.dtype], int(t2_plane.shape[-1]))
-            wargs = wa + ta + (ptr(pix_inds), float(t2_weight), ptr(t2_partials))
-            if crit is None:
-                crit = (0, 0.0, None)
+            wterm = byref(_lib.WeightTerm(*wa, *ta, ptr(pix_inds), float(t2_weight), ptr(t2_partials)))   # without crit: MSE, no entropy term
         if crit is not None:
             loss_kind, loss_param, opac_sup = crit
             oargs = (0.0, 0, None, None, None)            # ... and without the entropy term
@@ -370,18 +368,8 @@ class _RayMarching:
                 if any(x is None for x in os_) or opac.numel() < N or grad_ws.numel() < N or opac_partials.numel() < (N + 3) // 4:
                     raise RuntimeError("composite_rays_train_step: opac and grad_ws need N, opac_partials cdiv(N, 4) floats")
                 oargs = (float(opac_weight), int(bool(opac_value_only)), ptr(opac), ptr(grad_ws), ptr(opac_partials))
-            if wargs is not None:
-                check(_lib.load().lae_composite_rays_train_step_weighted(*args, *dargs, *xargs, int(loss_kind), float(loss_param), *oargs,
-                                                                         *wargs, stream()), "composite_rays_train_step_weighted")
-            else:
-                check(_lib.load().lae_composite_rays_train_step_crit(*args, *dargs, *xargs, int(loss_kind), float(loss_param), *oargs,
-                                                                     stream()), "composite_rays_train_step_crit")
-        elif dist_sup is not None:
-            check(_lib.load().lae_composite_rays_train_step_dist(*args, *dargs, *xargs, stream()), "composite_rays_train_step_dist")
-        elif depth_sup is not None:
-            check(_lib.load().lae_composite_rays_train_step_depth(*args, *dargs, stream()), "composite_rays_train_step_depth")
-        else:
-            check(_lib.load().lae_composite_rays_train_step(*args, stream()), "composite_rays_train_step")
+            cterm = byref(_lib.CritTerm(int(loss_kind), float(loss_param), *oargs))
+        check(_lib.load().lae_composite_rays_train_step(*args, dterm, xterm, cterm, wterm, stream()), "composite_rays_train_step")
         if defer_loss and N > 0:                      # N == 0: the library returned at once, there is nothing to finish
             capturing = torch.cuda.is_current_stream_capturing()
             key = _loss_key(grad_sigmas)
@@ -416,8 +404,7 @@ class _RayMarching:
                                     bg, rows_end, grad_sigmas, grad_rgbs, grad_scale, grad_depth, depth)
         if grad_depth is None or depth is None or grad_depth.numel() < N or depth.numel() < N:
             raise RuntimeError("composite_rays_train_backward_blend_depth: grad_depth and depth need a value per ray")
-        check(_lib.load().lae_composite_rays_train_backward_blend_depth(*args, ptr(grad_depth), ptr(depth), stream()),
-              "composite_rays_train_backward_blend_depth")
+        check(_lib.load().lae_composite_rays_train_backward_blend_ex(*args, stream()), "composite_rays_train_backward_blend_depth")
 
     @staticmethod
     def composite_rays_train_backward_blend_dist(grad_weights_sum, grad_image, grad_depth, grad_dist, sigmas, rgbs, deltas, rays,
@@ -429,8 +416,7 @@ class _RayMarching:
                                     bg, rows_end, grad_sigmas, grad_rgbs, grad_scale, grad_depth, depth, grad_dist, dist)
         if any(x is None or x.numel() < N for x in (depth, grad_dist, dist)) or (grad_depth is not None and grad_depth.numel() < N):
             raise RuntimeError("composite_rays_train_backward_blend_dist: depth, grad_dist, dist (and grad_depth) need a value per ray")
-        check(_lib.load().lae_composite_rays_train_backward_blend_dist(*args, ptr(grad_depth), ptr(depth), ptr(grad_dist), ptr(dist),
-                                                                       stream()), "composite_rays_train_backward_blend_dist")
+        check(_lib.load().lae_composite_rays_train_backward_blend_ex(*args, stream()), "composite_rays_train_backward_blend_dist")
 
     @staticmethod
     def colour_loss_forward(pred, target, n, loss_kind, loss_param, scale, loss_out, grad):

@@ -12,6 +12,7 @@
 #include <string.h>
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 #include <type_traits>
 #include <hip/hip_fp16.h>
 #include "lae_common.h"
@@ -630,29 +631,31 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_bwd(
 // fixed order (deterministic).
 struct StepLoss { const float* target; const float* scale; float* grad_image; float* partials; float* poison_loss; };
 
+// The four terms below are the C ABI's own structs (include/laenerf.h): the kernel takes what the caller filled in, the layout is
+// written once.
 // DEPTH: a second criterion on the raw depth D of the ray, the reference's depth supervision (nerf/utils.py:585-589, 634-635):
-//   z = depth_src[inds ? inds[index] : index] (fp32 or fp16),  m = z > 0 && nears[index] < fars[index],  res = m * (D - (z - nears[index])),
+//   z = src[inds ? inds[index] : index] (fp32 or fp16),  m = z > 0 && nears[index] < fars[index],  res = m * (D - (z - nears[index])),
 //   loss += lambda * mean(res^2),  g_D = ((res * (2 * lambda / N)) * scale) -> grad_depth[index]
 // and the backward carries g_D as k_composite_train_bwd<true, true> does (the reference's backward drops it; value_only restores that:
 // the value is computed, g_D is forced to zero).  A ray with g_D == 0 runs the statements of the flavour without DEPTH.
 // partials[] receive sum(sq + 3 * lambda * res^2): the finishers, which divide by 3 N, yield MSE + lambda * mean(res^2) as they are;
-// depth_partials[] receive sum(res^2) (lae_loss_finish with n_elem = N gives the depth term alone).
-struct DepthLoss { const void* src; int dtype; const int64_t* inds; float lambda; int value_only; float* grad_depth; float* partials; };
+// DepthLoss::partials receive sum(res^2) (lae_loss_finish with n_elem = N gives the depth term alone).
+using DepthLoss = lae_depth_term;
 
 // DIST: a further criterion, the distortion l_ray of the ray's weights (see DistGrad): loss += lambda * mean over ALL N rays of l_ray (a
 // ray without samples has l = 0), g = ((lambda / N) * scale) -> grad_dist[index] for every ray, carried through the backward as
 // k_composite_train_bwd<true, ., true> does; value_only forces g = 0.  With g == 0 (lambda == 0 or value_only: every ray of the launch)
 // the backward runs the statements of the flavour without DIST.  partials[] additionally receive 3 * lambda * sum(l_ray), partials of
 // the term alone go to DistLoss::partials (lae_loss_finish with n_elem = N gives L_dist).
-struct DistLoss { float lambda; int value_only; float* dist; float* grad_dist; float* partials; };
+using DistLoss = lae_dist_term;
 
 // CRIT: the colour criterion is chosen by `kind` (lae::colour_elem_loss; LAE_LOSS_MSE runs the statements above), and with
 // opac != NULL the opacity entropy of the ray's weights_sum W joins the loss: o = clamp(W, 1e-5, 1 - 1e-5),
-// h = -(o log2 o + (1 - o) log2(1 - o)), loss += lambda * mean over ALL N rays of h, grad_ws[index] = ((lambda / N) * (log2(1 - o)
-// - log2 o)) * scale where W lies in [1e-5, 1 - 1e-5] (torch.clamp's gradient) and 0 outside or with value_only.  The backward takes
+// h = -(o log2 o + (1 - o) log2(1 - o)), loss += opac_lambda * mean over ALL N rays of h, grad_ws[index] = ((opac_lambda / N) *
+// (log2(1 - o) - log2 o)) * scale where W lies in [1e-5, 1 - 1e-5] (torch.clamp's gradient) and 0 outside or with opac_value_only.  The backward takes
 // it where k_composite_train_bwd<true> takes grad_weights_sum -- the ray's constant of the bracket, nothing per sample.  partials[]
-// additionally receive 3 * lambda * sum(h), CritLoss::partials sum(h).  The CRIT = false instantiations are the kernels they were.
-struct CritLoss { int kind; float delta; float lambda; int value_only; float* opac; float* grad_ws; float* partials; };
+// additionally receive 3 * opac_lambda * sum(h), CritLoss::opac_partials sum(h).  The CRIT = false instantiations are the kernels they were.
+using CritLoss = lae_crit_term;
 
 // WGT (with CRIT, LAE_LOSS_MSE only): a per-pixel weight w on the colour residual and a second colour target t with its own weight,
 // the reference's train_step_npr (nerf/utils.py:523-526).  Both are gathered at inds[index] (or index) BEFORE the forward scan -- two
@@ -664,8 +667,19 @@ struct CritLoss { int kind; float delta; float lambda; int value_only; float* op
 // With w == 1 and no second target the statements reduce to those above bit for bit (1 * x is exact).  partials[] receive sq,
 // WeightLoss::partials sum(v2) (lae_loss_finish with n_elem = 3 N gives the second term alone).  The WGT = false instantiations are
 // the kernels they were.
-struct WeightLoss { const void* w_src; int w_dtype; const void* t2_src; int t2_dtype; int t2_channels; const int64_t* inds; float lambda;
-                    float* partials; };
+using WeightLoss = lae_weight_term;
+// a header edit that moves a field fails the build here: the kernels' argument bytes are these layouts
+static_assert(sizeof(DepthLoss) == 48 && offsetof(DepthLoss, src) == 0 && offsetof(DepthLoss, dtype) == 8 && offsetof(DepthLoss, inds) == 16 &&
+              offsetof(DepthLoss, lambda) == 24 && offsetof(DepthLoss, value_only) == 28 && offsetof(DepthLoss, grad_depth) == 32 &&
+              offsetof(DepthLoss, partials) == 40, "lae_depth_term");
+static_assert(sizeof(DistLoss) == 32 && offsetof(DistLoss, lambda) == 0 && offsetof(DistLoss, value_only) == 4 && offsetof(DistLoss, dist) == 8 &&
+              offsetof(DistLoss, grad_dist) == 16 && offsetof(DistLoss, partials) == 24, "lae_dist_term");
+static_assert(sizeof(CritLoss) == 40 && offsetof(CritLoss, kind) == 0 && offsetof(CritLoss, param) == 4 && offsetof(CritLoss, opac_lambda) == 8 &&
+              offsetof(CritLoss, opac_value_only) == 12 && offsetof(CritLoss, opac) == 16 && offsetof(CritLoss, grad_ws) == 24 &&
+              offsetof(CritLoss, opac_partials) == 32, "lae_crit_term");
+static_assert(sizeof(WeightLoss) == 56 && offsetof(WeightLoss, w_src) == 0 && offsetof(WeightLoss, w_dtype) == 8 && offsetof(WeightLoss, t2_src) == 16 &&
+              offsetof(WeightLoss, t2_dtype) == 24 && offsetof(WeightLoss, t2_channels) == 28 && offsetof(WeightLoss, inds) == 32 &&
+              offsetof(WeightLoss, lambda) == 40 && offsetof(WeightLoss, partials) == 48, "lae_weight_term");
 __device__ __forceinline__ float load_plane(const void* src, int dtype, size_t i) {
     return dtype == LAE_IMG_F16 ? __half2float(((const __half*)src)[i]) : ((const float*)src)[i];
 }
@@ -760,9 +774,9 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
         if constexpr (CRIT) {
             if (cl.kind != LAE_LOSS_MSE) {                                  // uniform over the launch
                 const float g1n = 1.0f / (float)(3u * N);
-                const lae::ElemLoss l0 = lae::colour_elem_loss(cl.kind, cl.delta, e0, sl.target[3 * (size_t)index]),
-                                    l1 = lae::colour_elem_loss(cl.kind, cl.delta, e1, sl.target[3 * (size_t)index + 1]),
-                                    l2 = lae::colour_elem_loss(cl.kind, cl.delta, e2, sl.target[3 * (size_t)index + 2]);
+                const lae::ElemLoss l0 = lae::colour_elem_loss(cl.kind, cl.param, e0, sl.target[3 * (size_t)index]),
+                                    l1 = lae::colour_elem_loss(cl.kind, cl.param, e1, sl.target[3 * (size_t)index + 1]),
+                                    l2 = lae::colour_elem_loss(cl.kind, cl.param, e2, sl.target[3 * (size_t)index + 2]);
                 sq = (l0.v + l1.v) + l2.v;
                 g0 = (l0.dv * g1n) * s; g1 = (l1.dv * g1n) * s; g2 = (l2.dv * g1n) * s;
             }
@@ -771,9 +785,9 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
                 const float oc = fminf(fmaxf(a.ws, 1e-5f), hi);
                 const float la = log2f(oc), lb = log2f(1.0f - oc);
                 oq = -(oc * la + (1.0f - oc) * lb);
-                sq = sq + (3.0f * cl.lambda) * oq;
+                sq = sq + (3.0f * cl.opac_lambda) * oq;
                 const bool inside = a.ws >= 1e-5f && a.ws <= hi;
-                gws_in = cl.value_only || !inside ? 0.0f : ((cl.lambda / (float)N) * (lb - la)) * s;
+                gws_in = cl.opac_value_only || !inside ? 0.0f : ((cl.opac_lambda / (float)N) * (lb - la)) * s;
                 if (lane == 0) { cl.opac[index] = oq; cl.grad_ws[index] = gws_in; }
             }
         }
@@ -852,7 +866,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_composite_train_step(
                 float u = 0.0f;
 #pragma unroll
                 for (int w = 0; w < COMP_WAVES; w++) u += s_oq[w];
-                cl.partials[blockIdx.x] = u;
+                cl.opac_partials[blockIdx.x] = u;
             }
         }
         if constexpr (WGT) {
@@ -997,84 +1011,101 @@ __global__ __launch_bounds__(COMPACT_BLOCK) void k_compact_scatter(const int32_t
     if (v >= 0) out[block_prefix[blockIdx.x] + local_prefix[i]] = v;
 }
 
-// ---------------------------------------------------------------- host side of K7 / K8: one body per pair of C entries
-// lae_composite_rays_train_step[_depth | _dist | _crit | _weighted]: the depth-, dist-, crit- and weight-only arguments are checked first,
-// before the N == 0 return
-template <bool DEPTH, bool DIST = false, bool CRIT = false, bool WGT = false>
+// ---------------------------------------------------------------- host side of K7 / K8: one body per C entry
+// the kernel argument of a term: its struct where the flavour has the term, NoArg where it does not
+template <bool ON, class T>
+std::conditional_t<ON, T, NoArg> term_arg(const T* p) {
+    if constexpr (ON) return *p;
+    else return NoArg{};
+}
+
+// lae_composite_rays_train_step.  A NULL term is absent.  The term-only arguments are checked first (weight, criterion, depth,
+// distortion), before the N == 0 return; then the pointers.
 int composite_train_step_impl(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
-                                     float T_thresh, const Blend& bl, const uint32_t* rows_end, const StepLoss& sl, float* weights_sum,
-                                     float* depth, float* image, float* grad_sigmas, float* grad_rgbs, float* loss_out, int defer_loss,
-                                     const std::conditional_t<DEPTH, DepthLoss, NoArg>& dl, const char* what, void* stream,
-                                     const std::conditional_t<DIST, DistLoss, NoArg>& xl = {},
-                                     const std::conditional_t<CRIT, CritLoss, NoArg>& cl = {},
-                                     const std::conditional_t<WGT, WeightLoss, NoArg>& wl = {}) {
-    if constexpr (WGT) {
-        if (cl.kind != LAE_LOSS_MSE) return LAE_EINVAL;                     // the reference has no weighted L1 / Huber / MAPE
-        if (wl.w_src && wl.w_dtype != LAE_IMG_F16 && wl.w_dtype != LAE_IMG_F32) return LAE_EINVAL;
-        if (wl.t2_src) {
-            if (wl.t2_dtype != LAE_IMG_F16 && wl.t2_dtype != LAE_IMG_F32) return LAE_EINVAL;
-            if (wl.t2_channels != 3 && wl.t2_channels != 4) return LAE_EINVAL;
-            if (!(wl.lambda >= 0.0f) || !(wl.lambda <= 3.0e38f)) return LAE_EINVAL;
+                              float T_thresh, const Blend& bl, const uint32_t* rows_end, const StepLoss& sl, float* weights_sum, float* depth,
+                              float* image, float* grad_sigmas, float* grad_rgbs, float* loss_out, int defer_loss, const DepthLoss* dl,
+                              const DistLoss* xl, const CritLoss* crit, const WeightLoss* wl, void* stream) {
+    // a weight term without a criterion struct is MSE without the entropy term; one without a plane is the CRIT call without WGT
+    const CritLoss mse{LAE_LOSS_MSE, 0.0f, 0.0f, 0, nullptr, nullptr, nullptr};
+    const CritLoss* cl = crit ? crit : wl ? &mse : nullptr;
+    const bool wgt = wl && (wl->w_src || wl->t2_src);
+    if (wgt) {
+        if (cl->kind != LAE_LOSS_MSE) return LAE_EINVAL;                    // the reference has no weighted L1 / Huber / MAPE
+        if (wl->w_src && wl->w_dtype != LAE_IMG_F16 && wl->w_dtype != LAE_IMG_F32) return LAE_EINVAL;
+        if (wl->t2_src) {
+            if (wl->t2_dtype != LAE_IMG_F16 && wl->t2_dtype != LAE_IMG_F32) return LAE_EINVAL;
+            if (wl->t2_channels != 3 && wl->t2_channels != 4) return LAE_EINVAL;
+            if (!(wl->lambda >= 0.0f) || !(wl->lambda <= 3.0e38f)) return LAE_EINVAL;
         }
     }
-    if constexpr (CRIT) {
-        if (!lae::colour_loss_kind_ok(cl.kind, cl.delta)) return LAE_EINVAL;
-        if (cl.opac && (!(cl.lambda >= 0.0f) || !(cl.lambda <= 3.0e38f))) return LAE_EINVAL;
+    if (cl) {
+        if (!lae::colour_loss_kind_ok(cl->kind, cl->param)) return LAE_EINVAL;
+        if (cl->opac && (!(cl->opac_lambda >= 0.0f) || !(cl->opac_lambda <= 3.0e38f))) return LAE_EINVAL;
     }
-    if constexpr (DEPTH) {
-        if (dl.dtype != LAE_IMG_F16 && dl.dtype != LAE_IMG_F32) return LAE_EINVAL;
-        if (!(dl.lambda >= 0.0f) || !(dl.lambda <= 3.0e38f)) return LAE_EINVAL;      // NaN, negative and infinite weights
+    if (dl) {
+        if (dl->dtype != LAE_IMG_F16 && dl->dtype != LAE_IMG_F32) return LAE_EINVAL;
+        if (!(dl->lambda >= 0.0f) || !(dl->lambda <= 3.0e38f)) return LAE_EINVAL;    // NaN, negative and infinite weights
     }
-    if constexpr (DIST) {
-        if (!(xl.lambda >= 0.0f) || !(xl.lambda <= 3.0e38f)) return LAE_EINVAL;
-    }
+    if (xl && (!(xl->lambda >= 0.0f) || !(xl->lambda <= 3.0e38f))) return LAE_EINVAL;
     if (N == 0) return LAE_OK;
     if (!rays || !weights_sum || !depth || !image || !bl.nears || !bl.fars || !bl.depth_out || !bl.image_out || !rows_end || !sl.target ||
         !sl.grad_image || !loss_out || !sl.partials)
         return LAE_ENULL;
-    if constexpr (DEPTH) {
-        if (!dl.src || !dl.grad_depth || !dl.partials) return LAE_ENULL;    // dl.inds may be NULL (src holds one value per ray)
-    }
-    if constexpr (DIST) {
-        if (!xl.dist || !xl.grad_dist || !xl.partials) return LAE_ENULL;
-    }
-    if constexpr (CRIT) {
-        if (cl.opac && (!cl.grad_ws || !cl.partials)) return LAE_ENULL;
-    }
-    if constexpr (WGT) {
-        if (wl.t2_src && !wl.partials) return LAE_ENULL;                    // wl.inds may be NULL (the planes hold one value per ray)
-    }
+    if (dl && (!dl->src || !dl->grad_depth || !dl->partials)) return LAE_ENULL;      // dl->inds may be NULL (src holds one value per ray)
+    if (xl && (!xl->dist || !xl->grad_dist || !xl->partials)) return LAE_ENULL;
+    if (cl && cl->opac && (!cl->grad_ws || !cl->opac_partials)) return LAE_ENULL;
+    if (wgt && wl->t2_src && !wl->partials) return LAE_ENULL;                        // wl->inds may be NULL (the planes hold one value per ray)
     if (M > 0 && (!sigmas || !rgbs || !deltas || !grad_sigmas || !grad_rgbs)) return LAE_ENULL;
     const uint32_t nb = lae::cdiv(N, COMP_WAVES);
-    k_composite_train_step<DEPTH, DIST, CRIT, WGT><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh,
-                                                                                         weights_sum, depth, image, bl, sl, rows_end, grad_sigmas,
-                                                                                         grad_rgbs, dl, xl, cl, wl);
+    auto launch = [&](auto with_depth, auto with_dist, auto with_crit, auto with_wgt) {
+        constexpr bool DEPTH = decltype(with_depth)::value, DIST = decltype(with_dist)::value, CRIT = decltype(with_crit)::value,
+                       WGT = decltype(with_wgt)::value;
+        k_composite_train_step<DEPTH, DIST, CRIT, WGT><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(
+            sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image, bl, sl, rows_end, grad_sigmas, grad_rgbs, term_arg<DEPTH>(dl),
+            term_arg<DIST>(xl), term_arg<CRIT>(cl), term_arg<WGT>(wl));
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    // twelve flavours: depth and distortion on or off, times no criterion struct (the CRIT = false kernels) / CRIT / CRIT with WGT
+    auto colour = [&](auto with_depth, auto with_dist) {
+        if (wgt) launch(with_depth, with_dist, yes, yes);
+        else if (cl) launch(with_depth, with_dist, yes, no);
+        else launch(with_depth, with_dist, no, no);
+    };
+    if (dl) xl ? colour(yes, yes) : colour(yes, no);
+    else xl ? colour(no, yes) : colour(no, no);
     // defer_loss: the one-block sum of the partials (5.5 us + a kernel boundary on the step's critical path for a number that
     // feeds nothing on the device) is left to lae_loss_finish or to a later launch that takes it along
     // (lae_nerf_head_backward); loss_out holds NaN until then
     if (!defer_loss) k_loss_finish<<<1, 1024, 0, STREAM(stream)>>>(sl.partials, nb, 3u * N, sl.scale, loss_out);
-    return lae::check_launch(what);
+    return lae::check_launch("composite_rays_train_step");
 }
 
-template <bool DEPTH, bool DIST = false>
+// lae_composite_rays_train_backward_blend_ex: DEPTH = grad_depth != NULL, DIST = grad_dist != NULL; `depth` is the D of both
 int composite_train_backward_blend_impl(const float* grad_weights_sum, const float* grad_image, const float* sigmas, const float* rgbs,
-                                               const float* deltas, const int32_t* rays, const float* weights_sum, const float* image,
-                                               uint32_t M, uint32_t N, float T_thresh, const Dense& dn, float* grad_sigmas, float* grad_rgbs,
-                                               const std::conditional_t<DEPTH, DepthGrad, NoArg>& dg, const char* what, void* stream,
-                                               const std::conditional_t<DIST, DistGrad, NoArg>& xg = {}) {
+                                        const float* deltas, const int32_t* rays, const float* weights_sum, const float* image, uint32_t M,
+                                        uint32_t N, float T_thresh, const Dense& dn, float* grad_sigmas, float* grad_rgbs,
+                                        const float* grad_depth, const float* depth, const float* grad_dist, const float* dist, void* stream) {
     if (N == 0 || M == 0) return LAE_OK;
     if (!grad_image || !sigmas || !rgbs || !deltas || !rays || !weights_sum || !image || !grad_sigmas || !grad_rgbs || !dn.rows_end)
         return LAE_ENULL;                                   // grad_weights_sum may be NULL (= zero)
-    if constexpr (DEPTH) {
-        if (!dg.grad_depth || !dg.depth) return LAE_ENULL;
-    }
-    if constexpr (DIST) {
-        if (!xg.grad_dist || !xg.dist || !xg.depth) return LAE_ENULL;
-    }
-    k_composite_train_bwd<true, DEPTH, DIST><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
-        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn, dg, xg);
-    return lae::check_launch(what);
+    if ((grad_depth || grad_dist) && !depth) return LAE_ENULL;
+    if (grad_dist && !dist) return LAE_ENULL;
+    const DepthGrad dg{grad_depth, depth};
+    const DistGrad xg{grad_dist, dist, depth};
+    auto launch = [&](auto with_depth, auto with_dist) {
+        constexpr bool DEPTH = decltype(with_depth)::value, DIST = decltype(with_dist)::value;
+        k_composite_train_bwd<true, DEPTH, DIST><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(
+            grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, dn,
+            term_arg<DEPTH>(&dg), term_arg<DIST>(&xg));
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (grad_depth) grad_dist ? launch(yes, yes) : launch(yes, no);
+    else grad_dist ? launch(no, yes) : launch(no, no);
+    return lae::check_launch("composite_rays_train_backward_blend");
 }
+
 
 }  // namespace
 
@@ -1197,28 +1228,19 @@ int lae_composite_rays_train_forward(const float* sigmas, const float* rgbs, con
 int lae_composite_rays_train_forward_blend(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
                                            uint32_t M, uint32_t N, float T_thresh, const float* nears, const float* fars,
                                            const float* bg_rays, float bg_r, float bg_g, float bg_b, float* weights_sum,
-                                           float* depth, float* image, float* depth_out, float* image_out, void* stream) {
+                                           float* depth, float* image, float* depth_out, float* image_out, float* dist, void* stream) {
     if (N == 0) return LAE_OK;
     if (!rays || !weights_sum || !depth || !image || !nears || !fars || !depth_out || !image_out) return LAE_ENULL;
     if (M > 0 && (!sigmas || !rgbs || !deltas)) return LAE_ENULL;
     const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
-    k_composite_train_fwd<true><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N,
-                                                                                              T_thresh, weights_sum, depth, image, bl, NoArg{});
+    const uint32_t nb = lae::cdiv(N, COMP_WAVES);
+    if (dist)
+        k_composite_train_fwd<true, true><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth,
+                                                                                 image, bl, dist);
+    else
+        k_composite_train_fwd<true><<<nb, COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image,
+                                                                           bl, NoArg{});
     return lae::check_launch("composite_rays_train_forward_blend");
-}
-
-int lae_composite_rays_train_forward_blend_dist(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
-                                                uint32_t M, uint32_t N, float T_thresh, const float* nears, const float* fars,
-                                                const float* bg_rays, float bg_r, float bg_g, float bg_b, float* weights_sum,
-                                                float* depth, float* image, float* depth_out, float* image_out, float* dist,
-                                                void* stream) {
-    if (N == 0) return LAE_OK;
-    if (!rays || !weights_sum || !depth || !image || !nears || !fars || !depth_out || !image_out || !dist) return LAE_ENULL;
-    if (M > 0 && (!sigmas || !rgbs || !deltas)) return LAE_ENULL;
-    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
-    k_composite_train_fwd<true, true><<<lae::cdiv(N, COMP_WAVES), COMP_BLOCK, 0, STREAM(stream)>>>(sigmas, rgbs, deltas, rays, M, N,
-                                                                                                    T_thresh, weights_sum, depth, image, bl, dist);
-    return lae::check_launch("composite_rays_train_forward_blend_dist");
 }
 
 int lae_composite_rays_train_step(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
@@ -1226,112 +1248,11 @@ int lae_composite_rays_train_step(const float* sigmas, const float* rgbs, const 
                                   float bg_g, float bg_b, const uint32_t* rows_end, const float* target, const float* scale,
                                   float* weights_sum, float* depth, float* image, float* depth_out, float* image_out,
                                   float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out, float* partials,
-                                  int defer_loss, void* stream) {
-    return composite_train_step_impl<false>(sigmas, rgbs, deltas, rays, M, N, T_thresh, Blend{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out},
-                                            rows_end, StepLoss{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr}, weights_sum, depth,
-                                            image, grad_sigmas, grad_rgbs, loss_out, defer_loss, NoArg{}, "composite_rays_train_step", stream);
-}
-
-int lae_composite_rays_train_step_depth(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
-                                        uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
-                                        float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
-                                        const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
-                                        float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
-                                        float* partials, int defer_loss, const void* depth_src, int depth_dtype,
-                                        const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
-                                        float* depth_partials, void* stream) {
-    return composite_train_step_impl<true>(sigmas, rgbs, deltas, rays, M, N, T_thresh, Blend{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out},
-                                           rows_end, StepLoss{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr}, weights_sum, depth,
-                                           image, grad_sigmas, grad_rgbs, loss_out, defer_loss,
-                                           DepthLoss{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials},
-                                           "composite_rays_train_step_depth", stream);
-}
-
-int lae_composite_rays_train_step_dist(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
-                                       uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
-                                       float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
-                                       const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
-                                       float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
-                                       float* partials, int defer_loss, const void* depth_src, int depth_dtype,
-                                       const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
-                                       float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
-                                       float* dist_partials, void* stream) {
-    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
-    const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
-    const DistLoss xl{dist_lambda, dist_value_only != 0, dist, grad_dist, dist_partials};
-    if (!depth_src)                                       // no depth term: the other depth arguments are not looked at
-        return composite_train_step_impl<false, true>(sigmas, rgbs, deltas, rays, M, N, T_thresh, bl, rows_end, sl, weights_sum, depth, image,
-                                                      grad_sigmas, grad_rgbs, loss_out, defer_loss, NoArg{}, "composite_rays_train_step_dist",
-                                                      stream, xl);
-    return composite_train_step_impl<true, true>(sigmas, rgbs, deltas, rays, M, N, T_thresh, bl, rows_end, sl, weights_sum, depth, image,
-                                                 grad_sigmas, grad_rgbs, loss_out, defer_loss,
-                                                 DepthLoss{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials},
-                                                 "composite_rays_train_step_dist", stream, xl);
-}
-
-int lae_composite_rays_train_step_crit(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
-                                       uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
-                                       float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
-                                       const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
-                                       float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
-                                       float* partials, int defer_loss, const void* depth_src, int depth_dtype,
-                                       const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
-                                       float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
-                                       float* dist_partials, int loss_kind, float loss_param, float opac_lambda, int opac_value_only,
-                                       float* opac, float* grad_ws, float* opac_partials, void* stream) {
-    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
-    const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
-    const DistLoss xl{dist_lambda, dist_value_only != 0, dist, grad_dist, dist_partials};
-    const DepthLoss dl{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials};
-    const CritLoss cl{loss_kind, loss_param, opac_lambda, opac_value_only != 0, opac, grad_ws, opac_partials};
-    const char* what = "composite_rays_train_step_crit";
-    // depth_src == NULL: no depth term; dist == NULL: no distortion term (their other arguments are not looked at)
-    auto run = [&](auto with_depth, auto with_dist, const auto& dla, const auto& xla) {
-        return composite_train_step_impl<decltype(with_depth)::value, decltype(with_dist)::value, true>(
-            sigmas, rgbs, deltas, rays, M, N, T_thresh, bl, rows_end, sl, weights_sum, depth, image, grad_sigmas, grad_rgbs, loss_out,
-            defer_loss, dla, what, stream, xla, cl);
-    };
-    constexpr std::true_type yes{};
-    constexpr std::false_type no{};
-    if (!depth_src) return dist ? run(no, yes, NoArg{}, xl) : run(no, no, NoArg{}, NoArg{});
-    return dist ? run(yes, yes, dl, xl) : run(yes, no, dl, NoArg{});
-}
-
-int lae_composite_rays_train_step_weighted(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
-                                           uint32_t N, float T_thresh, const float* nears, const float* fars, const float* bg_rays,
-                                           float bg_r, float bg_g, float bg_b, const uint32_t* rows_end, const float* target,
-                                           const float* scale, float* weights_sum, float* depth, float* image, float* depth_out,
-                                           float* image_out, float* grad_image, float* grad_sigmas, float* grad_rgbs, float* loss_out,
-                                           float* partials, int defer_loss, const void* depth_src, int depth_dtype,
-                                           const int64_t* depth_inds, float lambda, int depth_value_only, float* grad_depth,
-                                           float* depth_partials, float dist_lambda, int dist_value_only, float* dist, float* grad_dist,
-                                           float* dist_partials, int loss_kind, float loss_param, float opac_lambda, int opac_value_only,
-                                           float* opac, float* grad_ws, float* opac_partials, const void* w_src, int w_dtype,
-                                           const void* t2_src, int t2_dtype, int t2_channels, const int64_t* pix_inds, float t2_lambda,
-                                           float* t2_partials, void* stream) {
-    if (!w_src && !t2_src)                                // neither: the call, the instantiations and the bits of _crit
-        return lae_composite_rays_train_step_crit(sigmas, rgbs, deltas, rays, M, N, T_thresh, nears, fars, bg_rays, bg_r, bg_g, bg_b, rows_end,
-                                                  target, scale, weights_sum, depth, image, depth_out, image_out, grad_image, grad_sigmas,
-                                                  grad_rgbs, loss_out, partials, defer_loss, depth_src, depth_dtype, depth_inds, lambda,
-                                                  depth_value_only, grad_depth, depth_partials, dist_lambda, dist_value_only, dist, grad_dist,
-                                                  dist_partials, loss_kind, loss_param, opac_lambda, opac_value_only, opac, grad_ws,
-                                                  opac_partials, stream);
-    const Blend bl{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out};
-    const StepLoss sl{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr};
-    const DistLoss xl{dist_lambda, dist_value_only != 0, dist, grad_dist, dist_partials};
-    const DepthLoss dl{depth_src, depth_dtype, depth_inds, lambda, depth_value_only != 0, grad_depth, depth_partials};
-    const CritLoss cl{loss_kind, loss_param, opac_lambda, opac_value_only != 0, opac, grad_ws, opac_partials};
-    const WeightLoss wl{w_src, w_dtype, t2_src, t2_dtype, t2_channels, pix_inds, t2_lambda, t2_partials};
-    const char* what = "composite_rays_train_step_weighted";
-    auto run = [&](auto with_depth, auto with_dist, const auto& dla, const auto& xla) {
-        return composite_train_step_impl<decltype(with_depth)::value, decltype(with_dist)::value, true, true>(
-            sigmas, rgbs, deltas, rays, M, N, T_thresh, bl, rows_end, sl, weights_sum, depth, image, grad_sigmas, grad_rgbs, loss_out,
-            defer_loss, dla, what, stream, xla, cl, wl);
-    };
-    constexpr std::true_type yes{};
-    constexpr std::false_type no{};
-    if (!depth_src) return dist ? run(no, yes, NoArg{}, xl) : run(no, no, NoArg{}, NoArg{});
-    return dist ? run(yes, yes, dl, xl) : run(yes, no, dl, NoArg{});
+                                  int defer_loss, const lae_depth_term* depth_term, const lae_dist_term* dist_term,
+                                  const lae_crit_term* crit_term, const lae_weight_term* weight_term, void* stream) {
+    return composite_train_step_impl(sigmas, rgbs, deltas, rays, M, N, T_thresh, Blend{nears, fars, bg_rays, {bg_r, bg_g, bg_b}, image_out, depth_out},
+                                     rows_end, StepLoss{target, scale, grad_image, partials, defer_loss ? loss_out : nullptr}, weights_sum, depth,
+                                     image, grad_sigmas, grad_rgbs, loss_out, defer_loss, depth_term, dist_term, crit_term, weight_term, stream);
 }
 
 int lae_loss_finish(const float* partials, uint32_t n_part, uint32_t n_elem, const float* scale, float* loss_out, void* stream) {
@@ -1346,39 +1267,11 @@ int lae_composite_rays_train_backward_blend_ex(const float* grad_weights_sum, co
                                                const float* weights_sum, const float* image, uint32_t M, uint32_t N,
                                                float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
                                                const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
-                                               float* grad_rgbs, void* stream) {
-    return composite_train_backward_blend_impl<false>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh,
-                                                      Dense{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale}, grad_sigmas, grad_rgbs, NoArg{},
-                                                      "composite_rays_train_backward_blend", stream);
-}
-
-int lae_composite_rays_train_backward_blend_depth(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
-                                                  const float* rgbs, const float* deltas, const int32_t* rays,
-                                                  const float* weights_sum, const float* image, uint32_t M, uint32_t N,
-                                                  float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
-                                                  const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
-                                                  float* grad_rgbs, const float* grad_depth, const float* depth, void* stream) {
-    return composite_train_backward_blend_impl<true>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh,
-                                                     Dense{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale}, grad_sigmas, grad_rgbs,
-                                                     DepthGrad{grad_depth, depth}, "composite_rays_train_backward_blend_depth", stream);
-}
-
-int lae_composite_rays_train_backward_blend_dist(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
-                                                 const float* rgbs, const float* deltas, const int32_t* rays,
-                                                 const float* weights_sum, const float* image, uint32_t M, uint32_t N,
-                                                 float T_thresh, const float* bg_rays, float bg_r, float bg_g, float bg_b,
-                                                 const uint32_t* rows_end, const float* grad_scale, float* grad_sigmas,
-                                                 float* grad_rgbs, const float* grad_depth, const float* depth, const float* grad_dist,
-                                                 const float* dist, void* stream) {
-    const Dense dn{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale};
-    const DistGrad xg{grad_dist, dist, depth};
-    if (!grad_depth)                                      // no depth gradient; `depth` is still read: q_k needs D
-        return composite_train_backward_blend_impl<false, true>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
-                                                                T_thresh, dn, grad_sigmas, grad_rgbs, NoArg{},
-                                                                "composite_rays_train_backward_blend_dist", stream, xg);
-    return composite_train_backward_blend_impl<true, true>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
-                                                           T_thresh, dn, grad_sigmas, grad_rgbs, DepthGrad{grad_depth, depth},
-                                                           "composite_rays_train_backward_blend_dist", stream, xg);
+                                               float* grad_rgbs, const float* grad_depth, const float* depth, const float* grad_dist,
+                                               const float* dist, void* stream) {
+    return composite_train_backward_blend_impl(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh,
+                                               Dense{bg_rays, {bg_r, bg_g, bg_b}, rows_end, grad_scale}, grad_sigmas, grad_rgbs, grad_depth, depth,
+                                               grad_dist, dist, stream);
 }
 
 int lae_composite_rays_train_backward_blend(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
@@ -1389,7 +1282,8 @@ int lae_composite_rays_train_backward_blend(const float* grad_weights_sum, const
     if (N == 0 || M == 0) return LAE_OK;
     if (!grad_weights_sum) return LAE_ENULL;
     return lae_composite_rays_train_backward_blend_ex(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
-                                                      T_thresh, bg_rays, bg_r, bg_g, bg_b, rows_end, nullptr, grad_sigmas, grad_rgbs, stream);
+                                                      T_thresh, bg_rays, bg_r, bg_g, bg_b, rows_end, nullptr, grad_sigmas, grad_rgbs, nullptr, nullptr,
+                                                      nullptr, nullptr, stream);
 }
 
 int lae_composite_rays_train_backward(const float* grad_weights_sum, const float* grad_image, const float* sigmas,

@@ -17,7 +17,7 @@ a is 1 for 3-channel data (the reference reads the blue channel there, a bug tha
 skipped, and images no view points at, keep the background rule.  The training is the existing graph-replayed Trainer with
 `pixel_weights=True, second_weight=style_weight_d, depth_weight=depth_weight_d`: train_step_npr's loss
     mean((w (pred - gt))^2) + style_weight_d * mean(((1 - w / 2) (gt_style - pred))^2) + depth_weight_d * depth term
-inside the fused compositing kernel (`lae_composite_rays_train_step_weighted`), 16 steps per captured graph.
+inside the fused compositing kernel (`lae_composite_rays_train_step` with its weight term), 16 steps per captured graph.
 
 Departures from the reference:
   * the view of a batch is drawn i.i.d. by the resident sampler, not by a shuffled loader over the views;

@@ -233,7 +233,7 @@ class _composite_rays_train_blend(Function):
     image + (1 - weights_sum) * bg_color and clamp(depth - nears, min=0) / (fars - nears).  The backward writes every
     gradient row itself (no zero fills).  `rays` must come from this package's march_rays_train (ray-id order).
     Also returns the RAW depth D = sum_k w_k t_k, differentiable: where it receives a gradient the backward is
-    lae_composite_rays_train_backward_blend_depth, which carries what the reference's backward drops (raymarching.py:273-275)."""
+    lae_composite_rays_train_backward_blend_ex with grad_depth, which carries what the reference's backward drops (raymarching.py:273-275)."""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -312,8 +312,8 @@ def composite_rays_train_blend_depth(sigmas, rgbs, deltas, rays, nears, fars, bg
 
 class _composite_rays_train_blend_dist(Function):
     """_composite_rays_train_blend with one more differentiable output: dist [N], the distortion l_ray of every ray's weights
-    (`lae_composite_rays_train_forward_blend_dist`; formulas in include/laenerf.h).  Where dist receives a gradient the backward
-    is lae_composite_rays_train_backward_blend_dist, otherwise the one _composite_rays_train_blend would have run."""
+    (`lae_composite_rays_train_forward_blend` with dist; formulas in include/laenerf.h).  Where dist receives a gradient the backward
+    is lae_composite_rays_train_backward_blend_ex with grad_dist, otherwise the one _composite_rays_train_blend would have run."""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -425,16 +425,16 @@ class _composite_rays_train_blend_mse(Function):
     the step before).  The sample gradients are therefore computed in forward() for an upstream gradient of 1 and stored;
     backward() returns them -- multiplied by the upstream gradient unless that is known to be ones.
     depth_sup = (_DepthPlane, depth_inds, depth_weight, value_only) adds the depth criterion in the same kernel
-    (`lae_composite_rays_train_step_depth`): loss = MSE + depth_weight * mean(((D - (z - nears)) * (z > 0))^2), z gathered from the
+    (`lae_depth_term`): loss = MSE + depth_weight * mean(((D - (z - nears)) * (z > 0))^2), z gathered from the
     depth plane by the kernel; its outputs are grad_depth (d loss / d D) and depth_partials (the depth partial sums).
     dist_sup = (distort_weight, value_only) adds distort_weight * mean(l_ray), the distortion term
-    (`lae_composite_rays_train_step_dist`, with or without depth_sup); its outputs are l_ray per ray, d loss / d l_ray and its
+    (`lae_dist_term`, with or without depth_sup); its outputs are l_ray per ray, d loss / d l_ray and its
     partial sums.
     crit = (loss_kind, loss_param, None or (opacity_weight, value_only)) chooses the colour criterion and adds the opacity-entropy term
-    (`lae_composite_rays_train_step_crit`, with or without the other two); the term's outputs are the entropy per ray,
+    (`lae_crit_term`, with or without the other two); the term's outputs are the entropy per ray,
     d loss / d weights_sum and the entropy's partial sums.  crit=None is the call as it was.
     weight_sup = (_DepthPlane or None, _DepthPlane or None, pix_inds, second_weight) adds the per-pixel weights and the second colour
-    target (`lae_composite_rays_train_step_weighted`, MSE only); a second target's output is the term's partial sums.
+    target (`lae_weight_term`, MSE only); a second target's output is the term's partial sums.
     weight_sup=None is the call as it was.
     -> (loss, weights_sum, depth, image, [scaled loss, loss]) and then, for each term that is on in TERMS' order, the outputs named
     there (a term that is off has none)."""
@@ -567,7 +567,7 @@ def composite_rays_train_blend_mse(sigmas, rgbs, deltas, rays, nears, fars, targ
     opacity_grad=False: the value only, the sample gradients of the call without the term bit for bit.  `loss.opac` [N] holds h,
     `loss.grad_ws` [N] d loss / d weights_sum, finish_opacity_loss(loss) L_op.
     pixel_weights / second_target (default None: today's call, bit for bit; loss='mse' only): a per-pixel weight w on the colour
-    residual and a second colour target t with its own weight, in the same kernel (`lae_composite_rays_train_step_weighted`), alone,
+    residual and a second colour target t with its own weight, in the same kernel (`lae_weight_term` of the step), alone,
     together, and with every other term: the colour criterion becomes mean((w (image - target))^2) + second_weight *
     mean(((1 - w / 2) (t - image))^2), the reference's train_step_npr (nerf/utils.py:523-526).  Both are float16 / float32 tensors --
     pixel_weights one value per ray, second_target [N, 3 or 4] -- or, with pixel_inds [N] int64 (ResidentImages.sample's `inds`), any
@@ -803,10 +803,10 @@ def composite_depth_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=None,
                           fars=None, samples=False):
     """The training compositing with the depth gradient, restated sample by sample in `dtype` (default float64): the forward
     (k_composite_train_fwd: early stop after the first sample with T_post < T_thresh, that sample included; rays with
-    num_steps == 0 or offset + num_steps > M dropped), optionally the criterion of lae_composite_rays_train_step_depth
+    num_steps == 0 or offset + num_steps > M dropped), optionally the depth term of lae_composite_rays_train_step
     (target [N,3], z [N] already gathered, nears [N], optionally fars [N]: rays with nears >= fars, the sentinel interval of a ray
     that misses the bounding box, are unsupervised; grad_image / grad_depth are then the criterion's) and the backward
-    (lae_composite_rays_train_backward_blend_depth; bg: None = no blend term, [3] or [N,3]).  Everything is indexed as the
+    (lae_composite_rays_train_backward_blend_ex with grad_depth; bg: None = no blend term, [3] or [N,3]).  Everything is indexed as the
     kernels do: per-ray values by rays[n, 0]; n_rays: the length of the per-ray arrays when `rays` holds only some rows of a table.
     -> dict weights_sum, depth (raw D), image [N,3], stop [N] (index of the last sample used, -1 for a ray without samples),
     margin (the smallest |T_post / T_thresh - 1| over the samples used: how far the early stop is from flipping), and with
@@ -888,7 +888,7 @@ def composite_depth_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=None,
 def composite_distort_numpy(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=None, bg=None, grad_weights_sum=None, grad_image=None,
                             grad_depth=None, grad_dist=None, target=None, z=None, nears=None, depth_weight=0.0, distort_weight=0.0,
                             scale=1.0, depth_grad=True, distort_grad=True, n_rays=None, fars=None):
-    """composite_depth_numpy with the distortion term of lae_composite_rays_train_*_dist, restated sample by sample in `dtype`
+    """composite_depth_numpy with the distortion term of the lae_composite_rays_train_* entries, restated sample by sample in `dtype`
     (default float64).  Per ray, over the samples the forward uses, lengths in the march's units (m = t, interval = deltas[:,0]):
       dist = l_ray = (1/3) sum_k delta_k w_k^2 + 2 sum_k w_k (t_k W_<k - WT_<k)
       q_k  = dl / dw_k = (2/3) delta_k w_k + 2 (t_k (W_<k - (W - W_k)) + ((D - WT_k) - WT_<k))
@@ -980,7 +980,7 @@ def composite_train_step_numpy(sigmas, rgbs, deltas, rays, target, T_thresh=1e-4
                                depth_weight=0.0, distort_weight=0.0, scale=1.0, depth_grad=True, distort_grad=True, n_rays=None,
                                loss="mse", huber_delta=0.1, opacity_weight=None, opacity_grad=True, pixel_weights=None, second_target=None,
                                second_weight=0.0):
-    """lae_composite_rays_train_step_crit / _weighted restated in `dtype` (default float64): the forward, the colour criterion `loss`,
+    """lae_composite_rays_train_step with its criterion and weight terms restated in `dtype` (default float64): the forward, the colour criterion `loss`,
     the depth term (with z), the distortion term and the opacity entropy, then the backward with the criterion's gradients
       grad_image = ((dv * (1 / (3 N))) * scale)  (mse: (e * (2 / (3 N))) * scale),   grad_ws = ((opacity_weight / N) * dh) * scale.
     pixel_weights [N] (the gathered weights w) and second_target [N, 3 or 4] (the gathered second target s; 4 channels are blended

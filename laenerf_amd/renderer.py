@@ -577,7 +577,7 @@ class NeRFRenderer(nn.Module):
         operator -- losses.colour_loss_scaled on the blended image, the entropy written with torch operators -- where the default
         leaves the criterion to the caller, as before.
         pixel_weights / pixel_inds / second_target / second_weight (with gt and loss='mse' only): the per-pixel weights and the second
-        colour target of the same function (`lae_composite_rays_train_step_weighted`); None leaves the call as it was.  Without
+        colour target of the same function (`lae_weight_term` of the fused step); None leaves the call as it was.  Without
         fused_post_ops the same criterion, mean((w (image - gt))^2) + second_weight * mean(((1 - w / 2) (t - image))^2), is written
         with torch operators.
         grad_x: an fp32 [M,3] buffer the backward overwrites with the loss's gradient with respect to the sample positions (through the
@@ -626,7 +626,7 @@ class NeRFRenderer(nn.Module):
 
     @staticmethod
     def _weighted_unfused(image, gt, scaler, wsup):
-        """the weighted criterion of lae_composite_rays_train_step_weighted written with torch operators"""
+        """the weighted criterion of the fused step (lae_weight_term) written with torch operators"""
         from .losses import loss_scale_of
         from .raymarching.raymarching import check_weight
         plane, inds, second, second_weight, bg = wsup

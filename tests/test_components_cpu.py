@@ -176,8 +176,8 @@ def test_symbols_and_tag(hip_lib):
     for name in NAMES:
         assert re.search(r"LAE_API\s+int\s+" + name + r"\s*\(", hdr), name
         assert hasattr(hip_lib, name) and name in _lib.SIGNATURES
-    assert re.search(r'#define\s+LAE_ABI_TAG\s+"(\w+)"', hdr).group(1) == "abi27"
-    assert _lib.ABI_TAG == b"abi27" and hip_lib.lae_version().split()[-1] == b"abi27"
+    assert re.search(r'#define\s+LAE_ABI_TAG\s+"(\w+)"', hdr).group(1) == "abi28"
+    assert _lib.ABI_TAG == b"abi28" and hip_lib.lae_version().split()[-1] == b"abi28"
     assert "components.hip" in __import__("laenerf_amd.build", fromlist=["SOURCES"]).SOURCES
 
 

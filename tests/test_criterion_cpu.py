@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 from conftest import golden
 from depth_sup_util import T_THRESH, build_case
+from step_args import null_step
 
 KINDS = ("mse", "l1", "huber", "mape")
 DELTA = 0.1
@@ -203,16 +204,14 @@ BAD_DELTAS = [0.0, -0.1, float("inf"), float("nan")]
 
 
 def test_library_entries_refuse_invalid_arguments_before_any_launch(hip_lib):
-    step, colour, emap = hip_lib.lae_composite_rays_train_step_crit, hip_lib.lae_colour_loss_forward, hip_lib.lae_error_map_update_crit
-    head = [None] * 4 + [8, 4, 1e-4, None, None, None, 1.0, 1.0, 1.0] + [None] * 13 + [0]          # the arguments of _step, all NULL
-    mid = [None, 1, None, 0.1, 0, None, None] + [0.1, 0, None, None, None]                          # no depth, no distortion
-    crit = lambda kind=0, delta=0.1, lam=0.1, opac=None: [kind, delta, lam, 0, opac, None, None, None]
-    assert step(*head, *mid, *crit()) == -3                                  # NULL pointers
+    step, colour, emap = hip_lib.lae_composite_rays_train_step, hip_lib.lae_colour_loss_forward, hip_lib.lae_error_map_update_crit
+    crit = lambda kind=0, delta=0.1, lam=0.1, opac=None: (kind, delta, lam, 0, opac, None, None)   # the criterion term; no depth, no distortion
+    assert null_step(step, crit=crit()) == -3                                # NULL pointers
     for kind in (-1, 4):
-        assert step(*head, *mid, *crit(kind=kind)) == -1
+        assert null_step(step, crit=crit(kind=kind)) == -1
     for d in BAD_DELTAS:
-        assert step(*head, *mid, *crit(kind=2, delta=d)) == -1
-        assert step(*head, *mid, *crit(kind=1, delta=d)) == -3               # the parameter is Huber's alone
+        assert null_step(step, crit=crit(kind=2, delta=d)) == -1
+        assert null_step(step, crit=crit(kind=1, delta=d)) == -3             # the parameter is Huber's alone
         assert colour(None, None, 4, 2, d, None, None, None, None) == -3     # NULL comes first there, as in lae_mse_loss_forward
         assert emap(None, 1, 4, 4, None, None, None, None, 4, 2, d, None) == -1
     buf = (torch.zeros(4).data_ptr(),) * 4
@@ -220,11 +219,10 @@ def test_library_entries_refuse_invalid_arguments_before_any_launch(hip_lib):
         assert colour(buf[0], buf[1], 4, 2, d, None, buf[2], buf[3], None) == -1
     assert colour(buf[0], buf[1], 4, 7, 0.1, None, buf[2], buf[3], None) == -1 and colour(buf[0], buf[1], 0, 0, 0.1, None, buf[2], buf[3], None) == -1
     for w in BAD_WEIGHTS:                                                    # the weight counts only with the term (opac != NULL)
-        assert step(*head, *mid, *crit(lam=w, opac=buf[0])) == -1
-        assert step(*head, *mid, *crit(lam=w)) == -3
-    head[5] = 0
-    assert step(*head, *mid, *crit()) == 0                                   # N == 0: nothing to do
-    assert step(*head, *mid, *crit(kind=9)) == -1                            # the kind is checked first
+        assert null_step(step, crit=crit(lam=w, opac=buf[0])) == -1
+        assert null_step(step, crit=crit(lam=w)) == -3
+    assert null_step(step, N=0, crit=crit()) == 0                            # N == 0: nothing to do
+    assert null_step(step, N=0, crit=crit(kind=9)) == -1                     # the kind is checked first
     assert emap(None, 1, 4, 4, None, None, None, None, 0, 3, 0.0, None) == 0 and emap(None, 1, 4, 4, None, None, None, None, 4, 3, 0.0, None) == -3
 
 

@@ -2,8 +2,10 @@
 finite difference of its own forward in fp64, and the precondition on the committed inputs that makes an fp32 / fp64 comparison
 meaningful (no early stop close enough to the threshold to fall on another sample in fp32)."""
 import numpy as np
+import torch
 
 from depth_sup_util import T_THRESH, build_case, build_grads
+from step_args import null_step
 
 
 def _objective(c, rays, sig, rgb, gws, gimg, gD):
@@ -96,14 +98,15 @@ def test_criterion_restatement_matches_its_definition():
 
 
 def test_new_entries_refuse_invalid_arguments_before_any_launch(hip_lib):
-    step, bwd = hip_lib.lae_composite_rays_train_step_depth, hip_lib.lae_composite_rays_train_backward_blend_depth
-    head = [None] * 4 + [8, 4, 1e-4, None, None, None, 1.0, 1.0, 1.0] + [None] * 13 + [0]          # the arguments of _step, all NULL
-    tail = lambda dtype=1, lam=0.1: [None, dtype, None, lam, 0, None, None, None]
-    assert step(*head, *tail()) == -3                                     # NULL pointers
-    assert step(*head, *tail(dtype=0)) == -1                              # uint8 planes are not depth planes
-    assert step(*head, *tail(dtype=7)) == -1
-    assert step(*head, *tail(lam=-1.0)) == -1 and step(*head, *tail(lam=float("nan"))) == -1 and step(*head, *tail(lam=float("inf"))) == -1
-    head[5] = 0
-    assert step(*head, *tail()) == 0                                      # N == 0: nothing to do
-    assert bwd(*([None] * 8), 8, 4, 1e-4, None, 0.0, 0.0, 0.0, *([None] * 7)) == -3
-    assert bwd(*([None] * 8), 0, 4, 1e-4, None, 0.0, 0.0, 0.0, *([None] * 7)) == 0
+    step, bwd = hip_lib.lae_composite_rays_train_step, hip_lib.lae_composite_rays_train_backward_blend_ex
+    term = lambda dtype=1, lam=0.1: (None, dtype, None, lam, 0, None, None)                        # the depth term, its pointers NULL
+    assert null_step(step, depth=term()) == -3                            # NULL pointers
+    assert null_step(step, depth=term(dtype=0)) == -1                     # uint8 planes are not depth planes
+    assert null_step(step, depth=term(dtype=7)) == -1
+    for lam in (-1.0, float("nan"), float("inf")):
+        assert null_step(step, depth=term(lam=lam)) == -1
+    assert null_step(step, N=0, depth=term()) == 0                        # N == 0: nothing to do
+    assert bwd(*([None] * 8), 8, 4, 1e-4, None, 0.0, 0.0, 0.0, *([None] * 9)) == -3
+    assert bwd(*([None] * 8), 0, 4, 1e-4, None, 0.0, 0.0, 0.0, *([None] * 9)) == 0
+    p = torch.zeros(4).data_ptr()                                         # every other pointer given: grad_depth needs depth
+    assert bwd(*([p] * 8), 8, 4, 1e-4, None, 0.0, 0.0, 0.0, p, None, p, p, p, None, None, None, None) == -3

@@ -6,9 +6,11 @@ import types
 
 import numpy as np
 import pytest
+import torch
 
 from conftest import golden
 from depth_sup_util import T_THRESH, build_case
+from step_args import null_step
 
 LAMBDA = 0.25               # the weight of the fused-step tests (test_gpu_distort.py): the term is no rounding-level part of the loss
 
@@ -100,19 +102,19 @@ BAD_WEIGHTS = [-1.0, float("inf"), float("nan")]
 
 
 def test_library_entries_refuse_invalid_arguments_before_any_launch(hip_lib):
-    step, bwd, fwd = (hip_lib.lae_composite_rays_train_step_dist, hip_lib.lae_composite_rays_train_backward_blend_dist,
-                      hip_lib.lae_composite_rays_train_forward_blend_dist)
-    head = [None] * 4 + [8, 4, 1e-4, None, None, None, 1.0, 1.0, 1.0] + [None] * 13 + [0]          # the arguments of _step, all NULL
-    depth = lambda dtype=1, lam=0.1: [None, dtype, None, lam, 0, None, None]
-    tail = lambda lam=0.1: [lam, 0, None, None, None, None]
-    assert step(*head, *depth(), *tail()) == -3                           # NULL pointers
+    step, bwd, fwd = (hip_lib.lae_composite_rays_train_step, hip_lib.lae_composite_rays_train_backward_blend_ex,
+                      hip_lib.lae_composite_rays_train_forward_blend)
+    term = lambda lam=0.1: (lam, 0, None, None, None)                     # the distortion term, its pointers NULL; no depth term
+    assert null_step(step, dist=term()) == -3                             # NULL pointers
     for w in BAD_WEIGHTS:
-        assert step(*head, *depth(), *tail(lam=w)) == -1
-    head[5] = 0
-    assert step(*head, *depth(), *tail()) == 0                            # N == 0: nothing to do
-    assert step(*head, *depth(), *tail(lam=-1.0)) == -1                   # the weight is checked first
+        assert null_step(step, dist=term(lam=w)) == -1
+    assert null_step(step, N=0, dist=term()) == 0                         # N == 0: nothing to do
+    assert null_step(step, N=0, dist=term(lam=-1.0)) == -1                # the weight is checked first
     assert bwd(*([None] * 8), 8, 4, 1e-4, None, 0.0, 0.0, 0.0, *([None] * 9)) == -3
     assert bwd(*([None] * 8), 0, 4, 1e-4, None, 0.0, 0.0, 0.0, *([None] * 9)) == 0
+    p = torch.zeros(4).data_ptr()                                         # every other pointer given: grad_dist needs depth and dist
+    assert bwd(*([p] * 8), 8, 4, 1e-4, None, 0.0, 0.0, 0.0, p, None, p, p, None, None, p, p, None) == -3
+    assert bwd(*([p] * 8), 8, 4, 1e-4, None, 0.0, 0.0, 0.0, p, None, p, p, None, p, p, None, None) == -3
     assert fwd(*([None] * 4), 8, 4, 1e-4, None, None, None, 0.0, 0.0, 0.0, *([None] * 7)) == -3
     assert fwd(*([None] * 4), 8, 0, 1e-4, None, None, None, 0.0, 0.0, 0.0, *([None] * 7)) == 0
 

@@ -1,5 +1,5 @@
 """The colour criteria (mse / l1 / huber / mape) and the opacity-entropy term of the fused training step: the CRIT flavour of
-k_composite_train_step through lae_composite_rays_train_step_crit, its two small siblings (lae_colour_loss_forward,
+k_composite_train_step through lae_composite_rays_train_step with its criterion term, its two small siblings (lae_colour_loss_forward,
 lae_error_map_update_crit) and the Trainer's loss / opacity_weight.  Kernel cases: the hand-built table of depth_sup_util (passes of 64
 samples, early stops in the first and second pass and at lane 63, an empty and a dropped ray, a tail of unowned rows, N no multiple of
 the 4 rays of a workgroup), every output buffer poisoned with NaN.  The fp64 restatements are pinned by test_criterion_cpu.py.
@@ -92,8 +92,8 @@ def _finish(parts, n_elem):
 @pytest.mark.parametrize("with_dist", [False, True])
 @pytest.mark.parametrize("with_depth", [False, True])
 def test_mse_without_the_term_is_the_old_step(case, with_depth, with_dist, scaled, bg_rays):
-    """every output of the new entry (LAE_LOSS_MSE, opac == NULL) against lae_composite_rays_train_step_dist, the distortion weight 0 in
-    the cases without distortion -- and there also with dist == NULL against the entries without DIST"""
+    """every output of the step with the criterion term (LAE_LOSS_MSE, opac == NULL) against the step without it, the distortion weight 0
+    in the cases without distortion -- and there also without the distortion term against the kernels without DIST"""
     c, t = case
     target = _target(c["N"])
     scale = torch.tensor([SCALE], device=DEV) if scaled else None

@@ -52,7 +52,7 @@ def _forward(c, t):
 
 # ---------------------------------------------------------------------------------------------------------------- a
 def test_backward_with_depth_gradient_against_fp64(case, reference):
-    """lae_composite_rays_train_backward_blend_depth against the fp64 restatement.  Bound: the kernel family's own (rtol 1e-4, atol
+    """lae_composite_rays_train_backward_blend_ex with grad_depth against the fp64 restatement.  Bound: the kernel family's own (rtol 1e-4, atol
     3e-5 on grad_sigmas, test_gpu_raymarching.py), atol times max(1, max t) * max(1, max |grad_depth|), the magnitude of the new
     operand.  The fp32 restatement deviates from fp64 by 2.0e-8 on these inputs, far below a quarter of it."""
     from laenerf_amd.backend import raymarching_backend as B

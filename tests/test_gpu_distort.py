@@ -77,7 +77,7 @@ def test_forward_dist_against_fp64_and_the_other_outputs_keep_their_bits(case, r
 # ---------------------------------------------------------------------------------------------------------------- 2
 @pytest.mark.parametrize("with_depth", [False, True])
 def test_backward_with_dist_gradient_against_fp64(case, reference, with_depth):
-    """lae_composite_rays_train_backward_blend_dist against the fp64 restatement.  Bound: the kernel family's own (rtol 1e-4, atol 3e-5
+    """lae_composite_rays_train_backward_blend_ex with grad_dist against the fp64 restatement.  Bound: the kernel family's own (rtol 1e-4, atol 3e-5
     on grad_sigmas), atol times max(1, max |q_k|) * max(1, max |grad_dist|), the magnitude of the new operand (q in the colour's
     place; max |q_k| from the fp64 reference), and times the depth test's factor when the depth gradient is on as well."""
     from laenerf_amd.backend import raymarching_backend as B

@@ -1,5 +1,5 @@
 """Per-pixel weights and a second colour target in the fused training step: the WGT flavour of k_composite_train_step through
-lae_composite_rays_train_step_weighted.  Cases: N in {1, 5, 67} (below, across and no multiple of the 4 rays of a workgroup); rays of
+lae_composite_rays_train_step and its weight term.  Cases: N in {1, 5, 67} (below, across and no multiple of the 4 rays of a workgroup); rays of
 0, 1, 63, 64, 65 and 130 samples (the passes of 64) and one that stops early on T_thresh; planes gathered through duplicated pix_inds
 or, with pix_inds = NULL, by the ray; a tail of rows no ray owns; every output buffer poisoned with NaN.  The float64 restatement is
 pinned by test_weighted_step_cpu.py.
@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from gpu_util import DEV, N as NP, T
+from step_args import term_refs
 from test_weighted_step_cpu import check_weighted_einval
 
 pytestmark = pytest.mark.gpu
@@ -79,8 +80,8 @@ def _dt(t):
 
 
 def step(c, t, terms=(), w=None, t2=None, inds=None, lam=LAMBDA_2, entry="weighted", target=None, check=True):
-    """one call of lae_composite_rays_train_step_weighted (or _crit) through the binding table, every output poisoned -> the outputs;
-    check=False leaves out the host reads (for a capture)"""
+    """one call of lae_composite_rays_train_step through the binding table, always with the criterion term (MSE) and, unless
+    entry="crit", with the weight term; every output poisoned -> the outputs; check=False leaves out the host reads (for a capture)"""
     from laenerf_amd import _lib
     p = _lib.ptr
     M, n = c["M"], c["N"]
@@ -90,30 +91,24 @@ def step(c, t, terms=(), w=None, t2=None, inds=None, lam=LAMBDA_2, entry="weight
     args = [p(t["sigmas"]), p(t["rgbs"]), p(t["deltas"]), p(t["rays"]), M, n, T_THRESH, p(t["nears"]), p(t["fars"]),
             p(t["bg_rays"]) if "bg_rays" in terms else None, 1.0, 1.0, 1.0, p(t["rows_end"]), p(target), p(t["scale"]) if "scale" in terms else None,
             p(o["ws"]), p(o["dp"]), p(o["im"]), p(o["do"]), p(o["io"]), p(o["gi"]), p(o["gs"]), p(o["gc"]), p(o["loss"]), p(o["part"]), 0]
+    depth = dist = weight = None
     if "depth" in terms:
         o["gd"], o["dpart"] = _nan(n), _nan(nb)
-        args += [p(t["z"]), F32, None, LAMBDA_DEPTH, 0, p(o["gd"]), p(o["dpart"])]
-    else:
-        args += [None, 0, None, 0.0, 0, None, None]
+        depth = (p(t["z"]), F32, None, LAMBDA_DEPTH, 0, p(o["gd"]), p(o["dpart"]))
     if "dist" in terms:
         o["ds"], o["gx"], o["xpart"] = _nan(n), _nan(n), _nan(nb)
-        args += [LAMBDA_DIST, 0, p(o["ds"]), p(o["gx"]), p(o["xpart"])]
-    else:
-        args += [0.0, 0, None, None, None]
+        dist = (LAMBDA_DIST, 0, p(o["ds"]), p(o["gx"]), p(o["xpart"]))
     if "opac" in terms:
         o["op"], o["gw"], o["opart"] = _nan(n), _nan(n), _nan(nb)
-        args += [0, 0.1, LAMBDA_OPAC, 0, p(o["op"]), p(o["gw"]), p(o["opart"])]
+        crit = (0, 0.1, LAMBDA_OPAC, 0, p(o["op"]), p(o["gw"]), p(o["opart"]))
     else:
-        args += [0, 0.1, 0.0, 0, None, None, None]
-    lib = _lib.load()
-    if entry == "crit":
-        rc = lib.lae_composite_rays_train_step_crit(*args, _lib.stream())
-    else:
+        crit = (0, 0.1, 0.0, 0, None, None, None)
+    if entry != "crit":                                            # "crit": no weight term
         if t2 is not None:
             o["tpart"] = _nan(nb)
-        args += [p(w), 0 if w is None else _dt(w), p(t2), 0 if t2 is None else _dt(t2), 0 if t2 is None else int(t2.shape[-1]), p(inds),
-                 lam, p(o.get("tpart"))]
-        rc = lib.lae_composite_rays_train_step_weighted(*args, _lib.stream())
+        weight = (p(w), 0 if w is None else _dt(w), p(t2), 0 if t2 is None else _dt(t2), 0 if t2 is None else int(t2.shape[-1]), p(inds),
+                  lam, p(o.get("tpart")))
+    rc = _lib.load().lae_composite_rays_train_step(*args, *term_refs(depth, dist, crit, weight), _lib.stream())
     assert rc == 0, rc
     for k, v in o.items():
         assert not check or torch.isfinite(v).all(), k             # every output row is written
@@ -223,7 +218,7 @@ def test_against_the_fp64_restatement(cases, N, channels):
 @pytest.mark.parametrize("N", [5, 67])
 def test_weight_zero_removes_the_colour_exactly(cases, N):
     """rays whose weight is 0: grad_image is exactly 0 there, and their sample gradients are those of the other terms alone -- the
-    _crit call whose target at those rays is the ray's own blended pixel (e == 0 exactly), depth and entropy on"""
+    call without the weight term whose target at those rays is the ray's own blended pixel (e == 0 exactly), depth and entropy on"""
     c, t = cases[N]
     terms = ("depth", "opac", "scale", "bg_rays")
     w = t["w"].clone()
@@ -273,7 +268,7 @@ def test_two_calls_and_a_captured_replay_give_the_same_bits(cases):
 # ---------------------------------------------------------------------------------------------------------------- 4 arguments
 def test_every_einval_case():
     from laenerf_amd import _lib
-    check_weighted_einval(_lib.load().lae_composite_rays_train_step_weighted)
+    check_weighted_einval(_lib.load().lae_composite_rays_train_step)
 
 
 def test_backend_wrapper_and_operator(cases):

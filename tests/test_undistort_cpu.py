@@ -235,7 +235,7 @@ def test_package_exports_and_binding():
         assert getattr(laenerf_amd, name) is getattr(laenerf_amd.undistort, name) and name in laenerf_amd.__all__
     assert laenerf_amd.tsdf_numpy is laenerf_amd.tsdf.tsdf_numpy
     assert all(n in _lib.SIGNATURES for n in ("lae_undistort_map", "lae_distort_map", "lae_remap")) and "undistort.hip" in build.SOURCES
-    assert _lib.ABI_TAG == b"abi27"
+    assert _lib.ABI_TAG == b"abi28"
     with pytest.raises(AttributeError):
         laenerf_amd.no_such_thing
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+from step_args import null_step
 from test_criterion_cpu import _cpu_trainer
 
 T_THRESH = 1e-4
@@ -129,53 +130,63 @@ def test_loss_against_the_references_three_lines():
 BAD_WEIGHTS = [-1.0, float("inf"), float("nan")]
 
 
-def weighted_null_args(kind=0, w=None, w_dtype=2, t2=None, t2_dtype=2, channels=3, lam=0.5, t2_part=None, N=4):
-    """the arguments of lae_composite_rays_train_step_weighted with every pointer NULL but the ones given"""
-    head = [None] * 4 + [8, N, 1e-4, None, None, None, 1.0, 1.0, 1.0] + [None] * 13 + [0]
-    mid = [None, 1, None, 0.1, 0, None, None] + [0.1, 0, None, None, None]
-    crit = [kind, 0.1, 0.1, 0, None, None, None]
-    return head + mid + crit + [w, w_dtype, t2, t2_dtype, channels, None, lam, t2_part, None]
-
-
 def check_weighted_einval(step):
-    """every LAE_EINVAL case of the entry, before any launch (and before the NULL checks: -3 is what a valid call on NULL buffers gives)"""
+    """every LAE_EINVAL case of the weight term, before any launch (and before the NULL checks: -3 is what a valid call on NULL buffers
+    gives): the criterion term with the entropy off and the weight term with every pointer NULL but the ones given"""
+    def rc(kind=0, w=None, w_dtype=2, t2=None, t2_dtype=2, channels=3, lam=0.5, t2_part=None, N=4, with_crit=True):
+        return null_step(step, N=N, crit=(kind, 0.1, 0.1, 0, None, None, None) if with_crit else None,
+                         weight=(w, w_dtype, t2, t2_dtype, channels, None, lam, t2_part))
     buf = torch.zeros(16)
     p = buf.data_ptr()
-    assert step(*weighted_null_args()) == -3                                         # neither: _crit's own answer on NULL pointers
-    assert step(*weighted_null_args(w=p)) == -3 and step(*weighted_null_args(t2=p, t2_part=p)) == -3
+    assert rc() == -3                                                                # neither plane: the criterion term's own answer on NULL pointers
+    assert rc(w=p) == -3 and rc(t2=p, t2_part=p) == -3
     for kind in (1, 2, 3):                                                           # weights or a second target with another criterion
-        assert step(*weighted_null_args(kind=kind, w=p)) == -1
-        assert step(*weighted_null_args(kind=kind, t2=p, t2_part=p)) == -1
-        assert step(*weighted_null_args(kind=kind)) == -3                            # ... which alone is fine
+        assert rc(kind=kind, w=p) == -1
+        assert rc(kind=kind, t2=p, t2_part=p) == -1
+        assert rc(kind=kind) == -3                                                   # ... which alone is fine
     for lam in BAD_WEIGHTS:
-        assert step(*weighted_null_args(t2=p, t2_part=p, lam=lam)) == -1
-        assert step(*weighted_null_args(w=p, lam=lam)) == -3                         # the weight counts only with the second target
+        assert rc(t2=p, t2_part=p, lam=lam) == -1
+        assert rc(w=p, lam=lam) == -3                                                # the weight counts only with the second target
     for ch in (0, 1, 2, 5):
-        assert step(*weighted_null_args(t2=p, t2_part=p, channels=ch)) == -1
+        assert rc(t2=p, t2_part=p, channels=ch) == -1
     for dt in (0, 3, -1):                                                            # uint8 and unknown codes
-        assert step(*weighted_null_args(w=p, w_dtype=dt)) == -1
-        assert step(*weighted_null_args(t2=p, t2_part=p, t2_dtype=dt)) == -1
-        assert step(*weighted_null_args(t2=p, t2_part=p, w_dtype=dt)) == -3          # not looked at without the plane
-    assert step(*weighted_null_args(t2=p, t2_part=p, lam=-1.0, N=0)) == -1           # checked before the N == 0 return
-    assert step(*weighted_null_args(w=p, N=0)) == 0
+        assert rc(w=p, w_dtype=dt) == -1
+        assert rc(t2=p, t2_part=p, t2_dtype=dt) == -1
+        assert rc(t2=p, t2_part=p, w_dtype=dt) == -3                                 # not looked at without the plane
+    assert rc(t2=p, t2_part=p, lam=-1.0, N=0) == -1                                  # checked before the N == 0 return
+    assert rc(w=p, N=0) == 0
+    # without a criterion term the weight term means MSE: the same answers
+    assert rc(w=p, with_crit=False) == -3 and rc(w=p, w_dtype=0, with_crit=False) == -1 and rc(w=p, N=0, with_crit=False) == 0
+    assert rc(t2=p, t2_part=p, channels=5, with_crit=False) == -1
 
 
 def test_library_entry_refuses_invalid_arguments_before_any_launch(hip_lib):
-    check_weighted_einval(hip_lib.lae_composite_rays_train_step_weighted)
+    check_weighted_einval(hip_lib.lae_composite_rays_train_step)
 
 
 def test_symbols_in_header_and_binding(hip_lib):
     from laenerf_amd import _lib
     src = open(os.path.join(ROOT, "include", "laenerf.h")).read()
-    crit = _lib.SIGNATURES["lae_composite_rays_train_step_crit"]
-    for name, n_args in (("lae_composite_rays_train_step_weighted", len(crit) + 8), ("lae_ref_distill_init", 11),
-                         ("lae_ref_distill_scatter", 21)):
+    # the step: its 27 base arguments, the four terms, the stream
+    for name, n_args in (("lae_composite_rays_train_step", 27 + 4 + 1), ("lae_composite_rays_train_backward_blend_ex", 24),
+                         ("lae_composite_rays_train_forward_blend", 20), ("lae_ref_distill_init", 11), ("lae_ref_distill_scatter", 21)):
         m = re.search(r"LAE_API\s+int\s+" + name + r"\s*\(([^;]*)\);", src)
         assert m, name
         assert len(m.group(1).split(",")) == n_args == len(_lib.SIGNATURES[name]), name
         assert hasattr(hip_lib, name)
-    weighted = _lib.SIGNATURES["lae_composite_rays_train_step_weighted"]
-    assert weighted[:len(crit) - 1] == crit[:-1]                                     # every argument of _crit, then the new ones
+    step = re.search(r"LAE_API\s+int\s+lae_composite_rays_train_step\s*\(([^;]*)\);", src).group(1).split(",")
+    assert [re.sub(r"\s+", " ", a).strip().rsplit(" ", 1)[0] for a in step[-5:-1]] == [f"const {n}*" for n in _lib.TERM_STRUCTS]
+    assert _lib.SIGNATURES["lae_composite_rays_train_step"][-5:] == [_lib.vp] * 5
+    # the four term structs: the header's fields, names in order and C types, are the binding's
+    assert list(_lib.TERM_STRUCTS) == ["lae_depth_term", "lae_dist_term", "lae_crit_term", "lae_weight_term"]
+    ctype = lambda c: _lib.vp if c.endswith("*") else {"int": _lib.i32, "float": _lib.f32}[c]
+    for name, cls in _lib.TERM_STRUCTS.items():
+        m = re.search(r"typedef\s+struct\s+" + name + r"\s*\{([^}]*)\}\s*" + name + r"\s*;", src)
+        assert m, name
+        decls = [re.sub(r"\s+", " ", d).strip() for d in m.group(1).split(";") if d.strip()]
+        fields = [(d.rsplit(" ", 1)[1], ctype(d.rsplit(" ", 1)[0])) for d in decls]
+        assert fields == list(cls._fields_), name
+        assert len(fields) == {"lae_depth_term": 7, "lae_dist_term": 5, "lae_crit_term": 7, "lae_weight_term": 8}[name]
 
 
 def _data(**kw):
