@@ -75,7 +75,7 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: the depth term of the compositing step and of its backward; abi17: the distortion term of the compositing forward, backward and step; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: the colour criteria and the opacity entropy of the compositing step, lae_colour_loss_forward, lae_error_map_update_crit; abi23: pixel weights and a second target in the compositing step, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors, lae_undistort_map, lae_distort_map, lae_remap, lae_atlas_layout, lae_atlas_texels, lae_atlas_fuse_views, lae_atlas_pack -- a binding that needs them also checks that the library exports them; abi28: one lae_composite_rays_train_step whose loss terms are structs (lae_depth_term, lae_dist_term, lae_crit_term, lae_weight_term) in place of five cumulative entries, grad_depth / depth / grad_dist / dist on lae_composite_rays_train_backward_blend_ex and dist on lae_composite_rays_train_forward_blend in place of their _depth / _dist entries).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: the depth term of the compositing step and of its backward; abi17: the distortion term of the compositing forward, backward and step; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: the colour criteria and the opacity entropy of the compositing step, lae_colour_loss_forward, lae_error_map_update_crit; abi23: pixel weights and a second target in the compositing step, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors, lae_undistort_map, lae_distort_map, lae_remap, lae_atlas_layout, lae_atlas_texels, lae_atlas_fuse_views, lae_atlas_pack -- a binding that needs them also checks that the library exports them; abi28: one lae_composite_rays_train_step whose loss terms are structs (lae_depth_term, lae_dist_term, lae_crit_term, lae_weight_term) in place of five cumulative entries, grad_depth / depth / grad_dist / dist on lae_composite_rays_train_backward_blend_ex and dist on lae_composite_rays_train_forward_blend in place of their _depth / _dist entries; added under abi28 without touching an existing prototype: lae_simplify_keys, lae_simplify_pairs, lae_simplify_reduce, lae_simplify_first, lae_simplify_compact -- a binding that needs them also checks that the library exports them).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
 #define LAE_ABI_TAG "abi28"
@@ -1198,6 +1198,61 @@ LAE_API int lae_atlas_fuse_views(const float* packed, const float* poses, uint32
                                  uint32_t n_texels, float trunc, float min_cos, float* rgb, uint16_t* counts, uint32_t* n_grey,
                                  void* stream);
 LAE_API int lae_atlas_pack(const float* rgb, const int32_t* owner, uint32_t T, uint32_t cell, uint8_t* image, void* stream);
+
+/* ---- mesh simplification: quadric vertex clustering (csrc/simplify.hip; simplify.py restates the
+ * kernels in numpy and does the ordering between them).  The reference has no counterpart ----
+ * Inputs: verts fp32 [V,3] in any frame, tris int32 [T,3], cell fp32 > 0, origin fp32 (ox, oy, oz), dims (nx, ny, nz) with
+ *   nx ny nz < 4e18, optional colors fp32 [V,C] with C <= 4.
+ * 1. lae_simplify_keys: the cluster of a vertex.  ijk = floor(((double)p - (double)origin) / (double)cell) per axis,
+ *    keys[v] = (i ny + j) nz + k as int64.  A vertex that is not finite, below the origin or outside dims gets key -1 and ORs
+ *    LAE_SIMPLIFY_BAD_VERTEX into *flag (device int32, zeroed by the caller).
+ * 2. Output vertex ids (the caller's): an output vertex is the rank of its key among the non-empty clusters in ascending key
+ *    order; vertex_map int32 [V] maps input to output vertices.  The caller sorts the keys stably (vorder int64 [V]: the input
+ *    vertex at each sorted position, vkeys_sorted int64 [V]) and gives the segment starts vstart int64 [V_out + 1].
+ * 3. lae_simplify_pairs: per triangle its up-to-three (cluster, triangle) pairs -- pair_cluster int32 [3T], slot 3 t + corner:
+ *    the corner's cluster, or V_out where an earlier corner of t named that cluster already (and for a triangle with an index
+ *    outside [0, V), which ORs LAE_SIMPLIFY_BAD_INDEX into *flag) -- survives uint8 [T] (1 iff the three clusters differ), and
+ *    with tri_key != NULL the dedup key int64 [T]: the sorted triple packed lo << 42 | mid << 21 | hi, INT64_MAX for a triangle
+ *    that does not survive (V_out <= LAE_SIMPLIFY_DEDUP_MAX, else LAE_EINVAL).  The caller sorts the slots stably by cluster
+ *    (porder int64 [3T]: slot per sorted position; pstart int64 [V_out + 1]), so a cluster's triangles are in ascending order.
+ * 4. lae_simplify_reduce: per cluster, all in fp64 and relative to the cell centre c = origin + (ijk + 0.5) cell.  Over the
+ *    member vertices: count, mean position m, colour mean.  Over every triangle with at least one corner in the cluster, once
+ *    per cluster: n = (p1 - p0) x (p2 - p0) (squared-area weighting, no division), A += n n^T, b += -(n . p0) n, N += n.
+ *    Triangles that will be dropped contribute; a degenerate one contributes zero by itself.
+ *    lambda = reg trace(A) / 3 + 1e-18 cell^4; (A + lambda I) x = lambda m - b (SPD 3 x 3, condition <= 1 + 3 / reg); x clamped
+ *    per axis to [-cell / 2, cell / 2]; pos[c] = (float)(centre + x).  No branch: with no or only degenerate faces x = m.
+ *    LAE_SIMPLIFY_MEAN skips the solve (x = m).  normals (optional) = N / |N| rounded to fp32, zero where N is zero: they point
+ *    where the faces' right-hand normals point (lae_mesh_vertex_attrs' convention).  colors_out (optional) = the member mean.
+ *    lanes: 1, 16 or 64 adjacent lanes share a cluster (0: LAE_SIMPLIFY_LANES in the environment, else 16 where (V + T) / V_out
+ *    >= LAE_SIMPLIFY_WIDE_ITEMS and 1 below: the measured crossover); each lane sums every lanes-th item of the sorted segments
+ *    and the partial sums meet in a fixed butterfly, so the bytes depend on `lanes` and on nothing else.
+ * 5. lae_simplify_first (dedup): sorted_keys, order = the stable sort of tri_key -> keep uint8 [T]: 1 for the lowest input
+ *    index of every vertex set among the survivors, 0 elsewhere.  Without dedup keep = survives.
+ * 6. lae_simplify_compact: keep_incl int64 [T] = the inclusive running count of keep; out int32 [T_out, 3]: the kept triangles
+ *    in ascending input order, corner order kept, corners through vertex_map.
+ * Output vertices no triangle references stay (vertex_map is total).  Vertex clustering does not preserve manifoldness.
+ * No floating-point atomics anywhere: every sum has one owner and a fixed order, two calls give the same bytes.
+ * NULL pointers (colors, normals, colors_out, tri_key excepted): LAE_ENULL; cell <= 0 or not finite, a non-finite origin, a zero
+ *   dim, reg <= 0, C > 4, an unknown placement or lanes, V_out > V, T_out > T: LAE_EINVAL; both before any launch.  V, T, V_out or
+ *   T_out == 0: LAE_OK, nothing launched. */
+#define LAE_SIMPLIFY_BAD_VERTEX 1
+#define LAE_SIMPLIFY_BAD_INDEX 2
+#define LAE_SIMPLIFY_QUADRIC 0
+#define LAE_SIMPLIFY_MEAN 1
+#define LAE_SIMPLIFY_DEDUP_MAX (1u << 21)
+#define LAE_SIMPLIFY_WIDE_ITEMS 48
+LAE_API int lae_simplify_keys(const float* verts, uint32_t V, float ox, float oy, float oz, float cell, uint32_t nx, uint32_t ny,
+                              uint32_t nz, int64_t* keys, int32_t* flag, void* stream);
+LAE_API int lae_simplify_pairs(const int32_t* tris, uint32_t T, const int32_t* vertex_map, uint32_t V, uint32_t V_out,
+                               int32_t* pair_cluster, uint8_t* survives, int64_t* tri_key, int32_t* flag, void* stream);
+LAE_API int lae_simplify_reduce(const float* verts, uint32_t V, const float* colors, uint32_t C, const int32_t* tris, uint32_t T,
+                                const int64_t* vorder, const int64_t* vkeys_sorted, const int64_t* vstart, const int64_t* porder,
+                                const int64_t* pstart, uint32_t V_out, float ox, float oy, float oz, float cell, uint32_t nx,
+                                uint32_t ny, uint32_t nz, double reg, int placement, int lanes, float* pos, float* normals,
+                                float* colors_out, void* stream);
+LAE_API int lae_simplify_first(const int64_t* sorted_keys, const int64_t* order, uint32_t T, uint8_t* keep, void* stream);
+LAE_API int lae_simplify_compact(const int32_t* tris, uint32_t T, const int32_t* vertex_map, const uint8_t* keep,
+                                 const int64_t* keep_incl, uint32_t T_out, int32_t* out, void* stream);
 
 /* ---- undistortion at the door: resample lens-distorted captures into one pinhole camera, and back (csrc/undistort.hip;
  * DESIGN.md section 4g; undistort.py restates the three kernels in numpy).  The reference's scripts/colmap2nerf.py writes

@@ -178,6 +178,12 @@ SIGNATURES = {
     "lae_atlas_texels": [vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp],
     "lae_atlas_fuse_views": [vp, vp, u32, f32, f32, f32, f32, u32, u32, vp, vp, vp, vp, u32, f32, f32, vp, vp, vp, vp],
     "lae_atlas_pack": [vp, vp, u32, u32, vp, vp],
+    "lae_simplify_keys": [vp, u32, f32, f32, f32, f32, u32, u32, u32, vp, vp, vp],
+    "lae_simplify_pairs": [vp, u32, vp, u32, u32, vp, vp, vp, vp, vp],
+    "lae_simplify_reduce": [vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, u32, f32, f32, f32, f32, u32, u32, u32, f64, i32, i32, vp, vp,
+                            vp, vp],
+    "lae_simplify_first": [vp, vp, u32, vp, vp],
+    "lae_simplify_compact": [vp, u32, vp, vp, vp, u32, vp, vp],
     "lae_undistort_map": [vp, u32, f32, f32, f32, f32, u32, u32, vp, vp],
     "lae_distort_map": [vp, u32, u32, u32, f32, f32, f32, f32, u32, vp, vp, vp],
     "lae_remap": [vp, i32, u32, u32, u32, u32, vp, vp, u32, u32, u32, i32, vp, vp, vp],

@@ -890,12 +890,13 @@ class Trainer:
     def save_mesh(self, path, resolution=256, threshold=10, normals=False, colors=False, keep_largest=False, min_component=None,
                   min_component_fraction=None, **kwargs):
         """nerf/utils.py:722-741: the renderer's mesh as a binary PLY; normals / colors add per-vertex attributes; keep_largest /
-        min_component / min_component_fraction drop floaters (connected components of the density lattice) before marching cubes"""
+        min_component / min_component_fraction drop floaters (connected components of the density lattice) before marching cubes;
+        simplify=<cell in lattice spacings> (a keyword of NeRFRenderer.save_mesh) simplifies the mesh on the device"""
         if keep_largest or min_component is not None or min_component_fraction is not None:
             kwargs.update(keep_largest=keep_largest, min_component=min_component, min_component_fraction=min_component_fraction)
         if not normals and not colors:
             return self.r.save_mesh(path, resolution=resolution, threshold=threshold,
-                                    **{k: v for k, v in kwargs.items() if k in ("keep_largest", "min_component", "min_component_fraction")})
+                                    **{k: v for k, v in kwargs.items() if k in ("keep_largest", "min_component", "min_component_fraction", "simplify")})
         return self.r.save_mesh(path, resolution=resolution, threshold=threshold, normals=normals, colors=colors, **kwargs)
 
     def save_mesh_tsdf(self, path, data=None, frames=None, **kwargs):
