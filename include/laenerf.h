@@ -1127,6 +1127,43 @@ LAE_API int lae_mask_lift(const float* packed, const float* poses, uint32_t V, f
                           uint32_t W, const uint8_t* density_bitfield, uint32_t C, uint32_t G, float bound, float depth_margin,
                           uint32_t min_views, float min_share, uint8_t* grid_out, uint16_t* votes_out, void* stream);
 
+/* ---- region transform: move, rotate, scale, copy or delete the selected region at render time (csrc/region.hip, where the rule
+ * is written down in full; editing/region_transform.py restates both entries in numpy).  The reference has
+ * no counterpart ----
+ * The object-to-world map is x_new = s R (x - pivot) + pivot + t; the host passes (HOST pointers, read during the call) the forward
+ * map M [3,4], its inverse Minv [3,4] and Rt = R^T [3,3], each formed in float64 and rounded once to fp32, rows [m0 m1 m2 | m3].
+ * Grid: H a power of two in [4, 128], C = 1 or 2 (more cascades are refused: one thread walks a source cell's box at every finer
+ *   cascade, unmeasured beyond 2), bound = 2^(C-1); bitfields [C*H^3/8] uint8 in density_bitfield's layout.
+ * sel(q) = the selection bit of q's cell at q's OWN cascade: level = cascade_of(max |q_i|, C), coordinates
+ * (int)clamp((0.5 * fma(q_i, 1 / mip_bound, 1)) * H, 0, H - 1) -- the marcher's probe with dt left out.
+ * lae_region_warp: one sample row per thread, SoA loads and stores, no atomics, no host read, no allocation: capturable.  xyzs, dirs
+ *   [M,3] fp32; outputs xyzs_out, dirs_out [M,3], sigma_scale [M] fp32; xyzs_out / dirs_out may be xyzs / dirs (in place).  Per row,
+ *   p = Minv (x, 1) as ((m0 x + m1 y) + m2 z) + m3, one rounding per operation, never contracted:
+ *     moved    mode != DELETE, |p_i| <= bound for all i, sel(p) set:  xyz = p, dir = Rt d ((r0 dx + r1 dy) + r2 dz), sigma_scale = inv_scale
+ *     vacated  else, mode != COPY and sel(x) set:                      row unchanged, sigma_scale = 0
+ *     kept     otherwise:                                              row unchanged, sigma_scale = 1
+ *   The caller multiplies the field's density by sigma_scale before compositing.  Rows of zeros (the marcher's padding) pass through
+ *   with a finite result.  inv_scale = fp32(1 / s), s in [0.5, 2].
+ * lae_region_occupancy: the bitfield the marcher walks, a conservative superset of where the edited scene has density.
+ *   keep   out = occ; in modes MOVE and DELETE a bit is cleared iff its selection bit is set and the cell is of its own cascade
+ *          (cascade 0, or at c > 0 not all three coordinates in [H/4, 3H/4)).  No other bit is cleared.
+ *   image  (MOVE, COPY) every selected, occupied source cell (own-cascade cells and, at c > 0, the layer with a coordinate equal to
+ *          H/4, which a coordinate of exactly -2^(c-1) looks up) maps its 8 corners with M, takes their axis-aligned box, widens
+ *          it by `margin` (0 <= margin < 0.5 / H: a rounding allowance, region_transform.py derives it) and sets the bit of every
+ *          cell the box overlaps at every cascade, clipped to the cascade's domain; cell ranges by sel's coordinate statement.
+ *   Bits are set with 32-bit atomicOr: the same bytes from every call.  out must not be occ or sel; every byte of out is written.
+ * Both: a NULL pointer (M may be NULL with DELETE), a mode outside the three, inv_scale outside [0.5, 2], a grid the rules above
+ *   or `bytes` do not fit, a non-finite matrix entry, a margin out of range, a base that is not 4-byte aligned, out aliasing an
+ *   input: LAE_EINVAL before any launch (NULL included: this pair reports it as an invalid argument).  M == 0 rows: LAE_OK. */
+#define LAE_REGION_MOVE 0
+#define LAE_REGION_COPY 1
+#define LAE_REGION_DELETE 2
+LAE_API int lae_region_warp(const float* xyzs, const float* dirs, uint32_t M, const uint8_t* sel, uint64_t sel_bytes, const float* Minv,
+                            const float* Rt, float inv_scale, int mode, float bound, uint32_t C, uint32_t H, float* xyzs_out,
+                            float* dirs_out, float* sigma_scale, void* stream);
+LAE_API int lae_region_occupancy(const uint8_t* occ, const uint8_t* sel, uint64_t bytes, const float* M, float margin, int mode,
+                                 float bound, uint32_t C, uint32_t H, uint8_t* out, void* stream);
+
 /* ---- TSDF mesh export: fuse rendered depth and colour views on a lattice (csrc/tsdf.hip, where the rule is written down in
  * full; tsdf.py restates both kernels in numpy).  The reference has no counterpart ----
  * lae_tsdf_fuse: V packed views [V,H,W] (the plane lae_mask_lift_pack writes: t_surf = |packed|, the sign bit ignored, +inf = a

@@ -172,6 +172,8 @@ SIGNATURES = {
     "lae_min_dist_to_points": [vp, u32, vp, u32, f32, vp, vp, vp, vp],
     "lae_mask_lift_pack": [vp, vp, vp, u32, f32, vp, vp],
     "lae_mask_lift": [vp, vp, u32, f32, f32, f32, f32, u32, u32, vp, u32, u32, f32, f32, u32, f32, vp, vp, vp],
+    "lae_region_warp": [vp, vp, u32, vp, u64, vp, vp, f32, i32, f32, u32, u32, vp, vp, vp, vp],
+    "lae_region_occupancy": [vp, vp, u64, vp, f32, i32, f32, u32, u32, vp, vp],
     "lae_tsdf_fuse": [vp, vp, u32, f32, f32, f32, f32, u32, u32, vp, vp, vp, u32, u32, u32, vp, f32, u32, vp, vp, vp, vp],
     "lae_tsdf_vertex_colors": [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp],
     "lae_atlas_layout": [u32, u32, vp, vp, vp],

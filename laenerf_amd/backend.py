@@ -1314,6 +1314,32 @@ class _Undistort:
 
 undistort_backend = _Undistort
 
+
+class _Region:
+    """the region transform (include/laenerf.h lae_region_warp / lae_region_occupancy; csrc/region.hip).  Matrices: contiguous
+    float32 numpy arrays on the HOST (read during the call); every tensor on the device, contiguous, allocated by the caller
+    (editing/region_transform.py checks the shapes).  bound / C / H describe the grid the bitfields were packed for."""
+    MOVE, COPY, DELETE = 0, 1, 2
+
+    @staticmethod
+    def warp(xyzs, dirs, sel, Minv, Rt, inv_scale, mode, bound, C, H, xyzs_out, dirs_out, sigma_scale):
+        ts = (xyzs, dirs, sel, xyzs_out, dirs_out, sigma_scale)
+        need_cuda(*ts); need_contig(*ts)
+        _need_f32(xyzs, dirs, xyzs_out, dirs_out, sigma_scale)
+        check(_lib.load().lae_region_warp(ptr(xyzs), ptr(dirs), xyzs.shape[0], ptr(sel), sel.numel(), Minv.ctypes.data, Rt.ctypes.data,
+                                          float(inv_scale), int(mode), float(bound), int(C), int(H), ptr(xyzs_out), ptr(dirs_out),
+                                          ptr(sigma_scale), stream()), "region_warp")
+
+    @staticmethod
+    def occupancy(occ, sel, M, margin, mode, bound, C, H, out):
+        ts = (occ, sel, out)
+        need_cuda(*ts); need_contig(*ts)
+        check(_lib.load().lae_region_occupancy(ptr(occ), ptr(sel), occ.numel(), None if M is None else M.ctypes.data, float(margin), int(mode),
+                                               float(bound), int(C), int(H), ptr(out), stream()), "region_occupancy")
+
+
+region_backend = _Region
+
 for _cls in (_RayMarching, _GridEncoder, _SHEncoder, _FFMLP):
     for _k, _v in list(vars(_cls).items()):
         if isinstance(_v, staticmethod) and not _k.startswith("_") and _k not in ("fused_backward_available", "ffmlp_set_mode", "set_backward_mode",

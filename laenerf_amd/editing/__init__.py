@@ -15,3 +15,5 @@ from .semantic_encoder import SemanticEncoder, build_ref_supervision, load_vgg16
 from .ref_stage import (RefEditSet, RefStyleTrainer, pack_ref_arrays, ref_phase, ref_stage_numpy, ref_terms,  # noqa: F401
                         reference_ref_step, reference_ref_terms)
 from .ref_distill import build_ref_distill_data, distill_ref_npr, pack_ref_rows, ref_distill_numpy  # noqa: F401
+from .region_transform import (RegionTransform, bake_region_transform, region_occupancy, region_occupancy_numpy, region_warp,  # noqa: F401
+                               region_warp_numpy, render_transformed, seed_occupancy, transform_views)
