@@ -16,7 +16,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import raymarching
+from . import export, raymarching
 
 
 def sample_pdf(bins, weights, n_samples, det=False):
@@ -112,133 +112,50 @@ class NeRFRenderer(nn.Module):
     def density(self, x):
         return self.model.density(x)
 
-    # ------------------------------------------------------------------ mesh (nerf/utils.py:722-741 save_mesh)
-    @torch.no_grad()
+    # ------------------------------------------------------------------ mesh export (nerf/utils.py:722-741 save_mesh): thin calls into
+    # export.py, whose module docstring describes keep_largest / min_component / min_component_fraction, simplify and what comes back
     def extract_mesh(self, resolution=256, threshold=10, chunk=128, keep_largest=False, min_component=None, min_component_fraction=None,
                      simplify=None):
         """the reference's extract_geometry over aabb_infer: sigma of model.density under fp16 autocast (not multiplied by
         density_scale) on a resolution^3 lattice, marching cubes on the device -> vertices [V,3] float64, triangles [T,3] int32.
-        keep_largest / min_component (lattice points) / min_component_fraction (of the largest): floaters are dropped from the
-        field before marching cubes (mesh.drop_components); the kept surfaces are the unfiltered mesh's, bit for bit.
-        simplify: a cluster cell in multiples of the largest lattice spacing (simplify_grid; simplify.simplify_mesh: quadric vertex
-        clustering on the device) -- the vertices are then the simplified fp32 positions as float64."""
-        from . import mesh
-        if simplify is not None:
-            m = self._mesh_attributes(resolution, threshold, chunk, False, False, 1 << 20, keep_largest, min_component,
-                                      min_component_fraction, simplify=simplify)
-            return m["vertices"].double().cpu().numpy(), m["triangles"].cpu().numpy()
-        sigma = getattr(self.model, "density_sigma", None) or (lambda x: self.model.density(x)["sigma"])
+        The shared options and the return convention: export.py's docstring."""
+        m, v = export.density_mesh(self, resolution=resolution, threshold=threshold, chunk=chunk, host_only=True,
+                                   rule=(keep_largest, min_component, min_component_fraction), grid=export.grid_of(self, resolution, simplify))
+        return export.host_pair(m, v, self, resolution)
 
-        def query(pts):
-            with torch.autocast("cuda", dtype=torch.float16):
-                return sigma(pts)
-
-        return mesh.extract_geometry(self.aabb_infer[:3], self.aabb_infer[3:], resolution, threshold, query, S=chunk,
-                                     keep_largest=keep_largest, min_component=min_component, min_component_fraction=min_component_fraction)
-
-    @torch.no_grad()
     def extract_mesh_attributes(self, resolution=256, threshold=10, chunk=128, normals=True, colors=True, color_chunk=1 << 20,
                                 keep_largest=False, min_component=None, min_component_fraction=None, simplify=None):
         """extract_mesh with everything kept on the device, plus per-vertex attributes (mesh.vertex_attributes): -> a dict of
-        device tensors, `vertices` [V,3] fp32 in the box (the float64 scaling of extract_mesh rounded once to fp32), `triangles`
-        [T,3] int32, and on request `normals` [V,3] fp32 (unit, towards lower density) and `colors` [V,3] fp32 in [0, 1]: the
-        radiance self.model(vertex, -normal) under the sweep's fp16 autocast, queried color_chunk vertices at a time.  Only the
-        box and (V, T) are read back.  keep_largest / min_component / min_component_fraction as in extract_mesh (one more read of
-        16 bytes); normals still come from the unfiltered field, so a kept vertex has the position, normal and colour bits it has
-        without the rule.  simplify (a cell in multiples of the largest lattice spacing; None: nothing changes): the mesh goes
-        through simplify.simplify_mesh on the grid of simplify_grid -- `vertices`, `triangles` and `normals` are its outputs (the
-        normals the area-weighted face normals of each cluster) and `colors` the radiance at the new vertices along -normal."""
-        out = self._mesh_attributes(resolution, threshold, chunk, normals, colors, color_chunk, keep_largest, min_component,
-                                    min_component_fraction, simplify=simplify)
-        out.pop("index_vertices", None)
-        return out
+        device tensors, `vertices`, `triangles`, and on request `normals` [V,3] fp32 (unit, towards lower density) and `colors`
+        [V,3] fp32 in [0, 1]: the radiance self.model(vertex, -normal) under the sweep's fp16 autocast, queried color_chunk
+        vertices at a time.  Only the box and (V, T) are read back (with a component rule one more read of 16 bytes).  With
+        simplify the `colors` are the radiance at the new vertices along -normal.  The shared options: export.py's docstring."""
+        return export.density_mesh(self, resolution=resolution, threshold=threshold, chunk=chunk, normals=normals, colors=colors,
+                                   color_chunk=color_chunk, rule=(keep_largest, min_component, min_component_fraction),
+                                   grid=export.grid_of(self, resolution, simplify))[0]
 
     def simplify_grid(self, resolution, simplify):
-        """the cluster lattice of the exports' `simplify` argument -> (cell, origin fp32 [3], dims): the cell is `simplify` times the
-        largest spacing of the resolution^3 lattice over aabb_infer, the origin the box minimum, dims cover the box"""
-        import numpy as np
-        from . import mesh
-        if not float(simplify) > 0.0:
-            raise ValueError("simplify must be a positive cell size in lattice spacings (or None)")
-        aabb = self.aabb_infer.cpu()
-        bmin, bmax = mesh._bounds32(aabb[:3]), mesh._bounds32(aabb[3:])
-        cell = np.float32(float(simplify) * max(float(a[1] - a[0]) for a in mesh.lattice(bmin, bmax, int(resolution))))
-        dims = tuple(int(n) for n in np.floor((bmax.astype(np.float64) - bmin.astype(np.float64)) / np.float64(cell)) + 2)
-        return float(cell), bmin, dims
-
-    def _simplified(self, m, resolution, simplify, colors=None):
-        """m (a dict with `vertices` and `triangles`) through simplify.simplify_mesh on simplify_grid -> its dict"""
-        from . import simplify as simplify_mod
-        cell, origin, dims = self.simplify_grid(resolution, simplify)
-        return simplify_mod.simplify_mesh(m["vertices"], m["triangles"], cell, origin=origin, dims=dims, colors=colors)
-
-    def _mesh_attributes(self, resolution, threshold, chunk, normals, colors, color_chunk, keep_largest=False, min_component=None,
-                         min_component_fraction=None, simplify=None):
-        """extract_mesh_attributes plus `index_vertices`, the marching-cubes vertices in index space (not with simplify)"""
-        from . import mesh
-        sigma = getattr(self.model, "density_sigma", None) or (lambda x: self.model.density(x)["sigma"])
-
-        def query(pts):
-            with torch.autocast("cuda", dtype=torch.float16):
-                return sigma(pts)
-
-        aabb = self.aabb_infer.cpu()
-        bmin, bmax = aabb[:3], aabb[3:]
-        u = mesh.extract_fields(bmin, bmax, resolution, query, S=chunk, device=self.aabb_infer.device)
-        v, t = mesh.marching_cubes(mesh.drop_components(u, threshold, keep_largest, min_component, min_component_fraction), threshold)
-        if simplify is not None:
-            s = self._simplified({"vertices": mesh.vertex_attributes(u, v, bmin, bmax, want=("pos",))["pos"], "triangles": t}, resolution, simplify)
-            out = {"vertices": s["vertices"], "triangles": s["triangles"]}
-            if normals:
-                out["normals"] = s["normals"]
-            if colors:
-                flat = (s["normals"] == 0).all(1, keepdim=True)               # vertex_attributes' fallback direction
-                dirs = torch.where(flat, torch.tensor([0.0, 0.0, 1.0], device=flat.device), -s["normals"]).contiguous()
-                rgb = torch.empty_like(s["vertices"])
-                for i in range(0, rgb.shape[0], color_chunk):
-                    with torch.autocast("cuda", dtype=torch.float16):
-                        rgb[i:i + color_chunk] = self.model(s["vertices"][i:i + color_chunk], dirs[i:i + color_chunk])[1].float()
-                out["colors"] = rgb
-            return out
-        want = ("pos",) + (("normals",) if normals else ()) + (("dirs",) if colors else ())
-        attrs = mesh.vertex_attributes(u, v, bmin, bmax, want=want)
-        out = {"vertices": attrs["pos"], "triangles": t, "index_vertices": v}
-        if normals:
-            out["normals"] = attrs["normals"]
-        if colors:
-            rgb = torch.empty_like(attrs["pos"])
-            for i in range(0, v.shape[0], color_chunk):
-                with torch.autocast("cuda", dtype=torch.float16):
-                    rgb[i:i + color_chunk] = self.model(attrs["pos"][i:i + color_chunk], attrs["dirs"][i:i + color_chunk])[1].float()
-            out["colors"] = rgb
-        return out
+        """the cluster lattice of the exports' `simplify` argument -> (cell, origin fp32 [3], dims): export.simplify_grid"""
+        return export.simplify_grid(self, resolution, simplify)
 
     def save_mesh(self, path, resolution=256, threshold=10, normals=False, colors=False, color_chunk=1 << 20, keep_largest=False,
                   min_component=None, min_component_fraction=None, simplify=None):
         """extract_mesh written as a binary PLY (the reference exports through trimesh).  normals / colors: per-vertex
         `float nx ny nz` / `uchar red green blue` from extract_mesh_attributes, the file's bodies packed on the device
-        (mesh.pack_ply).  keep_largest / min_component / min_component_fraction: as in extract_mesh, the file without its floaters.
-        -> (vertices [V,3] float64, triangles [T,3] int32) on the host either way.  simplify: as in extract_mesh_attributes; the
-        vertices returned are then the simplified fp32 positions as float64"""
+        (mesh.pack_ply).  -> (vertices [V,3] float64, triangles [T,3] int32) on the host either way.  The shared options:
+        export.py's docstring."""
         from . import mesh
-        rule = dict(keep_largest=keep_largest, min_component=min_component, min_component_fraction=min_component_fraction)
-        if simplify is not None:
-            rule["simplify"] = simplify
-        if not normals and not colors:
-            v, t = self.extract_mesh(resolution, threshold, **rule)
-            mesh.write_ply(path, v, t)
-            return v, t
-        with torch.no_grad():
-            m = self._mesh_attributes(resolution, threshold, 128, normals, colors, color_chunk, **rule)
-        head, vb, fb = mesh.pack_ply(m["vertices"], m["triangles"], normals=m.get("normals"), colors=m.get("colors"))
-        mesh.write_ply_packed(path, head, vb, fb)
-        if simplify is not None:
-            return m["vertices"].double().cpu().numpy(), m["triangles"].cpu().numpy()
-        v = mesh.scale_vertices(m["index_vertices"].cpu().numpy(), self.aabb_infer[:3], self.aabb_infer[3:], resolution)
-        return v, m["triangles"].cpu().numpy()
+        m, v = export.density_mesh(self, resolution=resolution, threshold=threshold, chunk=128, normals=normals, colors=colors,
+                                   color_chunk=color_chunk, host_only=True, rule=(keep_largest, min_component, min_component_fraction),
+                                   grid=export.grid_of(self, resolution, simplify))
+        if normals or colors:
+            export.write_ply(path, m)
+            return export.host_pair(m, v, self, resolution)
+        pair = export.host_pair(m, v, self, resolution)
+        mesh.write_ply(path, *pair)                                            # the attribute-free file: the reference's layout
+        return pair
 
     # ------------------------------------------------------------------ TSDF mesh export (tsdf.py; DESIGN.md section 4h)
-    @torch.no_grad()
     def extract_mesh_tsdf(self, poses, intrinsics, H, W, resolution=256, trunc_voxels=3.0, frames=None, depths=None, opacities=None,
                           min_opacity=0.5, min_views=1, normals=True, colors=True, keep_largest=False, min_component=None,
                           min_component_fraction=None, simplify=None):
@@ -246,75 +163,28 @@ class NeRFRenderer(nn.Module):
         (tsdf.render_packed_views; depths / opacities replace the renders), fused into a truncated signed distance field on a
         resolution^3 lattice over aabb_infer (tsdf.tsdf_fuse, trunc = trunc_voxels x the largest axis spacing), and marching
         cubes runs at zero -- no density threshold to guess.  -> a dict of device tensors like extract_mesh_attributes:
-        `vertices` [V,3] fp32 in the box, `triangles` [T,3] int32, on request `normals` [V,3] fp32 (unit, outward) and `colors`
-        [V,3] fp32 in [0, 1] fused from `frames` ([V, H, W, 3] uint8 or fp32 on the device, in the poses' order: recolor_views(...),
-        tr.test(...)[0], ...; None: the model's own renders of the same views), plus `n_grey`, the number of vertices no view
-        coloured (grey 0.5).  keep_largest / min_component / min_component_fraction: mesh.drop_components on the fused field
-        before marching cubes.  The fill rule leaves what is seen only as occluded solid (tsdf.py's docstring): such blobs are
-        what keep_largest=True is for.  simplify (a cell in multiples of the largest lattice spacing, like trunc_voxels; None: nothing
-        changes): the mesh goes through simplify.simplify_mesh -- the colours are the means of the fused vertex colours over each
-        cluster's members, the normals the clusters' area-weighted face normals; `n_grey` stays the count BEFORE simplification."""
-        out = self._mesh_tsdf(poses, intrinsics, H, W, resolution, trunc_voxels, frames, depths, opacities, min_opacity, min_views,
-                              normals, colors, keep_largest, min_component, min_component_fraction, simplify=simplify)
-        out.pop("index_vertices", None)
-        return out
-
-    def _mesh_tsdf(self, poses, intrinsics, H, W, resolution, trunc_voxels, frames, depths, opacities, min_opacity, min_views, normals,
-                   colors, keep_largest, min_component, min_component_fraction, packed=None, simplify=None):
-        """extract_mesh_tsdf plus `index_vertices`, the marching-cubes vertices in index space.  packed: the views' surface
-        distance planes where the caller has rendered them already (extract_mesh_textured)"""
-        from . import mesh, tsdf
-        resolution = int(resolution)
-        if not float(trunc_voxels) > 0.0:
-            raise ValueError("extract_mesh_tsdf: trunc_voxels must be positive")
-        aabb = self.aabb_infer.cpu()
-        bmin, bmax = aabb[:3], aabb[3:]
-        dev = self.aabb_infer.device
-        poses = poses.reshape(-1, 4, 4).to(dev).float().contiguous()
-        axes = mesh.lattice(bmin, bmax, resolution)
-        trunc = float(trunc_voxels) * max(float(a[1] - a[0]) for a in axes)
-        own = None
-        if packed is not None:
-            pass
-        elif colors and frames is None:
-            packed, own = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity, return_frames=True)
-        else:
-            packed = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity)
-        f = tsdf.tsdf_fuse(packed, poses, intrinsics, H, W, axes, trunc, frames=(own if frames is None else frames) if colors else None,
-                           min_views=min_views)
-        u = f["u"]
-        v, t = mesh.marching_cubes(mesh.drop_components(u, 0.0, keep_largest, min_component, min_component_fraction), 0.0)
-        attrs = mesh.vertex_attributes(u, v, bmin, bmax, want=("pos",) + (("normals",) if normals else ()))
-        out = {"vertices": attrs["pos"], "triangles": t, "index_vertices": v}
-        if normals:
-            out["normals"] = attrs["normals"]
-        if colors:
-            out["colors"], out["n_grey"] = tsdf.tsdf_vertex_colors(f["rgb"], f["counts"], v)
-        if simplify is not None:
-            s = self._simplified(out, resolution, simplify, colors=out.get("colors"))
-            del out["index_vertices"]
-            out.update({k: s[k] for k in ("vertices", "triangles") + (("normals",) if normals else ()) + (("colors",) if colors else ())})
-        return out
+        `vertices`, `triangles`, on request `normals` [V,3] fp32 (unit, outward) and `colors` [V,3] fp32 in [0, 1] fused from
+        `frames` ([V, H, W, 3] uint8 or fp32 on the device, in the poses' order: recolor_views(...), tr.test(...)[0], ...; None:
+        the model's own renders of the same views), plus `n_grey`, the number of vertices no view coloured (grey 0.5).  The
+        component rule works on the fused field: the fill rule leaves what is seen only as occluded solid (tsdf.py's docstring),
+        and such blobs are what keep_largest=True is for.  With simplify the colours are the means of the fused vertex colours
+        over each cluster's members; `n_grey` stays the count BEFORE simplification.  The shared options: export.py's docstring."""
+        return export.tsdf_mesh(self, poses, intrinsics, H, W, resolution=resolution, trunc_voxels=trunc_voxels, frames=frames,
+                                depths=depths, opacities=opacities, min_opacity=min_opacity, min_views=min_views, normals=normals,
+                                colors=colors, rule=(keep_largest, min_component, min_component_fraction), simplify=simplify)[0]
 
     def save_mesh_tsdf(self, path, poses, intrinsics, H, W, resolution=256, trunc_voxels=3.0, frames=None, depths=None, opacities=None,
                        min_opacity=0.5, min_views=1, normals=True, colors=True, keep_largest=False, min_component=None,
                        min_component_fraction=None, simplify=None):
         """extract_mesh_tsdf written as a binary PLY, the file's bodies packed on the device (mesh.pack_ply).  An empty result
-        writes a valid PLY with zero elements.  -> (vertices [V,3] float64, triangles [T,3] int32) on the host, like save_mesh
-        (with simplify: the simplified fp32 positions as float64)"""
-        from . import mesh
-        with torch.no_grad():
-            m = self._mesh_tsdf(poses, intrinsics, H, W, resolution, trunc_voxels, frames, depths, opacities, min_opacity, min_views,
-                                normals, colors, keep_largest, min_component, min_component_fraction, simplify=simplify)
-        head, vb, fb = mesh.pack_ply(m["vertices"], m["triangles"], normals=m.get("normals"), colors=m.get("colors"))
-        mesh.write_ply_packed(path, head, vb, fb)
-        if simplify is not None:
-            return m["vertices"].double().cpu().numpy(), m["triangles"].cpu().numpy()
-        v = mesh.scale_vertices(m["index_vertices"].cpu().numpy(), self.aabb_infer[:3], self.aabb_infer[3:], int(resolution))
-        return v, m["triangles"].cpu().numpy()
+        writes a valid PLY with zero elements.  -> (vertices [V,3] float64, triangles [T,3] int32) on the host, like save_mesh"""
+        m, v = export.tsdf_mesh(self, poses, intrinsics, H, W, resolution=resolution, trunc_voxels=trunc_voxels, frames=frames,
+                                depths=depths, opacities=opacities, min_opacity=min_opacity, min_views=min_views, normals=normals,
+                                colors=colors, rule=(keep_largest, min_component, min_component_fraction), simplify=simplify)
+        export.write_ply(path, m)
+        return export.host_pair(m, v, self, resolution)
 
     # ------------------------------------------------------------------ textured mesh export (atlas.py; DESIGN.md section 4h)
-    @torch.no_grad()
     def extract_mesh_textured(self, resolution=256, threshold=10, cell=8, texture_size=None, source="field", geometry="density",
                               poses=None, intrinsics=None, H=None, W=None, frames=None, trunc_voxels=3.0, min_cos=0.25,
                               fallback="grey", keep_largest=False, min_component=None, min_component_fraction=None, chunk=128,
@@ -332,68 +202,13 @@ class NeRFRenderer(nn.Module):
         (fallback "field").  -> a dict of device tensors: `vertices` [V,3] fp32 in the box, `triangles` [T,3] int32, `normals`
         [V,3] fp32, `uv` [T,3,2] float64 per corner (atlas.atlas_uv), `texture` uint8 [S,S,3] (row 0 on top), `n_grey` int32 [1]
         (texels no view counted for; 0 for source "field"), `texels` (pos, dirs, owner and the fp32 colours rgb, cell-major) and
-        `layout`.  keep_largest / min_component / min_component_fraction: as in extract_mesh.  simplify (a cell in multiples of the
-        largest lattice spacing; None: nothing changes): the geometry goes through simplify.simplify_mesh first and the atlas is laid
-        out over the simplified triangles -- with a fixed texture_size every triangle gets a larger cell."""
-        from . import atlas, mesh, tsdf
-        if source not in ("field", "views") or geometry not in ("density", "tsdf") or fallback not in ("grey", "field"):
-            raise ValueError("extract_mesh_textured: source is 'field' or 'views', geometry 'density' or 'tsdf', fallback 'grey' or 'field'")
-        need_views = source == "views" or geometry == "tsdf"
-        if need_views and (poses is None or intrinsics is None or H is None or W is None):
-            raise ValueError("extract_mesh_textured: source='views' and geometry='tsdf' need poses, intrinsics, H and W")
-        resolution = int(resolution)
-        dev = self.aabb_infer.device
-        rule = dict(keep_largest=keep_largest, min_component=min_component, min_component_fraction=min_component_fraction)
-        packed = own = None
-        if need_views:
-            poses = poses.reshape(-1, 4, 4).to(dev).float().contiguous()
-            if source == "views" and frames is None:
-                packed, own = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity, return_frames=True)
-            else:
-                packed = tsdf.render_packed_views(self, poses, intrinsics, H, W, depths, opacities, min_opacity)
-        if geometry == "tsdf":
-            m = self._mesh_tsdf(poses, intrinsics, H, W, resolution, trunc_voxels, None, depths, opacities, min_opacity, min_views, True,
-                                False, packed=packed, **rule)
-        else:
-            m = self._mesh_attributes(resolution, threshold, chunk, True, False, color_chunk, **rule)
-        if simplify is not None:
-            m = self._simplified(m, resolution, simplify)
-        verts, tris, normals = m["vertices"], m["triangles"], m["normals"]
-        T = tris.shape[0]
-        lay = atlas.atlas_layout(T, cell, texture_size)
-        out = {"vertices": verts, "triangles": tris, "normals": normals, "layout": lay,
-               "uv": torch.from_numpy(atlas.atlas_uv(lay)).to(dev), "n_grey": torch.zeros(1, dtype=torch.int32, device=dev)}
-        if T == 0:
-            out["texture"] = torch.zeros(lay.S, lay.S, 3, dtype=torch.uint8, device=dev)
-            out["texels"] = None
-            return out
-        tx = atlas.atlas_texels(verts, tris, normals, lay.cell)
-
-        def field(pos, dirs):
-            rgb = torch.empty_like(pos)
-            for i in range(0, pos.shape[0], color_chunk):
-                with torch.autocast("cuda", dtype=torch.float16):
-                    rgb[i:i + color_chunk] = self.model(pos[i:i + color_chunk], dirs[i:i + color_chunk])[1].float()
-            return rgb
-
-        if source == "field":
-            rgb = field(tx["pos"], tx["dirs"])
-        else:
-            aabb = self.aabb_infer.cpu()
-            axes = mesh.lattice(aabb[:3], aabb[3:], resolution)
-            trunc = float(trunc_voxels) * max(float(a[1] - a[0]) for a in axes)
-            if not trunc > 0.0:
-                raise ValueError("extract_mesh_textured: trunc_voxels must be positive")
-            f = atlas.atlas_fuse_views(packed, poses, intrinsics, H, W, own if frames is None else frames, tx["pos"], tx["nrm"], tx["owner"],
-                                       trunc, min_cos, counts=fallback == "field")
-            rgb, out["n_grey"] = f["rgb"], f["n_grey"]
-            if fallback == "field":
-                unseen = ((f["counts"].to(torch.int32) == 0) & (tx["owner"] >= 0)).nonzero().reshape(-1)
-                if unseen.numel():
-                    rgb[unseen] = field(tx["pos"][unseen].contiguous(), tx["dirs"][unseen].contiguous())
-        out["texture"] = atlas.atlas_pack(rgb, tx["owner"], lay)
-        out["texels"] = {"pos": tx["pos"], "dirs": tx["dirs"], "owner": tx["owner"], "rgb": rgb}
-        return out
+        `layout`.  With simplify the atlas is laid out over the simplified triangles -- with a fixed texture_size every triangle
+        gets a larger cell.  The shared options: export.py's docstring."""
+        return export.textured_mesh(
+            self, resolution=resolution, threshold=threshold, cell=cell, texture_size=texture_size, source=source, geometry=geometry,
+            poses=poses, intrinsics=intrinsics, H=H, W=W, frames=frames, trunc_voxels=trunc_voxels, min_cos=min_cos, fallback=fallback,
+            rule=(keep_largest, min_component, min_component_fraction), chunk=chunk, color_chunk=color_chunk, depths=depths,
+            opacities=opacities, min_opacity=min_opacity, min_views=min_views, simplify=simplify)
 
     def save_mesh_textured(self, path, **kwargs):
         """extract_mesh_textured(**kwargs) written as `name.obj` + `name.mtl` + `name.png` (atlas.write_obj: per-corner texture
@@ -401,7 +216,7 @@ class NeRFRenderer(nn.Module):
         -> (vertices [V,3] float64, triangles [T,3] int32) on the host, like save_mesh"""
         from . import atlas
         m = self.extract_mesh_textured(**kwargs)
-        v, t = m["vertices"].double().cpu().numpy(), m["triangles"].cpu().numpy()
+        v, t = export.host_pair(m)
         atlas.write_obj(path, v, t, m["uv"].cpu().numpy(), m["texture"].cpu().numpy(), normals=m["normals"].cpu().numpy())
         return v, t
 
