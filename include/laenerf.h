@@ -75,7 +75,7 @@ extern "C" {
 
 /* library identification: returns the static string "laenerf-hip gfx950 " LAE_ABI_TAG.  The tag changes whenever a
  * signature of this header changes incompatibly (abi2: round 2 added pointer arguments in the middle of the optimizer /
- * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: the depth term of the compositing step and of its backward; abi17: the distortion term of the compositing forward, backward and step; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: the colour criteria and the opacity entropy of the compositing step, lae_colour_loss_forward, lae_error_map_update_crit; abi23: pixel weights and a second target in the compositing step, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors, lae_undistort_map, lae_distort_map, lae_remap, lae_atlas_layout, lae_atlas_texels, lae_atlas_fuse_views, lae_atlas_pack -- a binding that needs them also checks that the library exports them; abi28: one lae_composite_rays_train_step whose loss terms are structs (lae_depth_term, lae_dist_term, lae_crit_term, lae_weight_term) in place of five cumulative entries, grad_depth / depth / grad_dist / dist on lae_composite_rays_train_backward_blend_ex and dist on lae_composite_rays_train_forward_blend in place of their _depth / _dist entries; added under abi28 without touching an existing prototype: lae_simplify_keys, lae_simplify_pairs, lae_simplify_reduce, lae_simplify_first, lae_simplify_compact -- a binding that needs them also checks that the library exports them).  A binding compares
+ * grid-backward / frame entry points; abi3: round 3, optimizer state words and the compositing step; abi4: round 4, lae_ffmlp_set_mode values 2 and 16-18 removed; abi5: round 5, lae_render_frame_mode, frame-loop degrade path; abi6: round 6, lae_render_frame_last_status, lae_ffmlp_forward leaves forward_buffer untouched where the backward recomputes; abi7: lae_sample_train_batch, lae_march_rays_train_limit; abi8: lae_sample_train_batch_weighted, lae_error_map_update; abi9: lae_recolor_compact, lae_recolor_compose; abi10: lae_sample_edit_view, lae_style_loss_forward_dev, lae_style_loss_backward_dev; abi11: lae_distill_compose, lae_error_map_seed; abi12: lae_marching_cubes_scratch_bytes, lae_marching_cubes_count, lae_marching_cubes_emit; abi13: lae_style_loss_backward_image_dev, lae_style_image_scratch_bytes, lae_style_image_forward, lae_style_image_backward; abi14: lae_ema_update_gated, lae_eval_view, lae_lpips_head; abi16: the depth term of the compositing step and of its backward; abi17: the distortion term of the compositing forward, backward and step; abi18: lae_mesh_vertex_attrs, lae_mesh_pack_ply; abi19: lae_nnfm_pack, lae_nnfm_match, lae_nnfm_loss_forward, lae_nnfm_loss_backward and their *_bytes helpers; abi20: lae_rayreg_build, lae_rayreg_query, lae_rayreg_supervise and their *_bytes helpers; abi21: lae_style_loss_forward_dev_w, lae_style_loss_backward_image_dev_w, lae_ref_terms_forward, lae_ref_terms_backward, lae_ref_terms_scratch_bytes; abi22: the colour criteria and the opacity entropy of the compositing step, lae_colour_loss_forward, lae_error_map_update_crit; abi23: pixel weights and a second target in the compositing step, lae_ref_distill_init, lae_ref_distill_scatter; abi24: lae_grid_input_grad, lae_pose_ray_grad, lae_pose_step; abi25: lae_sample_train_batch_gain, lae_sample_train_batch_weighted_gain, lae_exposure_step, lae_exposure_publish; abi26: lae_consistency_pair; abi27: lae_components_label, lae_components_sizes, lae_components_filter; added under abi27 without touching an existing prototype: lae_sample_train_batch_patch, lae_lpips_head_grad, lae_patch_pack, lae_patch_unpack_grad, lae_ssim_scratch_doubles, lae_ssim, lae_ssim_patch_forward, lae_ssim_patch_backward, lae_tsdf_fuse, lae_tsdf_vertex_colors, lae_undistort_map, lae_distort_map, lae_remap, lae_atlas_layout, lae_atlas_texels, lae_atlas_fuse_views, lae_atlas_pack -- a binding that needs them also checks that the library exports them; abi28: one lae_composite_rays_train_step whose loss terms are structs (lae_depth_term, lae_dist_term, lae_crit_term, lae_weight_term) in place of five cumulative entries, grad_depth / depth / grad_dist / dist on lae_composite_rays_train_backward_blend_ex and dist on lae_composite_rays_train_forward_blend in place of their _depth / _dist entries; added under abi28 without touching an existing prototype: lae_simplify_keys, lae_simplify_pairs, lae_simplify_reduce, lae_simplify_first, lae_simplify_compact, lae_region_warp, lae_region_occupancy, lae_insert_route_scratch_bytes, lae_insert_route, lae_insert_blend, lae_insert_occupancy -- a binding that needs them also checks that the library exports them).  A binding compares
  * it with the tag it was written against BEFORE the first call: a stale .so used through newer prototypes would misalign
  * arguments silently (laenerf_amd/_lib.py does, and rebuilds or raises). */
 #define LAE_ABI_TAG "abi28"
@@ -1163,6 +1163,58 @@ LAE_API int lae_region_warp(const float* xyzs, const float* dirs, uint32_t M, co
                             float* dirs_out, float* sigma_scale, void* stream);
 LAE_API int lae_region_occupancy(const uint8_t* occ, const uint8_t* sel, uint64_t bytes, const float* M, float margin, int mode,
                                  float bound, uint32_t C, uint32_t H, uint8_t* out, void* stream);
+
+/* ---- scene insert: the selected object of one trained NeRF (the source) rendered inside another scene (the destination)
+ * (csrc/insert.hip; DESIGN.md section 4c "Scene insert"; editing/scene_insert.py restates the three entries in numpy).  The reference
+ * has no counterpart ----
+ * The map is x_dst = s R (x_src - pivot) + position; the host passes (HOST pointers, read during the call) the forward map M [3,4],
+ * its inverse Minv [3,4] and Rt = R^T [3,3], each formed in float64 and rounded once to fp32, rows [m0 m1 m2 | m3].
+ * Grids: the source's (bound_s, C_s, H_s) and the destination's (bound_d, C_d, H_d), each with H a power of two in [4, 128], C = 1 or 2
+ *   and bound = 2^(C-1); they may differ.  Bitfields [C*H^3/8] uint8 in density_bitfield's layout; src_sel (the selection) and src_occ
+ *   (the source's occupancy) are the source grid's.
+ * bit(g, q) = the bit of q's cell at q's OWN cascade in the source bitfield g: level = cascade_of(max |q_i|, C_s), coordinates
+ *   (int)clamp((0.5 * fma(q_i, 1 / mip_bound, 1)) * H_s, 0, H_s - 1) -- the marcher's probe with dt left out.
+ * Every operation below that decides a branch or produces an output is one rounded fp32 operation, never contracted.
+ *
+ * lae_insert_route: xyzs, dirs [M,3] fp32 (the destination marcher's rows), deltas [M,2] fp32 or NULL.  Per row p = Minv (x, 1) as
+ *   ((m0 x + m1 y) + m2 z) + m3 and q = Rt d as (r0 dx + r1 dy) + r2 dz.  The row is INSERTED iff (deltas == NULL or deltas[2i] != 0:
+ *   the marcher's padding rows are skipped) and |p_i| <= bound_s for all i and bit(src_sel, p) and bit(src_occ, p).
+ *   slot [M] int32: an inserted row's rank among the inserted rows in ascending row order, -1 for every other row;
+ *   xyzs_src, dirs_src [M cap, 3] fp32: row slot[i] = (p, q) of inserted row i (rows at and beyond *count are not written);
+ *   *count (DEVICE uint32) = the number of inserted rows.  scratch: lae_insert_route_scratch_bytes(M) bytes of device memory.
+ *   Three launches (a ballot and a prefix inside each workgroup of 1024 rows; one workgroup scans the workgroup counts, 1024 a pass
+ *   with a carry; a scatter): no workgroup waits for another, no atomics, no host read, no allocation -- capturable, and two calls give
+ *   the same bytes.  M == 0: *count = 0, LAE_OK.  M >= 2^31, an output overlapping an input or another output: LAE_EINVAL.
+ * lae_insert_blend: sigma_d [M], rgb_d [M,3] (the destination field's), sigma_s [n_src], rgb_s [n_src,3] (the source field's on the
+ *   compacted rows), each fp16 or fp32 by its own dtype code (LAE_F32 / LAE_F16); slot [M]; outputs sigma [M], rgb [M,3] fp32.
+ *   slot < 0 (or >= n_src: nothing is read outside the arrays): the destination's values.  Otherwise ss = sigma_s[slot] * inv_scale and
+ *     LAE_INSERT_REPLACE  sigma = ss, rgb = rgb_s[slot]                                     (the object is pasted over what stood there)
+ *     LAE_INSERT_ADD      sigma = sigma_d + ss; rgb = sigma > 0 ? rgb_d + (ss / sigma) * (rgb_s - rgb_d) : rgb_d
+ *                                                                              (the exact mixture of two participating media)
+ *   sigma / rgb may BE sigma_d / rgb_d when those are fp32 (in place); any other overlap of an output: LAE_EINVAL.  One row per
+ *   thread, streaming, capturable.  inv_scale = fp32(1 / s), s in [0.5, 2].
+ * lae_insert_occupancy: the bitfield the destination's marcher walks.  out = dst_occ, plus, for every source cell that is selected,
+ *   occupied and of its own cascade (cascade 0; at c > 0 not all three coordinates in (H_s/4, 3H_s/4): the layer with a coordinate
+ *   equal to H_s/4 counts, as in lae_region_occupancy), the image box: the 8 corners mapped with M, their axis-aligned box widened by
+ *   `margin` (0 <= margin < 0.5 / H_d: a rounding allowance, scene_insert.py derives it), and the bit of every destination cell the
+ *   box overlaps at every destination cascade, clipped to the cascade's domain; cell ranges by the destination's coordinate statement.
+ *   No bit is cleared.  Bits are set with 32-bit atomicOr: the same bytes from every call.  out overlaps no input; every byte of out
+ *   is written.
+ * All three: a NULL pointer (arrays of no rows may be NULL), a grid the rules above or the byte counts do not fit, a non-finite matrix
+ *   entry, inv_scale outside [0.5, 2], a mode outside the two, a dtype code outside the two, a margin out of range, a base that is not
+ *   aligned to its element (bitfields: 4 bytes), an overlapping output: LAE_EINVAL before any launch. */
+#define LAE_INSERT_REPLACE 0
+#define LAE_INSERT_ADD 1
+LAE_API uint64_t lae_insert_route_scratch_bytes(uint32_t M);
+LAE_API int lae_insert_route(const float* xyzs, const float* dirs, const float* deltas, uint32_t M, const uint8_t* src_sel,
+                             const uint8_t* src_occ, uint64_t src_bytes, const float* Minv, const float* Rt, float bound_s, uint32_t C_s,
+                             uint32_t H_s, int32_t* slot, float* xyzs_src, float* dirs_src, uint32_t* count, void* scratch, void* stream);
+LAE_API int lae_insert_blend(const void* sigma_d, int sigma_d_dtype, const void* rgb_d, int rgb_d_dtype, const void* sigma_s,
+                             int sigma_s_dtype, const void* rgb_s, int rgb_s_dtype, uint32_t n_src, const int32_t* slot, uint32_t M,
+                             float inv_scale, int mode, float* sigma, float* rgb, void* stream);
+LAE_API int lae_insert_occupancy(const uint8_t* dst_occ, uint64_t dst_bytes, const uint8_t* src_sel, const uint8_t* src_occ,
+                                 uint64_t src_bytes, const float* M, float margin, float bound_s, uint32_t C_s, uint32_t H_s, float bound_d,
+                                 uint32_t C_d, uint32_t H_d, uint8_t* out, void* stream);
 
 /* ---- TSDF mesh export: fuse rendered depth and colour views on a lattice (csrc/tsdf.hip, where the rule is written down in
  * full; tsdf.py restates both kernels in numpy).  The reference has no counterpart ----

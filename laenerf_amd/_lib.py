@@ -174,6 +174,10 @@ SIGNATURES = {
     "lae_mask_lift": [vp, vp, u32, f32, f32, f32, f32, u32, u32, vp, u32, u32, f32, f32, u32, f32, vp, vp, vp],
     "lae_region_warp": [vp, vp, u32, vp, u64, vp, vp, f32, i32, f32, u32, u32, vp, vp, vp, vp],
     "lae_region_occupancy": [vp, vp, u64, vp, f32, i32, f32, u32, u32, vp, vp],
+    "lae_insert_route_scratch_bytes": [u32],
+    "lae_insert_route": [vp, vp, vp, u32, vp, vp, u64, vp, vp, f32, u32, u32, vp, vp, vp, vp, vp, vp],
+    "lae_insert_blend": [vp, i32, vp, i32, vp, i32, vp, i32, u32, vp, u32, f32, i32, vp, vp, vp],
+    "lae_insert_occupancy": [vp, u64, vp, vp, u64, vp, f32, f32, u32, u32, f32, u32, u32, vp, vp],
     "lae_tsdf_fuse": [vp, vp, u32, f32, f32, f32, f32, u32, u32, vp, vp, vp, u32, u32, u32, vp, f32, u32, vp, vp, vp, vp],
     "lae_tsdf_vertex_colors": [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp],
     "lae_atlas_layout": [u32, u32, vp, vp, vp],
@@ -229,6 +233,7 @@ _RESTYPES = {
     "lae_ssim_scratch_doubles": u64,
     "lae_rayreg_query_bytes": u64,
     "lae_recolor_compact_scratch_bytes": u64,
+    "lae_insert_route_scratch_bytes": u64,
     "lae_marching_cubes_scratch_bytes": u64,
     "lae_style_image_scratch_bytes": u64,
     "lae_ref_terms_scratch_bytes": u64,

@@ -1340,6 +1340,48 @@ class _Region:
 
 region_backend = _Region
 
+
+class _Insert:
+    """the scene insert (include/laenerf.h lae_insert_route / lae_insert_blend / lae_insert_occupancy; csrc/insert.hip).  Matrices:
+    contiguous float32 numpy arrays on the HOST (read during the call); every tensor on the device, contiguous, allocated by the
+    caller (editing/scene_insert.py checks the shapes).  src_grid / dst_grid: (bound, C, H) of the grid a bitfield was packed for."""
+    REPLACE, ADD = 0, 1
+
+    @staticmethod
+    def route(xyzs, dirs, deltas, src_sel, src_occ, Minv, Rt, src_grid, slot, xyzs_src, dirs_src, count):
+        ts = (xyzs, dirs, src_sel, src_occ, slot, xyzs_src, dirs_src, count) + (() if deltas is None else (deltas,))
+        need_cuda(*ts); need_contig(*ts)
+        _need_f32(xyzs, dirs, xyzs_src, dirs_src, *(() if deltas is None else (deltas,)))
+        if slot.dtype != torch.int32 or count.dtype != torch.int32:
+            raise RuntimeError("insert_route: slot and count int32 (count < 2^31: its bits are the entry's uint32)")
+        lib, M = _lib.load(), xyzs.shape[0]
+        bound, C, H = src_grid
+        ws = _workspace(xyzs.device, lib.lae_insert_route_scratch_bytes(M))
+        check(lib.lae_insert_route(ptr(xyzs), ptr(dirs), None if deltas is None else ptr(deltas), M, ptr(src_sel), ptr(src_occ),
+                                   src_sel.numel(), Minv.ctypes.data, Rt.ctypes.data, float(bound), int(C), int(H), ptr(slot),
+                                   ptr(xyzs_src), ptr(dirs_src), ptr(count), ptr(ws), stream()), "insert_route")
+
+    @staticmethod
+    def blend(sigma_d, rgb_d, sigma_s, rgb_s, slot, inv_scale, mode, sigma, rgb):
+        ts = (sigma_d, rgb_d, sigma_s, rgb_s, slot, sigma, rgb)
+        need_cuda(*ts); need_contig(*ts)
+        _need_f32(sigma, rgb)
+        check(_lib.load().lae_insert_blend(ptr(sigma_d), _dtype_code(sigma_d), ptr(rgb_d), _dtype_code(rgb_d), ptr(sigma_s),
+                                           _dtype_code(sigma_s), ptr(rgb_s), _dtype_code(rgb_s), sigma_s.shape[0], ptr(slot),
+                                           sigma_d.shape[0], float(inv_scale), int(mode), ptr(sigma), ptr(rgb), stream()), "insert_blend")
+
+    @staticmethod
+    def occupancy(dst_occ, src_sel, src_occ, M, margin, src_grid, dst_grid, out):
+        ts = (dst_occ, src_sel, src_occ, out)
+        need_cuda(*ts); need_contig(*ts)
+        (bs, Cs, Hs), (bd, Cd, Hd) = src_grid, dst_grid
+        check(_lib.load().lae_insert_occupancy(ptr(dst_occ), dst_occ.numel(), ptr(src_sel), ptr(src_occ), src_sel.numel(), M.ctypes.data,
+                                               float(margin), float(bs), int(Cs), int(Hs), float(bd), int(Cd), int(Hd), ptr(out), stream()),
+              "insert_occupancy")
+
+
+insert_backend = _Insert
+
 for _cls in (_RayMarching, _GridEncoder, _SHEncoder, _FFMLP):
     for _k, _v in list(vars(_cls).items()):
         if isinstance(_v, staticmethod) and not _k.startswith("_") and _k not in ("fused_backward_available", "ffmlp_set_mode", "set_backward_mode",

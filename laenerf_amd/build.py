@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "liblaenerf_hip.so")
-SOURCES = ["raymarching.hip", "frame.hip", "gridencoder.hip", "gridbackward.hip", "shencoder.hip", "freqencoder.hip", "ffmlp.hip", "nerfhead.hip", "mlpbackward.hip", "densitygrid.hip", "optimizer.hip", "loss.hip", "palette.hip", "editgrid.hip", "masklift.hip", "region.hip", "tsdf.hip", "atlas.hip", "simplify.hip", "undistort.hip", "batch.hip", "recolor.hip", "style_batch.hip", "style_image.hip", "distill.hip", "mesh.hip", "components.hip", "evaluate.hip", "ssim.hip", "nnfm.hip", "rayreg.hip", "ref_stage.hip", "pose.hip", "exposure.hip", "lae_common.cpp"]
+SOURCES = ["raymarching.hip", "frame.hip", "gridencoder.hip", "gridbackward.hip", "shencoder.hip", "freqencoder.hip", "ffmlp.hip", "nerfhead.hip", "mlpbackward.hip", "densitygrid.hip", "optimizer.hip", "loss.hip", "palette.hip", "editgrid.hip", "masklift.hip", "region.hip", "insert.hip", "tsdf.hip", "atlas.hip", "simplify.hip", "undistort.hip", "batch.hip", "recolor.hip", "style_batch.hip", "style_image.hip", "distill.hip", "mesh.hip", "components.hip", "evaluate.hip", "ssim.hip", "nnfm.hip", "rayreg.hip", "ref_stage.hip", "pose.hip", "exposure.hip", "lae_common.cpp"]
 # -ffp-contract=off: only explicit fmaf() fuses -> bit-identical sample indices/positions vs the oracle
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",

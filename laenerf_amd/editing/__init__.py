@@ -17,3 +17,5 @@ from .ref_stage import (RefEditSet, RefStyleTrainer, pack_ref_arrays, ref_phase,
 from .ref_distill import build_ref_distill_data, distill_ref_npr, pack_ref_rows, ref_distill_numpy  # noqa: F401
 from .region_transform import (RegionTransform, bake_region_transform, region_occupancy, region_occupancy_numpy, region_warp,  # noqa: F401
                                region_warp_numpy, render_transformed, seed_occupancy, transform_views)
+from .scene_insert import (SceneInsert, bake_insert, insert_blend, insert_blend_numpy, insert_occupancy, insert_occupancy_numpy,  # noqa: F401
+                           insert_route, insert_route_numpy, insert_views, render_inserted)
